@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — MaGNet multi-view matching hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N>1: launched by torch.distributed.run)
 
 One STEP = one pass of the hot path (models/MAGNET.py:146-175) over a batch of `--frames`
 reference frames per GPU, starting from backbone outputs already resident in HBM:
@@ -12,10 +12,15 @@ V=4 source views, D=64 candidates, F=64, I=1, bf16-stored features, synthetic te
 Frames shard across ranks with no data-path collective (weak scaling: per-GPU work is fixed);
 the only collective is a one-time RCCL broadcast of G-Net/mask-head weights.
 
-Prints ONE JSON line on rank 0 (fields: see the task contract) including
-  roofline      — fused cost-volume kernel: algorithmic bytes per launch / HIP-event time per launch
+Prints ONE JSON line on rank 0 (fields: see the task contract).  A plain run sets up, warms up, times the K steps and prints the
+headline (`value`, `ms_per_step`); --dump-outputs DIR also writes what the last timed step returned as DIR/<name>.npy.
+--full adds everything else the line carries, each measured in passes of its own after the timed steps:
+  roofline      — fused cost-volume kernel: algorithmic bytes per launch / HIP-event time per launch, live rocprofv3 counters
+  roofline_conv — the 3x3 convolution launches against the matrix-core peak
+  sustained_frames_per_s, ms_per_step_inputs_in_kernel_layouts — the step run on for --sustain-s seconds / without its pack passes
   cpu_baseline  — the CPU oracle (oracle/, a restatement of the reference validated against it)
                   timed on this host's cores on a bounded sample of the same workload (rank 0, N=1)
+  rccl          — at N=1 too: a one-rank process group, the weight broadcast (with the F-Net bucket) and its verification
 """
 from __future__ import annotations
 
@@ -34,6 +39,7 @@ from magnet_amd import dist as mdist  # noqa: E402
 from magnet_amd import synth  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X spec (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy rate
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs stays under 64 MB in all, .npy headers included
 
 
 class _NoBackbone(torch.nn.Module):
@@ -66,6 +72,30 @@ def device_inputs(wl, B, seed, device):
                 nghbr_poses=synth.make_poses(wl.camera, B, V, cpu_gen).to(device),
                 is_valid=torch.ones(B, V, dtype=torch.int32),
                 cam_intrins=synth.make_intrinsics(wl.camera, h, w, B))
+
+
+def dump_outputs(out, dirname, seed=0):
+    """Write what one step returned as dirname/<name>.npy (float32): a list of predictions as pred_<i>, a dict under its keys.  When
+    the whole exceeds DUMP_BUDGET_BYTES every array keeps the same seeded share of itself: whole slices along its first dimension
+    (frames of a prediction) where at least one fits, else single elements.  The sample depends on the shapes and `seed` only, so
+    two runs with the same arguments write the same positions."""
+    import numpy as np
+    arrays = out if isinstance(out, dict) else {f"pred_{i}": t for i, t in enumerate(out)}
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(1, sum(t.numel() * 4 for t in arrays.values())))
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if frac < 1.0:
+            rng = np.random.default_rng(seed)
+            keep = int(t.shape[0] * frac)
+            if keep >= 1:
+                idx = np.sort(rng.choice(t.shape[0], keep, replace=False))
+                t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+            else:
+                idx = np.sort(rng.choice(t.numel(), max(1, int(t.numel() * frac)), replace=False))
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, f"{name}.npy"), t.float().cpu().numpy())
+    return sorted(arrays)
 
 
 def _cpu_model() -> str:
@@ -161,7 +191,7 @@ def _pmc_passes(passes, child_args, kernel_match, timeout_s=90):
     for tag, ctrs in passes.items():
         tmp = tempfile.mkdtemp(prefix="magnet_pmc_", dir="/tmp")
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", *ctrs, "--output-format", "csv", "-d", tmp, "-o", "p", "--",
-               sys.executable, os.path.abspath(__file__), "--no-pmc", "--no-cpu-baseline", "--sustain-s", "0", *child_args]
+               sys.executable, os.path.abspath(__file__), "--full", "--no-pmc", "--no-cpu-baseline", "--sustain-s", "0", *child_args]
         try:
             env = _child_env()
             # own session: on a timeout the whole group (profiler + the python it started) is stopped, not only the profiler
@@ -230,7 +260,7 @@ def live_counters(wl, B, fdt, timeout_s=90, path=0, dev_lib=False):
 def _step_child_args(a, steps, warmup):
     """The parent's own step configuration for a counter child: every flag that changes what a step executes is forwarded, so the
     counters describe the configuration of the line they are attached to; what is dropped are the flags that only add measurements
-    (--no-pmc / --no-cpu-baseline / --sustain-s are set by _pmc_passes) and the launcher's (--gpus).  --no-group: the child skips the
+    (--full / --no-pmc / --no-cpu-baseline / --sustain-s are set by _pmc_passes) and the launcher's (--gpus).  --no-group: the child skips the
     process group (no RCCL initialisation and no weight broadcast inside the profiler's time budget)."""
     args = ["--steps", str(steps), "--warmup", str(warmup), "--workload", a.workload, "--no-group",
             "--path", str(a.path), "--conv-backend", a.conv_backend]
@@ -418,7 +448,7 @@ def main():
                     "channel-last as the matrix-core F-Net writes them, x_d3 in the G-Net input buffer): no pack pass in the step")
     ap.add_argument("--overlap-pack", action="store_true", help="x_d3 repack on a side stream beside the matcher (measured: no gain)")
     ap.add_argument("--sustain-s", type=float, default=6.0, help="extra untimed-by-contract run of this many seconds after the K "
-                    "steps, reported as sustained_frames_per_s (0 = skip)")
+                    "steps, reported as sustained_frames_per_s (--full only; 0 = skip)")
     ap.add_argument("--with-fnet", action="store_true", help="the step starts from the IMAGES: F-Net (matrix-core path, magnet_amd/fnet.py) on the "
                     "1 + V images of every reference frame, then the loop; D-Net outputs stay resident synthetic tensors (torch.hub "
                     "backbone, not buildable offline).  Reported beside the contract line, never instead of it")
@@ -428,7 +458,14 @@ def main():
                     "counter children use); ignored under a launcher (RANK set)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / distributed self-test without a GPU: gloo backend, "
                     "the step is a no-op (used by tests/test_bench_launcher.py)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure roofline / roofline_conv (HIP-event pass, "
+                    "rocprofv3 counter passes), the sustained rate, the packed-input step and the CPU baseline, and at N=1 create the "
+                    "one-rank process group with the verified weight broadcast; a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps write what the last one returned as "
+                    "DIR/<name>.npy (float32; a fixed seeded sample when it exceeds 60 MB)")
     a = ap.parse_args()
+    if a.steps < 1 and not a.dry_run:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, one process per GPU (the reference spawns its
@@ -440,9 +477,10 @@ def main():
         raise SystemExit(3)                                  # launcher self-test (tests/test_bench_launcher.py): this rank dies early
     rccl = {"world": 1, "backend": None, "broadcast_bytes": 0, "broadcast_verified": None}
     try:
-        # always a process group on a GPU — one rank included: RCCL initialisation and the weight broadcast run under the driver's N = 1
-        # clock exactly as they will at N = 8 (train_MaGNet.py:197-210)
-        rank, world, local = mdist.init_from_env(backend="gloo" if a.dry_run else None, always=(a.dry_run or torch.cuda.is_available()) and not a.no_group)
+        # --full: a process group on a GPU — one rank included: RCCL initialisation and the weight broadcast run under the N = 1 clock
+        # exactly as they will at N = 8 (train_MaGNet.py:197-210).  A plain N = 1 run needs no collective for its headline
+        rank, world, local = mdist.init_from_env(backend="gloo" if a.dry_run else None,
+                                                 always=(a.dry_run or (a.full and torch.cuda.is_available())) and not a.no_group)
     except Exception as e:                                   # a one-rank RCCL group that cannot be created must not take the N = 1 line down
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise
@@ -482,7 +520,7 @@ def main():
         model = MAGNET(make_args(wl, iters), d_net=_NoBackbone(), f_net=_NoBackbone(), feat_dtype=fdt,
                        conv_backend=a.conv_backend)
     model_cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         import copy
         model_cpu = copy.deepcopy(model).eval()
     model = model.to(device).eval()
@@ -491,12 +529,12 @@ def main():
     model.fuse_conv_tail = not a.no_fuse_tail
     model.fuse_upsample = not a.no_fuse_upsample
     bcast_bytes = mdist.broadcast_module_(model, src=0)   # the one RCCL collective (weights), xGMI
-    bcast_ok = mdist.broadcast_verified(model, device=device) if bcast_bytes else None
+    bcast_ok = mdist.broadcast_verified(model, device=device) if bcast_bytes and a.full else None
 
-    # north_star: "RCCL-over-xGMI broadcast of shared F-Net weights": the 13.4 MB bucket travels in the default line too (the F-Net itself
+    # north_star: "RCCL-over-xGMI broadcast of shared F-Net weights": the 13.4 MB bucket travels in the --full line too (the F-Net itself
     # runs inside the step only with --with-fnet)
     fnet_bcast_bytes = 0
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and not a.with_fnet and not a.kernel_only:
+    if a.full and torch.distributed.is_available() and torch.distributed.is_initialized() and not a.with_fnet and not a.kernel_only:
         from magnet_amd import fnet as mfnet_b
         fa_b = make_args(wl, iters); fa_b.FNET_architecture = "PSM-Net"
         fnet_b = mfnet_b.FNET(fa_b).to(device).eval()
@@ -523,7 +561,7 @@ def main():
         fa = make_args(wl, iters); fa.FNET_architecture = "PSM-Net"
         model.f_net = mfnet.FNET(fa).to(device).eval()
         fnet_bcast_bytes = mdist.broadcast_module_(model.f_net, src=0)   # the shared F-Net weights (13.4 MB): their own flat bucket(s)
-        if fnet_bcast_bytes:
+        if fnet_bcast_bytes and a.full:
             bcast_ok = bool(bcast_ok) and mdist.broadcast_verified(model.f_net, device=device)
         model.d_net = _ResidentDNet(torch.cat([inp["ref_gmms"], inp["nghbr_gmms"]], dim=0),
                                     inp["x_d3"])          # the forward keeps x_d3[:B] only (MAGNET.py:139)
@@ -536,20 +574,23 @@ def main():
             CostVolumeCW.event_sink = ev_pairs if timed else None
             ConvStackMFMA.event_sink = conv_events if timed else None
             with torch.no_grad():
-                model(ref_img, nb_img, inp["nghbr_poses"], inp["is_valid"], inp["cam_intrins"], mode="test")
+                return model(ref_img, nb_img, inp["nghbr_poses"], inp["is_valid"], inp["cam_intrins"], mode="test")
     elif a.kernel_only:
         matcher = CostVolumeCW(inp["ref_feat"], inp["nghbr_feat"], inp["nghbr_gmms"], inp["nghbr_poses"],
                                inp["is_valid"], inp["cam_intrins"], 5, feat_dtype=fdt, path=a.path)
         if a.nchw_out:
             kw = dict(out=torch.empty(B, wl.D, wl.h, wl.w, device=device))
+            kernel_out = {"cost": kw["out"]}
         else:                                               # the form the step uses: the D cost channels of the G-Net input buffer
             ld = (wl.D + 7) // 8 * 8 + 256
             hi = torch.zeros(B * (wl.h + 2) * (wl.w + 2), ld, dtype=torch.bfloat16, device=device)
             kw = dict(out_split=(hi, torch.zeros_like(hi), ld))
+            kernel_out = {"cost_hi": hi[:, :wl.D], "cost_lo": kw["out_split"][1][:, :wl.D]}
 
         def step(timed):
             CostVolumeCW.event_sink = ev_pairs if timed else None   # HIP events around the fused kernel
             matcher(ref_gmm=inp["ref_gmms"], k_list=k_list, **kw)
+            return kernel_out
     elif a.packed_inputs:
         # what a backbone on the matrix-core path hands over: features in the matcher's layouts (magnet_amd/fnet.py writes
         # exactly these), x_d3 already in the G-Net input buffer.  Packed ONCE, outside the timed region.
@@ -561,16 +602,16 @@ def main():
             CostVolumeCW.event_sink = ev_pairs if timed else None
             ConvStackMFMA.event_sink = conv_events if timed else None
             with torch.no_grad():
-                model.match_and_refine(inp["ref_gmms"], None, None, None, inp["nghbr_gmms"], inp["nghbr_poses"], inp["is_valid"],
-                                       inp["cam_intrins"], mode="test", packed_feats=packed, x_d3_in_place=True)
+                return model.match_and_refine(inp["ref_gmms"], None, None, None, inp["nghbr_gmms"], inp["nghbr_poses"], inp["is_valid"],
+                                              inp["cam_intrins"], mode="test", packed_feats=packed, x_d3_in_place=True)
     else:
         def eager_step(timed):
             CostVolumeCW.event_sink = ev_pairs if timed else None
             ConvStackMFMA.event_sink = conv_events if timed else None
             with torch.no_grad():
-                model.match_and_refine(inp["ref_gmms"], inp["x_d3"], inp["ref_feat"], inp["nghbr_feat"],
-                                       inp["nghbr_gmms"], inp["nghbr_poses"], inp["is_valid"],
-                                       inp["cam_intrins"], mode="test")
+                return model.match_and_refine(inp["ref_gmms"], inp["x_d3"], inp["ref_feat"], inp["nghbr_feat"],
+                                              inp["nghbr_gmms"], inp["nghbr_poses"], inp["is_valid"],
+                                              inp["cam_intrins"], mode="test")
         step = eager_step
         if not a.no_graph and a.conv_backend == "mfma":
             # The step as ONE captured HIP graph (magnet_amd/graph.py): the same launches in the same order on the same resident inputs,
@@ -585,7 +626,7 @@ def main():
                 def step(timed):
                     if timed:
                         return eager_step(True)
-                    graphed(*graphed.static)                # inputs already in place: replay only
+                    return graphed(*graphed.static)         # inputs already in place: replay only; the graph's static outputs
                 graph_state = "replay"
             except Exception as e:                          # noqa: BLE001 — any capture failure: measure the eager step
                 print(f"[bench] HIP-graph capture failed ({type(e).__name__}: {e}); timing the eager step", file=sys.stderr)
@@ -597,24 +638,28 @@ def main():
     torch.cuda.synchronize(); mdist.barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step(False)                                          # the contract's timed region holds the step and nothing else
+        out = step(False)                                    # the contract's timed region holds the step and nothing else
     torch.cuda.synchronize()
     mine = time.perf_counter() - t0                          # this rank's own time for its K steps (before the closing barrier)
     mdist.barrier(); torch.cuda.synchronize()
     elapsed = mdist.max_over_ranks(time.perf_counter() - t0, device=device)
     per_rank = mdist.gather_floats(B * a.steps / max(mine, 1e-9), device=device)   # a straggler GPU shows here, not only in the max
+    if a.dump_outputs and rank == 0:                         # before anything else runs the step (a replay overwrites its outputs)
+        names = dump_outputs(out, a.dump_outputs)
+        print(f"[bench] last timed step's outputs written to {a.dump_outputs}: {', '.join(names)}", file=sys.stderr)
 
     # kernel times (roofline / roofline_conv): the same K steps again, back to back with the timed region, with HIP events on
     # the launch stream around the matcher and the convolution launches (kept out of the contract's clock: ~6 events per step)
-    for _ in range(a.steps):
-        step(True)
-    torch.cuda.synchronize()
-    CostVolumeCW.event_sink = None; ConvStackMFMA.event_sink = None
+    if a.full:
+        for _ in range(a.steps):
+            step(True)
+        torch.cuda.synchronize()
+        CostVolumeCW.event_sink = None; ConvStackMFMA.event_sink = None
 
     # steady state: the contract's K steps take ~0.2 s, before the chip has settled at its sustained clock under continuous
     # matrix-core load; run on for --sustain-s seconds (outside the contract's timed region) and report that rate too
     sustained = None
-    if a.sustain_s > 0:
+    if a.full and a.sustain_s > 0:
         n_sus, t_s = 0, time.perf_counter()
         while True:
             for _ in range(10):
@@ -630,7 +675,7 @@ def main():
     # the same step when the backbones hand their outputs over in the kernels' layouts (what magnet_amd/fnet.py's F-Net does):
     # no pack pass.  Reported next to the contract number, never instead of it.
     packed_ms = None
-    if not (a.kernel_only or a.packed_inputs or a.with_fnet) and a.conv_backend == "mfma":
+    if a.full and not (a.kernel_only or a.packed_inputs or a.with_fnet) and a.conv_backend == "mfma":
         packed = (lib.pack_features(inp["ref_feat"], lib.feat_enum(fdt), pad=0), lib.pack_features(inp["nghbr_feat"], lib.feat_enum(fdt), pad=1))
         gh, gl, ctot, coff = model.gnet_input_buffer(B, wl.h, wl.w, device)
         lib.pack_split(inp["x_d3"], gh, gl, ctot, coff)
@@ -653,7 +698,7 @@ def main():
     # kernel-only child run of this same workload (rank 0, one GPU, production path only; null when the profiler is not
     # available or a pass fails — never a stored number)
     traffic, traffic_src, pmc, binding, conv_binding = None, None, None, None, None
-    if rank == 0 and world == 1 and not a.no_pmc and not a.kernel_only and a.path == 0:
+    if a.full and rank == 0 and world == 1 and not a.no_pmc and not a.kernel_only and a.path == 0:
         traffic, traffic_src, pmc, binding = live_counters(wl, B, fdt, path=a.path, dev_lib=a.dev_lib)
         if a.conv_backend == "mfma" and not a.with_fnet:
             conv_binding = live_conv_counters(a)
@@ -690,18 +735,7 @@ def main():
                         + ("; the step's launches replayed as one captured HIP graph" if graph_state == "replay" else "; launched eagerly from the host")),
                        "launch": graph_state,
                        "parallelism": f"frames sharded over {world} GPU(s), no data-path collective; "
-                                      f"one RCCL weight broadcast ({bcast_bytes} B)"},
-            # `frac` is against the HBM roofline (the contract's target); `bound` says what the counters say binds the kernel
-            "roofline": {"bound": _bound_label(binding, traffic, kern_ms), "contract_roofline": "hbm",
-                         "kernel": "fused sample+warp+score (magnet_cost_volume_cw)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": kern_ms,
-                         "launches_timed": len(ev_pairs)},
-            "cost_volume_frames_per_s": B / (kern_ms * 1e-3) if kern_ms > 0 else None,
-            "sustained_frames_per_s": sustained,
-            "ms_per_step_inputs_in_kernel_layouts": packed_ms,
-            "frames_per_s_inputs_in_kernel_layouts": (world * B / (packed_ms * 1e-3)) if packed_ms else None,
+                                      + (f"one RCCL weight broadcast ({bcast_bytes} B)" if bcast_bytes else "no process group")},
             "weight_broadcast_bytes": bcast_bytes, "fnet_weight_broadcast_bytes": fnet_bcast_bytes,
             "rccl": dict(rccl, world=world, backend=(torch.distributed.get_backend() if torch.distributed.is_available() and torch.distributed.is_initialized() else None),
                          broadcast_bytes=bcast_bytes + fnet_bcast_bytes, broadcast_verified=bcast_ok),
@@ -709,30 +743,44 @@ def main():
             "per_rank_frames_per_s": per_rank,
             "per_rank_min_max": [min(per_rank), max(per_rank)],
         }
-        if pmc:
-            res["roofline"]["sq_counters"] = pmc            # instructions per (pixel, view), wait fraction: measured in this run
-        if binding:
-            res["roofline"]["binding"] = binding
-        if c3:
-            t3 = sum(t for t, _ in c3) / len(c3); f3 = sum(f for _, f in c3) / len(c3)
-            res["roofline_conv"] = {
-                "bound": "mfma", "kernel": "3x3 implicit-GEMM convolution (magnet_conv_mfma, bf16x3 split operands)",
-                "achieved": f3 / (t3 * 1e-3) / 1e12, "peak": 2500.0, "unit": "TFLOP/s",
-                "frac": f3 / (t3 * 1e-3) / 1e12 / 2500.0,
-                "note": "achieved = algorithmic fp32-equivalent flops (2*M*N*K) per launch / HIP-event time; the kernel "
-                        "executes 3 bf16 MFMAs per product term, so matrix-pipe utilisation is 3x this fraction",
-                "algorithmic_flops_per_launch": f3, "avg_launch_ms": t3, "launches_timed": len(c3),
-                "all_conv_layers_ms_per_step": conv_ms_all}
-            if conv_binding:
-                res["roofline_conv"].update(conv_binding)
-        if model_cpu is not None:
-            res["cpu_baseline"] = cpu_baseline(wl, model_cpu, iters)
-        if world > 1:
-            # the contract: counters (roofline.traffic / binding, roofline_conv.mfma_busy) and the CPU baseline are measured on rank 0 of
-            # the N = 1 run only; say so in the N > 1 line instead of leaving the fields silently absent
-            res["roofline"]["traffic_source"] = "N=1 only (live rocprofv3 passes run in the one-GPU launch)"
-            res["counters"] = "N=1 only"
-            res["cpu_baseline"] = "N=1 only"
+        if a.full:
+            res.update({
+                # `frac` is against the HBM roofline (the contract's target); `bound` says what the counters say binds the kernel
+                "roofline": {"bound": _bound_label(binding, traffic, kern_ms), "contract_roofline": "hbm",
+                             "kernel": "fused sample+warp+score (magnet_cost_volume_cw)",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": kern_ms,
+                             "launches_timed": len(ev_pairs)},
+                "cost_volume_frames_per_s": B / (kern_ms * 1e-3) if kern_ms > 0 else None,
+                "sustained_frames_per_s": sustained,
+                "ms_per_step_inputs_in_kernel_layouts": packed_ms,
+                "frames_per_s_inputs_in_kernel_layouts": (world * B / (packed_ms * 1e-3)) if packed_ms else None,
+            })
+            if pmc:
+                res["roofline"]["sq_counters"] = pmc            # instructions per (pixel, view), wait fraction: measured in this run
+            if binding:
+                res["roofline"]["binding"] = binding
+            if c3:
+                t3 = sum(t for t, _ in c3) / len(c3); f3 = sum(f for _, f in c3) / len(c3)
+                res["roofline_conv"] = {
+                    "bound": "mfma", "kernel": "3x3 implicit-GEMM convolution (magnet_conv_mfma, bf16x3 split operands)",
+                    "achieved": f3 / (t3 * 1e-3) / 1e12, "peak": 2500.0, "unit": "TFLOP/s",
+                    "frac": f3 / (t3 * 1e-3) / 1e12 / 2500.0,
+                    "note": "achieved = algorithmic fp32-equivalent flops (2*M*N*K) per launch / HIP-event time; the kernel "
+                            "executes 3 bf16 MFMAs per product term, so matrix-pipe utilisation is 3x this fraction",
+                    "algorithmic_flops_per_launch": f3, "avg_launch_ms": t3, "launches_timed": len(c3),
+                    "all_conv_layers_ms_per_step": conv_ms_all}
+                if conv_binding:
+                    res["roofline_conv"].update(conv_binding)
+            if model_cpu is not None:
+                res["cpu_baseline"] = cpu_baseline(wl, model_cpu, iters)
+            if world > 1:
+                # the contract: counters (roofline.traffic / binding, roofline_conv.mfma_busy) and the CPU baseline are measured on rank 0 of
+                # the N = 1 run only; say so in the N > 1 line instead of leaving the fields silently absent
+                res["roofline"]["traffic_source"] = "N=1 only (live rocprofv3 passes run in the one-GPU launch)"
+                res["counters"] = "N=1 only"
+                res["cpu_baseline"] = "N=1 only"
         _emit_result(res)
     mdist.barrier()
     if torch.distributed.is_available() and torch.distributed.is_initialized():

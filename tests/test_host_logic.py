@@ -138,6 +138,27 @@ def test_roofline_bound_label_follows_the_counters():
     assert bench._bound_label({"valu_busy": 0.5, "ta_busy": 0.9, "wait_frac": 0.2}, None, 1.0).startswith("vector-memory address unit")
 
 
+def test_bench_dump_outputs_stays_in_budget_and_samples_the_same_frames(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per output; over the budget every array keeps the same seeded frames (whole slices along
+    its first dimension), so two runs with the same arguments write the same positions; below the budget everything is written."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("bench_for_test3", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    preds = [torch.arange(64 * 2 * 6 * 8, dtype=torch.float32).reshape(64, 2, 6, 8) + i for i in range(2)]
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 16 * 2 * 6 * 8 * 4)      # room for 16 of the 64 frames of each array
+    assert bench.dump_outputs(preds, str(tmp_path / "a")) == ["pred_0", "pred_1"]
+    bench.dump_outputs(preds, str(tmp_path / "b"))
+    a0, a1, b0 = (np.load(tmp_path / d / f"pred_{i}.npy") for d, i in (("a", 0), ("a", 1), ("b", 0)))
+    assert a0.dtype == np.float32 and a0.shape == (16, 2, 6, 8) and np.array_equal(a0, b0) and np.array_equal(a1, a0 + 1)
+    frames = a0[:, 0, 0, 0] / (2 * 6 * 8)
+    assert np.array_equal(a0, preds[0].numpy()[frames.astype(int)]) and np.all(np.diff(frames) > 0)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 2 * 16 * 2 * 6 * 8 * 4 + 2 * 256
+    bench.dump_outputs({"cost": torch.ones(3, 5, dtype=torch.bfloat16)}, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "cost.npy"), np.ones((3, 5), np.float32))
+
+
 def test_counter_pass_children_get_a_single_process_environment():
     """Under `torch.distributed.run --nproc-per-node 1` bench.py's rocprofv3 child runs must not inherit the launcher's rendezvous: with
     TORCHELASTIC_USE_AGENT_STORE their own one-rank group would wait for the agent's store until the pass timed out (seen in round 5)."""

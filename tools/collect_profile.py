@@ -39,7 +39,7 @@ GiB_KB = float(1 << 20)
 fcorr = GiB_KB / calib["FETCH_SIZE"] if calib["FETCH_SIZE"] else 2.0
 wcorr = GiB_KB / calib["WRITE_SIZE"] if calib["WRITE_SIZE"] else 1.0
 with open(os.path.join(dst, "pmc_kernels.txt"), "w") as o:
-    o.write(f"# mean per dispatch over the rocprofv3 --pmc passes of `python bench.py --steps 20 --warmup 5` (tools/profile_round.sh)\n"
+    o.write(f"# mean per dispatch over the rocprofv3 --pmc passes of `python bench.py --full --steps 20 --warmup 5` (tools/profile_round.sh)\n"
             f"# calibration copy (1 GiB read + 1 GiB write): FETCH_SIZE {calib['FETCH_SIZE']} KB, WRITE_SIZE {calib['WRITE_SIZE']} KB"
             f" -> corrections x{fcorr:.3f}, x{wcorr:.3f}\n")
     for k, d in sorted(ctr.items()):
