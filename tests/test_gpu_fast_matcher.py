@@ -3,7 +3,9 @@
 The production kernel does not reproduce the reference's fp32 rounding sequence (homography.py:131-148): parity is
 (a) gate-flip fraction <= 1e-5 against the oracle's gate bits (homography.py:157-158), read back through the ABI's
 `gate_bits` debug output, (b) |hip - oracle| <= 2e-5 + 2e-5 |oracle| on every entry none of whose gates flipped,
-(c) abs_rel of the refinement loop's depth < 1e-4 (north_star).  The exact kernels (path 1/2/3) keep their bitwise /
+(c) abs_rel of the refinement loop's depth < 1e-4 (north_star), (d) wherever gate bits are read back, the fp64 explainer
+(tests/parity.py: explain_production): every gate that disagrees with fp64 sits within its margin, every entry equals
+(1/V) sum_v gate_hip * dot64_v within the value bound.  The exact kernels (path 1/2/3) keep their bitwise /
 zero-flip tests in test_gpu_parity.py."""
 import numpy as np
 import pytest
@@ -29,15 +31,40 @@ def _run(inp, k_list, device, feat_dtype="fp32", path=4, want_gates=True, kappa=
     return cost, gates
 
 
+def _run_split(inp, k_list, device, feat_dtype="fp32", path=4, kappa=5):
+    """The split-output form (out_split = (hi, lo, ld)) MAGNET.forward consumes: a poisoned channel-last buffer with a one-pixel
+    border and ld > D; returns the (B, h+2, w+2, ld) hi / lo planes."""
+    from magnet_amd.homography import CostVolumeCW
+    d = to_dev(inp, device)
+    cv = CostVolumeCW(d["ref_feat"], d["nghbr_feat"], d["nghbr_gmms"], d["nghbr_poses"], d["is_valid"],
+                      d["cam_intrins"], kappa, feat_dtype=feat_dtype, path=path)
+    B, F, h, w = inp["ref_feat"].shape
+    ld = (len(k_list) + 8 + 7) // 8 * 8
+    hi = torch.full((B * (h + 2) * (w + 2), ld), 7.0, dtype=torch.bfloat16, device=device); lo = torch.full_like(hi, 7.0)
+    cv(ref_gmm=d["ref_gmms"], k_list=k_list, out_split=(hi, lo, ld))
+    return hi.view(B, h + 2, w + 2, ld), lo.view(B, h + 2, w + 2, ld)
+
+
 def _check(inp, k, gpu, fdt="fp32", label="", path=4):
+    from magnet_amd.convnet import split_bf16
     orc, og, _ = oracle_cost(inp, k, aux=True)
     cost, gates = _run(inp, k, gpu, feat_dtype=fdt, path=path)
     h, w = inp["ref_feat"].shape[-2:]
     sens = position_sensitivity(inp, k, og, device=gpu)
-    st = assert_tolerant_parity(cost, orc, gates, og, label=label, sens=sens, eps=pos_eps(h, w), flip_rate_scale=flip_scale(h, w))
+    st = assert_tolerant_parity(cost, orc, gates, og, label=label, sens=sens, eps=pos_eps(h, w), flip_rate_scale=flip_scale(h, w),
+                                inp=inp, k_list=k, kappa=5.0, device=gpu)
     # the production launch (no debug output) is a different template instance: it must give the same volume
     plain, _ = _run(inp, k, gpu, feat_dtype=fdt, path=path, want_gates=False)
     assert torch.equal(plain, cost), f"{label}: gate-bit instance and production instance differ"
+    # and so is the split-output instance MAGNET.forward consumes: its planes are split_bf16 of the dense volume bit for bit, the
+    # border and the channels beyond D stay untouched
+    D = len(k)
+    hi4, lo4 = _run_split(inp, k, gpu, feat_dtype=fdt, path=path)
+    eh, el = split_bf16(cost.permute(0, 2, 3, 1).contiguous())
+    assert torch.equal(hi4[:, 1:-1, 1:-1, :D], eh) and torch.equal(lo4[:, 1:-1, 1:-1, :D], el), f"{label}: split-output instance differs"
+    for pl in (hi4, lo4):
+        assert torch.all(pl[..., D:] == 7.0) and torch.all(pl[:, 0] == 7.0) and torch.all(pl[:, -1] == 7.0) \
+            and torch.all(pl[:, :, 0] == 7.0) and torch.all(pl[:, :, -1] == 7.0), f"{label}: split output wrote outside the volume"
     return st
 
 
@@ -378,3 +405,43 @@ def test_fast_forward_abs_rel_vs_oracle_forward(hip_lib, gpu):
         abs_rel = oracle.abs_rel(np.abs(b_[:, 0]) + 1e-3, np.abs(a_[:, 0]) + 1e-3)
         print(f"[forward, iteration {i}] abs_rel(production HIP forward vs oracle forward) = {abs_rel:.3e}")
         assert np.isfinite(a_).all() and abs_rel < 1e-4
+
+
+def _pack_gmm_quad_torch(g):
+    """fp32 restatement of elementwise.hip: pack_gmm_quad_kernel.  g (N,2,h,w) -> (N,h+2,w+2,8): per quad origin (x0, y0) of the
+    zero-bordered map, {v00, v10 - v00, v01 - v00, (v11 - v01) - (v10 - v00)} for mu, then for sigma (x0 + 1 = v10, y0 + 1 = v01);
+    texels outside the image are 0."""
+    N, _, h, w = g.shape
+    p = torch.nn.functional.pad(g.float(), (1, 2, 1, 2))                   # padded map + one more zero row / column for the +1 taps
+    v00, v10, v01, v11 = p[..., :h + 2, :w + 2], p[..., :h + 2, 1:w + 3], p[..., 1:h + 3, :w + 2], p[..., 1:h + 3, 1:w + 3]
+    q = torch.stack([v00, v10 - v00, v01 - v00, (v11 - v01) - (v10 - v00)], dim=-1)   # (N,2,h+2,w+2,4)
+    return q.permute(0, 2, 3, 1, 4).reshape(N, h + 2, w + 2, 8).contiguous()
+
+
+def test_pack_gmm_quad_equals_the_torch_restatement(hip_lib, gpu):
+    """The quad-form (mu, sigma) map every D > 32 production launch reads, bit for bit: N > 1, a ragged w, quad origins on the padded
+    map's first / last rows and columns (half or wholly outside the image), and one NaN that must reach exactly the four quads that
+    contain its texel."""
+    from magnet_amd import lib
+    gen = torch.Generator().manual_seed(31)
+    for N, h, w in ((3, 7, 13), (2, 12, 61), (1, 1, 1)):
+        g = torch.randn(N, 2, h, w, generator=gen) * 3.0 + 2.0
+        g[:, 1] = g[:, 1].abs() * 1e-3 + torch.rand(N, h, w, generator=gen) * 1e4      # wide dynamic range: rounding of the differences shows
+        got = lib.pack_gmm_quad(g.to(gpu)).cpu()
+        want = _pack_gmm_quad_torch(g)
+        assert got.shape == (N, h + 2, w + 2, 8)
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), (N, h, w)
+        # border quads: origin row / column -1 (padded 0) and h / w (padded h+1 / w+1) hold only what lies inside the image
+        assert torch.equal(got[:, -1, :, 0], torch.zeros(N, w + 2)) and torch.equal(got[:, :, -1, 4], torch.zeros(N, h + 2))
+        assert torch.equal(got[:, 0, 0], torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]).expand(N, 8) * torch.stack(
+            [g[:, 0, 0, 0]] * 4 + [g[:, 1, 0, 0]] * 4, dim=-1))
+    N, h, w = 2, 9, 11
+    g = torch.rand(N, 2, h, w, generator=gen) + 1.0
+    g[1, 0, 4, 10] = float("nan")                                           # mu texel (y=4, x=10: the last column)
+    got = lib.pack_gmm_quad(g.to(gpu)).cpu()
+    assert torch.equal(torch.nan_to_num(got, nan=-1.0).view(torch.int32), torch.nan_to_num(_pack_gmm_quad_torch(g), nan=-1.0).view(torch.int32))
+    bad = torch.isnan(got).any(dim=-1)                                      # (N,h+2,w+2) quads holding a NaN
+    want = torch.zeros_like(bad)
+    want[1, 4:6, 10:12] = True                                              # padded origins (y0+1, x0+1) for y0 in {3, 4}, x0 in {9, 10}
+    assert torch.equal(bad, want)
+    assert not torch.isnan(got[1, 4:6, 10:12, 4:]).any()                    # sigma is untouched

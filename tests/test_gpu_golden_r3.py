@@ -107,7 +107,8 @@ def test_production_matcher_plain_bound_on_smooth_inputs(hip_lib, gpu, golden_r3
     cost, gates = _run(inp, k, gpu, "bf16" if bf16 else "fp32")
     sens = position_sensitivity(inp, k, og, device=gpu)
     eps = pos_eps(wl.h, wl.w)
-    st = assert_tolerant_parity(cost, orc, gates, og, n_views=wl.V, label=f"{name} smooth", sens=sens, eps=eps)
+    st = assert_tolerant_parity(cost, orc, gates, og, n_views=wl.V, label=f"{name} smooth", sens=sens, eps=eps,
+                                inp=inp, k_list=k, kappa=5.0, device=gpu)
     assert st["gate_flip_frac"] <= 1e-5 and st["frac_over_2e5"] < 1e-3, st
     got = cost.cpu().numpy().astype(np.float64)
     flipped = (gates.cpu().numpy().astype(bool) != og.astype(bool)).any(axis=1)
