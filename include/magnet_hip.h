@@ -360,6 +360,90 @@ MAGNET_API int magnet_depth_metrics_crop(const float *pred, const float *gt, dou
                                          float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1,
                                          void *stream);
 
+/* ---- training step of g_net / mask_head (train_MaGNet.py:87-98): loss, convex-upsampling backward, head backward, weight
+ * gradients.  Additive to v400: new entry points with their own argument structs (zero-initialise, then fill).  Every sum is
+ * taken in a fixed order with no atomics: results are bit-identical from run to run. */
+
+#define MAGNET_NLL_BLOCKS   256            /* workgroups of the loss's first reduction stage */
+#define MAGNET_NLL_MAX_ITER 16             /* n_iter limit of the loss */
+#define MAGNET_WGRAD_CHUNK  2048           /* rows per partial tile of magnet_wgrad */
+
+/* MagnetLoss, loss_fn 'gaussian' (utils/losses.py:28-52): for every iteration i, var = sigma^2 clamped to 1e-10 (no gradient
+ * where the clamp applies), nll = (mu - gt)^2 / (2 var) + 0.5 log var averaged over the masked pixels, weighted by
+ * gamma^(n_iter - 1 - i). */
+typedef struct MagnetNllArgs {
+    const float   *preds;                  /* (n_iter, B, 2, H, W) fp32 [mu, sigma] */
+    const float   *gt;                     /* (B, H, W) */
+    const uint8_t *mask;                   /* (B, H, W), 0 / 1 */
+    double        *sums;                   /* (1 + n_iter): masked count, per-iteration NLL sums (forward writes, backward reads) */
+    float         *loss;                   /* forward: the 0-d loss */
+    double        *work;                   /* forward: MAGNET_NLL_BLOCKS * (1 + n_iter) doubles of scratch */
+    const float   *grad_loss;              /* backward: device scalar dL/dloss (read on the device) */
+    float         *grad_preds;             /* backward: (n_iter, B, 2, H, W), every element written */
+    double         gamma;
+    int32_t        n_iter, B, H, W;
+} MagnetNllArgs;
+MAGNET_API int magnet_nll_loss_forward(const MagnetNllArgs *args, void *stream);
+MAGNET_API int magnet_nll_loss_backward(const MagnetNllArgs *args, void *stream);
+
+/* Backward of the learned convex upsampling (models/MAGNET.py:15-27) for n_pred predictions sharing one mask:
+ * grad_up (n_pred, B, 2, k h, k w), depth (n_pred, B, 2, h, w) -> grad_depth (same shape as depth) and grad_mask = the mask's
+ * gradient summed over the predictions.  The mask's logit (b, ch, y, x), ch < 9 k k, sits at mask[b*mask_sb + ch*mask_sc +
+ * y*mask_sy + x*mask_sx]; grad_mask's at grad_mask[b*gm_sb + ch*gm_sc + y*gm_sy + x*gm_sx] (only those elements are written).
+ * work: n_pred*B*2*9*h*w floats. */
+typedef struct MagnetUpsampleBwdArgs {
+    const float *grad_up, *depth, *mask;
+    float       *grad_depth, *grad_mask, *work;
+    int64_t      mask_sb, mask_sc, mask_sy, mask_sx;
+    int64_t      gm_sb, gm_sc, gm_sy, gm_sx;
+    int32_t      n_pred, B, h, w, k;       /* k <= 8 */
+} MagnetUpsampleBwdArgs;
+MAGNET_API int magnet_upsample_depth_backward(const MagnetUpsampleBwdArgs *args, void *stream);
+
+/* Backward through the 1x1 tail of a stack (models/MAGNET.py:53-55, :113-115): dh3 = W4^T dout [h3 > 0], dh2 = W3^T dh3 [h2 > 0],
+ * dh1 = W2^T dh2 [h1 > 0] on the matrix cores (bf16x3).  Rows are the zero-bordered grid of magnet_conv_mfma (rows = B (h+2) (w+2));
+ * every output is written on every row, zeros on the border rows.  G-Net form (dout == NULL, k0 = 32): dout = the Gaussian update's
+ * backward (models/MAGNET.py:60-69) from grad_gmm, the head's fp32 output gnet_out (channel 1 = pre-ELU sigma) and gmm_in. */
+typedef struct MagnetHeadDgradArgs {
+    const float *dout;                     /* fp32 (rows, k0) gradient of the last layer's output, or NULL (G-Net form) */
+    int32_t      k0;                       /* 32, 128 or 160: last layer's output channels padded to 32 */
+    const void  *wt_hi, *wt_lo;            /* bf16 [W4^T (128, k0) | W3^T (128, 128) | W2^T (128, 128)] (nn.Conv2d weight transposed) */
+    const void  *h3_hi, *h2_hi, *h1_hi;    /* bf16 hi planes (rows, 128) of the forward's post-ReLU activations */
+    void        *dout_hi, *dout_lo;        /* out: split bf16 (rows, k0) of dout (input of the last layer's weight gradient) */
+    void        *dh3_hi, *dh3_lo, *dh2_hi, *dh2_lo, *dh1_hi, *dh1_lo;   /* out: split bf16 (rows, 128) */
+    float       *acc;                      /* optional fp32 (rows, 128): acc_mode 1 acc = dh1, 2 acc += dh1 */
+    void        *acc_hi, *acc_lo;          /* optional: split bf16 of the updated acc */
+    int32_t      acc_mode;
+    int32_t      B, h, w;
+    int64_t      rows;
+    const float *grad_gmm;                 /* G-Net form: (B, 2, h, w) d(mu, sigma) of the update's output */
+    const float *gnet_out;                 /* G-Net form: fp32 (rows, gnet_ld) */
+    const float *gmm_in;                   /* G-Net form: (B, 2, h, w) the update's input (mu0, sigma0) */
+    int32_t      gnet_ld;
+} MagnetHeadDgradArgs;
+MAGNET_API int magnet_head_dgrad(const MagnetHeadDgradArgs *args, void *stream);
+
+/* Weight gradient of one convolution layer on the matrix cores (bf16x3, fp32 accumulation): dW[tap][o][c] = sum over the interior
+ * rows [wp+1, rows-wp-1) of dy[row][o] * x[row + off(tap)][c], off = (tap/3 - 1) wp + (tap%3 - 1) for taps = 9; bias gradient
+ * sum dy[row][o].  dy and x are split bf16 planes of the zero-bordered grid (dy zero on its border rows); x may be a channel
+ * slice of a wider buffer (x_ld).  The result for o < cout_valid, c < cin_valid lands in grad_w laid out as nn.Conv2d's
+ * (Cout, cin_total, kh, kw) at input channel cin_dst + c (accumulate = 1: added to what is there). */
+typedef struct MagnetWgradArgs {
+    const void *dy_hi, *dy_lo;
+    const void *x_hi, *x_lo;
+    int64_t     dy_ld, x_ld;               /* row pitches in elements (multiples of 8) */
+    int64_t     rows;
+    int32_t     cout, cin;                 /* channels read: multiples of 8 */
+    int32_t     taps, wp;                  /* taps 1 or 9; wp = w + 2 */
+    float      *grad_w;
+    float      *grad_b;                    /* optional (cout_valid) */
+    int32_t     cout_valid, cin_valid, cin_total, cin_dst;
+    int32_t     accumulate;
+    float      *work;                      /* magnet_wgrad_workspace(args) bytes */
+} MagnetWgradArgs;
+MAGNET_API int64_t magnet_wgrad_workspace(const MagnetWgradArgs *args);
+MAGNET_API int magnet_wgrad(const MagnetWgradArgs *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,12 @@ hipError_t launch_upsample_bilinear_cl(const float*, int, int, int, int, uint16_
 hipError_t launch_depth_metrics(const float*, const float*, double*, int, int, int, float, float, int, int, int, int, hipStream_t);
 hipError_t launch_make_rays(const double*, float*, int, int, int, hipStream_t);
 hipError_t launch_relative_poses(const double*, const double*, float*, int32_t*, int, int, hipStream_t);
+hipError_t launch_nll_forward(const MagnetNllArgs&, hipStream_t);
+hipError_t launch_nll_backward(const MagnetNllArgs&, hipStream_t);
+hipError_t launch_upsample_backward(const MagnetUpsampleBwdArgs&, hipStream_t);
+hipError_t launch_head_dgrad(const MagnetHeadDgradArgs&, hipStream_t);
+hipError_t launch_wgrad(const MagnetWgradArgs&, hipStream_t);
+long long wgrad_workspace_bytes(const MagnetWgradArgs&);
 }
 
 static thread_local char g_err[512] = "";
@@ -490,6 +496,76 @@ MAGNET_API int magnet_depth_metrics_crop(const float* pred, const float* gt, dou
         return fail(MAGNET_E_DIM, "magnet_depth_metrics_crop: bad arguments");
     hipError_t e = magnet::launch_depth_metrics(pred, gt, sums, B, H * W, W, min_depth, max_depth, y0, y1, x0, x1, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_depth_metrics_crop launch");
+}
+
+// ---- training step (train_bwd.hip) ----
+MAGNET_API int magnet_nll_loss_forward(const MagnetNllArgs* a, void* stream) {
+    if (!a || !a->preds || !a->gt || !a->mask || !a->sums || !a->loss || !a->work)
+        return fail(MAGNET_E_NULL, "magnet_nll_loss_forward: NULL pointer");
+    if (a->n_iter <= 0 || a->n_iter > MAGNET_NLL_MAX_ITER || a->B <= 0 || a->H <= 0 || a->W <= 0)
+        return fail(MAGNET_E_DIM, "magnet_nll_loss_forward: bad dims (1 <= n_iter <= %d)", MAGNET_NLL_MAX_ITER);
+    hipError_t e = magnet::launch_nll_forward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_nll_loss_forward launch");
+}
+
+MAGNET_API int magnet_nll_loss_backward(const MagnetNllArgs* a, void* stream) {
+    if (!a || !a->preds || !a->gt || !a->mask || !a->sums || !a->grad_loss || !a->grad_preds)
+        return fail(MAGNET_E_NULL, "magnet_nll_loss_backward: NULL pointer");
+    if (a->n_iter <= 0 || a->n_iter > MAGNET_NLL_MAX_ITER || a->B <= 0 || a->H <= 0 || a->W <= 0)
+        return fail(MAGNET_E_DIM, "magnet_nll_loss_backward: bad dims (1 <= n_iter <= %d)", MAGNET_NLL_MAX_ITER);
+    hipError_t e = magnet::launch_nll_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_nll_loss_backward launch");
+}
+
+MAGNET_API int magnet_upsample_depth_backward(const MagnetUpsampleBwdArgs* a, void* stream) {
+    if (!a || !a->grad_up || !a->depth || !a->mask || !a->grad_depth || !a->grad_mask || !a->work)
+        return fail(MAGNET_E_NULL, "magnet_upsample_depth_backward: NULL pointer");
+    if (a->n_pred <= 0 || a->B <= 0 || a->h <= 0 || a->w <= 0 || a->k <= 0 || a->k > 8)
+        return fail(MAGNET_E_DIM, "magnet_upsample_depth_backward: bad dims (1 <= k <= 8)");
+    hipError_t e = magnet::launch_upsample_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_upsample_depth_backward launch");
+}
+
+MAGNET_API int magnet_head_dgrad(const MagnetHeadDgradArgs* a, void* stream) {
+    if (!a || !a->wt_hi || !a->wt_lo || !a->h3_hi || !a->h2_hi || !a->h1_hi || !a->dout_hi || !a->dout_lo || !a->dh3_hi ||
+        !a->dh3_lo || !a->dh2_hi || !a->dh2_lo || !a->dh1_hi || !a->dh1_lo)
+        return fail(MAGNET_E_NULL, "magnet_head_dgrad: NULL pointer");
+    if (!a->dout && (!a->grad_gmm || !a->gnet_out || !a->gmm_in)) return fail(MAGNET_E_NULL, "magnet_head_dgrad: NULL pointer (G-Net form)");
+    if (a->acc_mode && !a->acc) return fail(MAGNET_E_NULL, "magnet_head_dgrad: acc_mode without acc");
+    if ((a->acc_hi == nullptr) != (a->acc_lo == nullptr)) return fail(MAGNET_E_NULL, "magnet_head_dgrad: acc_hi / acc_lo");
+    if (a->B <= 0 || a->h <= 0 || a->w <= 0 || a->rows != (int64_t)a->B * (a->h + 2) * (a->w + 2) ||
+        (a->k0 != 32 && a->k0 != 128 && a->k0 != 160) || (!a->dout && (a->k0 != 32 || a->gnet_ld < 2)) ||
+        a->acc_mode < 0 || a->acc_mode > 2 || (a->acc && !a->acc_mode))
+        return fail(MAGNET_E_DIM, "magnet_head_dgrad: bad dims (rows = B(h+2)(w+2), k0 in {32,128,160}, G-Net form k0 = 32)");
+    const void* al[] = {a->dout, a->wt_hi, a->wt_lo, a->h3_hi, a->h2_hi, a->h1_hi, a->dout_hi, a->dout_lo, a->dh3_hi, a->dh3_lo,
+                        a->dh2_hi, a->dh2_lo, a->dh1_hi, a->dh1_lo, a->acc, a->acc_hi, a->acc_lo};
+    for (const void* p : al) if (!aligned16(p)) return fail(MAGNET_E_ALIGN, "magnet_head_dgrad: pointers not 16-byte aligned");
+    hipError_t e = magnet::launch_head_dgrad(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_head_dgrad launch");
+}
+
+static int wgrad_check(const MagnetWgradArgs* a, const char* who) {
+    if (!a || !a->dy_hi || !a->dy_lo || !a->x_hi || !a->x_lo || !a->grad_w) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (a->cout <= 0 || a->cin <= 0 || (a->cout % 8) || (a->cin % 8) || (a->taps != 1 && a->taps != 9) || a->wp < 1 ||
+        a->rows <= 0 || a->dy_ld < a->cout || a->x_ld < a->cin || (a->dy_ld % 8) || (a->x_ld % 8) ||
+        a->cout_valid <= 0 || a->cout_valid > a->cout || a->cin_valid <= 0 || a->cin_valid > a->cin || a->cin_dst < 0 ||
+        a->cin_dst + a->cin_valid > a->cin_total)
+        return fail(MAGNET_E_DIM, "%s: bad dims (cout, cin, ld multiples of 8; taps 1 or 9; valid ranges inside)", who);
+    return 0;
+}
+
+MAGNET_API int64_t magnet_wgrad_workspace(const MagnetWgradArgs* a) {
+    if (int rc = wgrad_check(a, "magnet_wgrad_workspace")) return -(int64_t)rc;
+    return magnet::wgrad_workspace_bytes(*a);
+}
+
+MAGNET_API int magnet_wgrad(const MagnetWgradArgs* a, void* stream) {
+    if (int rc = wgrad_check(a, "magnet_wgrad")) return rc;
+    if (!a->work && magnet::wgrad_workspace_bytes(*a) > 0) return fail(MAGNET_E_NULL, "magnet_wgrad: NULL workspace");
+    const void* al[] = {a->dy_hi, a->dy_lo, a->x_hi, a->x_lo, a->work};
+    for (const void* p : al) if (!aligned16(p)) return fail(MAGNET_E_ALIGN, "magnet_wgrad: pointers not 16-byte aligned");
+    hipError_t e = magnet::launch_wgrad(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_wgrad launch");
 }
 
 }  // extern "C"

@@ -698,3 +698,168 @@ def upsample_bilinear_cl(x, in_ld, ph, pw, C, out_hi, out_lo, out_ld, N, h, w, p
         _check(lib.magnet_upsample_bilinear_cl(_dev(x, "x", torch.float32).data_ptr(), in_ld, ph, pw, C, _bf16_ptr(out_hi, "out_hi"),
                                                _bf16_ptr(out_lo, "out_lo"), out_ld, N, h, w, pad, _stream(x)),
                "magnet_upsample_bilinear_cl")
+
+
+# ---- training step of g_net / mask_head (include/magnet_hip.h: magnet_nll_loss_*, magnet_upsample_depth_backward,
+# ---- magnet_head_dgrad, magnet_wgrad; csrc/train_bwd.hip) -----------------------------------------------------------
+API_SYMBOLS = API_SYMBOLS + ("magnet_nll_loss_forward", "magnet_nll_loss_backward", "magnet_upsample_depth_backward",
+                             "magnet_head_dgrad", "magnet_wgrad_workspace", "magnet_wgrad")
+NLL_BLOCKS, NLL_MAX_ITER = 256, 16
+
+
+class MagnetNllArgs(ctypes.Structure):
+    """Mirror of `struct MagnetNllArgs` (include/magnet_hip.h)."""
+    _fields_ = [("preds", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("sums", ctypes.c_void_p),
+                ("loss", ctypes.c_void_p), ("work", ctypes.c_void_p), ("grad_loss", ctypes.c_void_p), ("grad_preds", ctypes.c_void_p),
+                ("gamma", ctypes.c_double),
+                ("n_iter", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+class MagnetUpsampleBwdArgs(ctypes.Structure):
+    """Mirror of `struct MagnetUpsampleBwdArgs` (include/magnet_hip.h)."""
+    _fields_ = [("grad_up", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("grad_depth", ctypes.c_void_p), ("grad_mask", ctypes.c_void_p), ("work", ctypes.c_void_p),
+                ("mask_sb", ctypes.c_int64), ("mask_sc", ctypes.c_int64), ("mask_sy", ctypes.c_int64), ("mask_sx", ctypes.c_int64),
+                ("gm_sb", ctypes.c_int64), ("gm_sc", ctypes.c_int64), ("gm_sy", ctypes.c_int64), ("gm_sx", ctypes.c_int64),
+                ("n_pred", ctypes.c_int32), ("B", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("k", ctypes.c_int32)]
+
+
+class MagnetHeadDgradArgs(ctypes.Structure):
+    """Mirror of `struct MagnetHeadDgradArgs` (include/magnet_hip.h)."""
+    _fields_ = [("dout", ctypes.c_void_p), ("k0", ctypes.c_int32),
+                ("wt_hi", ctypes.c_void_p), ("wt_lo", ctypes.c_void_p),
+                ("h3_hi", ctypes.c_void_p), ("h2_hi", ctypes.c_void_p), ("h1_hi", ctypes.c_void_p),
+                ("dout_hi", ctypes.c_void_p), ("dout_lo", ctypes.c_void_p),
+                ("dh3_hi", ctypes.c_void_p), ("dh3_lo", ctypes.c_void_p), ("dh2_hi", ctypes.c_void_p), ("dh2_lo", ctypes.c_void_p),
+                ("dh1_hi", ctypes.c_void_p), ("dh1_lo", ctypes.c_void_p),
+                ("acc", ctypes.c_void_p), ("acc_hi", ctypes.c_void_p), ("acc_lo", ctypes.c_void_p), ("acc_mode", ctypes.c_int32),
+                ("B", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("rows", ctypes.c_int64),
+                ("grad_gmm", ctypes.c_void_p), ("gnet_out", ctypes.c_void_p), ("gmm_in", ctypes.c_void_p), ("gnet_ld", ctypes.c_int32)]
+
+
+class MagnetWgradArgs(ctypes.Structure):
+    """Mirror of `struct MagnetWgradArgs` (include/magnet_hip.h)."""
+    _fields_ = [("dy_hi", ctypes.c_void_p), ("dy_lo", ctypes.c_void_p), ("x_hi", ctypes.c_void_p), ("x_lo", ctypes.c_void_p),
+                ("dy_ld", ctypes.c_int64), ("x_ld", ctypes.c_int64), ("rows", ctypes.c_int64),
+                ("cout", ctypes.c_int32), ("cin", ctypes.c_int32), ("taps", ctypes.c_int32), ("wp", ctypes.c_int32),
+                ("grad_w", ctypes.c_void_p), ("grad_b", ctypes.c_void_p),
+                ("cout_valid", ctypes.c_int32), ("cin_valid", ctypes.c_int32), ("cin_total", ctypes.c_int32), ("cin_dst", ctypes.c_int32),
+                ("accumulate", ctypes.c_int32), ("work", ctypes.c_void_p)]
+
+
+def _train_protos(lib):
+    if getattr(lib, "_train_protos_done", False):
+        return lib
+    P = ctypes.c_void_p
+    for name, st in (("magnet_nll_loss_forward", MagnetNllArgs), ("magnet_nll_loss_backward", MagnetNllArgs),
+                     ("magnet_upsample_depth_backward", MagnetUpsampleBwdArgs), ("magnet_head_dgrad", MagnetHeadDgradArgs),
+                     ("magnet_wgrad", MagnetWgradArgs)):
+        f = getattr(lib, name)
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.POINTER(st), P]
+    lib.magnet_wgrad_workspace.restype = ctypes.c_int64
+    lib.magnet_wgrad_workspace.argtypes = [ctypes.POINTER(MagnetWgradArgs)]
+    lib._train_protos_done = True
+    return lib
+
+
+def nll_loss_forward(preds, gt, mask, gamma: float):
+    """preds (I,B,2,H,W) fp32, gt (B,H,W) fp32, mask (B,H,W) bool -> (loss 0-d fp32, sums (1+I) float64: count, per-iteration
+    NLL sums).  Deterministic two-stage reduction on the device."""
+    lib = _train_protos(load())
+    p = _dev(preds, "preds", torch.float32)
+    g = _dev(gt, "gt", torch.float32)
+    m = _dev(mask, "mask", torch.bool)
+    I, B, C, H, W = p.shape
+    if C != 2 or tuple(g.shape) != (B, H, W) or tuple(m.shape) != (B, H, W):
+        raise MagnetError(f"nll_loss: shapes {tuple(p.shape)} {tuple(g.shape)} {tuple(m.shape)}, expected (I,B,2,H,W), (B,H,W), (B,H,W)")
+    if not 1 <= I <= NLL_MAX_ITER:
+        raise MagnetError(f"nll_loss: 1 <= n_iter <= {NLL_MAX_ITER}, got {I}")
+    sums = torch.empty(1 + I, dtype=torch.float64, device=p.device)
+    work = torch.empty(NLL_BLOCKS * (1 + I), dtype=torch.float64, device=p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    a = MagnetNllArgs(preds=p.data_ptr(), gt=g.data_ptr(), mask=m.data_ptr(), sums=sums.data_ptr(), loss=loss.data_ptr(),
+                      work=work.data_ptr(), gamma=float(gamma), n_iter=I, B=B, H=H, W=W)
+    with torch.cuda.device(p.device):
+        _check(lib.magnet_nll_loss_forward(ctypes.byref(a), _stream(p)), "magnet_nll_loss_forward")
+    return loss, sums
+
+
+def nll_loss_backward(preds, gt, mask, sums, grad_loss, gamma: float):
+    """d loss / d preds (I,B,2,H,W), scaled by the device scalar grad_loss (read on the device: no host sync)."""
+    lib = _train_protos(load())
+    p = _dev(preds, "preds", torch.float32)
+    gl = _dev(grad_loss.reshape(()), "grad_loss", torch.float32)
+    I, B, _, H, W = p.shape
+    out = torch.empty_like(p)
+    a = MagnetNllArgs(preds=p.data_ptr(), gt=_dev(gt, "gt", torch.float32).data_ptr(), mask=_dev(mask, "mask", torch.bool).data_ptr(),
+                      sums=_dev(sums, "sums", torch.float64).data_ptr(), grad_loss=gl.data_ptr(), grad_preds=out.data_ptr(),
+                      gamma=float(gamma), n_iter=I, B=B, H=H, W=W)
+    with torch.cuda.device(p.device):
+        _check(lib.magnet_nll_loss_backward(ctypes.byref(a), _stream(p)), "magnet_nll_loss_backward")
+    return out
+
+
+def upsample_depth_backward(grad_up, depths, mask, k: int, mask_layout=None, grad_mask=None, grad_mask_layout=None):
+    """Backward of the convex upsampling for n predictions sharing one mask.  grad_up (n,B,2,kh,kw), depths (n,B,2,h,w) ->
+    (grad_depths (n,B,2,h,w), grad_mask = the mask's gradient summed over the predictions).  mask: NCHW (B,9k^2,h,w) logits
+    (layouts None: grad_mask is returned in that layout), or contiguous fp32 storage addressed by mask_layout = (element offset,
+    sb, sc, sy, sx), with a preallocated contiguous grad_mask addressed by grad_mask_layout (the padded channel-last buffers of the
+    HIP training path)."""
+    lib = _train_protos(load())
+    gu = _dev(grad_up, "grad_up", torch.float32)
+    d = _dev(depths, "depths", torch.float32)
+    n, B, C, h, w = d.shape
+    if C != 2 or tuple(gu.shape) != (n, B, 2, k * h, k * w):
+        raise MagnetError(f"upsample_depth_backward: shapes {tuple(gu.shape)} / {tuple(d.shape)} (k = {k})")
+    m = _dev(mask, "mask", torch.float32)
+    if mask_layout is None:
+        if tuple(m.shape) != (B, 9 * k * k, h, w):
+            raise MagnetError(f"upsample_depth_backward: mask shape {tuple(m.shape)}, expected {(B, 9 * k * k, h, w)}")
+        grad_mask = torch.zeros_like(m)
+        mask_layout = grad_mask_layout = (0, 9 * k * k * h * w, h * w, w, 1)
+    elif grad_mask is None or grad_mask_layout is None:
+        raise MagnetError("upsample_depth_backward: mask_layout needs grad_mask and grad_mask_layout")
+    gm = _dev(grad_mask, "grad_mask", torch.float32)
+    gd = torch.empty_like(d)
+    work = torch.empty(n * B * 2 * 9 * h * w, dtype=torch.float32, device=d.device)
+    mo, msb, msc, msy, msx = mask_layout
+    go, gsb, gsc, gsy, gsx = grad_mask_layout
+    a = MagnetUpsampleBwdArgs(grad_up=gu.data_ptr(), depth=d.data_ptr(), mask=m.data_ptr() + 4 * mo, grad_depth=gd.data_ptr(),
+                              grad_mask=gm.data_ptr() + 4 * go, work=work.data_ptr(), mask_sb=msb, mask_sc=msc, mask_sy=msy,
+                              mask_sx=msx, gm_sb=gsb, gm_sc=gsc, gm_sy=gsy, gm_sx=gsx, n_pred=n, B=B, h=h, w=w, k=int(k))
+    with torch.cuda.device(d.device):
+        _check(lib.magnet_upsample_depth_backward(ctypes.byref(a), _stream(d)), "magnet_upsample_depth_backward")
+    return gd, grad_mask
+
+
+def head_dgrad(a: "MagnetHeadDgradArgs", device):
+    lib = _train_protos(load())
+    with torch.cuda.device(device):
+        _check(lib.magnet_head_dgrad(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+               "magnet_head_dgrad")
+
+
+def wgrad(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst=0, cout_valid=None, cin_valid=None, grad_b=None,
+          accumulate=False):
+    """Weight (and bias) gradient of one convolution layer on the matrix cores.  dy_* (rows, dy_ld) and x_* (rows, x_ld) split
+    bf16 planes of the zero-bordered grid (x_* may be a channel-offset view of a wider buffer); grad_w: the layer's
+    nn.Conv2d-shaped fp32 gradient (Cout, Cin_total, kh, kw), written at input channels [cin_dst, cin_dst + cin_valid)."""
+    lib = _train_protos(load())
+    for t, nme in ((dy_hi, "dy_hi"), (dy_lo, "dy_lo"), (x_hi, "x_hi"), (x_lo, "x_lo")):
+        _bf16_ptr(t, nme)
+    gw = _dev(grad_w, "grad_w", torch.float32)
+    if grad_b is not None:
+        _dev(grad_b, "grad_b", torch.float32)
+    a = MagnetWgradArgs(dy_hi=dy_hi.data_ptr(), dy_lo=dy_lo.data_ptr(), x_hi=x_hi.data_ptr(), x_lo=x_lo.data_ptr(),
+                        dy_ld=dy_hi.stride(0), x_ld=x_hi.stride(0), rows=int(rows), cout=int(cout), cin=int(cin), taps=int(taps),
+                        wp=int(wp), grad_w=gw.data_ptr(), grad_b=grad_b.data_ptr() if grad_b is not None else None,
+                        cout_valid=int(cout if cout_valid is None else cout_valid), cin_valid=int(cin if cin_valid is None else cin_valid),
+                        cin_total=gw.shape[1], cin_dst=int(cin_dst), accumulate=int(bool(accumulate)))
+    nbytes = lib.magnet_wgrad_workspace(ctypes.byref(a))
+    if nbytes < 0:
+        _check(int(-nbytes), "magnet_wgrad_workspace")
+    work = torch.empty(max(int(nbytes) // 4, 4), dtype=torch.float32, device=gw.device)
+    a.work = work.data_ptr()
+    with torch.cuda.device(gw.device):
+        _check(lib.magnet_wgrad(ctypes.byref(a), _stream(gw)), "magnet_wgrad")

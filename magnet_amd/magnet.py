@@ -8,9 +8,12 @@ What runs where (inference, conv_backend='mfma'):
   * Gaussian update tail, convex upsampling                     -> HIP kernels (lib.gaussian_update*/upsample_depth*)
   * a PSMNet-structured F-Net                                   -> HIP matrix-core path (magnet_amd/fnet.py)
   * D-Net                                                       -> caller-provided module (out of scope)
-Under autograd (mode='train' with trainable g_net / mask_head) the convolutions, the Gaussian update and the convex
-upsampling are torch ops, so gradients reach g_net and mask_head exactly as in the reference (train_MaGNet.py:87-98);
-the matcher is forward-only there too (the reference detaches its inputs, MAGNET.py:154,167-168).
+Under autograd (mode='train' with trainable g_net / mask_head), train_backend='torch' (the default) evaluates the convolutions,
+the Gaussian update and the convex upsampling as torch ops, so gradients reach g_net and mask_head exactly as in the reference
+(train_MaGNet.py:87-98).  train_backend='hip' runs the same step on HIP (magnet_amd/train.py): the heads layer by layer on the
+matrix-core kernel, the Gaussian update and the upsampling on the inference kernels, and a hand-written backward
+(csrc/train_bwd.hip: upsampling backward, dgrad through the 1x1 tails, weight gradients on the matrix cores); pair it with
+magnet_amd.losses.MagnetLoss.  The matcher is forward-only on both (the reference detaches its inputs, MAGNET.py:154,167-168).
 """
 from __future__ import annotations
 
@@ -100,10 +103,14 @@ class MAGNET(nn.Module):
     `f_net` (img -> (N,F,h,w)); both are required (an omitted backbone is an error naming the argument).
     `feat_dtype`: 'fp32' or 'bf16' storage of F-Net features inside the matcher.
     `conv_backend`: 'mfma' runs g_net / mask_head on the bf16x3 matrix-core kernel at inference (csrc/conv_mfma.hip,
-    fp32-grade); 'torch' keeps them on nn.Conv2d (MIOpen).  Autograd always takes the torch path."""
+    fp32-grade); 'torch' keeps them on nn.Conv2d (MIOpen).
+    `train_backend`: the path under autograd (mode='train' with trainable g_net / mask_head).  'torch' (default): nn.Conv2d and torch
+    ops, autograd's own backward.  'hip': the heads on the bf16x3 matrix-core kernel, backward in hand-written HIP (magnet_amd/train.py,
+    csrc/train_bwd.hip); gradients land in the nn.Conv2d parameters' .grad, deterministic bit for bit.  Needs the reference's heads
+    (downsample_ratio 4, 256-channel x_d3)."""
 
     def __init__(self, args, d_net: nn.Module | None = None, f_net: nn.Module | None = None,
-                 feat_dtype: str = "fp32", conv_backend: str = "mfma"):
+                 feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch"):
         super().__init__()
         self.args = args
         if d_net is None or f_net is None:
@@ -146,6 +153,9 @@ class MAGNET(nn.Module):
         if conv_backend not in ("mfma", "torch"):
             raise lib.MagnetError(f"conv_backend must be 'mfma' or 'torch', got {conv_backend!r}")
         self.conv_backend = conv_backend
+        if train_backend not in ("torch", "hip"):
+            raise lib.MagnetError(f"train_backend must be 'torch' or 'hip', got {train_backend!r}")
+        self.train_backend = train_backend
         self._work = {}                # cached device workspaces of the MFMA conv path, keyed by shape
         self.fuse_upsample = True      # the stacks' tails finish the job: G-Net's head applies the Gaussian update, the mask head
                                        # writes the upsampled predictions itself (no (B,144,h,w) mask in HBM); False: separate launches
@@ -215,6 +225,11 @@ class MAGNET(nn.Module):
                                                    list(self.g_net.parameters()) + list(self.mask_head.parameters()))
         if self.conv_backend == "mfma" and not training and self.downsample_ratio == 4 and (x_d3_in_place or x_d3.shape[1] == 256):
             return self._refine_mfma(matcher, ref_gmms, None if x_d3_in_place else x_d3, n_iter)
+        if training and self.train_backend == "hip":
+            if x_d3_in_place:
+                raise lib.MagnetError("x_d3_in_place is an inference form; train_backend='hip' takes x_d3 as a tensor")
+            from .train import refine_train_hip
+            return refine_train_hip(self, matcher, ref_gmms, x_d3, n_iter)
         if x_d3_in_place:
             raise lib.MagnetError("x_d3_in_place needs the matrix-core convolution path (conv_backend='mfma', inference)")
 
