@@ -444,6 +444,105 @@ typedef struct MagnetWgradArgs {
 MAGNET_API int64_t magnet_wgrad_workspace(const MagnetWgradArgs *args);
 MAGNET_API int magnet_wgrad(const MagnetWgradArgs *args, void *stream);
 
+/* ---- F-Net forward in training mode (train_FNet.py:69-119 with model.train()): BatchNorm2d with the statistics of the batch.
+ * Additive to v400: new entry points with their own argument struct (zero-initialise, then fill).  The statistics are summed in a
+ * fixed order in fp64 with no atomics: results, running statistics included, are bit-identical from run to run. */
+
+#define MAGNET_BN_BLOCKS 256               /* workgroups of the statistics' first reduction stage */
+
+/* firstconv.0 of the F-Net without BatchNorm and ReLU: (N, 3, H, W) fp32 image, wgt (32, 27) fp32 -> fp32 (N, H2+2, W2+2, 32)
+ * channel-last grid, H2 = (H-1)/2 + 1; only the interior is written. */
+MAGNET_API int magnet_fnet_stem_raw(const float *img, const float *wgt, float *out, int32_t N, int32_t H, int32_t W, void *stream);
+
+/* One BatchNorm2d in training mode over a channel-last grid: N images of hp x wp rows whose interior, rows (n, pad + y, pad + x)
+ * for y < hp - 2 pad, x < wp - 2 pad, holds the layer's C channels (pad = 0: no border).
+ * magnet_bn_train_stats: mean and invstd = 1 / sqrt(biased variance + eps) over the N (hp - 2 pad)(wp - 2 pad) interior positions;
+ *   running_mean / running_var (optional) become (1 - m) running + m stat with the unbiased variance, m = momentum, or
+ *   1 / (num_batches_tracked + 1) when momentum < 0 (nn.BatchNorm2d(momentum=None)); num_batches_tracked (optional) += 1.
+ * magnet_bn_train_apply: y = (x - mean) invstd gamma + beta (+ res, split bf16, same grid) (ReLU if relu), written over the
+ *   whole grid as split bf16 planes (out_hi / out_lo, border rows zero; may be a channel slice: out_ld) or, with out_f32,
+ *   over the interior in fp32. */
+typedef struct MagnetBnTrainArgs {
+    const float *x;                        /* pre-BN fp32 activations, x_ld elements per row (multiple of 4) */
+    int64_t      x_ld;
+    int32_t      N, hp, wp, pad, C;        /* C a multiple of 8, C <= min(x_ld, 2048) */
+    double      *work;                     /* stats: MAGNET_BN_BLOCKS * C * 2 doubles of scratch */
+    float       *mean, *invstd;            /* (C): written by stats, read by apply */
+    float       *running_mean, *running_var;
+    int64_t     *num_batches_tracked;
+    double       eps, momentum;
+    const float *gamma, *beta;             /* (C) the affine parameters */
+    const void  *res_hi, *res_lo;          /* optional residual (split bf16), res_ld elements per row */
+    int64_t      res_ld;
+    int32_t      relu;
+    void        *out_hi, *out_lo;          /* split bf16 output, out_ld elements per row (multiple of 8) */
+    float       *out_f32;                  /* or fp32 output (then out_hi / out_lo are ignored) */
+    int64_t      out_ld;
+} MagnetBnTrainArgs;
+MAGNET_API int magnet_bn_train_stats(const MagnetBnTrainArgs *args, void *stream);
+MAGNET_API int magnet_bn_train_apply(const MagnetBnTrainArgs *args, void *stream);
+
+/* ---- F-Net backward in training mode (csrc/train_fnet_bwd.hip).  Fixed-order sums, no atomics: bit-identical from run to run. */
+
+/* magnet_wgrad with other tap windows: taps 9 with dilation dil (>= 1), taps 4 = the space-to-depth 2x2 window (row offsets -wp-1,
+ * -wp, -1, 0; grad_w laid out as (Cout, cin_total, 2, 2)), or taps 1.  The rows summed are those whose every tap stays inside
+ * [0, rows); dy must be zero on the border rows, as for magnet_wgrad. */
+typedef struct MagnetWgradExArgs {
+    MagnetWgradArgs base;
+    int32_t         dil;
+    int32_t         reserved;
+} MagnetWgradExArgs;
+MAGNET_API int64_t magnet_wgrad_ex_workspace(const MagnetWgradExArgs *args);
+MAGNET_API int magnet_wgrad_ex(const MagnetWgradExArgs *args, void *stream);
+
+/* BatchNorm2d backward in training mode over the grid of magnet_bn_train_*: x the saved pre-BN activations, g the gradient of the
+ * layer's output (interior rows read).  relu: the output was ReLU'd; the mask is recomputed from x exactly as the apply did.
+ * dgamma = sum g' xhat, dbeta = sum g' (fp64 two-stage sums); dx = gamma invstd (g' - sum g' / n - xhat sum g' xhat / n) written as
+ * split bf16 over the whole grid (border rows zero). */
+typedef struct MagnetBnBwdArgs {
+    const float *x;
+    int64_t      x_ld;
+    int32_t      N, hp, wp, pad, C;
+    int32_t      relu;
+    const float *mean, *invstd, *gamma, *beta;
+    const float *g;
+    int64_t      g_ld;
+    double      *work;                     /* MAGNET_BN_BLOCKS * C * 2 + 2 * C doubles of scratch */
+    float       *dgamma, *dbeta;           /* (C) */
+    void        *dx_hi, *dx_lo;
+    int64_t      dx_ld;
+} MagnetBnBwdArgs;
+MAGNET_API int magnet_bn_train_backward(const MagnetBnBwdArgs *args, void *stream);
+
+/* (N, C, h, w) fp32 -> split bf16 planes of the zero-bordered grid (N, h+2pad, w+2pad, ld), channels [C, ld) and the border zero. */
+MAGNET_API int magnet_fnet_grad_pack(const float *nchw, void *out_hi, void *out_lo, int32_t N, int32_t C, int32_t h, int32_t w,
+                                     int32_t pad, int32_t ld, void *stream);
+/* Backward of magnet_space_to_depth: in fp32 (N, H4+2ipad, W4+2ipad, 4C) -> out fp32 interior of (N, H2+2, W2+2, C). */
+MAGNET_API int magnet_fnet_d2s_backward(const float *in, float *out, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t ipad,
+                                        void *stream);
+
+/* SPP backward.  magnet_spp_upsample_backward: gradient of the align_corners bilinear upsampling (ph x pw -> h x w), gathered per
+ * pooled cell in a fixed order: g (interior of the (N, h+2pad, w+2pad, g_ld) fp32 grid, channels [c_off, c_off + 32)) -> dq
+ * (N*ph*pw, 32).  magnet_spp_pool_backward: out (interior, 128 channels, out_ld) = g channels [c_off, c_off + 128) + sum over the
+ * four branches (k = 64, 32, 16, 8) of dpool[b][cell] / k^2 where the floor pooling covers the position. */
+typedef struct MagnetSppBwdArgs {
+    const float *g;
+    int64_t      g_ld;
+    int32_t      N, h, w, pad, c_off;
+    int32_t      ph, pw;
+    float       *dq;
+    const float *dpool[4];                 /* (N * (h/k) * (w/k), 128) for k = 64, 32, 16, 8 */
+    float       *out;
+    int64_t      out_ld;
+} MagnetSppBwdArgs;
+MAGNET_API int magnet_spp_upsample_backward(const MagnetSppBwdArgs *args, void *stream);
+MAGNET_API int magnet_spp_pool_backward(const MagnetSppBwdArgs *args, void *stream);
+
+/* Weight gradient of firstconv.0 (3 -> 32, 3x3 stride 2) from the NCHW fp32 image and dz (split bf16, (N, H2+2, W2+2, 32)):
+ * grad_w (32, 3, 3, 3).  work: MAGNET_BN_BLOCKS * 864 doubles. */
+MAGNET_API int magnet_fnet_stem_wgrad(const float *img, const void *dz_hi, const void *dz_lo, float *grad_w, double *work, int32_t N,
+                                      int32_t H, int32_t W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

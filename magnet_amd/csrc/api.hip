@@ -30,6 +30,17 @@ hipError_t launch_upsample_backward(const MagnetUpsampleBwdArgs&, hipStream_t);
 hipError_t launch_head_dgrad(const MagnetHeadDgradArgs&, hipStream_t);
 hipError_t launch_wgrad(const MagnetWgradArgs&, hipStream_t);
 long long wgrad_workspace_bytes(const MagnetWgradArgs&);
+hipError_t launch_fnet_stem_raw(const float*, const float*, float*, int, int, int, hipStream_t);
+hipError_t launch_bn_train_stats(const MagnetBnTrainArgs&, hipStream_t);
+hipError_t launch_bn_train_apply(const MagnetBnTrainArgs&, hipStream_t);
+hipError_t launch_wgrad_ex(const MagnetWgradExArgs&, hipStream_t);
+long long wgrad_ex_workspace_bytes(const MagnetWgradExArgs&);
+hipError_t launch_bn_train_backward(const MagnetBnBwdArgs&, hipStream_t);
+hipError_t launch_fnet_grad_pack(const float*, uint16_t*, uint16_t*, int, int, int, int, int, int, hipStream_t);
+hipError_t launch_fnet_d2s_backward(const float*, float*, int, int, int, int, int, hipStream_t);
+hipError_t launch_spp_upsample_backward(const MagnetSppBwdArgs&, hipStream_t);
+hipError_t launch_spp_pool_backward(const MagnetSppBwdArgs&, hipStream_t);
+hipError_t launch_fnet_stem_wgrad(const float*, const uint16_t*, const uint16_t*, float*, double*, int, int, int, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -566,6 +577,125 @@ MAGNET_API int magnet_wgrad(const MagnetWgradArgs* a, void* stream) {
     for (const void* p : al) if (!aligned16(p)) return fail(MAGNET_E_ALIGN, "magnet_wgrad: pointers not 16-byte aligned");
     hipError_t e = magnet::launch_wgrad(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_wgrad launch");
+}
+
+// ---- F-Net forward in training mode (train_fnet_fwd.hip) ----
+MAGNET_API int magnet_fnet_stem_raw(const float* img, const float* wgt, float* out, int32_t N, int32_t H, int32_t W, void* stream) {
+    if (!img || !wgt || !out) return fail(MAGNET_E_NULL, "magnet_fnet_stem_raw: NULL pointer");
+    if (N <= 0 || H < 2 || W < 2) return fail(MAGNET_E_DIM, "magnet_fnet_stem_raw: bad dims N=%d H=%d W=%d", N, H, W);
+    if (!aligned16(out)) return fail(MAGNET_E_ALIGN, "magnet_fnet_stem_raw: output must be 16-byte aligned");
+    hipError_t e = magnet::launch_fnet_stem_raw(img, wgt, out, N, H, W, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_stem_raw launch");
+}
+
+static int bn_train_check(const MagnetBnTrainArgs* a, const char* who) {
+    if (!a || !a->x || !a->mean || !a->invstd) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (a->N <= 0 || a->C <= 0 || a->C > 2048 || (a->C % 8) || a->pad < 0 || a->hp <= 2 * a->pad || a->wp <= 2 * a->pad || a->x_ld < a->C ||
+        (a->x_ld % 4) || (long long)a->N * (a->hp - 2 * a->pad) * (a->wp - 2 * a->pad) < 2)
+        return fail(MAGNET_E_DIM, "%s: bad dims (C a multiple of 8 up to 2048, x_ld >= C a multiple of 4, at least 2 positions)", who);
+    if (!aligned16(a->x)) return fail(MAGNET_E_ALIGN, "%s: x must be 16-byte aligned", who);
+    return 0;
+}
+
+MAGNET_API int magnet_bn_train_stats(const MagnetBnTrainArgs* a, void* stream) {
+    if (int rc = bn_train_check(a, "magnet_bn_train_stats")) return rc;
+    if (!a->work) return fail(MAGNET_E_NULL, "magnet_bn_train_stats: NULL workspace");
+    if (!(a->eps >= 0.0) || a->momentum > 1.0) return fail(MAGNET_E_DIM, "magnet_bn_train_stats: eps >= 0 and momentum <= 1 required");
+    hipError_t e = magnet::launch_bn_train_stats(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_bn_train_stats launch");
+}
+
+MAGNET_API int magnet_bn_train_apply(const MagnetBnTrainArgs* a, void* stream) {
+    if (int rc = bn_train_check(a, "magnet_bn_train_apply")) return rc;
+    if (!a->gamma || !a->beta || (!a->out_f32 && (!a->out_hi || !a->out_lo))) return fail(MAGNET_E_NULL, "magnet_bn_train_apply: NULL pointer");
+    if ((a->res_hi == nullptr) != (a->res_lo == nullptr)) return fail(MAGNET_E_NULL, "magnet_bn_train_apply: res_hi and res_lo come together");
+    if (a->out_ld < a->C || (a->out_f32 ? (a->out_ld % 4) : (a->out_ld % 8)) || (a->res_hi && (a->res_ld < a->C || (a->res_ld % 8))))
+        return fail(MAGNET_E_DIM, "magnet_bn_train_apply: out_ld / res_ld must be >= C and multiples of 8 (4 for fp32 output)");
+    const void* al[] = {a->out_f32, a->out_hi, a->out_lo, a->res_hi, a->res_lo};
+    for (const void* p : al) if (!aligned16(p)) return fail(MAGNET_E_ALIGN, "magnet_bn_train_apply: pointers not 16-byte aligned");
+    hipError_t e = magnet::launch_bn_train_apply(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_bn_train_apply launch");
+}
+
+// ---- F-Net backward in training mode (train_fnet_bwd.hip, train_bwd.hip) ----
+static int wgrad_ex_check(const MagnetWgradExArgs* e, const char* who) {
+    if (!e) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    const MagnetWgradArgs* a = &e->base;
+    if (!a->dy_hi || !a->dy_lo || !a->x_hi || !a->x_lo || !a->grad_w) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (a->cout <= 0 || a->cin <= 0 || (a->cout % 8) || (a->cin % 8) || (a->taps != 1 && a->taps != 4 && a->taps != 9) || a->wp < 3 ||
+        e->dil < 0 || e->dil > 8 || a->rows <= 0 || a->dy_ld < a->cout || a->x_ld < a->cin || (a->dy_ld % 8) || (a->x_ld % 8) ||
+        a->cout_valid <= 0 || a->cout_valid > a->cout || a->cin_valid <= 0 || a->cin_valid > a->cin || a->cin_dst < 0 ||
+        a->cin_dst + a->cin_valid > a->cin_total)
+        return fail(MAGNET_E_DIM, "%s: bad dims (cout, cin, ld multiples of 8; taps 1, 4 or 9; dil <= 8; valid ranges inside)", who);
+    return 0;
+}
+
+MAGNET_API int64_t magnet_wgrad_ex_workspace(const MagnetWgradExArgs* e) {
+    if (int rc = wgrad_ex_check(e, "magnet_wgrad_ex_workspace")) return -(int64_t)rc;
+    return magnet::wgrad_ex_workspace_bytes(*e);
+}
+
+MAGNET_API int magnet_wgrad_ex(const MagnetWgradExArgs* e, void* stream) {
+    if (int rc = wgrad_ex_check(e, "magnet_wgrad_ex")) return rc;
+    const MagnetWgradArgs* a = &e->base;
+    if (!a->work && magnet::wgrad_ex_workspace_bytes(*e) > 0) return fail(MAGNET_E_NULL, "magnet_wgrad_ex: NULL workspace");
+    const void* al[] = {a->dy_hi, a->dy_lo, a->x_hi, a->x_lo, a->work};
+    for (const void* p : al) if (!aligned16(p)) return fail(MAGNET_E_ALIGN, "magnet_wgrad_ex: pointers not 16-byte aligned");
+    hipError_t err = magnet::launch_wgrad_ex(*e, (hipStream_t)stream);
+    return err == hipSuccess ? 0 : hip_fail(err, "magnet_wgrad_ex launch");
+}
+
+MAGNET_API int magnet_bn_train_backward(const MagnetBnBwdArgs* a, void* stream) {
+    if (!a || !a->x || !a->mean || !a->invstd || !a->gamma || !a->beta || !a->g || !a->work || !a->dgamma || !a->dbeta || !a->dx_hi ||
+        !a->dx_lo)
+        return fail(MAGNET_E_NULL, "magnet_bn_train_backward: NULL pointer");
+    if (a->N <= 0 || a->C <= 0 || a->pad < 0 || a->hp <= 2 * a->pad || a->wp <= 2 * a->pad || a->x_ld < a->C || a->g_ld < a->C ||
+        a->dx_ld < a->C || (long long)a->N * (a->hp - 2 * a->pad) * (a->wp - 2 * a->pad) < 2)
+        return fail(MAGNET_E_DIM, "magnet_bn_train_backward: bad dims");
+    hipError_t e = magnet::launch_bn_train_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_bn_train_backward launch");
+}
+
+MAGNET_API int magnet_fnet_grad_pack(const float* nchw, void* out_hi, void* out_lo, int32_t N, int32_t C, int32_t h, int32_t w,
+                                     int32_t pad, int32_t ld, void* stream) {
+    if (!nchw || !out_hi || !out_lo) return fail(MAGNET_E_NULL, "magnet_fnet_grad_pack: NULL pointer");
+    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || pad < 0 || ld < C) return fail(MAGNET_E_DIM, "magnet_fnet_grad_pack: bad dims");
+    hipError_t e = magnet::launch_fnet_grad_pack(nchw, (uint16_t*)out_hi, (uint16_t*)out_lo, N, C, h, w, pad, ld, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_grad_pack launch");
+}
+
+MAGNET_API int magnet_fnet_d2s_backward(const float* in, float* out, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t ipad,
+                                        void* stream) {
+    if (!in || !out) return fail(MAGNET_E_NULL, "magnet_fnet_d2s_backward: NULL pointer");
+    if (N <= 0 || C <= 0 || H2 <= 0 || W2 <= 0 || ipad < 0) return fail(MAGNET_E_DIM, "magnet_fnet_d2s_backward: bad dims");
+    hipError_t e = magnet::launch_fnet_d2s_backward(in, out, N, C, H2, W2, ipad, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_d2s_backward launch");
+}
+
+MAGNET_API int magnet_spp_upsample_backward(const MagnetSppBwdArgs* a, void* stream) {
+    if (!a || !a->g || !a->dq) return fail(MAGNET_E_NULL, "magnet_spp_upsample_backward: NULL pointer");
+    if (a->N <= 0 || a->h <= 0 || a->w <= 0 || a->pad < 0 || a->ph <= 0 || a->pw <= 0 || a->c_off < 0 || a->g_ld < a->c_off + 32)
+        return fail(MAGNET_E_DIM, "magnet_spp_upsample_backward: bad dims");
+    hipError_t e = magnet::launch_spp_upsample_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_spp_upsample_backward launch");
+}
+
+MAGNET_API int magnet_spp_pool_backward(const MagnetSppBwdArgs* a, void* stream) {
+    if (!a || !a->g || !a->out || !a->dpool[0] || !a->dpool[1] || !a->dpool[2] || !a->dpool[3])
+        return fail(MAGNET_E_NULL, "magnet_spp_pool_backward: NULL pointer");
+    if (a->N <= 0 || a->h < 64 || a->w < 64 || a->pad < 0 || a->c_off < 0 || a->g_ld < a->c_off + 128 || a->out_ld < 128)
+        return fail(MAGNET_E_DIM, "magnet_spp_pool_backward: bad dims (h, w >= 64)");
+    hipError_t e = magnet::launch_spp_pool_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_spp_pool_backward launch");
+}
+
+MAGNET_API int magnet_fnet_stem_wgrad(const float* img, const void* dz_hi, const void* dz_lo, float* grad_w, double* work, int32_t N,
+                                      int32_t H, int32_t W, void* stream) {
+    if (!img || !dz_hi || !dz_lo || !grad_w || !work) return fail(MAGNET_E_NULL, "magnet_fnet_stem_wgrad: NULL pointer");
+    if (N <= 0 || H < 2 || W < 2) return fail(MAGNET_E_DIM, "magnet_fnet_stem_wgrad: bad dims");
+    hipError_t e = magnet::launch_fnet_stem_wgrad(img, (const uint16_t*)dz_hi, (const uint16_t*)dz_lo, grad_w, work, N, H, W,
+                                                  (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_stem_wgrad launch");
 }
 
 }  // extern "C"

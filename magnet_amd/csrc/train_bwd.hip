@@ -436,6 +436,7 @@ struct WgradP {
     int cout, cin, taps, wp, ntc, nto;
     long long p0, p1;           // summed rows [p0, p1)
     float* part;                // [chunk][tap][cout][cin]
+    long long toff[9];          // row offset of each tap
 };
 
 __device__ __forceinline__ int wg_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
@@ -463,7 +464,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradP a) {
     const int to = t % a.nto; t /= a.nto;
     const int tap = t;
     const int chunk = blockIdx.y;
-    const long long off = a.taps == 9 ? (long long)(tap / 3 - 1) * a.wp + (tap % 3 - 1) : 0;
+    const long long off = a.toff[tap];
     const int o0 = to * 64, c0 = tc * 64;
     const long long pb = a.p0 + (long long)chunk * WG_CHUNK;
     const long long pe = pb + WG_CHUNK < a.p1 ? pb + WG_CHUNK : a.p1;
@@ -581,7 +582,53 @@ long long wgrad_workspace_bytes(const MagnetWgradArgs& g) {
 hipError_t launch_wgrad(const MagnetWgradArgs& g, hipStream_t s) {
     const int nch = wgrad_chunks(g);
     WgradP a{(const uint16_t*)g.dy_hi, (const uint16_t*)g.dy_lo, (const uint16_t*)g.x_hi, (const uint16_t*)g.x_lo, g.dy_ld, g.x_ld,
-             g.cout, g.cin, g.taps, g.wp, (g.cin + 63) / 64, (g.cout + 63) / 64, (long long)g.wp + 1, g.rows - g.wp - 1, g.work};
+             g.cout, g.cin, g.taps, g.wp, (g.cin + 63) / 64, (g.cout + 63) / 64, (long long)g.wp + 1, g.rows - g.wp - 1, g.work, {}};
+    for (int t = 0; t < g.taps; ++t) a.toff[t] = g.taps == 9 ? (long long)(t / 3 - 1) * g.wp + (t % 3 - 1) : 0;
+    float* bpart = g.work + (size_t)nch * g.taps * g.cout * g.cin;
+    if (nch > 0) {
+        hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)(a.ntc * a.nto * g.taps), nch), dim3(256), 0, s, a);
+        if (g.grad_b) hipLaunchKernelGGL(wgrad_bias_kernel, dim3(nch, (g.cout + 15) / 16), dim3(256), 0, s, a, bpart);
+    }
+    const long long n = (long long)g.taps * g.cout_valid * g.cin_valid;
+    const long long nt = n > g.cout_valid ? n : g.cout_valid;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, a, nch, g, bpart);
+    return hipGetLastError();
+}
+
+// magnet_wgrad_ex: the same kernels with the tap offsets of a dilated 3x3 (taps 9, dil), of the space-to-depth 2x2 window
+// (taps 4: offsets -wp-1, -wp, -1, 0) or of a 1x1, summed over the rows [max(0, -min off), rows - max(0, max off)): every read stays
+// inside the grid, and dy is zero on the border rows the range leaves out
+static void wgrad_ex_range(const MagnetWgradExArgs& e, long long* toff, long long& p0, long long& p1) {
+    const MagnetWgradArgs& g = e.base;
+    const int d = e.dil > 1 ? e.dil : 1;
+    long long mn = 0, mx = 0;
+    for (int t = 0; t < g.taps; ++t) {
+        toff[t] = g.taps == 9 ? ((long long)(t / 3 - 1) * g.wp + (t % 3 - 1)) * d
+                : (g.taps == 4 ? (t == 0 ? -(long long)g.wp - 1 : (t == 1 ? -(long long)g.wp : (t == 2 ? -1 : 0))) : 0);
+        mn = toff[t] < mn ? toff[t] : mn;
+        mx = toff[t] > mx ? toff[t] : mx;
+    }
+    p0 = -mn;
+    p1 = g.rows - mx;
+}
+
+int wgrad_ex_chunks(const MagnetWgradExArgs& e) {
+    long long toff[9], p0, p1;
+    wgrad_ex_range(e, toff, p0, p1);
+    return p1 > p0 ? (int)((p1 - p0 + WG_CHUNK - 1) / WG_CHUNK) : 0;
+}
+
+long long wgrad_ex_workspace_bytes(const MagnetWgradExArgs& e) {
+    const long long nc = wgrad_ex_chunks(e);
+    return 4 * nc * ((long long)e.base.taps * e.base.cout * e.base.cin + e.base.cout);
+}
+
+hipError_t launch_wgrad_ex(const MagnetWgradExArgs& e, hipStream_t s) {
+    const MagnetWgradArgs& g = e.base;
+    const int nch = wgrad_ex_chunks(e);
+    WgradP a{(const uint16_t*)g.dy_hi, (const uint16_t*)g.dy_lo, (const uint16_t*)g.x_hi, (const uint16_t*)g.x_lo, g.dy_ld, g.x_ld,
+             g.cout, g.cin, g.taps, g.wp, (g.cin + 63) / 64, (g.cout + 63) / 64, 0, 0, g.work, {}};
+    wgrad_ex_range(e, a.toff, a.p0, a.p1);
     float* bpart = g.work + (size_t)nch * g.taps * g.cout * g.cin;
     if (nch > 0) {
         hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)(a.ntc * a.nto * g.taps), nch), dim3(256), 0, s, a);

@@ -863,3 +863,237 @@ def wgrad(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst=0
     a.work = work.data_ptr()
     with torch.cuda.device(gw.device):
         _check(lib.magnet_wgrad(ctypes.byref(a), _stream(gw)), "magnet_wgrad")
+
+
+# ---- F-Net forward in training mode (include/magnet_hip.h: magnet_fnet_stem_raw, magnet_bn_train_*; csrc/train_fnet_fwd.hip) ----
+API_SYMBOLS = API_SYMBOLS + ("magnet_fnet_stem_raw", "magnet_bn_train_stats", "magnet_bn_train_apply")
+BN_BLOCKS = 256
+
+
+class MagnetBnTrainArgs(ctypes.Structure):
+    """Mirror of `struct MagnetBnTrainArgs` (include/magnet_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_ld", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("hp", ctypes.c_int32), ("wp", ctypes.c_int32), ("pad", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("work", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p),
+                ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p), ("num_batches_tracked", ctypes.c_void_p),
+                ("eps", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("res_hi", ctypes.c_void_p), ("res_lo", ctypes.c_void_p), ("res_ld", ctypes.c_int64),
+                ("relu", ctypes.c_int32),
+                ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("out_f32", ctypes.c_void_p), ("out_ld", ctypes.c_int64)]
+
+
+def _bn_train_protos(lib):
+    if getattr(lib, "_bn_train_protos_done", False):
+        return lib
+    I, P = ctypes.c_int32, ctypes.c_void_p
+    lib.magnet_fnet_stem_raw.restype = ctypes.c_int
+    lib.magnet_fnet_stem_raw.argtypes = [P, P, P, I, I, I, P]
+    for name in ("magnet_bn_train_stats", "magnet_bn_train_apply"):
+        f = getattr(lib, name)
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.POINTER(MagnetBnTrainArgs), P]
+    lib._bn_train_protos_done = True
+    return lib
+
+
+def fnet_stem_raw(img, wgt, out):
+    """(N,3,H,W) fp32 image, wgt (32, 27) fp32 -> the interior of `out`, the fp32 (N*(H2+2)*(W2+2), 32) channel-last grid:
+    firstconv.0 without BatchNorm and ReLU."""
+    lib = _bn_train_protos(load())
+    x = _dev(img, "img", torch.float32)
+    N, C, H, W = x.shape
+    if C != 3:
+        raise MagnetError(f"fnet_stem_raw: expected 3 input channels, got {C}")
+    H2, W2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    o = _dev(out, "out", torch.float32)
+    if o.numel() < N * (H2 + 2) * (W2 + 2) * 32:
+        raise MagnetError("fnet_stem_raw: output grid too small")
+    with torch.cuda.device(x.device):
+        _check(lib.magnet_fnet_stem_raw(x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(), o.data_ptr(), N, H, W, _stream(x)),
+               "magnet_fnet_stem_raw")
+
+
+def bn_train(x, grid, mean, invstd, work, gamma, beta, eps, momentum, running_mean=None, running_var=None, num_batches_tracked=None,
+             res=None, relu=False, out=None, out_f32=None, stats=True):
+    """One BatchNorm2d in training mode (magnet_bn_train_stats, then magnet_bn_train_apply).  x: fp32 (rows, x_ld) grid
+    (possibly a channel-offset view), grid = (N, hp, wp, pad, C); res = (hi, lo) split residual views; out = (hi, lo) split
+    planes (channel-slice views allowed) or out_f32 an fp32 (rows, ld) tensor.  momentum None: cumulative average."""
+    lib = _bn_train_protos(load())
+    N, hp, wp, pad, C = (int(v) for v in grid)
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] < C:
+        raise MagnetError("bn_train: x must be a (rows, >= C) float32 GPU tensor with unit channel stride")
+    a = MagnetBnTrainArgs(x=x.data_ptr(), x_ld=x.stride(0), N=N, hp=hp, wp=wp, pad=pad, C=C,
+                          work=_dev(work, "work", torch.float64).data_ptr(), mean=_dev(mean, "mean", torch.float32).data_ptr(),
+                          invstd=_dev(invstd, "invstd", torch.float32).data_ptr(), eps=float(eps),
+                          momentum=-1.0 if momentum is None else float(momentum),
+                          gamma=_dev(gamma, "gamma", torch.float32).data_ptr(), beta=_dev(beta, "beta", torch.float32).data_ptr(),
+                          relu=int(bool(relu)))
+    if work.numel() < BN_BLOCKS * C * 2:
+        raise MagnetError("bn_train: workspace too small")
+    for t, n in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            setattr(a, n, _dev(t, n, torch.float32).data_ptr())
+    if num_batches_tracked is not None:
+        a.num_batches_tracked = _dev(num_batches_tracked, "num_batches_tracked", torch.int64).data_ptr()
+    if res is not None:
+        a.res_hi, a.res_lo, a.res_ld = _bf16_ptr(res[0], "res_hi"), _bf16_ptr(res[1], "res_lo"), res[0].stride(0)
+    if out_f32 is not None:
+        a.out_f32, a.out_ld = _dev(out_f32, "out_f32", torch.float32).data_ptr(), out_f32.stride(0)
+    elif out is not None:
+        a.out_hi, a.out_lo, a.out_ld = _bf16_ptr(out[0], "out_hi"), _bf16_ptr(out[1], "out_lo"), out[0].stride(0)
+    rows = N * hp * wp
+    if x.shape[0] < rows or (out_f32 is not None and out_f32.shape[0] < rows) or (out is not None and out[0].shape[0] < rows) or \
+            (res is not None and res[0].shape[0] < rows):
+        raise MagnetError(f"bn_train: a buffer holds fewer than the grid's {rows} rows")
+    with torch.cuda.device(x.device):
+        if stats:
+            _check(lib.magnet_bn_train_stats(ctypes.byref(a), _stream(x)), "magnet_bn_train_stats")
+        if out is not None or out_f32 is not None:
+            _check(lib.magnet_bn_train_apply(ctypes.byref(a), _stream(x)), "magnet_bn_train_apply")
+
+
+# ---- F-Net backward in training mode (include/magnet_hip.h; csrc/train_fnet_bwd.hip, csrc/train_bwd.hip) ----
+API_SYMBOLS = API_SYMBOLS + ("magnet_wgrad_ex_workspace", "magnet_wgrad_ex", "magnet_bn_train_backward", "magnet_fnet_grad_pack",
+                             "magnet_fnet_d2s_backward", "magnet_spp_upsample_backward", "magnet_spp_pool_backward",
+                             "magnet_fnet_stem_wgrad")
+
+
+class MagnetWgradExArgs(ctypes.Structure):
+    """Mirror of `struct MagnetWgradExArgs` (include/magnet_hip.h)."""
+    _fields_ = [("base", MagnetWgradArgs), ("dil", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MagnetBnBwdArgs(ctypes.Structure):
+    """Mirror of `struct MagnetBnBwdArgs` (include/magnet_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_ld", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("hp", ctypes.c_int32), ("wp", ctypes.c_int32), ("pad", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("relu", ctypes.c_int32),
+                ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("g", ctypes.c_void_p), ("g_ld", ctypes.c_int64), ("work", ctypes.c_void_p),
+                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p),
+                ("dx_hi", ctypes.c_void_p), ("dx_lo", ctypes.c_void_p), ("dx_ld", ctypes.c_int64)]
+
+
+class MagnetSppBwdArgs(ctypes.Structure):
+    """Mirror of `struct MagnetSppBwdArgs` (include/magnet_hip.h)."""
+    _fields_ = [("g", ctypes.c_void_p), ("g_ld", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("pad", ctypes.c_int32), ("c_off", ctypes.c_int32),
+                ("ph", ctypes.c_int32), ("pw", ctypes.c_int32),
+                ("dq", ctypes.c_void_p), ("dpool", ctypes.c_void_p * 4), ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int64)]
+
+
+def _fnet_bwd_protos(lib):
+    if getattr(lib, "_fnet_bwd_protos_done", False):
+        return lib
+    I, P = ctypes.c_int32, ctypes.c_void_p
+    lib.magnet_wgrad_ex_workspace.restype = ctypes.c_int64
+    lib.magnet_wgrad_ex_workspace.argtypes = [ctypes.POINTER(MagnetWgradExArgs)]
+    for name, st in (("magnet_wgrad_ex", MagnetWgradExArgs), ("magnet_bn_train_backward", MagnetBnBwdArgs),
+                     ("magnet_spp_upsample_backward", MagnetSppBwdArgs), ("magnet_spp_pool_backward", MagnetSppBwdArgs)):
+        f = getattr(lib, name)
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.POINTER(st), P]
+    lib.magnet_fnet_grad_pack.restype = ctypes.c_int
+    lib.magnet_fnet_grad_pack.argtypes = [P, P, P, I, I, I, I, I, I, P]
+    lib.magnet_fnet_d2s_backward.restype = ctypes.c_int
+    lib.magnet_fnet_d2s_backward.argtypes = [P, P, I, I, I, I, I, P]
+    lib.magnet_fnet_stem_wgrad.restype = ctypes.c_int
+    lib.magnet_fnet_stem_wgrad.argtypes = [P, P, P, P, P, I, I, I, P]
+    lib._fnet_bwd_protos_done = True
+    return lib
+
+
+def wgrad_ex(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, dil=1, cin_dst=0, cout_valid=None, cin_valid=None):
+    """magnet_wgrad with dilation (taps 9), the space-to-depth 2x2 window (taps 4, grad_w (Cout, Cin, 2, 2)) or taps 1."""
+    lib = _fnet_bwd_protos(_train_protos(load()))
+    for t, nme in ((dy_hi, "dy_hi"), (dy_lo, "dy_lo"), (x_hi, "x_hi"), (x_lo, "x_lo")):
+        _bf16_ptr(t, nme)
+    gw = _dev(grad_w, "grad_w", torch.float32)
+    for t, n in ((dy_hi, "dy"), (x_hi, "x")):
+        if t.shape[0] < rows:
+            raise MagnetError(f"wgrad_ex: {n} holds fewer than {rows} rows")
+    a = MagnetWgradExArgs()
+    b = a.base
+    b.dy_hi, b.dy_lo, b.x_hi, b.x_lo = dy_hi.data_ptr(), dy_lo.data_ptr(), x_hi.data_ptr(), x_lo.data_ptr()
+    b.dy_ld, b.x_ld, b.rows, b.cout, b.cin, b.taps, b.wp = dy_hi.stride(0), x_hi.stride(0), int(rows), int(cout), int(cin), int(taps), int(wp)
+    b.grad_w = gw.data_ptr()
+    b.cout_valid, b.cin_valid = int(cout if cout_valid is None else cout_valid), int(cin if cin_valid is None else cin_valid)
+    b.cin_total, b.cin_dst = gw.shape[1], int(cin_dst)
+    a.base = b
+    a.dil = int(dil)
+    nbytes = lib.magnet_wgrad_ex_workspace(ctypes.byref(a))
+    if nbytes < 0:
+        _check(int(-nbytes), "magnet_wgrad_ex_workspace")
+    work = torch.empty(max(int(nbytes) // 4, 4), dtype=torch.float32, device=gw.device)
+    a.base.work = work.data_ptr()
+    with torch.cuda.device(gw.device):
+        _check(lib.magnet_wgrad_ex(ctypes.byref(a), _stream(gw)), "magnet_wgrad_ex")
+
+
+def bn_train_backward(x, grid, mean, invstd, gamma, beta, relu, g, dgamma, dbeta, dx, work):
+    """BatchNorm2d backward (batch statistics).  x: the saved fp32 pre-BN grid; g: fp32 gradient grid (views allowed, unit channel
+    stride); dx = (hi, lo) split planes written over the whole grid."""
+    lib = _fnet_bwd_protos(load())
+    N, hp, wp, pad, C = (int(v) for v in grid)
+    rows = N * hp * wp
+    for t, n in ((x, "x"), (g, "g")):
+        if not t.is_cuda or t.dtype != torch.float32 or t.stride(1) != 1 or t.shape[0] < rows or t.shape[1] < C:
+            raise MagnetError(f"bn_train_backward: {n} must be a (>= {rows}, >= {C}) float32 GPU tensor with unit channel stride")
+    if dx[0].shape[0] < rows or work.numel() < (BN_BLOCKS * 2 + 2) * C:
+        raise MagnetError("bn_train_backward: dx or the workspace too small")
+    a = MagnetBnBwdArgs(x=x.data_ptr(), x_ld=x.stride(0), N=N, hp=hp, wp=wp, pad=pad, C=C, relu=int(bool(relu)),
+                        mean=_dev(mean, "mean", torch.float32).data_ptr(), invstd=_dev(invstd, "invstd", torch.float32).data_ptr(),
+                        gamma=_dev(gamma, "gamma", torch.float32).data_ptr(), beta=_dev(beta, "beta", torch.float32).data_ptr(),
+                        g=g.data_ptr(), g_ld=g.stride(0), work=_dev(work, "work", torch.float64).data_ptr(),
+                        dgamma=_dev(dgamma, "dgamma", torch.float32).data_ptr(), dbeta=_dev(dbeta, "dbeta", torch.float32).data_ptr(),
+                        dx_hi=_bf16_ptr(dx[0], "dx_hi"), dx_lo=_bf16_ptr(dx[1], "dx_lo"), dx_ld=dx[0].stride(0))
+    with torch.cuda.device(x.device):
+        _check(lib.magnet_bn_train_backward(ctypes.byref(a), _stream(x)), "magnet_bn_train_backward")
+
+
+def fnet_grad_pack(g_nchw, out_hi, out_lo, pad):
+    lib = _fnet_bwd_protos(load())
+    g = _dev(g_nchw, "grad", torch.float32)
+    N, C, h, w = g.shape
+    ld = out_hi.shape[1]
+    if out_hi.shape[0] < N * (h + 2 * pad) * (w + 2 * pad) or not out_hi.is_contiguous() or out_lo.shape != out_hi.shape:
+        raise MagnetError("fnet_grad_pack: output planes too small")
+    with torch.cuda.device(g.device):
+        _check(lib.magnet_fnet_grad_pack(g.data_ptr(), _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo"), N, C, h, w, int(pad),
+                                         int(ld), _stream(g)), "magnet_fnet_grad_pack")
+
+
+def fnet_d2s_backward(g_s, out, N, C, H2, W2, ipad):
+    lib = _fnet_bwd_protos(load())
+    with torch.cuda.device(g_s.device):
+        _check(lib.magnet_fnet_d2s_backward(_dev(g_s, "in", torch.float32).data_ptr(), _dev(out, "out", torch.float32).data_ptr(),
+                                            N, C, H2, W2, ipad, _stream(g_s)), "magnet_fnet_d2s_backward")
+
+
+def spp_upsample_backward(g, c_off, N, h, w, pad, ph, pw, dq):
+    lib = _fnet_bwd_protos(load())
+    a = MagnetSppBwdArgs(g=_dev(g, "g", torch.float32).data_ptr(), g_ld=g.stride(0), N=N, h=h, w=w, pad=pad, c_off=c_off, ph=ph, pw=pw,
+                         dq=_dev(dq, "dq", torch.float32).data_ptr())
+    with torch.cuda.device(g.device):
+        _check(lib.magnet_spp_upsample_backward(ctypes.byref(a), _stream(g)), "magnet_spp_upsample_backward")
+
+
+def spp_pool_backward(g, c_off, N, h, w, pad, dpools, out):
+    lib = _fnet_bwd_protos(load())
+    a = MagnetSppBwdArgs(g=_dev(g, "g", torch.float32).data_ptr(), g_ld=g.stride(0), N=N, h=h, w=w, pad=pad, c_off=c_off,
+                         out=_dev(out, "out", torch.float32).data_ptr(), out_ld=out.stride(0))
+    for i, d in enumerate(dpools):
+        a.dpool[i] = _dev(d, "dpool", torch.float32).data_ptr()
+    with torch.cuda.device(g.device):
+        _check(lib.magnet_spp_pool_backward(ctypes.byref(a), _stream(g)), "magnet_spp_pool_backward")
+
+
+def fnet_stem_wgrad(img, dz, grad_w, work):
+    lib = _fnet_bwd_protos(load())
+    x = _dev(img, "img", torch.float32)
+    N, _, H, W = x.shape
+    with torch.cuda.device(x.device):
+        _check(lib.magnet_fnet_stem_wgrad(x.data_ptr(), _bf16_ptr(dz[0], "dz_hi"), _bf16_ptr(dz[1], "dz_lo"),
+                                          _dev(grad_w, "grad_w", torch.float32).data_ptr(), _dev(work, "work", torch.float64).data_ptr(),
+                                          N, H, W, _stream(x)), "magnet_fnet_stem_wgrad")

@@ -371,16 +371,45 @@ class MAGNET(nn.Module):
 class MAGNET_F(nn.Module):
     """Mirror of the reference's F-Net training wrapper (models/MAGNET.py:179-202): F-Net features of the reference
     and source images -> est_costvolume_F (softmax over D fixed depth bins of the view-averaged feature correlation).
-    The volume and its gradient w.r.t. the features run in hand-written HIP (magnet_amd.homography.est_costvolume_F);
-    `f_net` is the caller's module (the reference's FNET; backbones are out of scope here) and trains through it."""
+    The volume and its gradient w.r.t. the features run in hand-written HIP (magnet_amd.homography.est_costvolume_F).
 
-    def __init__(self, args, f_net: nn.Module):
+    `f_net`: None builds this package's state_dict-compatible FNET(args), as the reference's constructor does; a module
+    (e.g. the reference's own FNET) is used as given.
+    `train_backend`: how the F-Net runs.  'torch' (default): the module's own forward (nn.Conv2d / BatchNorm2d), under
+    autograd.  'hip': in .eval() mode the matrix-core inference path (FNetMFMA, BatchNorm folded); in .train() mode the HIP
+    training-mode forward (magnet_amd/train_fnet.py: batch statistics, running statistics updated on the device); with grad
+    enabled, the features' grad_fn is the HIP F-Net backward and every F-Net parameter receives its .grad."""
+
+    def __init__(self, args, f_net: nn.Module | None = None, train_backend: str = "torch"):
         super().__init__()
+        if train_backend not in ("torch", "hip"):
+            raise lib.MagnetError(f"train_backend must be 'torch' or 'hip', got {train_backend!r}")
+        if f_net is None:
+            from .fnet import FNET
+            f_net = FNET(args)
         self.f_net = f_net
+        self.train_backend = train_backend
+        self._hip_runners = None
+
+    def _features_hip(self, imgs):
+        psm = getattr(self.f_net, "f_net", self.f_net)
+        if not all(hasattr(psm, a) for a in ("firstconv", "layer1", "layer2", "layer3", "layer4", "branch1", "lastconv")):
+            raise lib.MagnetError("train_backend='hip' needs a PSMNet-structured F-Net (firstconv, layer1..4, branch1..4, lastconv)")
+        if self._hip_runners is None or self._hip_runners[0] is not psm:
+            from .fnet import FNetMFMA
+            from .train_fnet import FNetTrainHIP
+            self._hip_runners = (psm, FNetMFMA(psm), FNetTrainHIP(psm))
+        if not psm.training:
+            return self._hip_runners[1].run(imgs)
+        if torch.is_grad_enabled() and (imgs.requires_grad or any(p.requires_grad for p in psm.parameters())):
+            from .train_fnet import fnet_train_hip
+            return fnet_train_hip(self._hip_runners[2], imgs)
+        return self._hip_runners[2].run(imgs)
 
     def forward(self, ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, d_center):
         B = ref_img.shape[0]
-        feat_4 = self.f_net(torch.cat((ref_img, nghbr_imgs), dim=0))            # MAGNET.py:188
+        imgs = torch.cat((ref_img, nghbr_imgs), dim=0)
+        feat_4 = self._features_hip(imgs) if self.train_backend == "hip" else self.f_net(imgs)   # MAGNET.py:188
         ref_feat_4, nghbr_feat_4 = feat_4[:B], feat_4[B:]
         Rs_src = nghbr_poses[:, :, :3, :3]                                       # MAGNET.py:193-194
         ts_src = nghbr_poses[:, :, :3, 3]

@@ -1,0 +1,94 @@
+"""Timing of one MAGNET_F training step of train_FNet.py (lines 69-119): the F-Net on the B(1+V) images in .train() mode, est_costvolume_F,
+the L1 loss on the expected depth, and the backward, for train_backend 'torch' (nn.Conv2d / BatchNorm2d under autograd) and 'hip'
+(magnet_amd/train_fnet.py), at 480 x 640, V = 4, D = 80, F = 64, B = 1 (the ScanNet config per GPU) and B = 4 (the driver's default).
+Also times the no-grad training-mode forward.  Prints one JSON line: ms_per_train_step and ms_per_train_forward per backend and batch,
+and the time per kernel of the HIP step (torch.profiler) at B = 4.
+
+    python tools/bench_train_fnet.py [--steps 10] [--warmup 3]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    from magnet_amd import fnet, lib, synth
+    from magnet_amd.magnet import MAGNET_F
+    from magnet_amd.train_fnet import FNetTrainHIP
+    lib.load()
+    dev = torch.device("cuda:0")
+    V, H, W, F, D = 4, 480, 640, 64, 80
+    args = SimpleNamespace(FNET_architecture="PSM-Net", FNET_feature_dim=F)
+    torch.manual_seed(0)
+    base = fnet.FNET(args).train()
+    d_center = torch.linspace(0.25, 8.0, D).view(1, -1, 1, 1)
+    res = {"config": dict(V=V, H=H, W=W, F=F, D=D), "steps": a.steps, "warmup": a.warmup, "ms_per_train_step": {},
+           "ms_per_train_forward": {}}
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            fn()
+        torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) * 1e3 / a.steps, 3)
+
+    for B in (1, 4):
+        gen = torch.Generator().manual_seed(B)
+        ref_img = torch.rand(B, 3, H, W, generator=gen).to(dev)
+        nb = torch.rand(V * B, 3, H, W, generator=gen).to(dev)
+        poses = synth.make_poses("scannet", B, V, gen).to(dev)
+        valid = torch.ones(B, V, dtype=torch.int32, device=dev)
+        cam = {k: v.to(dev) for k, v in synth.make_intrinsics("scannet", H // 4, W // 4, B).items()}
+        gt = (1.0 + 3.0 * torch.rand(B, 1, H // 4, W // 4, generator=gen)).to(dev)
+        for backend in ("torch", "hip"):
+            m = MAGNET_F(args, copy.deepcopy(base), train_backend=backend).to(dev).train()
+
+            def step():
+                m.zero_grad(set_to_none=True)
+                cv = m(ref_img, nb, poses, valid, cam, d_center)
+                pred = torch.sum(cv * d_center.to(dev), dim=1, keepdim=True)
+                mask = gt > 0.5
+                torch.mean(torch.abs(pred[mask] - gt[mask])).backward()
+
+            res["ms_per_train_step"][f"{backend}_B{B}"] = timed(step)
+            imgs = torch.cat((ref_img, nb))
+            psm = m.f_net.f_net
+            fwd = psm if backend == "torch" else FNetTrainHIP(psm).run
+            with torch.no_grad():
+                res["ms_per_train_forward"][f"{backend}_B{B}"] = timed(lambda: fwd(imgs))
+            if backend == "hip" and B == 4:
+                from torch.profiler import ProfilerActivity, profile
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    step()
+                    torch.cuda.synchronize()
+                per = {}
+                for e in prof.key_averages():
+                    if e.device_type == torch.autograd.DeviceType.CUDA:
+                        t = getattr(e, "device_time_total", None)
+                        if t is None:
+                            t = e.cuda_time_total
+                        per[e.key[:80]] = round(per.get(e.key[:80], 0.0) + t / 1e3, 3)
+                res["hip_step_kernels_ms_B4"] = dict(sorted(per.items(), key=lambda kv: -kv[1])[:16])
+            del m, fwd, psm
+            torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
