@@ -543,6 +543,31 @@ MAGNET_API int magnet_spp_pool_backward(const MagnetSppBwdArgs *args, void *stre
 MAGNET_API int magnet_fnet_stem_wgrad(const float *img, const void *dz_hi, const void *dz_lo, float *grad_w, double *work, int32_t N,
                                       int32_t H, int32_t W, void *stream);
 
+/* ---- the D-Net decoder (DenseDepth_BN at downsample ratio 4, models/submodules/D_dense_depth.py:104-195; magnet_amd/dnet.py) ----
+ * Its convolutions run on magnet_conv_mfma's kernel with BatchNorm folded into weights and bias; the bilinear upsampling and the skip
+ * concatenation on magnet_upsample_bilinear_cl / magnet_pack_split. */
+
+enum {                                     /* MagnetConvExArgs.act */
+    MAGNET_ACT_BASE       = 0,             /* as magnet_conv_mfma: base.relu decides */
+    MAGNET_ACT_LEAKY_RELU = 1              /* LeakyReLU(act_slope) after bias / addend / residual (UpSampleBN._net, D_dense_depth.py:29-43):
+                                              x < 0 -> x * act_slope.  Needs base.relu == 0 and no fused tail; every other output form
+                                              (bf16 planes, fp32, single bf16 plane, channel slices, zero border, repad) applies it */
+};
+
+/* magnet_conv_mfma with an activation mode.  act = MAGNET_ACT_BASE gives exactly magnet_conv_mfma(&args->base). */
+typedef struct MagnetConvExArgs {
+    MagnetConvArgs base;
+    int32_t        act;                    /* MAGNET_ACT_* */
+    float          act_slope;              /* negative slope of MAGNET_ACT_LEAKY_RELU (nn.LeakyReLU(): 0.01); finite */
+} MagnetConvExArgs;
+MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
+
+/* The D-Net's Gaussian activation behind its depth head (activation_G_magnet, models/DNET.py:62-67): from the head's fp32 output
+ * `in` (rows, in_ld) over zero-bordered (N, h+2*pad, w+2*pad) grids (channel 0 = mu, channel 1 = v; border rows are not read)
+ * -> out (N, 2, h, w) fp32 = [mu, sqrt(elu(v) + 1 + 1e-10)].  in_ld even, `in` 8-byte aligned. */
+MAGNET_API int magnet_dnet_gauss_head(const float *in, int32_t in_ld, int32_t N, int32_t h, int32_t w, int32_t pad, float *out,
+                                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

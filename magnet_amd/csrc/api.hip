@@ -41,6 +41,7 @@ hipError_t launch_fnet_d2s_backward(const float*, float*, int, int, int, int, in
 hipError_t launch_spp_upsample_backward(const MagnetSppBwdArgs&, hipStream_t);
 hipError_t launch_spp_pool_backward(const MagnetSppBwdArgs&, hipStream_t);
 hipError_t launch_fnet_stem_wgrad(const float*, const uint16_t*, const uint16_t*, float*, double*, int, int, int, hipStream_t);
+hipError_t launch_dnet_gauss_head(const float*, int, int, int, int, int, float*, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -287,7 +288,8 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_upsample_depth launch");
 }
 
-MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) {
+// magnet_conv_mfma and magnet_conv_mfma_ex: leaky != 0 selects LeakyReLU(leaky_slope) after bias (validated by the _ex entry point)
+static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
     if (!a->in_hi || !a->in_lo || !a->w_hi || !a->w_lo || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
     if (a->out_mode < 0 || a->out_mode > 2) return fail(MAGNET_E_DIM, "magnet_conv_mfma: out_mode must be 0, 1 or 2");
@@ -376,11 +378,36 @@ MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) {
                         (long long)a->rows, a->wp);
         p.gu_in = a->gu_in; p.gu_out = a->gu_out; p.up_B = a->up_B; p.up_h = a->up_h; p.up_w = a->up_w;
     }
+    p.leaky = leaky; p.leaky_slope = leaky_slope;
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
     hipError_t e = magnet::launch_conv_mfma(p, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv_mfma launch");
+}
+
+MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) { return conv_mfma_run(a, 0, 0.f, stream); }
+
+MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
+    if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_ex: args is NULL");
+    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: act=%d unknown", a->act);
+    if (a->act == MAGNET_ACT_LEAKY_RELU) {
+        if (a->base.relu || a->base.tail_w_hi) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: LeakyReLU excludes relu and the fused tail");
+        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
+            return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: act_slope must be finite");
+    }
+    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, stream);
+}
+
+MAGNET_API int magnet_dnet_gauss_head(const float* in, int32_t in_ld, int32_t N, int32_t h, int32_t w, int32_t pad, float* out,
+                                      void* stream) {
+    if (!in || !out) return fail(MAGNET_E_NULL, "magnet_dnet_gauss_head: NULL pointer");
+    if (N <= 0 || h <= 0 || w <= 0 || pad < 0 || in_ld < 2 || (in_ld % 2) != 0)
+        return fail(MAGNET_E_DIM, "magnet_dnet_gauss_head: bad dims N=%d h=%d w=%d pad=%d in_ld=%d (in_ld even, >= 2)", N, h, w, pad, in_ld);
+    if ((reinterpret_cast<uintptr_t>(in) & 7u) || (reinterpret_cast<uintptr_t>(out) & 3u))
+        return fail(MAGNET_E_ALIGN, "magnet_dnet_gauss_head: `in` must be 8-byte aligned");
+    hipError_t e = magnet::launch_dnet_gauss_head(in, in_ld, N, h, w, pad, out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_gauss_head launch");
 }
 
 MAGNET_API int magnet_fnet_stem(const float* img, const float* wgt, const float* bias, void* out_hi, void* out_lo, int32_t N,

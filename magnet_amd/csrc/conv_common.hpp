@@ -45,6 +45,10 @@ struct ConvParams {
     // its E8M0 exponent: in_sc [cin / 32][sc_rows] u32 {E8M0 of the hi block, E8M0 of the lo block, 0, 0}, w_sc [taps][cin / 32][cout_pad] u32
     const uint32_t* in_sc; const uint32_t* w_sc;
     long long sc_rows;                                // rows of one chunk plane of in_sc (>= rows)
+    // LeakyReLU (magnet_conv_mfma_ex; the D-Net decoder, D_dense_depth.py:29-43): leaky != 0 and relu == 0 -> negative outputs are
+    // multiplied by leaky_slope after bias / addend.  Plain epilogue only (not with the fused tail)
+    int leaky;
+    float leaky_slope;
 };
 
 struct ChainParams {

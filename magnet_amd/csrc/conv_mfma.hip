@@ -1779,7 +1779,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 float x = (stage[r * SROW + c8 + i] + ad[i]) + (BIAS_INV ? bv[i] : p.bias[ch + i]);
-                v[i] = (p.relu && x < 0.f) ? 0.f : x;
+                v[i] = (x < 0.f) ? (p.relu ? 0.f : (p.leaky ? x * p.leaky_slope : x)) : x;
                 if (!interior) v[i] = 0.f;
             }
             const size_t e = (size_t)orow * p.out_ld + ch;

@@ -1,0 +1,402 @@
+"""D-Net (MaGNet's single-view depth network): the DenseDepth_BN decoder of the reference at downsample ratio 4
+(models/DNET.py, models/submodules/D_dense_depth.py:28-43,104-195) — by arithmetic the largest block of end-to-end inference
+(about 228 GFLOP per 480x640 image).
+
+Three things live here:
+
+* `DenseDepthDecoder` / `DNET`: plain nn.Modules with the reference's architecture and **state_dict keys** (`conv2.*`,
+  `up1._net.{0,1,3,4}.*`, ..., `depth_head.{0,2,4}.*`, `mask_head.{0,2,4}.*`; `d_net.encoder.*` / `d_net.decoder.*` under DNET), so a
+  reference D-Net checkpoint loads unchanged.  The encoder (EfficientNet-B5 through torch.hub in the reference) is the caller's module:
+  anything that maps images to the reference's feature list (the decoder reads indices 5, 6, 8 and 11).
+* `seeded_decoder_state`: a deterministic numpy weight recipe per state_dict key (He-normal convolutions, non-trivial BatchNorm
+  statistics) shared by the golden generator (tests/golden/make_golden_dnet.py), the tests and the benchmark.
+* `DNetMFMA`: the decoder's inference path on MI355X.  BatchNorm (eval) is folded into the convolutions in fp64 on the host; every
+  convolution runs on the bf16x3 matrix-core kernel (fp32-grade) with LeakyReLU in its epilogue (magnet_conv_mfma_ex); activations are
+  zero-bordered channel-last split-bf16 planes; the bilinear upsampling and the skip features land in channel slices of the next
+  block's input (magnet_upsample_bilinear_cl, magnet_pack_split); the depth head runs as one fused launch and the Gaussian activation
+  behind it is csrc/dnet_kernels.hip.  `run(..., x_d3_out=...)` writes the reference frames' x_feat straight into MAGNET's G-Net input
+  buffer (interior rows, zero border, a channel slice): no NCHW x_d3, no repack.
+"""
+from __future__ import annotations
+
+import zlib
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import lib
+from .convnet import ConvStackMFMA, split_bf16
+
+# (block, skip feature index, skip channels, output channels) at downsample ratio 4 (D_dense_depth.py:130-135,176-180)
+_UP = (("up1", 8, 176, 1024), ("up2", 6, 64, 512), ("up3", 5, 40, 256))
+_SKIP_IN = 11                                              # x_block4: 2048 channels at 1/32 (the input of conv2)
+
+
+def _round_up(x, m):
+    return (x + m - 1) // m * m
+
+
+class UpSampleBN(nn.Module):
+    """Bilinear (align_corners=True) to the skip tensor's size, concatenate [up, skip], then twice conv3x3-BN-LeakyReLU
+    (D_dense_depth.py:28-43)."""
+
+    def __init__(self, skip_input, output_features):
+        super().__init__()
+        self._net = nn.Sequential(nn.Conv2d(skip_input, output_features, 3, padding=1), nn.BatchNorm2d(output_features), nn.LeakyReLU(),
+                                  nn.Conv2d(output_features, output_features, 3, padding=1), nn.BatchNorm2d(output_features),
+                                  nn.LeakyReLU())
+
+    def forward(self, x, concat_with):
+        up = F.interpolate(x, size=[concat_with.size(2), concat_with.size(3)], mode="bilinear", align_corners=True)
+        return self._net(torch.cat([up, concat_with], dim=1))
+
+
+def _head(cin, h_dim, cout):
+    return nn.Sequential(nn.Conv2d(cin, h_dim, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(h_dim, h_dim, 1), nn.ReLU(inplace=True),
+                         nn.Conv2d(h_dim, cout, 1))
+
+
+def upsample_depth_via_mask(depth, up_mask, k):
+    """Learned convex upsampling of the stand-alone D-Net (D_dense_depth.py:72-88)."""
+    N, C, H, W = depth.shape
+    wgt = torch.softmax(up_mask.reshape(N, 1, 9, k, k, H, W), dim=2)
+    patch = F.unfold(depth, [3, 3], padding=1).reshape(N, C, 9, 1, 1, H, W)
+    return (wgt * patch).sum(dim=2).permute(0, 1, 4, 2, 5, 3).reshape(N, C, k * H, k * W)
+
+
+class DenseDepthDecoder(nn.Module):
+    """The reference's `Decoder(num_classes, downsample_ratio=4, learned_upsampling=True, BN=True, dnet)`.
+    dnet=False (MaGNet): forward(features) -> (depth head output (N, num_classes, H/4, W/4), x_feat (N, 256, H/4, W/4));
+    dnet=True (stand-alone D-Net): the depth upsampled x4 through the learned mask head."""
+
+    def __init__(self, num_classes=2, downsample_ratio=4, dnet=False):
+        super().__init__()
+        if downsample_ratio != 4:
+            raise lib.MagnetError(f"DenseDepthDecoder: downsample_ratio {downsample_ratio} is not built (MaGNet uses 4)")
+        features = 2048
+        self.downsample_ratio = downsample_ratio
+        self.dnet = dnet
+        self.conv2 = nn.Conv2d(features, features, 1)
+        self.up1 = UpSampleBN(features + 176, features // 2)
+        self.up2 = UpSampleBN(features // 2 + 64, features // 4)
+        self.up3 = UpSampleBN(features // 4 + 40, features // 8)
+        self.depth_head = _head(features // 8, 128, num_classes)
+        self.mask_head = _head(features // 8, 128, 9 * downsample_ratio * downsample_ratio)
+
+    def forward(self, features):
+        x_d0 = self.conv2(features[_SKIP_IN])
+        x_d1 = self.up1(x_d0, features[8])
+        x_d2 = self.up2(x_d1, features[6])
+        x_feat = self.up3(x_d2, features[5])
+        depth = self.depth_head(x_feat)
+        if self.dnet:
+            return upsample_depth_via_mask(depth, self.mask_head(x_feat), self.downsample_ratio)
+        return depth, x_feat
+
+
+class DenseDepth(nn.Module):
+    """encoder (the caller's module: img -> feature list) + DenseDepthDecoder (D_dense_depth.py:198-213)."""
+
+    def __init__(self, encoder, num_classes=2, downsample_ratio=4, dnet=False):
+        super().__init__()
+        self.encoder = encoder
+        self.decoder = DenseDepthDecoder(num_classes, downsample_ratio, dnet)
+
+    def forward(self, x):
+        return self.decoder(self.encoder(x))
+
+
+def gaussian_activation(out, magnet=True):
+    """activation_G_magnet (models/DNET.py:62-67; magnet=True): (mu, sigma = sqrt(elu(v) + 1 + 1e-10)) of the head output, x_feat
+    passed through.  magnet=False: activation_G (DNET.py:55-60), the stand-alone D-Net's (mu, variance)."""
+    if not magnet:
+        mu, var = torch.split(out, 1, dim=1)
+        return torch.cat([mu, F.elu(var) + 1.0 + 1e-10], dim=1)
+    mu, var = torch.split(out[0], 1, dim=1)
+    var = F.elu(var) + 1.0 + 1e-10
+    return torch.cat([mu, torch.sqrt(var)], dim=1), out[1]
+
+
+class DNET(nn.Module):
+    """models/DNET.py with output_type 'G' and DNET_architecture 'DenseDepth_BN': `DNET(args, encoder, dnet=False)` is MaGNet's
+    D-Net, img -> ((N, 2, H/4, W/4) [mu, sigma], x_feat (N, 256, H/4, W/4)).  `encoder`: any module returning the reference's feature
+    list (EfficientNet-B5's, or magnet_amd.standin.StandinEncoder)."""
+
+    def __init__(self, args, encoder: nn.Module, dnet: bool = False):
+        super().__init__()
+        self.args = args
+        if getattr(args, "output_type", "G") != "G":
+            raise lib.MagnetError(f"DNET: output_type {args.output_type!r} is not built (MaGNet uses 'G')")
+        if getattr(args, "DNET_architecture", "DenseDepth_BN") != "DenseDepth_BN":
+            raise lib.MagnetError(f"DNET: architecture {args.DNET_architecture!r} is not built (the BatchNorm decoder 'DenseDepth_BN' is)")
+        self.dnet = dnet
+        self.d_net = DenseDepth(encoder, getattr(args, "output_dim", 2), args.downsample_ratio, dnet)
+
+    def forward(self, img):
+        return gaussian_activation(self.d_net(img), magnet=not self.dnet)
+
+
+def seeded_decoder_state(keys_shapes: dict, seed=0):
+    """Deterministic weights for a decoder state_dict: {key: np.float64 array}.  `keys_shapes`: {key: shape}, e.g.
+    {k: tuple(v.shape) for k, v in decoder.state_dict().items()}.  Each key draws from its own generator (seeded by the key's CRC32
+    and `seed`), so the recipe does not depend on key order.  Convolutions He-normal over fan-in with N(0, 0.05^2) biases; BatchNorm
+    gamma U(0.6, 1.4), beta N(0, 0.1^2), running mean N(0, 0.2^2), running variance U(0.5, 2): activations neither vanish nor blow up."""
+    out = {}
+    for key, shape in keys_shapes.items():
+        shape = tuple(shape)
+        rng = np.random.default_rng([zlib.crc32(key.encode()), int(seed)])
+        stem, leaf = key.rsplit(".", 1)
+        is_bn = stem + ".running_mean" in keys_shapes
+        if leaf == "num_batches_tracked":
+            out[key] = np.zeros(shape)
+        elif len(shape) == 4:                                              # convolution weight
+            out[key] = rng.standard_normal(shape) * np.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+        elif leaf == "running_mean":
+            out[key] = rng.standard_normal(shape) * 0.2
+        elif leaf == "running_var":
+            out[key] = rng.uniform(0.5, 2.0, shape)
+        elif leaf == "weight" and is_bn:
+            out[key] = rng.uniform(0.6, 1.4, shape)
+        elif leaf == "bias":
+            out[key] = rng.standard_normal(shape) * (0.1 if is_bn else 0.05)
+        else:
+            raise lib.MagnetError(f"seeded_decoder_state: no rule for {key}")
+    return out
+
+
+def load_seeded_decoder(decoder: nn.Module, seed=0):
+    """Fill `decoder` (ours or the reference's Decoder) with seeded_decoder_state."""
+    sd = decoder.state_dict()
+    vals = seeded_decoder_state({k: tuple(v.shape) for k, v in sd.items()}, seed)
+    decoder.load_state_dict({k: torch.from_numpy(vals[k]).to(sd[k].dtype) for k in sd})
+    return decoder
+
+
+# ======================================================================================================
+# inference on the matrix cores
+# ======================================================================================================
+def fold_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
+    """Conv2d (with bias) followed by eval-mode BatchNorm2d -> (weight, bias) in fp64: w * s, (b - mean) * s + beta, s = gamma / sqrt(var + eps)."""
+    w = conv.weight.detach().double()
+    b = conv.bias.detach().double() if conv.bias is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
+    s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    return w * s.view(-1, 1, 1, 1), (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
+
+
+def check_decoder(decoder: nn.Module):
+    """MagnetError unless `decoder` is the reference's BatchNorm decoder at downsample ratio 4 (ours or the reference's class)."""
+    if getattr(decoder, "downsample_ratio", None) != 4 or not all(hasattr(decoder, a) for a in ("conv2", "up1", "up2", "up3", "depth_head")):
+        raise lib.MagnetError("the HIP D-Net runs the DenseDepth decoder at downsample_ratio 4 (conv2, up1..up3, depth_head)")
+    for name, _, _, _ in _UP:
+        net = getattr(decoder, name)._net
+        if not (isinstance(net[1], nn.BatchNorm2d) and isinstance(net[4], nn.BatchNorm2d) and isinstance(net[2], nn.LeakyReLU)
+                and isinstance(net[5], nn.LeakyReLU)):
+            raise lib.MagnetError(f"the HIP D-Net runs the BatchNorm decoder (DenseDepth_BN); {name} is not conv-BN-LeakyReLU")
+        if type(net[0]) is not nn.Conv2d or type(net[3]) is not nn.Conv2d:
+            raise lib.MagnetError(f"the HIP D-Net needs plain nn.Conv2d layers ({name} has weight-standardised convolutions)")
+    dh = decoder.depth_head
+    if len(dh) != 5 or dh[4].out_channels != 2:
+        raise lib.MagnetError("the HIP D-Net needs the 2-output depth head (output_dim 2, output_type 'G')")
+
+
+def _planes(rows, c, dev):
+    return (torch.zeros((rows, c), dtype=torch.bfloat16, device=dev), torch.zeros((rows, c), dtype=torch.bfloat16, device=dev))
+
+
+class DNetMFMA:
+    """Inference runner for a DenseDepth_BN decoder at downsample ratio 4 (ours or the reference's `Decoder`), eval mode."""
+
+    # every convolution launch appends (start_event, end_event, flops) when set to a list (tools/bench_dnet.py)
+    event_sink = None
+
+    def __init__(self, decoder: nn.Module):
+        check_decoder(decoder)
+        self.decoder = decoder
+        self.slope = float(decoder.up1._net[2].negative_slope)
+        dh = decoder.depth_head
+        # the depth head (3x3 256->128 ReLU, 1x1 128->128 ReLU, 1x1 128->2) on the stack runner's fused epilogue, which has two hidden
+        # 1x1 layers: the second is the identity (its input is non-negative, so the ReLU behind it changes nothing)
+        eye = nn.Conv2d(128, 128, 1)
+        with torch.no_grad():
+            eye.weight.copy_(torch.eye(128).view(128, 128, 1, 1)); eye.bias.zero_()
+        self._head = ConvStackMFMA(nn.Sequential(dh[0], nn.ReLU(), dh[2], nn.ReLU(), eye, nn.ReLU(), dh[4]))
+        self._packed = None
+        self._key = None
+        self._bufs = {}
+        self._bufs_sig = None
+        self._head_work = {}
+
+    def _params_key(self, device):
+        d = self.decoder
+        return tuple((t.data_ptr(), t._version) for t in list(d.parameters()) + list(d.buffers())) + (str(device),)
+
+    @torch.no_grad()
+    def packed(self, device):
+        key = self._params_key(device)
+        if self._packed is not None and self._key == key:
+            return self._packed
+        d = self.decoder
+        P = {}
+
+        def put(name, w, b, cin_pad):
+            cout, cin, kh, kw = w.shape
+            wp = torch.zeros((kh * kw, cout, cin_pad), dtype=torch.float64, device=w.device)
+            wp[:, :, :cin] = w.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin)
+            hi, lo = split_bf16(wp.float().to(device))
+            P[name] = (hi, lo, b.float().to(device).contiguous(), kh * kw, cin_pad)
+
+        put("conv2", d.conv2.weight.detach().double(), d.conv2.bias.detach().double(), 2048)
+        cin = 2048
+        for name, _, skip_c, cout in _UP:
+            net = getattr(d, name)._net
+            put(name + ".0", *fold_bn(net[0], net[1]), _round_up(cin + skip_c, 32))
+            put(name + ".1", *fold_bn(net[3], net[4]), cout)
+            cin = cout
+        self._packed, self._key = P, key
+        return P
+
+    def _conv(self, name, src, in_ld, wp, rows, dst=None, out_f32=None, out_ld=0, border=None, repad=0):
+        hi, lo, bias, taps, cin = self._packed[name]
+        cout = hi.shape[1]
+        # every operand must hold what the launch touches (planes may be row / channel views of wider buffers)
+        for t in src:
+            if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) != in_ld or t.shape[0] < rows or t.shape[1] < cin:
+                raise lib.MagnetError(f"DNetMFMA {name}: input view {tuple(t.shape)} / pitch {t.stride(0)} does not hold {rows} x {cin} at {in_ld}")
+        ld = out_ld or cout
+        n_out = rows if not repad else rows // (border[0] * wp) * (border[0] - 2) * (wp - 2)
+        for t in (dst if dst is not None else (out_f32,)):
+            if t.dim() == 2:
+                ok = t.stride(1) == 1 and t.stride(0) == ld and t.shape[0] >= n_out and t.shape[1] >= cout
+            else:
+                ok = t.is_contiguous() and ld == cout and t.numel() >= n_out * ld
+            if not ok:
+                raise lib.MagnetError(f"DNetMFMA {name}: output {tuple(t.shape)} does not hold {n_out} rows of {cout} at pitch {ld}")
+        sink = DNetMFMA.event_sink
+        if sink is not None:
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, False, rows,
+                      out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1], out_f32=out_f32, out_ld=out_ld,
+                      border=border, repad=repad, leaky=None if name == "conv2" else self.slope)
+        if sink is not None:
+            e1.record()
+            sink.append((e0, e1, 2.0 * rows * cin * taps * hi.shape[1]))
+
+    def _buffers(self, dev, N, dims):
+        sig = (str(dev), N, dims)
+        if self._bufs_sig == sig:
+            return self._bufs
+        self._bufs.clear()                                          # one shape at a time: the buffers are large
+        self._head_work.clear()
+        self._bufs_sig = sig
+        (h32, w32), (h16, w16), (h8, w8), (h4, w4) = dims
+        r = lambda h, w: N * (h + 2) * (w + 2)
+        b = self._bufs
+        b["x4"] = _planes(r(h32, w32), 2048, dev)
+        b["d0"] = torch.empty((N * h32 * w32, 2048), dtype=torch.float32, device=dev)
+        cin = 2048
+        for (name, _, skip_c, cout), (h, w) in zip(_UP, ((h16, w16), (h8, w8), (h4, w4))):
+            b[name + ".in"] = _planes(r(h, w), _round_up(cin + skip_c, 32), dev)     # [upsampled | skip | zero pad], zero border
+            b[name + ".mid"] = _planes(r(h, w), cout, dev)
+            if name != "up3":
+                b[name + ".out"] = torch.empty((N * h * w, cout), dtype=torch.float32, device=dev)
+            cin = cout
+        b["feat"] = _planes(r(h4, w4), 256, dev)
+        return b
+
+    @torch.no_grad()
+    def run(self, features, n_ref=None, x_d3_out=None):
+        """features: the encoder's list (indices 5, 6, 8, 11 are read; NCHW fp32 on the GPU).
+        x_d3_out = (hi, lo, ctot, c_off) with n_ref = B: x_feat of images [0, B) is written into channels [c_off, c_off + 256) of
+        the split-bf16 zero-bordered (B*(h+2)*(w+2), ctot) buffer (MAGNET.gnet_input_buffer), border rows zero; returns
+        (ref_gmms (B,2,h,w), nghbr_gmms (N-B,2,h,w)).  Without x_d3_out: returns (mono_gmms (N,2,h,w), x_feat (N,256,h,w)) NCHW fp32,
+        as the reference's DNET(dnet=False)."""
+        if self.decoder.training:
+            raise lib.MagnetError("DNetMFMA folds BatchNorm running statistics: call .eval() on the D-Net first")
+        xs = {}
+        for i, c in ((_SKIP_IN, 2048),) + tuple((idx, sc) for _, idx, sc, _ in _UP):
+            t = features[i]
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != c:
+                raise lib.MagnetError(f"DNetMFMA: features[{i}] must be (N, {c}, h, w), got "
+                                      f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if not t.is_cuda:
+                raise lib.MagnetError("DNetMFMA: features must be on the GPU (no CPU fallback)")
+            xs[i] = t.detach().float().contiguous()
+        N = xs[_SKIP_IN].shape[0]
+        if any(t.shape[0] != N for t in xs.values()):
+            raise lib.MagnetError("DNetMFMA: the feature maps disagree on the batch size")
+        dims = tuple(tuple(xs[i].shape[2:]) for i in (_SKIP_IN, 8, 6, 5))
+        (h32, w32), _, _, (h4, w4) = dims
+        dev = xs[_SKIP_IN].device
+        if x_d3_out is not None:
+            if n_ref is None or not (1 <= int(n_ref) <= N):
+                raise lib.MagnetError(f"DNetMFMA: x_d3_out needs n_ref in [1, {N}] (the reference images lead the batch)")
+            n_ref = int(n_ref)
+            ghi, glo, g_ld, c_off = x_d3_out
+            rows_ref = n_ref * (h4 + 2) * (w4 + 2)
+            if any(t.dtype != torch.bfloat16 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (rows_ref, g_ld) for t in (ghi, glo)) \
+                    or c_off % 8 or c_off < 0 or c_off + 256 > g_ld:
+                raise lib.MagnetError(f"DNetMFMA: x_d3_out must be ({rows_ref}, ctot) planes with 256 channels at c_off (multiple of 8)")
+        elif n_ref is not None:
+            raise lib.MagnetError("DNetMFMA: n_ref goes with x_d3_out (without it run() returns the NCHW (mono_gmms, x_feat))")
+        P = self.packed(dev)
+        b = self._buffers(dev, N, dims)
+
+        # conv2 (1x1 2048 -> 2048, no activation; D_dense_depth.py:177) -> compact fp32 for the bilinear upsampling
+        lib.pack_split(xs[_SKIP_IN], b["x4"][0], b["x4"][1], 2048, 0)
+        wp = w32 + 2
+        self._conv("conv2", b["x4"], 2048, wp, N * (h32 + 2) * wp, out_f32=b["d0"], border=(h32 + 2, 1), repad=1)
+        prev, ph, pw, pc = b["d0"], h32, w32, 2048
+        for name, idx, skip_c, cout in _UP:                          # up1..up3 (D_dense_depth.py:178-180)
+            h, w = xs[idx].shape[2:]
+            wp, rows = w + 2, N * (h + 2) * (w + 2)
+            cat = b[name + ".in"]
+            cat_ld = cat[0].shape[1]
+            lib.upsample_bilinear_cl(prev, pc, ph, pw, pc, cat[0], cat[1], cat_ld, N, h, w, 1)     # channels [0, pc)
+            lib.pack_split(xs[idx], cat[0], cat[1], cat_ld, pc)                                    # channels [pc, pc + skip_c)
+            self._conv(name + ".0", cat, cat_ld, wp, rows, dst=b[name + ".mid"], border=(h + 2, 1))
+            if name != "up3":
+                self._conv(name + ".1", b[name + ".mid"], cout, wp, rows, out_f32=b[name + ".out"], border=(h + 2, 1), repad=1)
+                prev, ph, pw, pc = b[name + ".out"], h, w, cout
+        # up3's second convolution is x_feat: the reference frames' rows straight into the G-Net buffer, the others into `feat`
+        h, w, wp = h4, w4, w4 + 2
+        img_rows = (h + 2) * wp
+        mid = b["up3.mid"]
+        mono = torch.empty((N, 2, h, w), dtype=torch.float32, device=dev)
+        parts = []                                                   # (first image, images, planes, row pitch)
+        if x_d3_out is not None:
+            dst = (ghi[:, c_off:], glo[:, c_off:])
+            self._conv("up3.1", mid, 256, wp, n_ref * img_rows, dst=dst, out_ld=g_ld, border=(h + 2, 1))
+            parts.append((0, n_ref, dst, g_ld))
+        else:
+            n_ref = 0
+        if N > n_ref:
+            src = (mid[0][n_ref * img_rows:], mid[1][n_ref * img_rows:])
+            dst = (b["feat"][0][n_ref * img_rows:], b["feat"][1][n_ref * img_rows:])
+            self._conv("up3.1", src, 256, wp, (N - n_ref) * img_rows, dst=dst, border=(h + 2, 1))
+            parts.append((n_ref, N - n_ref, dst, 256))
+        # depth head (3x3 + 1x1 + 1x1, one launch) and the Gaussian activation (DNET.py:62-67)
+        for first, n, (fhi, flo), ld in parts:
+            if any(t.stride(0) != ld or t.shape[0] < n * img_rows or t.shape[1] < 256 for t in (fhi, flo)):
+                raise lib.MagnetError(f"DNetMFMA: depth-head input view {tuple(fhi.shape)} does not hold {n * img_rows} x 256 at pitch {ld}")
+            work = self._head_work.setdefault(n, {})
+            sink = DNetMFMA.event_sink
+            if sink is not None:
+                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+            out, out_ld = self._head.run(fhi, flo, ld, n * img_rows, wp, work)
+            if sink is not None:
+                e1.record()
+                sink.append((e0, e1, 2.0 * n * img_rows * (9 * 256 * 128 + 128 * 128 + 128 * 2)))
+            lib.dnet_gauss_head(out, out_ld, n, h, w, 1, mono[first:first + n])
+        if x_d3_out is not None:
+            return mono[:n_ref], mono[n_ref:]
+        x_feat = torch.empty((N, h, w, 256), dtype=torch.float32, device=dev)
+        self._conv("up3.1", mid, 256, wp, N * img_rows, out_f32=x_feat, border=(h + 2, 1), repad=1)
+        return mono, x_feat.permute(0, 3, 1, 2).contiguous()
+
+    def __call__(self, features):
+        """(mono_gmms (N,2,h,w), x_feat (N,256,h,w)) NCHW fp32: what the reference's DNET(dnet=False) returns for these features."""
+        return self.run(features)

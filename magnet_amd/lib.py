@@ -437,7 +437,7 @@ def _bf16_ptr(t, name):
 
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
-              mx=None):
+              mx=None, leaky=None):
     """One convolution layer on the matrix cores.  in_hi/in_lo: bf16 tensors whose data_ptr is row 0 (possibly a
     channel-offset view of a wider buffer, `in_ld` = its row pitch in elements); weights (taps, cout_pad, cin) bf16.
     F-Net extras (include/magnet_hip.h): dil (3x3 dilation), out_ld (write a channel slice: out tensors may then be
@@ -447,7 +447,8 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     upsample = (depths (n,B,2,h,w) fp32, outs (n,B,2,4h,4w) fp32): with tail cout_pad 144, the learned convex upsampling runs in
     the tail's last layer (models/MAGNET.py:15-27) and only `outs` is written.
     gauss = (gmm_in (B,2,h,w), gmm_out): with tail cout_pad 16 (G-Net's head) the Gaussian update of models/MAGNET.py:60-69 runs
-    in the tail's last layer and only `gmm_out` is written."""
+    in the tail's last layer and only `gmm_out` is written.
+    leaky = slope: LeakyReLU(slope) after bias instead of ReLU (magnet_conv_mfma_ex; relu must be False, no tail)."""
     lib = _conv_protos(load())
     a = MagnetConvArgs()
     if mx is not None:
@@ -504,7 +505,11 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
     with torch.cuda.device(in_hi.device):
-        _check(lib.magnet_conv_mfma(ctypes.byref(a), _stream(in_hi)), "magnet_conv_mfma")
+        if leaky is None:
+            _check(lib.magnet_conv_mfma(ctypes.byref(a), _stream(in_hi)), "magnet_conv_mfma")
+        else:
+            x = MagnetConvExArgs(base=a, act=ACT_LEAKY_RELU, act_slope=float(leaky))
+            _check(_dnet_protos(lib).magnet_conv_mfma_ex(ctypes.byref(x), _stream(in_hi)), "magnet_conv_mfma_ex")
 
 
 def pack_split(x_nchw, out_hi, out_lo, ctot, c_off):
@@ -1097,3 +1102,38 @@ def fnet_stem_wgrad(img, dz, grad_w, work):
         _check(lib.magnet_fnet_stem_wgrad(x.data_ptr(), _bf16_ptr(dz[0], "dz_hi"), _bf16_ptr(dz[1], "dz_lo"),
                                           _dev(grad_w, "grad_w", torch.float32).data_ptr(), _dev(work, "work", torch.float64).data_ptr(),
                                           N, H, W, _stream(x)), "magnet_fnet_stem_wgrad")
+
+
+# ---- the D-Net decoder (include/magnet_hip.h: magnet_conv_mfma_ex, magnet_dnet_gauss_head; csrc/dnet_kernels.hip) ----------------
+API_SYMBOLS = API_SYMBOLS + ("magnet_conv_mfma_ex", "magnet_dnet_gauss_head")
+ACT_BASE, ACT_LEAKY_RELU = 0, 1
+
+
+class MagnetConvExArgs(ctypes.Structure):
+    """Mirror of `struct MagnetConvExArgs` (include/magnet_hip.h)."""
+    _fields_ = [("base", MagnetConvArgs), ("act", ctypes.c_int32), ("act_slope", ctypes.c_float)]
+
+
+def _dnet_protos(lib):
+    if getattr(lib, "_dnet_protos_done", False):
+        return lib
+    I, P = ctypes.c_int32, ctypes.c_void_p
+    lib.magnet_conv_mfma_ex.restype = ctypes.c_int
+    lib.magnet_conv_mfma_ex.argtypes = [ctypes.POINTER(MagnetConvExArgs), P]
+    lib.magnet_dnet_gauss_head.restype = ctypes.c_int
+    lib.magnet_dnet_gauss_head.argtypes = [P, I, I, I, I, I, P, P]
+    lib._dnet_protos_done = True
+    return lib
+
+
+def dnet_gauss_head(head_out, ld, N, h, w, pad, out):
+    """Depth-head fp32 output (rows >= N*(h+2pad)*(w+2pad), ld) -> out (N,2,h,w) = [mu, sqrt(elu(v) + 1 + 1e-10)] (DNET.py:62-67)."""
+    lib = _dnet_protos(load())
+    x = _dev(head_out, "head_out", torch.float32)
+    if x.dim() != 2 or x.stride(1) != 1 or x.stride(0) != ld or x.shape[0] < N * (h + 2 * pad) * (w + 2 * pad) or x.shape[1] < 2:
+        raise MagnetError(f"dnet_gauss_head: head output {tuple(x.shape)} does not hold {N} ({h}+2*{pad}) x ({w}+2*{pad}) grids of pitch {ld}")
+    o = _dev(out, "out", torch.float32)
+    if tuple(o.shape) != (N, 2, h, w) or not o.is_contiguous():
+        raise MagnetError(f"dnet_gauss_head: out must be a contiguous ({N}, 2, {h}, {w}) tensor")
+    with torch.cuda.device(x.device):
+        _check(lib.magnet_dnet_gauss_head(x.data_ptr(), int(ld), N, h, w, pad, o.data_ptr(), _stream(x)), "magnet_dnet_gauss_head")

@@ -7,7 +7,9 @@ What runs where (inference, conv_backend='mfma'):
   * G-Net / mask-head convolutions                              -> HIP matrix-core kernel (lib.conv_mfma, bf16x3 split)
   * Gaussian update tail, convex upsampling                     -> HIP kernels (lib.gaussian_update*/upsample_depth*)
   * a PSMNet-structured F-Net                                   -> HIP matrix-core path (magnet_amd/fnet.py)
-  * D-Net                                                       -> caller-provided module (out of scope)
+  * D-Net                                                       -> caller-provided module; with dnet_backend='hip' its encoder runs
+                                                                   as given and the DenseDepth_BN decoder on the matrix-core path
+                                                                   (magnet_amd/dnet.py), writing x_d3 into G-Net's input buffer
 Under autograd (mode='train' with trainable g_net / mask_head), train_backend='torch' (the default) evaluates the convolutions,
 the Gaussian update and the convex upsampling as torch ops, so gradients reach g_net and mask_head exactly as in the reference
 (train_MaGNet.py:87-98).  train_backend='hip' runs the same step on HIP (magnet_amd/train.py): the heads layer by layer on the
@@ -107,10 +109,14 @@ class MAGNET(nn.Module):
     `train_backend`: the path under autograd (mode='train' with trainable g_net / mask_head).  'torch' (default): nn.Conv2d and torch
     ops, autograd's own backward.  'hip': the heads on the bf16x3 matrix-core kernel, backward in hand-written HIP (magnet_amd/train.py,
     csrc/train_bwd.hip); gradients land in the nn.Conv2d parameters' .grad, deterministic bit for bit.  Needs the reference's heads
-    (downsample_ratio 4, 256-channel x_d3)."""
+    (downsample_ratio 4, 256-channel x_d3).
+    `dnet_backend`: 'torch' (default) calls d_net as a module.  'hip' needs a D-Net with `.d_net.encoder` and `.d_net.decoder` (the
+    reference's DNET or magnet_amd.dnet.DNET, DenseDepth_BN at downsample ratio 4, Gaussian output): the encoder runs as given, the
+    decoder on the matrix-core path (magnet_amd.dnet.DNetMFMA), which writes the reference frames' x_d3 straight into
+    gnet_input_buffer(); needs conv_backend='mfma'.  While d_net is in training mode its own forward runs (batch-statistic BatchNorm)."""
 
     def __init__(self, args, d_net: nn.Module | None = None, f_net: nn.Module | None = None,
-                 feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch"):
+                 feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch", dnet_backend: str = "torch"):
         super().__init__()
         self.args = args
         if d_net is None or f_net is None:
@@ -156,6 +162,26 @@ class MAGNET(nn.Module):
         if train_backend not in ("torch", "hip"):
             raise lib.MagnetError(f"train_backend must be 'torch' or 'hip', got {train_backend!r}")
         self.train_backend = train_backend
+        if dnet_backend not in ("torch", "hip"):
+            raise lib.MagnetError(f"dnet_backend must be 'torch' or 'hip', got {dnet_backend!r}")
+        self.dnet_backend = dnet_backend
+        self._dnet = None
+        if dnet_backend == "hip":
+            if conv_backend != "mfma":
+                raise lib.MagnetError("dnet_backend='hip' runs the D-Net decoder on the matrix-core path: it needs conv_backend='mfma'")
+            if args.downsample_ratio != 4:
+                raise lib.MagnetError(f"dnet_backend='hip' runs the decoder at downsample_ratio 4, got {args.downsample_ratio}")
+            inner = getattr(d_net, "d_net", None)
+            if not isinstance(getattr(inner, "encoder", None), nn.Module) or not isinstance(getattr(inner, "decoder", None), nn.Module):
+                raise lib.MagnetError("dnet_backend='hip' needs a D-Net with .d_net.encoder and .d_net.decoder (the reference's DNET or "
+                                      "magnet_amd.dnet.DNET)")
+            act = getattr(d_net, "activation", None)
+            if act is not None and getattr(act, "__name__", "") != "activation_G_magnet":
+                raise lib.MagnetError("dnet_backend='hip' needs MaGNet's D-Net output (output_type 'G', dnet=False: activation_G_magnet)")
+            if getattr(d_net, "dnet", False):
+                raise lib.MagnetError("dnet_backend='hip' needs the D-Net built with dnet=False (mean, sigma and x_feat at 1/4)")
+            from .dnet import DNetMFMA
+            self._dnet = DNetMFMA(inner.decoder)          # checks the decoder: BatchNorm, LeakyReLU, 2-output head
         self._work = {}                # cached device workspaces of the MFMA conv path, keyed by shape
         self.fuse_upsample = True      # the stacks' tails finish the job: G-Net's head applies the Gaussian update, the mask head
                                        # writes the upsampled predictions itself (no (B,144,h,w) mask in HBM); False: separate launches
@@ -332,23 +358,40 @@ class MAGNET(nn.Module):
 
     def forward(self, ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, mode="train"):
         B = ref_img.shape[0]
+        heads_training = torch.is_grad_enabled() and any(p.requires_grad for p in
+                                                         list(self.g_net.parameters()) + list(self.mask_head.parameters()))
+        in_place = False
         with torch.no_grad():
-            mono_gmms, x_d3 = self.d_net(torch.cat((ref_img, nghbr_imgs), dim=0))        # MAGNET.py:135
-            mono_gmms = mono_gmms.detach()
-            ref_gmms = mono_gmms[:B, ...]
-            x_d3 = x_d3[:B, ...]
-            nghbr_gmms = mono_gmms[B:, ...]
+            imgs = torch.cat((ref_img, nghbr_imgs), dim=0)
+            if self.dnet_backend == "hip" and not self.d_net.training:
+                # encoder as given, decoder on the matrix cores (magnet_amd/dnet.py).  At inference its last layer writes the reference
+                # frames' x_d3 into the G-Net input buffer in place (no NCHW x_d3, no pack); a training step of the heads takes x_d3 as
+                # a tensor
+                feats = self.d_net.d_net.encoder(imgs)
+                if not heads_training:
+                    h, w = feats[5].shape[2:]
+                    ref_gmms, nghbr_gmms = self._dnet.run(feats, n_ref=B, x_d3_out=self.gnet_input_buffer(B, h, w, imgs.device))
+                    x_d3, in_place = None, True
+                else:
+                    mono_gmms, x_d3 = self._dnet(feats)
+                    ref_gmms, x_d3, nghbr_gmms = mono_gmms[:B], x_d3[:B], mono_gmms[B:]
+            else:
+                mono_gmms, x_d3 = self.d_net(imgs)                                        # MAGNET.py:135
+                mono_gmms = mono_gmms.detach()
+                ref_gmms = mono_gmms[:B, ...]
+                x_d3 = x_d3[:B, ...]
+                nghbr_gmms = mono_gmms[B:, ...]
             runner = self._fnet_runner()
             if runner is not None and ref_img.is_cuda:
                 # F-Net on the matrix cores; its last layer writes the matcher's layouts (no NCHW features, no pack)
-                packed = runner.run(torch.cat((ref_img, nghbr_imgs), dim=0), n_ref=B, feat_dtype=self.feat_dtype)
+                packed = runner.run(imgs, n_ref=B, feat_dtype=self.feat_dtype)
                 return self.match_and_refine(ref_gmms, x_d3, None, None, nghbr_gmms, nghbr_poses, is_valid, cam_intrins,
-                                             mode, packed_feats=packed)
-            feat_4 = self.f_net(torch.cat((ref_img, nghbr_imgs), dim=0))                 # MAGNET.py:142
+                                             mode, packed_feats=packed, x_d3_in_place=in_place)
+            feat_4 = self.f_net(imgs)                                                     # MAGNET.py:142
             ref_feat_4 = feat_4[:B, ...]
             nghbr_feat_4 = feat_4[B:, ...]
         return self.match_and_refine(ref_gmms, x_d3, ref_feat_4, nghbr_feat_4, nghbr_gmms, nghbr_poses,
-                                     is_valid, cam_intrins, mode)
+                                     is_valid, cam_intrins, mode, x_d3_in_place=in_place)
 
     def _side_stream(self, dev):
         st = self._side.get(str(dev))

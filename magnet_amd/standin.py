@@ -65,3 +65,52 @@ def seeded_magnet_weights(model, seed=0, gain=1.0):
             for name, p in sorted(mod.state_dict().items()):
                 scale = 0.05 if p.dim() > 1 else 0.01
                 p.copy_(torch.randn(p.shape, generator=g) * (scale * gain))
+
+
+class StandinEncoder(nn.Module):
+    """A cheap seeded stand-in for the D-Net's EfficientNet-B5 encoder (reference: models/submodules/D_dense_depth.py:7-25): img
+    (N,3,H,W) -> the reference's 12-entry feature list with B5's shapes where the decoder reads: [4] 24 channels at 1/2, [5] 40 at 1/4,
+    [6] 64 at 1/8, [8] 176 at 1/16, [11] 2048 at 1/32 (each stride-2 stage rounds up, as B5's 'same' padding does).  Each map is a
+    seeded 3x3 convolution of the average-pooled image followed by SiLU; entry 0 is the image, the entries no decoder reads are None."""
+
+    STAGES = ((4, 1, 24), (5, 2, 40), (6, 3, 64), (8, 4, 176), (11, 5, 2048))      # (index, number of 2x poolings, channels)
+
+    def __init__(self, seed=0):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+        self.convs = nn.ModuleList(nn.Conv2d(3, c, 3, padding=1) for _, _, c in self.STAGES)
+        with torch.no_grad():
+            for conv in self.convs:
+                conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * 1.5)
+                conv.bias.copy_(torch.randn(conv.bias.shape, generator=g) * 0.3)
+
+    def forward(self, img):
+        feats = [img] + [None] * 11
+        x, done = img, 0
+        for (idx, n_pool, _), conv in zip(self.STAGES, self.convs):
+            while done < n_pool:
+                x = nn.functional.avg_pool2d(x, 2, 2, ceil_mode=True)
+                done += 1
+            feats[idx] = nn.functional.silu(conv(x))
+        return feats
+
+
+def make_dnet_args(downsample_ratio=4):
+    """The argparse fields of the reference's DNET (models/DNET.py:8-33) for MaGNet's D-Net."""
+    return SimpleNamespace(output_type="G", DNET_architecture="DenseDepth_BN", output_dim=2, downsample_ratio=downsample_ratio,
+                           DNET_fix_encoder_weights="None")
+
+
+def make_dnet(seed=0, enc_seed=0, depth_prior=True):
+    """magnet_amd.dnet.DNET(dnet=False) with the stand-in encoder and seeded decoder weights (magnet_amd.dnet.seeded_decoder_state),
+    in eval mode.  depth_prior: the depth head's last layer is scaled by 1/4 and its bias set to (2.5, -3) so that the stand-in predicts
+    plausible scenes for the matcher, mu around 2.5 m (+-1.5) and sigma around 0.2 m (StubDNet's ranges); the raw recipe's mu is
+    centred on zero, where depth candidates cross the camera plane."""
+    from .dnet import DNET, load_seeded_decoder
+    d = DNET(make_dnet_args(), StandinEncoder(enc_seed), dnet=False)
+    load_seeded_decoder(d.d_net.decoder, seed)
+    if depth_prior:
+        with torch.no_grad():
+            d.d_net.decoder.depth_head[4].weight.mul_(0.25)
+            d.d_net.decoder.depth_head[4].bias.copy_(torch.tensor([2.5, -3.0]))
+    return d.eval()

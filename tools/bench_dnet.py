@@ -1,0 +1,114 @@
+"""Timing of the D-Net decoder (DenseDepth_BN at downsample ratio 4, magnet_amd/dnet.py) on one GPU: the torch module in fp32 eval
+mode (MIOpen; its output passed through activation_G_magnet) against DNetMFMA (matrix-core path, writing the reference frames' x_d3
+into a G-Net input buffer in place), on the stand-in encoder's features (the encoder is not timed):
+  * C2 (480 x 640, V = 4) with B = 1 and B = 4 frames (5 and 20 images), KITTI (352 x 1216, V = 2, B = 1: 3 images);
+  * MAGNET.forward at C2, B = 1, D = 64, I = 3 with the stand-in encoder and a PSMNet F-Net (matrix-core), dnet_backend 'torch' / 'hip'.
+Also the HIP decoder's time per convolution layer class (CUDA events around each launch) at C2, B = 1.  Prints one JSON line per
+measurement; --out FILE appends them.
+
+    python tools/bench_dnet.py [--steps 10] [--warmup 3] [--out profiles/dnet/bench_dnet.jsonl]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--skip-magnet", action="store_true")
+    a = ap.parse_args()
+    from magnet_amd import fnet, lib, synth
+    from magnet_amd.dnet import DNetMFMA, gaussian_activation
+    from magnet_amd.magnet import MAGNET
+    from magnet_amd.standin import make_args, make_dnet, seeded_magnet_weights
+    lib.load()
+    dev = torch.device("cuda:0")
+    lines = []
+
+    def emit(d):
+        d["gpu"] = torch.cuda.get_device_name(0)
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            fn()
+        torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) * 1e3 / a.steps, 3)
+
+    def images(n, H, W, seed):
+        return torch.rand(n, 3, H, W, generator=torch.Generator().manual_seed(seed)).to(dev)
+
+    d = make_dnet().to(dev)
+    dec = d.d_net.decoder
+    runner = DNetMFMA(dec)
+    for name, H, W, B, V in (("C2", 480, 640, 1, 4), ("C2", 480, 640, 4, 4), ("KITTI", 352, 1216, 1, 2)):
+        N = B * (1 + V)
+        with torch.no_grad():
+            feats = d.d_net.encoder(images(N, H, W, N))
+            h, w = feats[5].shape[2:]
+            ctot, c_off = 320, 64
+            ghi = torch.zeros((B * (h + 2) * (w + 2), ctot), dtype=torch.bfloat16, device=dev); glo = torch.zeros_like(ghi)
+            t_torch = timed(lambda: gaussian_activation(dec(feats)))
+            t_hip = timed(lambda: runner.run(feats, n_ref=B, x_d3_out=(ghi, glo, ctot, c_off)))
+            t_hip_nchw = timed(lambda: runner(feats))
+        emit(dict(bench="dnet_decoder", shape=name, H=H, W=W, B=B, V=V, images=N, steps=a.steps, warmup=a.warmup,
+                  ms_torch_fp32=t_torch, ms_hip_in_place=t_hip, ms_hip_nchw=t_hip_nchw, speedup=round(t_torch / t_hip, 2)))
+        if name == "C2" and B == 1:
+            sink = []
+            DNetMFMA.event_sink = sink
+            with torch.no_grad():
+                runner.run(feats, n_ref=B, x_d3_out=(ghi, glo, ctot, c_off))
+            torch.cuda.synchronize()
+            DNetMFMA.event_sink = None
+            ms = [e0.elapsed_time(e1) for e0, e1, _ in sink]
+            fl = [f for _, _, f in sink]
+            emit(dict(bench="dnet_decoder_layers", shape=name, B=B, launches=len(sink),
+                      ms_per_launch=[round(x, 3) for x in ms], tflops_per_launch=[round(f / (x * 1e9), 1) for f, x in zip(fl, ms)],
+                      ms_conv_total=round(sum(ms), 3), gflop_total=round(sum(fl) / 1e9, 1)))
+        del feats, ghi, glo
+        torch.cuda.empty_cache()
+
+    if not a.skip_magnet:
+        args = make_args(D=64, iters=3, dpv_h=120, dpv_w=160, fdim=64, V=4)
+        args.FNET_architecture, args.FNET_feature_dim = "PSM-Net", 64
+        torch.manual_seed(0)
+        f = fnet.FNET(args)
+        wl = synth.Workload("C2", "scannet", 120, 160, V=4, D=64, iters=3)
+        inp = synth.make_inputs(wl, B=1, seed=5)
+        ref_img, nb = images(1, 480, 640, 1), images(4, 480, 640, 2)
+        poses = inp["nghbr_poses"].to(dev)
+        res = {}
+        for be in ("torch", "hip"):
+            model = MAGNET(args, d_net=d, f_net=f, dnet_backend=be).to(dev).eval()
+            seeded_magnet_weights(model, seed=4)
+            with torch.no_grad():
+                res[be] = timed(lambda: model(ref_img, nb, poses, inp["is_valid"], inp["cam_intrins"], mode="test"))
+            del model
+            torch.cuda.empty_cache()
+        emit(dict(bench="magnet_forward", shape="C2", B=1, V=4, D=64, iters=3, encoder="standin", fnet="PSMNet (matrix-core)",
+                  steps=a.steps, warmup=a.warmup, ms_dnet_torch=res["torch"], ms_dnet_hip=res["hip"],
+                  speedup=round(res["torch"] / res["hip"], 2)))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as fh:
+            for d_ in lines:
+                fh.write(json.dumps(d_) + "\n")
+
+
+if __name__ == "__main__":
+    main()
