@@ -23,14 +23,32 @@ def _model(backend, gpu, case=None):
     return m.to(gpu).train()
 
 
-def _step(m, gpu, loss_fn=None):
+def _step(m, gpu, loss_fn=None, case=None, loss_scale=None):
     from magnet_amd.losses import MagnetLoss
-    _, ref_img, nghbr_imgs, poses, valid, intr, gt, gt_mask = train_case()
+    _, ref_img, nghbr_imgs, poses, valid, intr, gt, gt_mask = case or train_case()
     m.zero_grad(set_to_none=True)
     preds = m(ref_img.to(gpu), nghbr_imgs.to(gpu), poses.to(gpu), valid, intr, mode="train")
     loss = (loss_fn or MagnetLoss(LOSS_ARGS))(preds, gt.to(gpu), gt_mask.to(gpu))
-    loss.backward()
+    (loss if loss_scale is None else loss * loss_scale).backward()
     return preds, loss
+
+
+def training_case():
+    """The reference training configuration (train_scripts/magnet/scannet.txt, tools/bench_train.py): B = 4, 480 x 640 -> a 120 x 160
+    grid (79 056 padded rows: 39 wgrad chunks; 1.2 M loss pixels), V = 4, D = 5, I = 3, in the layout of train_case()."""
+    from magnet_amd import synth
+    from magnet_amd.standin import make_args
+    B, V, h, w = 4, 4, 120, 160
+    args = make_args(D=5, iters=3, dpv_h=h, dpv_w=w)
+    gen = torch.Generator().manual_seed(7)
+    ref_img = torch.rand(B, 3, 4 * h, 4 * w, generator=gen)
+    nb = torch.rand(V * B, 3, 4 * h, 4 * w, generator=gen)
+    poses = synth.make_poses("scannet", B, V, gen)
+    valid = torch.ones(B, V, dtype=torch.int32)
+    intr = synth.make_intrinsics("scannet", h, w, B)
+    gt = torch.rand(B, 1, 4 * h, 4 * w, generator=gen) * 3 + 1
+    gmask = torch.rand(B, 1, 4 * h, 4 * w, generator=gen) > 0.2
+    return args, ref_img, nb, poses, valid, intr, gt, gmask
 
 
 def _trainable(m):
@@ -86,11 +104,12 @@ def _rel_l2(a, b):
     return float((a.double() - b).norm() / b.norm())
 
 
-def _errors_vs_fp64(backend, gpu, capture):
+def _errors_vs_fp64(backend, gpu, capture, case=None):
     """Run one training step on `backend`, capture the inputs of every G-Net iteration, and return {param: rel L2 error}."""
-    m = _model(backend, gpu)
-    _, _, _, _, _, _, gt, gt_mask = train_case()
-    _step(m, gpu)
+    case = case or train_case()
+    m = _model(backend, gpu, case)
+    _, _, _, _, _, _, gt, gt_mask = case
+    _step(m, gpu, case=case)
     costs, gmms, x_d3 = capture(m)
     params = [(k, v.detach().cpu().double().requires_grad_(True)) for k, v in _trainable(m)]
     ref = _ref64(params, [c.cpu().double() for c in costs], [g.cpu().double() for g in gmms], x_d3.cpu().double(),
@@ -98,10 +117,7 @@ def _errors_vs_fp64(backend, gpu, capture):
     return {k: _rel_l2(v.grad.cpu(), ref[k]) for k, v in _trainable(m)}
 
 
-def test_every_trainable_parameter_against_fp64(hip_lib, gpu, monkeypatch):
-    """All 16 weight / bias tensors of both stacks: relative L2 error vs fp64 <= 1e-4.  The torch backend's error on the same inputs
-    is measured alongside (fp32 convolutions: ~1e-7); the HIP path's is bounded by its bf16x3 operand format (16 mantissa bits kept
-    per activation and weight, as at inference): measured 2e-8 .. 7e-5, G-Net's deeper layers the largest."""
+def _every_parameter_vs_fp64(gpu, monkeypatch, case=None, amplified=()):
     from magnet_amd import train as T
     from magnet_amd.magnet import GNET
     runs = []
@@ -127,12 +143,35 @@ def test_every_trainable_parameter_against_fp64(hip_lib, gpu, monkeypatch):
     def cap_torch(m):
         D = m.n_samples
         return [c[:, :D] for c, _ in seen[-3:]], [g for _, g in seen[-3:]], seen[-1][0][:, D:]
-    e_hip = _errors_vs_fp64("hip", gpu, cap_hip)
-    e_torch = _errors_vs_fp64("torch", gpu, cap_torch)
+    e_hip = _errors_vs_fp64("hip", gpu, cap_hip, case)
+    e_torch = _errors_vs_fp64("torch", gpu, cap_torch, case)
     print("rel L2 vs fp64 (hip, torch):", {k: (e_hip[k], e_torch[k]) for k in e_hip})
     for k in e_hip:
+        if k in amplified:
+            assert e_hip[k] <= 1e-4 or e_hip[k] <= 32 * e_torch[k], (k, e_hip[k], e_torch[k])
+            assert e_torch[k] <= 1e-3, (k, e_torch[k])
+            continue
         assert e_hip[k] <= 1e-4, (k, e_hip[k], e_torch[k])
         assert e_torch[k] <= 1e-5, (k, e_torch[k])                    # the fp64 restatement matches the reference formulas
+
+
+def test_every_trainable_parameter_against_fp64(hip_lib, gpu, monkeypatch):
+    """All 16 weight / bias tensors of both stacks: relative L2 error vs fp64 <= 1e-4.  The torch backend's error on the same inputs
+    is measured alongside (fp32 convolutions: ~1e-7); the HIP path's is bounded by its bf16x3 operand format (16 mantissa bits kept
+    per activation and weight, as at inference): measured 2e-8 .. 7e-5, G-Net's deeper layers the largest."""
+    _every_parameter_vs_fp64(gpu, monkeypatch)
+
+
+def test_every_trainable_parameter_against_fp64_at_training_shape(hip_lib, gpu, monkeypatch):
+    """The reference training configuration (B = 4, 120 x 160, 39 wgrad chunks, 1.2 M loss pixels): every G-Net tensor and the mask
+    head's last layer under the same 1e-4 bar.  The first three mask-head layers are ill-conditioned at this shape, whatever computes
+    them: their gradient is the softmax backward p (G - sum p G) of the upsampling, and G differs between the 9 taps only by the
+    differences of neighbouring depths, which are small on a 120 x 160 grid of a smooth depth map.  The forward's rounding of the
+    predictions is amplified by that cancellation.  The torch fp32 backend on the same inputs is 6e-5 - 9e-5 off there (3e-7 at
+    G11), and the HIP path 7e-4 - 8e-4 (16-bit operands).  Every launch of that backward is within its own derived bound
+    (test_backward_launch_audit_at_training_shape), so those three layers are held to 32 x the torch fp32 error instead."""
+    _every_parameter_vs_fp64(gpu, monkeypatch, training_case(),
+                             amplified={f"m{i}.{n}" for i in (0, 2, 4) for n in ("weight", "bias")})
 
 
 def test_magnet_loss_against_fp64(hip_lib, gpu):
@@ -276,3 +315,128 @@ def test_training_shape_adamw_gradscaler_both_backends(hip_lib, gpu):
     np.testing.assert_allclose(lh, lt, rtol=1e-4)
     for a, b in zip(ph, pt):
         assert float((a - b).norm()) <= 1e-4 * float(b.norm()), (float((a - b).norm()), float(b.norm()))
+
+
+@pytest.mark.parametrize("which", ["g11", "training"])
+def test_loss_scale_is_a_power_of_two_factor(hip_lib, gpu, which):
+    """GradScaler's initial scale 2^16 enters the backward only as a power-of-two factor on dL/dloss, read in fp64 before any
+    rounding, and every later operation is linear in the gradient (the ReLU masks come from the forward): so each .grad with the
+    scale equals 2^16 x the .grad without it, bit for bit, unless a value left the normal range (none does at these shapes)."""
+    case = training_case() if which == "training" else train_case()
+    m = _model("hip", gpu, case)
+    _step(m, gpu, case=case)
+    g1 = [p.grad.clone() for _, p in _trainable(m)]
+    _step(m, gpu, case=case, loss_scale=2.0 ** 16)
+    for (k, p), a in zip(_trainable(m), g1):
+        diff = int((p.grad != a * 2.0 ** 16).sum())
+        assert diff == 0, (k, diff, float((p.grad - a * 2.0 ** 16).abs().max()))
+
+
+def test_backward_launch_audit_at_training_shape(hip_lib, gpu, monkeypatch):
+    """One HIP training step at B = 4, 120 x 160, V = 4, D = 5, I = 3 with every lib entry point of the backward wrapped (the dgrad
+    through train._Runner._dgrad, the Python side of its one magnet_head_dgrad launch): each launch is checked, as it happens,
+    against its fp64 restatement (tests/heads_bwd_ref.py) on the exact inputs it received.  Every ratio <= 1 means each launch is
+    within the rounding its own arithmetic allows."""
+    import time
+
+    from magnet_amd import train as T
+    from tests import heads_bwd_ref as R
+
+    case = training_case()
+    m = _model("hip", gpu, case)
+    worst, t_check = {}, [0.0]
+    dims = {}
+
+    def note(entry, r):
+        worst[entry] = max(worst.get(entry, 0.0), r)
+
+    def wrap(name, check):
+        orig = getattr(lib, name)
+
+        def f(*a, **k):
+            pre = check(None, *a, **k)
+            out = orig(*a, **k)
+            t0 = time.time()
+            check(out, *a, pre=pre, **k)
+            t_check[0] += time.time() - t0
+            return out
+        monkeypatch.setattr(lib, name, f)
+
+    def c_nll_fwd(out, preds, gt, mask, gamma, pre=None):
+        if out is None:
+            return None
+        loss, sums = out
+        r = R.nll_forward_ref(preds, gt, mask, gamma)
+        assert float(sums[0]) == float(r["count"])
+        note("nll_loss_forward", max(R.check("nll sums", sums[1:], *r["sums"]), R.check("nll loss", loss, *r["loss"])))
+
+    def c_nll_bwd(out, preds, gt, mask, sums, grad_loss, gamma, pre=None):
+        if out is None:
+            return None
+        ref, bound = R.nll_backward_ref(preds, gt, mask, sums[0], float(grad_loss), gamma)
+        note("nll_loss_backward", R.check("nll grad", out, ref, bound))
+
+    def c_up(out, grad_up, depths, mask, k, mask_layout=None, grad_mask=None, grad_mask_layout=None, pre=None):
+        if out is None:
+            return grad_mask.clone()
+        gd, gm = out
+        n, B, _, h, w = depths.shape
+        shp = (B, 9 * k * k, h, w)
+        r = R.upsample_bwd_ref(grad_up, depths, mask, k, mask_layout=mask_layout)
+        note("upsample_depth_backward", max(R.check("upsample depth", gd, *r["grad_depth"]),
+                                            R.check("upsample mask", R.strided(gm, grad_mask_layout, shp), *r["grad_mask"])))
+        keep = R.addressed(gm, grad_mask_layout, shp)
+        assert torch.equal(gm[~keep], pre[~keep])                                        # border rows and channels 144..159
+        dims["rows"] = gm.shape[0]
+
+    def c_wgrad(out, dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst=0, cout_valid=None, cin_valid=None,
+                grad_b=None, accumulate=False, pre=None):
+        cv = cout if cout_valid is None else cout_valid
+        ci = cin if cin_valid is None else cin_valid
+        if pre is None and out is None:
+            return (grad_w.clone(), None if grad_b is None else grad_b.clone())
+        old_w, old_b = pre
+        r = R.wgrad_plain_ref(R.join(dy_hi, dy_lo), R.join(x_hi, x_lo), rows, wp, taps, cout, cin, cout_valid=cv, cin_valid=ci,
+                              old_w=old_w[:cv, cin_dst:cin_dst + ci] if accumulate else None,
+                              old_b=old_b[:cv] if accumulate and grad_b is not None else None)
+        key = f"wgrad taps {taps} cout {cout} cin {cin}"
+        note(key, R.check(key, grad_w[:cv, cin_dst:cin_dst + ci], *r["w"]))
+        if grad_b is not None:
+            note(key + " bias", R.check(key + " bias", grad_b[:cv], *r["b"]))
+        keep = torch.zeros(grad_w.shape, dtype=torch.bool, device=grad_w.device)
+        keep[:cv, cin_dst:cin_dst + ci] = True
+        assert torch.equal(grad_w[~keep], old_w[~keep])
+
+    for name, fn in (("nll_loss_forward", c_nll_fwd), ("nll_loss_backward", c_nll_bwd), ("upsample_depth_backward", c_up),
+                     ("wgrad", c_wgrad)):
+        wrap(name, fn)
+    orig_dgrad = T._Runner._dgrad
+
+    def dgrad(self, dout, k0, wt, hs, acc=None, acc_mode=0, acc_planes=None, gauss=None):
+        old = acc.clone() if acc is not None and acc_mode == 2 else None
+        outs = orig_dgrad(self, dout, k0, wt, hs, acc=acc, acc_mode=acc_mode, acc_planes=acc_planes, gauss=gauss)
+        t0 = time.time()
+        g = None if gauss is None else (gauss[0].contiguous(), gauss[1], gauss[2])
+        w, s, marg = R.check_head_dgrad(f"head_dgrad k0 {k0}", self.B, self.h, self.w, k0, wt, [x[0] for x in hs], outs,
+                                        dout=dout, gauss=g, sentinel=None)
+        note(f"head_dgrad k0 {k0}", w)
+        if acc is not None:
+            ra, ba = R.acc_ref(s, old, acc_mode)
+            note("head_dgrad acc", R.check(f"acc mode {acc_mode}", acc, ra, ba))
+            if acc_planes is not None:
+                eh, el = split_bf16(acc)
+                R.check_planes_exact("acc planes", acc_planes[0], acc_planes[1], eh, el)
+        note("head_dgrad marginal positions", marg)
+        t_check[0] += time.time() - t0
+        return outs
+    monkeypatch.setattr(T._Runner, "_dgrad", dgrad)
+    from magnet_amd.convnet import split_bf16
+    t0 = time.time()
+    _step(m, gpu, case=case)
+    torch.cuda.synchronize()
+    print(f"launch audit at B 4, 120 x 160 (rows {dims.get('rows')}): step + checks {time.time() - t0:.1f} s, checks {t_check[0]:.1f} s")
+    for e in sorted(worst):
+        print(f"  {e:36s} worst |got - ref| / bound {worst[e]:.3f}" if "marginal" not in e else f"  {e:36s} {worst[e]:.0f}")
+    assert {"nll_loss_forward", "nll_loss_backward", "upsample_depth_backward", "head_dgrad k0 32", "head_dgrad k0 160",
+            "head_dgrad acc"} <= set(worst)
+    assert max(v for e, v in worst.items() if "marginal" not in e) <= 1.0
