@@ -39,7 +39,7 @@ struct ConvParams {
     // fused Gaussian update (tail_cout == 16 only; models/MAGNET.py:60-69): the G-Net head's two outputs (o0, o1) of an interior
     // position update (mu, sigma) in place of the (rows, 16) fp32 write: gu_in (up_B, 2, up_h, up_w) -> gu_out, same layout
     const float* gu_in; float* gu_out;
-    int variant;                                      // dev: bit 1 = 8-wave ping-pong K loop (conv_mfma.hip, PP) instead of the default
+    int variant;                                      // host side only (launch_conv_mfma): 0; the dev library sets it from MAGNET_CONV_VARIANT
     // round 4, "2-unit" operand format of the 128-wide 3x3 layers (in_sc != nullptr): in_hi / w_hi = fp16 planes, in_lo / w_lo = per
     // 64-byte (row, 32-channel chunk) slice the 32 e4m3 bytes of hi then the 32 e4m3 bytes of lo = x - fp16(x), each block scaled by
     // its E8M0 exponent: in_sc [cin / 32][sc_rows] u32 {E8M0 of the hi block, E8M0 of the lo block, 0, 0}, w_sc [taps][cin / 32][cout_pad] u32

@@ -45,12 +45,6 @@ constexpr int CV_ROW = 64;                            // bytes per staged row (3
 // 80-byte padded rows: SQ_LDS_BANK_CONFLICT was 50 % of SQ_LDS_IDX_ACTIVE.
 __device__ __forceinline__ int cv_swz(int row, int slot) { return row * CV_ROW + ((slot ^ ((row >> 1) & 3)) << 4); }
 
-// The same image for the 32x32x16 fragment pattern (lane -> row = lane & 31, K slot = 2 * half + (lane >> 5)): the ds_read_b128 lane
-// groups {0-3,12-15,20-27} / {4-11,16-19,28-31} (and their upper-half twins) then hold, per residue of row mod 4, four rows that differ
-// in bits 2..3 (0/12/20/24, 4/8/16/28, ... — also after a shift by a tap offset), so XOR-ing the slot with (row >> 2) & 3 spreads them
-// over the four 16-byte slots of the 64-bank window; (row >> 1) & 3 above would put rows 0 and 8 on the same banks.
-__device__ __forceinline__ int cv_swz32(int row, int slot) { return row * CV_ROW + ((slot ^ ((row >> 2) & 3)) << 4); }
-
 __device__ __forceinline__ uint16_t bf16_rne(float f) { return f32_to_bf16_rne(f); }     // v_cvt_pk_bf16_f32 (warp_math.hpp)
 __device__ __forceinline__ void split_bf16(float x, uint16_t& hi, uint16_t& lo) {
     hi = bf16_rne(x);
@@ -62,75 +56,13 @@ __device__ __forceinline__ void split_bf16(float x, uint16_t& hi, uint16_t& lo) 
 // SPB = K stages per barrier interval (the LDS ring holds 2*SPB stages)
 __device__ __forceinline__ int act_swz(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
 
-// One 1x1 layer of the fused tail: this wave's 32 tile rows x (NF*16) output channels over K = 128, activations read
-// from the LDS tile (act_swz layout), weight fragments straight from global memory (64 KB per layer, L2-resident; no LDS
-// staging, so no barrier: the rows are wave-private).  Operands are swapped (weights = MFMA A operand): the accumulator is
-// C^T — a lane holds 4 CONSECUTIVE output channels of one row.
-// Arguments of the fused convex upsampling (ConvParams::up_*), passed by value to the row-owned last tail layer
+// Arguments of the fused convex upsampling (ConvParams::up_*), passed by value to the last tail layer
 struct UpArgs { const float* depth; float* out; int npred, h, w, B; };   // Gaussian update: depth = (mu, sigma) in, out = (mu, sigma) out, npred = -1
 
-template <int NF, bool LAST, int MT = 2>
-__device__ __forceinline__ void tail_layer(const uint16_t* __restrict__ w_hi, const uint16_t* __restrict__ w_lo,
-                                           const float* __restrict__ bias, unsigned char* act_hi, unsigned char* act_lo,
-                                           float* __restrict__ out, int out_ld, long long row0, long long rows, int lane, int wv) {
-    f32x4_t acc[NF][MT];
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-        for (int m = 0; m < MT; ++m) acc[n][m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int frow = lane & 15, kslot = lane >> 4;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        bf16x8_t xh[MT], xl[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const int row = wv * (MT * 16) + m * 16 + frow;
-            xh[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(act_hi + act_swz(row, kk * 4 + kslot)));
-            xl[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(act_lo + act_swz(row, kk * 4 + kslot)));
-        }
-#pragma unroll
-        for (int n = 0; n < NF; ++n) {
-            const size_t e = (size_t)(n * 16 + frow) * 128 + kk * 32 + kslot * 8;
-            const bf16x8_t wh = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(w_hi + e));
-            const bf16x8_t wl = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(w_lo + e));
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[m], acc[n][m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh[m], acc[n][m], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[m], acc[n][m], 0, 0, 0);
-        }
-    }
-    // all of this wave's reads of its rows are done (same wave, in-order LDS); publish the layer's output in place
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const int ch = n * 16 + (lane >> 4) * 4;
-            const int trow = wv * (MT * 16) + m * 16 + (lane & 15);
-            const float4 b4 = *reinterpret_cast<const float4*>(bias + ch);
-            float v[4] = {acc[n][m][0] + b4.x, acc[n][m][1] + b4.y, acc[n][m][2] + b4.z, acc[n][m][3] + b4.w};
-            if constexpr (!LAST) {
-                uint32_t h01, l01, h23, l23;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = v[r] < 0.f ? 0.f : v[r];
-                split_bf16x2(v[0], v[1], h01, l01); split_bf16x2(v[2], v[3], h23, l23);
-                const int off = act_swz(trow, ch >> 3) + (ch & 7) * 2;          // 8 bytes: channels ch..ch+3
-                *reinterpret_cast<uint2*>(act_hi + off) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(act_lo + off) = make_uint2(l01, l23);
-            } else {
-                const long long row = row0 + trow;
-                if (row < rows) *reinterpret_cast<float4*>(out + (size_t)row * out_ld + ch) = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Column-owned form of the same layer (default): wave w computes output fragments n = w, w + 4 (32 of the 128 output channels)
+// One 1x1 layer of the fused tail over K = 128: activations read from the LDS tile (act_swz layout), weight fragments straight from
+// global memory (64 KB per layer, L2-resident; no LDS staging).  Operands are swapped (weights = MFMA A operand): the accumulator is
+// C^T — a lane holds 4 CONSECUTIVE output channels of one row.
+// Column-owned: wave w computes output fragments n = w, w + 4 (32 of the 128 output channels)
 // for ALL rows of the tile, so it fetches a quarter of the layer's weights (16 KB instead of 64 KB per wave: with row ownership the
 // two resident workgroups pull 128 KB per K chunk through the CU's 64 B/clk vector-memory path for 1 536 cycles of MFMA work — the
 // tails ran at half the K loop's efficiency) and reads every row's activations from LDS (256 B/clk, cheap).  A remainder
@@ -331,13 +263,6 @@ __device__ __forceinline__ void tail_layer_cols(const uint16_t* __restrict__ w_h
 // One MFMA of the K loop.  SWAP (kernels with a fused tail): operands exchanged, so the accumulator holds C^T — a lane has 4
 // consecutive output CHANNELS of one row, and the tail's activation tile is written with packed conversions and 8-byte LDS stores
 // (the plain orientation gives 4 consecutive rows of one channel: 128 two-byte stores per lane and tile).
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-// 32x32x16 form, operands swapped as in the fused-tail kernels (weights = A operand): C^T block [32 channels][32 tile rows]; lane l,
-// register i: channel (i & 3) + 8 * (i >> 2) + 4 * (l >> 5), tile row l & 31 (cdna_hip_programming.md, fragment layout)
-__device__ __forceinline__ f32x16_t cv_mma32(const bf16x8_t& act, const bf16x8_t& wgt, const f32x16_t& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(wgt, act, c, 0, 0, 0);
-}
-
 template <bool SWAP>
 __device__ __forceinline__ f32x4_t cv_mma(const bf16x8_t& a, const bf16x8_t& b, const f32x4_t& c) {
     if constexpr (SWAP) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
@@ -347,34 +272,29 @@ __device__ __forceinline__ f32x4_t cv_mma(const bf16x8_t& a, const bf16x8_t& b, 
 // TAIL = 0: plain layer.  TAIL = 16-column fragments of the fused tail's last layer (1, 8 or 9): see ConvParams::tail_*.
 // PP = "ping-pong" K loop: NT = 512 threads = 8 waves = two wave groups (waves 0-3 / 4-7: one wave of each group per SIMD) that
 // run the same program half a K step apart — while one group issues its fragment reads and the LDS-DMA of the stage two steps
-// ahead, the other owns the matrix pipe — over a 3-slot LDS ring with counted vmcnt waits and raw s_barriers (no DMA drain at a
-// barrier).  The 4-wave / 2-slot loop (PP = false) drains the DMA queue (vmcnt(0)) at every step's __syncthreads and relies on a
-// second workgroup per CU to fill the gap: 41 % of the matrix pipe; see DESIGN.md §4.3.
+// ahead, the other owns the matrix pipe — with counted vmcnt waits and raw s_barriers (no DMA drain at a barrier); it exists with a
+// row window only (WIN = 2, WIN = 4).  The 4-wave / 2-slot loop (PP = false) drains the DMA queue (vmcnt(0)) at every step's
+// __syncthreads and relies on a second workgroup per CU to fill the gap: 41 % of the matrix pipe; see DESIGN.md §4.3.
 // WIN = row-window K loop: the taps of one tap ROW (ty fixed, tx = 0..tap_n-1) read the same activation rows shifted by tap_sx, so
 // their A operand is staged ONCE per (K chunk, ty) as a window of CV_BM + (tap_n-1)*tap_sx rows and the tx sub-steps read their
 // fragments at a row offset; only the weight tile changes per sub-step.  L2 requests per 3x3 tap row: 272 + 3*256 instead of
-// 3*(256 + 256).  WIN = 1: two window slots + two weight slots in LDS, one flat loop over the sub-steps (2x2 taps, dev A/B).
+// 3*(256 + 256).  WIN = 1: two window slots + two weight slots in LDS, one flat loop over the sub-steps (2x2 taps).
 // WIN = 2 (3x3 layers, default): the window's fragments for all three tx are held in registers, one window slot + a 3-slot weight
-// ring with counted vmcnt waits (prefetch distance 2).
+// ring with counted vmcnt waits (prefetch distance 2).  WIN = 4: the fp16 + block-scaled e4m3 operand format (ConvParams::in_sc).
 // __launch_bounds__(NT, 2): two waves per SIMD is what the LDS budget allows anyway, and with <= 256 registers hipcc selects the
 // VGPR form of the MFMAs — with the default bound it kept the accumulators in AGPRs and moved all 64 of them through VGPRs
 // (64 v_accvgpr_read + 64 v_accvgpr_write) on every trip of the K loop.
-// One output tile (CV_BM rows x BN channels).  `bid` of `n_tiles`: the tile's position in launch order (the block id of a one-tile-per-
-// workgroup launch, the loop counter of a persistent one); `by`: the channel block.
-// M32_ (round 5, DEV ONLY — MAGNET_CONV_VARIANT=16384): the fused-tail kernels' register-window loops (WIN == 2, with and without
-// ping-pong) on v_mfma_f32_32x32x16_bf16 — a wave's 64 x 64 tile as 2 x 2 blocks of 32 x 32 instead of 4 x 4 of 16 x 16: the same
-// MACs, fragment reads, registers and (by the guide's lane-group model) conflict-free LDS reads with the cv_swz32 image.  The bet: the
-// kernel is power-limited and the guide's microbenchmark floors are 2 382 TF for the 32x32 shape against 2 075 TF for 16x16.  Parity
-// green (tests/test_gpu_conv.py), measured 5.5 % SLOWER on both stacks (2.135 vs 2.02 ms per 3x3 launch, profiles/r5/conv_m32_ab.log):
-// the 32x32x16 shape halves the operand reads per MAC but doubles the fp32 accumulator traffic (K = 16 per instruction): 0.625 against
-// 0.5 register bytes per MAC.  Kept as a record; the product library does not instantiate it.
-template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool M32_ = false>
+// One output tile (CV_BM rows x BN channels).  `bid` of `n_tiles`: the tile's position in launch order (the block id); `by`: the channel
+// block.  Measured and not kept (the source is in the history): the ping-pong loop without a window (equal to the 4-wave loop, 5.83 vs
+// 5.91 ms per C2 step), with a 2-slot LDS window, with fragment double-buffering and with deeper prefetch (4 % slower: 2.19 vs 2.10 ms,
+// profiles/r4/conv_deeper_prefetch_vs_round3.log); persistent workgroups (0.7 % slower, profiles/r4/conv_persistent_ab.log); the 32x32x16 MFMA shape (5.5 %
+// slower, profiles/r5/conv_m32_ab.log); a row-owned fused tail (see tail_layer_cols).
+template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN>
 __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsigned bid, const unsigned n_tiles, const unsigned by, const int tid) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-descriptor builtins do not exist in the host pass (which only needs the stub)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // ring of 2*SPB stages (declared here, not passed in: a pointer
                                                                             // parameter is a generic pointer, and its casts to LDS pointers get null checks)
     constexpr int BN = NF * 16;
-    constexpr bool M32 = M32_ && TAIL > 0 && NF == 8 && WN == 2 && WIN == 2;
     constexpr int RP = NT / 4;                        // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
     constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (2 or 4)
     constexpr int WM = (NT / 64) / WN;                // waves along M
@@ -404,7 +324,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
     const int ksteps_per_tap = p.cin / CV_BK;
     const int nsteps = p.taps * ksteps_per_tap;
     const int st_r = tid >> 2, st_q = tid & 3;
-    const int st_k = (st_q ^ (M32 ? ((st_r >> 2) & 3) : ((st_r >> 1) & 3))) * 8;   // logical K offset (elements) this lane fetches (cv_swz / cv_swz32)
+    const int st_k = (st_q ^ ((st_r >> 1) & 3)) * 8;          // logical K offset (elements) this lane fetches (cv_swz)
     const int wave_row = __builtin_amdgcn_readfirstlane(wv * 16);   // first tile row this wave's DMA instruction fills
 
     // step order: K-chunk outer, tap inner — the 9 taps of one 32-channel chunk re-read (shifted) the same 64-byte
@@ -458,36 +378,15 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         if (++pf_tx == p.tap_n) { pf_tx = 0; if (++pf_ty == p.tap_n) { pf_ty = 0; pf_tap = 0; pf_k0 += CV_BK; } }   \
     }
 
-    f32x4_t acc[MF][NFW];                                      // (dead in the M32 instances)
-    f32x16_t acc32[M32 ? 2 : 1][M32 ? 2 : 1];                  // M32: [row block of 32][channel block of 32] of the wave's 64 x 64 tile
+    f32x4_t acc[MF][NFW];
 #pragma unroll
     for (int m = 0; m < MF; ++m)
 #pragma unroll
         for (int n = 0; n < NFW; ++n) acc[m][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int m = 0; m < (M32 ? 2 : 1); ++m)
-#pragma unroll
-        for (int n = 0; n < (M32 ? 2 : 1); ++n)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc32[m][n][i] = 0.f;
     // fused-tail kernels (C^T accumulators: 4 consecutive channels of one row per lane): the loop-invariant partial sums of the
     // hoisted G-Net layer (ConvParams::addend) are the accumulators' INITIAL value — sixteen 16-byte loads whose latency hides
     // behind the K loop's prologue instead of sitting exposed in the epilogue (the short K = 288 / 576 per-iteration layers)
-    if constexpr (M32) {
-        if (p.addend) {
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const long long row = row0 + wm * 64 + mb * 32 + (lane & 31);
-                        const int ch = wn * 64 + nb * 32 + g4 * 8 + (lane >> 5) * 4;
-                        const float4 a4 = *reinterpret_cast<const float4*>(p.addend + (size_t)(row < p.rows ? row : p.rows - 1) * p.addend_ld + ch);
-                        acc32[mb][nb][g4 * 4 + 0] = a4.x; acc32[mb][nb][g4 * 4 + 1] = a4.y; acc32[mb][nb][g4 * 4 + 2] = a4.z; acc32[mb][nb][g4 * 4 + 3] = a4.w;
-                    }
-        }
-    } else if constexpr (TAIL > 0) {
+    if constexpr (TAIL > 0) {
         if (p.addend) {
 #pragma unroll
             for (int m = 0; m < MF; ++m)
@@ -534,246 +433,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         }
     };
 
-    if constexpr (WIN == 3 && PP) {
-        // ---- ping-pong x LDS window x fragment double-buffering (dev, MAGNET_CONV_VARIANT=128): the fragments of sub-step s+1 are read
-        // at the START of the compute phase of sub-step s into a second register set (in the shadow of the 48 MFMAs), so a LOAD phase
-        // is only DMA issue + counted wait + barrier.  That needs every stage visible one phase earlier: 4-slot weight ring (DMA
-        // distance 3), 2-slot window filled at tx = 0 of the previous group.  With the groups staggered by one barrier:
-        //   L_s: [tx = 0: DMA window g+1 -> slot (g+1)&1]  DMA weights s+3 -> slot (s+3)&3;  vmcnt(pieces of THIS phase);  barrier
-        //   C_s: ds_read fragments of sub-step s+1 (window g' = (s+1)/3, weights slot (s+1)&3);  48 MFMAs of sub-step s;  lgkmcnt(0);  barrier
-        // RAW: what L_{s-1}'s waits retired (weights s+1, window parts issued at or before L_{s-2}) has passed both groups' waits and
-        // a barrier when C_s starts.  WAR: slot (s+3)&3 held stage s-1, read at the start of C_{s-2} and retired before the barrier
-        // that ends it; the window slot of g+1 held window g-1, last read at the start of C_{3g-2}.
-        static_assert(NT == 512 && SPB == 1 && BN % RP == 0 && CV_BM % RP == 0, "8 waves, whole DMA passes");
-        constexpr int BP = 2 * B_PT, AP = 2 * A_PT;
-        unsigned char* const a_ring = smem;                   // 2 x [hi | lo]
-        unsigned char* const b_ring = smem + 4 * A_BYTES;     // 4 x [hi | lo]
-        const int aw = CV_BM + 2 * p.tap_sx;
-        const int ngroups = 3 * ksteps_per_tap;               // even (checked by the launcher)
-        const int nsub = 3 * ngroups;
-        int g_ty = 0, g_k0 = 0, bs_tap = 0, bs_k0 = 0;
-        auto dma_a = [&](int slot) {
-            unsigned char* sa_hi = a_ring + slot * (2 * A_BYTES);
-            unsigned char* sa_lo = sa_hi + A_BYTES;
-            const int a_u = (((g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx) * p.in_ld + g_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < A_PT; ++i) {
-                CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-                CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-            }
-            if (wv == 0 && st_r < aw - CV_BM) {
-                const int ax = a_v[0] + CV_BM * p.in_ld * 2;
-                CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
-            }
-            if (++g_ty == 3) { g_ty = 0; g_k0 += CV_BK; }
-        };
-        auto dma_b = [&](int slot) {
-            unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            unsigned char* sb_lo = sb_hi + B_BYTES;
-            const int b_u = (bs_tap * p.cout_pad * p.cin + bs_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < B_PT; ++i) {
-                CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-            }
-            if (++bs_tap == 9) { bs_tap = 0; bs_k0 += CV_BK; }
-        };
-        int a_offx[3];
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
-        bf16x8_t xah0[MF], xal0[MF], xbh0[NFW], xbl0[NFW], xah1[MF], xal1[MF], xbh1[NFW], xbl1[NFW];
-        auto read_frags = [&](bf16x8_t (&fa_h)[MF], bf16x8_t (&fa_l)[MF], bf16x8_t (&fb_h)[NFW], bf16x8_t (&fb_l)[NFW], int aslot, int a_of, int bslot) {
-            const unsigned char* sa_hi = a_ring + aslot * (2 * A_BYTES);
-            const unsigned char* sb_hi = b_ring + bslot * (2 * B_BYTES);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                fb_h[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-                fb_l[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + B_BYTES + b_off + n * 16 * CV_ROW));
-            }
-#pragma unroll
-            for (int m = 0; m < MF; ++m) {
-                fa_h[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_hi + a_of + m * 16 * CV_ROW));
-                fa_l[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_hi + A_BYTES + a_of + m * 16 * CV_ROW));
-            }
-        };
-        int sidx = 0;                                         // sub-step counter
-        // one sub-step: TX static, (c*) = fragments of this sub-step, (n*) = register set filled for the next one
-        auto substep = [&](auto TXc, int gslot, bool lastg, bf16x8_t (&ca_h)[MF], bf16x8_t (&ca_l)[MF], bf16x8_t (&cb_h)[NFW], bf16x8_t (&cb_l)[NFW],
-                           bf16x8_t (&na_h)[MF], bf16x8_t (&na_l)[MF], bf16x8_t (&nb_h)[NFW], bf16x8_t (&nb_l)[NFW]) {
-            constexpr int TX = decltype(TXc)::value;
-            // ---- LOAD phase ----
-            asm volatile("" ::: "memory");
-            if (!lastg) {
-                dma_b((sidx + 3) & 3);
-                if constexpr (TX == 0) {
-                    dma_a(gslot ^ 1);
-                    if (wv == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP + AP + 2) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP + AP) : "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP) : "memory");
-                }
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_s_barrier();
-            // ---- COMPUTE phase ----
-            asm volatile("" ::: "memory");
-            if (sidx + 1 < nsub)
-                read_frags(na_h, na_l, nb_h, nb_l, TX == 2 ? (gslot ^ 1) : gslot, a_offx[(TX + 1) % 3], (sidx + 1) & 3);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ca_l[m], cb_h[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ca_h[m], cb_l[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ca_h[m], cb_h[n], acc[m][n]);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            ++sidx;
-        };
-        const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
-        dma_a(0);
-        dma_b(0); dma_b(1); dma_b(2);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        read_frags(xah0, xal0, xbh0, xbl0, 0, a_offx[0], 0);
-        if (grp == 1) __builtin_amdgcn_s_barrier();           // group 1 runs one barrier (= half a sub-step) behind group 0
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        for (int g = 0; g < ngroups; g += 2) {
-            const bool last2 = g + 2 == ngroups;
-            substep(I0{}, 0, false, xah0, xal0, xbh0, xbl0, xah1, xal1, xbh1, xbl1);
-            substep(I1{}, 0, false, xah1, xal1, xbh1, xbl1, xah0, xal0, xbh0, xbl0);
-            substep(I2{}, 0, false, xah0, xal0, xbh0, xbl0, xah1, xal1, xbh1, xbl1);
-            substep(I0{}, 1, last2, xah1, xal1, xbh1, xbl1, xah0, xal0, xbh0, xbl0);
-            substep(I1{}, 1, last2, xah0, xal0, xbh0, xbl0, xah1, xal1, xbh1, xbl1);
-            substep(I2{}, 1, last2, xah1, xal1, xbh1, xbl1, xah0, xal0, xbh0, xbl0);
-        }
-        if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
-        __syncthreads();                                      // nothing in flight; the ring is dead
-    } else
-    if constexpr (WIN == 1 && PP) {
-        // ---- ping-pong x LDS window (dev, MAGNET_CONV_VARIANT=64): as the register-window ping-pong loop below, but the window has
-        // two LDS slots (one workgroup per CU: 117 KB), so its DMA is spread over tx = 0 / 1 and every LOAD phase is the same 16
-        // fragment reads + 2 - 4 DMA pieces.  Phase order per group: L_s = reads of stage
-        // s, DMA of stage s+2 (and of window g+1 at tx = 1), counted vmcnt for everything older, lgkmcnt(0), barrier; C_s = MFMAs,
-        // barrier.  RAW: a stage is read one L phase after every wave's wait for it and a barrier both groups passed; WAR: a
-        // slot is refilled in the L phase after the one whose reads of it retired before a barrier both groups passed.
-        static_assert(NT == 512 && SPB == 1 && BN % RP == 0 && CV_BM % RP == 0, "8 waves, whole DMA passes");
-        constexpr int BP = 2 * B_PT, AP = 2 * A_PT;
-        unsigned char* const a_ring = smem;                   // 2 x [hi | lo]
-        unsigned char* const b_ring = smem + 4 * A_BYTES;
-        const int aw = CV_BM + 2 * p.tap_sx;
-        const int ngroups = 3 * ksteps_per_tap;
-        int g_ty = 0, g_k0 = 0, bs_tap = 0, bs_k0 = 0;
-        // window g + 1 -> slot (g + 1) & 1 in two parts: part 0 = first row pass + the rows past the tile, part 1 = second row pass
-        auto dma_a = [&](int slot, int part) {
-            unsigned char* sa_hi = a_ring + slot * (2 * A_BYTES);
-            unsigned char* sa_lo = sa_hi + A_BYTES;
-            const int a_u = (((g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx) * p.in_ld + g_k0) * 2;
-            CV_BLDS(ra_hi, sa_hi + (wave_row + part * RP) * CV_ROW, a_v[part] + a_u);
-            CV_BLDS(ra_lo, sa_lo + (wave_row + part * RP) * CV_ROW, a_v[part] + a_u);
-            if (part == 0) {
-                if (wv == 0 && st_r < aw - CV_BM) {
-                    const int ax = a_v[0] + CV_BM * p.in_ld * 2;
-                    CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                    CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
-                }
-            } else if (++g_ty == 3) { g_ty = 0; g_k0 += CV_BK; }
-        };
-        auto dma_b = [&](int slot) {
-            unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            unsigned char* sb_lo = sb_hi + B_BYTES;
-            const int b_u = (bs_tap * p.cout_pad * p.cin + bs_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < B_PT; ++i) {
-                CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-            }
-            if (++bs_tap == 9) { bs_tap = 0; bs_k0 += CV_BK; }
-        };
-        int a_offx[3];
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
-        static_assert(A_PT == 2, "two window row passes");
-        bf16x8_t ah[MF], al[MF], fbh[NFW], fbl[NFW];
-        auto load_a = [&](int slot, int a_of) {
-#pragma unroll
-            for (int m = 0; m < MF; ++m) {
-                ah[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_ring + slot * (2 * A_BYTES) + a_of + m * 16 * CV_ROW));
-                al[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_ring + slot * (2 * A_BYTES) + A_BYTES + a_of + m * 16 * CV_ROW));
-            }
-        };
-        auto load_b = [&](int slot) {
-            const unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            const unsigned char* sb_lo = sb_hi + B_BYTES;
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                fbh[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-                fbl[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
-            }
-        };
-        auto mfmas = [&](const bf16x8_t (&xh)[MF], const bf16x8_t (&xl)[MF]) {
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xl[m], fbh[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], fbl[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], fbh[n], acc[m][n]);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        };
-#define CV_END_LOAD(N)                                                                         \
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");                    \
-        __builtin_amdgcn_s_barrier();
-        const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
-        dma_a(0, 0); dma_a(0, 1);
-        dma_b(0);
-        dma_b(1);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP) : "memory");                 // window 0 and stage 0 landed (this wave's pieces)
-        __builtin_amdgcn_s_barrier();
-        if (grp == 1) __builtin_amdgcn_s_barrier();           // group 1 runs one barrier (= half a sub-step) behind group 0
-        for (int g = 0; g < ngroups; ++g) {
-            const bool lastg = g + 1 == ngroups;
-            const int as = g & 1;
-            // ---- tx = 0 ----
-            asm volatile("" ::: "memory");
-            load_a(as, a_offx[0]);
-            load_b(0);
-            dma_b(2);                                         // stage 3g + 2
-            if (!lastg) {
-                dma_a(as ^ 1, 0);                             // window g + 1, first part (its slot was last read in group g - 1)
-                if (wv == 0) { CV_END_LOAD(BP + 4) } else { CV_END_LOAD(BP + 2) }            // stage 3g + 1 landed
-            } else { CV_END_LOAD(BP) }
-            mfmas(ah, al);
-            // ---- tx = 1 ----
-            asm volatile("" ::: "memory");
-            load_a(as, a_offx[1]);
-            load_b(1);
-            if (!lastg) { dma_b(0); dma_a(as ^ 1, 1); CV_END_LOAD(BP + 2) }                  // stage 3g + 3, window part 2; stage 3g + 2 landed
-            else { CV_END_LOAD(0) }
-            mfmas(ah, al);
-            // ---- tx = 2 ----
-            asm volatile("" ::: "memory");
-            load_a(as, a_offx[2]);
-            load_b(2);
-            if (!lastg) { dma_b(1); CV_END_LOAD(BP) }         // stage 3g + 4; stage 3g + 3 and window g + 1 landed
-            else { CV_END_LOAD(0) }
-            mfmas(ah, al);
-        }
-#undef CV_END_LOAD
-        if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
-        __syncthreads();                                      // nothing in flight; the ring is dead
-    } else
     if constexpr (WIN == 4 && PP) {
         // ---- round 4: the "2-unit" operand split on the 8-wave ping-pong loop (ConvParams::in_sc != nullptr) ----
         // x = hi + lo with hi = fp16(x): the main term hi_x * hi_w runs on v_mfma_f32_16x16x32_f16 (1 matrix-pipe unit per 32 K instead of
@@ -860,7 +519,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         const int wq_off1 = g4 < 2 ? 2 * B_BYTES + cv_swz(wcol, gl) : QB_ZERO, wr_off1 = g4 < 2 ? 2 * B_BYTES + cv_swz(wcol, 2 + gl) : QB_ZERO;
         const int wn_str = g4 < 2 ? 16 * CV_ROW : 0;
         const int ws_off = 3 * B_BYTES + ((g4 < 3 ? g4 : 2) * BN + wcol) * 4;
-        const bool no_corr_mma = (p.variant & 0x1000) != 0;               // dev: timing ablation (wrong results)
         f16x8_t ah[MF], fbh[NFW];
         i32x8_t xr[MF], xq[MF], wq[NFW], wr[NFW];                          // correction operands: e4m3 lo / hi of the window rows, hi / lo of the weights
         int xsc[MF], wsc[NFW];
@@ -885,19 +543,17 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             for (int n = 0; n < NFW; ++n)
 #pragma unroll
                 for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[n], ah[m], acc[m][n], 0, 0, 0);
-            if (!no_corr_mma) {
 #pragma unroll
-                for (int n = 0; n < NFW; ++n) {
-                    if (n < a0 || n >= a1) continue;
+            for (int n = 0; n < NFW; ++n) {
+                if (n < a0 || n >= a1) continue;
 #pragma unroll
-                    for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wq[n], xr[m], acc[m][n], 0, 0, 0, wsc[n], 1, xsc[m]);
-                }
+                for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wq[n], xr[m], acc[m][n], 0, 0, 0, wsc[n], 1, xsc[m]);
+            }
 #pragma unroll
-                for (int n = 0; n < NFW; ++n) {
-                    if (n < b0 || n >= b1) continue;
+            for (int n = 0; n < NFW; ++n) {
+                if (n < b0 || n >= b1) continue;
 #pragma unroll
-                    for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wr[n], xq[m], acc[m][n], 0, 0, 1, wsc[n], 0, xsc[m]);
-                }
+                for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wr[n], xq[m], acc[m][n], 0, 0, 1, wsc[n], 0, xsc[m]);
             }
             __builtin_amdgcn_s_setprio(0);
             // (an MFMA may not leave its phase: without pinning the accumulators here hipcc sank correction MFMAs behind the barrier into the
@@ -982,135 +638,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         if (grp == 0) __builtin_amdgcn_s_barrier();                       // balance group 1's extra barrier
         __syncthreads();                                                  // nothing in flight; the ring is dead
     } else
-    if constexpr (WIN == 5 && PP) {
-        // ---- round 4: the ping-pong x register-window loop below with DEEPER prefetch.  Counters of the WIN == 2 loop (profiles/r4): the matrix
-        // pipe is 72 % busy and a LOAD phase waits ~700 cycles whatever it reads — the LDS-DMA round trip under load is ~1.1 us = 2 000 cycles,
-        // and a weight tile fetched two sub-steps (2 x 768 MFMA cycles) ahead has not landed.  The fused tail needs 128 KB of LDS anyway, so
-        // the K loop may use it: the window is DOUBLE-buffered (the next group's window is fetched a whole group ahead, at tx = 0) and the
-        // weight ring has FOUR slots (prefetch distance 3 sub-steps): 133 KB.
-        // ---- ping-pong x register window: 256-row tile, two wave groups half a step apart as in the PP
-        // loop below, but the LOAD phase of a sub-step is only the 8 weight-fragment reads (+ the 24 window reads once per group)
-        // and ~3.4 DMA pieces per wave, so it fits under the other group's 48 MFMAs.  Phase order per group: L_s = reads of stage
-        // s, DMA of stage s+2 (and of window g+1 at tx = 1), counted vmcnt for everything older, lgkmcnt(0), barrier; C_s = MFMAs,
-        // barrier.  RAW: a stage is read one L phase after every wave's wait for it and a barrier both groups passed; WAR: a
-        // slot is refilled in the L phase after the one whose reads of it retired before a barrier both groups passed.
-        static_assert(NT == 512 && SPB == 1 && BN % RP == 0 && CV_BM % RP == 0, "8 waves, whole DMA passes");
-        constexpr int BP = 2 * B_PT, AP = 2 * A_PT;
-        unsigned char* const a_base = smem;                                // 2 x [hi | lo] window
-        unsigned char* const b_ring = smem + 4 * A_BYTES;                  // 4 x [hi | lo] weight tile
-        const int aw = CV_BM + 2 * p.tap_sx;
-        const int ngroups = 3 * ksteps_per_tap;
-        int g_ty = 0, g_k0 = 0, bs_tap = 0, bs_k0 = 0;
-        auto dma_a = [&](int buf) {
-            unsigned char* sa_hi = a_base + buf * (2 * A_BYTES);
-            unsigned char* sa_lo = sa_hi + A_BYTES;
-            const int a_u = (((g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx) * p.in_ld + g_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < A_PT; ++i) {
-                CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-                CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-            }
-            if (wv == 0 && st_r < aw - CV_BM) {
-                const int ax = a_v[0] + CV_BM * p.in_ld * 2;
-                CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
-            }
-            if (++g_ty == 3) { g_ty = 0; g_k0 += CV_BK; }
-        };
-        auto dma_b = [&](int slot) {
-            unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            unsigned char* sb_lo = sb_hi + B_BYTES;
-            const int b_u = (bs_tap * p.cout_pad * p.cin + bs_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < B_PT; ++i) {
-                CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-            }
-            if (++bs_tap == 9) { bs_tap = 0; bs_k0 += CV_BK; }
-        };
-        int a_offx[3];
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
-        bf16x8_t ah[3][MF], al[3][MF], fbh[NFW], fbl[NFW];
-        auto load_b = [&](int slot) {
-            const unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            const unsigned char* sb_lo = sb_hi + B_BYTES;
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                fbh[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-                fbl[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
-            }
-        };
-        auto mfmas = [&](const bf16x8_t (&xh)[MF], const bf16x8_t (&xl)[MF]) {
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xl[m], fbh[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], fbl[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], fbh[n], acc[m][n]);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        };
-#define CV_END_LOAD(N)                                                                         \
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");                    \
-        __builtin_amdgcn_s_barrier();
-        const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
-        // issue order per LOAD phase — L0: window g + 1, stage 3g + 3;  L1: stage 3g + 4;  L2: stage 3g + 5.  Needed at the end of L_s: stage s + 1
-        // (at L2 also the window of g + 1, for the fragment reads of the next L0).  Loads retire in order; still outstanding may be:
-        //   L0: stage 3g+2 | window | stage 3g+3;   L1: window | stage 3g+3 | stage 3g+4;   L2: stage 3g+4 | stage 3g+5.
-        dma_a(0);
-        dma_b(0);
-        dma_b(1);
-        dma_b(2);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * BP) : "memory");             // window 0 and stage 0 landed (this wave's pieces)
-        __builtin_amdgcn_s_barrier();
-        if (grp == 1) __builtin_amdgcn_s_barrier();           // group 1 runs one barrier (= half a sub-step) behind group 0
-        int bslot = 0;
-        for (int g = 0; g < ngroups; ++g) {
-            const bool lastg = g + 1 == ngroups;
-            const unsigned char* a_win = a_base + (g & 1) * (2 * A_BYTES);
-            // ---- tx = 0 ----
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int tx = 0; tx < 3; ++tx)
-#pragma unroll
-                for (int m = 0; m < MF; ++m) {
-                    ah[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + a_offx[tx] + m * 16 * CV_ROW));
-                    al[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + A_BYTES + a_offx[tx] + m * 16 * CV_ROW));
-                }
-            load_b(bslot);
-            if (!lastg) {
-                dma_a((g + 1) & 1); dma_b((bslot + 3) & 3);
-                if (wv == 0) { CV_END_LOAD(2 * BP + AP + 2) } else { CV_END_LOAD(2 * BP + AP) }
-            } else { CV_END_LOAD(0) }
-            mfmas(ah[0], al[0]);
-            bslot = (bslot + 1) & 3;
-            // ---- tx = 1 ----
-            asm volatile("" ::: "memory");
-            load_b(bslot);
-            if (!lastg) {
-                dma_b((bslot + 3) & 3);
-                if (wv == 0) { CV_END_LOAD(2 * BP + AP + 2) } else { CV_END_LOAD(2 * BP + AP) }
-            } else { CV_END_LOAD(0) }
-            mfmas(ah[1], al[1]);
-            bslot = (bslot + 1) & 3;
-            // ---- tx = 2 ----
-            asm volatile("" ::: "memory");
-            load_b(bslot);
-            if (!lastg) { dma_b((bslot + 3) & 3); CV_END_LOAD(2 * BP) }
-            else { CV_END_LOAD(0) }
-            mfmas(ah[2], al[2]);
-            bslot = (bslot + 1) & 3;
-        }
-#undef CV_END_LOAD
-        if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
-        __syncthreads();                                      // nothing in flight; the ring is dead
-    } else
     if constexpr (WIN == 2 && PP) {
         // ---- ping-pong x register window (DEFAULT for 128-wide 3x3 layers): 256-row tile, two wave groups half a step apart as in the PP
         // loop below, but the LOAD phase of a sub-step is only the 8 weight-fragment reads (+ the 24 window reads once per group)
@@ -1155,87 +682,27 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         int a_offx[3];
 #pragma unroll
         for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
-        // M32: fragment (row block mb, K half h) of the window at tap tx / of the weight tile: index mb * 2 + h of the same register arrays
-        int a_offx32[3][2], b_off32[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-#pragma unroll
-            for (int tx = 0; tx < 3; ++tx) a_offx32[tx][h] = cv_swz32(wm * 64 + (lane & 31) + tx * p.tap_sx, 2 * h + (lane >> 5));
-            b_off32[h] = cv_swz32(wn * 64 + (lane & 31), 2 * h + (lane >> 5));
-        }
         bf16x8_t ah[3][MF], al[3][MF], fbh[NFW], fbl[NFW];
-#ifdef CONV_ABL      // ablation builds: LDS reads by 32-bit address (a conditional read through the generic pointer trips a backend bug: null check of the LDS cast)
-        typedef uint32_t cv_u32x4 __attribute__((ext_vector_type(4)));
-#define CV_LD16(ptr) (*reinterpret_cast<const __attribute__((address_space(3))) cv_u32x4*>((uint32_t)(uintptr_t)(ptr)))
-#else
-#define CV_LD16(ptr) (*reinterpret_cast<const uint4*>(ptr))
-#endif
         auto load_b = [&](int slot) {
             const unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
             const unsigned char* sb_lo = sb_hi + B_BYTES;
-            if constexpr (M32) {
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        fbh[nb * 2 + h] = __builtin_bit_cast(bf16x8_t, CV_LD16(sb_hi + b_off32[h] + nb * 32 * CV_ROW));
-                        fbl[nb * 2 + h] = __builtin_bit_cast(bf16x8_t, CV_LD16(sb_lo + b_off32[h] + nb * 32 * CV_ROW));
-                    }
-                return;
-            }
 #pragma unroll
             for (int n = 0; n < NFW; ++n) {
-                fbh[n] = __builtin_bit_cast(bf16x8_t, CV_LD16(sb_hi + b_off + n * 16 * CV_ROW));
-                fbl[n] = __builtin_bit_cast(bf16x8_t, CV_LD16(sb_lo + b_off + n * 16 * CV_ROW));
+                fbh[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
+                fbl[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
             }
         };
         auto load_win = [&]() {
-            if constexpr (M32) {
-#pragma unroll
-                for (int tx = 0; tx < 3; ++tx)
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            ah[tx][mb * 2 + h] = __builtin_bit_cast(bf16x8_t, CV_LD16(a_win + a_offx32[tx][h] + mb * 32 * CV_ROW));
-                            al[tx][mb * 2 + h] = __builtin_bit_cast(bf16x8_t, CV_LD16(a_win + A_BYTES + a_offx32[tx][h] + mb * 32 * CV_ROW));
-                        }
-                return;
-            }
 #pragma unroll
             for (int tx = 0; tx < 3; ++tx)
 #pragma unroll
                 for (int m = 0; m < MF; ++m) {
-                    ah[tx][m] = __builtin_bit_cast(bf16x8_t, CV_LD16(a_win + a_offx[tx] + m * 16 * CV_ROW));
-                    al[tx][m] = __builtin_bit_cast(bf16x8_t, CV_LD16(a_win + A_BYTES + a_offx[tx] + m * 16 * CV_ROW));
+                    ah[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + a_offx[tx] + m * 16 * CV_ROW));
+                    al[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + A_BYTES + a_offx[tx] + m * 16 * CV_ROW));
                 }
         };
         auto mfmas = [&](const bf16x8_t (&xh)[MF], const bf16x8_t (&xl)[MF]) {
             __builtin_amdgcn_s_setprio(1);
-            if constexpr (M32) {
-                // small terms first; consecutive MFMAs write different accumulators (4 blocks between two updates of one)
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) acc32[mb][nb] = cv_mma32(xl[mb * 2 + h], fbh[nb * 2 + h], acc32[mb][nb]);
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) acc32[mb][nb] = cv_mma32(xh[mb * 2 + h], fbl[nb * 2 + h], acc32[mb][nb]);
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) acc32[mb][nb] = cv_mma32(xh[mb * 2 + h], fbh[nb * 2 + h], acc32[mb][nb]);
-            } else {
-#if defined(CONV_ABL) && (CONV_ABL & 8)
-            if (false)
-#endif
 #pragma unroll
             for (int n = 0; n < NFW; ++n) {
 #pragma unroll
@@ -1245,7 +712,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
 #pragma unroll
                 for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], fbh[n], acc[m][n]);
             }
-            }
             __builtin_amdgcn_s_setprio(0);
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -1254,47 +720,37 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");                    \
         __builtin_amdgcn_s_barrier();
         const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
-#ifdef CONV_ABL
-        // timing ablations, compile-time (hipcc -DMAGNET_DEV -DCONV_ABL=bits; results are wrong): 1 no DMA inside the loop, 2 no weight-fragment
-        // reads, 4 no window reads, 8 no MFMAs
-        constexpr bool abl_dma = (CONV_ABL & 1) != 0, abl_b = (CONV_ABL & 2) != 0, abl_a = (CONV_ABL & 4) != 0;
-#else
-        constexpr bool abl_dma = false, abl_b = false, abl_a = false;
-#endif
         dma_a();
         dma_b(0);
         dma_b(1);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP) : "memory");                 // window 0 and stage 0 landed (this wave's pieces)
         __builtin_amdgcn_s_barrier();
         if (grp == 1) __builtin_amdgcn_s_barrier();           // group 1 runs one barrier (= half a sub-step) behind group 0
-        if constexpr (abl_a) load_win();
-        if constexpr (abl_b) load_b(0);
         for (int g = 0; g < ngroups; ++g) {
             const bool lastg = g + 1 == ngroups;
             // ---- tx = 0 ----
             asm volatile("" ::: "memory");
-            if constexpr (!abl_a) load_win();
-            if constexpr (!abl_b) load_b(0);
-            if constexpr (!abl_dma) dma_b(2);                           // stage 3g + 2
+            load_win();
+            load_b(0);
+            dma_b(2);                                         // stage 3g + 2
             CV_END_LOAD(BP)                                   // stage 3g + 1 landed
             mfmas(ah[0], al[0]);
             // ---- tx = 1 ----
             asm volatile("" ::: "memory");
-            if constexpr (!abl_b) load_b(1);
+            load_b(1);
             if (!lastg) {
-                if constexpr (!abl_dma) { dma_b(0); dma_a(); }          // stage 3g + 3, window g + 1
+                dma_b(0); dma_a();                            // stage 3g + 3, window g + 1
                 if (wv == 0) { CV_END_LOAD(BP + AP + 2) } else { CV_END_LOAD(BP + AP) }      // stage 3g + 2 landed
             } else { CV_END_LOAD(0) }
             mfmas(ah[1], al[1]);
             // ---- tx = 2 ----
             asm volatile("" ::: "memory");
-            if constexpr (!abl_b) load_b(2);
-            if (!lastg) { if constexpr (!abl_dma) dma_b(1); CV_END_LOAD(BP) }         // stage 3g + 4; stage 3g + 3 and window g + 1 landed
+            load_b(2);
+            if (!lastg) { dma_b(1); CV_END_LOAD(BP) }         // stage 3g + 4; stage 3g + 3 and window g + 1 landed
             else { CV_END_LOAD(0) }
             mfmas(ah[2], al[2]);
         }
 #undef CV_END_LOAD
-#undef CV_LD16
         if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
         __syncthreads();                                      // nothing in flight; the ring is dead
     } else
@@ -1354,46 +810,11 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         int a_offx[3];
 #pragma unroll
         for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
-        int a_offx32[3][2], b_off32[2];                      // M32: see the ping-pong loop above
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-#pragma unroll
-            for (int tx = 0; tx < 3; ++tx) a_offx32[tx][h] = cv_swz32(wm * 64 + (lane & 31) + tx * p.tap_sx, 2 * h + (lane >> 5));
-            b_off32[h] = cv_swz32(wn * 64 + (lane & 31), 2 * h + (lane >> 5));
-        }
         bf16x8_t ah[3][MF], al[3][MF];
         auto mfma_b = [&](int slot, const bf16x8_t (&xh)[MF], const bf16x8_t (&xl)[MF]) {
             const unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
             const unsigned char* sb_lo = sb_hi + B_BYTES;
             bf16x8_t fbh[NFW], fbl[NFW];
-            if constexpr (M32) {
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        fbh[nb * 2 + h] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off32[h] + nb * 32 * CV_ROW));
-                        fbl[nb * 2 + h] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off32[h] + nb * 32 * CV_ROW));
-                    }
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) acc32[mb][nb] = cv_mma32(xl[mb * 2 + h], fbh[nb * 2 + h], acc32[mb][nb]);
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) acc32[mb][nb] = cv_mma32(xh[mb * 2 + h], fbl[nb * 2 + h], acc32[mb][nb]);
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) acc32[mb][nb] = cv_mma32(xh[mb * 2 + h], fbh[nb * 2 + h], acc32[mb][nb]);
-                return;
-            }
 #pragma unroll
             for (int n = 0; n < NFW; ++n) {
                 fbh[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
@@ -1422,17 +843,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             // ---- tx = 0: stage 3g (slot 0) and window g have landed; refill slot 2 with stage 3g + 2 ----
             CV_WAIT_BARRIER(BP)
             dma_b(2);
-            if constexpr (M32) {
-#pragma unroll
-                for (int tx = 0; tx < 3; ++tx)
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            ah[tx][mb * 2 + h] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + a_offx32[tx][h] + mb * 32 * CV_ROW));
-                            al[tx][mb * 2 + h] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + A_BYTES + a_offx32[tx][h] + mb * 32 * CV_ROW));
-                        }
-            } else {
 #pragma unroll
             for (int tx = 0; tx < 3; ++tx)
 #pragma unroll
@@ -1440,7 +850,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                     ah[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + a_offx[tx] + m * 16 * CV_ROW));
                     al[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + A_BYTES + a_offx[tx] + m * 16 * CV_ROW));
                 }
-            }
             mfma_b(0, ah[0], al[0]);
             // ---- tx = 1: every wave holds window g in registers (lgkmcnt(0) before the barrier): fetch window g + 1 ----
             CV_WAIT_BARRIER(BP)
@@ -1536,70 +945,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             if (last_tx) { tx = 0; aslot ^= 1; a_of = a_offx[0]; }
             else { ++tx; a_of = tx == 1 ? a_offx[1] : a_offx[2]; }
         }
-    } else
-    if constexpr (PP) {
-        static_assert(NT == 512 && BN % RP == 0 && CV_BM % RP == 0 && A_PT + B_PT <= NFW, "ping-pong loop: 8 waves, whole DMA passes, one DMA pass per N fragment");
-        constexpr int GL = 2 * A_PT + 2 * B_PT;               // LDS-DMA instructions per wave and stage
-        // fragments of one stage: read in the LOAD phase, consumed in the COMPUTE phase
-        bf16x8_t fah[MF], fal[MF], fbh[NFW], fbl[NFW];
-        auto load_frags = [&](int buf) {
-            const unsigned char* sa_hi = smem + buf * STAGE_BYTES;
-            const unsigned char* sa_lo = sa_hi + A_BYTES;
-            const unsigned char* sb_hi = sa_hi + 2 * A_BYTES;
-            const unsigned char* sb_lo = sb_hi + B_BYTES;
-#pragma unroll
-            for (int m = 0; m < MF; ++m) {
-                fah[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_hi + a_off + m * 16 * CV_ROW));
-                fal[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_lo + a_off + m * 16 * CV_ROW));
-            }
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                fbh[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-                fbl[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
-            }
-        };
-        const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
-        if (0 < nsteps) CV_DMA(0, 0)
-        if (1 < nsteps) CV_DMA(1, 1)
-        if (nsteps > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");   // stage 0 landed (this wave's pieces)
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                         // ... and every other wave's
-        if (grp == 1) __builtin_amdgcn_s_barrier();           // group 1 runs one barrier (= half a step) behind group 0
-        int slot = 0;
-        for (int s = 0; s < nsteps; ++s) {
-            // ---- LOAD phase (the other group computes meanwhile) ----
-            asm volatile("" ::: "memory");
-            load_frags(slot);
-            // refill the slot last read one step ago: both groups' reads of it retired (lgkmcnt(0)) before barriers this wave
-            // has passed since.  (Issuing the DMA pieces between the MFMAs of the compute phase instead was measured slower:
-            // 6.15 vs 5.83 ms of convolutions per C2 step.)
-            const int nslot = slot == 0 ? 2 : slot - 1;       // (slot + 2) % 3
-            if (s + 2 < nsteps) {
-                CV_DMA(s + 2, nslot)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");             // stage s+1 landed; stage s+2 stays in flight
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            // ---- COMPUTE phase ----
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(fal[m], fbh[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(fah[m], fbl[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(fah[m], fbh[n], acc[m][n]);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            slot = slot == 2 ? 0 : slot + 1;
-        }
-        if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
-        __syncthreads();                                      // nothing in flight (last waits were vmcnt(0)): the ring is dead
     } else {
 #pragma unroll
     for (int q = 0; q < SPB; ++q)
@@ -1624,29 +969,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                       "the fused tail is written for 128-channel tiles with 32 rows per wave");
         unsigned char* act_hi = smem;                                   // [CV_BM rows][256 B]; the K ring is dead (barrier above)
         unsigned char* act_lo = smem + CV_BM * 256;
-        if constexpr (M32) {
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {          // C^T blocks (cv_mma32): registers 4 g4 .. 4 g4 + 3 = 4 consecutive channels of one row
-                        const int trow = wm * 64 + mb * 32 + (lane & 31);
-                        const int ch = wn * 64 + nb * 32 + g4 * 8 + (lane >> 5) * 4;
-                        float v[4] = {acc32[mb][nb][g4 * 4 + 0], acc32[mb][nb][g4 * 4 + 1], acc32[mb][nb][g4 * 4 + 2], acc32[mb][nb][g4 * 4 + 3]};
-                        const float4 b4 = *reinterpret_cast<const float4*>(p.bias + ch);
-                        v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
-                        if (p.relu) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = v[r] < 0.f ? 0.f : v[r];
-                        }
-                        uint32_t h01, l01, h23, l23;
-                        split_bf16x2(v[0], v[1], h01, l01); split_bf16x2(v[2], v[3], h23, l23);
-                        const int off = act_swz(trow, ch >> 3) + (ch & 7) * 2;
-                        *reinterpret_cast<uint2*>(act_hi + off) = make_uint2(h01, h23);
-                        *reinterpret_cast<uint2*>(act_lo + off) = make_uint2(l01, l23);
-                    }
-        } else
 #pragma unroll
         for (int m = 0; m < MF; ++m)
 #pragma unroll
@@ -1667,42 +989,29 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                 *reinterpret_cast<uint2*>(act_lo + off) = make_uint2(l01, l23);
             }
         __syncthreads();
-        if constexpr ((NT == 256 && CV_BM == 128) || (NT == 512 && CV_BM == 256)) {
-            if (!(p.variant & 32)) {                          // dev (MAGNET_CONV_VARIANT=32): the row-owned tail below
-                constexpr int NW = NT / 64;
-                tail_layer_cols<8, false, CV_BM, NW>(p.tail_w_hi, p.tail_w_lo, p.tail_bias, act_hi, act_lo, nullptr, 0, row0, p.rows, lane, wv);
-                tail_layer_cols<8, false, CV_BM, NW>(p.tail_w_hi + 128 * 128, p.tail_w_lo + 128 * 128, p.tail_bias + 128, act_hi, act_lo, nullptr,
-                                                     0, row0, p.rows, lane, wv);
-                if constexpr (TAIL == 9) {
-                    if (p.up_out) {                           // fused convex upsampling: the 144 logits meet in LDS, never in HBM
-                        tail_layer_cols<9, true, CV_BM, NW, true>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi,
-                                                                  act_lo, nullptr, 0, row0, p.rows, lane, wv,
-                                                                  UpArgs{p.up_depth, p.up_out, p.up_npred, p.up_h, p.up_w, p.up_B});
-                        return;
-                    }
-                }
-                tail_layer_cols<TAIL, true, CV_BM, NW>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi, act_lo,
-                                                       p.out_f32, p.tail_cout, row0, p.rows, lane, wv,
-                                                       (TAIL == 1 && p.gu_out) ? UpArgs{p.gu_in, p.gu_out, -1, p.up_h, p.up_w, p.up_B} : UpArgs{nullptr, nullptr, 0, 0, 0, 0});
+        constexpr int NW = NT / 64;
+        tail_layer_cols<8, false, CV_BM, NW>(p.tail_w_hi, p.tail_w_lo, p.tail_bias, act_hi, act_lo, nullptr, 0, row0, p.rows, lane, wv);
+        tail_layer_cols<8, false, CV_BM, NW>(p.tail_w_hi + 128 * 128, p.tail_w_lo + 128 * 128, p.tail_bias + 128, act_hi, act_lo, nullptr,
+                                             0, row0, p.rows, lane, wv);
+        if constexpr (TAIL == 9) {
+            if (p.up_out) {                           // fused convex upsampling: the 144 logits meet in LDS, never in HBM
+                tail_layer_cols<9, true, CV_BM, NW, true>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi,
+                                                          act_lo, nullptr, 0, row0, p.rows, lane, wv,
+                                                          UpArgs{p.up_depth, p.up_out, p.up_npred, p.up_h, p.up_w, p.up_B});
                 return;
             }
         }
-        tail_layer<8, false>(p.tail_w_hi, p.tail_w_lo, p.tail_bias, act_hi, act_lo, nullptr, 0, row0, p.rows, lane, wv);
-        tail_layer<8, false>(p.tail_w_hi + 128 * 128, p.tail_w_lo + 128 * 128, p.tail_bias + 128, act_hi, act_lo, nullptr, 0, row0,
-                             p.rows, lane, wv);
-        tail_layer<TAIL, true>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi, act_lo, p.out_f32,
-                               p.tail_cout, row0, p.rows, lane, wv);
+        tail_layer_cols<TAIL, true, CV_BM, NW>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi, act_lo,
+                                               p.out_f32, p.tail_cout, row0, p.rows, lane, wv,
+                                               (TAIL == 1 && p.gu_out) ? UpArgs{p.gu_in, p.gu_out, -1, p.up_h, p.up_w, p.up_B} : UpArgs{nullptr, nullptr, 0, 0, 0, 0});
         return;
     }
 
-#ifdef MAGNET_DEV
-    if (p.variant & 8192) return;                              // dev timing ablation (tools/conv_kscale.py): no epilogue
-#endif
     // ---- epilogue through LDS, one 16-row fragment per wave at a time: [16 rows][NFW*16] fp32 per wave ----
-    // Round 4 (tools/conv_kscale.py, profiles/r4/conv_no_epilogue.log): of the 8-wave kernel's 0.16 ms that do not depend on K (10 % of
+    // Round 4 (profiles/r4/conv_no_epilogue.log): of the 8-wave kernel's 0.16 ms that do not depend on K (10 % of
     // the launch at K = 9 x 256), 0.13 ms is this epilogue = 6.6 us per tile = the tile's 128 KB at ~20 GB/s per CU — x 256 CUs in
     // lockstep (one workgroup per CU, equal tile times) 5 - 6 TB/s: the stores of all tiles arrive as ONE burst at the fabric's write
-    // rate while the matrix pipes idle.  Tried against it: (1) persistent workgroups (see conv_mfma_kernel; no gain: a wave's loads and
+    // rate while the matrix pipes idle.  Tried against it: (1) persistent workgroups (profiles/r4/conv_persistent_ab.log; no gain: a wave's loads and
     // stores share vmcnt, so the next tile's first counted wait still drains the stores); (2) start skew of the first-round workgroups
     // by eighths of a tile time (conv_start_skew.log: fixed part 0.162 -> 0.118 ms, but the late starters end the launch late: +3 % at
     // K = 9 x 512, -2.6 % at K = 9 x 64, a wash at the G-Net shapes); (3) C^T accumulators stored straight from registers, no LDS stage
@@ -1803,96 +1112,46 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
 #endif
 }
 
-// PERSIST (round 4, dev only): one workgroup per CU walks the tiles bid, bid + gridDim.x, ... instead of one workgroup per tile.
-// tools/conv_kscale.py splits the 8-wave kernel's launch time into 182 us per 32-channel group (507 TFLOP/s fp32-equivalent inside the K
-// loop) + 0.16 - 0.20 ms that do not depend on K (10 - 12 % at K = 9 x 256: ~10 us per tile).  The bet was that those are workgroup
-// relaunch, kernel-argument loads and the drain of the epilogue's stores, which a persistent loop removes (no vmcnt wait between tiles:
-// the K loops' counted waits only get stricter with stores outstanding).  Measured (profiles/r4/conv_persistent_ab.log): 1.616 vs
-// 1.604 ms at K = 9 x 256, 2.134 vs 2.118 / 1.950 vs 1.914 ms on the two fused-tail stacks — the hardware's own relaunch already costs
-// nothing; the fixed part is the tile's exposed first-stage DMA latency, the ping-pong ramp and the epilogue, which only a next-tile
-// prefetch issued BEFORE the epilogue could hide (LDS for it exists only in the TAIL = 0 kernel).  Kept for that experiment.
-template <int NF, int WN, int CV_BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0, bool PERSIST = false, bool M32 = false>
+template <int NF, int WN, int CV_BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0>
 __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const ConvParams p) {
-    if constexpr (PERSIST) {
-        const unsigned n_tiles = (unsigned)((p.rows + CV_BM - 1) / CV_BM);     // (loop-invariant hoisting is the trap of this form: see below)
-        for (unsigned t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-            // the tail's weight / bias loads have the same addresses for every tile: opaque pointers per trip, or the compiler hoists
-            // hundreds of registers of them out of this loop (first version: 1.2 - 2 KB of scratch per lane)
-            ConvParams q = p;
-            asm volatile("" : "+s"(q.tail_w_hi), "+s"(q.tail_w_lo), "+s"(q.tail_bias), "+s"(q.bias), "+s"(q.w_hi), "+s"(q.w_lo));
-            // ... and an opaque thread id: every per-lane constant of a tile (fragment offsets, DMA offsets, the tails' column indices) is
-            // the same for each tile, and hoisted out of the loop they would all be live across it
-            int tid = threadIdx.x;
-            asm volatile("" : "+v"(tid));
-            conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN, M32>(q, t, n_tiles, blockIdx.y, tid);
-            // the epilogue's LDS reads (staging rows, the tail's activation tile) retire before any wave's next-tile DMA lands
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-    } else {
-        conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN, M32>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
-    }
+    conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
 }
 
 template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0>
 static size_t conv_lds_bytes() {
     const size_t tiles = (WIN == 4 && PP) ? 2 * (2 * (size_t)(BM + 8) * CV_ROW + 512 * 4) + 4 * (size_t)(NF * 16) * CV_ROW + 2 * (3 * (size_t)(NF * 16) * CV_ROW + 512 * 4 + 16)
-                       : (WIN == 3 && PP) ? 4 * (size_t)(BM + 8) * CV_ROW + 4 * 2 * (size_t)(NF * 16) * CV_ROW
-                       : (WIN == 1 && PP) ? 4 * (size_t)(BM + 8) * CV_ROW + 3 * 2 * (size_t)(NF * 16) * CV_ROW
-                       : (WIN == 5 && PP) ? 4 * (size_t)(BM + 8) * CV_ROW + 4 * 2 * (size_t)(NF * 16) * CV_ROW
                        : WIN == 2 ? 2 * (size_t)(BM + 8) * CV_ROW + 3 * 2 * (size_t)(NF * 16) * CV_ROW
-                                  : (PP ? 3 : 2 * SPB) * (2 * (size_t)(WIN ? BM + 8 : BM) * CV_ROW + 2 * (size_t)(NF * 16) * CV_ROW);
+                                  : 2 * SPB * (2 * (size_t)(WIN ? BM + 8 : BM) * CV_ROW + 2 * (size_t)(NF * 16) * CV_ROW);
     const size_t stage = (size_t)(NT / 64) * 16 * ((NF / WN) * 16 + 4) * 4;
     return tiles > stage ? tiles : stage;
 }
 
-static int conv_cu_count() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
-template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0, bool PERSIST = false, bool M32 = false>
+template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0>
 static hipError_t launch_conv_nf(const ConvParams& p, hipStream_t s) {
     dim3 grid((unsigned)((p.rows + BM - 1) / BM), (unsigned)(p.cout_pad / (NF * 16))), block(NT);
     size_t lds = conv_lds_bytes<NF, WN, BM, SPB, NT, PP, WIN>();
     if (TAIL > 0 && lds < (size_t)BM * 512) lds = (size_t)BM * 512;     // the fused tail's activation tile: BM rows x 256 B x (hi, lo)
     if (TAIL == 9 && lds < (size_t)128 * 148 * 4) lds = (size_t)128 * 148 * 4;   // fused upsampling: 128 rows x 144 logits (+4 pad) fp32 (two 4-wave workgroups still fit a CU)
-    if (PERSIST) {
-        // one workgroup per CU (these tiles take more than half a CU's LDS); a multiple of 8 keeps a workgroup's tiles on one XCD
-        unsigned ncu = (unsigned)conv_cu_count() / 8 * 8;
-        if (ncu == 0) ncu = 8;
-        if (grid.x > ncu) grid.x = ncu;
-    }
     static bool attr_set = false;
     if (!attr_set && lds > 64 * 1024) {          // > 64 KiB of dynamic LDS needs the opt-in attribute
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN, PERSIST, M32>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN, PERSIST, M32>), grid, block, lds, s, p);
+    hipLaunchKernelGGL((conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>), grid, block, lds, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
+    // p.variant is 0 in the product library; the dev library takes it from MAGNET_CONV_VARIANT.  Each bit only moves a launch to an
+    // instance that other shapes reach anyway: 1 = no row window, 8 = the 2-slot LDS window instead of the register window, 16 = the
+    // 4-wave register-window loop where the 8-wave one is the default, 256 / 2048 = the 8-wave loop for addend / split-bf16 launches.
     // 128 channels: 2x2 waves of 64x64 on a 128-row tile.
     // Measured alternatives on the G-Net 3x3 layer (64 frames; this configuration: 2.31 ms): 64-row tile / 3 workgroups
     // per CU 2.80 ms; two K stages per barrier (4-stage ring, 128 KB LDS, 1 workgroup per CU) 3.51 ms; 256-row tile
     // (1 workgroup per CU) 3.45 ms.  The kernel lives on inter-workgroup overlap: keep 2 workgroups per CU.
-    const bool pp = (p.variant & 2) != 0;        // dev (MAGNET_CONV_VARIANT=2): the 8-wave ping-pong K loop — measured equal to the
-                                                 // default 4-wave / 2-slot loop (5.83 vs 5.91 ms per C2 step), so it is not the default
     if (p.tail_w_hi) {                           // 3x3 (or 1x1) 128-wide layer + its three 1x1 successors in one kernel
         if (p.cout_pad != 128) return hipErrorInvalidValue;
-        if ((p.variant & 32) && (p.up_out || p.gu_out)) return hipErrorInvalidValue;   // dev: the row-owned tail has no fused update / upsampling
-        if (pp) {
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true>(p, s);
-        }
         if (p.in_sc) {                                          // round 4: fp16 + block-scaled e4m3 operand format (see the WIN == 4 loop)
             if (p.tap_n != 3 || !p.w_sc || p.rows < 256ll * 256 || p.addend) return hipErrorInvalidValue;
             if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 4>(p, s);
@@ -1900,60 +1159,18 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
             if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 4>(p, s);
             return hipErrorInvalidValue;
         }
-        const bool win = p.tap_n > 1 && !(p.variant & 1);       // dev (MAGNET_CONV_VARIANT=1): one A stage per tap
-        if (win && (p.variant & 4)) {                           // dev (MAGNET_CONV_VARIANT=4): 256-row tile, 8 waves, one workgroup per CU
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, false, 1>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, false, 1>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, false, 1>(p, s);
-        }
-        if (win && p.tap_n == 3 && (p.variant & 128) && (p.cin / 32) % 2 == 0) {   // dev (MAGNET_CONV_VARIANT=128): + fragment double-buffering
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 3>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 3>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 3>(p, s);
-        }
-        if (win && p.tap_n == 3 && (p.variant & 64)) {          // dev (MAGNET_CONV_VARIANT=64): ping-pong x 2-slot LDS window, 256-row tile
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 1>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 1>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 1>(p, s);
-        }
+        const bool win = p.tap_n > 1 && !(p.variant & 1);
         // default: ping-pong x register window, 256-row tile, 8 waves — when there is at least one such tile per CU (256 CUs);
         // fewer rows (single-frame inference: 78 tiles at 120x160) spread better as 128-row tiles of the 4-wave kernel
         // — and not for the per-iteration launches of a hoisted first layer (fp32 addend, K = 9 x 32 .. 9 x 64): those are short K
         // loops between an exposed 128 KB addend load and the tail, where two co-resident 4-wave workgroups overlap better than one
         // 8-wave workgroup (same-box A/B: 425 vs 464 us at K = 288, 766 vs 804 us at K = 576)
-        if (win && p.tap_n == 3 && !(p.variant & (16 | 8)) && p.rows >= 256ll * 256 && !p.addend && (p.variant & 512)) {   // dev (MAGNET_CONV_VARIANT=512): round 4's deeper-prefetch loop (double-buffered window, 4-slot weight ring) — measured 4 % SLOWER (2.19 vs 2.10 ms): the LOAD phases are not waiting for the DMA
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 5>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 5>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 5>(p, s);
-        }
-        if (win && p.tap_n == 3 && !(p.variant & (16 | 8)) && p.rows >= 256ll * 256 && (!p.addend || (p.variant & 256))) {   // dev (MAGNET_CONV_VARIANT=256): 8-wave form for addend launches too
-                                                                // dev (MAGNET_CONV_VARIANT=16): the 4-wave register-window loop below
-#ifdef MAGNET_DEV
-            if (p.variant & 4096) {                             // dev (MAGNET_CONV_VARIANT=4096): persistent workgroups (see conv_mfma_kernel): 0.7 % SLOWER
-                if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 2, true>(p, s);
-                if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 2, true>(p, s);
-                if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 2, true>(p, s);
-            }
-#endif
-#ifdef MAGNET_DEV
-            if (p.variant & 16384) {                            // dev (MAGNET_CONV_VARIANT=16384): round 5's 32x32x16 form (M32_), measured 5.5 % SLOWER
-                if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 2, false, true>(p, s);
-                if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 2, false, true>(p, s);
-                if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 2, false, true>(p, s);
-            }
-#endif
+        if (win && p.tap_n == 3 && !(p.variant & (16 | 8)) && p.rows >= 256ll * 256 && (!p.addend || (p.variant & 256))) {
             if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 2>(p, s);
             if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 2>(p, s);
             if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 2>(p, s);
         }
-        if (win && p.tap_n == 3 && !(p.variant & 8)) {          // dev (MAGNET_CONV_VARIANT=8): the 2-slot window loop below
-#ifdef MAGNET_DEV
-            if (p.variant & 16384) {                            // (the 4-wave kernel in the same form: a frame gives the same bits alone and in a batch)
-                if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 128, 1, 1, 256, false, 2, false, true>(p, s);
-                if (p.tail_cout == 128) return launch_conv_nf<8, 2, 128, 1, 8, 256, false, 2, false, true>(p, s);
-                if (p.tail_cout == 144) return launch_conv_nf<8, 2, 128, 1, 9, 256, false, 2, false, true>(p, s);
-            }
-#endif
+        if (win && p.tap_n == 3 && !(p.variant & 8)) {
             if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 128, 1, 1, 256, false, 2>(p, s);
             if (p.tail_cout == 128) return launch_conv_nf<8, 2, 128, 1, 8, 256, false, 2>(p, s);
             if (p.tail_cout == 144) return launch_conv_nf<8, 2, 128, 1, 9, 256, false, 2>(p, s);
@@ -1968,29 +1185,19 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
         if (p.tail_cout == 144) return launch_conv_nf<8, 2, 128, 1, 9>(p, s);
         return hipErrorInvalidValue;
     }
-    // (the 8-wave ping-pong form of this loop, the default of the fused-tail kernels above, is no faster on the F-Net's plain
-    // 128-wide layers: 18.93 vs 18.79 ms per 40 images)
     // the loop-invariant x_d3 part of G-Net's first layer (fp32 partial sums, I >= 2): the fused-tail kernels' 8-wave ping-pong x
     // register-window loop (same-box: C3 step -1 %); on the F-Net's plain 128-wide layers (split-bf16 outputs) it is equal to the
     // 4-wave loop (18.64 - 18.72 vs 18.69 - 18.75 ms per 40 images; dev MAGNET_CONV_VARIANT=2048 forces it there)
     if (p.cout_pad == 128 && p.tap_n == 3 && (p.out_mode == 1 || (p.variant & 2048)) && !(p.variant & (16 | 9)) && p.rows >= 256ll * 256 && !p.add_hi && !p.img_rows)
-    {
-#ifdef MAGNET_DEV
-        if (p.variant & 4096) return launch_conv_nf<8, 2, 256, 1, 0, 512, true, 2, true>(p, s);
-#endif
         return launch_conv_nf<8, 2, 256, 1, 0, 512, true, 2>(p, s);
-    }
-    if (p.cout_pad % 128 == 0 && p.tap_n == 3 && !(p.variant & 9) && !pp) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 2>(p, s);
-    if (p.cout_pad % 128 == 0 && p.tap_n > 1 && !(p.variant & 1) && !pp) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 1>(p, s);
-    if (p.cout_pad % 128 == 0 && pp) return launch_conv_nf<8, 2, 256, 1, 0, 512, true>(p, s);
+    if (p.cout_pad % 128 == 0 && p.tap_n == 3 && !(p.variant & 9)) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 2>(p, s);
+    if (p.cout_pad % 128 == 0 && p.tap_n > 1 && !(p.variant & 1)) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 1>(p, s);
     if (p.cout_pad % 128 == 0) return launch_conv_nf<8, 2, 128, 1>(p, s);
     if (p.cout_pad == 144) return launch_conv_nf<9, 1, 128, 1>(p, s);
     if (p.cout_pad == 16)  return launch_conv_nf<1, 1, 128, 1>(p, s);
     // F-Net trunk widths: 4 waves stacked along M.  Measured on the whole F-Net (40 images, 23.5 ms): 256-row tiles for
     // the 32- / 64-wide layers 24.1 / 24.2 ms, 192-row tile for 64-wide 24.6 ms, 2x2 waves for 64-wide 23.6 ms — no better.
-    // 32- and 64-wide 3x3 layers of the trunk: the register-window loop too (their A operand is 2/3 of the DMA pieces of a K
-    // step); dev
-    // (MAGNET_CONV_VARIANT=8): one A stage per tap
+    // 32- and 64-wide 3x3 layers of the trunk: the register-window loop too (their A operand is 2/3 of the DMA pieces of a K step)
     // (round 3, with the register window: 256-row tiles = 64 rows per wave for the 64-wide layers 18.5 vs 18.0 ms per 40 images, for the
     // 32-wide ones 18.1 vs 18.0 — their fragment-read share was not the limit; not kept)
     if (p.cout_pad == 32 && p.tap_n == 3 && !(p.variant & 9))  return launch_conv_nf<2, 1, 128, 1, 0, 256, false, 2>(p, s);

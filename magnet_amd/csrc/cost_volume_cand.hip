@@ -71,14 +71,13 @@ constexpr uint32_t KEY_CLOSED = 0xffffffffu;
 // DL   = candidates per pixel group inside a wave (8,16,32,64); PPW = 64/DL pixels per iteration
 // CPL  = 16-byte channel chunks per lane in the correlation (F*sizeof(FeatT)/16 <= 8*CPL), FULL = exactly
 // MINW = waves per SIMD to compile for; VAR = compile-time specialisation: 0 generic matcher (run-time options), 1 est_costvolume_F
-// mode, 2 production matcher (candidates sampled in-kernel, no stats counters, no dev ablations): fewer scalar tests and live registers
+// mode, 2 production matcher (candidates sampled in-kernel, no stats counters): fewer scalar tests and live registers
 template <typename FeatT, int DL, int CPL, bool FULL, int MINW, int VAR, int LPU = 8>
 __global__ __launch_bounds__(256, MINW) void cv_cand_kernel(const CvParams p) {
     constexpr int IPP = 64 / (4 * LPU);                   // items per correlation pass: LPU lanes per (item, tap) unit
     constexpr int CSTR = LPU * 16;                        // byte stride between a lane's channel chunks
     constexpr bool MODEF = VAR == 1;                      // est_costvolume_F semantics
-    constexpr bool FASTV = VAR == 2;                      // production matcher: sampled candidates, no stats, no dev ablations
-    const int abl = FASTV ? 0 : CV_DEV(p);
+    constexpr bool FASTV = VAR == 2;                      // production matcher: sampled candidates, no stats
     uint32_t* const stats = FASTV ? nullptr : p.stats;
     const float* const d_volume = FASTV ? nullptr : p.d_volume;
     constexpr int PPW = 64 / DL;
@@ -206,15 +205,14 @@ __global__ __launch_bounds__(256, MINW) void cv_cand_kernel(const CvParams p) {
                 // tap registers: only leader lanes' values are ever read (through ds_bpermute); declared per iteration so that
                 // they are not carried around the loop (8 VGPRs less during the correlation)
                 CGmmPair g0 = {0.f, 0.f, 0.f, 0.f}, g1 = {0.f, 0.f, 0.f, 0.f};
-                if (lead && !(abl & 2) && !MODEF) {
+                if (lead && !MODEF) {
                     g0 = *reinterpret_cast<const CGmmPair*>(sgm + qi * 8u);
                     g1 = *reinterpret_cast<const CGmmPair*>(sgm + (qi + (uint32_t)Wp) * 8u);
                 }
                 // gate = inwin && |z - mu_w| < kappa sigma_w (homography.py:157-158), evaluated from the leaders' tap registers.
-                // Dev option (path bit 16 << 8): SPECULATIVE order — correlate every distinct IN-IMAGE quad and apply the gate
-                // when the result is accumulated, so the feature loads do not wait for the (mu,sigma) taps (one memory round
-                // trip per iteration instead of two).  Same results; measured SLOWER (C2 1.97 vs 1.89 ms, D=5 0.88 vs 0.67,
-                // C4 2.10 vs 1.65): the extra (item, tap) dot products cost more than the round trip saves.
+                // (A speculative order — correlate every distinct IN-IMAGE quad and apply the gate when the result is accumulated, one
+                // memory round trip per iteration instead of two — gave the same results and measured SLOWER: C2 1.97 vs 1.89 ms,
+                // D=5 0.88 vs 0.67, C4 2.10 vs 1.65; the extra (item, tap) dot products cost more than the round trip saves.)
                 bool gate = false;
                 auto eval_gate = [&]() {
                     const unsigned long long lb = __ballot(lead);
@@ -232,21 +230,17 @@ __global__ __launch_bounds__(256, MINW) void cv_cand_kernel(const CvParams p) {
                     const float mu_w = bilerp(g0.mu0, g0.mu1, g1.mu0, g1.mu1, t);
                     const float sg_w = bilerp(g0.sg0, g0.sg1, g1.sg0, g1.sg1, t);
                     gate = inwin && (__builtin_fabsf(zw - mu_w) < sg_w * p.kappa);    // homography.py:157-158
-                    if (abl & 2) gate = inwin && ((j0 & 3) != 0);                // dev: taps skipped, ~75 % open
-                    if (abl & 8) gate = false;                                   // dev: geometry only
                     if (MODEF) gate = inwin;                                       // est_costvolume_F has no gate
                 };
-                const bool spec = (abl & 16) && !(abl & 8);
-                if (!spec) eval_gate();
+                eval_gate();
                 if (!FASTV && !MODEF && p.gate_bits && live)                      // debug output of the gate bits (parity tests)
                     p.gate_bits[(((size_t)b * p.V + v) * p.D + j) * hw + (size_t)y * p.w + x] = gate ? 1 : 0;
-                const bool open = spec ? inwin : gate;                               // lanes whose quad becomes an item
 
                 // ---------------- distinct open quads of the wave -> items ----------------
-                const uint32_t key = open ? qi : KEY_CLOSED;
+                const uint32_t key = gate ? qi : KEY_CLOSED;                        // open lanes: their quad becomes an item
                 uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)KEY_CLOSED, (int)key, 0x138, 0xf, 0xf, false);  // wave_shr:1
                 if (j0 == 0) prev = KEY_CLOSED;                                   // first candidate of a pixel group
-                const bool fresh = open && (key != prev);
+                const bool fresh = gate && (key != prev);
                 const unsigned long long bal = __ballot(fresh);
                 const int nitems = __popcll(bal);
                 if (nitems == 0) continue;                                        // wave-uniform: nothing open in this view
@@ -259,12 +253,12 @@ __global__ __launch_bounds__(256, MINW) void cv_cand_kernel(const CvParams p) {
                 wave_lds_fence();
 
                 // ---------------- correlation: unit = (item, tap), 8 lanes x 16 B per unit ----------------
-                const int passes = (abl & 1) ? 0 : (nitems + IPP - 1) / IPP;  // IPP items (4*IPP units) per pass
+                const int passes = (nitems + IPP - 1) / IPP;                  // IPP items (4*IPP units) per pass
                 for (int ps = 0; ps < passes; ps += 2) {
                     uint4 sv[2][CPL], rv[2][CPL];
                     // second pass of the pair only if it holds an item (wave-uniform): at ~3.5 items per (pixel, view) a third of
                     // the iterations need one pass
-                    const bool second = (IPP * (ps + 1) < nitems) || (abl & 32);
+                    const bool second = IPP * (ps + 1) < nitems;
 #pragma unroll
                     for (int a = 0; a < 2; ++a) {
                         if (a == 1 && !second) break;
@@ -294,8 +288,7 @@ __global__ __launch_bounds__(256, MINW) void cv_cand_kernel(const CvParams p) {
                 }
                 wave_lds_fence();
 
-                // ---------------- gate (speculative order), bilinear combine + fp64 view accumulation ----------------
-                if (spec) eval_gate();
+                // ---------------- bilinear combine + fp64 view accumulation ----------------
                 if (gate) {
                     const float4 c4 = *reinterpret_cast<const float4*>(ctab + myitem * 4);
                     const float c = bilerp(c4.x, c4.y, c4.z, c4.w, t);

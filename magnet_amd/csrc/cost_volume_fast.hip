@@ -37,17 +37,18 @@ namespace magnet {
 // DL   = candidates per pixel group inside a wave (8,16,32,64); PPW = 64/DL pixels per iteration
 // CPL  = 16-byte channel chunks per lane in the VALU correlation (F*sizeof(FeatT)/16 <= LPU*CPL), FULL = exactly
 // MINW = waves per SIMD to compile for; LPU = lanes per texel of the VALU correlation
-// OPT  = bit 1: write gate bits (debug / parity tests); bit 2: texel-pair items (the product form; quad items are kept for dev A/B)
+// OPT  = bit 1: write gate bits (debug / parity tests); bit 2: always set (texel-pair items; the quad-item form of rounds 2 - 4 is in the
+//        history, the bit keeps the instances' symbol names)
 template <typename FeatT, int DL, int CPL, bool FULL, int MINW, int LPU, int OPT>
 __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
     constexpr bool GBITS = (OPT & 2) != 0;
-    constexpr bool TX = (OPT & 4) != 0;
-    constexpr int TPI = TX ? 2 : 4;                       // texels per item
+    static_assert((OPT & 4) != 0, "texel-pair items only");
+    constexpr int TPI = 2;                                // texels per item
     constexpr int IPP = 64 / (TPI * LPU);                 // items per correlation pass
     constexpr int CSTR = LPU * 16;                        // byte stride between a lane's channel chunks (VALU correlation)
     constexpr int PPW = 64 / DL;
-    constexpr int CT_BYTES = TX ? (128 + 2) * 8 : 16 + 1024;          // TX: [2 zero pairs | 128 pairs] x {c0, c1}; else [zero | 64 items] x 4 taps
-    constexpr int IT_BYTES = TX ? (128 + 2) * 8 : 272;                // TX: {byte offset of texel 0, of texel 1} (+ pixel in the low bits); else texel index (+ pixel)
+    constexpr int CT_BYTES = (128 + 2) * 8;               // [2 zero pairs | 128 pairs] x {c0, c1}
+    constexpr int IT_BYTES = (128 + 2) * 8;               // {byte offset of texel 0, of texel 1} (+ pixel in the low bits)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -72,16 +73,15 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
     // Round 3: only the 8 pixels the next iterations work on are staged (re-staged once in the middle of the wave's 16): with 16 the
     // fp32 instances sat at 5 workgroups per CU by LDS, and the path is occupancy-sensitive (capped at 4 / 3: +11 % / +36 % time)
     const int ref_lds = PPW > 1 ? 8 * (int)texel_bytes : 0;
-    const int md_bytes = TX ? p.V * 64 : 0;
+    const int md_bytes = p.V * 64;
     const int wave_bytes = p.V * 512 + CT_BYTES + IT_BYTES + out_bytes + md_bytes + ref_lds;
     unsigned char* wbase = smem + wv * wave_bytes;
     unsigned char* refl = wbase + (wave_bytes - ref_lds);                             // [8 px][texel_bytes]
     float4*   pvtab = reinterpret_cast<float4*>(wbase);                               // [V][16 px][2]
-    float4*   ctab  = reinterpret_cast<float4*>(wbase + p.V * 512);                   // quad items: [zero slot for closed lanes | 64 items] x 4 taps
-    float2*   ctab2 = reinterpret_cast<float2*>(wbase + p.V * 512);                   // pair items: [2 zero slots | 128 pairs] x 2 texels
-    uint32_t* items = reinterpret_cast<uint32_t*>(wbase + p.V * 512 + CT_BYTES);      // quad items: [64 + pad]; pair items: [128 + pad] x 2
+    float2*   ctab2 = reinterpret_cast<float2*>(wbase + p.V * 512);                   // [2 zero slots for closed lanes | 128 pairs] x 2 texels
+    uint32_t* items = reinterpret_cast<uint32_t*>(wbase + p.V * 512 + CT_BYTES);      // [128 + pad] x 2
     float*    outb  = reinterpret_cast<float*>(wbase + p.V * 512 + CT_BYTES + IT_BYTES);   // [OUT_PX][DL] results of one block
-    uint32_t* mtab  = reinterpret_cast<uint32_t*>(wbase + p.V * 512 + CT_BYTES + IT_BYTES + out_bytes);   // TX: [V][16 px] travel mode | signed step << 2
+    uint32_t* mtab  = reinterpret_cast<uint32_t*>(wbase + p.V * 512 + CT_BYTES + IT_BYTES + out_bytes);   // [V][16 px] travel mode | signed step << 2
 
     // ---- depth-linear projection terms for the wave's 16 pixels x V views (once per tile row) ----
     for (int e = lane; e < 16 * p.V; e += 64) {
@@ -92,14 +92,11 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
         const PixelView pv = make_pixel_view(p.intM + (size_t)b * 9, p.poses + ((size_t)b * p.V + v) * 16, r0, r1, r2);
         pvtab[e * 2 + 0] = make_float4(pv.rpx, pv.rpy, pv.rpz, pv.rcz);
         pvtab[e * 2 + 1] = make_float4(pv.kt0, pv.kt1, pv.kt2, pv.tz);
-        if (TX) {
-            const uint32_t md = travel_mode(pv);
-            const int step = ((md & 1u) ? Wp : 1) * ((md & 2u) ? -1 : 1);             // key of the next quad along the direction of travel - this quad's key
-            mtab[e] = md | ((uint32_t)step << 2);
-        }
+        const uint32_t md = travel_mode(pv);
+        const int step = ((md & 1u) ? Wp : 1) * ((md & 2u) ? -1 : 1);                 // key of the next quad along the direction of travel - this quad's key
+        mtab[e] = md | ((uint32_t)step << 2);
     }
-    if (TX) { if (lane < 2) ctab2[lane] = make_float2(0.f, 0.f); }
-    else if (lane == 0) ctab[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < 2) ctab2[lane] = make_float2(0.f, 0.f);
     fwave_lds_fence();
 
     const int nchunk = (int)(texel_bytes / 16);
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
     // lane roles
     const int g = lane / DL, j0 = lane % DL;                                      // geometry: pixel group, candidate
     const int sub = lane & (LPU - 1), tap = (lane / LPU) & (TPI - 1), upair = lane / (TPI * LPU);   // correlation: chunk, texel of the item, item of the pass
-    const uint32_t lane_src_off = (TX ? 0u : (uint32_t)((tap & 1) + (tap >> 1) * Wp) * texel_bytes) + (uint32_t)sub * 16u;
+    const uint32_t lane_src_off = (uint32_t)sub * 16u;
     const uint32_t row_bytes = (uint32_t)Wp * texel_bytes;
     const unsigned char* __restrict__ ref_row = reinterpret_cast<const unsigned char*>(p.ref_feat) +
         ((size_t)b * hw + (size_t)yc * p.w) * texel_bytes;                        // reference features of this pixel row
@@ -177,7 +174,7 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
                 const cvr_gptr sgm = (cvr_gptr)(unsigned long long)v4_uniform_ptr((const void*)(sgm_b + (size_t)v * sgm_vstride));
                 // ---------------- geometry ----------------
                 const float4 pa = pvtab[(v * 16 + q) * 2 + 0], pb = pvtab[(v * 16 + q) * 2 + 1];
-                const uint32_t md = TX ? mtab[v * 16 + q] : 0u;
+                const uint32_t md = mtab[v * 16 + q];
                 const float Px = __builtin_fmaf(pa.x, d, pb.x);                  // homography.py:132
                 const float Py = __builtin_fmaf(pa.y, d, pb.y);
                 const float Pz = __builtin_fmaf(pa.z, d, pb.z);
@@ -213,28 +210,23 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
                 int incl = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
                                 __builtin_amdgcn_mbcnt_lo((uint32_t)bal, fresh ? 1u : 0u));         // leaders at or below this lane
                 float fmin = 0.f, fmaj = 0.f;
-                if (TX) {
-                    const bool rowm = (md & 1u) != 0, neg = (md & 2u) != 0;
-                    // a leader whose quad is the previous run's quad moved one step along the direction of travel shares that run's
-                    // second pair (FKEY_CLOSED + a step is no valid key)
-                    const bool shr = fresh && (prev + (uint32_t)((int)md >> 2) == key);
-                    const unsigned long long sbal = __builtin_amdgcn_ballot_w64(shr);
-                    const int ns = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sbal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sbal, shr ? 1u : 0u));
-                    nitems = 2 * nitems - __popcll(sbal);                         // pairs of this view
-                    incl = 2 * (incl - 1) - ns;                                   // the lane's first pair, numbered in travel order
-                    const uint32_t oJ = rowm ? row_bytes : texel_bytes, oM = rowm ? texel_bytes : row_bytes;
-                    const uint32_t o0 = __umul24(qi, texel_bytes) + (PPW > 1 ? (uint32_t)(q & 7) : 0u);   // (the pixel -> its reference vector in LDS)
-                    const uint32_t oF = o0 + (neg ? oJ : 0u), oS = o0 + (neg ? 0u : oJ);           // first / second pair in travel order
-                    if (fresh && !shr) *reinterpret_cast<uint2*>(items + incl * 2) = make_uint2(oF, oF + oM);
-                    if (fresh) *reinterpret_cast<uint2*>(items + (incl + 1) * 2) = make_uint2(oS, oS + oM);
-                    if (lane == 0) *reinterpret_cast<uint2*>(items + nitems * 2) = make_uint2(0u, 0u);   // pad to a whole pass: pixel 0, texel 0
-                    incl = gate ? incl + 2 : 0;                                   // closed lanes: the zero pairs
-                    fmin = rowm ? bx : by; fmaj = rowm ? by : bx;
-                    fmaj = neg ? 1.0f - fmaj : fmaj;                              // pairs are numbered in travel order
-                } else {
-                    if (fresh) items[incl - 1] = PPW == 1 ? qi : (((uint32_t)q << 26) | qi);
-                    if (lane == 0) items[nitems] = 0u;                            // pad to a whole pass: pixel 0, texel 0
-                }
+                const bool rowm = (md & 1u) != 0, neg = (md & 2u) != 0;
+                // a leader whose quad is the previous run's quad moved one step along the direction of travel shares that run's
+                // second pair (FKEY_CLOSED + a step is no valid key)
+                const bool shr = fresh && (prev + (uint32_t)((int)md >> 2) == key);
+                const unsigned long long sbal = __builtin_amdgcn_ballot_w64(shr);
+                const int ns = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sbal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sbal, shr ? 1u : 0u));
+                nitems = 2 * nitems - __popcll(sbal);                         // pairs of this view
+                incl = 2 * (incl - 1) - ns;                                   // the lane's first pair, numbered in travel order
+                const uint32_t oJ = rowm ? row_bytes : texel_bytes, oM = rowm ? texel_bytes : row_bytes;
+                const uint32_t o0 = __umul24(qi, texel_bytes) + (PPW > 1 ? (uint32_t)(q & 7) : 0u);   // (the pixel -> its reference vector in LDS)
+                const uint32_t oF = o0 + (neg ? oJ : 0u), oS = o0 + (neg ? 0u : oJ);           // first / second pair in travel order
+                if (fresh && !shr) *reinterpret_cast<uint2*>(items + incl * 2) = make_uint2(oF, oF + oM);
+                if (fresh) *reinterpret_cast<uint2*>(items + (incl + 1) * 2) = make_uint2(oS, oS + oM);
+                if (lane == 0) *reinterpret_cast<uint2*>(items + nitems * 2) = make_uint2(0u, 0u);   // pad to a whole pass: pixel 0, texel 0
+                incl = gate ? incl + 2 : 0;                                   // closed lanes: the zero pairs
+                fmin = rowm ? bx : by; fmaj = rowm ? by : bx;
+                fmaj = neg ? 1.0f - fmaj : fmaj;                              // pairs are numbered in travel order
                 fwave_lds_fence();
 
                 // ---------------- correlation ----------------
@@ -247,9 +239,9 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
                         for (int a = 0; a < 2; ++a) {
                             if (a == 1 && !second) break;
                             const int it = min(IPP * (ps + a) + upair, nitems);   // tail of the last pass: the pad item
-                            const uint32_t item = TX ? items[it * 2 + tap] : items[it];
-                            const cvr_gptr sp = src + ((TX ? (item & ~15u) : __umul24(item & 0xffffffu, texel_bytes)) + lane_src_off);
-                            const unsigned char* rp = refl + (__umul24(TX ? (item & 7u) : ((item >> 26) & 7u), texel_bytes) + (uint32_t)sub * 16u);   // LDS (PPW > 1 only)
+                            const uint32_t item = items[it * 2 + tap];
+                            const cvr_gptr sp = src + ((item & ~15u) + lane_src_off);
+                            const unsigned char* rp = refl + (__umul24(item & 7u, texel_bytes) + (uint32_t)sub * 16u);   // LDS (PPW > 1 only)
 #pragma unroll
                             for (int cc = 0; cc < CPL; ++cc) {
                                 const bool okc = FULL || (sub + LPU * cc < nchunk);
@@ -266,30 +258,18 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
                             for (int cc = 0; cc < CPL; ++cc) part = fdot_chunk(rv[a][cc], sv[a][cc], part, FeatT());
                             part = LPU == 8 ? freduce8(part) : freduce4(part);
                             const int it = IPP * (ps + a) + upair;
-                            if (sub == 0 && it < nitems) {
-                                if (TX) reinterpret_cast<float*>(ctab2 + it + 2)[tap] = part;
-                                else reinterpret_cast<float*>(ctab + it + 1)[tap] = part;
-                            }
+                            if (sub == 0 && it < nitems) reinterpret_cast<float*>(ctab2 + it + 2)[tap] = part;
                         }
                     }
                 }
                 fwave_lds_fence();
 
                 // ---------------- bilinear combine + view accumulation ----------------
-                if (TX) {
-                    const float2 cA = ctab2[incl], cB = ctab2[incl + 1];
-                    const float t = __builtin_fmaf(fmin, cA.y - cA.x, cA.x), l = __builtin_fmaf(fmin, cB.y - cB.x, cB.x);
-                    const float c = __builtin_fmaf(fmaj, l - t, t);               // homography.py:150,155 (grid_sample's bilinear weights, factored)
-                    acc += gate ? c : 0.f;                                        // homography.py:159,116 (fp32 here); the fractions of a closed lane may be NaN
-                } else {
-                    const float4 c4 = ctab[gate ? incl : 0];                      // closed lanes: the zero slot
-                    float c = c4.x * wnw;
-                    c = __builtin_fmaf(c4.y, wne, c);
-                    c = __builtin_fmaf(c4.z, wsw, c);
-                    c = __builtin_fmaf(c4.w, wse, c);
-                    acc += gate ? c : 0.f;                                        // homography.py:159,116 (fp32 here); the weights of a closed lane may be NaN
-                }
-                fwave_lds_fence();                                                // ctab/items are rewritten by the next view
+                const float2 cA = ctab2[incl], cB = ctab2[incl + 1];
+                const float t = __builtin_fmaf(fmin, cA.y - cA.x, cA.x), l = __builtin_fmaf(fmin, cB.y - cB.x, cB.x);
+                const float c = __builtin_fmaf(fmaj, l - t, t);               // homography.py:150,155 (grid_sample's bilinear weights, factored)
+                acc += gate ? c : 0.f;                                        // homography.py:159,116 (fp32 here); the fractions of a closed lane may be NaN
+                fwave_lds_fence();                                                // ctab2/items are rewritten by the next view
             }
             const float cval = acc * invV;                                        // homography.py:118,120
             if (p.cost_hi) {
@@ -322,29 +302,15 @@ __global__ __launch_bounds__(256, MINW) void cv_fast_kernel(const CvParams p) {
 }
 
 template <int DL>
-static size_t fast_lds_bytes(const CvParams& p, bool tx = true) {
-    const size_t tables = tx ? (size_t)(130 * 8 + 130 * 8 + p.V * 64) : (size_t)(16 + 1024 + 272);
+static size_t fast_lds_bytes(const CvParams& p) {
+    const size_t tables = (size_t)(130 * 8 + 130 * 8 + p.V * 64);
     return (size_t)4 * (p.V * 512 + tables + (p.cost_hi ? 0 : 8 * DL * 4) + (DL < 64 ? 8 * p.F * (p.feat_bf16 ? 2 : 4) : 0));
 }
 
 template <typename FeatT, int DL, int CPL, bool FULL, int MINW, int LPU>
 static hipError_t launch_fast(const CvParams& p, hipStream_t stream) {
     const dim3 grid((unsigned)((size_t)p.tiles_x * p.tiles_y * p.B)), block(256);
-#ifdef MAGNET_DEV
-    if (CV_DEV(p) & 0x400) {                                                       // dev: quad items (rounds 2 - 4) for same-box A/B
-        const size_t lq = fast_lds_bytes<DL>(p, false);
-        if (p.gate_bits) hipLaunchKernelGGL((cv_fast_kernel<FeatT, DL, CPL, FULL, MINW, LPU, 2>), grid, block, lq, stream, p);
-        else hipLaunchKernelGGL((cv_fast_kernel<FeatT, DL, CPL, FULL, MINW, LPU, 0>), grid, block, lq, stream, p);
-        return hipGetLastError();
-    }
-#endif
-    size_t lds = fast_lds_bytes<DL>(p);
-#ifdef MAGNET_DEV
-    {   // dev: cap the workgroups per CU by asking for more LDS than the kernel uses (occupancy sensitivity)
-        const int cap = (CV_DEV(p) & 0x300000) == 0x300000 ? 3 : (CV_DEV(p) & 0x200000) ? 4 : 0;
-        if (cap) { const size_t need = (size_t)160 * 1024 / (cap + 1) + 512; if (lds < need) lds = need; }
-    }
-#endif
+    const size_t lds = fast_lds_bytes<DL>(p);
     if (p.gate_bits) hipLaunchKernelGGL((cv_fast_kernel<FeatT, DL, CPL, FULL, MINW, LPU, 6>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((cv_fast_kernel<FeatT, DL, CPL, FULL, MINW, LPU, 4>), grid, block, lds, stream, p);
     return hipGetLastError();
@@ -369,18 +335,6 @@ hipError_t launch_cv_fast(const CvParams& p, hipStream_t stream, bool* handled) 
     if ((size_t)(p.h + 2) * (p.w + 2) * p.F * esz >= ((size_t)1 << 32)) return hipSuccess;   // 32-bit byte offsets
     if (fast_lds_bytes<64>(p) > 64 * 1024 || (p.D <= 32 && fast_lds_bytes<32>(p) > 64 * 1024)) return hipSuccess;   // absurd V (D <= 32: + the reference vectors)
     if (p.src_gmq && !(CV_DEV(p) & 0x100)) {                                                  // D > 32 with the quad-form (mu, sigma) map: the round-3 kernel (dev bit 0x100: the round-2 kernels)
-#ifdef MAGNET_DEV
-        // round 4's two measured experiments, dev library only (profiles/r4/NOTES.md): 0x8 = quads AND texels staged in LDS by DMA, correlation on
-        // the matrix pipe (cost_volume_v4.hip: 1.24 - 1.35 ms); 0x20 = round 3's kernel with the quads prefetched one unit ahead (cost_volume_v5.hip: 1.11 ms)
-        if (CV_DEV(p) & 0x8) {
-            const hipError_t e4 = launch_cv_v4(p, stream, handled);
-            if (e4 != hipSuccess || *handled) return e4;
-        }
-        if (CV_DEV(p) & 0x20) {
-            const hipError_t e5 = launch_cv_v5(p, stream, handled);
-            if (e5 != hipSuccess || *handled) return e5;
-        }
-#endif
         const hipError_t e = launch_cv_v3(p, stream, handled);
         if (e != hipSuccess || *handled) return e;
     }

@@ -24,14 +24,13 @@
 // that run's second pair and emits only one.  Slot numbering runs along increasing x (y), whatever the direction of travel, so the
 // combine is direction-free: c = lerp(lerp(pair s), lerp(pair s + 1)).  The mode only decides how many pairs are shared, never the
 // result: any (mode, direction) gives the same texels to the same quads.
-#include <stdlib.h>
 #include "cv_runs.hpp"
 
 namespace magnet {
 
 // CPL / FULL / LPU: as in cv_fast_kernel (VALU correlation units of LPU lanes x CPL 16-byte chunks)
-// VG = views per group (1..4); OPT bit 0 = write the gate bits (debug / parity tests); bit 2 = texel-pair items (TX; the product form —
-// quad items are kept for dev A/B only)
+// VG = views per group (1..4); OPT bit 0 = write the gate bits (debug / parity tests); bit 2 = texel-pair items (TX): what bf16 features
+// get; fp32 features get quad items (the launcher)
 template <typename FeatT, int CPL, bool FULL, int MINW, int LPU, int VG, int OPT>
 __global__ __launch_bounds__(256, MINW) void cv_fast64_kernel(const CvParams p) {
     constexpr int DL = 64;
@@ -424,10 +423,7 @@ static hipError_t launch_fast64_v(const CvParams& p0, hipStream_t stream) {
     // than the texels it saves (C4L 2.79 -> 3.09 ms), and at 3.5 items per (pixel, view) (C2, C4 grids, which cost_volume_v3.hip serves)
     // it loses 15 - 20 %: profiles/r5/ablate_tx.log
     bool tx = sizeof(FeatT) == 2;
-#ifdef MAGNET_DEV
-    { static const int strip = getenv("MAGNET_STRIP") ? atoi(getenv("MAGNET_STRIP")) : -1; if (strip >= 0) p.strip_tx = strip; }   // dev: block order A/B
-    if (CV_DEV(p) & 0x400) tx = !tx;                                               // dev: the other item form, same box
-#endif
+    if (CV_DEV(p) & 0x400) tx = !tx;                                               // dev: the other item form (shipped for the other feature type)
     if (!tx) {
         if (p.gate_bits) hipLaunchKernelGGL((cv_fast64_kernel<FeatT, CPL, FULL, MINW, LPU, VG, 1>), grid, block, fast64_lds_bytes(p, false), stream, p);
         else hipLaunchKernelGGL((cv_fast64_kernel<FeatT, CPL, FULL, MINW, LPU, VG, 0>), grid, block, fast64_lds_bytes(p, false), stream, p);

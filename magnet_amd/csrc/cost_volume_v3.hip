@@ -36,7 +36,6 @@
 // Arithmetic and tolerance contract: as cost_volume_fast.hip (fma-contracted geometry, one v_rcp_f32, padded-map texel
 // coordinates, fp32 view sum); the (mu, sigma) and correlation interpolations use the quad form / difference-form weights,
 // which changes results by fp32 rounding only (homography.py:150-152,155-159).
-#include <stdlib.h>
 #include "cv_runs.hpp"
 
 namespace magnet {
@@ -51,30 +50,20 @@ constexpr int V3_MS = (V3_IT + 68 * 8 + 15) / 16 * 16;   // [NPX] x 8 B: (mu, si
 constexpr int V3_FIX = V3_MS + V3_NPX * 8;         // then: view table [Vr] x 8 B, projection table [Vr][NPX] x 32 B, reference vectors, output stage
 
 // CPL / FULL / LPU: VALU correlation units of LPU lanes x CPL 16-byte chunks (as cv_fast_kernel); VG = views per group;
-// OPT bit 0: write the gate bits (debug / parity tests); bit 1 (dev builds): no dot products; bit 6: split output form only;
-// bits 8..11: correlation passes whose loads are in flight together
-// dev A/B (HALFQ): q0 holds 8 fp16 {mu quad form, sigma quad form}; widen to the two fp32 quads
-__device__ __forceinline__ void v3_unpack_quad16(float4& q0, float4& q1) {
-    typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-    const h2_t a = __builtin_bit_cast(h2_t, q0.x), b = __builtin_bit_cast(h2_t, q0.y), c = __builtin_bit_cast(h2_t, q0.z), d = __builtin_bit_cast(h2_t, q0.w);
-    q0 = make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
-    q1 = make_float4((float)c[0], (float)c[1], (float)d[0], (float)d[1]);
-}
-
+// OPT bit 0: write the gate bits (debug / parity tests); bit 6: split output form only; bits 8..11: correlation passes whose loads are
+// in flight together; bit 13: two pixels per correlation batch.  (Round 6 measured the quad-form (mu, sigma) map as 8 fp16 per entry:
+// no gain, profiles/r6/ablate_halfq.log.)
 template <typename FeatT, int CPL, bool FULL, int MINW, int LPU, int VG, int OPT>
 __global__ __launch_bounds__(256, MINW) void cv_v3_kernel(const CvParams p) {
     constexpr bool GBITS = (OPT & 1) != 0;
-    constexpr bool NO_CORR = (OPT & 2) != 0;              // dev: no feature loads / dot products
     constexpr bool SPLIT = (OPT & 64) != 0;               // the split-bf16 channel-last output form only (cost_hi given): no NCHW staging code, fewer live scalars
     constexpr int NPX = V3_NPX;
     constexpr int IPP = 64 / (4 * LPU);                   // items per correlation pass
-    constexpr int HALFQ = (OPT >> 14) & 3;                // dev A/B (round 6, tools/ablate.py ABLATE_HALFQ): the quad-form (mu, sigma) entry as 8 fp16 = ONE 16-byte
-                                                          // load per candidate from a 16-byte-stride map (the tool converts the map); gates differ from the fp32 map's
-                                                          // at the 1e-3 level (outside the contract), the amount of work does not: what the map's bytes cost
     constexpr bool PX2 = (OPT & 0x2000) != 0 && SPLIT && FULL;   // two pixels per correlation batch (round 5; split output form, F = 64 instances)
-    constexpr bool QF = LPU == 4 && !(OPT & 128);                         // an item's four taps share a 16-lane row: correlations stored in quad form (cv_runs.hpp)
+    constexpr bool QF = LPU == 4;                         // an item's four taps share a 16-lane row: correlations stored in quad form (cv_runs.hpp)
     constexpr int O_IT = V3_IT, O_MS = V3_MS, O_FIX = V3_FIX;
-    constexpr int NPASS = ((OPT >> 8) & 15) ? ((OPT >> 8) & 15) : V3_NPASS_DEFAULT;   // passes fetched together
+    constexpr int NPASS = (OPT >> 8) & 15;                // passes fetched together (the launcher: V3_NPASS_DEFAULT, or 1 with 4 chunks per lane)
+    static_assert(NPASS > 0, "OPT carries the pass count");
     constexpr int CSTR = LPU * 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -172,8 +161,8 @@ __global__ __launch_bounds__(256, MINW) void cv_v3_kernel(const CvParams p) {
     const v3_gptr src_b = uniform_base(reinterpret_cast<const unsigned char*>(p.src_feat) + (size_t)b * map_texels * texel_bytes);
     // quad-form (mu, sigma) map of frame b over all views, as a buffer: the hardware bounds check replaces the clamp of the quad key
     const __amdgpu_buffer_rsrc_t rsrc_q = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)v4_uniform_ptr(reinterpret_cast<const unsigned char*>(p.src_gmq) + (size_t)b * map_texels * (HALFQ ? 16 : 32)), 0,
-        (int)(((uint32_t)(p.V - 1) * vstride + map_texels) * (HALFQ ? 16u : 32u)), 0x00020000);
+        (void*)v4_uniform_ptr(reinterpret_cast<const unsigned char*>(p.src_gmq) + (size_t)b * map_texels * 32), 0,
+        (int)(((uint32_t)(p.V - 1) * vstride + map_texels) * 32u), 0x00020000);
     const float kappa = p.kappa;
     // split output: bases of the wave's first pixel pinned into SGPRs, per pixel a 32-bit byte offset (round 4; was 64-bit per-lane math)
     v4_gu8* const hi_base = (SPLIT || p.cost_hi) ? v4_uniform_gptr(p.cost_hi + (((size_t)b * Hp + (y + 1)) * Wp + (x_base + 1)) * (size_t)p.cost_ld) : nullptr;
@@ -291,10 +280,9 @@ __global__ __launch_bounds__(256, MINW) void cv_v3_kernel(const CvParams p) {
                             const unsigned long long wy = __builtin_amdgcn_ballot_w64(__float_as_uint(iys) < ylim);
                             Wb[u] = (u < nact) ? (wx & wy & jmask) : 0ull;
                             keyf[pp][u] = __umul24(v3_cvt_u32_sat(iys), (uint32_t)Wp) + v3_cvt_u32_sat(ixs) + vt.x;
-                            const int qo = (int)(keyf[pp][u] << (HALFQ ? 4 : 5));
+                            const int qo = (int)(keyf[pp][u] << 5);
                             q0[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, qo, 0, 0));
-                            if constexpr (HALFQ != 0) v3_unpack_quad16(q0[u], q1[u]);
-                            else q1[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, qo + 16, 0, 0));
+                            q1[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, qo + 16, 0, 0));
                             if (GBITS) vidx[u] = vt.y;
                             __builtin_amdgcn_sched_barrier(0);
                             if (u > 0) { gate_view(u - 1); __builtin_amdgcn_sched_barrier(0); }
@@ -452,10 +440,9 @@ __global__ __launch_bounds__(256, MINW) void cv_v3_kernel(const CvParams p) {
                     // quad index relative to (frame b, view 0): truncation = floor inside the window (ixs, iys >= 0); garbage outside it
                     keyf[u] = __umul24(v3_cvt_u32_sat(iys), (uint32_t)Wp) + v3_cvt_u32_sat(ixs) + vt.x;
                     // bounds-checked buffer loads (round 4): the key of a lane outside the window is garbage and reads as zero; was min + global load
-                    const int qo = (int)(keyf[u] << (HALFQ ? 4 : 5));
+                    const int qo = (int)(keyf[u] << 5);
                     q0[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, qo, 0, 0));
-                    if constexpr (HALFQ != 0) v3_unpack_quad16(q0[u], q1[u]);
-                    else q1[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, qo + 16, 0, 0));
+                    q1[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, qo + 16, 0, 0));
                     if (GBITS) vidx[u] = vt.y;
                     __builtin_amdgcn_sched_barrier(0);
                     if (u > 0) { gate_view(u - 1); __builtin_amdgcn_sched_barrier(0); }
@@ -479,7 +466,7 @@ __global__ __launch_bounds__(256, MINW) void cv_v3_kernel(const CvParams p) {
                 if (IPP > 1)
                     v3_st2_mask((1ull << (IPP - 1)) - 1ull, wb + V3_IT + ((uint32_t)n_items + (uint32_t)lane) * 8u, 0u, wb + V3_CT + V3_CAP * 16);
                 fwave_lds_fence();
-                if (!NO_CORR) correlate(n_items);
+                correlate(n_items);
                 fwave_lds_fence();
 #pragma unroll
                 for (int u = 0; u < VG; ++u) {
@@ -554,40 +541,16 @@ static hipError_t launch_v3_v(const CvParams& p0, hipStream_t stream) {
     // block order: raster rows up to 256-pixel-wide grids; wider ones (C4's 304) walk 32-pixel-wide vertical strips, whose source
     // footprint per XCD is smaller (profiles/r5/v3_strip.log: C2 0.821 = 0.820 ms, C5 0.882 -> 0.877, C4 0.696 -> 0.682 ms)
     p.strip_tx = p.w > 256 ? 1 : 0;
-    size_t lds = v3_lds_bytes(p, VG);
-#ifdef MAGNET_DEV
-    { static const int strip = getenv("MAGNET_STRIP") ? atoi(getenv("MAGNET_STRIP")) : -1; if (strip >= 0) p.strip_tx = strip; }   // dev: block order A/B
-    {   // dev: cap the workgroups per CU (waves per SIMD) by asking for more LDS than the kernel uses
-        const int cap = (CV_DEV(p) & 0x300000) == 0x300000 ? 3 : (CV_DEV(p) & 0x200000) ? 4 : (CV_DEV(p) & 0x100000) ? 5 : 0;
-        if (cap) { const size_t need = (size_t)160 * 1024 / (cap + 1) + 512; if (lds < need) lds = need; }
-    }
-#endif
+    const size_t lds = v3_lds_bytes(p, VG);
     constexpr int NP = (CPL >= 4 ? 1 : V3_NPASS_DEFAULT) << 8;     // 4 chunks per lane: one pass already has 4 wave-loads in flight
     constexpr int MW2 = CPL >= 4 ? 4 : (MINW > 5 ? 5 : MINW);             // the NCHW-output and gate-bit instances carry more live values: one wave per SIMD less instead of scratch
-#ifdef MAGNET_DEV
-    if (CV_DEV(p) & 0x200) { hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MW2, LPU, VG, NP | 2>), grid, block, lds, stream, p); return hipGetLastError(); }      // no dot products (timing only)
-    if (p.cost_hi && (CV_DEV(p) & 0x20000)) { hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MINW, LPU, VG, NP | 64 | 128>), grid, block, lds, stream, p); return hipGetLastError(); }   // dev: four-weight combine instead of the quad-form slots
-    if (p.cost_hi && (CV_DEV(p) & 0x4000)) { hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MINW, LPU, VG, 64 | 0x200>), grid, block, lds, stream, p); return hipGetLastError(); }
-    if (p.cost_hi && (CV_DEV(p) & 0x40000)) { hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MINW, LPU, VG, 64 | 0x300>), grid, block, lds, stream, p); return hipGetLastError(); }
-    if (p.cost_hi && (CV_DEV(p) & 0x80000)) { hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MINW, LPU, VG, 64 | 0x400>), grid, block, lds, stream, p); return hipGetLastError(); }
-#endif
-    // The split-output form of the F = 64 instances (what MAGNET.forward runs) takes TWO pixels per correlation batch, compiled for 8 waves
-    // per SIMD (63 - 64 registers, no scratch): bit-identical to the one-pixel loop, C2 0.822 -> 0.796 ms (profiles/r5/ablate_px2.log).
-    // dev flag 0x10: the one-pixel loop, same box.
-#ifdef MAGNET_DEV
-    if constexpr (FULL && CPL == 2 && VG <= 2) {       // dev A/B 0x80: the product instance reading an fp16 quad-form map (16 B per candidate, 16-byte stride; see HALFQ)
-        if (p.cost_hi && !p.gate_bits && (CV_DEV(p) & 0x80)) { hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, 8, LPU, VG, NP | 64 | 0x2000 | 0x4000>), grid, block, lds, stream, p); return hipGetLastError(); }
-    }
-#endif
-    if constexpr (FULL && CPL == 2 && VG <= 2) {
-        if (p.cost_hi && !p.gate_bits && !(CV_DEV(p) & 0x10)) {
-            hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, 8, LPU, VG, NP | 64 | 0x2000>), grid, block, lds, stream, p);
-            return hipGetLastError();
-        }
-    }
     if (p.gate_bits) hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MW2, LPU, VG, NP | 1>), grid, block, lds, stream, p);
-    else if (p.cost_hi) hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MINW, LPU, VG, NP | 64>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MW2, LPU, VG, NP>), grid, block, lds, stream, p);
+    else if (p.cost_hi) {
+        // The split-output form of the F = 64 instances (what MAGNET.forward runs) takes TWO pixels per correlation batch, compiled for 8 waves
+        // per SIMD (63 - 64 registers, no scratch): bit-identical to the one-pixel loop, C2 0.822 -> 0.796 ms (profiles/r5/ablate_px2.log).
+        if constexpr (FULL && CPL == 2 && VG <= 2) hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, 8, LPU, VG, NP | 64 | 0x2000>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MINW, LPU, VG, NP | 64>), grid, block, lds, stream, p);
+    } else hipLaunchKernelGGL((cv_v3_kernel<FeatT, CPL, FULL, MW2, LPU, VG, NP>), grid, block, lds, stream, p);
     return hipGetLastError();
 }
 
@@ -595,16 +558,11 @@ template <typename FeatT, int CPL, bool FULL, int MINW, int LPU>
 static hipError_t launch_v3(const CvParams& p, hipStream_t stream) {
     // views in flight per pixel.  Two: 68 registers = 7 waves per SIMD; four views cost 78 registers = 6 waves and lose 3 % both
     // alone (0.906 vs 0.879 ms per 64 C2 frames, warm) and inside the step; one view (8 waves) has too little to overlap: 0.975
-    int vg = p.V == 1 ? 1 : (p.V % 2 == 0 ? 2 : (p.V % 3 == 0 ? 3 : 2));
-#ifdef MAGNET_DEV
-    if (CV_DEV(p) & 0x400000) vg = 4;                                                     // dev: views per group
-    if (CV_DEV(p) & 0x800000) vg = 1;
-#endif
+    const int vg = p.V == 1 ? 1 : (p.V % 2 == 0 ? 2 : (p.V % 3 == 0 ? 3 : 2));
     switch (vg) {
         case 1: return launch_v3_v<FeatT, CPL, FULL, MINW, LPU, 1>(p, stream);
         case 2: return launch_v3_v<FeatT, CPL, FULL, MINW, LPU, 2>(p, stream);
-        case 3: return launch_v3_v<FeatT, CPL, FULL, MINW, LPU, 3>(p, stream);
-        default: return launch_v3_v<FeatT, CPL, FULL, MINW, LPU, 4>(p, stream);
+        default: return launch_v3_v<FeatT, CPL, FULL, MINW, LPU, 3>(p, stream);
     }
 }
 
@@ -626,7 +584,7 @@ hipError_t launch_cv_v3(const CvParams& p, hipStream_t stream, bool* handled) {
         if ((size_t)p.V * p.B * map * 32 >= ((size_t)1 << 32)) return hipSuccess;
     }
     const int nchunk = (int)(p.F * esz / 16);
-    if (v3_lds_bytes(p, 4) > 64 * 1024) return hipSuccess;
+    if (v3_lds_bytes(p, 4) > 64 * 1024) return hipSuccess;          // conservative: sized for 4 views per group (measured and not kept), the launchers use 1 - 3
     {   // the scalar block -> tile divisions by reciprocal multiplication are exact while grid * tiles < 2^32
         const uint64_t tiles = (uint64_t)((p.w + 4 * V3_NPX - 1) / (4 * V3_NPX)) * (uint64_t)p.h;
         if (tiles * (uint64_t)p.B * tiles >= ((uint64_t)1 << 32)) return hipSuccess;
@@ -634,21 +592,12 @@ hipError_t launch_cv_v3(const CvParams& p, hipStream_t stream, bool* handled) {
     *handled = true;
     // MINW = waves per SIMD the instance is compiled for: the largest that needs no scratch (78 registers for bf16 F = 64)
     if (p.feat_bf16) {
-#ifdef MAGNET_DEV
-        if (nchunk == 8 && (CV_DEV(p) & 0x1000)) return launch_v3<uint16_t, 2, true, 8, 4>(p, stream);    // dev: occupancy A/B
-        if (nchunk == 8 && (CV_DEV(p) & 0x2000)) return launch_v3<uint16_t, 2, true, 4, 4>(p, stream);
-        if (nchunk == 8 && (CV_DEV(p) & 0x10000)) return launch_v3<uint16_t, 2, true, 7, 4>(p, stream);
-#endif
         if (nchunk == 8)  return launch_v3<uint16_t, 2, true, 6, 4>(p, stream);          // F = 64: 4 lanes x 32 B per (item, tap) unit
         if (nchunk <= 8)  return launch_v3<uint16_t, 1, false, 6, 8>(p, stream);
         if (nchunk <= 16) return launch_v3<uint16_t, 2, false, 5, 8>(p, stream);
     } else {
-#ifdef MAGNET_DEV
-        // dev: 4 lanes x 64 B per unit (4 items per pass, quad-form slots) — 74 instead of 68 registers, 6 instead of 7 waves:
-        // C4 0.828 vs 0.748 ms, C2 with fp32 features 1.274 vs 1.213 ms
-        if (nchunk == 16 && (CV_DEV(p) & 0x8000)) return launch_v3<float, 4, true, 5, 4>(p, stream);
-#endif
-        if (nchunk == 16) return launch_v3<float, 2, true, 5, 8>(p, stream);             // F = 64: 8 lanes x 32 B per unit
+        // F = 64: 8 lanes x 32 B per unit (4 lanes x 64 B: 74 instead of 68 registers, 6 instead of 7 waves — C4 0.828 vs 0.748 ms)
+        if (nchunk == 16) return launch_v3<float, 2, true, 5, 8>(p, stream);
         if (nchunk <= 8)  return launch_v3<float, 1, false, 6, 8>(p, stream);
         if (nchunk <= 16) return launch_v3<float, 2, false, 5, 8>(p, stream);
         if (nchunk <= 32) return launch_v3<float, 4, false, 4, 8>(p, stream);

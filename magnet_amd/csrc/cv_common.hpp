@@ -42,8 +42,9 @@ struct CvParams {
     float k[MAGNET_MAX_CANDIDATES];   // (float)k_j, read with wave-uniform indices (scalar loads)
 };
 
-// Development switches (timing ablations, kernel variants for same-box A/B: tools/README.md).  The product library is compiled without
-// MAGNET_DEV: every CV_DEV(p) is the constant 0 there and the branches it guards are removed by the compiler.
+// Development switches (tools/README.md): each one routes a launch to another kernel instance that the product library ships too, so
+// that the tools and the test-suite can reach it at any shape.  The product library is compiled without MAGNET_DEV: every CV_DEV(p) is
+// the constant 0 there.
 #ifdef MAGNET_DEV
 #define CV_DEV(p) ((p).ablate)
 #else
@@ -100,8 +101,6 @@ hipError_t launch_cv_cand(const CvParams& p, hipStream_t stream, bool* handled);
 hipError_t launch_cv_fast(const CvParams& p, hipStream_t stream, bool* handled);
 hipError_t launch_cv_fast64(const CvParams& p, hipStream_t stream, bool* handled);
 hipError_t launch_cv_v3(const CvParams& p, hipStream_t stream, bool* handled);
-hipError_t launch_cv_v4(const CvParams& p, hipStream_t stream, bool* handled);
-hipError_t launch_cv_v5(const CvParams& p, hipStream_t stream, bool* handled);
 hipError_t launch_cvf_bwd(const CvParams& p, const float* gout, float* grad_ref, float* grad_src, hipStream_t stream,
                           bool* handled);
 hipError_t launch_cvf_bwd_ref_only(const CvParams& p, const float* gout, float* grad_ref, hipStream_t stream, bool* handled);

@@ -1,4 +1,4 @@
-// cv_runs.hpp — helpers shared by the run-based production matchers (cost_volume_v3.hip, cost_volume_v4.hip): wave-private LDS
+// cv_runs.hpp — helpers shared by the run-based production matchers (cost_volume_v3.hip, cost_volume_fast.hip, cost_volume_fast64.hip): wave-private LDS
 // access by 32-bit byte address, stores / selects under 64-bit scalar lane masks, the 4-lane DPP reduction, run bookkeeping.
 #pragma once
 #include "cv_fast_common.hpp"

@@ -1,13 +1,13 @@
 """HIP-graph replay of the refinement loop: the host leaves the loop.
 
 At 64 frames per step the path is GPU-bound (5.8 ms of kernels, ~15 device operations): replaying the captured step still saves the
-inter-operation gaps — 5.78 -> 5.69 ms per C2 step, same box (round 6; bench.py replays the step this way by default, --no-graph: eager).  The reference's own evaluation loop feeds ONE
-frame at a time (test_MaGNet.py:166-170, batch size 1).  `GraphedRefine` captures `MAGNET.match_and_refine` for a fixed shape
-into a HIP graph once (torch.cuda.CUDAGraph: our kernels are launched on torch's capture stream, so they are recorded like
-torch's own) and replays it per frame: one launch from the host's point of view.  Measured on MI355X (bench.py --frames 1
-[--graph]): 0.386 -> 0.356 ms per one-frame step (2 590 -> 2 810 frames/s), 4 frames 0.839 -> 0.823 ms: the small-batch step is
-bound by its serial chain of ~13 kernels that each under-fill the chip (one frame = 155 convolution tiles for 256 CUs), not by
-launch overhead — batching frames (64 per step: 7 500 frames/s) is what pays; the graph only removes the host from the loop.  Inputs are copied into the graph's static tensors (device-to-device,
+inter-operation gaps — 5.78 -> 5.69 ms per C2 step (11 067 -> 11 239 frames/s), same box (profiles/r6/graph_replay_ab.jsonl; bench.py
+replays the step this way by default, --no-graph: eager).  The reference's own evaluation loop feeds ONE frame at a time
+(test_MaGNet.py:166-170, batch size 1).  `GraphedRefine` captures `MAGNET.match_and_refine` for a fixed shape into a HIP graph once
+(torch.cuda.CUDAGraph: our kernels are launched on torch's capture stream, so they are recorded like torch's own) and replays it per
+frame: one launch from the host's point of view.  A small-batch step is bound by its serial chain of ~13 kernels that each under-fill
+the chip (one frame = 155 convolution tiles for 256 CUs), not by launch overhead — batching frames is what pays; the graph only removes
+the host from the loop.  Inputs are copied into the graph's static tensors (device-to-device,
 a few MB); outputs are the graph's static output tensors (clone them to keep a result across replays)."""
 from __future__ import annotations
 

@@ -56,9 +56,8 @@ timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fvolume_s
 timeout 200 python tools/bench_end_to_end.py > $O/bench_end_to_end.json 2> $O/bench_end_to_end.err
 timeout 200 python tools/bench_pipeline.py 2>/dev/null | tail -1 > $O/bench_pipeline.json
 # matcher variants (dev library) + instruction / gather microbenchmarks
-ABLATE_PX2=1 timeout 150 python tools/ablate.py C2 64 split 2>&1 | grep -v amdgpu.ids > $O/ablate_C2_split.log
+timeout 150 python tools/ablate.py C2 64 split 2>&1 | grep -v amdgpu.ids > $O/ablate_C2_split.log
 # round 6: the records that close the review's items (same box as the bench line above)
-ABLATE_HALFQ=1 timeout 200 python tools/ablate.py C2 64 split 2>&1 | grep -v amdgpu.ids > $O/ablate_halfq.log           # (mu, sigma) map bytes: fp16 map A/B
 timeout 300 python tools/clock_recovery.py 2>&1 | grep -v "amdgpu.ids\|UserWarning\|model = MAGNET" > $O/clock_recovery.jsonl      # matcher time vs idle gap behind matrix-core work
 # mask head on a side stream (same-box A/B + the kernel trace that shows the kernels serialise), frames-per-step sweep (launch quantisation: 256-row tiles over 256 CUs)
 B6="python bench.py --full --no-cpu-baseline --no-pmc --sustain-s 0 --no-graph"
