@@ -568,6 +568,18 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
 MAGNET_API int magnet_dnet_gauss_head(const float *in, int32_t in_ld, int32_t N, int32_t h, int32_t w, int32_t pad, float *out,
                                       void *stream);
 
+/* The stand-alone D-Net's tail (DNET(dnet=True): upsample_depth_via_mask, models/submodules/D_dense_depth.py:85-100,187-192, then
+ * activation_G, models/DNET.py:55-60) in one launch.  `head`: the depth head's fp32 output (rows, head_ld) over (N, h+2, w+2) grids,
+ * channel 0 = mu, channel 1 = v, as magnet_dnet_gauss_head reads it; `mask`: the mask head's logits (rows, mask_ld) over the same
+ * grids, channel n*16 + i*4 + j, as magnet_upsample_depth_cl reads them.  out (N, 2, 4h, 4w) fp32 NCHW, every element written:
+ *   w[n] = softmax over the 9 taps n of mask[.., n*16 + i*4 + j]
+ *   up[c][4y+i][4x+j] = sum_n w[n] * head[c] at (y + n/3 - 1, x + n%3 - 1), zero outside the image (F.unfold(padding=1); decided
+ *                       by index: border rows of `head` are not read)
+ *   out = [up[0], elu(up[1]) + 1 + 1e-10]      -- the RAW (mu, v) are upsampled, the activation follows at full resolution.
+ * k = 4 only.  head_ld even and >= 2, `head` 8-byte aligned; mask_ld >= 144 and a multiple of 4, `mask` and `out` 16-byte aligned. */
+MAGNET_API int magnet_dnet_upsample_gauss(const float *head, int32_t head_ld, const float *mask, int32_t mask_ld, int32_t N,
+                                          int32_t h, int32_t w, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ hipError_t launch_spp_upsample_backward(const MagnetSppBwdArgs&, hipStream_t);
 hipError_t launch_spp_pool_backward(const MagnetSppBwdArgs&, hipStream_t);
 hipError_t launch_fnet_stem_wgrad(const float*, const uint16_t*, const uint16_t*, float*, double*, int, int, int, hipStream_t);
 hipError_t launch_dnet_gauss_head(const float*, int, int, int, int, int, float*, hipStream_t);
+hipError_t launch_dnet_upsample_gauss(const float*, int, const float*, int, int, int, int, float*, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -408,6 +409,19 @@ MAGNET_API int magnet_dnet_gauss_head(const float* in, int32_t in_ld, int32_t N,
         return fail(MAGNET_E_ALIGN, "magnet_dnet_gauss_head: `in` must be 8-byte aligned");
     hipError_t e = magnet::launch_dnet_gauss_head(in, in_ld, N, h, w, pad, out, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_gauss_head launch");
+}
+
+MAGNET_API int magnet_dnet_upsample_gauss(const float* head, int32_t head_ld, const float* mask, int32_t mask_ld, int32_t N, int32_t h,
+                                          int32_t w, float* out, void* stream) {
+    if (!head || !mask || !out) return fail(MAGNET_E_NULL, "magnet_dnet_upsample_gauss: NULL pointer");
+    if (N <= 0 || h <= 0 || w <= 0 || head_ld < 2 || (head_ld & 1) || mask_ld < 144 || (mask_ld % 4) ||
+        (long long)N * h * w * 4 > 0x7fffffffLL * 256)
+        return fail(MAGNET_E_DIM, "magnet_dnet_upsample_gauss: bad dims N=%d h=%d w=%d head_ld=%d mask_ld=%d (head_ld even, >= 2; mask_ld >= 144, "
+                                  "mask_ld %% 4 == 0)", N, h, w, head_ld, mask_ld);
+    if ((reinterpret_cast<uintptr_t>(head) & 7) || !aligned16(mask) || !aligned16(out))
+        return fail(MAGNET_E_ALIGN, "magnet_dnet_upsample_gauss: `head` must be 8-byte, `mask` and `out` 16-byte aligned");
+    hipError_t e = magnet::launch_dnet_upsample_gauss(head, head_ld, mask, mask_ld, N, h, w, out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_upsample_gauss launch");
 }
 
 MAGNET_API int magnet_fnet_stem(const float* img, const float* wgt, const float* bias, void* out_hi, void* out_lo, int32_t N,

@@ -15,7 +15,10 @@ Three things live here:
   zero-bordered channel-last split-bf16 planes; the bilinear upsampling and the skip features land in channel slices of the next
   block's input (magnet_upsample_bilinear_cl, magnet_pack_split); the depth head runs as one fused launch and the Gaussian activation
   behind it is csrc/dnet_kernels.hip.  `run(..., x_d3_out=...)` writes the reference frames' x_feat straight into MAGNET's G-Net input
-  buffer (interior rows, zero border, a channel slice): no NCHW x_d3, no repack.
+  buffer (interior rows, zero border, a channel slice): no NCHW x_d3, no repack.  `run_standalone` is the stand-alone D-Net
+  (`DNET(dnet=True)`, what test_DNet.py evaluates): the same decoder pass, then the depth head and the mask head as two fused launches
+  and magnet_dnet_upsample_gauss (learned convex upsampling x4 of the raw (mu, v), activation_G behind it) -> (N, 2, H, W)
+  [mu, variance].  `DNET(..., backend="hip")` routes an eval-mode forward through it.
 """
 from __future__ import annotations
 
@@ -121,20 +124,33 @@ def gaussian_activation(out, magnet=True):
 
 class DNET(nn.Module):
     """models/DNET.py with output_type 'G' and DNET_architecture 'DenseDepth_BN': `DNET(args, encoder, dnet=False)` is MaGNet's
-    D-Net, img -> ((N, 2, H/4, W/4) [mu, sigma], x_feat (N, 256, H/4, W/4)).  `encoder`: any module returning the reference's feature
-    list (EfficientNet-B5's, or magnet_amd.standin.StandinEncoder)."""
+    D-Net, img -> ((N, 2, H/4, W/4) [mu, sigma], x_feat (N, 256, H/4, W/4)); `dnet=True` is the stand-alone D-Net of test_DNet.py /
+    train_DNet.py, img -> (N, 2, H, W) [mu, variance].  `encoder`: any module returning the reference's feature list
+    (EfficientNet-B5's, or magnet_amd.standin.StandinEncoder).
+    backend: 'torch' (default) runs the modules as they are; 'hip' runs the decoder, the heads and the tail of an eval-mode forward on
+    DNetMFMA (the caller's encoder stays a torch module); in .train() the torch forward runs, as MAGNET does for its D-Net."""
 
-    def __init__(self, args, encoder: nn.Module, dnet: bool = False):
+    def __init__(self, args, encoder: nn.Module, dnet: bool = False, backend: str = "torch"):
         super().__init__()
         self.args = args
         if getattr(args, "output_type", "G") != "G":
             raise lib.MagnetError(f"DNET: output_type {args.output_type!r} is not built (MaGNet uses 'G')")
         if getattr(args, "DNET_architecture", "DenseDepth_BN") != "DenseDepth_BN":
             raise lib.MagnetError(f"DNET: architecture {args.DNET_architecture!r} is not built (the BatchNorm decoder 'DenseDepth_BN' is)")
+        if backend not in ("torch", "hip"):
+            raise lib.MagnetError(f"DNET: backend must be 'torch' or 'hip', got {backend!r}")
         self.dnet = dnet
+        self.backend = backend
         self.d_net = DenseDepth(encoder, getattr(args, "output_dim", 2), args.downsample_ratio, dnet)
+        self._runner = None
+        if backend == "hip":
+            check_decoder(self.d_net.decoder, standalone=dnet)
+            self._runner = DNetMFMA(self.d_net.decoder)
 
     def forward(self, img):
+        if self._runner is not None and not self.training:
+            feats = self.d_net.encoder(img)
+            return self._runner.run_standalone(feats) if self.dnet else self._runner.run(feats)
         return gaussian_activation(self.d_net(img), magnet=not self.dnet)
 
 
@@ -185,8 +201,9 @@ def fold_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     return w * s.view(-1, 1, 1, 1), (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
 
 
-def check_decoder(decoder: nn.Module):
-    """MagnetError unless `decoder` is the reference's BatchNorm decoder at downsample ratio 4 (ours or the reference's class)."""
+def check_decoder(decoder: nn.Module, standalone: bool = False):
+    """MagnetError unless `decoder` is the reference's BatchNorm decoder at downsample ratio 4 (ours or the reference's class).
+    standalone: also require the learned-upsampling mask head (3x3 256->128, 1x1 128->128, 1x1 128->144) of the stand-alone form."""
     if getattr(decoder, "downsample_ratio", None) != 4 or not all(hasattr(decoder, a) for a in ("conv2", "up1", "up2", "up3", "depth_head")):
         raise lib.MagnetError("the HIP D-Net runs the DenseDepth decoder at downsample_ratio 4 (conv2, up1..up3, depth_head)")
     for name, _, _, _ in _UP:
@@ -199,6 +216,16 @@ def check_decoder(decoder: nn.Module):
     dh = decoder.depth_head
     if len(dh) != 5 or dh[4].out_channels != 2:
         raise lib.MagnetError("the HIP D-Net needs the 2-output depth head (output_dim 2, output_type 'G')")
+    if standalone:
+        mh = getattr(decoder, "mask_head", None)
+        ok = isinstance(mh, nn.Sequential) and len(mh) == 5 and all(type(mh[i]) is nn.Conv2d for i in (0, 2, 4)) \
+            and all(isinstance(mh[i], nn.ReLU) for i in (1, 3))
+        ok = ok and (mh[0].in_channels, mh[0].out_channels, mh[0].kernel_size) == (256, 128, (3, 3)) \
+            and (mh[2].in_channels, mh[2].out_channels, mh[2].kernel_size) == (128, 128, (1, 1)) \
+            and (mh[4].in_channels, mh[4].out_channels, mh[4].kernel_size) == (128, 144, (1, 1))
+        if not ok:
+            raise lib.MagnetError("the stand-alone HIP D-Net needs the learned-upsampling mask head (3x3 256->128, 1x1 128->128, "
+                                  "1x1 128->144: 9 taps x 4 x 4 sub-pixels)")
 
 
 def _planes(rows, c, dev):
@@ -222,6 +249,9 @@ class DNetMFMA:
         with torch.no_grad():
             eye.weight.copy_(torch.eye(128).view(128, 128, 1, 1)); eye.bias.zero_()
         self._head = ConvStackMFMA(nn.Sequential(dh[0], nn.ReLU(), dh[2], nn.ReLU(), eye, nn.ReLU(), dh[4]))
+        self._eye = eye
+        self._mask = None                                           # the mask head's stack: built by the first run_standalone()
+        self._mask_work = {}
         self._packed = None
         self._key = None
         self._bufs = {}
@@ -290,6 +320,7 @@ class DNetMFMA:
             return self._bufs
         self._bufs.clear()                                          # one shape at a time: the buffers are large
         self._head_work.clear()
+        self._mask_work.clear()
         self._bufs_sig = sig
         (h32, w32), (h16, w16), (h8, w8), (h4, w4) = dims
         r = lambda h, w: N * (h + 2) * (w + 2)
@@ -306,13 +337,8 @@ class DNetMFMA:
         b["feat"] = _planes(r(h4, w4), 256, dev)
         return b
 
-    @torch.no_grad()
-    def run(self, features, n_ref=None, x_d3_out=None):
-        """features: the encoder's list (indices 5, 6, 8, 11 are read; NCHW fp32 on the GPU).
-        x_d3_out = (hi, lo, ctot, c_off) with n_ref = B: x_feat of images [0, B) is written into channels [c_off, c_off + 256) of
-        the split-bf16 zero-bordered (B*(h+2)*(w+2), ctot) buffer (MAGNET.gnet_input_buffer), border rows zero; returns
-        (ref_gmms (B,2,h,w), nghbr_gmms (N-B,2,h,w)).  Without x_d3_out: returns (mono_gmms (N,2,h,w), x_feat (N,256,h,w)) NCHW fp32,
-        as the reference's DNET(dnet=False)."""
+    def _features(self, features):
+        """The four feature maps the decoder reads, checked: ({index: (N, C, h, w) fp32 contiguous}, N, dims, device)."""
         if self.decoder.training:
             raise lib.MagnetError("DNetMFMA folds BatchNorm running statistics: call .eval() on the D-Net first")
         xs = {}
@@ -328,20 +354,12 @@ class DNetMFMA:
         if any(t.shape[0] != N for t in xs.values()):
             raise lib.MagnetError("DNetMFMA: the feature maps disagree on the batch size")
         dims = tuple(tuple(xs[i].shape[2:]) for i in (_SKIP_IN, 8, 6, 5))
-        (h32, w32), _, _, (h4, w4) = dims
-        dev = xs[_SKIP_IN].device
-        if x_d3_out is not None:
-            if n_ref is None or not (1 <= int(n_ref) <= N):
-                raise lib.MagnetError(f"DNetMFMA: x_d3_out needs n_ref in [1, {N}] (the reference images lead the batch)")
-            n_ref = int(n_ref)
-            ghi, glo, g_ld, c_off = x_d3_out
-            rows_ref = n_ref * (h4 + 2) * (w4 + 2)
-            if any(t.dtype != torch.bfloat16 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (rows_ref, g_ld) for t in (ghi, glo)) \
-                    or c_off % 8 or c_off < 0 or c_off + 256 > g_ld:
-                raise lib.MagnetError(f"DNetMFMA: x_d3_out must be ({rows_ref}, ctot) planes with 256 channels at c_off (multiple of 8)")
-        elif n_ref is not None:
-            raise lib.MagnetError("DNetMFMA: n_ref goes with x_d3_out (without it run() returns the NCHW (mono_gmms, x_feat))")
-        P = self.packed(dev)
+        return xs, N, dims, xs[_SKIP_IN].device
+
+    def _decode(self, xs, N, dims, dev):
+        """conv2 and up1..up3 up to the input planes of up3's second convolution (buffers()["up3.mid"]); returns the buffer dict."""
+        (h32, w32) = dims[0]
+        self.packed(dev)
         b = self._buffers(dev, N, dims)
 
         # conv2 (1x1 2048 -> 2048, no activation; D_dense_depth.py:177) -> compact fp32 for the bilinear upsampling
@@ -360,6 +378,29 @@ class DNetMFMA:
             if name != "up3":
                 self._conv(name + ".1", b[name + ".mid"], cout, wp, rows, out_f32=b[name + ".out"], border=(h + 2, 1), repad=1)
                 prev, ph, pw, pc = b[name + ".out"], h, w, cout
+        return b
+
+    @torch.no_grad()
+    def run(self, features, n_ref=None, x_d3_out=None):
+        """features: the encoder's list (indices 5, 6, 8, 11 are read; NCHW fp32 on the GPU).
+        x_d3_out = (hi, lo, ctot, c_off) with n_ref = B: x_feat of images [0, B) is written into channels [c_off, c_off + 256) of
+        the split-bf16 zero-bordered (B*(h+2)*(w+2), ctot) buffer (MAGNET.gnet_input_buffer), border rows zero; returns
+        (ref_gmms (B,2,h,w), nghbr_gmms (N-B,2,h,w)).  Without x_d3_out: returns (mono_gmms (N,2,h,w), x_feat (N,256,h,w)) NCHW fp32,
+        as the reference's DNET(dnet=False)."""
+        xs, N, dims, dev = self._features(features)
+        h4, w4 = dims[3]
+        if x_d3_out is not None:
+            if n_ref is None or not (1 <= int(n_ref) <= N):
+                raise lib.MagnetError(f"DNetMFMA: x_d3_out needs n_ref in [1, {N}] (the reference images lead the batch)")
+            n_ref = int(n_ref)
+            ghi, glo, g_ld, c_off = x_d3_out
+            rows_ref = n_ref * (h4 + 2) * (w4 + 2)
+            if any(t.dtype != torch.bfloat16 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (rows_ref, g_ld) for t in (ghi, glo)) \
+                    or c_off % 8 or c_off < 0 or c_off + 256 > g_ld:
+                raise lib.MagnetError(f"DNetMFMA: x_d3_out must be ({rows_ref}, ctot) planes with 256 channels at c_off (multiple of 8)")
+        elif n_ref is not None:
+            raise lib.MagnetError("DNetMFMA: n_ref goes with x_d3_out (without it run() returns the NCHW (mono_gmms, x_feat))")
+        b = self._decode(xs, N, dims, dev)
         # up3's second convolution is x_feat: the reference frames' rows straight into the G-Net buffer, the others into `feat`
         h, w, wp = h4, w4, w4 + 2
         img_rows = (h + 2) * wp
@@ -396,6 +437,44 @@ class DNetMFMA:
         x_feat = torch.empty((N, h, w, 256), dtype=torch.float32, device=dev)
         self._conv("up3.1", mid, 256, wp, N * img_rows, out_f32=x_feat, border=(h + 2, 1), repad=1)
         return mono, x_feat.permute(0, 3, 1, 2).contiguous()
+
+    @torch.no_grad()
+    def run_standalone(self, features):
+        """The stand-alone D-Net behind the encoder: (N, 2, 4h, 4w) fp32 [mu, variance], what the reference's DNET(dnet=True) returns in
+        eval mode for these features (D_dense_depth.py:187-192, DNET.py:55-60).  The decoder pass of run(), x_feat kept as split-bf16
+        planes, then three launches: the depth head, the mask head (both 3x3 + fused 1x1 tails) and magnet_dnet_upsample_gauss."""
+        xs, N, dims, dev = self._features(features)
+        if self._mask is None:
+            check_decoder(self.decoder, standalone=True)
+            mh = self.decoder.mask_head
+            # as the depth head: the fused epilogue has two hidden 1x1 layers, the second is the identity behind a ReLU
+            self._mask = ConvStackMFMA(nn.Sequential(mh[0], nn.ReLU(), mh[2], nn.ReLU(), self._eye, nn.ReLU(), mh[4]))
+        b = self._decode(xs, N, dims, dev)
+        h, w = dims[3]
+        wp = w + 2
+        rows = N * (h + 2) * wp
+        feat = b["feat"]
+        self._conv("up3.1", b["up3.mid"], 256, wp, rows, dst=feat, border=(h + 2, 1))
+        sink = DNetMFMA.event_sink
+        outs = []
+        for stack, work, cout in ((self._head, self._head_work, 2), (self._mask, self._mask_work, 144)):
+            if sink is not None:
+                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+            outs.append(stack.run(feat[0], feat[1], 256, rows, wp, work.setdefault(N, {})))
+            if sink is not None:
+                e1.record()
+                sink.append((e0, e1, 2.0 * rows * (9 * 256 * 128 + 128 * 128 + 128 * cout)))
+        (head, head_ld), (mask, mask_ld) = outs
+        out = torch.empty((N, 2, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+        if sink is not None:
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        lib.dnet_upsample_gauss(head, head_ld, mask, mask_ld, N, h, w, out)
+        if sink is not None:
+            e1.record()
+            sink.append((e0, e1, 0.0))                                # not a convolution: bandwidth, no matrix-core work
+        return out
 
     def __call__(self, features):
         """(mono_gmms (N,2,h,w), x_feat (N,256,h,w)) NCHW fp32: what the reference's DNET(dnet=False) returns for these features."""

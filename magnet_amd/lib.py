@@ -1105,7 +1105,7 @@ def fnet_stem_wgrad(img, dz, grad_w, work):
 
 
 # ---- the D-Net decoder (include/magnet_hip.h: magnet_conv_mfma_ex, magnet_dnet_gauss_head; csrc/dnet_kernels.hip) ----------------
-API_SYMBOLS = API_SYMBOLS + ("magnet_conv_mfma_ex", "magnet_dnet_gauss_head")
+API_SYMBOLS = API_SYMBOLS + ("magnet_conv_mfma_ex", "magnet_dnet_gauss_head", "magnet_dnet_upsample_gauss")
 ACT_BASE, ACT_LEAKY_RELU = 0, 1
 
 
@@ -1122,6 +1122,8 @@ def _dnet_protos(lib):
     lib.magnet_conv_mfma_ex.argtypes = [ctypes.POINTER(MagnetConvExArgs), P]
     lib.magnet_dnet_gauss_head.restype = ctypes.c_int
     lib.magnet_dnet_gauss_head.argtypes = [P, I, I, I, I, I, P, P]
+    lib.magnet_dnet_upsample_gauss.restype = ctypes.c_int
+    lib.magnet_dnet_upsample_gauss.argtypes = [P, I, P, I, I, I, I, P, P]
     lib._dnet_protos_done = True
     return lib
 
@@ -1137,3 +1139,35 @@ def dnet_gauss_head(head_out, ld, N, h, w, pad, out):
         raise MagnetError(f"dnet_gauss_head: out must be a contiguous ({N}, 2, {h}, {w}) tensor")
     with torch.cuda.device(x.device):
         _check(lib.magnet_dnet_gauss_head(x.data_ptr(), int(ld), N, h, w, pad, o.data_ptr(), _stream(x)), "magnet_dnet_gauss_head")
+
+
+def check_dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out):
+    """The shape / pitch / device rules of dnet_upsample_gauss (MagnetError); tensors on any device, nothing is launched."""
+    N, h, w, head_ld, mask_ld = int(N), int(h), int(w), int(head_ld), int(mask_ld)
+    if N <= 0 or h <= 0 or w <= 0:
+        raise MagnetError(f"dnet_upsample_gauss: bad dims N={N} h={h} w={w}")
+    if head_ld < 2 or head_ld % 2 or mask_ld < 144 or mask_ld % 4:
+        raise MagnetError(f"dnet_upsample_gauss: head_ld {head_ld} must be even and >= 2, mask_ld {mask_ld} a multiple of 4 and >= 144")
+    rows = N * (h + 2) * (w + 2)
+    for t, name, ld, c in ((head_out, "head output", head_ld, 2), (mask_out, "mask logits", mask_ld, 144)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise MagnetError(f"dnet_upsample_gauss: {name} must be a float32 tensor")
+        if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) != ld or t.shape[0] < rows or t.shape[1] < c:
+            raise MagnetError(f"dnet_upsample_gauss: {name} {tuple(t.shape)} does not hold {N} ({h}+2) x ({w}+2) grids of {c} channels at pitch {ld}")
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (N, 2, 4 * h, 4 * w) or not out.is_contiguous():
+        raise MagnetError(f"dnet_upsample_gauss: out must be a contiguous float32 ({N}, 2, {4 * h}, {4 * w}) tensor")
+    if head_out.device != out.device or mask_out.device != out.device:
+        raise MagnetError("dnet_upsample_gauss: head output, mask logits and out must be on the same device")
+
+
+def dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out):
+    """The stand-alone D-Net's tail in one launch: depth-head fp32 output (rows >= N*(h+2)*(w+2), head_ld; channel 0 = mu, 1 = v) and
+    mask-head logits (rows, mask_ld; channel n*16 + i*4 + j) -> out (N,2,4h,4w) = [up(mu), elu(up(v)) + 1 + 1e-10]
+    (D_dense_depth.py:85-100 then DNET.py:55-60)."""
+    check_dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out)
+    x, m, o = _dev(head_out, "head_out", torch.float32), _dev(mask_out, "mask_out", torch.float32), _dev(out, "out", torch.float32)
+    lib = _dnet_protos(load())
+    with torch.cuda.device(x.device):
+        _check(lib.magnet_dnet_upsample_gauss(x.data_ptr(), int(head_ld), m.data_ptr(), int(mask_ld), int(N), int(h), int(w), o.data_ptr(),
+                                              _stream(x)), "magnet_dnet_upsample_gauss")
+    return out

@@ -6,7 +6,13 @@ into a G-Net input buffer in place), on the stand-in encoder's features (the enc
 Also the HIP decoder's time per convolution layer class (CUDA events around each launch) at C2, B = 1.  Prints one JSON line per
 measurement; --out FILE appends them.
 
+--standalone times the stand-alone D-Net instead (DNET(dnet=True): decoder + depth head + mask head + learned convex upsampling +
+activation_G, encoder not timed): torch fp32 against DNetMFMA.run_standalone at C2 with N = 1 (the way test_DNet.py feeds it) and
+N = 4 and at KITTI with N = 1, plus the per-launch event times and the time of everything behind x_feat (the two head launches and
+magnet_dnet_upsample_gauss).  Each timing is the median of --repeats timed loops of --steps calls.
+
     python tools/bench_dnet.py [--steps 10] [--warmup 3] [--out profiles/dnet/bench_dnet.jsonl]
+    python tools/bench_dnet.py --standalone [--steps 20] [--warmup 5] [--repeats 5] [--out profiles/dnet/bench_dnet_standalone.jsonl]
 """
 import argparse
 import json
@@ -26,6 +32,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-magnet", action="store_true")
+    ap.add_argument("--standalone", action="store_true")
+    ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     from magnet_amd import fnet, lib, synth
     from magnet_amd.dnet import DNetMFMA, gaussian_activation
@@ -52,6 +60,59 @@ def main():
 
     def images(n, H, W, seed):
         return torch.rand(n, 3, H, W, generator=torch.Generator().manual_seed(seed)).to(dev)
+
+    def write_out():
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as fh:
+                for d_ in lines:
+                    fh.write(json.dumps(d_) + "\n")
+
+    if a.standalone:
+        import statistics
+        d = make_dnet(dnet=True).to(dev)
+        dec = d.d_net.decoder
+        runner = DNetMFMA(dec)
+
+        def median_ms(fn):
+            for _ in range(a.warmup):
+                fn()
+            torch.cuda.synchronize()
+            reps = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fn()
+                torch.cuda.synchronize()
+                reps.append((time.perf_counter() - t0) * 1e3 / a.steps)
+            return round(statistics.median(reps), 3), round(min(reps), 3), round(max(reps), 3)
+
+        for name, H, W, N in (("C2", 480, 640, 1), ("C2", 480, 640, 4), ("KITTI", 352, 1216, 1)):
+            with torch.no_grad():
+                feats = d.d_net.encoder(images(N, H, W, N))
+                # interleaved A/B/A/B: both forms see the same clocks
+                t_torch = median_ms(lambda: gaussian_activation(dec(feats), magnet=False))
+                t_hip = median_ms(lambda: runner.run_standalone(feats))
+                t_torch2 = median_ms(lambda: gaussian_activation(dec(feats), magnet=False))
+                t_hip2 = median_ms(lambda: runner.run_standalone(feats))
+                per = []
+                for _ in range(5):
+                    sink = []
+                    DNetMFMA.event_sink = sink
+                    runner.run_standalone(feats)
+                    torch.cuda.synchronize()
+                    DNetMFMA.event_sink = None
+                    per.append([e0.elapsed_time(e1) for e0, e1, _ in sink])
+            ms = [round(statistics.median(col), 3) for col in zip(*per)]
+            mt, mh = min(t_torch[0], t_torch2[0]), max(t_hip[0], t_hip2[0])      # the comparison least favourable to the HIP form
+            emit(dict(bench="dnet_standalone", shape=name, H=H, W=W, N=N, steps=a.steps, warmup=a.warmup, repeats=a.repeats,
+                      ms_torch_fp32=[t_torch, t_torch2], ms_hip=[t_hip, t_hip2], speedup_worst_case=round(mt / mh, 2),
+                      hip_faster=bool(mh < mt), launches=len(ms), ms_per_launch=ms, ms_decoder_convs=round(sum(ms[:-3]), 3),
+                      ms_depth_head=ms[-3], ms_mask_head=ms[-2], ms_upsample_gauss=ms[-1], ms_behind_x_feat=round(sum(ms[-3:]), 3)))
+            del feats
+            torch.cuda.empty_cache()
+        write_out()
+        return
 
     d = make_dnet().to(dev)
     dec = d.d_net.decoder
@@ -103,11 +164,7 @@ def main():
         emit(dict(bench="magnet_forward", shape="C2", B=1, V=4, D=64, iters=3, encoder="standin", fnet="PSMNet (matrix-core)",
                   steps=a.steps, warmup=a.warmup, ms_dnet_torch=res["torch"], ms_dnet_hip=res["hip"],
                   speedup=round(res["torch"] / res["hip"], 2)))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as fh:
-            for d_ in lines:
-                fh.write(json.dumps(d_) + "\n")
+    write_out()
 
 
 if __name__ == "__main__":
