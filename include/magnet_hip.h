@@ -212,7 +212,9 @@ MAGNET_API int magnet_upsample_depth(const float *depth, const float *mask, floa
  * Replaces the nn.Conv2d stacks of models/MAGNET.py:51-56 (GNET.gnet) and :111-116 (mask_head).
  * Activations live in ZERO-BORDERED channel-last buffers (B, h+2, w+2, C) stored as two bf16 planes
  * (hi = bf16(x), lo = bf16(x - hi)); `rows` = B*(h+2)*(w+2) flattened positions; a 3x3 tap is the row
- * offset dy*(w+2)+dx.  Border rows of the output hold unspecified finite values: read interior rows only.
+ * offset dy*(w+2)+dx.  Border rows of the output hold unspecified finite values or are not written at all: read interior rows
+ * only.  (Launches with gu_in or up_depth know their image geometry and tile each image on its own from its first interior image
+ * row when that takes fewer workgroups: the top and bottom border image rows are then not computed.  MagnetConvExArgs.tiling.)
  * Weights: two bf16 planes of [taps][cout_pad][cin] (cin contiguous) — magnet_amd/convnet.py prepacks them
  * from nn.Conv2d's [cout][cin][kh][kw]; bias fp32 [cout_pad] (zero in the padding).
  * Limits: cin % 32 == 0; taps in {1, 4, 9}; cout_pad a multiple of 128, or 144, 64, 32, 16.
@@ -554,13 +556,29 @@ enum {                                     /* MagnetConvExArgs.act */
                                               (bf16 planes, fp32, single bf16 plane, channel slices, zero border, repad) applies it */
 };
 
-/* magnet_conv_mfma with an activation mode.  act = MAGNET_ACT_BASE gives exactly magnet_conv_mfma(&args->base). */
+enum {                                     /* MagnetConvExArgs.tiling: bit flags, for tests and A/B runs; 0 = the library chooses */
+    MAGNET_TILING_FLAT  = 1,               /* cut the flattened rows into tiles from row 0 on, also where per-image tiling (launches with
+                                              base.gu_in / base.up_depth) would take fewer workgroups.  Same kernel, same interior results. */
+    MAGNET_TILING_BM256 = 2                /* fused-tail 3x3 launches: the 256-row 8-wave kernel also below 65 536 rows */
+};
+
+/* magnet_conv_mfma with an activation mode.  act = MAGNET_ACT_BASE and the other fields zero give exactly magnet_conv_mfma(&args->base). */
 typedef struct MagnetConvExArgs {
     MagnetConvArgs base;
     int32_t        act;                    /* MAGNET_ACT_* */
     float          act_slope;              /* negative slope of MAGNET_ACT_LEAKY_RELU (nn.LeakyReLU(): 0.01); finite */
+    int32_t        tiling;                 /* MAGNET_TILING_* flags */
+    int64_t       *tiles_out;              /* optional HOST pointer: receives the number of row tiles (workgroups along x) launched */
 } MagnetConvExArgs;
 MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
+
+/* Row tiling of the launches that know their image geometry (base.gu_in / base.up_depth): the number of bm-row tiles (workgroups
+ * along x) for n_img zero-bordered (h + 2, wp) grids, and in *tiles_per_img (optional) the tiles per image, or 0 for flat tiling.
+ * Flat: tile t covers rows [t bm, (t + 1) bm) of the flattened buffer, ceil(n_img (h + 2) wp / bm) tiles.  Per image: tile t of image i
+ * covers the bm rows from i (h + 2) wp + wp + t bm on, ceil(h wp / bm) tiles per image; the top and bottom border image rows get no
+ * tile.  Per-image tiling is used only when it takes fewer tiles than flat and an image's last tile ends inside that image.  Host
+ * arithmetic only (no GPU needed); returns 0 on bad dimensions.  bm is 256 for fused-tail 3x3 launches of at least 65 536 rows, else 128. */
+MAGNET_API int64_t magnet_conv_row_tiles(int32_t n_img, int32_t h, int32_t wp, int32_t bm, int32_t *tiles_per_img);
 
 /* The D-Net's Gaussian activation behind its depth head (activation_G_magnet, models/DNET.py:62-67): from the head's fp32 output
  * `in` (rows, in_ld) over zero-bordered (N, h+2*pad, w+2*pad) grids (channel 0 = mu, channel 1 = v; border rows are not read)

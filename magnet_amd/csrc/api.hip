@@ -290,7 +290,7 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 }
 
 // magnet_conv_mfma and magnet_conv_mfma_ex: leaky != 0 selects LeakyReLU(leaky_slope) after bias (validated by the _ex entry point)
-static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, void* stream) {
+static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
     if (!a->in_hi || !a->in_lo || !a->w_hi || !a->w_lo || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
     if (a->out_mode < 0 || a->out_mode > 2) return fail(MAGNET_E_DIM, "magnet_conv_mfma: out_mode must be 0, 1 or 2");
@@ -380,14 +380,17 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
         p.gu_in = a->gu_in; p.gu_out = a->gu_out; p.up_B = a->up_B; p.up_h = a->up_h; p.up_w = a->up_w;
     }
     p.leaky = leaky; p.leaky_slope = leaky_slope;
+    long long tiles = 0;
+    p.tiling = tiling; p.tiles_out = tiles_out ? &tiles : nullptr;
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
     hipError_t e = magnet::launch_conv_mfma(p, (hipStream_t)stream);
+    if (tiles_out) *tiles_out = tiles;
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv_mfma launch");
 }
 
-MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) { return conv_mfma_run(a, 0, 0.f, stream); }
+MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) { return conv_mfma_run(a, 0, 0.f, 0, nullptr, stream); }
 
 MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_ex: args is NULL");
@@ -397,7 +400,16 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
         if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
             return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: act_slope must be finite");
     }
-    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, stream);
+    if (a->tiling & ~(MAGNET_TILING_FLAT | MAGNET_TILING_BM256)) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: tiling=%d unknown", a->tiling);
+    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream);
+}
+
+MAGNET_API int64_t magnet_conv_row_tiles(int32_t n_img, int32_t h, int32_t wp, int32_t bm, int32_t* tiles_per_img) {
+    int per = 0;
+    if (n_img <= 0 || h <= 0 || wp < 3 || bm <= 0) { if (tiles_per_img) *tiles_per_img = 0; return 0; }
+    const long long n = magnet::conv_row_tiles(n_img, h, wp, bm, &per);
+    if (tiles_per_img) *tiles_per_img = per;
+    return n;
 }
 
 MAGNET_API int magnet_dnet_gauss_head(const float* in, int32_t in_ld, int32_t N, int32_t h, int32_t w, int32_t pad, float* out,

@@ -49,7 +49,24 @@ struct ConvParams {
     // multiplied by leaky_slope after bias / addend.  Plain epilogue only (not with the fused tail)
     int leaky;
     float leaky_slope;
+    // row tiling (launch_conv_mfma decides; see conv_mfma_tile).  tiles_per_img = 0: tile t starts at row t * BM of the flat buffer.
+    // tiles_per_img > 0 (launches that carry up_B / up_h / wp): every image is tiled on its own from its first interior image row,
+    // tile t starts at row (t / tiles_per_img) * (up_h + 2) * wp + wp + (t % tiles_per_img) * BM; the border image rows get no tile
+    int tiles_per_img;
+    int tiling;                                       // host side only: MAGNET_TILING_* of MagnetConvExArgs (0 = the launcher chooses)
+    long long* tiles_out;                             // host side only, optional: receives the number of row tiles launched
 };
+
+// Row tiles of a launch over `n_img` zero-bordered (h + 2, wp) grids with `bm`-row tiles.  Returns the tile count and sets *per_img to
+// the tiles per image (per-image tiling) or to 0 (flat tiling).  Per-image tiling covers the h * wp rows from each image's first
+// interior image row; it is taken only when it launches FEWER tiles than the flat form and the last tile of an image ends inside that
+// image (so a tile never computes rows of two images and every interior row belongs to exactly one tile).
+inline long long conv_row_tiles(long long n_img, long long h, long long wp, long long bm, int* per_img) {
+    const long long flat = (n_img * (h + 2) * wp + bm - 1) / bm, per = (h * wp + bm - 1) / bm;
+    const bool by_image = n_img * per < flat && per * bm <= (h + 1) * wp;
+    *per_img = by_image ? (int)per : 0;
+    return by_image ? n_img * per : flat;
+}
 
 struct ChainParams {
     const uint16_t* in_hi;  const uint16_t* in_lo;    // (rows, 128)

@@ -285,7 +285,10 @@ __device__ __forceinline__ f32x4_t cv_mma(const bf16x8_t& a, const bf16x8_t& b, 
 // VGPR form of the MFMAs — with the default bound it kept the accumulators in AGPRs and moved all 64 of them through VGPRs
 // (64 v_accvgpr_read + 64 v_accvgpr_write) on every trip of the K loop.
 // One output tile (CV_BM rows x BN channels).  `bid` of `n_tiles`: the tile's position in launch order (the block id); `by`: the channel
-// block.  Measured and not kept (the source is in the history): the ping-pong loop without a window (equal to the 4-wave loop, 5.83 vs
+// block.  A tile is CV_BM consecutive rows of the flattened (B, h+2, w+2) buffer.  Flat tiling cuts the whole buffer into tiles; per-image
+// tiling (ConvParams::tiles_per_img, the launches with a fused Gaussian update / upsampling) cuts each image's h * wp rows from its first
+// interior image row on, so the top and bottom border image rows — which no consumer reads — get no tile, and 64 frames of 120x160
+// are 64 x 76 = 4 864 tiles = 19 full rounds of 256 workgroups instead of 4 941 = 19.3 (profiles/r8/NOTES.md).  Measured and not kept (the source is in the history): the ping-pong loop without a window (equal to the 4-wave loop, 5.83 vs
 // 5.91 ms per C2 step), with a 2-slot LDS window, with fragment double-buffering and with deeper prefetch (4 % slower: 2.19 vs 2.10 ms,
 // profiles/r4/conv_deeper_prefetch_vs_round3.log); persistent workgroups (0.7 % slower, profiles/r4/conv_persistent_ab.log); the 32x32x16 MFMA shape (5.5 %
 // slower, profiles/r5/conv_m32_ab.log); a row-owned fused tail (see tail_layer_cols).
@@ -313,7 +316,14 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         const unsigned n = n_tiles, q = n / 8, r = n % 8, xcd = bid % 8, idx = bid / 8;
         tile_id = (long long)((xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-    const long long row0 = tile_id * CV_BM;
+    // tile -> first row.  Flat: tile t starts at row t * BM.  Per image (ConvParams::tiles_per_img, chosen by launch_conv_nf): tile t of
+    // image i starts at the image's first interior image row + t * BM.  Either way the tile is the CV_BM consecutive flat rows from
+    // row0 on, so nothing below depends on the form; bid is wave-uniform, so the division runs once per workgroup on the scalar unit
+    long long row0 = tile_id * CV_BM;
+    if (p.tiles_per_img) {
+        const unsigned img = (unsigned)tile_id / (unsigned)p.tiles_per_img, t = (unsigned)tile_id - img * (unsigned)p.tiles_per_img;
+        row0 = (long long)img * ((p.up_h + 2) * p.wp) + p.wp + (long long)t * CV_BM;
+    }
     const int n0 = by * BN;
 
     // staging by LDS-DMA (global_load_lds_dwordx4: global -> LDS without a VGPR round trip or ds_write): a
@@ -1127,8 +1137,18 @@ static size_t conv_lds_bytes() {
 }
 
 template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0>
-static hipError_t launch_conv_nf(const ConvParams& p, hipStream_t s) {
-    dim3 grid((unsigned)((p.rows + BM - 1) / BM), (unsigned)(p.cout_pad / (NF * 16))), block(NT);
+static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
+    // row tiles: the launches with a fused Gaussian update / upsampling know their image geometry (up_B, up_h, wp; rows checked by the
+    // API) and write interior positions only, so each image can be tiled on its own without its top and bottom border image rows —
+    // taken when that is fewer tiles (conv_row_tiles; 64 frames of 120x160: 4 864 = 19 x 256 instead of 4 941).  MAGNET_TILING_FLAT
+    // (MagnetConvExArgs; dev library: MAGNET_CONV_VARIANT bit 4096) keeps the flat form: same kernel, the other row0 formula.
+    ConvParams p = p_in;
+    long long n_tiles = (p.rows + BM - 1) / BM;
+    p.tiles_per_img = 0;
+    if (p.up_B > 0 && (p.gu_out || p.up_out) && !(p.tiling & 1) && !(p.variant & 4096))
+        n_tiles = conv_row_tiles(p.up_B, p.up_h, p.wp, BM, &p.tiles_per_img);
+    if (p.tiles_out) *p.tiles_out = n_tiles;
+    dim3 grid((unsigned)n_tiles, (unsigned)(p.cout_pad / (NF * 16))), block(NT);
     size_t lds = conv_lds_bytes<NF, WN, BM, SPB, NT, PP, WIN>();
     if (TAIL > 0 && lds < (size_t)BM * 512) lds = (size_t)BM * 512;     // the fused tail's activation tile: BM rows x 256 B x (hi, lo)
     if (TAIL == 9 && lds < (size_t)128 * 148 * 4) lds = (size_t)128 * 148 * 4;   // fused upsampling: 128 rows x 144 logits (+4 pad) fp32 (two 4-wave workgroups still fit a CU)
@@ -1145,7 +1165,8 @@ static hipError_t launch_conv_nf(const ConvParams& p, hipStream_t s) {
 hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     // p.variant is 0 in the product library; the dev library takes it from MAGNET_CONV_VARIANT.  Each bit only moves a launch to an
     // instance that other shapes reach anyway: 1 = no row window, 8 = the 2-slot LDS window instead of the register window, 16 = the
-    // 4-wave register-window loop where the 8-wave one is the default, 256 / 2048 = the 8-wave loop for addend / split-bf16 launches.
+    // 4-wave register-window loop where the 8-wave one is the default, 256 / 2048 = the 8-wave loop for addend / split-bf16 launches,
+    // 4096 = flat row tiling where per-image tiling is the default (launch_conv_nf).
     // 128 channels: 2x2 waves of 64x64 on a 128-row tile.
     // Measured alternatives on the G-Net 3x3 layer (64 frames; this configuration: 2.31 ms): 64-row tile / 3 workgroups
     // per CU 2.80 ms; two K stages per barrier (4-stage ring, 128 KB LDS, 1 workgroup per CU) 3.51 ms; 256-row tile
@@ -1165,7 +1186,8 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
         // — and not for the per-iteration launches of a hoisted first layer (fp32 addend, K = 9 x 32 .. 9 x 64): those are short K
         // loops between an exposed 128 KB addend load and the tail, where two co-resident 4-wave workgroups overlap better than one
         // 8-wave workgroup (same-box A/B: 425 vs 464 us at K = 288, 766 vs 804 us at K = 576)
-        if (win && p.tap_n == 3 && !(p.variant & (16 | 8)) && p.rows >= 256ll * 256 && (!p.addend || (p.variant & 256))) {
+        // (MAGNET_TILING_BM256 of MagnetConvExArgs takes it at any row count: the tests reach its tile edges with small grids)
+        if (win && p.tap_n == 3 && !(p.variant & (16 | 8)) && (p.rows >= 256ll * 256 || (p.tiling & 2)) && (!p.addend || (p.variant & 256))) {
             if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 2>(p, s);
             if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 2>(p, s);
             if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 2>(p, s);

@@ -437,7 +437,7 @@ def _bf16_ptr(t, name):
 
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
-              mx=None, leaky=None):
+              mx=None, leaky=None, tiling=None):
     """One convolution layer on the matrix cores.  in_hi/in_lo: bf16 tensors whose data_ptr is row 0 (possibly a
     channel-offset view of a wider buffer, `in_ld` = its row pitch in elements); weights (taps, cout_pad, cin) bf16.
     F-Net extras (include/magnet_hip.h): dil (3x3 dilation), out_ld (write a channel slice: out tensors may then be
@@ -448,7 +448,9 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     the tail's last layer (models/MAGNET.py:15-27) and only `outs` is written.
     gauss = (gmm_in (B,2,h,w), gmm_out): with tail cout_pad 16 (G-Net's head) the Gaussian update of models/MAGNET.py:60-69 runs
     in the tail's last layer and only `gmm_out` is written.
-    leaky = slope: LeakyReLU(slope) after bias instead of ReLU (magnet_conv_mfma_ex; relu must be False, no tail)."""
+    leaky = slope: LeakyReLU(slope) after bias instead of ReLU (magnet_conv_mfma_ex; relu must be False, no tail).
+    tiling = TILING_* flags (magnet_conv_mfma_ex; tests and A/B runs).  Returns the number of row tiles launched when the launch went
+    through magnet_conv_mfma_ex, else None."""
     lib = _conv_protos(load())
     a = MagnetConvArgs()
     if mx is not None:
@@ -505,11 +507,14 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
     with torch.cuda.device(in_hi.device):
-        if leaky is None:
+        if leaky is None and tiling is None:
             _check(lib.magnet_conv_mfma(ctypes.byref(a), _stream(in_hi)), "magnet_conv_mfma")
-        else:
-            x = MagnetConvExArgs(base=a, act=ACT_LEAKY_RELU, act_slope=float(leaky))
-            _check(_dnet_protos(lib).magnet_conv_mfma_ex(ctypes.byref(x), _stream(in_hi)), "magnet_conv_mfma_ex")
+            return None
+        tiles = ctypes.c_int64(0)
+        x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
+                             tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
+        _check(_dnet_protos(lib).magnet_conv_mfma_ex(ctypes.byref(x), _stream(in_hi)), "magnet_conv_mfma_ex")
+        return tiles.value
 
 
 def pack_split(x_nchw, out_hi, out_lo, ctot, c_off):
@@ -1105,13 +1110,15 @@ def fnet_stem_wgrad(img, dz, grad_w, work):
 
 
 # ---- the D-Net decoder (include/magnet_hip.h: magnet_conv_mfma_ex, magnet_dnet_gauss_head; csrc/dnet_kernels.hip) ----------------
-API_SYMBOLS = API_SYMBOLS + ("magnet_conv_mfma_ex", "magnet_dnet_gauss_head", "magnet_dnet_upsample_gauss")
+API_SYMBOLS = API_SYMBOLS + ("magnet_conv_mfma_ex", "magnet_conv_row_tiles", "magnet_dnet_gauss_head", "magnet_dnet_upsample_gauss")
 ACT_BASE, ACT_LEAKY_RELU = 0, 1
+TILING_FLAT, TILING_BM256 = 1, 2
 
 
 class MagnetConvExArgs(ctypes.Structure):
     """Mirror of `struct MagnetConvExArgs` (include/magnet_hip.h)."""
-    _fields_ = [("base", MagnetConvArgs), ("act", ctypes.c_int32), ("act_slope", ctypes.c_float)]
+    _fields_ = [("base", MagnetConvArgs), ("act", ctypes.c_int32), ("act_slope", ctypes.c_float),
+                ("tiling", ctypes.c_int32), ("tiles_out", ctypes.POINTER(ctypes.c_int64))]
 
 
 def _dnet_protos(lib):
@@ -1120,6 +1127,8 @@ def _dnet_protos(lib):
     I, P = ctypes.c_int32, ctypes.c_void_p
     lib.magnet_conv_mfma_ex.restype = ctypes.c_int
     lib.magnet_conv_mfma_ex.argtypes = [ctypes.POINTER(MagnetConvExArgs), P]
+    lib.magnet_conv_row_tiles.restype = ctypes.c_int64
+    lib.magnet_conv_row_tiles.argtypes = [I, I, I, I, ctypes.POINTER(I)]
     lib.magnet_dnet_gauss_head.restype = ctypes.c_int
     lib.magnet_dnet_gauss_head.argtypes = [P, I, I, I, I, I, P, P]
     lib.magnet_dnet_upsample_gauss.restype = ctypes.c_int
