@@ -4,6 +4,9 @@ torch is used for device memory and streams only: every call passes `tensor.data
 current HIP stream through the C boundary.  There is NO CPU fallback — if the library is missing,
 or an argument lives on the CPU, the call raises.  torch must be imported before the library is
 loaded so that libmagnet_hip.so binds to the same libamdhip64 (same SONAME) torch has loaded.
+
+The binding is declared once: the constants, the argument-struct mirrors and `_PROTOS`, the prototype of every
+entry point, which load() applies before it returns the handle.  tests/test_abi.py checks all three against the header.
 """
 from __future__ import annotations
 
@@ -15,18 +18,15 @@ import torch  # noqa: F401  (must precede CDLL: shares torch's HIP runtime)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmagnet_hip.so")
 
+# the enums and #defines of include/magnet_hip.h
 FEAT_F32, FEAT_BF16 = 0, 1
-MAX_CANDIDATES = 256
-
-API_SYMBOLS = ("magnet_version", "magnet_last_error", "magnet_device_count", "magnet_pack_features",
-               "magnet_pack_gmm", "magnet_pack_gmm_quad",
-               "magnet_cost_volume_cw", "magnet_cost_volume_f_backward", "magnet_cost_volume_f_backward_ws",
-               "magnet_cost_volume_f_backward_workspace", "magnet_gaussian_update",
-               "magnet_upsample_depth")
-
-
-# argument-error codes of include/magnet_hip.h (positive return values; negative = -(hipError_t))
+# argument-error codes (positive return values; negative = -(hipError_t))
 E_NULL, E_DIM, E_DTYPE, E_ALIGN, E_NODEVICE, E_SHAPE = 1, 2, 3, 4, 5, 6
+MAX_CANDIDATES = 256
+NLL_BLOCKS, NLL_MAX_ITER = 256, 16
+BN_BLOCKS = 256
+ACT_BASE, ACT_LEAKY_RELU = 0, 1
+TILING_FLAT, TILING_BM256 = 1, 2
 
 
 class MagnetError(RuntimeError):
@@ -61,6 +61,164 @@ class MagnetCostVolumeArgs(ctypes.Structure):
     ]
 
 
+class MagnetConvArgs(ctypes.Structure):
+    """Mirror of `struct MagnetConvArgs` (include/magnet_hip.h)."""
+    _fields_ = [
+        ("in_hi", ctypes.c_void_p), ("in_lo", ctypes.c_void_p), ("w_hi", ctypes.c_void_p), ("w_lo", ctypes.c_void_p),
+        ("bias", ctypes.c_void_p), ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("out_f32", ctypes.c_void_p),
+        ("rows", ctypes.c_int64),
+        ("cin", ctypes.c_int32), ("cout_pad", ctypes.c_int32), ("taps", ctypes.c_int32), ("wp", ctypes.c_int32),
+        ("relu", ctypes.c_int32), ("out_mode", ctypes.c_int32), ("in_ld", ctypes.c_int32),
+        ("addend", ctypes.c_void_p), ("addend_ld", ctypes.c_int32),
+        ("dil", ctypes.c_int32), ("out_ld", ctypes.c_int32),
+        ("add_hi", ctypes.c_void_p), ("add_lo", ctypes.c_void_p), ("add_ld", ctypes.c_int32),
+        ("border_hp", ctypes.c_int32), ("border_pad", ctypes.c_int32), ("repad", ctypes.c_int32),
+        ("tail_w_hi", ctypes.c_void_p), ("tail_w_lo", ctypes.c_void_p), ("tail_bias", ctypes.c_void_p),
+        ("tail_cout_pad", ctypes.c_int32),
+        ("up_depth", ctypes.c_void_p), ("up_out", ctypes.c_void_p),
+        ("up_npred", ctypes.c_int32), ("up_B", ctypes.c_int32), ("up_h", ctypes.c_int32), ("up_w", ctypes.c_int32),
+        ("gu_in", ctypes.c_void_p), ("gu_out", ctypes.c_void_p),
+        ("in_sc", ctypes.c_void_p), ("w_sc", ctypes.c_void_p), ("sc_rows", ctypes.c_int64),
+    ]
+
+
+class MagnetNllArgs(ctypes.Structure):
+    """Mirror of `struct MagnetNllArgs` (include/magnet_hip.h)."""
+    _fields_ = [("preds", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("sums", ctypes.c_void_p),
+                ("loss", ctypes.c_void_p), ("work", ctypes.c_void_p), ("grad_loss", ctypes.c_void_p), ("grad_preds", ctypes.c_void_p),
+                ("gamma", ctypes.c_double),
+                ("n_iter", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+class MagnetUpsampleBwdArgs(ctypes.Structure):
+    """Mirror of `struct MagnetUpsampleBwdArgs` (include/magnet_hip.h)."""
+    _fields_ = [("grad_up", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("grad_depth", ctypes.c_void_p), ("grad_mask", ctypes.c_void_p), ("work", ctypes.c_void_p),
+                ("mask_sb", ctypes.c_int64), ("mask_sc", ctypes.c_int64), ("mask_sy", ctypes.c_int64), ("mask_sx", ctypes.c_int64),
+                ("gm_sb", ctypes.c_int64), ("gm_sc", ctypes.c_int64), ("gm_sy", ctypes.c_int64), ("gm_sx", ctypes.c_int64),
+                ("n_pred", ctypes.c_int32), ("B", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("k", ctypes.c_int32)]
+
+
+class MagnetHeadDgradArgs(ctypes.Structure):
+    """Mirror of `struct MagnetHeadDgradArgs` (include/magnet_hip.h)."""
+    _fields_ = [("dout", ctypes.c_void_p), ("k0", ctypes.c_int32),
+                ("wt_hi", ctypes.c_void_p), ("wt_lo", ctypes.c_void_p),
+                ("h3_hi", ctypes.c_void_p), ("h2_hi", ctypes.c_void_p), ("h1_hi", ctypes.c_void_p),
+                ("dout_hi", ctypes.c_void_p), ("dout_lo", ctypes.c_void_p),
+                ("dh3_hi", ctypes.c_void_p), ("dh3_lo", ctypes.c_void_p), ("dh2_hi", ctypes.c_void_p), ("dh2_lo", ctypes.c_void_p),
+                ("dh1_hi", ctypes.c_void_p), ("dh1_lo", ctypes.c_void_p),
+                ("acc", ctypes.c_void_p), ("acc_hi", ctypes.c_void_p), ("acc_lo", ctypes.c_void_p), ("acc_mode", ctypes.c_int32),
+                ("B", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("rows", ctypes.c_int64),
+                ("grad_gmm", ctypes.c_void_p), ("gnet_out", ctypes.c_void_p), ("gmm_in", ctypes.c_void_p), ("gnet_ld", ctypes.c_int32)]
+
+
+class MagnetWgradArgs(ctypes.Structure):
+    """Mirror of `struct MagnetWgradArgs` (include/magnet_hip.h)."""
+    _fields_ = [("dy_hi", ctypes.c_void_p), ("dy_lo", ctypes.c_void_p), ("x_hi", ctypes.c_void_p), ("x_lo", ctypes.c_void_p),
+                ("dy_ld", ctypes.c_int64), ("x_ld", ctypes.c_int64), ("rows", ctypes.c_int64),
+                ("cout", ctypes.c_int32), ("cin", ctypes.c_int32), ("taps", ctypes.c_int32), ("wp", ctypes.c_int32),
+                ("grad_w", ctypes.c_void_p), ("grad_b", ctypes.c_void_p),
+                ("cout_valid", ctypes.c_int32), ("cin_valid", ctypes.c_int32), ("cin_total", ctypes.c_int32), ("cin_dst", ctypes.c_int32),
+                ("accumulate", ctypes.c_int32), ("work", ctypes.c_void_p)]
+
+
+class MagnetBnTrainArgs(ctypes.Structure):
+    """Mirror of `struct MagnetBnTrainArgs` (include/magnet_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_ld", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("hp", ctypes.c_int32), ("wp", ctypes.c_int32), ("pad", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("work", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p),
+                ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p), ("num_batches_tracked", ctypes.c_void_p),
+                ("eps", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("res_hi", ctypes.c_void_p), ("res_lo", ctypes.c_void_p), ("res_ld", ctypes.c_int64),
+                ("relu", ctypes.c_int32),
+                ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("out_f32", ctypes.c_void_p), ("out_ld", ctypes.c_int64)]
+
+
+class MagnetWgradExArgs(ctypes.Structure):
+    """Mirror of `struct MagnetWgradExArgs` (include/magnet_hip.h)."""
+    _fields_ = [("base", MagnetWgradArgs), ("dil", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MagnetBnBwdArgs(ctypes.Structure):
+    """Mirror of `struct MagnetBnBwdArgs` (include/magnet_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_ld", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("hp", ctypes.c_int32), ("wp", ctypes.c_int32), ("pad", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("relu", ctypes.c_int32),
+                ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("g", ctypes.c_void_p), ("g_ld", ctypes.c_int64), ("work", ctypes.c_void_p),
+                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p),
+                ("dx_hi", ctypes.c_void_p), ("dx_lo", ctypes.c_void_p), ("dx_ld", ctypes.c_int64)]
+
+
+class MagnetSppBwdArgs(ctypes.Structure):
+    """Mirror of `struct MagnetSppBwdArgs` (include/magnet_hip.h)."""
+    _fields_ = [("g", ctypes.c_void_p), ("g_ld", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("pad", ctypes.c_int32), ("c_off", ctypes.c_int32),
+                ("ph", ctypes.c_int32), ("pw", ctypes.c_int32),
+                ("dq", ctypes.c_void_p), ("dpool", ctypes.c_void_p * 4), ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int64)]
+
+
+class MagnetConvExArgs(ctypes.Structure):
+    """Mirror of `struct MagnetConvExArgs` (include/magnet_hip.h)."""
+    _fields_ = [("base", MagnetConvArgs), ("act", ctypes.c_int32), ("act_slope", ctypes.c_float),
+                ("tiling", ctypes.c_int32), ("tiles_out", ctypes.POINTER(ctypes.c_int64))]
+
+
+# (restype, argtypes) of every MAGNET_API declaration of include/magnet_hip.h, in header order; load() applies them all
+_C, _L, _F, _I, _P, _S = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER
+_PROTOS = {
+    "magnet_version": (_C, []),
+    "magnet_last_error": (ctypes.c_char_p, []),
+    "magnet_device_count": (_C, []),
+    "magnet_pack_features": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "magnet_pack_gmm": (_C, [_P, _P, _I, _I, _I, _P]),
+    "magnet_pack_gmm_quad": (_C, [_P, _P, _I, _I, _I, _P]),
+    "magnet_cost_volume_cw": (_C, [_S(MagnetCostVolumeArgs), _P]),
+    "magnet_cost_volume_f_backward": (_C, [_S(MagnetCostVolumeArgs), _P, _P, _P, _P]),
+    "magnet_make_rays": (_C, [_P, _P, _I, _I, _I, _P]),
+    "magnet_relative_poses": (_C, [_P, _P, _P, _P, _I, _I, _P]),
+    "magnet_cost_volume_f_backward_workspace": (_L, [_S(MagnetCostVolumeArgs)]),
+    "magnet_cost_volume_f_backward_ws": (_C, [_S(MagnetCostVolumeArgs), _P, _P, _P, _P, _L, _P]),
+    "magnet_gaussian_update": (_C, [_P, _P, _P, _I, _I, _P]),
+    "magnet_upsample_depth": (_C, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "magnet_conv_mfma": (_C, [_S(MagnetConvArgs), _P]),
+    "magnet_pack_mx": (_C, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _P]),
+    "magnet_fnet_stem": (_C, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "magnet_space_to_depth": (_C, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "magnet_avgpool_cl": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "magnet_upsample_bilinear_cl": (_C, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "magnet_conv1x1_chain": (_C, [_P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    "magnet_pack_split": (_C, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
+    "magnet_gaussian_update_cl": (_C, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    "magnet_upsample_depth_cl": (_C, [_P, _P, _I, _P, _I, _I, _I, _P]),
+    "magnet_upsample_depth_cl_n": (_C, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "magnet_depth_metrics": (_C, [_P, _P, _P, _I, _I, _F, _F, _P]),
+    "magnet_depth_metrics_crop": (_C, [_P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P]),
+    "magnet_nll_loss_forward": (_C, [_S(MagnetNllArgs), _P]),
+    "magnet_nll_loss_backward": (_C, [_S(MagnetNllArgs), _P]),
+    "magnet_upsample_depth_backward": (_C, [_S(MagnetUpsampleBwdArgs), _P]),
+    "magnet_head_dgrad": (_C, [_S(MagnetHeadDgradArgs), _P]),
+    "magnet_wgrad_workspace": (_L, [_S(MagnetWgradArgs)]),
+    "magnet_wgrad": (_C, [_S(MagnetWgradArgs), _P]),
+    "magnet_fnet_stem_raw": (_C, [_P, _P, _P, _I, _I, _I, _P]),
+    "magnet_bn_train_stats": (_C, [_S(MagnetBnTrainArgs), _P]),
+    "magnet_bn_train_apply": (_C, [_S(MagnetBnTrainArgs), _P]),
+    "magnet_wgrad_ex_workspace": (_L, [_S(MagnetWgradExArgs)]),
+    "magnet_wgrad_ex": (_C, [_S(MagnetWgradExArgs), _P]),
+    "magnet_bn_train_backward": (_C, [_S(MagnetBnBwdArgs), _P]),
+    "magnet_fnet_grad_pack": (_C, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "magnet_fnet_d2s_backward": (_C, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "magnet_spp_upsample_backward": (_C, [_S(MagnetSppBwdArgs), _P]),
+    "magnet_spp_pool_backward": (_C, [_S(MagnetSppBwdArgs), _P]),
+    "magnet_fnet_stem_wgrad": (_C, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "magnet_conv_mfma_ex": (_C, [_S(MagnetConvExArgs), _P]),
+    "magnet_conv_row_tiles": (_L, [_I, _I, _I, _I, _S(_I)]),
+    "magnet_dnet_gauss_head": (_C, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
+}
+API_SYMBOLS = tuple(_PROTOS)
+
 _lib = None
 
 
@@ -74,7 +232,7 @@ def use_dev_build():
 
 
 def load() -> ctypes.CDLL:
-    """Load the library (once).  Raises MagnetError if it has not been built."""
+    """Load the library (once) and type every entry point.  Raises MagnetError if it has not been built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -83,24 +241,9 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built. Run `python -m magnet_amd.build` "
             "(or __graft_entry__.build()). magnet_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    I, P = ctypes.c_int32, ctypes.c_void_p
-    lib.magnet_version.restype = ctypes.c_int
-    lib.magnet_last_error.restype = ctypes.c_char_p
-    lib.magnet_device_count.restype = ctypes.c_int
-    lib.magnet_pack_features.restype = ctypes.c_int
-    lib.magnet_pack_features.argtypes = [P, P, I, I, I, I, I, I, P]
-    lib.magnet_pack_gmm.restype = ctypes.c_int
-    lib.magnet_pack_gmm.argtypes = [P, P, I, I, I, P]
-    lib.magnet_pack_gmm_quad.restype = ctypes.c_int
-    lib.magnet_pack_gmm_quad.argtypes = [P, P, I, I, I, P]
-    lib.magnet_cost_volume_cw.restype = ctypes.c_int
-    lib.magnet_cost_volume_cw.argtypes = [ctypes.POINTER(MagnetCostVolumeArgs), P]
-    lib.magnet_cost_volume_f_backward.restype = ctypes.c_int
-    lib.magnet_cost_volume_f_backward.argtypes = [ctypes.POINTER(MagnetCostVolumeArgs), P, P, P, P]
-    lib.magnet_gaussian_update.restype = ctypes.c_int
-    lib.magnet_gaussian_update.argtypes = [P, P, P, I, I, P]
-    lib.magnet_upsample_depth.restype = ctypes.c_int
-    lib.magnet_upsample_depth.argtypes = [P, P, P, I, I, I, I, I, P]
+    for name, (restype, argtypes) in _PROTOS.items():
+        f = getattr(lib, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -123,8 +266,30 @@ def _dev(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
     return t
 
 
-def _stream(t: torch.Tensor) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+def _bf16_ptr(t, name, contiguous=False):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or (contiguous and not t.is_contiguous()):
+        raise MagnetError(f"{name} must be a {'contiguous ' if contiguous else ''}bf16 GPU tensor")
+    return t.data_ptr()
+
+
+def _stream(t) -> ctypes.c_void_p:
+    """The current HIP stream of a tensor's device (or of a torch.device)."""
+    return ctypes.c_void_p(torch.cuda.current_stream(getattr(t, "device", t)).cuda_stream)
+
+
+def _launch(name: str, on, *args):
+    """Call the entry point `name` with `args` and, as its last argument, the current stream of `on` (a tensor or a
+    torch.device), with that device current; a non-zero return raises MagnetError."""
+    with torch.cuda.device(getattr(on, "device", on)):
+        _check(getattr(load(), name)(*args, _stream(on)), name)
+
+
+def _workspace(name: str, args) -> int:
+    """A `*_workspace` query: the bytes the call described by `args` needs; the library answers -(MAGNET_E_*) on bad arguments."""
+    nbytes = int(getattr(load(), name)(ctypes.byref(args)))
+    if nbytes < 0:
+        _check(-nbytes, name)
+    return nbytes
 
 
 def feat_torch_dtype(feat_dtype: int):
@@ -151,39 +316,30 @@ def pack_features(feat_nchw: torch.Tensor, feat_dtype: int = FEAT_F32, pad: int 
         _dev(out, "out", feat_torch_dtype(feat_dtype))
         if tuple(out.shape) != shape:
             raise MagnetError(f"out has shape {tuple(out.shape)}, expected {shape}")
-    with torch.cuda.device(x.device):
-        _check(load().magnet_pack_features(x.data_ptr(), out.data_ptr(), N, F, h, w, feat_dtype, int(pad), _stream(x)),
-               "magnet_pack_features")
+    _launch("magnet_pack_features", x, x.data_ptr(), out.data_ptr(), N, F, h, w, feat_dtype, int(pad))
+    return out
+
+
+def _pack_gmm(name, channels, gmm_nchw, out):
+    g = _dev(gmm_nchw, "gmm_nchw", torch.float32)
+    N, two, h, w = g.shape
+    if two != 2:
+        raise MagnetError(f"gmm_nchw must be (N,2,h,w), got {tuple(g.shape)}")
+    if out is None:
+        out = torch.empty((N, h + 2, w + 2, channels), dtype=torch.float32, device=g.device)
+    _launch(name, g, g.data_ptr(), _dev(out, "out", torch.float32).data_ptr(), N, h, w)
     return out
 
 
 def pack_gmm(gmm_nchw: torch.Tensor, out: torch.Tensor | None = None):
     """(N,2,h,w) fp32 [mu,sigma] planes -> (N,h+2,w+2,2) interleaved with a zero border."""
-    g = _dev(gmm_nchw, "gmm_nchw", torch.float32)
-    N, two, h, w = g.shape
-    if two != 2:
-        raise MagnetError(f"gmm_nchw must be (N,2,h,w), got {tuple(g.shape)}")
-    if out is None:
-        out = torch.empty((N, h + 2, w + 2, 2), dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        _check(load().magnet_pack_gmm(g.data_ptr(), _dev(out, "out", torch.float32).data_ptr(), N, h, w, _stream(g)),
-               "magnet_pack_gmm")
-    return out
+    return _pack_gmm("magnet_pack_gmm", 2, gmm_nchw, out)
 
 
 def pack_gmm_quad(gmm_nchw: torch.Tensor, out: torch.Tensor | None = None):
     """(N,2,h,w) fp32 [mu,sigma] planes -> (N,h+2,w+2,8): the zero-bordered map per quad origin in quad form
     (MagnetCostVolumeArgs.src_gmm_quad; the production matcher's bilinear (mu, sigma) samples are 3 fma each)."""
-    g = _dev(gmm_nchw, "gmm_nchw", torch.float32)
-    N, two, h, w = g.shape
-    if two != 2:
-        raise MagnetError(f"gmm_nchw must be (N,2,h,w), got {tuple(g.shape)}")
-    if out is None:
-        out = torch.empty((N, h + 2, w + 2, 8), dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        _check(load().magnet_pack_gmm_quad(g.data_ptr(), _dev(out, "out", torch.float32).data_ptr(), N, h, w, _stream(g)),
-               "magnet_pack_gmm_quad")
-    return out
+    return _pack_gmm("magnet_pack_gmm_quad", 8, gmm_nchw, out)
 
 
 def cost_volume_cw(ref_feat_cl, src_feat_pad, src_gmm_pad, poses, is_valid, intM, rays, kappa,
@@ -259,10 +415,7 @@ def cost_volume_cw(ref_feat_cl, src_feat_pad, src_gmm_pad, poses, is_valid, intM
     if out_split is not None:
         # (hi, lo, ld): split-bf16 planes of the conv kernel's zero-bordered channel-last buffer, written in place
         oh, ol, ld = out_split
-        for t in (oh, ol):
-            if not t.is_cuda or t.dtype != torch.bfloat16:
-                raise MagnetError("out_split planes must be bf16 GPU tensors")
-        a.cost_hi, a.cost_lo, a.cost_ld = oh.data_ptr(), ol.data_ptr(), int(ld)
+        a.cost_hi, a.cost_lo, a.cost_ld = _bf16_ptr(oh, "out_split hi plane"), _bf16_ptr(ol, "out_split lo plane"), int(ld)
     elif out is None:
         out = torch.empty((B, D, h, w), dtype=torch.float32, device=r.device)
     else:
@@ -294,8 +447,7 @@ def cost_volume_cw(ref_feat_cl, src_feat_pad, src_gmm_pad, poses, is_valid, intM
     for t in (s, g, po, iv, K, ry):
         if t.device != r.device:
             raise MagnetError("all tensors must be on the same device")
-    with torch.cuda.device(r.device):
-        _check(load().magnet_cost_volume_cw(ctypes.byref(a), _stream(r)), "magnet_cost_volume_cw")
+    _launch("magnet_cost_volume_cw", r, ctypes.byref(a))
     return out
 
 
@@ -333,23 +485,14 @@ def cost_volume_f_backward(ref_feat_cl, src_feat_pad, poses, is_valid, intM, ray
     a.poses, a.is_valid, a.intM, a.rays = po.data_ptr(), iv.data_ptr(), K.data_ptr(), ry.data_ptr()
     grad_ref = torch.empty_like(r)
     grad_src = torch.zeros_like(s)
-    l = load()
-    with torch.cuda.device(r.device):
-        if (int(path) & 0xff) == 0:
-            # gather path: deterministic, no atomics; workspace = projection terms + per-(view, bin, tile) bounding boxes
-            l.magnet_cost_volume_f_backward_workspace.restype = ctypes.c_int64
-            l.magnet_cost_volume_f_backward_workspace.argtypes = [ctypes.c_void_p]
-            l.magnet_cost_volume_f_backward_ws.restype = ctypes.c_int
-            l.magnet_cost_volume_f_backward_ws.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p]
-            nbytes = int(l.magnet_cost_volume_f_backward_workspace(ctypes.byref(a)))
-            if nbytes < 0:
-                raise MagnetError("magnet_cost_volume_f_backward_workspace: " + l.magnet_last_error().decode())
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
-            _check(l.magnet_cost_volume_f_backward_ws(ctypes.byref(a), g.data_ptr(), grad_ref.data_ptr(), grad_src.data_ptr(),
-                                                      ws.data_ptr(), nbytes, _stream(r)), "magnet_cost_volume_f_backward_ws")
-        else:
-            _check(l.magnet_cost_volume_f_backward(ctypes.byref(a), g.data_ptr(), grad_ref.data_ptr(),
-                                                   grad_src.data_ptr(), _stream(r)), "magnet_cost_volume_f_backward")
+    if (int(path) & 0xff) == 0:
+        # gather path: deterministic, no atomics; workspace = projection terms + per-(view, bin, tile) bounding boxes
+        nbytes = _workspace("magnet_cost_volume_f_backward_workspace", a)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
+        _launch("magnet_cost_volume_f_backward_ws", r, ctypes.byref(a), g.data_ptr(), grad_ref.data_ptr(), grad_src.data_ptr(),
+                ws.data_ptr(), nbytes)
+    else:
+        _launch("magnet_cost_volume_f_backward", r, ctypes.byref(a), g.data_ptr(), grad_ref.data_ptr(), grad_src.data_ptr())
     return grad_ref, grad_src
 
 
@@ -361,9 +504,7 @@ def gaussian_update(gnet_out, gmm_in, out=None):
     if out is None:
         out = torch.empty_like(g)
     B, _, h, w = g.shape
-    with torch.cuda.device(g.device):
-        _check(load().magnet_gaussian_update(o.data_ptr(), g.data_ptr(), _dev(out, "out", torch.float32).data_ptr(),
-                                             B, h * w, _stream(g)), "magnet_gaussian_update")
+    _launch("magnet_gaussian_update", g, o.data_ptr(), g.data_ptr(), _dev(out, "out", torch.float32).data_ptr(), B, h * w)
     return out
 
 
@@ -375,66 +516,13 @@ def upsample_depth(depth, up_mask, k: int, out=None):
         raise MagnetError(f"up_mask shape {tuple(m.shape)}, expected {(B, 9 * k * k, h, w)}")
     if out is None:
         out = torch.empty((B, C, k * h, k * w), dtype=torch.float32, device=d.device)
-    with torch.cuda.device(d.device):
-        _check(load().magnet_upsample_depth(d.data_ptr(), m.data_ptr(), _dev(out, "out", torch.float32).data_ptr(),
-                                            B, C, h, w, k, _stream(d)), "magnet_upsample_depth")
+    _launch("magnet_upsample_depth", d, d.data_ptr(), m.data_ptr(), _dev(out, "out", torch.float32).data_ptr(), B, C, h, w, k)
     return out
 
 
 # ---------------------------------------------------------------------------------------------------
 # G-Net / mask-head convolutions on the matrix cores (include/magnet_hip.h: magnet_conv_mfma & friends)
 # ---------------------------------------------------------------------------------------------------
-class MagnetConvArgs(ctypes.Structure):
-    """Mirror of `struct MagnetConvArgs` (include/magnet_hip.h)."""
-    _fields_ = [
-        ("in_hi", ctypes.c_void_p), ("in_lo", ctypes.c_void_p), ("w_hi", ctypes.c_void_p), ("w_lo", ctypes.c_void_p),
-        ("bias", ctypes.c_void_p), ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("out_f32", ctypes.c_void_p),
-        ("rows", ctypes.c_int64),
-        ("cin", ctypes.c_int32), ("cout_pad", ctypes.c_int32), ("taps", ctypes.c_int32), ("wp", ctypes.c_int32),
-        ("relu", ctypes.c_int32), ("out_mode", ctypes.c_int32), ("in_ld", ctypes.c_int32),
-        ("addend", ctypes.c_void_p), ("addend_ld", ctypes.c_int32),
-        ("dil", ctypes.c_int32), ("out_ld", ctypes.c_int32),
-        ("add_hi", ctypes.c_void_p), ("add_lo", ctypes.c_void_p), ("add_ld", ctypes.c_int32),
-        ("border_hp", ctypes.c_int32), ("border_pad", ctypes.c_int32), ("repad", ctypes.c_int32),
-        ("tail_w_hi", ctypes.c_void_p), ("tail_w_lo", ctypes.c_void_p), ("tail_bias", ctypes.c_void_p),
-        ("tail_cout_pad", ctypes.c_int32),
-        ("up_depth", ctypes.c_void_p), ("up_out", ctypes.c_void_p),
-        ("up_npred", ctypes.c_int32), ("up_B", ctypes.c_int32), ("up_h", ctypes.c_int32), ("up_w", ctypes.c_int32),
-        ("gu_in", ctypes.c_void_p), ("gu_out", ctypes.c_void_p),
-        ("in_sc", ctypes.c_void_p), ("w_sc", ctypes.c_void_p), ("sc_rows", ctypes.c_int64),
-    ]
-
-
-API_SYMBOLS = API_SYMBOLS + ("magnet_conv_mfma", "magnet_pack_split", "magnet_pack_mx", "magnet_gaussian_update_cl",
-                             "magnet_upsample_depth_cl", "magnet_upsample_depth_cl_n")
-
-
-def _conv_protos(lib):
-    if getattr(lib, "_conv_protos_done", False):
-        return lib
-    I, P = ctypes.c_int32, ctypes.c_void_p
-    lib.magnet_conv_mfma.restype = ctypes.c_int
-    lib.magnet_conv_mfma.argtypes = [ctypes.POINTER(MagnetConvArgs), P]
-    lib.magnet_pack_split.restype = ctypes.c_int
-    lib.magnet_pack_split.argtypes = [P, P, P, I, I, I, I, I, I, ctypes.c_int64, P]
-    lib.magnet_pack_mx.restype = ctypes.c_int
-    lib.magnet_pack_mx.argtypes = [P, P, P, P, I, I, I, I, I, I, ctypes.c_int64, ctypes.c_int64, P]
-    lib.magnet_gaussian_update_cl.restype = ctypes.c_int
-    lib.magnet_gaussian_update_cl.argtypes = [P, I, P, P, I, I, I, P]
-    lib.magnet_upsample_depth_cl.restype = ctypes.c_int
-    lib.magnet_upsample_depth_cl.argtypes = [P, P, I, P, I, I, I, P]
-    lib.magnet_upsample_depth_cl_n.restype = ctypes.c_int
-    lib.magnet_upsample_depth_cl_n.argtypes = [P, P, I, P, I, I, I, I, P]
-    lib._conv_protos_done = True
-    return lib
-
-
-def _bf16_ptr(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16:
-        raise MagnetError(f"{name} must be a bf16 GPU tensor")
-    return t.data_ptr()
-
-
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
               mx=None, leaky=None, tiling=None):
@@ -451,7 +539,6 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     leaky = slope: LeakyReLU(slope) after bias instead of ReLU (magnet_conv_mfma_ex; relu must be False, no tail).
     tiling = TILING_* flags (magnet_conv_mfma_ex; tests and A/B runs).  Returns the number of row tiles launched when the launch went
     through magnet_conv_mfma_ex, else None."""
-    lib = _conv_protos(load())
     a = MagnetConvArgs()
     if mx is not None:
         # mx = (in_sc, w_sc, sc_rows): the fp16 + block-scaled e4m3 operand format (include/magnet_hip.h v302): in_hi / w_hi are fp16
@@ -468,8 +555,7 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.in_sc, a.w_sc, a.sc_rows = isc.data_ptr(), wsc.data_ptr(), int(sc_rows)
     else:
         for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo")):
-            if not t.is_cuda or t.dtype != torch.bfloat16:
-                raise MagnetError(f"conv_mfma: {n} must be a bf16 GPU tensor")
+            _bf16_ptr(t, f"conv_mfma: {n}")
     a.in_hi, a.in_lo, a.w_hi, a.w_lo = in_hi.data_ptr(), in_lo.data_ptr(), w_hi.data_ptr(), w_lo.data_ptr()
     a.bias = _dev(bias, "bias", torch.float32).data_ptr()
     a.rows, a.cin, a.cout_pad, a.taps, a.wp = int(rows), int(cin), int(w_hi.shape[1]), int(taps), int(wp)
@@ -506,36 +592,32 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_hi = 2, _bf16_ptr(out_bf16, "out_bf16")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
-    with torch.cuda.device(in_hi.device):
-        if leaky is None and tiling is None:
-            _check(lib.magnet_conv_mfma(ctypes.byref(a), _stream(in_hi)), "magnet_conv_mfma")
-            return None
-        tiles = ctypes.c_int64(0)
-        x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
-                             tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
-        _check(_dnet_protos(lib).magnet_conv_mfma_ex(ctypes.byref(x), _stream(in_hi)), "magnet_conv_mfma_ex")
-        return tiles.value
+    if leaky is None and tiling is None:
+        _launch("magnet_conv_mfma", in_hi, ctypes.byref(a))
+        return None
+    tiles = ctypes.c_int64(0)
+    x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
+                         tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
+    _launch("magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
+    return tiles.value
 
 
 def pack_split(x_nchw, out_hi, out_lo, ctot, c_off):
     """fp32 (N,C,h,w) (dense, or a leading-channel slice of a wider NCHW tensor) -> interior of the split-bf16
     padded channel-last buffer (N,h+2,w+2,ctot), channels [c_off, c_off+C)."""
-    lib = _conv_protos(load())
     if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
         raise MagnetError("pack_split: input must be a float32 GPU tensor")
     N, C, h, w = x_nchw.shape
     if x_nchw.stride()[1:] != (h * w, w, 1):
         raise MagnetError(f"pack_split: unsupported input strides {x_nchw.stride()}")
-    with torch.cuda.device(x_nchw.device):
-        _check(lib.magnet_pack_split(x_nchw.data_ptr(), out_hi.data_ptr(), out_lo.data_ptr(), N, C, h, w, int(ctot),
-                                     int(c_off), int(x_nchw.stride(0)) if N > 1 else 0, _stream(x_nchw)), "magnet_pack_split")
+    _launch("magnet_pack_split", x_nchw, x_nchw.data_ptr(), out_hi.data_ptr(), out_lo.data_ptr(), N, C, h, w, int(ctot), int(c_off),
+            int(x_nchw.stride(0)) if N > 1 else 0)
 
 
 def pack_mx(x_nchw, out_f16, out_qr, out_sc, ctot, c_off, sc_rows):
     """fp32 (N,C,h,w) -> channels [c_off, c_off+C) of the interior of a padded channel-last buffer (N,h+2,w+2,ctot) in the fp16 + e4m3
     operand format of conv_mfma(mx=...): out_f16 fp16 plane, out_qr 2-byte container plane (hi | lo e4m3 bytes per 32-channel block),
     out_sc int32 [ctot / 32][sc_rows] E8M0 pairs."""
-    lib = _conv_protos(load())
     if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
         raise MagnetError("pack_mx: input must be a float32 GPU tensor")
     N, C, h, w = x_nchw.shape
@@ -549,41 +631,34 @@ def pack_mx(x_nchw, out_f16, out_qr, out_sc, ctot, c_off, sc_rows):
             raise MagnetError(f"pack_mx: {name} must be a contiguous tensor on {x_nchw.device} with at least {need} elements")
     if int(ctot) % 32 or int(c_off) % 32 or int(c_off) + C > int(ctot) or int(sc_rows) < rows:
         raise MagnetError("pack_mx: ctot / c_off must be multiples of 32 with c_off + C <= ctot, and sc_rows >= N (h+2) (w+2)")
-    with torch.cuda.device(x_nchw.device):
-        _check(lib.magnet_pack_mx(x_nchw.data_ptr(), out_f16.data_ptr(), out_qr.data_ptr(), out_sc.data_ptr(), N, C, h, w, int(ctot),
-                                  int(c_off), int(sc_rows), int(x_nchw.stride(0)) if N > 1 else 0, _stream(x_nchw)), "magnet_pack_mx")
+    _launch("magnet_pack_mx", x_nchw, x_nchw.data_ptr(), out_f16.data_ptr(), out_qr.data_ptr(), out_sc.data_ptr(), N, C, h, w, int(ctot),
+            int(c_off), int(sc_rows), int(x_nchw.stride(0)) if N > 1 else 0)
 
 
 def gaussian_update_cl(gnet_out_pad, ld, gmm_in, h, w, out=None):
-    lib = _conv_protos(load())
     g = _dev(gmm_in, "gmm_in", torch.float32)
     if out is None:
         out = torch.empty_like(g)
-    with torch.cuda.device(g.device):
-        _check(lib.magnet_gaussian_update_cl(_dev(gnet_out_pad, "gnet_out_pad", torch.float32).data_ptr(), int(ld),
-                                             g.data_ptr(), out.data_ptr(), g.shape[0], h, w, _stream(g)),
-               "magnet_gaussian_update_cl")
+    _launch("magnet_gaussian_update_cl", g, _dev(gnet_out_pad, "gnet_out_pad", torch.float32).data_ptr(), int(ld), g.data_ptr(),
+            out.data_ptr(), g.shape[0], h, w)
     return out
 
 
 def upsample_depth_cl(depth, mask_pad, ld, out=None):
-    lib = _conv_protos(load())
     d = _dev(depth, "depth", torch.float32)
     B, C, h, w = d.shape
     if C != 2:
         raise MagnetError("upsample_depth_cl: depth must be (B,2,h,w)")
     if out is None:
         out = torch.empty((B, 2, 4 * h, 4 * w), dtype=torch.float32, device=d.device)
-    with torch.cuda.device(d.device):
-        _check(lib.magnet_upsample_depth_cl(d.data_ptr(), _dev(mask_pad, "mask_pad", torch.float32).data_ptr(), int(ld),
-                                            out.data_ptr(), B, h, w, _stream(d)), "magnet_upsample_depth_cl")
+    _launch("magnet_upsample_depth_cl", d, d.data_ptr(), _dev(mask_pad, "mask_pad", torch.float32).data_ptr(), int(ld), out.data_ptr(),
+            B, h, w)
     return out
 
 
 def upsample_depth_cl_n(depths, mask_pad, ld):
     """Every prediction of the refinement loop upsampled with the same mask in ONE launch (models/MAGNET.py:173): `depths` is a
     list of (B,2,h,w) tensors; returns the list of (B,2,4h,4w) outputs (contiguous slices of one buffer)."""
-    lib = _conv_protos(load())
     if len(depths) == 1:
         return [upsample_depth_cl(depths[0], mask_pad, ld)]
     d = torch.stack([_dev(x, "depth", torch.float32) for x in depths])
@@ -591,192 +666,75 @@ def upsample_depth_cl_n(depths, mask_pad, ld):
     if C != 2:
         raise MagnetError("upsample_depth_cl_n: depths must be (B,2,h,w)")
     out = torch.empty((n, B, 2, 4 * h, 4 * w), dtype=torch.float32, device=d.device)
-    with torch.cuda.device(d.device):
-        _check(lib.magnet_upsample_depth_cl_n(d.data_ptr(), _dev(mask_pad, "mask_pad", torch.float32).data_ptr(), int(ld),
-                                              out.data_ptr(), n, B, h, w, _stream(d)), "magnet_upsample_depth_cl_n")
+    _launch("magnet_upsample_depth_cl_n", d, d.data_ptr(), _dev(mask_pad, "mask_pad", torch.float32).data_ptr(), int(ld), out.data_ptr(),
+            n, B, h, w)
     return [out[i] for i in range(n)]
-
-
-API_SYMBOLS = API_SYMBOLS + ("magnet_conv1x1_chain",)
 
 
 def conv1x1_chain(in_hi, in_lo, w_hi, w_lo, bias, out, rows, cout_pad):
     """relu(1x1 128->128), relu(1x1 128->128), 1x1 128->cout_pad in one launch (see include/magnet_hip.h)."""
-    lib = _conv_protos(load())
-    if not getattr(lib, "_chain_proto", False):
-        P = ctypes.c_void_p
-        lib.magnet_conv1x1_chain.restype = ctypes.c_int
-        lib.magnet_conv1x1_chain.argtypes = [P, P, P, P, P, P, ctypes.c_int64, ctypes.c_int32, P]
-        lib._chain_proto = True
-    for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo")):
-        if not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous():
-            raise MagnetError(f"conv1x1_chain: {n} must be a contiguous bf16 GPU tensor")
-    with torch.cuda.device(in_hi.device):
-        _check(lib.magnet_conv1x1_chain(in_hi.data_ptr(), in_lo.data_ptr(), w_hi.data_ptr(), w_lo.data_ptr(),
-                                        _dev(bias, "bias", torch.float32).data_ptr(),
-                                        _dev(out, "out", torch.float32).data_ptr(), int(rows), int(cout_pad),
-                                        _stream(in_hi)), "magnet_conv1x1_chain")
-
-
-API_SYMBOLS = API_SYMBOLS + ("magnet_depth_metrics", "magnet_depth_metrics_crop", "magnet_make_rays", "magnet_relative_poses")
+    planes = [_bf16_ptr(t, f"conv1x1_chain: {n}", contiguous=True)
+              for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo"))]
+    _launch("magnet_conv1x1_chain", in_hi, *planes, _dev(bias, "bias", torch.float32).data_ptr(),
+            _dev(out, "out", torch.float32).data_ptr(), int(rows), int(cout_pad))
 
 
 def make_rays(ray_params, h: int, w: int):
     """(B,8) float64 GPU {fx, fy, cx, cy, sx, sy, left, top} -> unit_ray_array_2D (B,3,h*w) fp32 on the device, bit-identical to
     the loaders' host table (dataloader_scannet.py:139-147, dataloader_kitti.py:113-118)."""
-    lib = load()
     prm = _dev(ray_params, "ray_params", torch.float64)
     if prm.dim() != 2 or prm.shape[1] != 8:
         raise MagnetError(f"ray_params shape {tuple(prm.shape)}, expected (B, 8)")
     B = prm.shape[0]
     out = torch.empty((B, 3, h * w), dtype=torch.float32, device=prm.device)
-    lib.magnet_make_rays.restype = ctypes.c_int
-    lib.magnet_make_rays.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
-    with torch.cuda.device(prm.device):
-        _check(lib.magnet_make_rays(prm.data_ptr(), out.data_ptr(), B, int(h), int(w), _stream(prm)), "magnet_make_rays")
+    _launch("magnet_make_rays", prm, prm.data_ptr(), out.data_ptr(), B, int(h), int(w))
     return out
 
 
 def relative_poses(ext_ref, ext_nghbr):
     """utils.data_preprocess on the device (utils/utils.py:72-98): float64 GPU extrinsics ext_ref (B,4,4), ext_nghbr (B,V,4,4) ->
     (poses (B,V,4,4) fp32, is_valid (B,V) int32), both on the device, ready for the matcher."""
-    lib = load()
     er = _dev(ext_ref, "ext_ref", torch.float64); en = _dev(ext_nghbr, "ext_nghbr", torch.float64)
     if er.dim() != 3 or tuple(er.shape[1:]) != (4, 4) or en.dim() != 4 or en.shape[0] != er.shape[0] or tuple(en.shape[2:]) != (4, 4):
         raise MagnetError(f"relative_poses: shapes {tuple(er.shape)} {tuple(en.shape)}, expected (B,4,4) and (B,V,4,4)")
     B, V = en.shape[:2]
     poses = torch.empty((B, V, 4, 4), dtype=torch.float32, device=er.device)
     valid = torch.empty((B, V), dtype=torch.int32, device=er.device)
-    lib.magnet_relative_poses.restype = ctypes.c_int
-    lib.magnet_relative_poses.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
-    with torch.cuda.device(er.device):
-        _check(lib.magnet_relative_poses(er.data_ptr(), en.data_ptr(), poses.data_ptr(), valid.data_ptr(), B, V, _stream(er)),
-               "magnet_relative_poses")
+    _launch("magnet_relative_poses", er, er.data_ptr(), en.data_ptr(), poses.data_ptr(), valid.data_ptr(), B, V)
     return poses, valid
 
 
 # ---- F-Net non-GEMM layers (row N3) -------------------------------------------------------------------------------
-API_SYMBOLS = API_SYMBOLS + ("magnet_fnet_stem", "magnet_space_to_depth", "magnet_avgpool_cl", "magnet_upsample_bilinear_cl")
-
-
-def _fnet_protos(lib):
-    if getattr(lib, "_fnet_protos_done", False):
-        return lib
-    I, P = ctypes.c_int32, ctypes.c_void_p
-    lib.magnet_fnet_stem.restype = ctypes.c_int
-    lib.magnet_fnet_stem.argtypes = [P, P, P, P, P, I, I, I, P]
-    lib.magnet_space_to_depth.restype = ctypes.c_int
-    lib.magnet_space_to_depth.argtypes = [P, P, P, P, I, I, I, I, I, P]
-    lib.magnet_avgpool_cl.restype = ctypes.c_int
-    lib.magnet_avgpool_cl.argtypes = [P, P, I, I, I, I, I, I, I, P, P, P]
-    lib.magnet_upsample_bilinear_cl.restype = ctypes.c_int
-    lib.magnet_upsample_bilinear_cl.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, P]
-    lib._fnet_protos_done = True
-    return lib
-
-
 def fnet_stem(img, wgt, bias, out_hi, out_lo):
     """(N,3,H,W) fp32 image -> 32-channel split planes (N,H2+2,W2+2,32): 3x3/s2 conv + folded BN + ReLU (F_psmnet.py:40)."""
-    lib = _fnet_protos(load())
     x = _dev(img, "img", torch.float32)
     N, C, H, W = x.shape
     if C != 3:
         raise MagnetError(f"fnet_stem: expected 3 input channels, got {C}")
-    with torch.cuda.device(x.device):
-        _check(lib.magnet_fnet_stem(x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(),
-                                    _dev(bias, "bias", torch.float32).data_ptr(), _bf16_ptr(out_hi, "out_hi"),
-                                    _bf16_ptr(out_lo, "out_lo"), N, H, W, _stream(x)), "magnet_fnet_stem")
+    _launch("magnet_fnet_stem", x, x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(), _dev(bias, "bias", torch.float32).data_ptr(),
+            _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo"), N, H, W)
 
 
 def space_to_depth(in_hi, in_lo, out_hi, out_lo, N, C, H2, W2, opad):
-    lib = _fnet_protos(load())
-    with torch.cuda.device(in_hi.device):
-        _check(lib.magnet_space_to_depth(_bf16_ptr(in_hi, "in_hi"), _bf16_ptr(in_lo, "in_lo"), _bf16_ptr(out_hi, "out_hi"),
-                                         _bf16_ptr(out_lo, "out_lo"), N, C, H2, W2, opad, _stream(in_hi)), "magnet_space_to_depth")
+    _launch("magnet_space_to_depth", in_hi, _bf16_ptr(in_hi, "in_hi"), _bf16_ptr(in_lo, "in_lo"), _bf16_ptr(out_hi, "out_hi"),
+            _bf16_ptr(out_lo, "out_lo"), N, C, H2, W2, opad)
 
 
 def avgpool_cl(in_hi, in_lo, ld, N, h, w, pad, k, C, out_hi, out_lo):
-    lib = _fnet_protos(load())
-    with torch.cuda.device(in_hi.device):
-        _check(lib.magnet_avgpool_cl(_bf16_ptr(in_hi, "in_hi"), _bf16_ptr(in_lo, "in_lo"), ld, N, h, w, pad, k, C,
-                                     _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo"), _stream(in_hi)), "magnet_avgpool_cl")
+    _launch("magnet_avgpool_cl", in_hi, _bf16_ptr(in_hi, "in_hi"), _bf16_ptr(in_lo, "in_lo"), ld, N, h, w, pad, k, C,
+            _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo"))
 
 
 def upsample_bilinear_cl(x, in_ld, ph, pw, C, out_hi, out_lo, out_ld, N, h, w, pad):
-    lib = _fnet_protos(load())
-    with torch.cuda.device(x.device):
-        _check(lib.magnet_upsample_bilinear_cl(_dev(x, "x", torch.float32).data_ptr(), in_ld, ph, pw, C, _bf16_ptr(out_hi, "out_hi"),
-                                               _bf16_ptr(out_lo, "out_lo"), out_ld, N, h, w, pad, _stream(x)),
-               "magnet_upsample_bilinear_cl")
+    _launch("magnet_upsample_bilinear_cl", x, _dev(x, "x", torch.float32).data_ptr(), in_ld, ph, pw, C, _bf16_ptr(out_hi, "out_hi"),
+            _bf16_ptr(out_lo, "out_lo"), out_ld, N, h, w, pad)
 
 
 # ---- training step of g_net / mask_head (include/magnet_hip.h: magnet_nll_loss_*, magnet_upsample_depth_backward,
 # ---- magnet_head_dgrad, magnet_wgrad; csrc/train_bwd.hip) -----------------------------------------------------------
-API_SYMBOLS = API_SYMBOLS + ("magnet_nll_loss_forward", "magnet_nll_loss_backward", "magnet_upsample_depth_backward",
-                             "magnet_head_dgrad", "magnet_wgrad_workspace", "magnet_wgrad")
-NLL_BLOCKS, NLL_MAX_ITER = 256, 16
-
-
-class MagnetNllArgs(ctypes.Structure):
-    """Mirror of `struct MagnetNllArgs` (include/magnet_hip.h)."""
-    _fields_ = [("preds", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("sums", ctypes.c_void_p),
-                ("loss", ctypes.c_void_p), ("work", ctypes.c_void_p), ("grad_loss", ctypes.c_void_p), ("grad_preds", ctypes.c_void_p),
-                ("gamma", ctypes.c_double),
-                ("n_iter", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
-
-
-class MagnetUpsampleBwdArgs(ctypes.Structure):
-    """Mirror of `struct MagnetUpsampleBwdArgs` (include/magnet_hip.h)."""
-    _fields_ = [("grad_up", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("mask", ctypes.c_void_p),
-                ("grad_depth", ctypes.c_void_p), ("grad_mask", ctypes.c_void_p), ("work", ctypes.c_void_p),
-                ("mask_sb", ctypes.c_int64), ("mask_sc", ctypes.c_int64), ("mask_sy", ctypes.c_int64), ("mask_sx", ctypes.c_int64),
-                ("gm_sb", ctypes.c_int64), ("gm_sc", ctypes.c_int64), ("gm_sy", ctypes.c_int64), ("gm_sx", ctypes.c_int64),
-                ("n_pred", ctypes.c_int32), ("B", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("k", ctypes.c_int32)]
-
-
-class MagnetHeadDgradArgs(ctypes.Structure):
-    """Mirror of `struct MagnetHeadDgradArgs` (include/magnet_hip.h)."""
-    _fields_ = [("dout", ctypes.c_void_p), ("k0", ctypes.c_int32),
-                ("wt_hi", ctypes.c_void_p), ("wt_lo", ctypes.c_void_p),
-                ("h3_hi", ctypes.c_void_p), ("h2_hi", ctypes.c_void_p), ("h1_hi", ctypes.c_void_p),
-                ("dout_hi", ctypes.c_void_p), ("dout_lo", ctypes.c_void_p),
-                ("dh3_hi", ctypes.c_void_p), ("dh3_lo", ctypes.c_void_p), ("dh2_hi", ctypes.c_void_p), ("dh2_lo", ctypes.c_void_p),
-                ("dh1_hi", ctypes.c_void_p), ("dh1_lo", ctypes.c_void_p),
-                ("acc", ctypes.c_void_p), ("acc_hi", ctypes.c_void_p), ("acc_lo", ctypes.c_void_p), ("acc_mode", ctypes.c_int32),
-                ("B", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("rows", ctypes.c_int64),
-                ("grad_gmm", ctypes.c_void_p), ("gnet_out", ctypes.c_void_p), ("gmm_in", ctypes.c_void_p), ("gnet_ld", ctypes.c_int32)]
-
-
-class MagnetWgradArgs(ctypes.Structure):
-    """Mirror of `struct MagnetWgradArgs` (include/magnet_hip.h)."""
-    _fields_ = [("dy_hi", ctypes.c_void_p), ("dy_lo", ctypes.c_void_p), ("x_hi", ctypes.c_void_p), ("x_lo", ctypes.c_void_p),
-                ("dy_ld", ctypes.c_int64), ("x_ld", ctypes.c_int64), ("rows", ctypes.c_int64),
-                ("cout", ctypes.c_int32), ("cin", ctypes.c_int32), ("taps", ctypes.c_int32), ("wp", ctypes.c_int32),
-                ("grad_w", ctypes.c_void_p), ("grad_b", ctypes.c_void_p),
-                ("cout_valid", ctypes.c_int32), ("cin_valid", ctypes.c_int32), ("cin_total", ctypes.c_int32), ("cin_dst", ctypes.c_int32),
-                ("accumulate", ctypes.c_int32), ("work", ctypes.c_void_p)]
-
-
-def _train_protos(lib):
-    if getattr(lib, "_train_protos_done", False):
-        return lib
-    P = ctypes.c_void_p
-    for name, st in (("magnet_nll_loss_forward", MagnetNllArgs), ("magnet_nll_loss_backward", MagnetNllArgs),
-                     ("magnet_upsample_depth_backward", MagnetUpsampleBwdArgs), ("magnet_head_dgrad", MagnetHeadDgradArgs),
-                     ("magnet_wgrad", MagnetWgradArgs)):
-        f = getattr(lib, name)
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.POINTER(st), P]
-    lib.magnet_wgrad_workspace.restype = ctypes.c_int64
-    lib.magnet_wgrad_workspace.argtypes = [ctypes.POINTER(MagnetWgradArgs)]
-    lib._train_protos_done = True
-    return lib
-
-
 def nll_loss_forward(preds, gt, mask, gamma: float):
     """preds (I,B,2,H,W) fp32, gt (B,H,W) fp32, mask (B,H,W) bool -> (loss 0-d fp32, sums (1+I) float64: count, per-iteration
     NLL sums).  Deterministic two-stage reduction on the device."""
-    lib = _train_protos(load())
     p = _dev(preds, "preds", torch.float32)
     g = _dev(gt, "gt", torch.float32)
     m = _dev(mask, "mask", torch.bool)
@@ -790,14 +748,12 @@ def nll_loss_forward(preds, gt, mask, gamma: float):
     loss = torch.empty((), dtype=torch.float32, device=p.device)
     a = MagnetNllArgs(preds=p.data_ptr(), gt=g.data_ptr(), mask=m.data_ptr(), sums=sums.data_ptr(), loss=loss.data_ptr(),
                       work=work.data_ptr(), gamma=float(gamma), n_iter=I, B=B, H=H, W=W)
-    with torch.cuda.device(p.device):
-        _check(lib.magnet_nll_loss_forward(ctypes.byref(a), _stream(p)), "magnet_nll_loss_forward")
+    _launch("magnet_nll_loss_forward", p, ctypes.byref(a))
     return loss, sums
 
 
 def nll_loss_backward(preds, gt, mask, sums, grad_loss, gamma: float):
     """d loss / d preds (I,B,2,H,W), scaled by the device scalar grad_loss (read on the device: no host sync)."""
-    lib = _train_protos(load())
     p = _dev(preds, "preds", torch.float32)
     gl = _dev(grad_loss.reshape(()), "grad_loss", torch.float32)
     I, B, _, H, W = p.shape
@@ -805,8 +761,7 @@ def nll_loss_backward(preds, gt, mask, sums, grad_loss, gamma: float):
     a = MagnetNllArgs(preds=p.data_ptr(), gt=_dev(gt, "gt", torch.float32).data_ptr(), mask=_dev(mask, "mask", torch.bool).data_ptr(),
                       sums=_dev(sums, "sums", torch.float64).data_ptr(), grad_loss=gl.data_ptr(), grad_preds=out.data_ptr(),
                       gamma=float(gamma), n_iter=I, B=B, H=H, W=W)
-    with torch.cuda.device(p.device):
-        _check(lib.magnet_nll_loss_backward(ctypes.byref(a), _stream(p)), "magnet_nll_loss_backward")
+    _launch("magnet_nll_loss_backward", p, ctypes.byref(a))
     return out
 
 
@@ -816,7 +771,6 @@ def upsample_depth_backward(grad_up, depths, mask, k: int, mask_layout=None, gra
     (layouts None: grad_mask is returned in that layout), or contiguous fp32 storage addressed by mask_layout = (element offset,
     sb, sc, sy, sx), with a preallocated contiguous grad_mask addressed by grad_mask_layout (the padded channel-last buffers of the
     HIP training path)."""
-    lib = _train_protos(load())
     gu = _dev(grad_up, "grad_up", torch.float32)
     d = _dev(depths, "depths", torch.float32)
     n, B, C, h, w = d.shape
@@ -838,16 +792,25 @@ def upsample_depth_backward(grad_up, depths, mask, k: int, mask_layout=None, gra
     a = MagnetUpsampleBwdArgs(grad_up=gu.data_ptr(), depth=d.data_ptr(), mask=m.data_ptr() + 4 * mo, grad_depth=gd.data_ptr(),
                               grad_mask=gm.data_ptr() + 4 * go, work=work.data_ptr(), mask_sb=msb, mask_sc=msc, mask_sy=msy,
                               mask_sx=msx, gm_sb=gsb, gm_sc=gsc, gm_sy=gsy, gm_sx=gsx, n_pred=n, B=B, h=h, w=w, k=int(k))
-    with torch.cuda.device(d.device):
-        _check(lib.magnet_upsample_depth_backward(ctypes.byref(a), _stream(d)), "magnet_upsample_depth_backward")
+    _launch("magnet_upsample_depth_backward", d, ctypes.byref(a))
     return gd, grad_mask
 
 
 def head_dgrad(a: "MagnetHeadDgradArgs", device):
-    lib = _train_protos(load())
-    with torch.cuda.device(device):
-        _check(lib.magnet_head_dgrad(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
-               "magnet_head_dgrad")
+    _launch("magnet_head_dgrad", device, ctypes.byref(a))
+
+
+def _wgrad_args(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst, cout_valid, cin_valid, grad_b=None,
+                accumulate=False):
+    """MagnetWgradArgs of wgrad / wgrad_ex, without the workspace."""
+    planes = [_bf16_ptr(t, n) for t, n in ((dy_hi, "dy_hi"), (dy_lo, "dy_lo"), (x_hi, "x_hi"), (x_lo, "x_lo"))]
+    gw = _dev(grad_w, "grad_w", torch.float32)
+    return MagnetWgradArgs(dy_hi=planes[0], dy_lo=planes[1], x_hi=planes[2], x_lo=planes[3],
+                           dy_ld=dy_hi.stride(0), x_ld=x_hi.stride(0), rows=int(rows), cout=int(cout), cin=int(cin), taps=int(taps),
+                           wp=int(wp), grad_w=gw.data_ptr(),
+                           grad_b=_dev(grad_b, "grad_b", torch.float32).data_ptr() if grad_b is not None else None,
+                           cout_valid=int(cout if cout_valid is None else cout_valid), cin_valid=int(cin if cin_valid is None else cin_valid),
+                           cin_total=gw.shape[1], cin_dst=int(cin_dst), accumulate=int(bool(accumulate)))
 
 
 def wgrad(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst=0, cout_valid=None, cin_valid=None, grad_b=None,
@@ -855,62 +818,16 @@ def wgrad(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst=0
     """Weight (and bias) gradient of one convolution layer on the matrix cores.  dy_* (rows, dy_ld) and x_* (rows, x_ld) split
     bf16 planes of the zero-bordered grid (x_* may be a channel-offset view of a wider buffer); grad_w: the layer's
     nn.Conv2d-shaped fp32 gradient (Cout, Cin_total, kh, kw), written at input channels [cin_dst, cin_dst + cin_valid)."""
-    lib = _train_protos(load())
-    for t, nme in ((dy_hi, "dy_hi"), (dy_lo, "dy_lo"), (x_hi, "x_hi"), (x_lo, "x_lo")):
-        _bf16_ptr(t, nme)
-    gw = _dev(grad_w, "grad_w", torch.float32)
-    if grad_b is not None:
-        _dev(grad_b, "grad_b", torch.float32)
-    a = MagnetWgradArgs(dy_hi=dy_hi.data_ptr(), dy_lo=dy_lo.data_ptr(), x_hi=x_hi.data_ptr(), x_lo=x_lo.data_ptr(),
-                        dy_ld=dy_hi.stride(0), x_ld=x_hi.stride(0), rows=int(rows), cout=int(cout), cin=int(cin), taps=int(taps),
-                        wp=int(wp), grad_w=gw.data_ptr(), grad_b=grad_b.data_ptr() if grad_b is not None else None,
-                        cout_valid=int(cout if cout_valid is None else cout_valid), cin_valid=int(cin if cin_valid is None else cin_valid),
-                        cin_total=gw.shape[1], cin_dst=int(cin_dst), accumulate=int(bool(accumulate)))
-    nbytes = lib.magnet_wgrad_workspace(ctypes.byref(a))
-    if nbytes < 0:
-        _check(int(-nbytes), "magnet_wgrad_workspace")
-    work = torch.empty(max(int(nbytes) // 4, 4), dtype=torch.float32, device=gw.device)
+    a = _wgrad_args(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst, cout_valid, cin_valid, grad_b, accumulate)
+    work = torch.empty(max(_workspace("magnet_wgrad_workspace", a) // 4, 4), dtype=torch.float32, device=grad_w.device)
     a.work = work.data_ptr()
-    with torch.cuda.device(gw.device):
-        _check(lib.magnet_wgrad(ctypes.byref(a), _stream(gw)), "magnet_wgrad")
+    _launch("magnet_wgrad", grad_w, ctypes.byref(a))
 
 
 # ---- F-Net forward in training mode (include/magnet_hip.h: magnet_fnet_stem_raw, magnet_bn_train_*; csrc/train_fnet_fwd.hip) ----
-API_SYMBOLS = API_SYMBOLS + ("magnet_fnet_stem_raw", "magnet_bn_train_stats", "magnet_bn_train_apply")
-BN_BLOCKS = 256
-
-
-class MagnetBnTrainArgs(ctypes.Structure):
-    """Mirror of `struct MagnetBnTrainArgs` (include/magnet_hip.h)."""
-    _fields_ = [("x", ctypes.c_void_p), ("x_ld", ctypes.c_int64),
-                ("N", ctypes.c_int32), ("hp", ctypes.c_int32), ("wp", ctypes.c_int32), ("pad", ctypes.c_int32), ("C", ctypes.c_int32),
-                ("work", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p),
-                ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p), ("num_batches_tracked", ctypes.c_void_p),
-                ("eps", ctypes.c_double), ("momentum", ctypes.c_double),
-                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
-                ("res_hi", ctypes.c_void_p), ("res_lo", ctypes.c_void_p), ("res_ld", ctypes.c_int64),
-                ("relu", ctypes.c_int32),
-                ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("out_f32", ctypes.c_void_p), ("out_ld", ctypes.c_int64)]
-
-
-def _bn_train_protos(lib):
-    if getattr(lib, "_bn_train_protos_done", False):
-        return lib
-    I, P = ctypes.c_int32, ctypes.c_void_p
-    lib.magnet_fnet_stem_raw.restype = ctypes.c_int
-    lib.magnet_fnet_stem_raw.argtypes = [P, P, P, I, I, I, P]
-    for name in ("magnet_bn_train_stats", "magnet_bn_train_apply"):
-        f = getattr(lib, name)
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.POINTER(MagnetBnTrainArgs), P]
-    lib._bn_train_protos_done = True
-    return lib
-
-
 def fnet_stem_raw(img, wgt, out):
     """(N,3,H,W) fp32 image, wgt (32, 27) fp32 -> the interior of `out`, the fp32 (N*(H2+2)*(W2+2), 32) channel-last grid:
     firstconv.0 without BatchNorm and ReLU."""
-    lib = _bn_train_protos(load())
     x = _dev(img, "img", torch.float32)
     N, C, H, W = x.shape
     if C != 3:
@@ -919,9 +836,7 @@ def fnet_stem_raw(img, wgt, out):
     o = _dev(out, "out", torch.float32)
     if o.numel() < N * (H2 + 2) * (W2 + 2) * 32:
         raise MagnetError("fnet_stem_raw: output grid too small")
-    with torch.cuda.device(x.device):
-        _check(lib.magnet_fnet_stem_raw(x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(), o.data_ptr(), N, H, W, _stream(x)),
-               "magnet_fnet_stem_raw")
+    _launch("magnet_fnet_stem_raw", x, x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(), o.data_ptr(), N, H, W)
 
 
 def bn_train(x, grid, mean, invstd, work, gamma, beta, eps, momentum, running_mean=None, running_var=None, num_batches_tracked=None,
@@ -929,7 +844,6 @@ def bn_train(x, grid, mean, invstd, work, gamma, beta, eps, momentum, running_me
     """One BatchNorm2d in training mode (magnet_bn_train_stats, then magnet_bn_train_apply).  x: fp32 (rows, x_ld) grid
     (possibly a channel-offset view), grid = (N, hp, wp, pad, C); res = (hi, lo) split residual views; out = (hi, lo) split
     planes (channel-slice views allowed) or out_f32 an fp32 (rows, ld) tensor.  momentum None: cumulative average."""
-    lib = _bn_train_protos(load())
     N, hp, wp, pad, C = (int(v) for v in grid)
     if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] < C:
         raise MagnetError("bn_train: x must be a (rows, >= C) float32 GPU tensor with unit channel stride")
@@ -956,95 +870,28 @@ def bn_train(x, grid, mean, invstd, work, gamma, beta, eps, momentum, running_me
     if x.shape[0] < rows or (out_f32 is not None and out_f32.shape[0] < rows) or (out is not None and out[0].shape[0] < rows) or \
             (res is not None and res[0].shape[0] < rows):
         raise MagnetError(f"bn_train: a buffer holds fewer than the grid's {rows} rows")
-    with torch.cuda.device(x.device):
-        if stats:
-            _check(lib.magnet_bn_train_stats(ctypes.byref(a), _stream(x)), "magnet_bn_train_stats")
-        if out is not None or out_f32 is not None:
-            _check(lib.magnet_bn_train_apply(ctypes.byref(a), _stream(x)), "magnet_bn_train_apply")
+    if stats:
+        _launch("magnet_bn_train_stats", x, ctypes.byref(a))
+    if out is not None or out_f32 is not None:
+        _launch("magnet_bn_train_apply", x, ctypes.byref(a))
 
 
 # ---- F-Net backward in training mode (include/magnet_hip.h; csrc/train_fnet_bwd.hip, csrc/train_bwd.hip) ----
-API_SYMBOLS = API_SYMBOLS + ("magnet_wgrad_ex_workspace", "magnet_wgrad_ex", "magnet_bn_train_backward", "magnet_fnet_grad_pack",
-                             "magnet_fnet_d2s_backward", "magnet_spp_upsample_backward", "magnet_spp_pool_backward",
-                             "magnet_fnet_stem_wgrad")
-
-
-class MagnetWgradExArgs(ctypes.Structure):
-    """Mirror of `struct MagnetWgradExArgs` (include/magnet_hip.h)."""
-    _fields_ = [("base", MagnetWgradArgs), ("dil", ctypes.c_int32), ("reserved", ctypes.c_int32)]
-
-
-class MagnetBnBwdArgs(ctypes.Structure):
-    """Mirror of `struct MagnetBnBwdArgs` (include/magnet_hip.h)."""
-    _fields_ = [("x", ctypes.c_void_p), ("x_ld", ctypes.c_int64),
-                ("N", ctypes.c_int32), ("hp", ctypes.c_int32), ("wp", ctypes.c_int32), ("pad", ctypes.c_int32), ("C", ctypes.c_int32),
-                ("relu", ctypes.c_int32),
-                ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
-                ("g", ctypes.c_void_p), ("g_ld", ctypes.c_int64), ("work", ctypes.c_void_p),
-                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p),
-                ("dx_hi", ctypes.c_void_p), ("dx_lo", ctypes.c_void_p), ("dx_ld", ctypes.c_int64)]
-
-
-class MagnetSppBwdArgs(ctypes.Structure):
-    """Mirror of `struct MagnetSppBwdArgs` (include/magnet_hip.h)."""
-    _fields_ = [("g", ctypes.c_void_p), ("g_ld", ctypes.c_int64),
-                ("N", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("pad", ctypes.c_int32), ("c_off", ctypes.c_int32),
-                ("ph", ctypes.c_int32), ("pw", ctypes.c_int32),
-                ("dq", ctypes.c_void_p), ("dpool", ctypes.c_void_p * 4), ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int64)]
-
-
-def _fnet_bwd_protos(lib):
-    if getattr(lib, "_fnet_bwd_protos_done", False):
-        return lib
-    I, P = ctypes.c_int32, ctypes.c_void_p
-    lib.magnet_wgrad_ex_workspace.restype = ctypes.c_int64
-    lib.magnet_wgrad_ex_workspace.argtypes = [ctypes.POINTER(MagnetWgradExArgs)]
-    for name, st in (("magnet_wgrad_ex", MagnetWgradExArgs), ("magnet_bn_train_backward", MagnetBnBwdArgs),
-                     ("magnet_spp_upsample_backward", MagnetSppBwdArgs), ("magnet_spp_pool_backward", MagnetSppBwdArgs)):
-        f = getattr(lib, name)
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.POINTER(st), P]
-    lib.magnet_fnet_grad_pack.restype = ctypes.c_int
-    lib.magnet_fnet_grad_pack.argtypes = [P, P, P, I, I, I, I, I, I, P]
-    lib.magnet_fnet_d2s_backward.restype = ctypes.c_int
-    lib.magnet_fnet_d2s_backward.argtypes = [P, P, I, I, I, I, I, P]
-    lib.magnet_fnet_stem_wgrad.restype = ctypes.c_int
-    lib.magnet_fnet_stem_wgrad.argtypes = [P, P, P, P, P, I, I, I, P]
-    lib._fnet_bwd_protos_done = True
-    return lib
-
-
 def wgrad_ex(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, dil=1, cin_dst=0, cout_valid=None, cin_valid=None):
     """magnet_wgrad with dilation (taps 9), the space-to-depth 2x2 window (taps 4, grad_w (Cout, Cin, 2, 2)) or taps 1."""
-    lib = _fnet_bwd_protos(_train_protos(load()))
-    for t, nme in ((dy_hi, "dy_hi"), (dy_lo, "dy_lo"), (x_hi, "x_hi"), (x_lo, "x_lo")):
-        _bf16_ptr(t, nme)
-    gw = _dev(grad_w, "grad_w", torch.float32)
+    a = MagnetWgradExArgs(base=_wgrad_args(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, cin_dst, cout_valid, cin_valid),
+                          dil=int(dil))
     for t, n in ((dy_hi, "dy"), (x_hi, "x")):
         if t.shape[0] < rows:
             raise MagnetError(f"wgrad_ex: {n} holds fewer than {rows} rows")
-    a = MagnetWgradExArgs()
-    b = a.base
-    b.dy_hi, b.dy_lo, b.x_hi, b.x_lo = dy_hi.data_ptr(), dy_lo.data_ptr(), x_hi.data_ptr(), x_lo.data_ptr()
-    b.dy_ld, b.x_ld, b.rows, b.cout, b.cin, b.taps, b.wp = dy_hi.stride(0), x_hi.stride(0), int(rows), int(cout), int(cin), int(taps), int(wp)
-    b.grad_w = gw.data_ptr()
-    b.cout_valid, b.cin_valid = int(cout if cout_valid is None else cout_valid), int(cin if cin_valid is None else cin_valid)
-    b.cin_total, b.cin_dst = gw.shape[1], int(cin_dst)
-    a.base = b
-    a.dil = int(dil)
-    nbytes = lib.magnet_wgrad_ex_workspace(ctypes.byref(a))
-    if nbytes < 0:
-        _check(int(-nbytes), "magnet_wgrad_ex_workspace")
-    work = torch.empty(max(int(nbytes) // 4, 4), dtype=torch.float32, device=gw.device)
+    work = torch.empty(max(_workspace("magnet_wgrad_ex_workspace", a) // 4, 4), dtype=torch.float32, device=grad_w.device)
     a.base.work = work.data_ptr()
-    with torch.cuda.device(gw.device):
-        _check(lib.magnet_wgrad_ex(ctypes.byref(a), _stream(gw)), "magnet_wgrad_ex")
+    _launch("magnet_wgrad_ex", grad_w, ctypes.byref(a))
 
 
 def bn_train_backward(x, grid, mean, invstd, gamma, beta, relu, g, dgamma, dbeta, dx, work):
     """BatchNorm2d backward (batch statistics).  x: the saved fp32 pre-BN grid; g: fp32 gradient grid (views allowed, unit channel
     stride); dx = (hi, lo) split planes written over the whole grid."""
-    lib = _fnet_bwd_protos(load())
     N, hp, wp, pad, C = (int(v) for v in grid)
     rows = N * hp * wp
     for t, n in ((x, "x"), (g, "g")):
@@ -1058,96 +905,54 @@ def bn_train_backward(x, grid, mean, invstd, gamma, beta, relu, g, dgamma, dbeta
                         g=g.data_ptr(), g_ld=g.stride(0), work=_dev(work, "work", torch.float64).data_ptr(),
                         dgamma=_dev(dgamma, "dgamma", torch.float32).data_ptr(), dbeta=_dev(dbeta, "dbeta", torch.float32).data_ptr(),
                         dx_hi=_bf16_ptr(dx[0], "dx_hi"), dx_lo=_bf16_ptr(dx[1], "dx_lo"), dx_ld=dx[0].stride(0))
-    with torch.cuda.device(x.device):
-        _check(lib.magnet_bn_train_backward(ctypes.byref(a), _stream(x)), "magnet_bn_train_backward")
+    _launch("magnet_bn_train_backward", x, ctypes.byref(a))
 
 
 def fnet_grad_pack(g_nchw, out_hi, out_lo, pad):
-    lib = _fnet_bwd_protos(load())
     g = _dev(g_nchw, "grad", torch.float32)
     N, C, h, w = g.shape
     ld = out_hi.shape[1]
     if out_hi.shape[0] < N * (h + 2 * pad) * (w + 2 * pad) or not out_hi.is_contiguous() or out_lo.shape != out_hi.shape:
         raise MagnetError("fnet_grad_pack: output planes too small")
-    with torch.cuda.device(g.device):
-        _check(lib.magnet_fnet_grad_pack(g.data_ptr(), _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo"), N, C, h, w, int(pad),
-                                         int(ld), _stream(g)), "magnet_fnet_grad_pack")
+    _launch("magnet_fnet_grad_pack", g, g.data_ptr(), _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo"), N, C, h, w, int(pad), int(ld))
 
 
 def fnet_d2s_backward(g_s, out, N, C, H2, W2, ipad):
-    lib = _fnet_bwd_protos(load())
-    with torch.cuda.device(g_s.device):
-        _check(lib.magnet_fnet_d2s_backward(_dev(g_s, "in", torch.float32).data_ptr(), _dev(out, "out", torch.float32).data_ptr(),
-                                            N, C, H2, W2, ipad, _stream(g_s)), "magnet_fnet_d2s_backward")
+    _launch("magnet_fnet_d2s_backward", g_s, _dev(g_s, "in", torch.float32).data_ptr(), _dev(out, "out", torch.float32).data_ptr(),
+            N, C, H2, W2, ipad)
 
 
 def spp_upsample_backward(g, c_off, N, h, w, pad, ph, pw, dq):
-    lib = _fnet_bwd_protos(load())
     a = MagnetSppBwdArgs(g=_dev(g, "g", torch.float32).data_ptr(), g_ld=g.stride(0), N=N, h=h, w=w, pad=pad, c_off=c_off, ph=ph, pw=pw,
                          dq=_dev(dq, "dq", torch.float32).data_ptr())
-    with torch.cuda.device(g.device):
-        _check(lib.magnet_spp_upsample_backward(ctypes.byref(a), _stream(g)), "magnet_spp_upsample_backward")
+    _launch("magnet_spp_upsample_backward", g, ctypes.byref(a))
 
 
 def spp_pool_backward(g, c_off, N, h, w, pad, dpools, out):
-    lib = _fnet_bwd_protos(load())
     a = MagnetSppBwdArgs(g=_dev(g, "g", torch.float32).data_ptr(), g_ld=g.stride(0), N=N, h=h, w=w, pad=pad, c_off=c_off,
                          out=_dev(out, "out", torch.float32).data_ptr(), out_ld=out.stride(0))
     for i, d in enumerate(dpools):
         a.dpool[i] = _dev(d, "dpool", torch.float32).data_ptr()
-    with torch.cuda.device(g.device):
-        _check(lib.magnet_spp_pool_backward(ctypes.byref(a), _stream(g)), "magnet_spp_pool_backward")
+    _launch("magnet_spp_pool_backward", g, ctypes.byref(a))
 
 
 def fnet_stem_wgrad(img, dz, grad_w, work):
-    lib = _fnet_bwd_protos(load())
     x = _dev(img, "img", torch.float32)
     N, _, H, W = x.shape
-    with torch.cuda.device(x.device):
-        _check(lib.magnet_fnet_stem_wgrad(x.data_ptr(), _bf16_ptr(dz[0], "dz_hi"), _bf16_ptr(dz[1], "dz_lo"),
-                                          _dev(grad_w, "grad_w", torch.float32).data_ptr(), _dev(work, "work", torch.float64).data_ptr(),
-                                          N, H, W, _stream(x)), "magnet_fnet_stem_wgrad")
+    _launch("magnet_fnet_stem_wgrad", x, x.data_ptr(), _bf16_ptr(dz[0], "dz_hi"), _bf16_ptr(dz[1], "dz_lo"),
+            _dev(grad_w, "grad_w", torch.float32).data_ptr(), _dev(work, "work", torch.float64).data_ptr(), N, H, W)
 
 
 # ---- the D-Net decoder (include/magnet_hip.h: magnet_conv_mfma_ex, magnet_dnet_gauss_head; csrc/dnet_kernels.hip) ----------------
-API_SYMBOLS = API_SYMBOLS + ("magnet_conv_mfma_ex", "magnet_conv_row_tiles", "magnet_dnet_gauss_head", "magnet_dnet_upsample_gauss")
-ACT_BASE, ACT_LEAKY_RELU = 0, 1
-TILING_FLAT, TILING_BM256 = 1, 2
-
-
-class MagnetConvExArgs(ctypes.Structure):
-    """Mirror of `struct MagnetConvExArgs` (include/magnet_hip.h)."""
-    _fields_ = [("base", MagnetConvArgs), ("act", ctypes.c_int32), ("act_slope", ctypes.c_float),
-                ("tiling", ctypes.c_int32), ("tiles_out", ctypes.POINTER(ctypes.c_int64))]
-
-
-def _dnet_protos(lib):
-    if getattr(lib, "_dnet_protos_done", False):
-        return lib
-    I, P = ctypes.c_int32, ctypes.c_void_p
-    lib.magnet_conv_mfma_ex.restype = ctypes.c_int
-    lib.magnet_conv_mfma_ex.argtypes = [ctypes.POINTER(MagnetConvExArgs), P]
-    lib.magnet_conv_row_tiles.restype = ctypes.c_int64
-    lib.magnet_conv_row_tiles.argtypes = [I, I, I, I, ctypes.POINTER(I)]
-    lib.magnet_dnet_gauss_head.restype = ctypes.c_int
-    lib.magnet_dnet_gauss_head.argtypes = [P, I, I, I, I, I, P, P]
-    lib.magnet_dnet_upsample_gauss.restype = ctypes.c_int
-    lib.magnet_dnet_upsample_gauss.argtypes = [P, I, P, I, I, I, I, P, P]
-    lib._dnet_protos_done = True
-    return lib
-
-
 def dnet_gauss_head(head_out, ld, N, h, w, pad, out):
     """Depth-head fp32 output (rows >= N*(h+2pad)*(w+2pad), ld) -> out (N,2,h,w) = [mu, sqrt(elu(v) + 1 + 1e-10)] (DNET.py:62-67)."""
-    lib = _dnet_protos(load())
     x = _dev(head_out, "head_out", torch.float32)
     if x.dim() != 2 or x.stride(1) != 1 or x.stride(0) != ld or x.shape[0] < N * (h + 2 * pad) * (w + 2 * pad) or x.shape[1] < 2:
         raise MagnetError(f"dnet_gauss_head: head output {tuple(x.shape)} does not hold {N} ({h}+2*{pad}) x ({w}+2*{pad}) grids of pitch {ld}")
     o = _dev(out, "out", torch.float32)
     if tuple(o.shape) != (N, 2, h, w) or not o.is_contiguous():
         raise MagnetError(f"dnet_gauss_head: out must be a contiguous ({N}, 2, {h}, {w}) tensor")
-    with torch.cuda.device(x.device):
-        _check(lib.magnet_dnet_gauss_head(x.data_ptr(), int(ld), N, h, w, pad, o.data_ptr(), _stream(x)), "magnet_dnet_gauss_head")
+    _launch("magnet_dnet_gauss_head", x, x.data_ptr(), int(ld), N, h, w, pad, o.data_ptr())
 
 
 def check_dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out):
@@ -1175,8 +980,5 @@ def dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out):
     (D_dense_depth.py:85-100 then DNET.py:55-60)."""
     check_dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out)
     x, m, o = _dev(head_out, "head_out", torch.float32), _dev(mask_out, "mask_out", torch.float32), _dev(out, "out", torch.float32)
-    lib = _dnet_protos(load())
-    with torch.cuda.device(x.device):
-        _check(lib.magnet_dnet_upsample_gauss(x.data_ptr(), int(head_ld), m.data_ptr(), int(mask_ld), int(N), int(h), int(w), o.data_ptr(),
-                                              _stream(x)), "magnet_dnet_upsample_gauss")
+    _launch("magnet_dnet_upsample_gauss", x, x.data_ptr(), int(head_ld), m.data_ptr(), int(mask_ld), int(N), int(h), int(w), o.data_ptr())
     return out

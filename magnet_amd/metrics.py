@@ -3,7 +3,6 @@ reductions on the device (magnet_depth_metrics) so the (B,2,H,W) predictions are
 the reference's validate() does `.cpu().numpy()` on full maps (test_MaGNet.py:54-56)."""
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -28,13 +27,6 @@ def crop_window(kind, H: int, W: int):
 def depth_metric_sums(pred: torch.Tensor, gt: torch.Tensor, min_depth: float, max_depth: float, crop=None) -> torch.Tensor:
     """pred (B,2,H,W) fp32 [mu, sigma]; gt (B,1,H,W) or (B,H,W) fp32 -> (B,16) float64 sums (device).
     crop: None, 'garg', 'eigen' or an explicit (y0, y1, x0, x1) window.  Fixed summation order: deterministic."""
-    l = lib.load()
-    if not getattr(l, "_metrics_proto", False):
-        l.magnet_depth_metrics.restype = ctypes.c_int
-        l.magnet_depth_metrics.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int32] * 2 + [ctypes.c_float] * 2 + [ctypes.c_void_p]
-        l.magnet_depth_metrics_crop.restype = ctypes.c_int
-        l.magnet_depth_metrics_crop.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int32] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int32] * 4 + [ctypes.c_void_p]
-        l._metrics_proto = True
     p = lib._dev(pred.detach().float().contiguous(), "pred", torch.float32)
     g = lib._dev(gt.detach().float().contiguous(), "gt", torch.float32)
     B, two, H, W = p.shape
@@ -42,13 +34,11 @@ def depth_metric_sums(pred: torch.Tensor, gt: torch.Tensor, min_depth: float, ma
         raise lib.MagnetError(f"depth_metric_sums: pred {tuple(p.shape)} / gt {tuple(g.shape)} mismatch")
     sums = torch.empty((B, 16), dtype=torch.float64, device=p.device)
     win = crop_window(crop, H, W) if isinstance(crop, (str, type(None))) else tuple(int(c) for c in crop)
-    with torch.cuda.device(p.device):
-        if win is None:
-            lib._check(l.magnet_depth_metrics(p.data_ptr(), g.data_ptr(), sums.data_ptr(), B, H * W, float(min_depth),
-                                              float(max_depth), lib._stream(p)), "magnet_depth_metrics")
-        else:
-            lib._check(l.magnet_depth_metrics_crop(p.data_ptr(), g.data_ptr(), sums.data_ptr(), B, H, W, float(min_depth),
-                                                   float(max_depth), *win, lib._stream(p)), "magnet_depth_metrics_crop")
+    if win is None:
+        lib._launch("magnet_depth_metrics", p, p.data_ptr(), g.data_ptr(), sums.data_ptr(), B, H * W, float(min_depth), float(max_depth))
+    else:
+        lib._launch("magnet_depth_metrics_crop", p, p.data_ptr(), g.data_ptr(), sums.data_ptr(), B, H, W, float(min_depth),
+                    float(max_depth), *win)
     return sums
 
 

@@ -1,7 +1,8 @@
-"""The C-ABI library loads and exports every symbol include/magnet_hip.h declares; the ctypes
-mirror of the argument struct has the C layout; argument errors come back as codes (no compute
-is launched here — that is what the -m gpu tests do)."""
+"""The C-ABI library loads and exports every symbol include/magnet_hip.h declares; the binding's prototype
+table, the ctypes mirrors of all argument structs and its constants agree with the header; argument errors
+come back as codes (no compute is launched here — that is what the -m gpu tests do)."""
 import ctypes
+import functools
 import os
 import re
 import subprocess
@@ -13,15 +14,65 @@ REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 HEADER = os.path.join(REPO, "include", "magnet_hip.h")
 
 
+def _header():
+    """include/magnet_hip.h without its comments."""
+    return re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+
+
+def _declarations():
+    """{name: (return type, [parameter declarations])} of every `MAGNET_API <ret> magnet_x(<params>);`, in header order."""
+    decls = {}
+    for ret, name, params in re.findall(r"MAGNET_API\s+([\w\s\*]+?)\b(magnet_\w+)\s*\(([^()]*)\)\s*;", _header()):
+        params = " ".join(params.split())
+        decls[name] = (" ".join(ret.split()), [] if params == "void" else [p.strip() for p in params.split(",")])
+    return decls
+
+
 def _declared_symbols():
-    src = open(HEADER).read()
-    return sorted(set(re.findall(r"MAGNET_API\s+[\w\s\*]+?\b(magnet_\w+)\s*\(", src)))
+    return sorted(_declarations())
+
+
+def _struct_fields():
+    """{struct: [field names]} of every `typedef struct Magnet* { ... } Magnet*;`, in header order."""
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(Magnet\w+)\s*\{(.*?)\}\s*\1\s*;", _header(), flags=re.S):
+        out[name] = [f for decl in body.split(";") for f in re.findall(r"(\w+)\s*(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
+    return out
+
+
+STRUCTS = _struct_fields()
+# the Python mirror (magnet_amd/lib.py) of every enum value and #define the package uses is "MAGNET_" + its name
+CONSTANTS = ("E_NULL", "E_DIM", "E_DTYPE", "E_ALIGN", "E_NODEVICE", "E_SHAPE", "FEAT_F32", "FEAT_BF16", "MAX_CANDIDATES", "NLL_BLOCKS",
+             "NLL_MAX_ITER", "BN_BLOCKS", "ACT_BASE", "ACT_LEAKY_RELU", "TILING_FLAT", "TILING_BM256")
+
+
+@functools.lru_cache(maxsize=None)
+def _c_probe():
+    """What the C compiler makes of the header, from one gcc run: {struct: (sizeof, [(offsetof, sizeof) per field])} and {macro / enum
+    name: value}."""
+    prog = '#include "%s"\n#include <stdio.h>\n#include <stddef.h>\nint main(){\n' % HEADER
+    for s, fields in STRUCTS.items():
+        prog += 'printf("S %s %%zu", sizeof(%s));' % (s, s)
+        for f in fields:
+            prog += 'printf(" %%zu %%zu", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (s, f, s, f)
+        prog += 'printf("\\n");\n'
+    for c in ("HIP_VERSION",) + CONSTANTS:
+        prog += 'printf("C MAGNET_%s %%lld\\n", (long long)MAGNET_%s);\n' % (c, c)
+    prog += "return 0;}\n"
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
+        open(c, "w").write(prog)
+        subprocess.check_call(["gcc", c, "-o", exe])
+        lines = [ln.split() for ln in subprocess.check_output([exe]).decode().splitlines()]
+    structs = {ln[1]: (int(ln[2]), list(zip(map(int, ln[3::2]), map(int, ln[4::2])))) for ln in lines if ln[0] == "S"}
+    return structs, {ln[1]: int(ln[2]) for ln in lines if ln[0] == "C"}
 
 
 def test_header_declares_expected_entry_points():
     syms = _declared_symbols()
     assert {"magnet_cost_volume_cw", "magnet_pack_features", "magnet_gaussian_update",
             "magnet_upsample_depth", "magnet_version", "magnet_last_error"} <= set(syms)
+    assert len(syms) == len(re.findall(r"^MAGNET_API\b", _header(), flags=re.M)) >= 48      # the parser misses no declaration
 
 
 def test_library_exports_every_declared_symbol(hip_lib):
@@ -29,25 +80,117 @@ def test_library_exports_every_declared_symbol(hip_lib):
     for s in _declared_symbols():
         assert hasattr(hip_lib, s), f"{s} declared in include/magnet_hip.h but not exported"
     assert set(_declared_symbols()) == set(lib.API_SYMBOLS)
-    assert hip_lib.magnet_version() == 400
+    assert hip_lib.magnet_version() == _c_probe()[1]["MAGNET_HIP_VERSION"]
 
 
-@pytest.mark.parametrize("struct", ["MagnetCostVolumeArgs", "MagnetConvArgs"])
+_C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+              "double": ctypes.c_double}
+
+
+def _ctypes_for(c_decl, L, is_param):
+    """The ctypes types that may stand for one C return type or parameter declaration of the header."""
+    words = re.sub(r"\bconst\b", " ", c_decl).replace("*", " ").split()
+    if is_param:
+        assert len(words) == 2, f"unnamed or unparsed parameter {c_decl!r}"
+    base, stars = words[0], c_decl.count("*")
+    if stars == 0:
+        return (_C_SCALARS[base],)
+    assert stars == 1, c_decl
+    if base.startswith("Magnet"):
+        return (ctypes.POINTER(getattr(L, base)),)
+    if base == "char" and not is_param:
+        return (ctypes.c_char_p,)
+    return (ctypes.c_void_p,) + ((ctypes.POINTER(_C_SCALARS[base]),) if base in _C_SCALARS else ())
+
+
+def _proto_mismatches(table, L):
+    """Every way the prototype table {name: (restype, argtypes)} differs from the header's declarations ([] = it matches)."""
+    decls = _declarations()
+    errs = []
+    if list(table) != list(decls):
+        errs.append(f"names / order: table only {sorted(set(table) - set(decls))}, header only {sorted(set(decls) - set(table))}")
+    for name in set(table) & set(decls):
+        (restype, argtypes), (ret, params) = table[name], decls[name]
+        if restype not in _ctypes_for(ret, L, False):
+            errs.append(f"{name}: restype {restype} for `{ret}`")
+        if len(argtypes) != len(params):
+            errs.append(f"{name}: {len(argtypes)} argtypes for {len(params)} parameters")
+        errs += [f"{name}: argument {i} is {a} for `{p}`" for i, (a, p) in enumerate(zip(argtypes, params))
+                 if a not in _ctypes_for(p, L, True)]
+    return errs
+
+
+def test_prototype_table_matches_the_header():
+    from magnet_amd import lib as L
+    assert len(_declarations()) >= 48
+    assert _proto_mismatches(L._PROTOS, L) == []
+    assert L.API_SYMBOLS == tuple(_declarations())
+
+
+def test_prototype_comparison_rejects_wrong_tables():
+    """Negative control of _proto_mismatches: an int64_t typed 32 bits wide, a dropped parameter, another struct's pointer, a missing
+    entry."""
+    from magnet_amd import lib as L
+
+    def changed(name, edit):
+        table = dict(L._PROTOS)
+        restype, argtypes = table[name]
+        table[name] = (restype, edit(list(argtypes)))
+        return table
+
+    def narrow(argtypes):
+        argtypes[argtypes.index(ctypes.c_int64)] = ctypes.c_int32
+        return argtypes
+
+    for name in ("magnet_pack_split", "magnet_conv1x1_chain", "magnet_cost_volume_f_backward_ws"):
+        errs = _proto_mismatches(changed(name, narrow), L)
+        assert len(errs) == 1 and name in errs[0] and "int64_t" in errs[0], errs
+    errs = _proto_mismatches(changed("magnet_upsample_depth", lambda a: a[:-1]), L)
+    assert len(errs) == 1 and "8 argtypes for 9" in errs[0], errs
+    errs = _proto_mismatches(changed("magnet_wgrad", lambda a: [ctypes.POINTER(L.MagnetWgradExArgs)] + a[1:]), L)
+    assert len(errs) == 1 and "magnet_wgrad: argument 0" in errs[0], errs
+    errs = _proto_mismatches(changed("magnet_conv_mfma", lambda a: [ctypes.c_void_p] + a[1:]), L)
+    assert len(errs) == 1 and "magnet_conv_mfma: argument 0" in errs[0], errs               # a struct pointer is not "any pointer"
+    table = dict(L._PROTOS)
+    table["magnet_wgrad_workspace"] = (ctypes.c_int, table["magnet_wgrad_workspace"][1])
+    assert len(_proto_mismatches(table, L)) == 1                                             # int64_t return read as int
+    del table["magnet_wgrad_workspace"]
+    assert any("header only ['magnet_wgrad_workspace']" in e for e in _proto_mismatches(table, L))
+
+
+def test_every_entry_point_is_typed_after_load(hip_lib):
+    """No function reached through load() is left with ctypes' default of 32-bit int arguments."""
+    from magnet_amd import lib as L
+    assert len(L.API_SYMBOLS) == len(set(L.API_SYMBOLS)) >= 48
+    for name in L.API_SYMBOLS:
+        f = getattr(hip_lib, name)
+        restype, argtypes = L._PROTOS[name]
+        assert f.argtypes is not None and list(f.argtypes) == argtypes, name
+        assert f.restype is restype, name
+
+
+def test_every_header_struct_has_a_mirror():
+    from magnet_amd import lib as L
+    mirrors = {n for n, v in vars(L).items() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert mirrors == set(STRUCTS) and len(STRUCTS) >= 11
+
+
+@pytest.mark.parametrize("struct", list(STRUCTS))
 def test_struct_layout_matches_c(hip_lib, struct):
     from magnet_amd import lib as L
     A = getattr(L, struct)
     fields = [f[0] for f in A._fields_]
-    prog = '#include "%s"\n#include <stdio.h>\n#include <stddef.h>\nint main(){printf("%%zu", sizeof(%s));' % (HEADER, struct)
-    for f in fields:
-        prog += 'printf(" %%zu", offsetof(%s, %s));' % (struct, f)
-    prog += "return 0;}\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c"); exe = os.path.join(d, "t")
-        open(c, "w").write(prog)
-        subprocess.check_call(["gcc", c, "-o", exe])
-        vals = [int(x) for x in subprocess.check_output([exe]).decode().split()]
-    assert vals[0] == ctypes.sizeof(A)
-    assert vals[1:] == [getattr(A, f).offset for f in fields]
+    assert fields == STRUCTS[struct]                          # the header's fields, all of them, in its order
+    size, layout = _c_probe()[0][struct]
+    assert size == ctypes.sizeof(A)
+    assert layout == [(getattr(A, f).offset, getattr(A, f).size) for f in fields]
+
+
+def test_constants_match_the_header():
+    from magnet_amd import lib as L
+    values = _c_probe()[1]
+    for name in CONSTANTS:
+        assert getattr(L, name) == values["MAGNET_" + name], name
 
 
 def test_argument_errors_are_codes_not_crashes(hip_lib):
@@ -65,8 +208,7 @@ def test_argument_errors_are_codes_not_crashes(hip_lib):
     assert hip_lib.magnet_gaussian_update(16, 16, 16, 0, 5, None) == 2
     assert hip_lib.magnet_upsample_depth(16, 16, 16, 1, 2, 4, 4, 3, None) == 2  # k must be 1,2,4,8
     # convolution / F-Net entry points
-    from magnet_amd.lib import MagnetConvArgs, _conv_protos, _fnet_protos
-    _conv_protos(hip_lib); _fnet_protos(hip_lib)
+    from magnet_amd.lib import MagnetConvArgs
     c = MagnetConvArgs()
     assert hip_lib.magnet_conv_mfma(ctypes.byref(c), None) == 1
     c.in_hi = c.in_lo = c.w_hi = c.w_lo = c.bias = c.out_hi = c.out_lo = 16

@@ -133,7 +133,7 @@ def test_conv_ex_struct_layout_matches_c(hip_lib):
 
 
 def test_conv_ex_and_gauss_head_argument_errors(hip_lib):
-    L = lib._dnet_protos(lib._conv_protos(hip_lib))
+    L = hip_lib
     assert L.magnet_conv_mfma_ex(None, None) == 1
     x = lib.MagnetConvExArgs()
     c = x.base

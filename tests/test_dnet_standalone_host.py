@@ -78,7 +78,7 @@ def test_abi_grows_by_one_symbol(hip_lib):
                      r"\s*int32_t N,\s*int32_t h, int32_t w, float \*out, void \*stream\);", text)
     assert re.search(r"#define MAGNET_HIP_VERSION 400\b", text)
     assert hasattr(hip_lib, "magnet_dnet_upsample_gauss")
-    L = lib._dnet_protos(hip_lib)
+    L = hip_lib
     assert L.magnet_dnet_upsample_gauss(None, 16, 16, 144, 1, 4, 4, 16, None) == 1             # NULL
     assert L.magnet_dnet_upsample_gauss(16, 3, 16, 144, 1, 4, 4, 16, None) == 2                # head_ld even
     assert L.magnet_dnet_upsample_gauss(16, 16, 16, 140, 1, 4, 4, 16, None) == 2               # mask_ld >= 144

@@ -25,10 +25,8 @@ GUARD = 4096                                      # sentinel floats in front of 
 
 
 def _row_tiles(hip_lib, n_img, h, wp, bm):
-    from magnet_amd import lib
-    L = lib._dnet_protos(hip_lib)
     per = ctypes.c_int32(-1)
-    n = L.magnet_conv_row_tiles(n_img, h, wp, bm, ctypes.byref(per))
+    n = hip_lib.magnet_conv_row_tiles(n_img, h, wp, bm, ctypes.byref(per))
     return n, per.value
 
 
@@ -51,8 +49,7 @@ def test_tile_rule_covers_every_interior_row_once_and_keeps_tiles_inside_their_i
     the last image start at the image's first interior image row, cover all its interior rows and end inside the image; and where
     per-image tiling would be fewer tiles and stay inside the image it is not passed over.  (Shapes whose last tile would leave the
     image can never be chosen, whatever B: they are probed at four batch sizes only.)"""
-    from magnet_amd import lib
-    f = lib._dnet_protos(hip_lib).magnet_conv_row_tiles
+    f = hip_lib.magnet_conv_row_tiles
     per_c = ctypes.c_int32(0)
     ref = ctypes.byref(per_c)
     rec = []

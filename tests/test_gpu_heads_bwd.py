@@ -178,7 +178,7 @@ def test_head_dgrad_gauss_form_with_acc_chain(hip_lib, gpu, grid):
 # ---- nll --------------------------------------------------------------------------------------------------------------------------
 def _nll_backward_into(preds, gt, mask, sums, grad_loss, gamma, out):
     """magnet_nll_loss_backward into a preallocated buffer (NaN-filled by the caller: every element must be written)."""
-    l = lib._train_protos(lib.load())
+    l = lib.load()
     I, B, _, H, W = preds.shape
     a = lib.MagnetNllArgs(preds=preds.data_ptr(), gt=gt.data_ptr(), mask=mask.data_ptr(), sums=sums.data_ptr(),
                           grad_loss=grad_loss.data_ptr(), grad_preds=out.data_ptr(), gamma=float(gamma), n_iter=I, B=B, H=H, W=W)

@@ -51,7 +51,6 @@ def test_new_entry_points_declared_and_exported(hip_lib):
 
 
 def test_new_entry_points_return_null_codes(hip_lib):
-    lib._train_protos(hip_lib)
     for name, st in (("magnet_nll_loss_forward", lib.MagnetNllArgs), ("magnet_nll_loss_backward", lib.MagnetNllArgs),
                      ("magnet_upsample_depth_backward", lib.MagnetUpsampleBwdArgs), ("magnet_head_dgrad", lib.MagnetHeadDgradArgs),
                      ("magnet_wgrad", lib.MagnetWgradArgs)):
@@ -65,7 +64,6 @@ def test_new_entry_points_return_null_codes(hip_lib):
 
 
 def test_new_entry_points_return_dim_codes(hip_lib):
-    lib._train_protos(hip_lib)
     a = lib.MagnetWgradArgs(dy_hi=16, dy_lo=16, x_hi=16, x_lo=16, grad_w=16, work=16, dy_ld=8, x_ld=8, rows=100, cout=7, cin=8,
                             taps=1, wp=6, cout_valid=7, cin_valid=8, cin_total=8)
     assert hip_lib.magnet_wgrad(ctypes.byref(a), None) == lib.E_DIM          # cout % 8
