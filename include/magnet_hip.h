@@ -598,6 +598,33 @@ MAGNET_API int magnet_dnet_gauss_head(const float *in, int32_t in_ld, int32_t N,
 MAGNET_API int magnet_dnet_upsample_gauss(const float *head, int32_t head_ld, const float *mask, int32_t mask_ld, int32_t N,
                                           int32_t h, int32_t w, float *out, void *stream);
 
+/* FnetLoss: the tail of the F-Net training step (train_FNet.py:95-104) on the raw volume x (B, D, h, w) of
+ * magnet_cost_volume_cw(mode = 1): p = softmax over the D bins, pred = sum_j p_j d_j, loss = mean over the valid pixels of
+ * |pred - gt|, valid iff gt > min_depth && !(gt > max_depth) (the driver's gt[gt > max_depth] = 0; mask = gt > min_depth, which needs
+ * min_depth >= 0).  1 <= D <= MAGNET_MAX_CANDIDATES.  Forward: one ascending pass over x (online softmax in fp32, accurate expf);
+ * writes pred, and with gt != NULL also m (the per-pixel maximum), rz (1 / sum_j exp(x_j - m)), sums and loss (NaN when no pixel is
+ * valid).  With gt == NULL only x, d and pred are used: the expected depth alone (validate(), train_FNet.py:166-167).
+ * Backward: grad_x_j = grad_loss / count * sign(pred - gt) * p_j * (d_j - pred) on valid pixels (sign(0) = 0), 0 elsewhere; every
+ * element of grad_x is written; grad_loss and count are read on the device.  The loss is summed in fp64 by MAGNET_NLL_BLOCKS
+ * workgroups and then in a fixed order: no atomics, bit-identical from run to run. */
+typedef struct MagnetFnetLossArgs {
+    const float   *x;                      /* (B, D, h, w) fp32 contiguous: the raw (pre-softmax) volume */
+    const float   *d;                      /* (D) fp32 bin centres, on the device */
+    const float   *gt;                     /* (B, h, w) fp32 at the volume's resolution, or NULL (forward: pred only) */
+    float         *pred;                   /* (B, h, w): forward writes, backward reads */
+    float         *m;                      /* (B, h, w): forward writes (gt != NULL), backward reads */
+    float         *rz;                     /* (B, h, w): forward writes (gt != NULL), backward reads */
+    double        *sums;                   /* (2): valid count, sum of |pred - gt| (forward writes, backward reads) */
+    float         *loss;                   /* forward: the 0-d loss */
+    double        *work;                   /* forward: MAGNET_NLL_BLOCKS * 2 doubles of scratch */
+    const float   *grad_loss;              /* backward: device scalar dL/dloss (read on the device) */
+    float         *grad_x;                 /* backward: (B, D, h, w), every element written */
+    float          min_depth, max_depth;
+    int32_t        B, D, h, w;
+} MagnetFnetLossArgs;
+MAGNET_API int magnet_fnet_loss_forward(const MagnetFnetLossArgs *args, void *stream);
+MAGNET_API int magnet_fnet_loss_backward(const MagnetFnetLossArgs *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

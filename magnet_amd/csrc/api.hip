@@ -43,6 +43,8 @@ hipError_t launch_spp_pool_backward(const MagnetSppBwdArgs&, hipStream_t);
 hipError_t launch_fnet_stem_wgrad(const float*, const uint16_t*, const uint16_t*, float*, double*, int, int, int, hipStream_t);
 hipError_t launch_dnet_gauss_head(const float*, int, int, int, int, int, float*, hipStream_t);
 hipError_t launch_dnet_upsample_gauss(const float*, int, const float*, int, int, int, int, float*, hipStream_t);
+hipError_t launch_fnet_loss_forward(const MagnetFnetLossArgs&, hipStream_t);
+hipError_t launch_fnet_loss_backward(const MagnetFnetLossArgs&, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -749,6 +751,29 @@ MAGNET_API int magnet_fnet_stem_wgrad(const float* img, const void* dz_hi, const
     hipError_t e = magnet::launch_fnet_stem_wgrad(img, (const uint16_t*)dz_hi, (const uint16_t*)dz_lo, grad_w, work, N, H, W,
                                                   (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_stem_wgrad launch");
+}
+
+static int fnet_loss_dims(const MagnetFnetLossArgs* a, const char* who) {
+    if (a->D < 1 || a->D > MAGNET_MAX_CANDIDATES || a->B <= 0 || a->h <= 0 || a->w <= 0)
+        return fail(MAGNET_E_DIM, "%s: bad dims B=%d D=%d h=%d w=%d (1 <= D <= %d)", who, a->B, a->D, a->h, a->w, MAGNET_MAX_CANDIDATES);
+    if (!(a->min_depth >= 0.f)) return fail(MAGNET_E_DIM, "%s: min_depth must be >= 0 (the validity test assumes it)", who);
+    return 0;
+}
+
+MAGNET_API int magnet_fnet_loss_forward(const MagnetFnetLossArgs* a, void* stream) {
+    if (!a || !a->x || !a->d || !a->pred || (a->gt && (!a->m || !a->rz || !a->sums || !a->loss || !a->work)))
+        return fail(MAGNET_E_NULL, "magnet_fnet_loss_forward: NULL pointer");
+    if (int rc = fnet_loss_dims(a, "magnet_fnet_loss_forward")) return rc;
+    hipError_t e = magnet::launch_fnet_loss_forward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_loss_forward launch");
+}
+
+MAGNET_API int magnet_fnet_loss_backward(const MagnetFnetLossArgs* a, void* stream) {
+    if (!a || !a->x || !a->d || !a->gt || !a->pred || !a->m || !a->rz || !a->sums || !a->grad_loss || !a->grad_x)
+        return fail(MAGNET_E_NULL, "magnet_fnet_loss_backward: NULL pointer");
+    if (int rc = fnet_loss_dims(a, "magnet_fnet_loss_backward")) return rc;
+    hipError_t e = magnet::launch_fnet_loss_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_loss_backward launch");
 }
 
 }  // extern "C"

@@ -219,13 +219,16 @@ class _CostVolumeF(torch.autograd.Function):
         return g_ref, g_src, None, None, None, None, None, None, None
 
 
-def est_costvolume_F(d_center, ref_feat, nghbr_feat, R, t, is_valid, cam_intrins, path: int = 0, bwd_path: int = 0):
+def est_costvolume_F(d_center, ref_feat, nghbr_feat, R, t, is_valid, cam_intrins, path: int = 0, bwd_path: int = 0,
+                     softmax: bool = True):
     """Drop-in for homography.est_costvolume_F (reference homography.py:10-46), the matching volume the
     F-Net is trained through (MAGNET.py:197-200): differentiable w.r.t. ref_feat and nghbr_feat.
 
     d_center (1,D,1,1) fixed depth bins (CPU or GPU tensor); ref_feat (B,F,h,w); nghbr_feat (V*B,F,h,w)
     view-major; R (B,V,3,3); t (B,V,3); is_valid (B,V); cam_intrins dict.  Returns softmax over D of the
-    view-averaged feature correlation, (B,D,h,w) fp32.  path = 1 selects the bit-faithful generic kernel."""
+    view-averaged feature correlation, (B,D,h,w) fp32.  path = 1 selects the bit-faithful generic kernel.
+    softmax=False returns the raw (pre-softmax) differentiable volume instead: the input of magnet_amd.losses.FnetLoss and of
+    expected_depth_F, which fuse the softmax with what follows it."""
     if not ref_feat.is_cuda:
         raise lib.MagnetError("est_costvolume_F: features must be on the GPU (no CPU fallback)")
     dev = ref_feat.device
@@ -239,4 +242,37 @@ def est_costvolume_F(d_center, ref_feat, nghbr_feat, R, t, is_valid, cam_intrins
         rays = lib.make_rays(_to_device_cached(cam_intrins["ray_params"], dev, torch.float64, _INTRINS_CACHE),
                              ref_feat.shape[2], ref_feat.shape[3])
     raw = _CostVolumeF.apply(ref_feat, nghbr_feat, bins, poses, iv, intM, rays, path, bwd_path)
-    return torch.softmax(raw, dim=1)                                   # homography.py:45
+    return torch.softmax(raw, dim=1) if softmax else raw                # homography.py:45
+
+
+_D_CENTER_CACHE: dict = {}
+
+
+def d_center_device(d_center: torch.Tensor, device) -> torch.Tensor:
+    """The bin centres as a contiguous fp32 (D) tensor on `device`.  The driver hands over the same (1,D,1,1) tensor on every step:
+    the copy is cached by (data_ptr, _version), so a step does no copy (and, for a CPU tensor, no upload) for it.  An entry belongs to
+    the tensor OBJECT it was made from (weak reference): another tensor that reuses a freed tensor's address never hits."""
+    key = (d_center.data_ptr(), d_center._version, str(d_center.device), str(d_center.dtype), d_center.numel(), str(device))
+    hit = _D_CENTER_CACHE.get(key)
+    if hit is not None and hit[0]() is d_center:
+        return hit[1]
+    for k_ in [k_ for k_, v_ in _D_CENTER_CACHE.items() if v_[0]() is None or k_ == key]:
+        del _D_CENTER_CACHE[k_]                                   # dead owners, and a stale entry of this key
+    if len(_D_CENTER_CACHE) > 16:
+        _D_CENTER_CACHE.clear()
+    dev = d_center.detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous().clone()
+    _D_CENTER_CACHE[key] = (weakref.ref(d_center), dev)
+    return dev
+
+
+def expected_depth_F(raw_volume, d_center):
+    """torch.sum(torch.softmax(raw_volume, 1) * d_center, 1, keepdim=True) in one pass over the raw volume of
+    est_costvolume_F(softmax=False): the expected depth of validate() (train_FNet.py:166-167).  (B,D,h,w) -> (B,1,h,w), no grad."""
+    if not isinstance(d_center, torch.Tensor):
+        raise lib.MagnetError(f"expected_depth_F: d_center must be a torch.Tensor, got {type(d_center).__name__}")
+    if not isinstance(raw_volume, torch.Tensor) or not raw_volume.is_cuda:
+        raise lib.MagnetError("expected_depth_F: raw_volume must be a GPU tensor (no CPU fallback)")
+    x = raw_volume.detach().float().contiguous()
+    if x.dim() != 4 or d_center.numel() != x.shape[1]:
+        raise lib.MagnetError(f"expected_depth_F: raw_volume {tuple(x.shape)} / d_center {tuple(d_center.shape)}, expected (B,D,h,w) and D bins")
+    return lib.fnet_loss_forward(x, d_center_device(d_center, x.device)).unsqueeze(1)

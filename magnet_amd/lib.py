@@ -165,6 +165,15 @@ class MagnetConvExArgs(ctypes.Structure):
                 ("tiling", ctypes.c_int32), ("tiles_out", ctypes.POINTER(ctypes.c_int64))]
 
 
+class MagnetFnetLossArgs(ctypes.Structure):
+    """Mirror of `struct MagnetFnetLossArgs` (include/magnet_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("d", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("pred", ctypes.c_void_p),
+                ("m", ctypes.c_void_p), ("rz", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("loss", ctypes.c_void_p),
+                ("work", ctypes.c_void_p), ("grad_loss", ctypes.c_void_p), ("grad_x", ctypes.c_void_p),
+                ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float),
+                ("B", ctypes.c_int32), ("D", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
 # (restype, argtypes) of every MAGNET_API declaration of include/magnet_hip.h, in header order; load() applies them all
 _C, _L, _F, _I, _P, _S = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER
 _PROTOS = {
@@ -216,6 +225,8 @@ _PROTOS = {
     "magnet_conv_row_tiles": (_L, [_I, _I, _I, _I, _S(_I)]),
     "magnet_dnet_gauss_head": (_C, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
+    "magnet_fnet_loss_backward": (_C, [_S(MagnetFnetLossArgs), _P]),
 }
 API_SYMBOLS = tuple(_PROTOS)
 
@@ -762,6 +773,61 @@ def nll_loss_backward(preds, gt, mask, sums, grad_loss, gamma: float):
                       sums=_dev(sums, "sums", torch.float64).data_ptr(), grad_loss=gl.data_ptr(), grad_preds=out.data_ptr(),
                       gamma=float(gamma), n_iter=I, B=B, H=H, W=W)
     _launch("magnet_nll_loss_backward", p, ctypes.byref(a))
+    return out
+
+
+def _fnet_loss_args(raw, d, who):
+    x = _dev(raw, "raw_volume", torch.float32)
+    dc = _dev(d, "d_center", torch.float32)
+    if x.dim() != 4 or dc.dim() != 1 or dc.shape[0] != x.shape[1] or dc.device != x.device:
+        raise MagnetError(f"{who}: raw_volume {tuple(x.shape)} / d_center {tuple(dc.shape)}, expected (B,D,h,w) and (D) on one device")
+    B, D, h, w = x.shape
+    if not 1 <= D <= MAX_CANDIDATES:
+        raise MagnetError(f"{who}: 1 <= D <= {MAX_CANDIDATES}, got {D}")
+    return x, MagnetFnetLossArgs(x=x.data_ptr(), d=dc.data_ptr(), B=B, D=D, h=h, w=w)
+
+
+def fnet_loss_forward(raw_volume, d_center, gt=None, min_depth: float = 0.0, max_depth: float = 0.0):
+    """raw_volume (B,D,h,w) fp32 (the mode-1 matcher's output), d_center (D) fp32 on the device.  gt None -> pred (B,h,w), the expected
+    depth sum_j softmax(raw)_j d_j.  gt (B,h,w) fp32 -> (loss 0-d fp32, pred, m, rz, sums (2) float64: valid count, sum |pred - gt|)
+    with valid = gt > min_depth and not gt > max_depth; m, rz, sums are what fnet_loss_backward reads.  Deterministic reduction."""
+    x, a = _fnet_loss_args(raw_volume, d_center, "fnet_loss_forward")
+    B, D, h, w = x.shape
+    pred = torch.empty((B, h, w), dtype=torch.float32, device=x.device)
+    a.pred = pred.data_ptr()
+    if gt is None:
+        _launch("magnet_fnet_loss_forward", x, ctypes.byref(a))
+        return pred
+    g = _dev(gt, "gt", torch.float32)
+    if tuple(g.shape) != (B, h, w) or g.device != x.device:
+        raise MagnetError(f"fnet_loss_forward: gt shape {tuple(g.shape)}, expected {(B, h, w)} on {x.device}")
+    m, rz = torch.empty_like(pred), torch.empty_like(pred)
+    sums = torch.empty(2, dtype=torch.float64, device=x.device)
+    work = torch.empty(NLL_BLOCKS * 2, dtype=torch.float64, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    a.gt, a.m, a.rz, a.sums, a.loss, a.work = g.data_ptr(), m.data_ptr(), rz.data_ptr(), sums.data_ptr(), loss.data_ptr(), work.data_ptr()
+    a.min_depth, a.max_depth = float(min_depth), float(max_depth)
+    _launch("magnet_fnet_loss_forward", x, ctypes.byref(a))
+    return loss, pred, m, rz, sums
+
+
+def fnet_loss_backward(raw_volume, d_center, gt, pred, m, rz, sums, grad_loss, min_depth: float, max_depth: float, out=None):
+    """d loss / d raw_volume (B,D,h,w), scaled by the device scalar grad_loss (read on the device: no host sync).  Every element of the
+    result is written (`out`: a contiguous fp32 buffer of that shape to write into)."""
+    x, a = _fnet_loss_args(raw_volume, d_center, "fnet_loss_backward")
+    B, D, h, w = x.shape
+    gl = _dev(grad_loss.reshape(()), "grad_loss", torch.float32)
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(_dev(out, "out", torch.float32).shape) != tuple(x.shape):
+        raise MagnetError(f"fnet_loss_backward: out shape {tuple(out.shape)}, expected {tuple(x.shape)}")
+    for t, name in ((gt, "gt"), (pred, "pred"), (m, "m"), (rz, "rz")):
+        if tuple(_dev(t, name, torch.float32).shape) != (B, h, w):
+            raise MagnetError(f"fnet_loss_backward: {name} shape {tuple(t.shape)}, expected {(B, h, w)}")
+    a.gt, a.pred, a.m, a.rz = gt.data_ptr(), pred.data_ptr(), m.data_ptr(), rz.data_ptr()
+    a.sums, a.grad_loss, a.grad_x = _dev(sums, "sums", torch.float64).data_ptr(), gl.data_ptr(), out.data_ptr()
+    a.min_depth, a.max_depth = float(min_depth), float(max_depth)
+    _launch("magnet_fnet_loss_backward", x, ctypes.byref(a))
     return out
 
 

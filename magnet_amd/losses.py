@@ -1,11 +1,14 @@
-"""Training losses (reference utils/losses.py).  MagnetLoss is the loss of train_MaGNet.py:87-98 on HIP kernels
-(csrc/train_bwd.hip); DnetLoss is out of scope with the D-Net."""
+"""Training losses (reference utils/losses.py and the inline loss of train_FNet.py).  MagnetLoss is the loss of train_MaGNet.py:87-98
+on HIP kernels (csrc/train_bwd.hip); FnetLoss is the tail of the F-Net step, train_FNet.py:95-104 (softmax over the bins, expected
+depth, masked L1), fused on HIP kernels (csrc/fnet_loss.hip); DnetLoss is out of scope with the D-Net."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import lib
+from .homography import d_center_device
 
 
 class _GaussianNLL(torch.autograd.Function):
@@ -53,3 +56,67 @@ class MagnetLoss(nn.Module):
         gt = gt_depth.detach().float().reshape(B, H, W).contiguous()
         mask = gt_depth_mask.detach().reshape(B, H, W).bool().contiguous()
         return _GaussianNLL.apply(float(self.gamma), gt, mask, *preds)
+
+
+class _FnetL1(torch.autograd.Function):
+    """mean over the valid pixels of |sum_j softmax(raw)_j d_j - gt| and the detached expected depth, from the raw volume in one pass;
+    backward: one read of raw, one write of its gradient (closed form), grad_output read on the device (no host sync).  The gradient is
+    a fresh contiguous tensor: the cost volume's backward takes it as it is."""
+
+    @staticmethod
+    def forward(ctx, raw, d, gt, min_depth, max_depth):
+        x = raw.detach()
+        loss, pred, m, rz, sums = lib.fnet_loss_forward(x, d, gt, min_depth, max_depth)
+        ctx.depths = (min_depth, max_depth)
+        ctx.save_for_backward(x, d, gt, pred, m, rz, sums)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_pred):
+        x, d, gt, pred, m, rz, sums = ctx.saved_tensors
+        g = lib.fnet_loss_backward(x, d, gt, pred, m, rz, sums, grad_out.float().reshape(()).contiguous(), *ctx.depths)
+        return g, None, None, None, None
+
+
+class FnetLoss(nn.Module):
+    """The loss of the reference's F-Net driver (train_FNet.py:95-104) on the RAW volume of MAGNET_F(..., softmax=False):
+    reads args.loss_fn (only 'l1' exists, as in the reference), args.min_depth and args.max_depth;
+    forward(raw_volume (B,D,h,w), d_center (D bins, any shape), gt_dmap (B,1,H,W)) -> 0-d tensor.  A gt_dmap of another resolution is
+    brought to the volume's with F.interpolate(mode='nearest') as the driver does; pixels with gt > max_depth or gt <= min_depth do not
+    count (the driver's gt[gt > max_depth] = 0 commutes with nearest sampling, so gt_dmap may come clipped or not).
+    pred_dmap: the detached (B,1,h,w) expected depth of the last forward (visualize_F, the progress line).  GPU tensors only."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.loss_type = args.loss_fn
+        self.min_depth = float(args.min_depth)
+        self.max_depth = float(args.max_depth)
+        self.pred_dmap = None
+
+    def forward(self, raw_volume, d_center, gt_dmap):
+        if self.loss_type != "l1":
+            raise lib.MagnetError(f"FnetLoss: loss_fn {self.loss_type!r} is not supported (the reference has 'l1' only)")
+        for t, name in ((raw_volume, "raw_volume"), (d_center, "d_center"), (gt_dmap, "gt_dmap")):
+            if not isinstance(t, torch.Tensor):
+                raise lib.MagnetError(f"FnetLoss: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if raw_volume.dim() != 4 or gt_dmap.dim() != 4 or gt_dmap.shape[0] != raw_volume.shape[0] or gt_dmap.shape[1] != 1:
+            raise lib.MagnetError(f"FnetLoss: raw_volume {tuple(raw_volume.shape)} / gt_dmap {tuple(gt_dmap.shape)}, expected (B,D,h,w) and (B,1,H,W)")
+        B, D, h, w = raw_volume.shape
+        if d_center.numel() != D:
+            raise lib.MagnetError(f"FnetLoss: d_center has {d_center.numel()} bins, raw_volume has D = {D}")
+        if not 1 <= D <= lib.MAX_CANDIDATES:
+            raise lib.MagnetError(f"FnetLoss: 1 <= D <= {lib.MAX_CANDIDATES}, got {D}")
+        if self.min_depth < 0:
+            raise lib.MagnetError(f"FnetLoss: min_depth must be >= 0, got {self.min_depth}")
+        for t, name in ((raw_volume, "raw_volume"), (gt_dmap, "gt_dmap")):
+            if not t.is_cuda:
+                raise lib.MagnetError(f"FnetLoss: {name} must be a GPU tensor (magnet_amd has no CPU fallback)")
+        gt = gt_dmap.detach().float()
+        if tuple(gt.shape[2:]) != (h, w):
+            gt = F.interpolate(gt, size=[h, w], mode="nearest")               # train_FNet.py:98
+        x = raw_volume if raw_volume.dtype == torch.float32 and raw_volume.is_contiguous() else raw_volume.float().contiguous()
+        loss, pred = _FnetL1.apply(x, d_center_device(d_center, x.device), gt.reshape(B, h, w).contiguous(), self.min_depth, self.max_depth)
+        self.pred_dmap = pred.unsqueeze(1)
+        return loss

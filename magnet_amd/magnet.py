@@ -449,11 +449,12 @@ class MAGNET_F(nn.Module):
             return fnet_train_hip(self._hip_runners[2], imgs)
         return self._hip_runners[2].run(imgs)
 
-    def forward(self, ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, d_center):
+    def forward(self, ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, d_center, softmax: bool = True):
+        """softmax=False: the raw volume, for magnet_amd.losses.FnetLoss / homography.expected_depth_F."""
         B = ref_img.shape[0]
         imgs = torch.cat((ref_img, nghbr_imgs), dim=0)
         feat_4 = self._features_hip(imgs) if self.train_backend == "hip" else self.f_net(imgs)   # MAGNET.py:188
         ref_feat_4, nghbr_feat_4 = feat_4[:B], feat_4[B:]
         Rs_src = nghbr_poses[:, :, :3, :3]                                       # MAGNET.py:193-194
         ts_src = nghbr_poses[:, :, :3, 3]
-        return est_costvolume_F(d_center, ref_feat_4, nghbr_feat_4, Rs_src, ts_src, is_valid, cam_intrins)
+        return est_costvolume_F(d_center, ref_feat_4, nghbr_feat_4, Rs_src, ts_src, is_valid, cam_intrins, softmax=softmax)

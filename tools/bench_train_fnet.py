@@ -1,10 +1,12 @@
 """Timing of one MAGNET_F training step of train_FNet.py (lines 69-119): the F-Net on the B(1+V) images in .train() mode, est_costvolume_F,
 the L1 loss on the expected depth, and the backward, for train_backend 'torch' (nn.Conv2d / BatchNorm2d under autograd) and 'hip'
 (magnet_amd/train_fnet.py), at 480 x 640, V = 4, D = 80, F = 64, B = 1 (the ScanNet config per GPU) and B = 4 (the driver's default).
+--loss torch (default) runs the driver's own tail (softmax in est_costvolume_F, expected depth and masked L1 as torch ops); --loss hip takes the
+raw volume and magnet_amd.losses.FnetLoss (the fused tail, csrc/fnet_loss.hip).
 Also times the no-grad training-mode forward.  Prints one JSON line: ms_per_train_step and ms_per_train_forward per backend and batch,
 and the time per kernel of the HIP step (torch.profiler) at B = 4.
 
-    python tools/bench_train_fnet.py [--steps 10] [--warmup 3]
+    python tools/bench_train_fnet.py [--steps 10] [--warmup 3] [--loss {torch,hip}]
 """
 import argparse
 import copy
@@ -24,8 +26,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--loss", default="torch", choices=["torch", "hip"], help="the tail of the step: torch ops (the driver's) or FnetLoss")
     a = ap.parse_args()
     from magnet_amd import fnet, lib, synth
+    from magnet_amd.losses import FnetLoss
     from magnet_amd.magnet import MAGNET_F
     from magnet_amd.train_fnet import FNetTrainHIP
     lib.load()
@@ -35,7 +39,8 @@ def main():
     torch.manual_seed(0)
     base = fnet.FNET(args).train()
     d_center = torch.linspace(0.25, 8.0, D).view(1, -1, 1, 1)
-    res = {"config": dict(V=V, H=H, W=W, F=F, D=D), "steps": a.steps, "warmup": a.warmup, "ms_per_train_step": {},
+    fnet_loss = FnetLoss(SimpleNamespace(loss_fn="l1", min_depth=0.5, max_depth=10.0))
+    res = {"config": dict(V=V, H=H, W=W, F=F, D=D), "loss": a.loss, "steps": a.steps, "warmup": a.warmup, "ms_per_train_step": {},
            "ms_per_train_forward": {}}
 
     def timed(fn):
@@ -61,6 +66,9 @@ def main():
 
             def step():
                 m.zero_grad(set_to_none=True)
+                if a.loss == "hip":
+                    fnet_loss(m(ref_img, nb, poses, valid, cam, d_center, softmax=False), d_center, gt).backward()
+                    return
                 cv = m(ref_img, nb, poses, valid, cam, d_center)
                 pred = torch.sum(cv * d_center.to(dev), dim=1, keepdim=True)
                 mask = gt > 0.5
