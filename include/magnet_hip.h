@@ -625,6 +625,55 @@ typedef struct MagnetFnetLossArgs {
 MAGNET_API int magnet_fnet_loss_forward(const MagnetFnetLossArgs *args, void *stream);
 MAGNET_API int magnet_fnet_loss_backward(const MagnetFnetLossArgs *args, void *stream);
 
+/* DnetLoss: the tail of the stand-alone D-Net's training step behind the two head convolutions (upsample_depth_via_mask,
+ * models/submodules/D_dense_depth.py:86-100; activation_G, models/DNET.py:56-60; DnetLoss 'gaussian', utils/losses.py:8-24) in
+ * fused kernels.  depth (B, 2, h, w) is the RAW head output [mu, v]; the mask logit (b, ch, y, x), ch = t*16 + i*4 + j < 144 with
+ * t = 3 (dy + 1) + (dx + 1) (unfold order), sits at mask[b*mask_sb + ch*mask_sc + y*mask_sy + x*mask_sx] and its gradient at
+ * grad_mask[b*gm_sb + ch*gm_sc + y*gm_sy + x*gm_sx] (element strides, as MagnetUpsampleBwdArgs).  Per fine pixel (4y+i, 4x+j):
+ *   w_t = softmax over the 9 taps; mu = sum_t w_t depth[0](y+dy, x+dx), vu likewise for depth[1] (zero outside the image, by index);
+ *   var = (elu(vu) + 1) + 1e-10; nll = (mu - gt)^2 / (2 var) + 0.5 log var; loss = mean of nll over the pixels with valid != 0.
+ * The arithmetic of the upsampling is magnet_dnet_upsample_gauss's, operation for operation: pred is that entry point's output to
+ * the bit.  Forward writes pred (optional), sums and loss (NaN when no pixel is valid).  Backward recomputes the softmax from the
+ * logits and writes every element of grad_depth and all 144 channels of grad_mask at every pixel (zeros when no pixel is valid);
+ * grad_loss and the count are read on the device.  Sums are taken in fp64 per workgroup and then in a fixed order: no atomics,
+ * bit-identical from run to run.  k = 4 only.  gt and pred 16-byte aligned, valid 4-byte aligned. */
+typedef struct MagnetDnetLossArgs {
+    const float   *depth;                  /* (B, 2, h, w) fp32 contiguous: the raw head output [mu, v] */
+    const float   *mask;                   /* the 144 logits per coarse pixel, addressed through mask_s* */
+    const float   *gt;                     /* (B, 4h, 4w) fp32 */
+    const uint8_t *valid;                  /* (B, 4h, 4w), 0 / 1 */
+    int64_t        mask_sb, mask_sc, mask_sy, mask_sx;
+    int64_t        gm_sb, gm_sc, gm_sy, gm_sx;
+    float         *pred;                   /* forward, optional: (B, 2, 4h, 4w) [mu, var] */
+    double        *sums;                   /* (2): valid count, NLL sum (forward writes, backward reads) */
+    float         *loss;                   /* forward: the 0-d loss */
+    void          *work;                   /* magnet_dnet_loss_workspace(args) bytes of scratch, forward and backward */
+    const float   *grad_loss;              /* backward: device scalar dL/dloss (read on the device) */
+    float         *grad_depth;             /* backward: (B, 2, h, w), every element written */
+    float         *grad_mask;              /* backward: addressed through gm_s*, 144 channels of every pixel written */
+    int32_t        B, h, w, k;             /* k = 4 */
+} MagnetDnetLossArgs;
+MAGNET_API int64_t magnet_dnet_loss_workspace(const MagnetDnetLossArgs *args);
+MAGNET_API int magnet_dnet_loss_forward(const MagnetDnetLossArgs *args, void *stream);
+MAGNET_API int magnet_dnet_loss_backward(const MagnetDnetLossArgs *args, void *stream);
+
+/* The plain form, the reference's own call: pred (B, 2, H, W) [mu, var] already upsampled and activated.  The same NLL with var as
+ * it is; var < 1e-10 -> 1e-10 (losses.py:19), and a pixel where that clamp applies (var <= 0 included) gets no var gradient.
+ * grad_pred: every element written.  work: MAGNET_NLL_BLOCKS * 2 doubles. */
+typedef struct MagnetDnetNllArgs {
+    const float   *pred;                   /* (B, 2, H, W) fp32 [mu, var] */
+    const float   *gt;                     /* (B, H, W) */
+    const uint8_t *valid;                  /* (B, H, W), 0 / 1 */
+    double        *sums;                   /* (2): valid count, NLL sum (forward writes, backward reads) */
+    float         *loss;                   /* forward: the 0-d loss */
+    double        *work;                   /* forward: MAGNET_NLL_BLOCKS * 2 doubles of scratch */
+    const float   *grad_loss;              /* backward: device scalar dL/dloss (read on the device) */
+    float         *grad_pred;              /* backward: (B, 2, H, W) */
+    int32_t        B, H, W;
+} MagnetDnetNllArgs;
+MAGNET_API int magnet_dnet_nll_forward(const MagnetDnetNllArgs *args, void *stream);
+MAGNET_API int magnet_dnet_nll_backward(const MagnetDnetNllArgs *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

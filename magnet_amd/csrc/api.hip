@@ -45,6 +45,11 @@ hipError_t launch_dnet_gauss_head(const float*, int, int, int, int, int, float*,
 hipError_t launch_dnet_upsample_gauss(const float*, int, const float*, int, int, int, int, float*, hipStream_t);
 hipError_t launch_fnet_loss_forward(const MagnetFnetLossArgs&, hipStream_t);
 hipError_t launch_fnet_loss_backward(const MagnetFnetLossArgs&, hipStream_t);
+long long dnet_loss_workspace_bytes(const MagnetDnetLossArgs&);
+hipError_t launch_dnet_loss_forward(const MagnetDnetLossArgs&, hipStream_t);
+hipError_t launch_dnet_loss_backward(const MagnetDnetLossArgs&, hipStream_t);
+hipError_t launch_dnet_nll_forward(const MagnetDnetNllArgs&, hipStream_t);
+hipError_t launch_dnet_nll_backward(const MagnetDnetNllArgs&, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -774,6 +779,63 @@ MAGNET_API int magnet_fnet_loss_backward(const MagnetFnetLossArgs* a, void* stre
     if (int rc = fnet_loss_dims(a, "magnet_fnet_loss_backward")) return rc;
     hipError_t e = magnet::launch_fnet_loss_backward(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_loss_backward launch");
+}
+
+// ---- DnetLoss (dnet_loss.hip) ----
+static int dnet_loss_dims(const MagnetDnetLossArgs* a, const char* who) {
+    if (!a) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (a->k != 4) return fail(MAGNET_E_DIM, "%s: k=%d is not built (the D-Net's downsample ratio is 4)", who, a->k);
+    if (a->B <= 0 || a->h <= 0 || a->w <= 0 || (long long)a->B * a->h * a->w > (1LL << 31))
+        return fail(MAGNET_E_DIM, "%s: bad dims B=%d h=%d w=%d (positive, B h w <= 2^31)", who, a->B, a->h, a->w);
+    return 0;
+}
+
+static int dnet_loss_common(const MagnetDnetLossArgs* a, const char* who) {
+    if (!a || !a->depth || !a->mask || !a->gt || !a->valid || !a->sums || !a->work) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (int rc = dnet_loss_dims(a, who)) return rc;
+    if (!aligned16(a->gt) || !aligned16(a->pred) || (reinterpret_cast<uintptr_t>(a->valid) & 3u) || (reinterpret_cast<uintptr_t>(a->work) & 7u))
+        return fail(MAGNET_E_ALIGN, "%s: gt and pred must be 16-byte, work 8-byte and valid 4-byte aligned", who);
+    return 0;
+}
+
+MAGNET_API int64_t magnet_dnet_loss_workspace(const MagnetDnetLossArgs* a) {
+    if (int rc = dnet_loss_dims(a, "magnet_dnet_loss_workspace")) return -(int64_t)rc;
+    return magnet::dnet_loss_workspace_bytes(*a);
+}
+
+MAGNET_API int magnet_dnet_loss_forward(const MagnetDnetLossArgs* a, void* stream) {
+    if (int rc = dnet_loss_common(a, "magnet_dnet_loss_forward")) return rc;
+    if (!a->loss) return fail(MAGNET_E_NULL, "magnet_dnet_loss_forward: NULL pointer");
+    hipError_t e = magnet::launch_dnet_loss_forward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_loss_forward launch");
+}
+
+MAGNET_API int magnet_dnet_loss_backward(const MagnetDnetLossArgs* a, void* stream) {
+    if (int rc = dnet_loss_common(a, "magnet_dnet_loss_backward")) return rc;
+    if (!a->grad_loss || !a->grad_depth || !a->grad_mask) return fail(MAGNET_E_NULL, "magnet_dnet_loss_backward: NULL pointer");
+    hipError_t e = magnet::launch_dnet_loss_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_loss_backward launch");
+}
+
+static int dnet_nll_dims(const MagnetDnetNllArgs* a, const char* who) {
+    if (a->B <= 0 || a->H <= 0 || a->W <= 0) return fail(MAGNET_E_DIM, "%s: bad dims B=%d H=%d W=%d", who, a->B, a->H, a->W);
+    return 0;
+}
+
+MAGNET_API int magnet_dnet_nll_forward(const MagnetDnetNllArgs* a, void* stream) {
+    if (!a || !a->pred || !a->gt || !a->valid || !a->sums || !a->loss || !a->work)
+        return fail(MAGNET_E_NULL, "magnet_dnet_nll_forward: NULL pointer");
+    if (int rc = dnet_nll_dims(a, "magnet_dnet_nll_forward")) return rc;
+    hipError_t e = magnet::launch_dnet_nll_forward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_nll_forward launch");
+}
+
+MAGNET_API int magnet_dnet_nll_backward(const MagnetDnetNllArgs* a, void* stream) {
+    if (!a || !a->pred || !a->gt || !a->valid || !a->sums || !a->grad_loss || !a->grad_pred)
+        return fail(MAGNET_E_NULL, "magnet_dnet_nll_backward: NULL pointer");
+    if (int rc = dnet_nll_dims(a, "magnet_dnet_nll_backward")) return rc;
+    hipError_t e = magnet::launch_dnet_nll_backward(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_nll_backward launch");
 }
 
 }  // extern "C"

@@ -72,7 +72,8 @@ def upsample_depth_via_mask(depth, up_mask, k):
 class DenseDepthDecoder(nn.Module):
     """The reference's `Decoder(num_classes, downsample_ratio=4, learned_upsampling=True, BN=True, dnet)`.
     dnet=False (MaGNet): forward(features) -> (depth head output (N, num_classes, H/4, W/4), x_feat (N, 256, H/4, W/4));
-    dnet=True (stand-alone D-Net): the depth upsampled x4 through the learned mask head."""
+    dnet=True (stand-alone D-Net): the depth upsampled x4 through the learned mask head, or with forward(features, upsample=False) the
+    raw pair (depth (N, num_classes, H/4, W/4), up_mask (N, 144, H/4, W/4)) for losses.DnetLoss."""
 
     def __init__(self, num_classes=2, downsample_ratio=4, dnet=False):
         super().__init__()
@@ -88,13 +89,17 @@ class DenseDepthDecoder(nn.Module):
         self.depth_head = _head(features // 8, 128, num_classes)
         self.mask_head = _head(features // 8, 128, 9 * downsample_ratio * downsample_ratio)
 
-    def forward(self, features):
+    def forward(self, features, upsample=True):
         x_d0 = self.conv2(features[_SKIP_IN])
         x_d1 = self.up1(x_d0, features[8])
         x_d2 = self.up2(x_d1, features[6])
         x_feat = self.up3(x_d2, features[5])
         depth = self.depth_head(x_feat)
+        if not upsample and not self.dnet:
+            raise lib.MagnetError("DenseDepthDecoder: upsample=False is the stand-alone D-Net's form (dnet=True)")
         if self.dnet:
+            if not upsample:                                       # the raw pair that losses.DnetLoss fuses with the loss
+                return depth, self.mask_head(x_feat)
             return upsample_depth_via_mask(depth, self.mask_head(x_feat), self.downsample_ratio)
         return depth, x_feat
 
@@ -107,8 +112,9 @@ class DenseDepth(nn.Module):
         self.encoder = encoder
         self.decoder = DenseDepthDecoder(num_classes, downsample_ratio, dnet)
 
-    def forward(self, x):
-        return self.decoder(self.encoder(x))
+    def forward(self, x, upsample=True):
+        feats = self.encoder(x)
+        return self.decoder(feats) if upsample else self.decoder(feats, upsample=False)
 
 
 def gaussian_activation(out, magnet=True):
@@ -125,7 +131,8 @@ def gaussian_activation(out, magnet=True):
 class DNET(nn.Module):
     """models/DNET.py with output_type 'G' and DNET_architecture 'DenseDepth_BN': `DNET(args, encoder, dnet=False)` is MaGNet's
     D-Net, img -> ((N, 2, H/4, W/4) [mu, sigma], x_feat (N, 256, H/4, W/4)); `dnet=True` is the stand-alone D-Net of test_DNet.py /
-    train_DNet.py, img -> (N, 2, H, W) [mu, variance].  `encoder`: any module returning the reference's feature list
+    train_DNet.py, img -> (N, 2, H, W) [mu, variance], or with forward(img, upsample=False) the raw (depth, up_mask) of the torch modules
+    for losses.DnetLoss's fused tail.  `encoder`: any module returning the reference's feature list
     (EfficientNet-B5's, or magnet_amd.standin.StandinEncoder).
     backend: 'torch' (default) runs the modules as they are; 'hip' runs the decoder, the heads and the tail of an eval-mode forward on
     DNetMFMA (the caller's encoder stays a torch module); in .train() the torch forward runs, as MAGNET does for its D-Net."""
@@ -147,7 +154,13 @@ class DNET(nn.Module):
             check_decoder(self.d_net.decoder, standalone=dnet)
             self._runner = DNetMFMA(self.d_net.decoder)
 
-    def forward(self, img):
+    def forward(self, img, upsample=True):
+        if not upsample:
+            # the training form for losses.DnetLoss: the torch modules up to the two heads, on either backend; the upsampling, the
+            # activation and the loss follow fused, so the pair is returned raw: (depth (N,2,h,w) [mu, v], up_mask (N,144,h,w))
+            if not self.dnet:
+                raise lib.MagnetError("DNET: upsample=False is the stand-alone D-Net's form (dnet=True)")
+            return self.d_net(img, upsample=False)
         if self._runner is not None and not self.training:
             feats = self.d_net.encoder(img)
             return self._runner.run_standalone(feats) if self.dnet else self._runner.run(feats)

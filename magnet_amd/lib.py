@@ -174,6 +174,23 @@ class MagnetFnetLossArgs(ctypes.Structure):
                 ("B", ctypes.c_int32), ("D", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
+class MagnetDnetLossArgs(ctypes.Structure):
+    """Mirror of `struct MagnetDnetLossArgs` (include/magnet_hip.h)."""
+    _fields_ = [("depth", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("valid", ctypes.c_void_p),
+                ("mask_sb", ctypes.c_int64), ("mask_sc", ctypes.c_int64), ("mask_sy", ctypes.c_int64), ("mask_sx", ctypes.c_int64),
+                ("gm_sb", ctypes.c_int64), ("gm_sc", ctypes.c_int64), ("gm_sy", ctypes.c_int64), ("gm_sx", ctypes.c_int64),
+                ("pred", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("loss", ctypes.c_void_p), ("work", ctypes.c_void_p),
+                ("grad_loss", ctypes.c_void_p), ("grad_depth", ctypes.c_void_p), ("grad_mask", ctypes.c_void_p),
+                ("B", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("k", ctypes.c_int32)]
+
+
+class MagnetDnetNllArgs(ctypes.Structure):
+    """Mirror of `struct MagnetDnetNllArgs` (include/magnet_hip.h)."""
+    _fields_ = [("pred", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("sums", ctypes.c_void_p),
+                ("loss", ctypes.c_void_p), ("work", ctypes.c_void_p), ("grad_loss", ctypes.c_void_p), ("grad_pred", ctypes.c_void_p),
+                ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
 # (restype, argtypes) of every MAGNET_API declaration of include/magnet_hip.h, in header order; load() applies them all
 _C, _L, _F, _I, _P, _S = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER
 _PROTOS = {
@@ -227,6 +244,11 @@ _PROTOS = {
     "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_fnet_loss_backward": (_C, [_S(MagnetFnetLossArgs), _P]),
+    "magnet_dnet_loss_workspace": (_L, [_S(MagnetDnetLossArgs)]),
+    "magnet_dnet_loss_forward": (_C, [_S(MagnetDnetLossArgs), _P]),
+    "magnet_dnet_loss_backward": (_C, [_S(MagnetDnetLossArgs), _P]),
+    "magnet_dnet_nll_forward": (_C, [_S(MagnetDnetNllArgs), _P]),
+    "magnet_dnet_nll_backward": (_C, [_S(MagnetDnetNllArgs), _P]),
 }
 API_SYMBOLS = tuple(_PROTOS)
 
@@ -828,6 +850,108 @@ def fnet_loss_backward(raw_volume, d_center, gt, pred, m, rz, sums, grad_loss, m
     a.sums, a.grad_loss, a.grad_x = _dev(sums, "sums", torch.float64).data_ptr(), gl.data_ptr(), out.data_ptr()
     a.min_depth, a.max_depth = float(min_depth), float(max_depth)
     _launch("magnet_fnet_loss_backward", x, ctypes.byref(a))
+    return out
+
+
+def _dnet_loss_args(depth, mask, gt, valid, mask_layout, who):
+    """The checked operands of the fused DnetLoss tail and a MagnetDnetLossArgs with the inputs filled.  mask: NCHW (B,144,h,w)
+    logits of any strides (a channel-last plane passes as it is: only the element strides differ), or with mask_layout = (element
+    offset, sb, sc, sy, sx) contiguous fp32 storage addressed through it."""
+    d = _dev(depth, "depth", torch.float32)
+    if d.dim() != 4 or d.shape[1] != 2:
+        raise MagnetError(f"{who}: depth {tuple(d.shape)}, expected (B,2,h,w)")
+    B, _, h, w = d.shape
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype != torch.float32:
+        raise MagnetError(f"{who}: mask must be a float32 GPU tensor (magnet_amd has no CPU fallback)")
+    if mask_layout is None:
+        if tuple(mask.shape) != (B, 144, h, w):
+            raise MagnetError(f"{who}: mask shape {tuple(mask.shape)}, expected {(B, 144, h, w)}")
+        mask_layout = (0,) + tuple(mask.stride())
+    else:
+        _dev(mask, "mask", torch.float32)
+    g = _dev(gt, "gt", torch.float32)
+    v = _dev(valid, "valid", torch.bool)
+    if tuple(g.shape) != (B, 4 * h, 4 * w) or tuple(v.shape) != (B, 4 * h, 4 * w):
+        raise MagnetError(f"{who}: gt {tuple(g.shape)} / valid {tuple(v.shape)}, expected {(B, 4 * h, 4 * w)}")
+    if any(t.device != d.device for t in (mask, g, v)):
+        raise MagnetError(f"{who}: depth, mask, gt and valid must be on one device")
+    mo, sb, sc, sy, sx = mask_layout
+    a = MagnetDnetLossArgs(depth=d.data_ptr(), mask=mask.data_ptr() + 4 * mo, gt=g.data_ptr(), valid=v.data_ptr(), mask_sb=sb, mask_sc=sc,
+                           mask_sy=sy, mask_sx=sx, B=B, h=h, w=w, k=4)
+    return d, a
+
+
+def dnet_loss_forward(depth, mask, gt, valid, mask_layout=None, pred=True):
+    """The fused tail of the stand-alone D-Net's training step: depth (B,2,h,w) fp32 raw head output [mu, v], mask the 144 logits
+    per coarse pixel, gt (B,4h,4w) fp32, valid (B,4h,4w) bool -> (loss 0-d fp32, sums (2) float64: valid count and NLL sum,
+    pred (B,2,4h,4w) [mu, var] or None with pred=False).  Deterministic reduction; nothing waits for the device."""
+    d, a = _dnet_loss_args(depth, mask, gt, valid, mask_layout, "dnet_loss_forward")
+    B, _, h, w = d.shape
+    out = torch.empty((B, 2, 4 * h, 4 * w), dtype=torch.float32, device=d.device) if pred else None
+    sums = torch.empty(2, dtype=torch.float64, device=d.device)
+    loss = torch.empty((), dtype=torch.float32, device=d.device)
+    work = torch.empty(_workspace("magnet_dnet_loss_workspace", a) // 8 + 1, dtype=torch.float64, device=d.device)
+    a.pred, a.sums, a.loss, a.work = (out.data_ptr() if pred else None), sums.data_ptr(), loss.data_ptr(), work.data_ptr()
+    _launch("magnet_dnet_loss_forward", d, ctypes.byref(a))
+    return loss, sums, out
+
+
+def dnet_loss_backward(depth, mask, gt, valid, sums, grad_loss, mask_layout=None, grad_mask=None, grad_mask_layout=None):
+    """(grad_depth (B,2,h,w), grad_mask) of the fused tail, scaled by the device scalar grad_loss (read on the device: no host sync).
+    grad_mask: by default a fresh tensor of the mask's shape and strides; or a preallocated contiguous fp32 buffer addressed by
+    grad_mask_layout = (element offset, sb, sc, sy, sx).  All 144 channels of every pixel are written."""
+    d, a = _dnet_loss_args(depth, mask, gt, valid, mask_layout, "dnet_loss_backward")
+    gl = _dev(grad_loss.reshape(()), "grad_loss", torch.float32)
+    if grad_mask is None:
+        if mask_layout is not None:
+            raise MagnetError("dnet_loss_backward: mask_layout needs grad_mask and grad_mask_layout")
+        grad_mask = torch.empty_like(mask)                                  # preserve_format: the mask's own dense strides
+        if not grad_mask.is_contiguous() and not grad_mask.is_contiguous(memory_format=torch.channels_last):
+            grad_mask = torch.empty(mask.shape, dtype=torch.float32, device=d.device)
+        grad_mask_layout = (0,) + tuple(grad_mask.stride())
+    elif grad_mask_layout is None:
+        raise MagnetError("dnet_loss_backward: grad_mask needs grad_mask_layout")
+    else:
+        _dev(grad_mask, "grad_mask", torch.float32)
+    gd = torch.empty_like(d)
+    work = torch.empty(_workspace("magnet_dnet_loss_workspace", a) // 8 + 1, dtype=torch.float64, device=d.device)
+    go, gsb, gsc, gsy, gsx = grad_mask_layout
+    a.gm_sb, a.gm_sc, a.gm_sy, a.gm_sx = gsb, gsc, gsy, gsx
+    a.sums, a.work, a.grad_loss = _dev(sums, "sums", torch.float64).data_ptr(), work.data_ptr(), gl.data_ptr()
+    a.grad_depth, a.grad_mask = gd.data_ptr(), grad_mask.data_ptr() + 4 * go
+    _launch("magnet_dnet_loss_backward", d, ctypes.byref(a))
+    return gd, grad_mask
+
+
+def _dnet_nll_args(pred, gt, valid, who):
+    p = _dev(pred, "pred", torch.float32)
+    g = _dev(gt, "gt", torch.float32)
+    v = _dev(valid, "valid", torch.bool)
+    if p.dim() != 4 or p.shape[1] != 2 or tuple(g.shape) != (p.shape[0],) + tuple(p.shape[2:]) or tuple(v.shape) != tuple(g.shape):
+        raise MagnetError(f"{who}: shapes {tuple(p.shape)} {tuple(g.shape)} {tuple(v.shape)}, expected (B,2,H,W), (B,H,W), (B,H,W)")
+    B, _, H, W = p.shape
+    return p, MagnetDnetNllArgs(pred=p.data_ptr(), gt=g.data_ptr(), valid=v.data_ptr(), B=B, H=H, W=W)
+
+
+def dnet_nll_forward(pred, gt, valid):
+    """The reference's own DnetLoss call: pred (B,2,H,W) fp32 [mu, var], gt (B,H,W) fp32, valid (B,H,W) bool -> (loss 0-d fp32,
+    sums (2) float64: valid count, NLL sum); var < 1e-10 counts as 1e-10."""
+    p, a = _dnet_nll_args(pred, gt, valid, "dnet_nll_forward")
+    sums = torch.empty(2, dtype=torch.float64, device=p.device)
+    work = torch.empty(NLL_BLOCKS * 2, dtype=torch.float64, device=p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    a.sums, a.loss, a.work = sums.data_ptr(), loss.data_ptr(), work.data_ptr()
+    _launch("magnet_dnet_nll_forward", p, ctypes.byref(a))
+    return loss, sums
+
+
+def dnet_nll_backward(pred, gt, valid, sums, grad_loss):
+    """d loss / d pred (B,2,H,W) of dnet_nll_forward, scaled by the device scalar grad_loss; no var gradient where the clamp applied."""
+    p, a = _dnet_nll_args(pred, gt, valid, "dnet_nll_backward")
+    gl = _dev(grad_loss.reshape(()), "grad_loss", torch.float32)
+    out = torch.empty_like(p)
+    a.sums, a.grad_loss, a.grad_pred = _dev(sums, "sums", torch.float64).data_ptr(), gl.data_ptr(), out.data_ptr()
+    _launch("magnet_dnet_nll_backward", p, ctypes.byref(a))
     return out
 
 

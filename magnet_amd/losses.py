@@ -1,6 +1,8 @@
 """Training losses (reference utils/losses.py and the inline loss of train_FNet.py).  MagnetLoss is the loss of train_MaGNet.py:87-98
 on HIP kernels (csrc/train_bwd.hip); FnetLoss is the tail of the F-Net step, train_FNet.py:95-104 (softmax over the bins, expected
-depth, masked L1), fused on HIP kernels (csrc/fnet_loss.hip); DnetLoss is out of scope with the D-Net."""
+depth, masked L1), fused on HIP kernels (csrc/fnet_loss.hip); DnetLoss is the loss of train_DNet.py (utils/losses.py:8-24), either on
+the upsampled prediction as the reference calls it or fused with the stand-alone D-Net's tail behind the two head convolutions
+(learned convex upsampling, activation_G, NLL; csrc/dnet_loss.hip)."""
 from __future__ import annotations
 
 import torch
@@ -119,4 +121,92 @@ class FnetLoss(nn.Module):
         x = raw_volume if raw_volume.dtype == torch.float32 and raw_volume.is_contiguous() else raw_volume.float().contiguous()
         loss, pred = _FnetL1.apply(x, d_center_device(d_center, x.device), gt.reshape(B, h, w).contiguous(), self.min_depth, self.max_depth)
         self.pred_dmap = pred.unsqueeze(1)
+        return loss
+
+
+class _DnetNll(torch.autograd.Function):
+    """mean over the valid pixels of (mu - gt)^2 / (2 var) + 0.5 log var on pred (B,2,H,W) [mu, var], var clamped to 1e-10 (no var
+    gradient where clamped); backward reads grad_output on the device (no host sync)."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, valid):
+        p = pred.detach()
+        loss, sums = lib.dnet_nll_forward(p, gt, valid)
+        ctx.save_for_backward(p, gt, valid, sums)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        p, gt, valid, sums = ctx.saved_tensors
+        return lib.dnet_nll_backward(p, gt, valid, sums, grad_out.float().reshape(()).contiguous()), None, None
+
+
+class _DnetTail(torch.autograd.Function):
+    """The loss from the raw head output and the mask logits in one pass, and the detached (B,2,4h,4w) [mu, var]; the backward
+    recomputes the softmax from the logits (only the inputs and the two fp64 sums are saved), reads grad_output on the device and
+    returns the gradients of both inputs."""
+
+    @staticmethod
+    def forward(ctx, depth, up_mask, gt, valid):
+        d, m = depth.detach(), up_mask.detach()
+        loss, sums, pred = lib.dnet_loss_forward(d, m, gt, valid)
+        ctx.save_for_backward(d, m, gt, valid, sums)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_pred):
+        d, m, gt, valid, sums = ctx.saved_tensors
+        gd, gm = lib.dnet_loss_backward(d, m, gt, valid, sums, grad_out.float().reshape(()).contiguous())
+        return gd, gm, None, None
+
+
+class DnetLoss(nn.Module):
+    """Drop-in for the reference's utils.losses.DnetLoss (utils/losses.py:8-24): reads args.loss_fn (only 'gaussian' exists, as in the
+    reference).  forward(out, gt_depth (B,1,H,W), gt_depth_mask (B,1,H,W) bool) -> 0-d tensor, with
+      out = pred (B,2,H,W) [mu, var]: the reference's call on the upsampled prediction, or
+      out = (depth (B,2,h,w), up_mask (B,144,h,w)), what DNET(dnet=True)(img, upsample=False) returns: the tail of the step fused
+            (upsample_depth_via_mask, activation_G and the loss in one pass over the logits; H = 4h, W = 4w).  After such a call
+            `pred` is the detached (B,2,H,W) [mu, var] (visualize_D, the progress line).
+    Inputs that are not fp32 (the mask may be channel-last) are brought to fp32; GPU tensors only (no CPU fallback)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.loss_type = args.loss_fn
+        self.pred = None
+
+    def forward(self, out, gt_depth, gt_depth_mask):
+        if self.loss_type != "gaussian":
+            raise lib.MagnetError(f"DnetLoss: loss_fn {self.loss_type!r} is not supported (the reference has 'gaussian' only)")
+        fused = isinstance(out, (tuple, list))
+        if fused and len(out) != 2:
+            raise lib.MagnetError("DnetLoss: the fused form takes (depth, up_mask)")
+        tensors = [(out[0], "depth"), (out[1], "up_mask")] if fused else [(out, "pred")]
+        for t, name in tensors + [(gt_depth, "gt_depth"), (gt_depth_mask, "gt_depth_mask")]:
+            if not isinstance(t, torch.Tensor):
+                raise lib.MagnetError(f"DnetLoss: {name} must be a torch.Tensor, got {type(t).__name__}")
+        first = tensors[0][0]
+        if first.dim() != 4 or first.shape[1] != 2:
+            raise lib.MagnetError(f"DnetLoss: {tensors[0][1]} {tuple(first.shape)}, expected (B,2,{'h,w' if fused else 'H,W'})")
+        B, _, h, w = first.shape
+        H, W = (4 * h, 4 * w) if fused else (h, w)
+        if fused and tuple(out[1].shape) != (B, 144, h, w):
+            raise lib.MagnetError(f"DnetLoss: up_mask {tuple(out[1].shape)}, expected {(B, 144, h, w)} (9 taps x 4 x 4 sub-pixels)")
+        if tuple(gt_depth.shape) != (B, 1, H, W) or tuple(gt_depth_mask.shape) != (B, 1, H, W):
+            raise lib.MagnetError(f"DnetLoss: gt_depth {tuple(gt_depth.shape)} / gt_depth_mask {tuple(gt_depth_mask.shape)}, "
+                                  f"expected {(B, 1, H, W)}")
+        for t, name in tensors + [(gt_depth, "gt_depth"), (gt_depth_mask, "gt_depth_mask")]:
+            if not t.is_cuda:
+                raise lib.MagnetError(f"DnetLoss: {name} must be a GPU tensor (magnet_amd has no CPU fallback)")
+        gt = gt_depth.detach().float().reshape(B, H, W).contiguous()
+        valid = gt_depth_mask.detach().reshape(B, H, W).bool().contiguous()
+        f32 = lambda t: t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+        if not fused:
+            return _DnetNll.apply(f32(out), gt, valid)
+        mask = out[1]
+        if mask.dtype != torch.float32 or not (mask.is_contiguous() or mask.is_contiguous(memory_format=torch.channels_last)):
+            mask = mask.float().contiguous()
+        loss, self.pred = _DnetTail.apply(f32(out[0]), mask, gt, valid)
         return loss
