@@ -8,6 +8,7 @@ heads and tail run on the HIP path (DNET(dnet=True, backend='hip')), and the met
 
     python eval_dnet.py --frames 8 [--batch 1] [--backend hip] [--log out.txt]
     python eval_dnet.py --dataset_path ROOT --split split.txt [--dataset_format 7scenes]
+    python eval_dnet.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
 """
 import argparse
 import os
@@ -18,6 +19,7 @@ import torch
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
+from magnet_amd import evaluate as E  # noqa: E402
 from magnet_amd import metrics as M  # noqa: E402
 
 
@@ -72,6 +74,23 @@ def validate(model, args, test_loader, device):
         return metrics.get_value()
 
 
+def validate_sharded(model, args, test_loader, device, rank=0, world=1, with_count=False):
+    """validate() over this rank's share of the batches with the metric rows kept on the device: the model's (mu, variance) goes to the
+    metric kernel as it is (kind='variance': the clamp of utils.py:133 applies to the variance itself, no sqrt / square round trip),
+    nothing is read back per batch, and the rows of all ranks are gathered once and averaged in loader order."""
+    with torch.no_grad():
+        crop = "garg" if getattr(args, "garg_crop", False) else ("eigen" if getattr(args, "eigen_crop", False) else None)
+        table = M.MetricTable(device, args.min_depth, args.max_depth, crop=crop, kind="variance")
+
+        def step(t_data_dict):
+            img = t_data_dict["img"].to(device)
+            gt_dmap = t_data_dict["depth"].to(device)
+            table.append_pred(model(img), gt_dmap)                                  # (B, 2, H, W) [mu, variance]
+
+        metrics, n = E.evaluate(step, test_loader, table, rank, world)
+        return (metrics, n) if with_count else metrics
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=8); ap.add_argument("--batch", type=int, default=1)
@@ -85,11 +104,10 @@ def main():
                     help="folder layout; the split file has '<scene> <frame>' or '<scene> <sequence> <frame>' lines")
     ap.add_argument("--garg_crop", action="store_true", help="KITTI: evaluate inside the Garg ECCV16 window (test_DNet.py:56-58)")
     ap.add_argument("--eigen_crop", action="store_true", help="KITTI: evaluate inside the Eigen NIPS14 window (test_DNet.py:59-61)")
+    E.add_arguments(ap)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("eval_dnet.py needs an MI355X (no CPU fallback)")
+    rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.standin import make_dnet
-    device = torch.device("cuda:0")
     args = argparse.Namespace(min_depth=a.min_depth, max_depth=a.max_depth, garg_crop=a.garg_crop, eigen_crop=a.eigen_crop)
     model = make_dnet(dnet=True, backend=a.backend).to(device).eval()    # seeded weights unless the caller loads a checkpoint
     if a.dataset_path:
@@ -105,8 +123,15 @@ def main():
     else:
         loader = SyntheticFrames(a.frames, a.batch, a.input_height, a.input_width, seed=a.seed)
         title = "synthetic frames=%d D-Net backend=%s" % (a.frames, a.backend)
-    m = validate(model, args, loader, device)
-    M.log_metrics(a.log, m, title)
+    if not sharded:
+        M.log_metrics(a.log, validate(model, args, loader, device), title)
+        return
+    m, n = validate_sharded(model, args, loader, device, rank, world, with_count=True)
+    if rank == 0:
+        M.log_metrics(a.log, m, title)
+        if a.dump_metrics:
+            E.dump_metrics(a.dump_metrics, m, n)
+    E.finish()
 
 
 if __name__ == "__main__":

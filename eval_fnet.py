@@ -10,6 +10,7 @@ kernel takes (mu, sigma): sigma = 1 is passed and nll is reported as 0.0, as uti
 
     python eval_fnet.py --frames 8 [--batch 1] [--V 4] [--D 80] [--log out.txt]
     python eval_fnet.py --dataset_path ROOT --split split.txt [--dataset_format 7scenes]
+    python eval_fnet.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
 """
 import argparse
 import os
@@ -22,6 +23,7 @@ import torch.nn.functional as F
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
+from magnet_amd import evaluate as E  # noqa: E402
 from magnet_amd import metrics as M  # noqa: E402
 from magnet_amd.homography import expected_depth_F  # noqa: E402
 from magnet_amd.preprocess import data_preprocess_device  # noqa: E402
@@ -58,6 +60,30 @@ def validate(model, args, test_loader, device, d_center):
         return metrics.get_value()
 
 
+def validate_sharded(model, args, test_loader, device, d_center, rank=0, world=1, with_count=False):
+    """validate() over this rank's share of the batches with the metric rows kept on the device: the expected-depth map goes to the
+    metric kernel alone (kind=None: no plane of ones, nll 0.0 written by the kernel), nothing is read back per batch, and the rows of
+    all ranks are gathered once and averaged in loader order."""
+    with torch.no_grad():
+        crop = "garg" if getattr(args, "garg_crop", False) else ("eigen" if getattr(args, "eigen_crop", False) else None)
+        table = M.MetricTable(device, args.min_depth, args.max_depth, crop=crop, kind=None)
+
+        def step(batch):
+            data_array, cam_intrins = batch
+            cur_batch_size = data_array[0]["img"].size()[0]
+            ref_dat, nghbr_dats, nghbr_poses, is_valid = data_preprocess_device(data_array, cur_batch_size, device)
+            ref_img = ref_dat["img"].to(device)
+            gt_dmap = ref_dat["gt_dmap"].to(device)                                      # gt > max_depth is masked by the kernel
+            nghbr_imgs = torch.cat([d["img"].to(device) for d in nghbr_dats], dim=0)       # view-major
+            raw = model(ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, d_center, softmax=False)
+            pred_dmap = expected_depth_F(raw, d_center)
+            pred_dmap = F.interpolate(pred_dmap, size=[ref_img.shape[2], ref_img.shape[3]], mode="nearest")
+            table.append(pred_dmap, gt_dmap)
+
+        metrics, n = E.evaluate(step, test_loader, table, rank, world)
+        return (metrics, n) if with_count else metrics
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=8); ap.add_argument("--batch", type=int, default=1)
@@ -72,11 +98,10 @@ def main():
                     help="folder layout; the split file has '<scene> <frame>' or '<scene> <sequence> <frame>' lines")
     ap.add_argument("--garg_crop", action="store_true", help="KITTI: evaluate inside the Garg ECCV16 window (train_FNet.py:180-181)")
     ap.add_argument("--eigen_crop", action="store_true", help="KITTI: evaluate inside the Eigen NIPS14 window (train_FNet.py:182-183)")
+    E.add_arguments(ap)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("eval_fnet.py needs an MI355X (no CPU fallback)")
+    rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.magnet import MAGNET_F
-    device = torch.device("cuda:0")
     args = argparse.Namespace(min_depth=a.min_depth, max_depth=a.max_depth, garg_crop=a.garg_crop, eigen_crop=a.eigen_crop,
                               FNET_architecture="PSM-Net", FNET_feature_dim=64)
     torch.manual_seed(a.seed)
@@ -95,8 +120,15 @@ def main():
         from eval_synthetic import SyntheticWindows
         loader = SyntheticWindows((a.frames + a.batch - 1) // a.batch, a.batch, a.V, a.input_height, a.input_width, seed=a.seed)
         title = "synthetic frames=%d F-Net V=%d D=%d" % (a.frames, a.V, a.D)
-    m = validate(model, args, loader, device, d_center)
-    M.log_metrics(a.log, m, title)
+    if not sharded:
+        M.log_metrics(a.log, validate(model, args, loader, device, d_center), title)
+        return
+    m, n = validate_sharded(model, args, loader, device, d_center, rank, world, with_count=True)
+    if rank == 0:
+        M.log_metrics(a.log, m, title)
+        if a.dump_metrics:
+            E.dump_metrics(a.dump_metrics, m, n)
+    E.finish()
 
 
 if __name__ == "__main__":

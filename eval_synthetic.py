@@ -7,6 +7,7 @@ log_metrics line.  Differences: frames come from a seeded synthetic window gener
 the backbones are caller-provided (stub D-Net/F-Net here), and the metric reductions run on the device.
 
     python eval_synthetic.py --frames 8 --batch 2 [--D 5] [--iters 3] [--V 4] [--log out.txt]
+    python eval_synthetic.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
 """
 import argparse
 import os
@@ -17,6 +18,7 @@ import torch
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
+from magnet_amd import evaluate as E  # noqa: E402
 from magnet_amd import metrics as M  # noqa: E402
 from magnet_amd import synth  # noqa: E402
 from magnet_amd.magnet import MAGNET  # noqa: E402
@@ -69,6 +71,27 @@ def validate(model, args, test_loader, device):
         return metrics.get_value()
 
 
+def validate_sharded(model, args, test_loader, device, rank=0, world=1, with_count=False):
+    """validate() over this rank's share of the batches with the metric rows kept on the device (kind='sigma' on pred_list[-1]):
+    nothing is read back per batch, and the rows of all ranks are gathered once and averaged in loader order."""
+    with torch.no_grad():
+        crop = "garg" if getattr(args, "garg_crop", False) else ("eigen" if getattr(args, "eigen_crop", False) else None)
+        table = M.MetricTable(device, args.min_depth, args.max_depth, crop=crop, kind="sigma")
+
+        def step(batch):
+            data_array, cam_intrins = batch
+            cur_batch_size = data_array[0]["img"].size()[0]
+            ref_dat, nghbr_dats, nghbr_poses, is_valid = data_preprocess_device(data_array, cur_batch_size, device)
+            ref_img = ref_dat["img"].to(device)
+            gt_dmap = ref_dat["gt_dmap"].to(device)
+            nghbr_imgs = torch.cat([d["img"].to(device) for d in nghbr_dats], dim=0)       # view-major
+            pred_list = model(ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, mode="test")
+            table.append_pred(pred_list[-1], gt_dmap)
+
+        metrics, n = E.evaluate(step, test_loader, table, rank, world)
+        return (metrics, n) if with_count else metrics
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=8); ap.add_argument("--batch", type=int, default=2)
@@ -84,11 +107,10 @@ def main():
     ap.add_argument("--garg_crop", action="store_true", help="KITTI: evaluate inside the Garg ECCV16 window (test_MaGNet.py:67-68)")
     ap.add_argument("--eigen_crop", action="store_true", help="KITTI: evaluate inside the Eigen NIPS14 window (test_MaGNet.py:69-70)")
     ap.add_argument("--psmnet", action="store_true", help="use the PSMNet F-Net (matrix-core path) instead of the stub F-Net")
+    E.add_arguments(ap)
     a = ap.parse_args()
+    rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.standin import StubDNet, StubFNet, make_args, seeded_magnet_weights
-    if not torch.cuda.is_available():
-        raise SystemExit("eval_synthetic.py needs an MI355X (no CPU fallback)")
-    device = torch.device("cuda:0")
     args = make_args(D=a.D, iters=a.iters, dpv_h=a.input_height // 4, dpv_w=a.input_width // 4, V=a.V)
     args.min_depth, args.max_depth = a.min_depth, a.max_depth
     args.garg_crop, args.eigen_crop = a.garg_crop, a.eigen_crop
@@ -112,8 +134,15 @@ def main():
     else:
         loader = SyntheticWindows((a.frames + a.batch - 1) // a.batch, a.batch, a.V, a.input_height, a.input_width, nan_every=3)
         title = "synthetic frames=%d V=%d D=%d iters=%d" % (a.frames, a.V, a.D, a.iters)
-    m = validate(model, args, loader, device)
-    M.log_metrics(a.log, m, title)
+    if not sharded:
+        M.log_metrics(a.log, validate(model, args, loader, device), title)
+        return
+    m, n = validate_sharded(model, args, loader, device, rank, world, with_count=True)
+    if rank == 0:
+        M.log_metrics(a.log, m, title)
+        if a.dump_metrics:
+            E.dump_metrics(a.dump_metrics, m, n)
+    E.finish()
 
 
 if __name__ == "__main__":

@@ -21,7 +21,8 @@
  *     the library never synchronises the device and keeps no device memory between calls.  ONE exception to
  *     "never allocates": magnet_depth_metrics / magnet_depth_metrics_crop take their B x 64 x 13 doubles of
  *     partial sums from the stream-ordered pool (hipMallocAsync + hipFreeAsync on `stream`, inside the call);
- *     every other entry point works in caller-provided buffers only.
+ *     every other entry point works in caller-provided buffers only (magnet_depth_metrics_ex is the same reduction in a caller's
+ *     work buffer).
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls are
  *     asynchronous on that stream and re-entrant across streams.
  *   - Return value: 0 on success; >0 = MAGNET_E_* argument error; <0 = -(hipError_t).  Nothing is
@@ -361,6 +362,34 @@ MAGNET_API int magnet_depth_metrics(const float *pred, const float *gt, double *
 MAGNET_API int magnet_depth_metrics_crop(const float *pred, const float *gt, double *sums, int32_t B, int32_t H, int32_t W,
                                          float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1,
                                          void *stream);
+
+/* The evaluation loops' form of the same reductions (additive to v400): the two planes are addressed through strides, the second
+ * plane may hold the variance itself (test_DNet.py hands utils.compute_depth_errors the variance) or be absent (train_FNet.py's
+ * validate() has no uncertainty), the partial sums go to a caller-provided work buffer (no allocation), and the second stage can
+ * also write each frame's 12 metrics, so that an evaluation loop never reads anything back per batch. */
+enum {                                     /* MagnetDepthMetricsArgs.kind: what the `second` planes hold */
+    MAGNET_METRICS_SIGMA    = 0,           /* sigma: squared, then clamped at 1e-6; sums equal magnet_depth_metrics[_crop] to the bit */
+    MAGNET_METRICS_VARIANCE = 1,           /* the variance, clamped at 1e-6 (utils.py:133-134) */
+    MAGNET_METRICS_NONE     = 2            /* no second plane: sum 12 is 0 and the nll entry of every row is 0.0 */
+};
+typedef struct MagnetDepthMetricsArgs {
+    const float *mu;                       /* B planes of H x W (rows contiguous), mu_stride elements apart */
+    const float *second;                   /* sigma or variance planes, second_stride elements apart; NULL exactly when kind == NONE */
+    const float *gt;                       /* (B, H, W) contiguous */
+    int64_t      mu_stride, second_stride;
+    int32_t      B, H, W, kind;
+    float        min_depth, max_depth;
+    int32_t      crop, y0, y1, x0, x1;     /* crop != 0: evaluate inside rows [y0, y1) x columns [x0, x1) */
+    double      *sums;                     /* optional OUT (B, 16), as magnet_depth_metrics writes them */
+    double      *rows;                     /* optional OUT (B, 12): per-frame abs_rel abs_diff sq_rel rmse rmse_log irmse log_10 silog a1 a2 a3
+                                              nll, the fp64 expressions of magnet_amd/metrics.py's metrics_from_sums, each operation rounded
+                                              on its own; a frame without a valid pixel gives NaN (nll 0.0 under NONE) */
+    void        *work;                     /* magnet_depth_metrics_workspace(B) bytes of scratch */
+} MagnetDepthMetricsArgs;
+/* Bytes of `work` for B frames (B x 64 x 13 doubles); -(MAGNET_E_DIM) for B <= 0. */
+MAGNET_API int64_t magnet_depth_metrics_workspace(int32_t B);
+/* Two launches on `stream`, no allocation, no synchronisation; at least one of sums / rows must be given (8-byte aligned, as work). */
+MAGNET_API int magnet_depth_metrics_ex(const MagnetDepthMetricsArgs *args, void *stream);
 
 /* ---- training step of g_net / mask_head (train_MaGNet.py:87-98): loss, convex-upsampling backward, head backward, weight
  * gradients.  Additive to v400: new entry points with their own argument structs (zero-initialise, then fill).  Every sum is

@@ -22,6 +22,8 @@ hipError_t launch_space_to_depth(const uint16_t*, const uint16_t*, uint16_t*, ui
 hipError_t launch_avgpool_cl(const uint16_t*, const uint16_t*, int, int, int, int, int, int, int, uint16_t*, uint16_t*, hipStream_t);
 hipError_t launch_upsample_bilinear_cl(const float*, int, int, int, int, uint16_t*, uint16_t*, int, int, int, int, int, hipStream_t);
 hipError_t launch_depth_metrics(const float*, const float*, double*, int, int, int, float, float, int, int, int, int, hipStream_t);
+long long depth_metrics_workspace_bytes(int);
+hipError_t launch_depth_metrics_ex(const MagnetDepthMetricsArgs&, hipStream_t);
 hipError_t launch_make_rays(const double*, float*, int, int, int, hipStream_t);
 hipError_t launch_relative_poses(const double*, const double*, float*, int32_t*, int, int, hipStream_t);
 hipError_t launch_nll_forward(const MagnetNllArgs&, hipStream_t);
@@ -567,6 +569,29 @@ MAGNET_API int magnet_depth_metrics_crop(const float* pred, const float* gt, dou
         return fail(MAGNET_E_DIM, "magnet_depth_metrics_crop: bad arguments");
     hipError_t e = magnet::launch_depth_metrics(pred, gt, sums, B, H * W, W, min_depth, max_depth, y0, y1, x0, x1, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_depth_metrics_crop launch");
+}
+
+MAGNET_API int64_t magnet_depth_metrics_workspace(int32_t B) {
+    if (B <= 0) return -(int64_t)fail(MAGNET_E_DIM, "magnet_depth_metrics_workspace: bad B=%d", B);
+    return magnet::depth_metrics_workspace_bytes(B);
+}
+
+static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+MAGNET_API int magnet_depth_metrics_ex(const MagnetDepthMetricsArgs* a, void* stream) {
+    if (!a || !a->mu || !a->gt || !a->work || (!a->sums && !a->rows)) return fail(MAGNET_E_NULL, "magnet_depth_metrics_ex: NULL pointer");
+    if (a->B <= 0 || a->H <= 0 || a->W <= 0 || (long long)a->H * a->W > 0x7fffffffLL - 64 * 256 || !(a->max_depth > a->min_depth))
+        return fail(MAGNET_E_DIM, "magnet_depth_metrics_ex: bad arguments B=%d H=%d W=%d", a->B, a->H, a->W);
+    if (a->kind != MAGNET_METRICS_SIGMA && a->kind != MAGNET_METRICS_VARIANCE && a->kind != MAGNET_METRICS_NONE)
+        return fail(MAGNET_E_DIM, "magnet_depth_metrics_ex: unknown kind %d", a->kind);
+    if ((a->kind == MAGNET_METRICS_NONE) != (a->second == nullptr))
+        return fail(MAGNET_E_DIM, "magnet_depth_metrics_ex: second must be NULL exactly when kind is MAGNET_METRICS_NONE");
+    if (a->crop && (a->y0 < 0 || a->x0 < 0 || a->y1 > a->H || a->x1 > a->W || a->y1 <= a->y0 || a->x1 <= a->x0))
+        return fail(MAGNET_E_DIM, "magnet_depth_metrics_ex: empty or out-of-frame crop [%d,%d) x [%d,%d)", a->y0, a->y1, a->x0, a->x1);
+    if (!aligned8(a->sums) || !aligned8(a->rows) || !aligned8(a->work))
+        return fail(MAGNET_E_ALIGN, "magnet_depth_metrics_ex: sums / rows / work not 8-byte aligned");
+    hipError_t e = magnet::launch_depth_metrics_ex(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_depth_metrics_ex launch");
 }
 
 // ---- training step (train_bwd.hip) ----

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "warp_math.hpp"
+#include "../../include/magnet_hip.h"
 
 namespace magnet {
 
@@ -304,15 +305,20 @@ constexpr int MET_PARTS = 64;      // workgroups per frame in the first stage (f
 // -> 4 wave partials added in order) writing 13 partial sums; stage 2 = one wave per frame adding the MET_PARTS partials in
 // index order.  Optional evaluation window [cy0,cy1) x [cx0,cx1) = the reference's rectangular garg / eigen crops
 // (test_MaGNet.py:63-71); cy1 < 0 = whole frame.
-__global__ __launch_bounds__(256) void depth_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                             double* __restrict__ part, int HW, int W, float dmin, float dmax,
-                                                             int cy0, int cy1, int cx0, int cx1) {
+// KIND (MAGNET_METRICS_*) says what the second plane holds: SIGMA squares it, VARIANCE takes it as it is (both clamp the variance
+// at 1e-6), NONE reads no second plane and leaves sum 12 at 0.  The planes of frame b start at mu + b * mu_stride and
+// second + b * second_stride, so the two channels of one (B,2,H,W) tensor and two separate tensors are the same launch.
+template <int KIND>
+__global__ __launch_bounds__(256) void depth_metrics_kernel(const float* __restrict__ mu0, long long mu_stride,
+                                                             const float* __restrict__ second0, long long second_stride,
+                                                             const float* __restrict__ gt, double* __restrict__ part, int HW, int W,
+                                                             float dmin, float dmax, int cy0, int cy1, int cx0, int cx1) {
     const int b = blockIdx.y;
     double acc[13];
 #pragma unroll
     for (int i = 0; i < 13; ++i) acc[i] = 0.0;
-    const float* mu = pred + (size_t)b * 2 * HW;
-    const float* sg = mu + HW;
+    const float* mu = mu0 + (long long)b * mu_stride;
+    const float* sg = KIND == MAGNET_METRICS_NONE ? nullptr : second0 + (long long)b * second_stride;
     const float* g = gt + (size_t)b * HW;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += MET_PARTS * 256) {
         float gv = g[i];
@@ -329,13 +335,15 @@ __global__ __launch_bounds__(256) void depth_metrics_kernel(const float* __restr
         const double G = gv, P = pv, d = G - P;
         const double lg = log(G), lp = log(P);
         const double t = fmax(G / P, P / G);
-        double var = (double)sg[i] * (double)sg[i];
-        var = var < 1e-6 ? 1e-6 : var;                                 // utils.py:134
         acc[0] += 1.0; acc[1] += fabs(d); acc[2] += fabs(d) / G; acc[3] += d * d / G; acc[4] += d * d;
         acc[5] += (lg - lp) * (lg - lp); acc[6] += (lp - lg); acc[7] += fabs(log10(G) - log10(P));
         acc[8] += (1.0 / G - 1.0 / P) * (1.0 / G - 1.0 / P);
         acc[9] += (t < 1.25) ? 1.0 : 0.0; acc[10] += (t < 1.25 * 1.25) ? 1.0 : 0.0; acc[11] += (t < 1.25 * 1.25 * 1.25) ? 1.0 : 0.0;
-        acc[12] += 0.5 * (log(var) + 1.8378770664093453 + d * d / var);    // ln(2 pi)
+        if (KIND != MAGNET_METRICS_NONE) {
+            double var = KIND == MAGNET_METRICS_SIGMA ? (double)sg[i] * (double)sg[i] : (double)sg[i];   // test_DNet.py hands over the variance
+            var = var < 1e-6 ? 1e-6 : var;                             // utils.py:134
+            acc[12] += 0.5 * (log(var) + 1.8378770664093453 + d * d / var);    // ln(2 pi)
+        }
     }
     __shared__ double red[4][13];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -360,6 +368,43 @@ __global__ __launch_bounds__(64) void depth_metrics_final_kernel(const double* _
     sums[(size_t)b * MET_N + k] = v;
 }
 
+// Stage 2 of magnet_depth_metrics_ex: the same fixed-order final sum, and from it the frame's 12 metrics in metrics.METRIC_ORDER
+// (abs_rel abs_diff sq_rel rmse rmse_log irmse log_10 silog a1 a2 a3 nll) with exactly the fp64 expressions of
+// metrics.metrics_from_sums, every operation rounded on its own (this file is compiled with -ffp-contract=off and spells no
+// fma here): x / n, sqrt(x / n), silog = sqrt(max(s5 / n - (s6 / n) * (s6 / n), 0)) * 100.  n == 0: a row of NaN; without a
+// second plane the nll entry is 0.0 for every frame, the empty one included (what utils.compute_depth_errors(..., None) reports).
+__global__ __launch_bounds__(64) void depth_metrics_rows_kernel(const double* __restrict__ part, double* __restrict__ sums,
+                                                                 double* __restrict__ rows, int no_second) {
+    __shared__ double s[MET_N];
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k < MET_N) {
+        double v = 0.0;
+        if (k < 13)
+            for (int q = 0; q < MET_PARTS; ++q) v += part[((size_t)b * MET_PARTS + q) * 13 + k];
+        s[k] = v;
+        if (sums) sums[(size_t)b * MET_N + k] = v;
+    }
+    __syncthreads();
+    if (!rows || k >= 12) return;
+    const double n = s[0];
+    double r;
+    if (k == 11 && no_second) {
+        r = 0.0;
+    } else if (n <= 0.0) {
+        r = __builtin_nan("");
+    } else if (k == 7) {
+        const double mean_err = s[6] / n;
+        const double sq = mean_err * mean_err;
+        const double x = s[5] / n - sq;
+        r = sqrt(0.0 > x ? 0.0 : x) * 100.0;                           // Python's max(x, 0.0): x unless 0.0 > x
+    } else {
+        const int src = k == 0 ? 2 : k == 1 ? 1 : k == 2 ? 3 : k == 3 ? 4 : k == 4 ? 5 : k == 5 ? 8 : k == 6 ? 7 : k == 11 ? 12 : k + 1;
+        r = s[src] / n;
+        if (k >= 3 && k <= 5) r = sqrt(r);                             // rmse, rmse_log, irmse
+    }
+    rows[(size_t)b * 12 + k] = r;
+}
+
 // the partial sums live in a stream-ordered allocation (hipMallocAsync / hipFreeAsync): no state kept between calls, safe
 // with concurrent calls on different streams
 hipError_t launch_depth_metrics(const float* pred, const float* gt, double* sums, int B, int HW, int W, float dmin, float dmax,
@@ -367,12 +412,32 @@ hipError_t launch_depth_metrics(const float* pred, const float* gt, double* sums
     double* part = nullptr;
     hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)B * MET_PARTS * 13 * sizeof(double), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(depth_metrics_kernel, dim3(MET_PARTS, (unsigned)B), dim3(256), 0, s, pred, gt, part, HW, W, dmin, dmax,
-                       cy0, cy1, cx0, cx1);
+    hipLaunchKernelGGL(depth_metrics_kernel<MAGNET_METRICS_SIGMA>, dim3(MET_PARTS, (unsigned)B), dim3(256), 0, s, pred, 2LL * HW,
+                       pred + HW, 2LL * HW, gt, part, HW, W, dmin, dmax, cy0, cy1, cx0, cx1);
     hipLaunchKernelGGL(depth_metrics_final_kernel, dim3((unsigned)B), dim3(64), 0, s, part, sums);
     e = hipGetLastError();
     const hipError_t e2 = hipFreeAsync(part, s);
     return e != hipSuccess ? e : e2;
+}
+
+// magnet_depth_metrics_ex: the partial sums go to the caller's work buffer (no allocation), two launches, no synchronisation
+long long depth_metrics_workspace_bytes(int B) { return (long long)B * MET_PARTS * 13 * (long long)sizeof(double); }
+
+hipError_t launch_depth_metrics_ex(const MagnetDepthMetricsArgs& a, hipStream_t s) {
+    double* part = static_cast<double*>(a.work);
+    const int HW = a.H * a.W;
+    const int cy0 = a.crop ? a.y0 : 0, cy1 = a.crop ? a.y1 : -1, cx0 = a.crop ? a.x0 : 0, cx1 = a.crop ? a.x1 : 0;
+    const dim3 grid(MET_PARTS, (unsigned)a.B), block(256);
+#define MAGNET_MET_LAUNCH(KIND) \
+    hipLaunchKernelGGL(depth_metrics_kernel<KIND>, grid, block, 0, s, a.mu, (long long)a.mu_stride, a.second, \
+                       (long long)a.second_stride, a.gt, part, HW, a.W, a.min_depth, a.max_depth, cy0, cy1, cx0, cx1)
+    if (a.kind == MAGNET_METRICS_SIGMA) MAGNET_MET_LAUNCH(MAGNET_METRICS_SIGMA);
+    else if (a.kind == MAGNET_METRICS_VARIANCE) MAGNET_MET_LAUNCH(MAGNET_METRICS_VARIANCE);
+    else MAGNET_MET_LAUNCH(MAGNET_METRICS_NONE);
+#undef MAGNET_MET_LAUNCH
+    hipLaunchKernelGGL(depth_metrics_rows_kernel, dim3((unsigned)a.B), dim3(64), 0, s, part, a.sums, a.rows,
+                       a.kind == MAGNET_METRICS_NONE ? 1 : 0);
+    return hipGetLastError();
 }
 
 // ---- learned convex upsampling -------------------------------------------------------------------

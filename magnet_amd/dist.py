@@ -11,6 +11,8 @@ backend 'nccl' is RCCL on ROCm; 'gloo' is used by the CPU tests.
 from __future__ import annotations
 
 import os
+import sys
+import time
 
 import torch
 import torch.distributed as dist
@@ -157,3 +159,55 @@ def gather_floats(value: float, device=None) -> list:
 def barrier():
     if dist.is_available() and dist.is_initialized():
         dist.barrier()
+
+
+def spawn_ranks(n: int, argv, poll_s: float = 0.2, grace_s: float = 5.0) -> int:
+    """Run `python argv...` as n fresh child processes, one rank each (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment;
+    the child maps LOCAL_RANK to its GPU), as the reference spawns its DDP workers (train_MaGNet.py:323-338).  argv: the script path
+    followed by its arguments.  Rank 0's stdout passes through; every rank's stderr passes through tagged "[rank r]"; the stdout of
+    ranks > 0 is forwarded to stderr with the same tag.  ALL children are polled: the first one that exits non-zero (or is killed)
+    takes the others down (SIGTERM, SIGKILL after `grace_s`) - a dead rank must not leave the rest waiting in a collective until its
+    timeout - and its return code is returned.  This process keeps running its own program: the ranks are children, never a
+    replacement of it."""
+    import socket
+    import subprocess
+    import threading
+    sock = socket.socket(); sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]; sock.close()
+    procs, pumps = [], []
+
+    def pump(stream, tag):
+        for line in iter(stream.readline, ""):
+            sys.stderr.write(f"{tag} {line}" if line.strip() else line)
+        stream.close()
+
+    for r in range(n):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+        pr = subprocess.Popen([sys.executable] + list(argv), env=env, text=True, bufsize=1,
+                              stdout=None if r == 0 else subprocess.PIPE, stderr=subprocess.PIPE)
+        procs.append(pr)
+        for st in ([pr.stderr] if r == 0 else [pr.stderr, pr.stdout]):
+            t = threading.Thread(target=pump, args=(st, f"[rank {r}]"), daemon=True); t.start(); pumps.append(t)
+    rc, alive = 0, set(range(n))
+    while alive:
+        for r in sorted(alive):
+            code = procs[r].poll()
+            if code is None:
+                continue
+            alive.discard(r)
+            if code != 0 and rc == 0:
+                rc = code if code > 0 else 128 - code                  # killed by signal s -> 128 + s
+                sys.stderr.write(f"[launcher] rank {r} exited with {code}: stopping the other {len(alive)} rank(s)\n")
+                for o in alive:
+                    procs[o].terminate()
+                t_end = time.monotonic() + grace_s
+                while time.monotonic() < t_end and any(procs[o].poll() is None for o in alive):
+                    time.sleep(poll_s)
+                for o in alive:
+                    if procs[o].poll() is None:
+                        procs[o].kill()
+        if alive:
+            time.sleep(poll_s)
+    for t in pumps:
+        t.join(timeout=2.0)
+    return rc

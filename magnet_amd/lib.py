@@ -27,6 +27,7 @@ NLL_BLOCKS, NLL_MAX_ITER = 256, 16
 BN_BLOCKS = 256
 ACT_BASE, ACT_LEAKY_RELU = 0, 1
 TILING_FLAT, TILING_BM256 = 1, 2
+METRICS_SIGMA, METRICS_VARIANCE, METRICS_NONE = 0, 1, 2
 
 
 class MagnetError(RuntimeError):
@@ -80,6 +81,16 @@ class MagnetConvArgs(ctypes.Structure):
         ("gu_in", ctypes.c_void_p), ("gu_out", ctypes.c_void_p),
         ("in_sc", ctypes.c_void_p), ("w_sc", ctypes.c_void_p), ("sc_rows", ctypes.c_int64),
     ]
+
+
+class MagnetDepthMetricsArgs(ctypes.Structure):
+    """Mirror of `struct MagnetDepthMetricsArgs` (include/magnet_hip.h)."""
+    _fields_ = [("mu", ctypes.c_void_p), ("second", ctypes.c_void_p), ("gt", ctypes.c_void_p),
+                ("mu_stride", ctypes.c_int64), ("second_stride", ctypes.c_int64),
+                ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("kind", ctypes.c_int32),
+                ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float),
+                ("crop", ctypes.c_int32), ("y0", ctypes.c_int32), ("y1", ctypes.c_int32), ("x0", ctypes.c_int32), ("x1", ctypes.c_int32),
+                ("sums", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("work", ctypes.c_void_p)]
 
 
 class MagnetNllArgs(ctypes.Structure):
@@ -221,6 +232,8 @@ _PROTOS = {
     "magnet_upsample_depth_cl_n": (_C, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "magnet_depth_metrics": (_C, [_P, _P, _P, _I, _I, _F, _F, _P]),
     "magnet_depth_metrics_crop": (_C, [_P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P]),
+    "magnet_depth_metrics_workspace": (_L, [_I]),
+    "magnet_depth_metrics_ex": (_C, [_S(MagnetDepthMetricsArgs), _P]),
     "magnet_nll_loss_forward": (_C, [_S(MagnetNllArgs), _P]),
     "magnet_nll_loss_backward": (_C, [_S(MagnetNllArgs), _P]),
     "magnet_upsample_depth_backward": (_C, [_S(MagnetUpsampleBwdArgs), _P]),
