@@ -234,7 +234,8 @@ typedef struct MagnetConvArgs {
                                               of a wider buffer in place (pointer offset + in_ld) */
     const float *addend;                   /* optional fp32 (rows, addend_ld): added to the accumulator before bias / ReLU.
                                               Used to hoist the loop-invariant x_d3 part of G-Net's first layer out of
-                                              the refinement loop (models/MAGNET.py:151-168): W*[cost|x_d3] = Wc*cost + Wx*x_d3 */
+                                              the refinement loop (models/MAGNET.py:151-168): W*[cost|x_d3] = Wc*cost + Wx*x_d3.
+                                              Excludes add_hi / add_lo: a launch has ONE pre-bias term (both: MAGNET_E_DIM) */
     int32_t      addend_ld;                /* row pitch of addend (0 = cout_pad) */
     int32_t      dil;                      /* taps = 9: dilation (0 or 1 = none); the grid's border must be >= dil wide
                                               (F_psmnet.py:47 layer4).  taps = 4: the 2x2 window (-1,-1),(-1,0),(0,-1),(0,0)
@@ -242,7 +243,8 @@ typedef struct MagnetConvArgs {
     int32_t      out_ld;                   /* elements between output rows (0 = cout_pad): write a channel slice of a wider
                                               buffer in place (the 320-channel concatenation, F_psmnet.py:122) */
     const void  *add_hi, *add_lo;          /* optional split-bf16 (rows, add_ld) residual input added before bias / ReLU
-                                              (BasicBlock `out += x`, F_psmnet.py:27-33) */
+                                              (BasicBlock `out += x`, F_psmnet.py:27-33): hi + lo is formed in fp32 (exact: it is
+                                              the fp32 value the planes were split from).  Excludes `addend` (both: MAGNET_E_DIM) */
     int32_t      add_ld;
     int32_t      border_hp;                /* > 0: rows are positions of (image, border_hp, wp) grids with a `border_pad`-wide
                                               border; outputs at border positions are written as ZEROS (they are the next
@@ -331,7 +333,11 @@ MAGNET_API int magnet_conv1x1_chain(const void *in_hi, const void *in_lo, const 
 
 /* fp32 NCHW (N, C, h, w) (image stride `in_img_stride` elements, 0 = C*h*w) -> the interior of the split-bf16
  * padded channel-last buffer (N, h+2, w+2, ctot), channels [c_off, c_off+round_up(C,8)) (the round-up lanes are
- * written as zeros).  c_off % 8 == 0.  The border must have been zeroed once by the caller (never written). */
+ * written as zeros).  c_off % 8 == 0.  The border must have been zeroed once by the caller (never written).
+ * CONTRACT: whole 8-channel vectors are stored, so with C % 8 != 0 the channels [c_off+C, c_off+round_up(C,8)) of every interior
+ * position are OVERWRITTEN with +0 in both planes (C = 5: channels 5..7); a caller that packs several tensors side by side must
+ * place each at a multiple of 8 and pack in ascending order or leave the gap unused (ConvStackMFMA's in_map relies on the zeros:
+ * the first layer's weights are zero there, and 0 * 0 adds nothing).  No other element of the buffer is touched. */
 MAGNET_API int magnet_pack_split(const float *nchw, void *out_hi, void *out_lo, int32_t N, int32_t C, int32_t h,
                                  int32_t w, int32_t ctot, int32_t c_off, int64_t in_img_stride, void *stream);
 

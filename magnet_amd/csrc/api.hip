@@ -351,6 +351,8 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
     if ((a->add_hi != nullptr) != (a->add_lo != nullptr)) return fail(MAGNET_E_NULL, "magnet_conv_mfma: add_hi and add_lo come together");
     if (a->add_hi && (!aligned16(a->add_hi) || !aligned16(a->add_lo) || (p.add_ld % 8) != 0 || p.add_ld < a->cout_pad))
         return fail(MAGNET_E_ALIGN, "magnet_conv_mfma: add_hi/add_lo must be 16-byte aligned with add_ld >= cout_pad, a multiple of 8");
+    // the epilogue holds ONE pre-bias term per channel: with both, the addend would replace the residual (no caller passes both)
+    if (a->addend && a->add_hi) return fail(MAGNET_E_DIM, "magnet_conv_mfma: addend and add_hi/add_lo exclude each other (one pre-bias term per launch)");
     if (a->border_hp) {
         if (a->wp < 1 || a->border_pad < 0 || a->border_hp <= 2 * a->border_pad || a->wp <= 2 * a->border_pad ||
             (a->rows % ((long long)a->border_hp * a->wp)) != 0)
