@@ -9,18 +9,10 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import lib
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
-
-
-def split_bf16(x: torch.Tensor):
-    hi = x.to(torch.bfloat16)
-    lo = (x - hi.float()).to(torch.bfloat16)
-    return hi.contiguous(), lo.contiguous()
+from .planes import PackCache, pack_taps, planes, round_up, split_bf16, timed
 
 
 def mx_quant(v: torch.Tensor):
@@ -51,7 +43,14 @@ def _cout_pad(c):
         return 16
     if c == 144:
         return 144
-    return _round_up(c, 128)
+    return round_up(c, 128)
+
+
+def _buf(work, key, make):
+    """work[key], made on first use."""
+    if key not in work:
+        work[key] = make()
+    return work[key]
 
 
 class ConvStackMFMA:
@@ -87,8 +86,7 @@ class ConvStackMFMA:
         # on the CU, weights come straight from L2, LDS need stays at the K ring's 64 KB (2 workgroups per CU).
         self.fuse_epilogue = True
         self._chain = None
-        self._packed = None
-        self._key = None
+        self._cache = PackCache(lambda: [p for conv, _ in self.layers for p in conv.parameters()])
 
     def can_fuse_gauss(self, device):
         """True when run(..., gauss=...) is available: the reference's G-Net (3x3 + three 1x1, 2 outputs) with the fused epilogue on."""
@@ -104,34 +102,30 @@ class ConvStackMFMA:
     def cin_pad(self):
         c0 = self.layers[0][0].in_channels
         if self.in_map is None:
-            return _round_up(c0, 32)
-        return _round_up(max(d + n for _, n, d in self.in_map), 32)
+            return round_up(c0, 32)
+        return round_up(max(d + n for _, n, d in self.in_map), 32)
 
-    def _params_key(self, device):
-        return tuple((p.data_ptr(), p._version) for conv, _ in self.layers for p in conv.parameters()) + (str(device),)
+    def packed(self, device):
+        """Per layer the padded split-bf16 weights, the bias and the launch geometry; the repack also rebuilds (or drops) _chain."""
+        return self._cache.get(device, lambda: self._pack(device))
 
     @torch.no_grad()
-    def packed(self, device):
-        key = self._params_key(device)
-        if self._packed is not None and self._key == key:
-            return self._packed
+    def _pack(self, device):
         out = []
         cin_p = self.cin_pad()
         for li, (conv, relu) in enumerate(self.layers):
             W = conv.weight.detach().to(device=device, dtype=torch.float32)          # (Cout, Cin, kh, kw)
             cout, cin, kh, kw = W.shape
             cp = _cout_pad(cout)
-            Wp = torch.zeros((kh * kw, cp, cin_p), dtype=torch.float32, device=device)
-            Wt = W.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin)                   # (tap, Cout, Cin)
             if li == 0 and self.in_map is not None:
+                Wm = torch.zeros((cout, cin_p, kh, kw), dtype=torch.float32, device=device)
                 for src, n, dst in self.in_map:
-                    Wp[:, :cout, dst:dst + n] = Wt[:, :, src:src + n]
-            else:
-                Wp[:, :cout, :cin] = Wt
+                    Wm[:, dst:dst + n] = W[:, src:src + n]
+                W = Wm
+            hi, lo = (F.pad(t, (0, 0, 0, cp - cout)) for t in pack_taps(W, cin_p))   # (tap, cout_pad, cin_pad)
             bias = torch.zeros(cp, dtype=torch.float32, device=device)
             if conv.bias is not None:
                 bias[:cout] = conv.bias.detach().to(device=device, dtype=torch.float32)
-            hi, lo = split_bf16(Wp)
             out.append(dict(w_hi=hi, w_lo=lo, bias=bias, taps=kh * kw, cin=cin_p, cout=cout, cout_pad=cp, relu=relu))
             cin_p = cp                                                                 # next layer reads all padded channels
             if li + 1 < len(self.layers) and cp % 32 != 0:
@@ -145,56 +139,50 @@ class ConvStackMFMA:
                 w_hi=torch.cat([o["w_hi"].reshape(-1) for o in out[1:]]).contiguous(),
                 w_lo=torch.cat([o["w_lo"].reshape(-1) for o in out[1:]]).contiguous(),
                 bias=torch.cat([o["bias"] for o in out[1:]]).contiguous(), cout_pad=out[3]["cout_pad"])
-        self._packed, self._key = out, key
         return out
 
-    @torch.no_grad()
     def packed_mx(self, device):
         """First layer's weights in the fp16 + e4m3 operand format (conv_mfma.hip, WIN == 4 loop): (w_f16 (taps, cout_pad, cin), w_qr
         (taps, cout_pad, cin) int16 container, w_sc (taps, cin / 32, cout_pad) int32)."""
-        pk = self.packed(device)[0]
-        key = ("mx", self._key)
-        if getattr(self, "_mx_key", None) != key:
+        @torch.no_grad()
+        def build():
+            pk = self.packed(device)[0]
             w = (pk["w_hi"].float() + pk["w_lo"].float())                   # the 16-bit-mantissa weights the bf16x3 path multiplies by
             hi, qr, sc = split_mx(w)
-            self._mx, self._mx_key = dict(w_hi=hi, w_lo=qr, w_sc=sc.permute(0, 2, 1).contiguous()), key
-        return self._mx
+            return dict(w_hi=hi, w_lo=qr, w_sc=sc.permute(0, 2, 1).contiguous())
+        return self._cache.get(device, build, "mx")
 
-    @torch.no_grad()
     def packed_first_split(self, device, n_var, inv_off):
         """First layer split by input channels of the (padded) input buffer: channels [0, n_var) vary per refinement
         iteration (the cost volume), channels [inv_off, cin_pad) are loop-invariant (x_d3), everything between is padding.
         Returns (variable part, invariant part): variable = weights over buffer channels [0, round_up(n_var,32)) (+ bias,
         ReLU); invariant = weights over buffer channels [inv_off, cin_pad) only — its launch reads the buffer at a channel
         offset, so no MFMA work is spent on the cost channels' zero weights (no bias, no ReLU)."""
-        pk = self.packed(device)[0]
-        key = ("split", n_var, inv_off, self._key)
-        if getattr(self, "_split_key", None) == key:
-            return self._split
-        if inv_off % 32 or inv_off < n_var:
-            raise lib.MagnetError("packed_first_split: the invariant channels must start at a multiple of 32 behind the variable ones")
-        w = (pk["w_hi"].float() + pk["w_lo"].float())                       # exact: hi + lo is how the kernel sees them
-        cv = _round_up(n_var, 32)
-        wv = w[:, :, :cv].clone(); wv[:, :, n_var:] = 0
-        wi = w[:, :, inv_off:].clone()
-        # re-splitting hi + lo is exact (16 mantissa bits): hi, lo are recovered bit for bit
-        vh, vl = split_bf16(wv.contiguous()); ih, il = split_bf16(wi.contiguous())
-        var = dict(w_hi=vh, w_lo=vl, bias=pk["bias"], taps=pk["taps"], cin=cv, cout_pad=pk["cout_pad"], relu=pk["relu"])
-        inv = dict(w_hi=ih, w_lo=il, bias=torch.zeros_like(pk["bias"]), taps=pk["taps"], cin=pk["cin"] - inv_off,
-                   cout_pad=pk["cout_pad"], relu=False)
-        self._split_key, self._split = key, (var, inv)
-        return self._split
+        @torch.no_grad()
+        def build():
+            pk = self.packed(device)[0]
+            if inv_off % 32 or inv_off < n_var:
+                raise lib.MagnetError("packed_first_split: the invariant channels must start at a multiple of 32 behind the variable ones")
+            w = (pk["w_hi"].float() + pk["w_lo"].float())                       # exact: hi + lo is how the kernel sees them
+            cv = round_up(n_var, 32)
+            wv = w[:, :, :cv].clone(); wv[:, :, n_var:] = 0
+            wi = w[:, :, inv_off:].clone()
+            # re-splitting hi + lo is exact (16 mantissa bits): hi, lo are recovered bit for bit
+            vh, vl = split_bf16(wv.contiguous()); ih, il = split_bf16(wi.contiguous())
+            var = dict(w_hi=vh, w_lo=vl, bias=pk["bias"], taps=pk["taps"], cin=cv, cout_pad=pk["cout_pad"], relu=pk["relu"])
+            inv = dict(w_hi=ih, w_lo=il, bias=torch.zeros_like(pk["bias"]), taps=pk["taps"], cin=pk["cin"] - inv_off,
+                       cout_pad=pk["cout_pad"], relu=False)
+            return var, inv
+        return self._cache.get(device, build, "split", n_var, inv_off)
 
     def run_invariant(self, in_hi, in_lo, in_ld, rows, wp, work, n_var, inv_off):
         """Loop-invariant partial sums of the first layer: fp32 (rows, cout_pad), computed once per forward.  in_hi / in_lo:
         channel 0 of the buffer; the launch starts at channel inv_off."""
         _, inv = self.packed_first_split(in_hi.device, n_var, inv_off)
-        key = ("partial", rows, inv["cout_pad"])
-        if key not in work:
-            work[key] = torch.empty((rows, inv["cout_pad"]), dtype=torch.float32, device=in_hi.device)
+        out = _buf(work, ("partial", rows, inv["cout_pad"]), lambda: torch.empty((rows, inv["cout_pad"]), dtype=torch.float32, device=in_hi.device))
         lib.conv_mfma(in_hi[:, inv_off:], in_lo[:, inv_off:], in_ld, inv["cin"], inv["w_hi"], inv["w_lo"], inv["bias"], inv["taps"], wp,
-                      False, rows, out_f32=work[key])
-        return work[key]
+                      False, rows, out_f32=out)
+        return out
 
     def run(self, in_hi, in_lo, in_ld, rows, wp, work, first_addend=None, n_var=None, inv_off=None, upsample=None, gauss=None, mx=None):
         """in_hi/in_lo: bf16 views whose data_ptr is row 0, channel 0 of this stack's input; `work`: dict for cached
@@ -204,87 +192,52 @@ class ConvStackMFMA:
         gauss = (gmm_in, gmm_out): G-Net's stack only — the Gaussian update runs behind the head (returns (None, 16)); can_fuse_gauss().
         mx = (in_sc, sc_rows): the input planes are in the fp16 + e4m3 operand format (in_hi fp16, in_lo the e4m3 container, in_sc the
         E8M0 plane of lib.pack_mx); fused-epilogue stacks with at least 65 536 rows only."""
-        packs = self.packed(in_hi.device)
+        dev = in_hi.device
+        packs = self.packed(dev)
         if first_addend is not None:
             # first layer over the per-iteration channels only; the invariant part arrives as `first_addend`
-            packs = [self.packed_first_split(in_hi.device, n_var, inv_off)[0]] + list(packs[1:])
-        cur_hi, cur_lo, cur_ld = in_hi, in_lo, in_ld
+            packs = [self.packed_first_split(dev, n_var, inv_off)[0]] + list(packs[1:])
+        sink = ConvStackMFMA.event_sink
+
+        def out_f32(c):
+            return _buf(work, ("out", rows, c), lambda: torch.empty((rows, c), dtype=torch.float32, device=dev))
+
+        def flops(pk):
+            return 2.0 * rows * pk["cout_pad"] * pk["cin"] * pk["taps"]
+
         if self._chain is not None and self.fuse_epilogue:
             pk, ch = packs[0], self._chain
-            key = ("out", rows, ch["cout_pad"])
-            if key not in work and upsample is None and gauss is None:
-                work[key] = torch.empty((rows, ch["cout_pad"]), dtype=torch.float32, device=in_hi.device)
-            sink = ConvStackMFMA.event_sink
-            if sink is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                sink.append((e0, e1, 2.0 * rows * (pk["cout_pad"] * pk["cin"] * pk["taps"] + 128 * (256 + ch["cout_pad"])), pk["taps"]))
+            out = None if (upsample is not None or gauss is not None) else out_f32(ch["cout_pad"])
+            w_hi, w_lo, form = pk["w_hi"], pk["w_lo"], dict(addend=first_addend)
             if mx is not None:
                 if first_addend is not None:
                     raise lib.MagnetError("ConvStackMFMA.run: the fp16 + e4m3 format has no addend form")
-                wm = self.packed_mx(in_hi.device)
-                lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], wm["w_hi"], wm["w_lo"], pk["bias"], pk["taps"], wp, pk["relu"], rows,
-                              out_f32=None if (upsample is not None or gauss is not None) else work[key],
-                              tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss,
-                              mx=(mx[0], wm["w_sc"], mx[1]))
-            else:
-                lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp, pk["relu"], rows,
-                              out_f32=None if (upsample is not None or gauss is not None) else work[key], addend=first_addend,
-                              tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss)
-            if sink is not None:
-                e1.record()
-            return (None if (upsample is not None or gauss is not None) else work[key]), ch["cout_pad"]
+                wm = self.packed_mx(dev)
+                w_hi, w_lo, form = wm["w_hi"], wm["w_lo"], dict(mx=(mx[0], wm["w_sc"], mx[1]))
+            with timed(sink, flops(pk) + 2.0 * rows * 128 * (256 + ch["cout_pad"]), pk["taps"]):
+                lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], w_hi, w_lo, pk["bias"], pk["taps"], wp, pk["relu"], rows, out_f32=out,
+                              tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss, **form)
+            return out, ch["cout_pad"]
         if self._chain is not None and self.fuse_tail and first_addend is None:
-            pk = packs[0]
-            key = ("hid", 0, rows, 128)
-            if key not in work:
-                work[key] = (torch.empty((rows, 128), dtype=torch.bfloat16, device=in_hi.device),
-                             torch.empty((rows, 128), dtype=torch.bfloat16, device=in_hi.device))
-            oh, ol = work[key]
-            sink = ConvStackMFMA.event_sink
-            if sink is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                sink.append((e0, e1, 2.0 * rows * pk["cout_pad"] * pk["cin"] * pk["taps"], pk["taps"]))
-            lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
-                          pk["relu"], rows, out_hi=oh, out_lo=ol)
-            if sink is not None:
-                e1.record()
-            ch = self._chain
-            key = ("out", rows, ch["cout_pad"])
-            if key not in work:
-                work[key] = torch.empty((rows, ch["cout_pad"]), dtype=torch.float32, device=in_hi.device)
-            if sink is not None:
-                c0 = torch.cuda.Event(enable_timing=True); c1 = torch.cuda.Event(enable_timing=True)
-                c0.record()
-                sink.append((c0, c1, 2.0 * rows * 128 * (256 + ch["cout_pad"]), 1))
-            lib.conv1x1_chain(oh, ol, ch["w_hi"], ch["w_lo"], ch["bias"], work[key], rows, ch["cout_pad"])
-            if sink is not None:
-                c1.record()
-            return work[key], ch["cout_pad"]
-        for li, pk in enumerate(packs):
-            last = li == len(packs) - 1
-            sink = ConvStackMFMA.event_sink
-            if sink is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                sink.append((e0, e1, 2.0 * rows * pk["cout_pad"] * pk["cin"] * pk["taps"], pk["taps"]))
-            if last:
-                key = ("out", rows, pk["cout_pad"])
-                if key not in work:
-                    work[key] = torch.empty((rows, pk["cout_pad"]), dtype=torch.float32, device=in_hi.device)
+            pk, ch = packs[0], self._chain
+            oh, ol = _buf(work, ("hid", 0, rows, 128), lambda: planes(rows, 128, dev))
+            with timed(sink, flops(pk), pk["taps"]):
+                lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
+                              pk["relu"], rows, out_hi=oh, out_lo=ol)
+            out = out_f32(ch["cout_pad"])
+            with timed(sink, 2.0 * rows * 128 * (256 + ch["cout_pad"]), 1):
+                lib.conv1x1_chain(oh, ol, ch["w_hi"], ch["w_lo"], ch["bias"], out, rows, ch["cout_pad"])
+            return out, ch["cout_pad"]
+        cur_hi, cur_lo, cur_ld = in_hi, in_lo, in_ld
+        for li, pk in enumerate(packs[:-1]):
+            oh, ol = _buf(work, ("hid", li & 1, rows, pk["cout_pad"]), lambda: planes(rows, pk["cout_pad"], dev))
+            with timed(sink, flops(pk), pk["taps"]):
                 lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
-                              pk["relu"], rows, out_f32=work[key])
-                if sink is not None:
-                    e1.record()
-                return work[key], pk["cout_pad"]
-            key = ("hid", li & 1, rows, pk["cout_pad"])
-            if key not in work:
-                work[key] = (torch.empty((rows, pk["cout_pad"]), dtype=torch.bfloat16, device=in_hi.device),
-                             torch.empty((rows, pk["cout_pad"]), dtype=torch.bfloat16, device=in_hi.device))
-            oh, ol = work[key]
-            lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
-                          pk["relu"], rows, out_hi=oh, out_lo=ol, addend=first_addend if li == 0 else None)
-            if sink is not None:
-                e1.record()
+                              pk["relu"], rows, out_hi=oh, out_lo=ol, addend=first_addend if li == 0 else None)
             cur_hi, cur_lo, cur_ld = oh, ol, pk["cout_pad"]
+        pk = packs[-1]
+        out = out_f32(pk["cout_pad"])
+        with timed(sink, flops(pk), pk["taps"]):
+            lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
+                          pk["relu"], rows, out_f32=out)
+        return out, pk["cout_pad"]

@@ -30,15 +30,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import lib
-from .convnet import ConvStackMFMA, split_bf16
+from .convnet import ConvStackMFMA
+from .planes import PackCache, fold_bn, pack_taps, planes, round_up, timed
 
 # (block, skip feature index, skip channels, output channels) at downsample ratio 4 (D_dense_depth.py:130-135,176-180)
 _UP = (("up1", 8, 176, 1024), ("up2", 6, 64, 512), ("up3", 5, 40, 256))
 _SKIP_IN = 11                                              # x_block4: 2048 channels at 1/32 (the input of conv2)
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 class UpSampleBN(nn.Module):
@@ -206,14 +203,6 @@ def load_seeded_decoder(decoder: nn.Module, seed=0):
 # ======================================================================================================
 # inference on the matrix cores
 # ======================================================================================================
-def fold_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
-    """Conv2d (with bias) followed by eval-mode BatchNorm2d -> (weight, bias) in fp64: w * s, (b - mean) * s + beta, s = gamma / sqrt(var + eps)."""
-    w = conv.weight.detach().double()
-    b = conv.bias.detach().double() if conv.bias is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
-    s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-    return w * s.view(-1, 1, 1, 1), (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
-
-
 def check_decoder(decoder: nn.Module, standalone: bool = False):
     """MagnetError unless `decoder` is the reference's BatchNorm decoder at downsample ratio 4 (ours or the reference's class).
     standalone: also require the learned-upsampling mask head (3x3 256->128, 1x1 128->128, 1x1 128->144) of the stand-alone form."""
@@ -241,10 +230,6 @@ def check_decoder(decoder: nn.Module, standalone: bool = False):
                                   "1x1 128->144: 9 taps x 4 x 4 sub-pixels)")
 
 
-def _planes(rows, c, dev):
-    return (torch.zeros((rows, c), dtype=torch.bfloat16, device=dev), torch.zeros((rows, c), dtype=torch.bfloat16, device=dev))
-
-
 class DNetMFMA:
     """Inference runner for a DenseDepth_BN decoder at downsample ratio 4 (ours or the reference's `Decoder`), eval mode."""
 
@@ -266,38 +251,31 @@ class DNetMFMA:
         self._mask = None                                           # the mask head's stack: built by the first run_standalone()
         self._mask_work = {}
         self._packed = None
-        self._key = None
+        self._cache = PackCache(lambda: list(decoder.parameters()) + list(decoder.buffers()))
         self._bufs = {}
         self._bufs_sig = None
         self._head_work = {}
 
-    def _params_key(self, device):
-        d = self.decoder
-        return tuple((t.data_ptr(), t._version) for t in list(d.parameters()) + list(d.buffers())) + (str(device),)
+    def packed(self, device):
+        self._packed = self._cache.get(device, lambda: self._pack(device))
+        return self._packed
 
     @torch.no_grad()
-    def packed(self, device):
-        key = self._params_key(device)
-        if self._packed is not None and self._key == key:
-            return self._packed
+    def _pack(self, device):
         d = self.decoder
         P = {}
 
         def put(name, w, b, cin_pad):
-            cout, cin, kh, kw = w.shape
-            wp = torch.zeros((kh * kw, cout, cin_pad), dtype=torch.float64, device=w.device)
-            wp[:, :, :cin] = w.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin)
-            hi, lo = split_bf16(wp.float().to(device))
-            P[name] = (hi, lo, b.float().to(device).contiguous(), kh * kw, cin_pad)
+            hi, lo = pack_taps(w.to(device), cin_pad)
+            P[name] = (hi, lo, b.float().to(device).contiguous(), hi.shape[0], cin_pad)
 
         put("conv2", d.conv2.weight.detach().double(), d.conv2.bias.detach().double(), 2048)
         cin = 2048
         for name, _, skip_c, cout in _UP:
             net = getattr(d, name)._net
-            put(name + ".0", *fold_bn(net[0], net[1]), _round_up(cin + skip_c, 32))
+            put(name + ".0", *fold_bn(net[0], net[1]), round_up(cin + skip_c, 32))
             put(name + ".1", *fold_bn(net[3], net[4]), cout)
             cin = cout
-        self._packed, self._key = P, key
         return P
 
     def _conv(self, name, src, in_ld, wp, rows, dst=None, out_f32=None, out_ld=0, border=None, repad=0):
@@ -316,16 +294,10 @@ class DNetMFMA:
                 ok = t.is_contiguous() and ld == cout and t.numel() >= n_out * ld
             if not ok:
                 raise lib.MagnetError(f"DNetMFMA {name}: output {tuple(t.shape)} does not hold {n_out} rows of {cout} at pitch {ld}")
-        sink = DNetMFMA.event_sink
-        if sink is not None:
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, False, rows,
-                      out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1], out_f32=out_f32, out_ld=out_ld,
-                      border=border, repad=repad, leaky=None if name == "conv2" else self.slope)
-        if sink is not None:
-            e1.record()
-            sink.append((e0, e1, 2.0 * rows * cin * taps * hi.shape[1]))
+        with timed(DNetMFMA.event_sink, 2.0 * rows * cin * taps * cout):
+            lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, False, rows,
+                          out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1], out_f32=out_f32, out_ld=out_ld,
+                          border=border, repad=repad, leaky=None if name == "conv2" else self.slope)
 
     def _buffers(self, dev, N, dims):
         sig = (str(dev), N, dims)
@@ -338,16 +310,16 @@ class DNetMFMA:
         (h32, w32), (h16, w16), (h8, w8), (h4, w4) = dims
         r = lambda h, w: N * (h + 2) * (w + 2)
         b = self._bufs
-        b["x4"] = _planes(r(h32, w32), 2048, dev)
+        b["x4"] = planes(r(h32, w32), 2048, dev, zero=True)
         b["d0"] = torch.empty((N * h32 * w32, 2048), dtype=torch.float32, device=dev)
         cin = 2048
         for (name, _, skip_c, cout), (h, w) in zip(_UP, ((h16, w16), (h8, w8), (h4, w4))):
-            b[name + ".in"] = _planes(r(h, w), _round_up(cin + skip_c, 32), dev)     # [upsampled | skip | zero pad], zero border
-            b[name + ".mid"] = _planes(r(h, w), cout, dev)
+            b[name + ".in"] = planes(r(h, w), round_up(cin + skip_c, 32), dev, zero=True)     # [upsampled | skip | zero pad], zero border
+            b[name + ".mid"] = planes(r(h, w), cout, dev, zero=True)
             if name != "up3":
                 b[name + ".out"] = torch.empty((N * h * w, cout), dtype=torch.float32, device=dev)
             cin = cout
-        b["feat"] = _planes(r(h4, w4), 256, dev)
+        b["feat"] = planes(r(h4, w4), 256, dev, zero=True)
         return b
 
     def _features(self, features):
@@ -436,14 +408,8 @@ class DNetMFMA:
             if any(t.stride(0) != ld or t.shape[0] < n * img_rows or t.shape[1] < 256 for t in (fhi, flo)):
                 raise lib.MagnetError(f"DNetMFMA: depth-head input view {tuple(fhi.shape)} does not hold {n * img_rows} x 256 at pitch {ld}")
             work = self._head_work.setdefault(n, {})
-            sink = DNetMFMA.event_sink
-            if sink is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-            out, out_ld = self._head.run(fhi, flo, ld, n * img_rows, wp, work)
-            if sink is not None:
-                e1.record()
-                sink.append((e0, e1, 2.0 * n * img_rows * (9 * 256 * 128 + 128 * 128 + 128 * 2)))
+            with timed(DNetMFMA.event_sink, 2.0 * n * img_rows * (9 * 256 * 128 + 128 * 128 + 128 * 2)):
+                out, out_ld = self._head.run(fhi, flo, ld, n * img_rows, wp, work)
             lib.dnet_gauss_head(out, out_ld, n, h, w, 1, mono[first:first + n])
         if x_d3_out is not None:
             return mono[:n_ref], mono[n_ref:]
@@ -471,22 +437,12 @@ class DNetMFMA:
         sink = DNetMFMA.event_sink
         outs = []
         for stack, work, cout in ((self._head, self._head_work, 2), (self._mask, self._mask_work, 144)):
-            if sink is not None:
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-            outs.append(stack.run(feat[0], feat[1], 256, rows, wp, work.setdefault(N, {})))
-            if sink is not None:
-                e1.record()
-                sink.append((e0, e1, 2.0 * rows * (9 * 256 * 128 + 128 * 128 + 128 * cout)))
+            with timed(sink, 2.0 * rows * (9 * 256 * 128 + 128 * 128 + 128 * cout)):
+                outs.append(stack.run(feat[0], feat[1], 256, rows, wp, work.setdefault(N, {})))
         (head, head_ld), (mask, mask_ld) = outs
         out = torch.empty((N, 2, 4 * h, 4 * w), dtype=torch.float32, device=dev)
-        if sink is not None:
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        lib.dnet_upsample_gauss(head, head_ld, mask, mask_ld, N, h, w, out)
-        if sink is not None:
-            e1.record()
-            sink.append((e0, e1, 0.0))                                # not a convolution: bandwidth, no matrix-core work
+        with timed(sink, 0.0):                                        # not a convolution: bandwidth, no matrix-core work
+            lib.dnet_upsample_gauss(head, head_ld, mask, mask_ld, N, h, w, out)
         return out
 
     def __call__(self, features):

@@ -23,12 +23,31 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import lib
-from .convnet import split_bf16
+from .planes import PackCache, fold_bn, pack_s2d, pack_taps, planes, timed
+
+_pack_taps = pack_taps                                     # the name this packer had while it lived here; callers may still import it
 
 # (name, planes, blocks, stride, dilation) — F_psmnet.py:44-47
 _TRUNK = (("layer1", 32, 3, 1, 1), ("layer2", 64, 16, 2, 1), ("layer3", 128, 3, 1, 1), ("layer4", 128, 3, 1, 2))
 # (name, pooling window) in the order the reference concatenates them LAST-to-first (F_psmnet.py:50-64,122)
 _SPP = (("branch1", 64), ("branch2", 32), ("branch3", 16), ("branch4", 8))
+
+
+def convs(psm):
+    """Every convolution of a PSMNet in forward order: (name, Conv2d, its BatchNorm2d or None, True for the stride-2 3x3 layer
+    that runs as a 2x2 window over a space-to-depth input).  The names are the runners' pack keys; "firstconv.0" is the stem."""
+    for i in (0, 2, 4):
+        yield f"firstconv.{i}", *psm.firstconv[i], False
+    for name, _, _, stride, _ in _TRUNK:
+        for i, u in enumerate(getattr(psm, name)):
+            yield f"{name}.{i}.conv1", *u.conv1[0], i == 0 and stride == 2
+            yield f"{name}.{i}.conv2", *u.conv2, False
+            if u.downsample is not None:
+                yield f"{name}.{i}.downsample", *u.downsample, False
+    for name, _ in _SPP:
+        yield name, *getattr(psm, name)[1], False
+    yield "lastconv.0", *psm.lastconv[0], False
+    yield "lastconv.2", psm.lastconv[2], None, False
 
 
 def _conv_bn(cin, cout, k, stride=1, dilation=1):
@@ -99,33 +118,6 @@ class FNET(nn.Module):
 # ======================================================================================================
 # inference on the matrix cores
 # ======================================================================================================
-def _fold(seq: nn.Sequential):
-    """(Conv2d, BatchNorm2d) in eval mode -> fp32 weight (cout,cin,kh,kw), bias (cout), folded in fp64."""
-    conv, bn = seq[0], seq[1]
-    w = conv.weight.detach().double()
-    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-    return (w * scale.view(-1, 1, 1, 1)).float(), (bn.bias.detach().double() - bn.running_mean.detach().double() * scale).float()
-
-
-def _pack_taps(w: torch.Tensor):
-    """(cout, cin, kh, kw) fp32 -> split bf16 planes (kh*kw, cout, cin), cin contiguous."""
-    cout, cin, kh, kw = w.shape
-    return split_bf16(w.permute(2, 3, 0, 1).reshape(kh * kw, cout, cin).contiguous())
-
-
-def _pack_s2d(w: torch.Tensor):
-    """3x3 stride-2 pad-1 weights (cout, C, 3, 3) -> the equivalent 2x2-window weights over a space-to-depth input:
-    planes (4, cout, 4*C); tap (ty,tx) in {-1,0}^2 -> index (ty+1)*2+(tx+1); channel (py*2+px)*C + c."""
-    cout, C = w.shape[:2]
-    out = torch.zeros((4, cout, 4 * C), dtype=torch.float32, device=w.device)
-    k_of = {(-1, 1): 0, (0, 0): 1, (0, 1): 2}                       # (tap offset, phase) -> kernel index; (-1, 0) has none
-    for (ty, py), ky in k_of.items():
-        for (tx, px), kx in k_of.items():
-            ph = py * 2 + px
-            out[(ty + 1) * 2 + (tx + 1), :, ph * C:(ph + 1) * C] = w[:, :, ky, kx]
-    return split_bf16(out)
-
-
 class FNetMFMA:
     """Inference runner for a `PSMNet` (or the reference's own PSMNet instance: same attribute structure)."""
 
@@ -142,49 +134,32 @@ class FNetMFMA:
     def __init__(self, psm: nn.Module):
         self.psm = psm
         self._packed = None
-        self._key = None
+        self._cache = PackCache(lambda: list(psm.parameters()) + list(psm.buffers()))
         self._bufs = {}
         self._bufs_sig = None
         self._streams = {}
 
     # ---- weights ---------------------------------------------------------------------------------------------
-    def _params_key(self, device):
-        return tuple((t.data_ptr(), t._version) for t in list(self.psm.parameters()) + list(self.psm.buffers())) + (str(device),)
+    def packed(self, device):
+        self._packed = self._cache.get(device, lambda: self._pack(device))
+        return self._packed
 
     @torch.no_grad()
-    def packed(self, device):
-        key = self._params_key(device)
-        if self._packed is not None and self._key == key:
-            return self._packed
+    def _pack(self, device):
         P = {}
-
-        def put(name, w, b, s2d=False):
-            w = w.to(device); b = b.to(device)
-            hi, lo = (_pack_s2d if s2d else _pack_taps)(w)
-            P[name] = (hi, lo, b.contiguous(), w.shape[0])
-
-        psm = self.psm
-        w0, b0 = _fold(psm.firstconv[0])
-        P["stem"] = (w0.to(device).reshape(32, 27).contiguous(), b0.to(device).contiguous())
-        put("firstconv.2", *_fold(psm.firstconv[2]))
-        put("firstconv.4", *_fold(psm.firstconv[4]))
-        for name, planes, blocks, stride, dilation in _TRUNK:
-            layer = getattr(psm, name)
-            for i in range(blocks):
-                u = layer[i]
-                put(f"{name}.{i}.conv1", *_fold(u.conv1[0]), s2d=(i == 0 and stride == 2))
-                put(f"{name}.{i}.conv2", *_fold(u.conv2))
-                if u.downsample is not None:
-                    put(f"{name}.{i}.downsample", *_fold(u.downsample))
-        for name, _ in _SPP:
-            put(name, *_fold(getattr(psm, name)[1]))
-        put("lastconv.0", *_fold(psm.lastconv[0]))
-        wl = psm.lastconv[2].weight.detach().float()
-        put("lastconv.2", wl, torch.zeros(wl.shape[0]))
-        self.feature_dim = wl.shape[0]
+        for name, conv, bn, s2d in convs(self.psm):
+            if bn is None:
+                w, b = conv.weight.detach().float(), torch.zeros(conv.out_channels)
+            else:
+                w, b = (t.float() for t in fold_bn(conv, bn))
+            w, b = w.to(device), b.to(device).contiguous()
+            if name == "firstconv.0":
+                P["stem"] = (w.reshape(32, 27).contiguous(), b)
+            else:
+                P[name] = (*(pack_s2d if s2d else pack_taps)(w), b, w.shape[0])
+        self.feature_dim = P["lastconv.2"][3]
         if self.feature_dim not in (16, 32, 64, 128):
             raise lib.MagnetError(f"FNetMFMA: feature_dim {self.feature_dim} unsupported (16, 32, 64, 128)")
-        self._packed, self._key = P, key
         return P
 
     # ---- activations -----------------------------------------------------------------------------------------
@@ -202,33 +177,23 @@ class FNetMFMA:
         if H4 < 64 or W4 < 64:
             raise lib.MagnetError(f"FNetMFMA: input {H}x{W} too small for the 64x64 pooling branch (needs H/4, W/4 >= 64)")
         rows_a, rows_b = N * (H2 + 2) * (W2 + 2), N * (H4 + 4) * (W4 + 4)
-
-        def planes(rows, c):
-            return (torch.zeros((rows, c), dtype=torch.bfloat16, device=dev), torch.zeros((rows, c), dtype=torch.bfloat16, device=dev))
-
         b = {"dims": (H2, W2, H4, W4, rows_a, rows_b),
-             "A": [planes(rows_a, 32) for _ in range(3)],
-             "S": planes(rows_b, 128),
-             "B": [planes(rows_b, 64) for _ in range(3)],
-             "C": [planes(rows_b, 128) for _ in range(3)],
-             "cat": planes(rows_b, 320),
-             "pool": {k: (planes(N * (H4 // k) * (W4 // k), 128),
+             "A": [planes(rows_a, 32, dev, zero=True) for _ in range(3)],
+             "S": planes(rows_b, 128, dev, zero=True),
+             "B": [planes(rows_b, 64, dev, zero=True) for _ in range(3)],
+             "C": [planes(rows_b, 128, dev, zero=True) for _ in range(3)],
+             "cat": planes(rows_b, 320, dev, zero=True),
+             "pool": {k: (planes(N * (H4 // k) * (W4 // k), 128, dev, zero=True),
                           torch.empty((N * (H4 // k) * (W4 // k), 32), dtype=torch.float32, device=dev)) for _, k in _SPP}}
         self._bufs[key] = b
         return b
 
     def _conv(self, name, src, in_ld, cin, taps, wp, rows, relu, dst=None, out_ld=0, add=None, border=None, dil=0, **kw):
         hi, lo, bias, cout = self._packed[name]
-        sink = FNetMFMA.event_sink
-        if sink is not None:
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, relu, rows,
-                      out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1],
-                      out_ld=out_ld, add=add, border=border, dil=dil, **kw)
-        if sink is not None:
-            e1.record()
-            sink.append((e0, e1, 2.0 * rows * cin * taps * cout))
+        with timed(FNetMFMA.event_sink, 2.0 * rows * cin * taps * cout):
+            lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, relu, rows,
+                          out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1],
+                          out_ld=out_ld, add=add, border=border, dil=dil, **kw)
 
     @torch.no_grad()
     def run(self, img: torch.Tensor, n_ref: int | None = None, feat_dtype="fp32"):

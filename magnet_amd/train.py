@@ -14,14 +14,16 @@ copy) + 16 x 4 B (head output)) per iteration; mask head P x (3 x 128 x 4 B + 14
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 
 from . import lib
-from .convnet import ConvStackMFMA, split_bf16
+from .convnet import ConvStackMFMA
+from .planes import planes, round_up, split_bf16
 
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
+# the zero-bordered channel-last grid one stack runs on: B frames of (h+2) x (w+2) = wp rows
+_Grid = namedtuple("_Grid", "B h w rows wp dev")
 
 
 def _split_t(wt_list):
@@ -48,8 +50,60 @@ def _params(model):
     return out
 
 
-def _planes(rows, c, dev):
-    return (torch.empty((rows, c), dtype=torch.bfloat16, device=dev), torch.empty((rows, c), dtype=torch.bfloat16, device=dev))
+def _stack_forward(grid, packs, x, in_ld, first=None, addend=None):
+    """One packed stack (3x3 + three 1x1) layer by layer on the planes x = (hi, lo) of pitch in_ld: ([h1, h2, h3] post-ReLU split
+    planes, fp32 output (rows, cout_pad)).  first: the pack that takes the first layer's place; addend: fp32 (rows, 128) added to it."""
+    rows, wp, dev = grid.rows, grid.wp, grid.dev
+    hs = []
+    for li in range(3):
+        pk = first if li == 0 and first is not None else packs[li]
+        o = planes(rows, 128, dev)
+        lib.conv_mfma(x[0], x[1], in_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp, True, rows,
+                      out_hi=o[0], out_lo=o[1], addend=addend if li == 0 else None)
+        hs.append(o)
+        x, in_ld = o, 128
+    pk = packs[3]
+    out = torch.empty((rows, pk["cout_pad"]), dtype=torch.float32, device=dev)
+    lib.conv_mfma(x[0], x[1], 128, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], 1, wp, False, rows, out_f32=out)
+    return hs, out
+
+
+def _dgrad(grid, dout, k0, wt, hs, acc=None, acc_mode=0, acc_planes=None, gauss=None):
+    """The one magnet_head_dgrad launch of a stack: (dout, dh3, dh2, dh1) split planes."""
+    rows, dev = grid.rows, grid.dev
+    dout_p = planes(rows, k0, dev)
+    d3, d2, d1 = planes(rows, 128, dev), planes(rows, 128, dev), planes(rows, 128, dev)
+    a = lib.MagnetHeadDgradArgs(
+        dout=dout.data_ptr() if dout is not None else None, k0=k0, wt_hi=wt[0].data_ptr(), wt_lo=wt[1].data_ptr(),
+        h3_hi=hs[2][0].data_ptr(), h2_hi=hs[1][0].data_ptr(), h1_hi=hs[0][0].data_ptr(),
+        dout_hi=dout_p[0].data_ptr(), dout_lo=dout_p[1].data_ptr(), dh3_hi=d3[0].data_ptr(), dh3_lo=d3[1].data_ptr(),
+        dh2_hi=d2[0].data_ptr(), dh2_lo=d2[1].data_ptr(), dh1_hi=d1[0].data_ptr(), dh1_lo=d1[1].data_ptr(),
+        acc=acc.data_ptr() if acc is not None else None,
+        acc_hi=acc_planes[0].data_ptr() if acc_planes is not None else None,
+        acc_lo=acc_planes[1].data_ptr() if acc_planes is not None else None, acc_mode=acc_mode,
+        B=grid.B, h=grid.h, w=grid.w, rows=rows)
+    if gauss is not None:
+        gg, out, gmm_in = gauss
+        gg = gg.contiguous()
+        a.grad_gmm, a.gnet_out, a.gmm_in, a.gnet_ld = gg.data_ptr(), out.data_ptr(), gmm_in.data_ptr(), out.shape[1]
+    lib.head_dgrad(a, dev)
+    return dout_p, d3, d2, d1
+
+
+def _tail_wgrads(grid, dh, hs, g, cout_last, accumulate):
+    """Weight / bias gradients of the three 1x1 layers; g = [W1, b1, W2, b2, W3, b3, W4, b4] of the stack."""
+    rows, wp = grid.rows, grid.wp
+    dout_p, d3, d2, _ = dh
+    lib.wgrad(dout_p[0], dout_p[1], hs[2][0], hs[2][1], rows, wp, 1, round_up(cout_last, 8), 128, g[6], cout_valid=cout_last,
+              grad_b=g[7], accumulate=accumulate)
+    lib.wgrad(d3[0], d3[1], hs[1][0], hs[1][1], rows, wp, 1, 128, 128, g[4], grad_b=g[5], accumulate=accumulate)
+    lib.wgrad(d2[0], d2[1], hs[0][0], hs[0][1], rows, wp, 1, 128, 128, g[2], grad_b=g[3], accumulate=accumulate)
+
+
+def _stack_backward(grid, dout, k0, wt, hs, g, x, cin, cin_dst, cout_last):
+    dh = _dgrad(grid, dout, k0, wt, hs)
+    _tail_wgrads(grid, dh, hs, g, cout_last, accumulate=False)
+    lib.wgrad(dh[3][0], dh[3][1], x[0], x[1], grid.rows, grid.wp, 9, 128, cin, g[0], cin_dst=cin_dst, grad_b=g[1])
 
 
 class _Runner:
@@ -67,8 +121,9 @@ class _Runner:
         _, _, ctot, Dp = m.gnet_input_buffer(B, h, w, dev)          # builds the stacks (the cached inference buffer is not used)
         g_stack, m_stack = m._stacks
         rows, wp = B * (h + 2) * (w + 2), w + 2
-        cv = _round_up(D, 32)
+        cv = round_up(D, 32)
         self.B, self.h, self.w, self.D, self.Dp, self.ctot, self.rows, self.wp, self.cv = B, h, w, D, Dp, ctot, rows, wp, cv
+        grid = self.grid = _Grid(B, h, w, rows, wp, dev)
         # a fresh input buffer per forward: the backward reads its x_d3 channels, whatever runs in between
         gin_hi = torch.zeros((rows, ctot), dtype=torch.bfloat16, device=dev)
         gin_lo = torch.zeros((rows, ctot), dtype=torch.bfloat16, device=dev)
@@ -99,44 +154,20 @@ class _Runner:
                 self.matcher(ref_gmm=pred_list[-1], k_list=m.k_list, out=cost_nchw)
                 lib.pack_split(cost_nchw, gin_hi, gin_lo, ctot, 0)
             it = {"cost": (gin_hi[:, :cv].clone(), gin_lo[:, :cv].clone()), "gmm_in": pred_list[-1]}
-            h1 = _planes(rows, 128, dev)
-            lib.conv_mfma(gin_hi, gin_lo, ctot, var["cin"], var["w_hi"], var["w_lo"], var["bias"], var["taps"], wp, True, rows,
-                          out_hi=h1[0], out_lo=h1[1], addend=partial)                                    # MAGNET.py:51-56,62
-            hs = [h1]
-            for li in (1, 2):
-                pk = gp[li]
-                o = _planes(rows, 128, dev)
-                lib.conv_mfma(hs[-1][0], hs[-1][1], 128, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], 1, wp, True, rows,
-                              out_hi=o[0], out_lo=o[1])
-                hs.append(o)
-            pk = gp[3]
-            out = torch.empty((rows, pk["cout_pad"]), dtype=torch.float32, device=dev)
-            lib.conv_mfma(hs[-1][0], hs[-1][1], 128, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], 1, wp, False, rows, out_f32=out)
-            it["h"], it["out"] = hs, out
-            pred_list.append(lib.gaussian_update_cl(out, pk["cout_pad"], pred_list[-1], h, w))           # MAGNET.py:60-69
+            it["h"], it["out"] = _stack_forward(grid, gp, self.gin, ctot, first=var, addend=partial)  # MAGNET.py:51-56,62
+            pred_list.append(lib.gaussian_update_cl(it["out"], gp[3]["cout_pad"], pred_list[-1], h, w))  # MAGNET.py:60-69
             self.iters.append(it)
         # mask head (MAGNET.py:172) on the x_d3 channels of the same buffer
-        hs = []
-        cur = (gin_hi[:, Dp:], gin_lo[:, Dp:], ctot)
-        for li in range(3):
-            pk = mp[li]
-            o = _planes(rows, 128, dev)
-            lib.conv_mfma(cur[0], cur[1], cur[2], pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp, True, rows,
-                          out_hi=o[0], out_lo=o[1])
-            hs.append(o)
-            cur = (o[0], o[1], 128)
-        pk = mp[3]
-        mask = torch.empty((rows, pk["cout_pad"]), dtype=torch.float32, device=dev)
-        lib.conv_mfma(cur[0], cur[1], 128, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], 1, wp, False, rows, out_f32=mask)
-        self.mh, self.mask, self.mask_ld = hs, mask, pk["cout_pad"]
+        self.mh, self.mask = _stack_forward(grid, mp, (gin_hi[:, Dp:], gin_lo[:, Dp:]), ctot)
+        self.mask_ld = mp[3]["cout_pad"]
         self.preds = pred_list[1:]
-        return lib.upsample_depth_cl_n(self.preds, mask, pk["cout_pad"])                                # MAGNET.py:173
+        return lib.upsample_depth_cl_n(self.preds, self.mask, self.mask_ld)                         # MAGNET.py:173
 
     @torch.no_grad()
     def backward(self, grad_ups):
         m = self.model
-        B, h, w, D, Dp, rows, wp, cv = self.B, self.h, self.w, self.D, self.Dp, self.rows, self.wp, self.cv
-        dev = self.mask.device
+        grid, D, Dp, cv = self.grid, self.D, self.Dp, self.cv
+        B, h, w, rows, wp, dev = grid
         gin_hi, gin_lo = self.gin
         params = _params(m)
         grads = [torch.zeros(p.shape, dtype=torch.float32, device=dev) for p in params]
@@ -151,18 +182,18 @@ class _Runner:
                                                  grad_mask_layout=((wp + 1) * mk, pg * mk, 1, wp * mk, mk))
         # ---- mask head ----
         mwt = _transposed(self.mp, mk)
-        self._stack_backward(dmask, mk, mwt, self.mh, grads[8:16], (gin_hi[:, Dp:], gin_lo[:, Dp:]), 256, 0,
-                             m.mask_head[6].out_channels)
+        _stack_backward(grid, dmask, mk, mwt, self.mh, grads[8:16], (gin_hi[:, Dp:], gin_lo[:, Dp:]), 256, 0,
+                        m.mask_head[6].out_channels)
         # ---- G-Net, iteration by iteration (each iteration's backward is local: MAGNET.py:168 detaches pred_list[-1]) ----
         gwt = _transposed(self.gp, 32)
         acc = torch.empty((rows, 128), dtype=torch.float32, device=dev)
-        acc_planes = _planes(rows, 128, dev)
+        acc_planes = planes(rows, 128, dev)
         n = len(self.iters)
         for i, it in enumerate(self.iters):
             last = i == n - 1
-            dh = self._dgrad(None, 32, gwt, it["h"], acc=acc, acc_mode=1 if i == 0 else 2, acc_planes=acc_planes if last else None,
-                             gauss=(d_preds[i], it["out"], it["gmm_in"]))
-            self._tail_wgrads(dh, it["h"], grads[0:8], cout_last=2, accumulate=i > 0)
+            dh = _dgrad(grid, None, 32, gwt, it["h"], acc=acc, acc_mode=1 if i == 0 else 2, acc_planes=acc_planes if last else None,
+                        gauss=(d_preds[i], it["out"], it["gmm_in"]))
+            _tail_wgrads(grid, dh, it["h"], grads[0:8], cout_last=2, accumulate=i > 0)
             # first layer, cost channels (buffer channels [0, D) -> nn.Conv2d input channels [0, D)), per iteration
             lib.wgrad(dh[3][0], dh[3][1], it["cost"][0], it["cost"][1], rows, wp, 9, 128, cv, grads[0], cin_dst=0, cin_valid=D,
                       accumulate=i > 0)
@@ -170,40 +201,6 @@ class _Runner:
         lib.wgrad(acc_planes[0], acc_planes[1], gin_hi[:, Dp:], gin_lo[:, Dp:], rows, wp, 9, 128, 256, grads[0], cin_dst=D,
                   grad_b=grads[1])
         return grads
-
-    def _dgrad(self, dout, k0, wt, hs, acc=None, acc_mode=0, acc_planes=None, gauss=None):
-        rows, dev = self.rows, self.mask.device
-        dout_p = _planes(rows, k0, dev)
-        d3, d2, d1 = _planes(rows, 128, dev), _planes(rows, 128, dev), _planes(rows, 128, dev)
-        a = lib.MagnetHeadDgradArgs(
-            dout=dout.data_ptr() if dout is not None else None, k0=k0, wt_hi=wt[0].data_ptr(), wt_lo=wt[1].data_ptr(),
-            h3_hi=hs[2][0].data_ptr(), h2_hi=hs[1][0].data_ptr(), h1_hi=hs[0][0].data_ptr(),
-            dout_hi=dout_p[0].data_ptr(), dout_lo=dout_p[1].data_ptr(), dh3_hi=d3[0].data_ptr(), dh3_lo=d3[1].data_ptr(),
-            dh2_hi=d2[0].data_ptr(), dh2_lo=d2[1].data_ptr(), dh1_hi=d1[0].data_ptr(), dh1_lo=d1[1].data_ptr(),
-            acc=acc.data_ptr() if acc is not None else None,
-            acc_hi=acc_planes[0].data_ptr() if acc_planes is not None else None,
-            acc_lo=acc_planes[1].data_ptr() if acc_planes is not None else None, acc_mode=acc_mode,
-            B=self.B, h=self.h, w=self.w, rows=rows)
-        if gauss is not None:
-            gg, out, gmm_in = gauss
-            gg = gg.contiguous()
-            a.grad_gmm, a.gnet_out, a.gmm_in, a.gnet_ld = gg.data_ptr(), out.data_ptr(), gmm_in.data_ptr(), out.shape[1]
-        lib.head_dgrad(a, dev)
-        return dout_p, d3, d2, d1
-
-    def _tail_wgrads(self, dh, hs, g, cout_last, accumulate):
-        """Weight / bias gradients of the three 1x1 layers; g = [W1, b1, W2, b2, W3, b3, W4, b4] of the stack."""
-        rows, wp = self.rows, self.wp
-        dout_p, d3, d2, _ = dh
-        lib.wgrad(dout_p[0], dout_p[1], hs[2][0], hs[2][1], rows, wp, 1, _round_up(cout_last, 8), 128, g[6], cout_valid=cout_last,
-                  grad_b=g[7], accumulate=accumulate)
-        lib.wgrad(d3[0], d3[1], hs[1][0], hs[1][1], rows, wp, 1, 128, 128, g[4], grad_b=g[5], accumulate=accumulate)
-        lib.wgrad(d2[0], d2[1], hs[0][0], hs[0][1], rows, wp, 1, 128, 128, g[2], grad_b=g[3], accumulate=accumulate)
-
-    def _stack_backward(self, dout, k0, wt, hs, g, x, cin, cin_dst, cout_last):
-        dh = self._dgrad(dout, k0, wt, hs)
-        self._tail_wgrads(dh, hs, g, cout_last, accumulate=False)
-        lib.wgrad(dh[3][0], dh[3][1], x[0], x[1], self.rows, self.wp, 9, 128, cin, g[0], cin_dst=cin_dst, grad_b=g[1])
 
 
 class _HeadsTrainHIP(torch.autograd.Function):

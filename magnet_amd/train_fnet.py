@@ -28,8 +28,8 @@ import torch
 import torch.nn as nn
 
 from . import lib
-from .convnet import split_bf16
-from .fnet import _SPP, _TRUNK, _pack_s2d, _pack_taps
+from .fnet import _SPP, convs
+from .planes import PackCache, pack_s2d, pack_taps, planes, s2d_matrix, split_bf16
 
 
 def check_input(img: torch.Tensor, psm: nn.Module):
@@ -61,35 +61,6 @@ def bn_running_update(running_mean, running_var, mean, var_biased, n, momentum, 
     return ((1.0 - m) * running_mean + m * mean, (1.0 - m) * running_var + m * var_biased * n / (n - 1.0), num_batches_tracked + 1)
 
 
-def _bns(psm):
-    """conv name -> its BatchNorm2d, in the order the forward runs them."""
-    out = {"firstconv.0": psm.firstconv[0][1], "firstconv.2": psm.firstconv[2][1], "firstconv.4": psm.firstconv[4][1]}
-    for name, _, blocks, _, _ in _TRUNK:
-        layer = getattr(psm, name)
-        for i in range(blocks):
-            u = layer[i]
-            out[f"{name}.{i}.conv1"] = u.conv1[0][1]
-            out[f"{name}.{i}.conv2"] = u.conv2[1]
-            if u.downsample is not None:
-                out[f"{name}.{i}.downsample"] = u.downsample[1]
-    for name, _ in _SPP:
-        out[name] = getattr(psm, name)[1][1]
-    out["lastconv.0"] = psm.lastconv[0][1]
-    return out
-
-
-def _s2d_matrix(w: torch.Tensor):
-    """_pack_s2d's fp32 matrix (4, cout, 4C) before the split."""
-    cout, C = w.shape[:2]
-    out = torch.zeros((4, cout, 4 * C), dtype=torch.float32, device=w.device)
-    k_of = {(-1, 1): 0, (0, 0): 1, (0, 1): 2}
-    for (ty, py), ky in k_of.items():
-        for (tx, px), kx in k_of.items():
-            ph = py * 2 + px
-            out[(ty + 1) * 2 + (tx + 1), :, ph * C:(ph + 1) * C] = w[:, :, ky, kx]
-    return out
-
-
 def s2d_grad_to_3x3(g4: torch.Tensor, C: int):
     """Weight gradient over the space-to-depth 2x2 window (cout, 4C, 2, 2) -> the 3x3 stride-2 layer's (cout, C, 3, 3): every 3x3
     tap is exactly one (window tap, phase) pair."""
@@ -104,21 +75,13 @@ def s2d_grad_to_3x3(g4: torch.Tensor, C: int):
 
 def dgrad_pack(w: torch.Tensor):
     """Input-gradient weights of a stride-1 conv (cout, cin, k, k): flipped taps, transposed -> split planes (k*k, cin, cout)."""
-    return _pack_taps(w.flip(2, 3).transpose(0, 1).contiguous())
+    return pack_taps(w.flip(2, 3).transpose(0, 1).contiguous())
 
 
 def dgrad_pack_s2d(w: torch.Tensor):
     """Input-gradient weights of the space-to-depth 2x2 window: tap t takes the window's tap 3 - t, transposed -> (4, 4C, cout).
     Run over the gradient read wp + 1 rows further, the window's offsets (-wp-1, -wp, -1, 0) become (0, 1, wp, wp+1): the mirror."""
-    return split_bf16(_s2d_matrix(w).flip(0).transpose(1, 2).contiguous())
-
-
-def _planes(rows, c, dev):
-    return (torch.empty((rows, c), dtype=torch.bfloat16, device=dev), torch.empty((rows, c), dtype=torch.bfloat16, device=dev))
-
-
-def _zplanes(rows, c, dev):
-    return (torch.zeros((rows, c), dtype=torch.bfloat16, device=dev), torch.zeros((rows, c), dtype=torch.bfloat16, device=dev))
+    return split_bf16(s2d_matrix(w).flip(0).transpose(1, 2).contiguous())
 
 
 class FNetTrainHIP:
@@ -128,43 +91,24 @@ class FNetTrainHIP:
     def __init__(self, psm: nn.Module):
         self.psm = psm
         self._packed = None
-        self._key = None
+        self._cache = PackCache(lambda: list(psm.parameters()))
         self._work = {}
         self.rec = None
 
-    def _params_key(self, device):
-        return tuple((p.data_ptr(), p._version) for p in self.psm.parameters()) + (str(device),)
-
-    @torch.no_grad()
     def packed(self, device):
         """The module's conv weights as split-bf16 tap planes (no folding), with a zero bias; repacked when a weight changes."""
-        key = self._params_key(device)
-        if self._packed is not None and self._key == key:
-            return self._packed
-        psm = self.psm
+        self._packed = self._cache.get(device, lambda: self._pack(device))
+        return self._packed
+
+    @torch.no_grad()
+    def _pack(self, device):
         P = {}
-
-        def put(name, conv, s2d=False):
+        for name, conv, _, s2d in convs(self.psm):
             w = conv.weight.detach().float().to(device)
-            hi, lo = (_pack_s2d if s2d else _pack_taps)(w)
-            P[name] = (hi, lo, torch.zeros(w.shape[0], dtype=torch.float32, device=device), w.shape[0])
-
-        P["stem"] = psm.firstconv[0][0].weight.detach().float().to(device).reshape(32, 27).contiguous()
-        put("firstconv.2", psm.firstconv[2][0])
-        put("firstconv.4", psm.firstconv[4][0])
-        for name, _, blocks, stride, _ in _TRUNK:
-            layer = getattr(psm, name)
-            for i in range(blocks):
-                u = layer[i]
-                put(f"{name}.{i}.conv1", u.conv1[0][0], s2d=(i == 0 and stride == 2))
-                put(f"{name}.{i}.conv2", u.conv2[0])
-                if u.downsample is not None:
-                    put(f"{name}.{i}.downsample", u.downsample[0])
-        for name, _ in _SPP:
-            put(name, getattr(psm, name)[1][0])
-        put("lastconv.0", psm.lastconv[0][0])
-        put("lastconv.2", psm.lastconv[2])
-        self._packed, self._key = P, key
+            if name == "firstconv.0":
+                P["stem"] = w.reshape(32, 27).contiguous()
+            else:
+                P[name] = (*(pack_s2d if s2d else pack_taps)(w), torch.zeros(w.shape[0], dtype=torch.float32, device=device), w.shape[0])
         return P
 
     def _ws(self, dev, n):
@@ -204,7 +148,7 @@ class FNetTrainHIP:
             if t.device != dev:
                 raise lib.MagnetError(f"F-Net training forward: module tensors must be on {dev}")
         P = self.packed(dev)
-        self._bn_mods = _bns(psm)
+        self._bn_mods = {name: bn for name, _, bn, _ in convs(psm) if bn is not None}     # in forward order
         self.rec = {} if save else None
         H2, W2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         H4, W4 = (H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1
@@ -217,57 +161,57 @@ class FNetTrainHIP:
         # ---- H/2 stage: firstconv + layer1 (32 channels, border 1) ----
         z = torch.empty((rows_a, 32), dtype=torch.float32, device=dev)
         lib.fnet_stem_raw(img, P["stem"], z)                                                     # F_psmnet.py:40
-        a0 = _planes(rows_a, 32, dev)
+        a0 = planes(rows_a, 32, dev)
         if save:
             self.rec["firstconv.0"] = dict(out=a0)
         self._bn("firstconv.0", z, ga + (32,), True, out=a0)
-        a1 = _planes(rows_a, 32, dev)
+        a1 = planes(rows_a, 32, dev)
         self._layer("firstconv.2", a0, 32, 32, 9, wpa, rows_a, ga, True, a1)
-        x = _planes(rows_a, 32, dev)
+        x = planes(rows_a, 32, dev)
         self._layer("firstconv.4", a1, 32, 32, 9, wpa, rows_a, ga, True, x)
         for i in range(3):                                                                       # layer1
-            t, o = _planes(rows_a, 32, dev), _planes(rows_a, 32, dev)
+            t, o = planes(rows_a, 32, dev), planes(rows_a, 32, dev)
             self._layer(f"layer1.{i}.conv1", x, 32, 32, 9, wpa, rows_a, ga, True, t)
             self._layer(f"layer1.{i}.conv2", t, 32, 32, 9, wpa, rows_a, ga, False, o, res=x)
             x = o
         # ---- H/4 stage (border 2: layer4 is dilated) ----
-        S = _zplanes(rows_b, 128, dev)
+        S = planes(rows_b, 128, dev, zero=True)
         lib.space_to_depth(x[0], x[1], S[0], S[1], N, 32, H2, W2, 2)
-        b0, b1, b2 = _planes(rows_b, 64, dev), _planes(rows_b, 64, dev), _planes(rows_b, 64, dev)
+        b0, b1, b2 = planes(rows_b, 64, dev), planes(rows_b, 64, dev), planes(rows_b, 64, dev)
         self._layer("layer2.0.conv1", S, 128, 128, 4, wpb, rows_b, gb, True, b0)                # 3x3 stride 2
         self._layer("layer2.0.downsample", (S[0][:, :32], S[1][:, :32]), 128, 32, 1, wpb, rows_b, gb, False, b1)   # phase 0
         self._layer("layer2.0.conv2", b0, 64, 64, 9, wpb, rows_b, gb, False, b2, res=b1)
         cur, ld = b2, 64
-        cat = _zplanes(rows_b, 320, dev)
+        cat = planes(rows_b, 320, dev, zero=True)
         raw = (cat[0][:, 0:64], cat[1][:, 0:64])
         for i in range(1, 16):
-            t = _planes(rows_b, 64, dev)
+            t = planes(rows_b, 64, dev)
             self._layer(f"layer2.{i}.conv1", cur, ld, 64, 9, wpb, rows_b, gb, True, t)
             last = i == 15                                                                       # output_raw -> concat[:, 0:64]
-            o = raw if last else _planes(rows_b, 64, dev)
+            o = raw if last else planes(rows_b, 64, dev)
             self._layer(f"layer2.{i}.conv2", t, 64, 64, 9, wpb, rows_b, gb, False, o, res=cur)
             cur, ld = (raw, 320) if last else (o, 64)
         skip = (cat[0][:, 64:192], cat[1][:, 64:192])
         units = [("layer3", i, 0) for i in range(3)] + [("layer4", i, 2) for i in range(3)]
         for n_unit, (name, i, dil) in enumerate(units):
             cin = 64 if (name == "layer3" and i == 0) else 128
-            t = _planes(rows_b, 128, dev)
+            t = planes(rows_b, 128, dev)
             self._layer(f"{name}.{i}.conv1", cur, ld, cin, 9, wpb, rows_b, gb, True, t, dil=dil)
             if f"{name}.{i}.downsample" in P:
-                r = _planes(rows_b, 128, dev)
+                r = planes(rows_b, 128, dev)
                 self._layer(f"{name}.{i}.downsample", cur, ld, cin, 1, wpb, rows_b, gb, False, r)
                 res = r
             else:
                 res = cur
             last = n_unit == len(units) - 1                                                      # output_skip -> concat[:, 64:192]
-            o = skip if last else _planes(rows_b, 128, dev)
+            o = skip if last else planes(rows_b, 128, dev)
             self._layer(f"{name}.{i}.conv2", t, 128, 128, 9, wpb, rows_b, gb, False, o, res=res, dil=dil)
             cur, ld = (skip, 320) if last else (o, 128)
         # ---- SPP branches: pool -> 1x1 conv -> BN over the pooled cells -> ReLU -> bilinear back to H/4 into the concat ----
         for slot, (name, k) in enumerate(_SPP):                     # branch1 -> channels 288:320 ... branch4 -> 192:224
             ph, pw = H4 // k, W4 // k
             cells = N * ph * pw
-            pool = _planes(cells, 128, dev)
+            pool = planes(cells, 128, dev)
             lib.avgpool_cl(skip[0], skip[1], 320, N, H4, W4, 2, k, 128, pool[0], pool[1])
             hi, lo, zb, _ = P[name]
             zq = torch.empty((cells, 32), dtype=torch.float32, device=dev)
@@ -279,7 +223,7 @@ class FNetTrainHIP:
             off = 288 - 32 * slot
             lib.upsample_bilinear_cl(q, 32, ph, pw, 32, cat[0][:, off:off + 32], cat[1][:, off:off + 32], 320, N, H4, W4, 2)
         # ---- lastconv ----
-        c0 = _planes(rows_b, 128, dev)
+        c0 = planes(rows_b, 128, dev)
         self._layer("lastconv.0", cat, 320, 320, 9, wpb, rows_b, gb, True, c0)
         Fd = P["lastconv.2"][3]
         out = torch.empty((N, H4, W4, Fd), dtype=torch.float32, device=dev)
@@ -301,7 +245,7 @@ class FNetTrainHIP:
         r, bn = self.rec[name], self._bn_mods[name]
         grid = r["grid"]
         rows = grid[0] * grid[1] * grid[2]
-        dz = _planes(rows, grid[4], g.device)
+        dz = planes(rows, grid[4], g.device)
         dgamma = torch.empty_like(bn.weight, dtype=torch.float32)
         dbeta = torch.empty_like(bn.bias, dtype=torch.float32)
         lib.bn_train_backward(r["z"], grid, r["stats"][0], r["stats"][1], bn.weight.detach(), bn.bias.detach(), r["relu"], g, dgamma,
@@ -387,7 +331,7 @@ class FNetTrainHIP:
         w2 = psm.lastconv[2].weight
         Fd = w2.shape[0]
         Fp = max(Fd, 32)
-        dF = _planes(rows_b, Fp, dev)
+        dF = planes(rows_b, Fp, dev)
         lib.fnet_grad_pack(grad_feat.float().contiguous(), dF[0], dF[1], 2)
         gw = torch.empty(w2.shape, dtype=torch.float32, device=dev)
         c0 = self.rec["lastconv.2"]["x"]
@@ -395,7 +339,7 @@ class FNetTrainHIP:
         self.grads[id(w2)] = gw
         wt = torch.zeros((128, Fp, 1, 1), dtype=torch.float32, device=dev)
         wt[:, :Fd] = w2.detach().float().transpose(0, 1)
-        hi, lo = _pack_taps(wt)
+        hi, lo = pack_taps(wt)
         g_l0 = torch.empty((rows_b, 128), dtype=torch.float32, device=dev)
         lib.conv_mfma(dF[0], dF[1], Fp, Fp, hi, lo, torch.zeros(128, device=dev), 1, wpb, False, rows_b, out_f32=g_l0)
         # ---- lastconv.0 (3x3, 320 -> 128) ----

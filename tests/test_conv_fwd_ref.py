@@ -9,7 +9,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from magnet_amd.convnet import split_bf16
-from magnet_amd.fnet import _pack_taps
+from magnet_amd.planes import pack_taps
 from tests import conv_fwd_ref as C
 
 
@@ -213,7 +213,7 @@ def _plain_case(taps, cin, cout, dil=1, seed=0, N=2, h=9, w=13, heavy=True):
     k = {9: 3, 4: 2, 1: 1}[taps]
     wt = make((cout, cin, k, k), 200 + seed, (taps * cin) ** -0.5)
     xh, xl = split_bf16(xg.reshape(rows, cin))
-    wh, wl = _pack_taps(wt)
+    wh, wl = pack_taps(wt)
     bias = torch.randn(cout, generator=_g(300 + seed)) * 0.5
     res = split_bf16(make((rows, cout), 400 + seed))
     addend = make((rows, cout), 500 + seed)
@@ -251,7 +251,7 @@ def test_fp32_emulation_of_the_plain_forms_stays_inside_the_bound(taps, cin, cou
 def _tail_case(tail_cout, seed, heavy=True, taps=9, cin=64):
     c = _plain_case(taps, cin, 128, 1, seed=seed, heavy=heavy)
     ws, bs = _tail_params(tail_cout, 600 + seed, positive=heavy)
-    planes = [_pack_taps(wv) for wv in ws]
+    planes = [pack_taps(wv) for wv in ws]
     c["twh"] = torch.cat([p[0].reshape(-1) for p in planes]); c["twl"] = torch.cat([p[1].reshape(-1) for p in planes])
     c["tb"] = torch.cat(bs); c["tail_cout"] = tail_cout
     return c

@@ -12,8 +12,9 @@ import torch
 import torch.nn as nn
 
 from magnet_amd import lib
-from magnet_amd.dnet import DNET, DenseDepthDecoder, fold_bn, load_seeded_decoder, seeded_decoder_state
+from magnet_amd.dnet import DNET, DenseDepthDecoder, load_seeded_decoder, seeded_decoder_state
 from magnet_amd.magnet import MAGNET
+from magnet_amd.planes import fold_bn
 from magnet_amd.standin import StandinEncoder, StubFNet, make_args, make_dnet, make_dnet_args
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))

@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from magnet_amd import fnet
+from magnet_amd.planes import fold_bn, pack_s2d
 from tests.stubs import procedural_images, seeded_fnet_state
 
 
@@ -31,15 +32,15 @@ def test_state_dict_layout():
 
 
 def test_bn_fold_and_s2d_weights():
-    """conv+BN(eval) == folded conv; stride-2 3x3 == 2x2-window conv over the space-to-depth tensor with _pack_s2d weights."""
+    """conv+BN(eval) == folded conv; stride-2 3x3 == 2x2-window conv over the space-to-depth tensor with pack_s2d weights."""
     torch.manual_seed(0)
     seq = fnet._conv_bn(8, 16, 3, stride=2).eval()
     seq[1].running_mean.normal_(); seq[1].running_var.uniform_(0.5, 2.0); seq[1].weight.data.uniform_(0.5, 1.5); seq[1].bias.data.normal_()
     x = torch.randn(2, 8, 10, 14)
-    w, b = fnet._fold(seq)
+    w, b = (t.float() for t in fold_bn(seq[0], seq[1]))
     ref = seq(x)
     np.testing.assert_allclose(torch.nn.functional.conv2d(x, w, b, stride=2, padding=1).detach().numpy(), ref.detach().numpy(), atol=2e-5)
-    hi, lo = fnet._pack_s2d(w)                                   # (4, 16, 32) planes
+    hi, lo = pack_s2d(w)                                   # (4, 16, 32) planes
     w4 = (hi.float() + lo.float())                               # bf16x2 reconstruction (16 mantissa bits)
     s2d = torch.cat([x[:, :, py::2, px::2] for py in (0, 1) for px in (0, 1)], dim=1)          # (2, 32, 5, 7)
     s2d = torch.nn.functional.pad(s2d, (1, 0, 1, 0))             # taps reach (-1,-1)

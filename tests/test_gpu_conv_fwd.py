@@ -1,7 +1,7 @@
 """Every forward conv_mfma instance, one direct launch each, against the fp64 restatement of tests/conv_fwd_ref.py, pointwise.
 
 Each test makes ONE lib.conv_mfma / lib.conv1x1_chain / lib.pack_split call on planes split with convnet.split_bf16 and weights packed
-with fnet._pack_taps, and compares it with the reference of exactly the planes the kernel received through `check` (|got - ref| <=
+with planes.pack_taps, and compares it with the reference of exactly the planes the kernel received through `check` (|got - ref| <=
 bound at every element; the bound is derived in conv_fwd_ref.py, not measured).  Outputs live inside one allocation with NaN guard
 bands on both sides; rows at or past `rows`, channels outside a written slice and (under repad) the target grid's border must keep
 their sentinel bit for bit.  Biases are random and non-zero in every padded channel, and every padded output channel is compared.
@@ -88,7 +88,7 @@ def _case(gpu, N, h, w, pad, cin, cout, taps, dil=1, in_wide=False, seed=0):
     if key in _CACHE:
         return _CACHE[key]
     from magnet_amd.convnet import split_bf16
-    from magnet_amd.fnet import _pack_taps
+    from magnet_amd.planes import pack_taps
     hp, wp = h + 2 * pad, w + 2 * pad
     rows = N * hp * wp
     in_ld, c0 = (cin + 24, 16) if in_wide else (cin, 0)
@@ -97,7 +97,7 @@ def _case(gpu, N, h, w, pad, cin, cout, taps, dil=1, in_wide=False, seed=0):
     xb[:, pad:pad + h, pad:pad + w, c0:c0 + cin] = _heavy((N, h, w, cin), 11 + seed)
     hi, lo = split_bf16(xb.reshape(rows, in_ld).to(gpu))
     k = {9: 3, 4: 2, 1: 1}[taps]
-    wh, wl = _pack_taps(_heavy((cout, cin, k, k), 12 + seed, (taps * cin) ** -0.5).to(gpu))
+    wh, wl = pack_taps(_heavy((cout, cin, k, k), 12 + seed, (taps * cin) ** -0.5).to(gpu))
     bias = (torch.randn(cout, generator=_g(13 + seed)) * 0.5).to(gpu)
     assert bool((bias != 0).all())
     rh, rl = split_bf16(_heavy((rows, cout + 8), 14 + seed).to(gpu))
@@ -267,11 +267,11 @@ def test_output_modes(hip_lib, gpu, form, cout):
 def _tail_pack(gpu, tail_cout, seed=0):
     key = ("tail", tail_cout, seed)
     if key not in _CACHE:
-        from magnet_amd.fnet import _pack_taps
+        from magnet_amd.planes import pack_taps
         g = _g(50 + seed)
         ws = [(torch.randn(n, 128, 1, 1, generator=g) ** 3).abs() / 128 for n in (128, 128, tail_cout)]
         bs = [torch.randn(n, generator=g).abs() * 0.5 + 0.01 for n in (128, 128, tail_cout)]
-        planes = [_pack_taps(wv.to(gpu)) for wv in ws]
+        planes = [pack_taps(wv.to(gpu)) for wv in ws]
         t = dict(wh=torch.cat([p[0].reshape(-1) for p in planes]).contiguous(), wl=torch.cat([p[1].reshape(-1) for p in planes]).contiguous(),
                  bias=torch.cat(bs).to(gpu), cout=tail_cout)
         t["w64"] = C.join(t["wh"], t["wl"])

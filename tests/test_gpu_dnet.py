@@ -9,10 +9,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from magnet_amd import fnet, lib, synth
+from magnet_amd import lib, synth
 from magnet_amd.convnet import split_bf16
 from magnet_amd.dnet import DenseDepthDecoder, DNetMFMA, gaussian_activation, load_seeded_decoder
 from magnet_amd.magnet import MAGNET
+from magnet_amd.planes import pack_taps
 from magnet_amd.standin import StubFNet, make_args, make_dnet, seeded_magnet_weights
 from tests.stubs import procedural_images
 
@@ -34,7 +35,7 @@ def test_leaky_conv_every_output_form(hip_lib, gpu, form):
     x = torch.randn(N, h, w, cin, generator=g); wt = torch.randn(cout, cin, 3, 3, generator=g) / (3 * cin ** 0.5)
     b = torch.randn(cout, generator=g) * 0.5
     xh, xl = _planes(x, pad, gpu)
-    wh, wl = fnet._pack_taps(wt.to(gpu))
+    wh, wl = pack_taps(wt.to(gpu))
     hp, wp = h + 2, w + 2
     rows = N * hp * wp
     xr = (xh.double() + xl.double()).cpu().reshape(N, hp, wp, cin)[:, 1:-1, 1:-1]

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 from magnet_amd import fnet, lib
 from magnet_amd.convnet import split_bf16
+from magnet_amd.planes import pack_taps
 from tests.stubs import StubDNet, make_args, procedural_images, seeded_fnet_state, seeded_magnet_weights
 
 pytestmark = pytest.mark.gpu
@@ -90,7 +91,7 @@ def test_conv_extensions(hip_lib, gpu, cfg):
     x = torch.randn(N, h, w, cin, generator=g); wt = torch.randn(cout, cin, k, k, generator=g) / (k * cin ** 0.5); b = torch.randn(cout, generator=g)
     r = torch.randn(N, h, w, cout, generator=g)
     xh, xl = _planes(x, pad, gpu); rh, rl = _planes(r, pad, gpu)
-    wh, wl = fnet._pack_taps(wt.to(gpu))
+    wh, wl = pack_taps(wt.to(gpu))
     rows, wp = N * (h + 2 * pad) * (w + 2 * pad), w + 2 * pad
     oh = torch.full((rows, cout), 7.0, dtype=torch.bfloat16, device=gpu); ol = torch.full_like(oh, 7.0)     # poisoned
     lib.conv_mfma(xh, xl, cin, cin, wh, wl, b.to(gpu), k * k, wp, cfg["relu"], rows, out_hi=oh, out_lo=ol,
@@ -113,7 +114,7 @@ def test_conv_repad_outputs(hip_lib, gpu):
     N, h, w, pad, cin, cout = 3, 9, 12, 2, 128, 64
     x = torch.randn(N, h, w, cin, generator=g); wt = torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5
     xh, xl = _planes(x, pad, gpu)
-    wh, wl = fnet._pack_taps(wt.to(gpu))
+    wh, wl = pack_taps(wt.to(gpu))
     rows, wp = N * (h + 4) * (w + 4), w + 4
     zero_b = torch.zeros(cout, device=gpu)
     xr = (xh.float() + xl.float()).cpu().reshape(N, h + 4, wp, cin)[:, 2:-2, 2:-2]

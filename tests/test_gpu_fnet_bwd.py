@@ -8,7 +8,7 @@ import torch
 
 from magnet_amd import lib
 from magnet_amd.convnet import split_bf16
-from magnet_amd.fnet import _pack_taps
+from magnet_amd.planes import pack_taps
 from magnet_amd.train_fnet import dgrad_pack, dgrad_pack_s2d
 from tests import fnet_bwd_ref as R
 
@@ -312,7 +312,7 @@ def test_conv_dgrad_lastconv2_pack(hip_lib, gpu):
     w2 = torch.randn(Fd, 128, 1, 1, generator=gen).to(gpu) * 0.1
     wt = torch.zeros((128, Fp, 1, 1), device=gpu)
     wt[:, :Fd] = w2.transpose(0, 1)
-    hi, lo = _pack_taps(wt)
+    hi, lo = pack_taps(wt)
     out = torch.full((rows, 128), NAN, device=gpu)
     lib.conv_mfma(dF[0], dF[1], Fp, Fp, hi, lo, torch.zeros(128, device=gpu), 1, wp, False, rows, out_f32=out)
     ref, bound = R.conv_ref(R.join(*dF), R.join(hi, lo), 1, wp, rows)

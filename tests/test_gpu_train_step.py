@@ -334,7 +334,7 @@ def test_loss_scale_is_a_power_of_two_factor(hip_lib, gpu, which):
 
 def test_backward_launch_audit_at_training_shape(hip_lib, gpu, monkeypatch):
     """One HIP training step at B = 4, 120 x 160, V = 4, D = 5, I = 3 with every lib entry point of the backward wrapped (the dgrad
-    through train._Runner._dgrad, the Python side of its one magnet_head_dgrad launch): each launch is checked, as it happens,
+    through train._dgrad, the Python side of its one magnet_head_dgrad launch): each launch is checked, as it happens,
     against its fp64 restatement (tests/heads_bwd_ref.py) on the exact inputs it received.  Every ratio <= 1 means each launch is
     within the rounding its own arithmetic allows."""
     import time
@@ -410,7 +410,7 @@ def test_backward_launch_audit_at_training_shape(hip_lib, gpu, monkeypatch):
     for name, fn in (("nll_loss_forward", c_nll_fwd), ("nll_loss_backward", c_nll_bwd), ("upsample_depth_backward", c_up),
                      ("wgrad", c_wgrad)):
         wrap(name, fn)
-    orig_dgrad = T._Runner._dgrad
+    orig_dgrad = T._dgrad
 
     def dgrad(self, dout, k0, wt, hs, acc=None, acc_mode=0, acc_planes=None, gauss=None):
         old = acc.clone() if acc is not None and acc_mode == 2 else None
@@ -429,7 +429,7 @@ def test_backward_launch_audit_at_training_shape(hip_lib, gpu, monkeypatch):
         note("head_dgrad marginal positions", marg)
         t_check[0] += time.time() - t0
         return outs
-    monkeypatch.setattr(T._Runner, "_dgrad", dgrad)
+    monkeypatch.setattr(T, "_dgrad", dgrad)
     from magnet_amd.convnet import split_bf16
     t0 = time.time()
     _step(m, gpu, case=case)
