@@ -8,6 +8,7 @@ the backbones are caller-provided (stub D-Net/F-Net here), and the metric reduct
 
     python eval_synthetic.py --frames 8 --batch 2 [--D 5] [--iters 3] [--V 4] [--log out.txt]
     python eval_synthetic.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
+    python eval_synthetic.py --dataset_path ROOT --split split.txt --reuse_backbones [--pool_frames 64]
 """
 import argparse
 import os
@@ -22,7 +23,7 @@ from magnet_amd import evaluate as E  # noqa: E402
 from magnet_amd import metrics as M  # noqa: E402
 from magnet_amd import synth  # noqa: E402
 from magnet_amd.magnet import MAGNET  # noqa: E402
-from magnet_amd.preprocess import data_preprocess, data_preprocess_device  # noqa: E402,F401
+from magnet_amd.preprocess import data_preprocess, data_preprocess_device, split_data_array  # noqa: E402,F401
 
 
 class SyntheticWindows:
@@ -53,7 +54,37 @@ class SyntheticWindows:
             yield frames, synth.make_intrinsics(self.cam, self.H // 4, self.W // 4, self.B)
 
 
-def validate(model, args, test_loader, device):
+class FolderBatches:
+    """data.batches(dataset, batch) with a length, which the sharded loop asks for."""
+
+    def __init__(self, dataset, batch):
+        self.dataset, self.batch = dataset, batch
+
+    def __len__(self):
+        return (len(self.dataset) + self.batch - 1) // self.batch
+
+    def __iter__(self):
+        from magnet_amd import data
+        return data.batches(self.dataset, self.batch)
+
+
+def frame_ids(data_array, B):
+    """(ref_ids (B), nghbr_ids (V B), view-major as nghbr_imgs) of a loader batch: a frame's id is its (scene_name, img_idx)."""
+    ref_dat, nghbr_dats = split_data_array(data_array)
+    ids = lambda d: list(zip(d["scene_name"][:B], d["img_idx"][:B]))
+    return ids(ref_dat), [fid for d in nghbr_dats for fid in ids(d)]
+
+
+def run_model(model, runner, data_array, B, ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins):
+    """model(...) as test_MaGNet.py:50 calls it, or with `runner` (magnet_amd.sequence.SequenceRunner over the same model) the
+    same prediction with every frame's backbones run once."""
+    if runner is None:
+        return model(ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, mode="test")
+    ref_ids, nghbr_ids = frame_ids(data_array, B)
+    return runner.forward(ref_ids, ref_img, nghbr_ids, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, mode="test")
+
+
+def validate(model, args, test_loader, device, runner=None):
     """The reference's validate() (test_MaGNet.py:27-81), metrics reduced on the device."""
     with torch.no_grad():
         metrics = M.RunningAverageDict()
@@ -64,14 +95,14 @@ def validate(model, args, test_loader, device):
             ref_img = ref_dat["img"].to(device)
             gt_dmap = ref_dat["gt_dmap"].to(device)
             nghbr_imgs = torch.cat([d["img"].to(device) for d in nghbr_dats], dim=0)       # view-major
-            pred_list = model(ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, mode="test")
+            pred_list = run_model(model, runner, data_array, cur_batch_size, ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins)
             crop = "garg" if getattr(args, "garg_crop", False) else ("eigen" if getattr(args, "eigen_crop", False) else None)
             for m in M.compute_depth_errors(pred_list[-1], gt_dmap, args.min_depth, args.max_depth, crop=crop):   # test_MaGNet.py:58-79
                 metrics.update(m)
         return metrics.get_value()
 
 
-def validate_sharded(model, args, test_loader, device, rank=0, world=1, with_count=False):
+def validate_sharded(model, args, test_loader, device, rank=0, world=1, with_count=False, runner=None):
     """validate() over this rank's share of the batches with the metric rows kept on the device (kind='sigma' on pred_list[-1]):
     nothing is read back per batch, and the rows of all ranks are gathered once and averaged in loader order."""
     with torch.no_grad():
@@ -85,7 +116,7 @@ def validate_sharded(model, args, test_loader, device, rank=0, world=1, with_cou
             ref_img = ref_dat["img"].to(device)
             gt_dmap = ref_dat["gt_dmap"].to(device)
             nghbr_imgs = torch.cat([d["img"].to(device) for d in nghbr_dats], dim=0)       # view-major
-            pred_list = model(ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins, mode="test")
+            pred_list = run_model(model, runner, data_array, cur_batch_size, ref_img, nghbr_imgs, nghbr_poses, is_valid, cam_intrins)
             table.append_pred(pred_list[-1], gt_dmap)
 
         metrics, n = E.evaluate(step, test_loader, table, rank, world)
@@ -107,8 +138,15 @@ def main():
     ap.add_argument("--garg_crop", action="store_true", help="KITTI: evaluate inside the Garg ECCV16 window (test_MaGNet.py:67-68)")
     ap.add_argument("--eigen_crop", action="store_true", help="KITTI: evaluate inside the Eigen NIPS14 window (test_MaGNet.py:69-70)")
     ap.add_argument("--psmnet", action="store_true", help="use the PSMNet F-Net (matrix-core path) instead of the stub F-Net")
+    ap.add_argument("--reuse_backbones", action="store_true",
+                    help="with --dataset_path: run each frame's backbones once and gather the views of every window from a frame pool "
+                         "(magnet_amd/sequence.py); frame ids are the loader's (scene_name, img_idx).  The torch stand-in backbones round differently "
+                         "in a batch of another size, so the metrics agree with the default run's to about 7 digits, not to the bit")
+    ap.add_argument("--pool_frames", type=int, default=64, help="with --reuse_backbones: frames the pool holds (least recently used go first)")
     E.add_arguments(ap)
     a = ap.parse_args()
+    if a.reuse_backbones and not a.dataset_path:
+        raise SystemExit("--reuse_backbones needs --dataset_path: the synthetic windows share no frames")
     rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.standin import StubDNet, StubFNet, make_args, seeded_magnet_weights
     args = make_args(D=a.D, iters=a.iters, dpv_h=a.input_height // 4, dpv_w=a.input_width // 4, V=a.V)
@@ -122,6 +160,7 @@ def main():
     model = MAGNET(args, d_net=StubDNet(1), f_net=f_net, feat_dtype=a.feat_dtype)
     seeded_magnet_weights(model, 3)
     model = model.to(device).eval()
+    runner = None
     if a.dataset_path:
         from magnet_amd import data
         with open(a.split) as f:
@@ -129,15 +168,18 @@ def main():
         Folder = data.SevenScenesFolder if a.dataset_format == "7scenes" else data.ScanNetFolder
         ds = Folder(a.dataset_path, samples, n_views=a.V, window_radius=a.window_radius,
                                 input_hw=(a.input_height, a.input_width), dpv_hw=(a.input_height // 4, a.input_width // 4))
-        loader = data.batches(ds, a.batch)
+        loader = FolderBatches(ds, a.batch)
+        if a.reuse_backbones:
+            from magnet_amd.sequence import SequenceRunner
+            runner = SequenceRunner(model, a.pool_frames)
         title = "scannet-format folder %s (%d windows) V=%d D=%d iters=%d" % (a.dataset_path, len(ds), a.V, a.D, a.iters)
     else:
         loader = SyntheticWindows((a.frames + a.batch - 1) // a.batch, a.batch, a.V, a.input_height, a.input_width, nan_every=3)
         title = "synthetic frames=%d V=%d D=%d iters=%d" % (a.frames, a.V, a.D, a.iters)
     if not sharded:
-        M.log_metrics(a.log, validate(model, args, loader, device), title)
+        M.log_metrics(a.log, validate(model, args, loader, device, runner), title)
         return
-    m, n = validate_sharded(model, args, loader, device, rank, world, with_count=True)
+    m, n = validate_sharded(model, args, loader, device, rank, world, with_count=True, runner=runner)
     if rank == 0:
         M.log_metrics(a.log, m, title)
         if a.dump_metrics:

@@ -633,6 +633,45 @@ MAGNET_API int magnet_dnet_gauss_head(const float *in, int32_t in_ld, int32_t N,
 MAGNET_API int magnet_dnet_upsample_gauss(const float *head, int32_t head_ld, const float *mask, int32_t mask_ld, int32_t N,
                                           int32_t h, int32_t w, float *out, void *stream);
 
+/* Sequence inference (magnet_amd/sequence.py): a frame pool of n_slots slots keeps one frame's backbone outputs per slot, in the
+ * layouts the kernels read:
+ *   pool_feat  (n_slots, h+2, w+2, F) channel-last F-Net features, zero border, fp32 or bf16 (feat_dtype), F % 8 == 0
+ *   pool_gmm   (n_slots, 2, h, w) fp32 [mu, sigma]
+ *   pool_xd3_hi / pool_xd3_lo (n_slots, (h+2)(w+2), 256) split-bf16 planes of x_d3, zero border rows
+ * magnet_gather_views assembles the inputs of one refinement step of B windows with V source views in one launch.  `slots`
+ * ((1 + V) B int32, on the device): entry [b] is the slot of window b's reference frame, entry [B + v B + b] the slot of its view v
+ * (view-major, as nghbr_imgs and src_pad).  Destinations, each optional (NULL skips it; gin_hi and gin_lo go together):
+ *   ref_cl  (B, h, w, F)          the interior of the reference slot's features
+ *   src_pad (V B, h+2, w+2, F)    whole padded frames
+ *   ref_gmm (B, 2, h, w), src_gmm (V B, 2, h, w)
+ *   gin_hi / gin_lo               the reference slot's 256 x_d3 channels into channels [gin_c_off, gin_c_off + 256) of rows
+ *                                 [b (h+2)(w+2), (b+1)(h+2)(w+2)) of planes of row pitch gin_ld elements (MAGNET.gnet_input_buffer);
+ *                                 no other channel is written
+ * An entry < 0 or >= n_slots means "no frame": its destination is filled with zeros and nothing is read for it; the kernel never
+ * reads outside the pool whatever the table holds.  Values are copied bit for bit.
+ * pool_feat, the x_d3 planes, ref_cl, src_pad, gin_hi and gin_lo 16-byte aligned, gin_ld % 8 == 0, gin_c_off % 8 == 0; the
+ * (mu, sigma) tensors only 4-byte (16-byte vectors are used where a source and its destination frame allow).  A pool tensor may be
+ * NULL when no destination reads it. */
+typedef struct MagnetGatherViewsArgs {
+    const int32_t *slots;                  /* ((1 + V) B) int32 on the device */
+    int32_t        n_slots;
+    int32_t        B, V, h, w, F;
+    int32_t        feat_dtype;             /* MAGNET_FEAT_* */
+    const void    *pool_feat;
+    const float   *pool_gmm;
+    const void    *pool_xd3_hi;
+    const void    *pool_xd3_lo;
+    void          *ref_cl;
+    void          *src_pad;
+    float         *ref_gmm;
+    float         *src_gmm;
+    void          *gin_hi;
+    void          *gin_lo;
+    int64_t        gin_ld;
+    int32_t        gin_c_off;
+} MagnetGatherViewsArgs;
+MAGNET_API int magnet_gather_views(const MagnetGatherViewsArgs *args, void *stream);
+
 /* FnetLoss: the tail of the F-Net training step (train_FNet.py:95-104) on the raw volume x (B, D, h, w) of
  * magnet_cost_volume_cw(mode = 1): p = softmax over the D bins, pred = sum_j p_j d_j, loss = mean over the valid pixels of
  * |pred - gt|, valid iff gt > min_depth && !(gt > max_depth) (the driver's gt[gt > max_depth] = 0; mask = gt > min_depth, which needs

@@ -52,6 +52,7 @@ hipError_t launch_dnet_loss_forward(const MagnetDnetLossArgs&, hipStream_t);
 hipError_t launch_dnet_loss_backward(const MagnetDnetLossArgs&, hipStream_t);
 hipError_t launch_dnet_nll_forward(const MagnetDnetNllArgs&, hipStream_t);
 hipError_t launch_dnet_nll_backward(const MagnetDnetNllArgs&, hipStream_t);
+hipError_t launch_gather_views(const MagnetGatherViewsArgs&, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -863,6 +864,32 @@ MAGNET_API int magnet_dnet_nll_backward(const MagnetDnetNllArgs* a, void* stream
     if (int rc = dnet_nll_dims(a, "magnet_dnet_nll_backward")) return rc;
     hipError_t e = magnet::launch_dnet_nll_backward(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_dnet_nll_backward launch");
+}
+
+MAGNET_API int magnet_gather_views(const MagnetGatherViewsArgs* a, void* stream) {
+    if (!a || !a->slots) return fail(MAGNET_E_NULL, "magnet_gather_views: NULL pointer");
+    if ((a->ref_cl || a->src_pad) && !a->pool_feat) return fail(MAGNET_E_NULL, "magnet_gather_views: ref_cl / src_pad need pool_feat");
+    if ((a->ref_gmm || a->src_gmm) && !a->pool_gmm) return fail(MAGNET_E_NULL, "magnet_gather_views: ref_gmm / src_gmm need pool_gmm");
+    if ((a->gin_hi != nullptr) != (a->gin_lo != nullptr) || (a->gin_hi && (!a->pool_xd3_hi || !a->pool_xd3_lo)))
+        return fail(MAGNET_E_NULL, "magnet_gather_views: gin_hi and gin_lo go together and need both x_d3 pool planes");
+    if (a->feat_dtype != MAGNET_FEAT_F32 && a->feat_dtype != MAGNET_FEAT_BF16)
+        return fail(MAGNET_E_DTYPE, "magnet_gather_views: unknown dtype %d", a->feat_dtype);
+    const long long R = ((long long)a->h + 2) * ((long long)a->w + 2);
+    if (a->n_slots <= 0 || a->B <= 0 || a->V < 0 || a->h <= 0 || a->w <= 0 || a->F <= 0 || (a->F % 8) != 0 ||
+        (1LL + a->V) * a->B > 0x7fffffffLL || R * 32 > 0x7fffffffLL || R * a->F / 4 > 0x7fffffffLL)
+        return fail(MAGNET_E_DIM, "magnet_gather_views: bad dims n_slots=%d B=%d V=%d h=%d w=%d F=%d (F must be a multiple of 8)",
+                    a->n_slots, a->B, a->V, a->h, a->w, a->F);
+    if (a->gin_hi && (a->gin_c_off < 0 || (a->gin_c_off % 8) != 0 || (a->gin_ld % 8) != 0 || a->gin_c_off + 256 > a->gin_ld))
+        return fail(MAGNET_E_DIM, "magnet_gather_views: gin_ld=%lld gin_c_off=%d (multiples of 8, gin_c_off + 256 <= gin_ld)",
+                    (long long)a->gin_ld, a->gin_c_off);
+    if (!aligned16(a->pool_feat) || !aligned16(a->pool_xd3_hi) || !aligned16(a->pool_xd3_lo) || !aligned16(a->ref_cl) ||
+        !aligned16(a->src_pad) || !aligned16(a->gin_hi) || !aligned16(a->gin_lo))
+        return fail(MAGNET_E_ALIGN, "magnet_gather_views: features, x_d3 planes and their destinations must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(a->pool_gmm) | reinterpret_cast<uintptr_t>(a->ref_gmm) | reinterpret_cast<uintptr_t>(a->src_gmm) |
+         reinterpret_cast<uintptr_t>(a->slots)) & 3u)
+        return fail(MAGNET_E_ALIGN, "magnet_gather_views: slots and the (mu, sigma) tensors must be 4-byte aligned");
+    hipError_t e = magnet::launch_gather_views(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_gather_views launch");
 }
 
 }  // extern "C"

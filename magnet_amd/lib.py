@@ -202,6 +202,16 @@ class MagnetDnetNllArgs(ctypes.Structure):
                 ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
 
 
+class MagnetGatherViewsArgs(ctypes.Structure):
+    """Mirror of `struct MagnetGatherViewsArgs` (include/magnet_hip.h)."""
+    _fields_ = [("slots", ctypes.c_void_p), ("n_slots", ctypes.c_int32),
+                ("B", ctypes.c_int32), ("V", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("F", ctypes.c_int32),
+                ("feat_dtype", ctypes.c_int32),
+                ("pool_feat", ctypes.c_void_p), ("pool_gmm", ctypes.c_void_p), ("pool_xd3_hi", ctypes.c_void_p), ("pool_xd3_lo", ctypes.c_void_p),
+                ("ref_cl", ctypes.c_void_p), ("src_pad", ctypes.c_void_p), ("ref_gmm", ctypes.c_void_p), ("src_gmm", ctypes.c_void_p),
+                ("gin_hi", ctypes.c_void_p), ("gin_lo", ctypes.c_void_p), ("gin_ld", ctypes.c_int64), ("gin_c_off", ctypes.c_int32)]
+
+
 # (restype, argtypes) of every MAGNET_API declaration of include/magnet_hip.h, in header order; load() applies them all
 _C, _L, _F, _I, _P, _S = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER
 _PROTOS = {
@@ -255,6 +265,7 @@ _PROTOS = {
     "magnet_conv_row_tiles": (_L, [_I, _I, _I, _I, _S(_I)]),
     "magnet_dnet_gauss_head": (_C, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "magnet_gather_views": (_C, [_S(MagnetGatherViewsArgs), _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_fnet_loss_backward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_dnet_loss_workspace": (_L, [_S(MagnetDnetLossArgs)]),
@@ -1185,3 +1196,91 @@ def dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out):
     x, m, o = _dev(head_out, "head_out", torch.float32), _dev(mask_out, "mask_out", torch.float32), _dev(out, "out", torch.float32)
     _launch("magnet_dnet_upsample_gauss", x, x.data_ptr(), int(head_ld), m.data_ptr(), int(mask_ld), int(N), int(h), int(w), o.data_ptr())
     return out
+
+
+# ---- sequence inference (include/magnet_hip.h: magnet_gather_views; csrc/frame_pool.hip; magnet_amd/sequence.py) -------------------
+def gather_views(slots, B, V, pool_feat=None, pool_gmm=None, pool_xd3=None, ref_cl=None, src_pad=None, ref_gmm=None, src_gmm=None,
+                 gin=None):
+    """One launch from the frame pool into a step's input buffers through the device slot table `slots` ((1 + V) B int32: [b] the
+    reference frame of window b, [B + v B + b] its view v; an entry outside [0, n_slots) stands for no frame and gives zeros).
+    pool_feat (n_slots, h+2, w+2, F) fp32 / bf16, pool_gmm (n_slots, 2, h, w) fp32, pool_xd3 = (hi, lo) bf16 planes
+    (n_slots, (h+2)(w+2), 256).  Destinations, each optional: ref_cl (B, h, w, F), src_pad (V B, h+2, w+2, F), ref_gmm (B, 2, h, w),
+    src_gmm (V B, 2, h, w), gin = (hi, lo, ld, c_off): the reference frames' x_d3 into channels [c_off, c_off + 256) of the
+    (B (h+2)(w+2), ld) planes of MAGNET.gnet_input_buffer()."""
+    B, V = int(B), int(V)
+    t = _dev(slots, "slots", torch.int32)
+    if B <= 0 or V < 0 or tuple(t.shape) != ((1 + V) * B,):
+        raise MagnetError(f"gather_views: slots has shape {tuple(t.shape)}, expected ({(1 + V) * B},) for B = {B}, V = {V}")
+    a = MagnetGatherViewsArgs(slots=t.data_ptr(), B=B, V=V)
+    used = [t]
+    n_slots = h = w = None
+
+    def geometry(n, hh, ww, what):
+        nonlocal n_slots, h, w
+        if n_slots is None:
+            n_slots, h, w = int(n), int(hh), int(ww)
+        elif (n_slots, h, w) != (int(n), int(hh), int(ww)):
+            raise MagnetError(f"gather_views: {what} is for {n} slots of {hh} x {ww}, the other pool tensors for {n_slots} of {h} x {w}")
+
+    def dest(x, name, dtype, shape):
+        x = _dev(x, name, dtype)
+        if tuple(x.shape) != shape:
+            raise MagnetError(f"gather_views: {name} has shape {tuple(x.shape)}, expected {shape}")
+        used.append(x)
+        return x.data_ptr()
+
+    if pool_feat is not None:
+        f = _dev(pool_feat, "pool_feat")
+        if f.dim() != 4 or f.shape[1] < 3 or f.shape[2] < 3:
+            raise MagnetError(f"gather_views: pool_feat must be (n_slots, h+2, w+2, F), got {tuple(f.shape)}")
+        geometry(f.shape[0], f.shape[1] - 2, f.shape[2] - 2, "pool_feat")
+        a.pool_feat, a.F, a.feat_dtype = f.data_ptr(), int(f.shape[3]), feat_enum(f.dtype)
+        used.append(f)
+    else:
+        a.F = 8                                                  # no feature destination: any valid width
+    if pool_gmm is not None:
+        g = _dev(pool_gmm, "pool_gmm", torch.float32)
+        if g.dim() != 4 or g.shape[1] != 2:
+            raise MagnetError(f"gather_views: pool_gmm must be (n_slots, 2, h, w), got {tuple(g.shape)}")
+        geometry(g.shape[0], g.shape[2], g.shape[3], "pool_gmm")
+        a.pool_gmm = g.data_ptr()
+        used.append(g)
+    if n_slots is None and pool_xd3 is not None:
+        raise MagnetError("gather_views: the x_d3 planes do not carry h and w: pass pool_feat or pool_gmm with them")
+    if n_slots is None:
+        raise MagnetError("gather_views: no pool tensor given")
+    R = (h + 2) * (w + 2)
+    if pool_xd3 is not None:
+        for x, name in zip(pool_xd3, ("pool_xd3 hi plane", "pool_xd3 lo plane")):
+            x = _dev(x, name, torch.bfloat16)
+            if tuple(x.shape) != (n_slots, R, 256):
+                raise MagnetError(f"gather_views: {name} has shape {tuple(x.shape)}, expected {(n_slots, R, 256)}")
+            used.append(x)
+        a.pool_xd3_hi, a.pool_xd3_lo = pool_xd3[0].data_ptr(), pool_xd3[1].data_ptr()
+    a.n_slots, a.h, a.w = n_slots, h, w
+    if ref_cl is not None or src_pad is not None:
+        if pool_feat is None:
+            raise MagnetError("gather_views: ref_cl / src_pad need pool_feat")
+        if ref_cl is not None:
+            a.ref_cl = dest(ref_cl, "ref_cl", pool_feat.dtype, (B, h, w, a.F))
+        if src_pad is not None:
+            a.src_pad = dest(src_pad, "src_pad", pool_feat.dtype, (V * B, h + 2, w + 2, a.F))
+    if ref_gmm is not None or src_gmm is not None:
+        if pool_gmm is None:
+            raise MagnetError("gather_views: ref_gmm / src_gmm need pool_gmm")
+        if ref_gmm is not None:
+            a.ref_gmm = dest(ref_gmm, "ref_gmm", torch.float32, (B, 2, h, w))
+        if src_gmm is not None:
+            a.src_gmm = dest(src_gmm, "src_gmm", torch.float32, (V * B, 2, h, w))
+    if gin is not None:
+        if pool_xd3 is None:
+            raise MagnetError("gather_views: gin needs pool_xd3")
+        ghi, glo, ld, c_off = gin
+        ld, c_off = int(ld), int(c_off)
+        if ld % 8 or c_off % 8 or c_off < 0 or c_off + 256 > ld:
+            raise MagnetError(f"gather_views: gin pitch {ld} and channel offset {c_off} must be multiples of 8 with c_off + 256 <= pitch")
+        a.gin_hi, a.gin_lo = dest(ghi, "gin hi plane", torch.bfloat16, (B * R, ld)), dest(glo, "gin lo plane", torch.bfloat16, (B * R, ld))
+        a.gin_ld, a.gin_c_off = ld, c_off
+    if any(x.device != t.device for x in used):
+        raise MagnetError("gather_views: all tensors must be on the same device")
+    _launch("magnet_gather_views", t, ctypes.byref(a))
