@@ -269,6 +269,60 @@ __device__ __forceinline__ f32x4_t cv_mma(const bf16x8_t& a, const bf16x8_t& b, 
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
+// The 16-byte fragment read (LDS or global): 8 bf16 / fp16 of one row's K slot
+template <typename V = bf16x8_t>
+__device__ __forceinline__ V ld_frag(const void* ptr) { return __builtin_bit_cast(V, *reinterpret_cast<const uint4*>(ptr)); }
+
+// The step between a LOAD phase and the reads of what it waited for: all but the N newest DMA pieces of this wave have landed and its
+// LDS reads have returned, then the workgroup barrier.  SCHED: nothing may be scheduled across the step in either direction (WIN == 4);
+// FENCE: a trailing compiler fence, so that no LDS access is hoisted above the barrier (WIN == 2, 4 waves).
+template <int N, bool SCHED = false, bool FENCE = false>
+__device__ __forceinline__ void wait_barrier() {
+    if constexpr (SCHED) __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+    __builtin_amdgcn_s_barrier();
+    if constexpr (SCHED) __builtin_amdgcn_sched_barrier(0);
+    if constexpr (FENCE) asm volatile("" ::: "memory");
+}
+
+// Position of a staging stream in the K loop's step order (K chunk outer, `i` inner): i = tap row of a window stream, tap of a
+// weight stream.  advance(n) steps to the next of the n inner positions and says whether it moved on to the next K chunk.
+struct StepCounter {
+    int i = 0, k0 = 0;
+    __device__ __forceinline__ bool advance(int n) {
+        const bool wrap = ++i == n;
+        if (wrap) { i = 0; k0 += CV_BK; }
+        return wrap;
+    }
+};
+
+// LDS layout of the K loop's ring for one kernel instance.  conv_mfma_tile places its slots with these constants and launch_conv_nf
+// asks for TOTAL bytes, so the launcher's byte count is the kernel's by construction (a mismatch would be an out-of-bounds LDS-DMA).
+// A window slot is the [hi | lo] planes of AW_ROWS rows (a plain A tile: CV_BM rows); a weight slot the [hi | lo] planes of BN rows.
+//   WIN == 0: 2*SPB stages of [window | weights], interleaved         WIN == 1: 2 window slots, then 2 weight slots
+//   WIN == 2: 1 window slot, then a 3-slot weight ring                 WIN == 4: 2 x {window, scales of its rows [512] u32}, a 4-slot ring
+//   of fp16 weight planes, then 2 x {3 taps x qr weight tile, weight scales [512] u32, 16 zero bytes (block 3 of the weight operand)}
+template <int NF, int WN, int BM, int SPB, int NT, bool PP, int WIN>
+struct ConvLds {
+    static_assert(WIN != 4 || PP, "the fp16 + e4m3 format exists on the ping-pong loop only");
+    static constexpr int BN = NF * 16;
+    static constexpr int AW_ROWS = WIN ? BM + 8 : BM;             // window: up to (3-1)*2 extra rows (dilation 2), padded to 8
+    static constexpr int A_BYTES = AW_ROWS * CV_ROW, B_BYTES = BN * CV_ROW;       // one plane of a window / of a weight tile
+    static constexpr int SC_BYTES = WIN == 4 ? 512 * 4 : 0;
+    static constexpr int AW_BYTES = 2 * A_BYTES + SC_BYTES;       // window slot
+    static constexpr int BW_BYTES = WIN == 4 ? B_BYTES : 2 * B_BYTES;             // weight slot
+    static constexpr int QB_ZERO = 3 * B_BYTES + SC_BYTES, QB_BYTES = WIN == 4 ? QB_ZERO + 16 : 0;
+    static constexpr int A_SLOTS = WIN == 2 ? 1 : WIN == 0 ? 2 * SPB : 2;
+    static constexpr int B_SLOTS = WIN == 4 ? 4 : WIN == 2 ? 3 : 2 * SPB;
+    static constexpr int A_STRIDE = WIN ? AW_BYTES : AW_BYTES + BW_BYTES;         // bytes from a window slot to the next
+    static constexpr int B_STRIDE = WIN ? BW_BYTES : AW_BYTES + BW_BYTES;         // bytes from a weight slot to the next
+    static constexpr int B_RING = WIN ? A_SLOTS * AW_BYTES : AW_BYTES;            // first weight slot
+    static constexpr int RING_BYTES = A_SLOTS * AW_BYTES + B_SLOTS * BW_BYTES + 2 * QB_BYTES;
+    static constexpr int QB_BASE = RING_BYTES - 2 * QB_BYTES;
+    static constexpr int EPI_BYTES = (NT / 64) * 16 * ((NF / WN) * 16 + 4) * 4;   // the plain epilogue's staging rows (SROW floats per row)
+    static constexpr int TOTAL = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
+};
+
 // TAIL = 0: plain layer.  TAIL = 16-column fragments of the fused tail's last layer (1, 8 or 9): see ConvParams::tail_*.
 // PP = "ping-pong" K loop: NT = 512 threads = 8 waves = two wave groups (waves 0-3 / 4-7: one wave of each group per SIMD) that
 // run the same program half a K step apart — while one group issues its fragment reads and the LDS-DMA of the stage two steps
@@ -295,18 +349,16 @@ __device__ __forceinline__ f32x4_t cv_mma(const bf16x8_t& a, const bf16x8_t& b, 
 template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN>
 __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsigned bid, const unsigned n_tiles, const unsigned by, const int tid) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-descriptor builtins do not exist in the host pass (which only needs the stub)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // ring of 2*SPB stages (declared here, not passed in: a pointer
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the K loop's ring (ConvLds; declared here, not passed in: a pointer
                                                                             // parameter is a generic pointer, and its casts to LDS pointers get null checks)
-    constexpr int BN = NF * 16;
-    constexpr int RP = NT / 4;                        // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
+    using L = ConvLds<NF, WN, CV_BM, SPB, NT, PP, WIN>;
+    constexpr int BN = L::BN, A_BYTES = L::A_BYTES, B_BYTES = L::B_BYTES;
+    constexpr int RP = NT / 4;                      // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
     constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (2 or 4)
     constexpr int WM = (NT / 64) / WN;                // waves along M
     constexpr int MF = CV_BM / (WM * 16);             // M fragments per wave (2 or 4)
     constexpr int NFW = NF / WN;                      // N fragments per wave
     static_assert(NF % WN == 0, "N fragments must split evenly over the waves");
-    constexpr int AW_ROWS = WIN ? CV_BM + 8 : CV_BM;           // window: up to (3-1)*2 extra rows (dilation 2), padded to 8
-    constexpr int A_BYTES = AW_ROWS * CV_ROW, B_BYTES = BN * CV_ROW;
-    constexpr int STAGE_BYTES = 2 * A_BYTES + 2 * B_BYTES;    // hi + lo planes of A and B
     const int lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN;
     // XCD-aware tile order: hardware deals consecutive block ids round-robin to the 8 XCDs; remap so each XCD (one
@@ -363,30 +415,43 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
     for (int i = 0; i < A_PT; ++i) a_v[i] = (((int)(row0 - base_row) + st_r + i * RP) * p.in_ld + st_k) * 2;
 #pragma unroll
     for (int i = 0; i < B_PT; ++i) b_v[i] = ((n0 + st_r + i * RP) * p.cin + st_k) * 2;
-    int pf_tap = 0, pf_ty = 0, pf_tx = 0, pf_k0 = 0;           // (tap = ty*n+tx, first channel) of the next stage to fetch
     typedef void __attribute__((address_space(3)))* lptr_t;
 #define CV_BLDS(rsrc, lp, voff) __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr_t)(lp), 16, (voff), 0, 0, 0)
-#define CV_DMA(S, BUF)                                                                                 \
-    {                                                                                                  \
-        unsigned char* sa_hi = smem + (BUF) * STAGE_BYTES;                                             \
-        unsigned char* sa_lo = sa_hi + A_BYTES;                                                        \
-        unsigned char* sb_hi = sa_hi + 2 * A_BYTES;                                                    \
-        unsigned char* sb_lo = sb_hi + B_BYTES;                                                        \
-        const int a_u = (((pf_ty + p.tap_o0) * p.tap_sy + (pf_tx + p.tap_o0) * p.tap_sx) * p.in_ld + pf_k0) * 2;    \
-        const int b_u = (pf_tap * p.cout_pad * p.cin + pf_k0) * 2;                                     \
-        _Pragma("unroll") for (int i = 0; i < A_PT; ++i) {                                             \
-            CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);                        \
-            CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);                        \
-        }                                                                                              \
-        _Pragma("unroll") for (int i = 0; i < B_PT; ++i) {                                             \
-            if (st_r + i * RP < BN) {                                                                  \
-                CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);                    \
-                CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);                    \
-            }                                                                                          \
-        }                                                                                              \
-        ++pf_tap;                                                                                      \
-        if (++pf_tx == p.tap_n) { pf_tx = 0; if (++pf_ty == p.tap_n) { pf_ty = 0; pf_tap = 0; pf_k0 += CV_BK; } }   \
-    }
+    // ---- the building blocks of every K loop below; the loops differ in their schedule only ----
+    auto win_slot = [&](int s) { return smem + s * L::A_STRIDE; };                  // ConvLds: the layout
+    auto wt_slot = [&](int s) { return smem + L::B_RING + s * L::B_STRIDE; };
+    // wave-uniform byte offset of the window (or plain A tile) of tap (ty, tx), K chunk from k0 on.  (The weight tile's offset,
+    // (tap * cout_pad * cin + k0) * 2, is spelled at its stage_weights calls: in a helper that takes `tap` by value the compiler
+    // associates the product the other way round and every prologue changes.)
+    auto a_step = [&](int ty, int tx, int k0) { return (((ty + p.tap_o0) * p.tap_sy + (tx + p.tap_o0) * p.tap_sx) * p.in_ld + k0) * 2; };
+    // hi / lo DMA pieces of a row window of `aw` rows into the slot at sa_hi; the aw - CV_BM rows past the tile are a few lanes of wave 0
+    // (two more pieces for its counted waits).  A plain A tile is a window of CV_BM rows.
+    auto stage_window = [&](unsigned char* sa_hi, const int a_u, const int aw) {
+        unsigned char* sa_lo = sa_hi + A_BYTES;
+#pragma unroll
+        for (int i = 0; i < A_PT; ++i) {
+            CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
+            CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
+        }
+        if constexpr (WIN != 0) {
+            if (wv == 0 && st_r < aw - CV_BM) {
+                const int ax = a_v[0] + CV_BM * p.in_ld * 2;
+                CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
+                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
+            }
+        }
+    };
+    // hi / lo DMA pieces of a weight tile; the last row pass is partial only where BN is no multiple of the rows of a pass
+    auto stage_weights = [&](unsigned char* sb_hi, unsigned char* sb_lo, const int b_u) {
+#pragma unroll
+        for (int i = 0; i < B_PT; ++i) {
+            if constexpr (BN % RP != 0) {
+                if (st_r + i * RP >= BN) continue;
+            }
+            CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
+            CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
+        }
+    };
 
     f32x4_t acc[MF][NFW];
 #pragma unroll
@@ -416,31 +481,39 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
     const int a_off = cv_swz(wm * (MF * 16) + frow, lane >> 4);       // + m*16*CV_ROW
     const int b_off = cv_swz(wn * (NFW * 16) + frow, lane >> 4);      // + n*16*CV_ROW
 
-    // one K stage of MFMAs from ring slot BUF
-    auto compute = [&](int buf) {
-        const unsigned char* sa_hi = smem + buf * STAGE_BYTES;
-        const unsigned char* sa_lo = sa_hi + A_BYTES;
-        const unsigned char* sb_hi = sa_hi + 2 * A_BYTES;
-        const unsigned char* sb_lo = sb_hi + B_BYTES;
+    // fragment rows of a window shifted by tx*tap_sx: the swizzle term follows the ACTUAL LDS row, so one offset per tx
+    int a_offx[3];
+#pragma unroll
+    for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
+
+    // the split product of one fragment column n: term-major order — consecutive MFMAs write DIFFERENT accumulators (a dependent
+    // MFMA on the same accumulator waits out the full pipeline latency); small terms first
+    auto mma3 = [&](const int n, const bf16x8_t (&ah)[MF], const bf16x8_t (&al)[MF], const bf16x8_t bh, const bf16x8_t bl) {
+#pragma unroll
+        for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(al[m], bh, acc[m][n]);
+#pragma unroll
+        for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ah[m], bl, acc[m][n]);
+#pragma unroll
+        for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ah[m], bh, acc[m][n]);
+    };
+    // fragment reads of a weight slot's NFW columns
+    auto load_b = [&](const unsigned char* sb_hi, bf16x8_t (&fbh)[NFW], bf16x8_t (&fbl)[NFW]) {
+#pragma unroll
+        for (int n = 0; n < NFW; ++n) {
+            fbh[n] = ld_frag(sb_hi + b_off + n * 16 * CV_ROW);
+            fbl[n] = ld_frag(sb_hi + B_BYTES + b_off + n * 16 * CV_ROW);
+        }
+    };
+    // one K stage of MFMAs: window (or A tile) slot at sa_hi read at fragment offset a_of, weight slot at sb_hi
+    auto compute = [&](const unsigned char* sa_hi, const unsigned char* sb_hi, const int a_of) {
         bf16x8_t ah[MF], al[MF];
 #pragma unroll
         for (int m = 0; m < MF; ++m) {
-            ah[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_hi + a_off + m * 16 * CV_ROW));
-            al[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_lo + a_off + m * 16 * CV_ROW));
+            ah[m] = ld_frag(sa_hi + a_of + m * 16 * CV_ROW);
+            al[m] = ld_frag(sa_hi + A_BYTES + a_of + m * 16 * CV_ROW);
         }
 #pragma unroll
-        for (int n = 0; n < NFW; ++n) {
-            const bf16x8_t bh = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-            const bf16x8_t bl = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
-            // term-major order: consecutive MFMAs write DIFFERENT accumulators (a dependent MFMA on the same
-            // accumulator waits out the full pipeline latency); small terms first
-#pragma unroll
-            for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(al[m], bh, acc[m][n]);
-#pragma unroll
-            for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ah[m], bl, acc[m][n]);
-#pragma unroll
-            for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ah[m], bh, acc[m][n]);
-        }
+        for (int n = 0; n < NFW; ++n) mma3(n, ah, al, ld_frag(sb_hi + b_off + n * 16 * CV_ROW), ld_frag(sb_hi + B_BYTES + b_off + n * 16 * CV_ROW));
     };
 
     if constexpr (WIN == 4 && PP) {
@@ -458,64 +531,41 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         // sub-step reads only the fragments it multiplies — tx = 0: f16; tx = 1: f16 + term lo_x * hi_w; tx = 2: f16 + term hi_x * lo_w.
         static_assert(NT == 512 && SPB == 1 && BN % RP == 0 && CV_BM % RP == 0 && B_PT == 1, "8 waves, whole DMA passes");
         constexpr int AP = 2 * A_PT;
-        constexpr int QB_ZERO = 3 * B_BYTES + 512 * 4;                    // 16 zero bytes behind the scales: block 3 of the weight operand
-        constexpr int QB_BYTES = QB_ZERO + 16;
-        constexpr int AW_BYTES = 2 * A_BYTES + 512 * 4;                   // [f16 | qr] window + the scales of its rows [512] u32
-        unsigned char* const a_base = smem;                               // 2 x window
-        unsigned char* const b_ring = smem + 2 * AW_BYTES;                // 4 x f16 weight tile (prefetch distance 3 sub-steps)
-        unsigned char* const qb_base = b_ring + 4 * B_BYTES;              // 2 x {3 taps x qr weight tile, weight scales [512] u32, zeros}
+        constexpr int QB_ZERO = L::QB_ZERO, QB_BYTES = L::QB_BYTES;
+        unsigned char* const qb_base = smem + L::QB_BASE;
         const int aw = CV_BM + 2 * p.tap_sx;
         const int ngroups = 3 * ksteps_per_tap;
-        int g_ty = 0, g_k0 = 0, bs_tap = 0, bs_k0 = 0, q_ty = 0, q_k0 = 0;
+        StepCounter gw, bs, gq;                                             // next window (i = ty) / f16 weight tile (i = tap) / qr weights (i = ty)
         // buffers of the scales: activations [chunk][rows] u32 {E8M0 of q, E8M0 of r, 0, 0}; weights [tap][chunk][cout_pad] u32
         const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in_sc + base_row), 0,
                                                                               (int)(((long long)(p.cin / 32 - 1) * p.sc_rows + (end_row - base_row)) * 4), flags);
         const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_sc, 0, p.taps * (p.cin / 32) * p.cout_pad * 4, flags);
-        auto dma_a = [&](int buf) {                                       // window of group g_ty/g_k0: f16 plane, qr plane, scales
-            unsigned char* sa_hi = a_base + buf * AW_BYTES;
-            unsigned char* sa_lo = sa_hi + A_BYTES;
-            const int a_u = (((g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx) * p.in_ld + g_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < A_PT; ++i) {
-                CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-                CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-            }
-            if (wv == 0 && st_r < aw - CV_BM) {
-                const int ax = a_v[0] + CV_BM * p.in_ld * 2;
-                CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
-            }
+        auto dma_a = [&](int buf) {                                       // window of group gw: f16 plane, qr plane, scales
+            unsigned char* sa_hi = win_slot(buf);
+            stage_window(sa_hi, a_step(gw.i, 0, gw.k0), aw);
             // scales of window rows [0, 512): one dword per lane, wave w rows 64 w .. 64 w + 63 (rows past the window read as 0 or are never used)
-            const int srow = (int)(row0 - base_row) + (g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx + wv * 64 + lane;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lptr_t)(sa_hi + 2 * A_BYTES + wv * 256), 4, (srow + (g_k0 / 32) * (int)p.sc_rows) * 4, 0, 0, 0);
-            if (++g_ty == 3) { g_ty = 0; g_k0 += CV_BK; }
+            const int srow = (int)(row0 - base_row) + (gw.i + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx + wv * 64 + lane;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lptr_t)(sa_hi + 2 * A_BYTES + wv * 256), 4, (srow + (gw.k0 / 32) * (int)p.sc_rows) * 4, 0, 0, 0);
+            gw.advance(3);
         };
-        auto dma_b = [&](int slot) {                                      // f16 weight tile of the next sub-step
-            unsigned char* sb_hi = b_ring + slot * B_BYTES;
-            const int b_u = (bs_tap * p.cout_pad * p.cin + bs_k0) * 2;
-            CV_BLDS(rb_hi, sb_hi + wave_row * CV_ROW, b_v[0] + b_u);
-            if (++bs_tap == 9) { bs_tap = 0; bs_k0 += CV_BK; }
+        auto dma_b = [&](int slot) {                                      // f16 weight tile of the next sub-step (no lo plane: see dma_q)
+            CV_BLDS(rb_hi, wt_slot(slot) + wave_row * CV_ROW, b_v[0] + (bs.i * p.cout_pad * p.cin + bs.k0) * 2);
+            bs.advance(9);
         };
-        auto dma_q = [&](int buf) {                                       // qr weight tiles of the three taps of group q_ty/q_k0 + their scales
+        auto dma_q = [&](int buf) {                                       // qr weight tiles of the three taps of group gq + their scales
             unsigned char* qb = qb_base + buf * QB_BYTES;
 #pragma unroll
-            for (int tx = 0; tx < 3; ++tx) {
-                const int b_u = ((q_ty * 3 + tx) * p.cout_pad * p.cin + q_k0) * 2;
-                CV_BLDS(rb_lo, qb + tx * B_BYTES + wave_row * CV_ROW, b_v[0] + b_u);
-            }
+            for (int tx = 0; tx < 3; ++tx) CV_BLDS(rb_lo, qb + tx * B_BYTES + wave_row * CV_ROW, b_v[0] + ((gq.i * 3 + tx) * p.cout_pad * p.cin + gq.k0) * 2);
             // scales [3][BN]: 3 * BN dwords of the 512-dword field; wave w fetches entries 64 w .. 64 w + 63 (past 3 * BN: out of range -> 0)
             const int e = wv * 64 + lane, tx = e / BN, col = e - tx * BN;
-            const int so = e < 3 * BN ? (((q_ty * 3 + tx) * (p.cin / 32) + q_k0 / 32) * p.cout_pad + n0 + col) * 4 : 0x7ffffff0;
+            const int so = e < 3 * BN ? (((gq.i * 3 + tx) * (p.cin / 32) + gq.k0 / 32) * p.cout_pad + n0 + col) * 4 : 0x7ffffff0;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lptr_t)(qb + 3 * B_BYTES + wv * 256), 4, so, 0, 0, 0);
-            if (++q_ty == 3) { q_ty = 0; q_k0 += CV_BK; }
+            gq.advance(3);
         };
         // fragment addresses.  f16 window / weights: as the bf16 hi plane.  Correction operands: lane (r = lane & 15, g = lane >> 4)
         // holds 16 bytes of block g >> 1 (tap tx = g >> 1, channels 16 (g & 1) ..) and 16 bytes of block 2 + (g >> 1) (g < 2: tap 2;
         // g >= 2: block 3 — the weight side reads zeros, the activation side re-reads its first half: finite bytes x 0)
         const int g4 = lane >> 4, gh = g4 >> 1, gl = g4 & 1;
-        int a_offx[3];
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, g4);
         int xq_off[2], xr_off[2];                                         // [half] within the qr window (slots 0, 1 = q; 2, 3 = r)
         {
             const int r1 = wm * (MF * 16) + frow + gh * p.tap_sx, r2 = g4 < 2 ? wm * (MF * 16) + frow + 2 * p.tap_sx : r1;
@@ -537,11 +587,11 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             return i32x8_t{(int)u0.x, (int)u0.y, (int)u0.z, (int)u0.w, (int)u1.x, (int)u1.y, (int)u1.z, (int)u1.w};
         };
         auto load_f16 = [&](const unsigned char* win, int slot, int tx) {
-            const unsigned char* sb_hi = b_ring + slot * B_BYTES;
+            const unsigned char* sb_hi = wt_slot(slot);
 #pragma unroll
-            for (int m = 0; m < MF; ++m) ah[m] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(win + a_offx[tx] + m * 16 * CV_ROW));
+            for (int m = 0; m < MF; ++m) ah[m] = ld_frag<f16x8_t>(win + a_offx[tx] + m * 16 * CV_ROW);
 #pragma unroll
-            for (int n = 0; n < NFW; ++n) fbh[n] = __builtin_bit_cast(f16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
+            for (int n = 0; n < NFW; ++n) fbh[n] = ld_frag<f16x8_t>(sb_hi + b_off + n * 16 * CV_ROW);
         };
         // 16 f16 MFMAs (main term of this tap) + the correction MFMAs of fragment columns [a0, a1) of term 1 (hi_w x lo_x) and [b0, b1) of
         // term 2 (lo_w x hi_x).  Operands swapped as in cv_mma<true> (weights = A): C^T accumulators.  Scale bytes: 0 = hi (q), 1 = lo (r).
@@ -581,11 +631,6 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             wsc[n] = *reinterpret_cast<const int*>(qb + ws_off + n * 16 * 4);
         };
         auto ld_wr = [&](const unsigned char* qb, const int n) { wr[n] = ld8(qb + wr_off0 + n * 16 * CV_ROW, qb + wr_off1 + n * wn_str); };
-#define CV_END_LOAD(N)                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");                    \
-        __builtin_amdgcn_s_barrier();                                                          \
-        __builtin_amdgcn_sched_barrier(0);
         const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
         if (tid < 8) reinterpret_cast<uint32_t*>(qb_base + (tid >> 2) * QB_BYTES + QB_ZERO)[tid & 3] = 0u;
         // Prefetch distances.  The compute phases are short now (tx = 0: 16 MFMAs), so an f16 weight tile is fetched THREE sub-steps
@@ -605,7 +650,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         int bslot = 0;                                                    // ring slot of the sub-step being read
         for (int g = 0; g < ngroups; ++g) {
             const bool lastg = g + 1 == ngroups;
-            const unsigned char* win = a_base + (g & 1) * AW_BYTES;
+            const unsigned char* win = win_slot(g & 1);
             const unsigned char* qb = qb_base + (g & 1) * QB_BYTES;
             // ---- tx = 0: main term + term 1 of columns 0, 1 ----
             asm volatile("" ::: "memory");
@@ -618,8 +663,8 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             ld_wq(qb, 0); ld_wq(qb, 1);
             if (!lastg) {
                 dma_a((g + 1) & 1); dma_q((g + 1) & 1); dma_b((bslot + 3) & 3);
-                if (wv == 0) { CV_END_LOAD(AP + 5 + 2 + 2) } else { CV_END_LOAD(AP + 5 + 2) }
-            } else { CV_END_LOAD(0) }
+                if (wv == 0) wait_barrier<AP + 5 + 2 + 2, true>(); else wait_barrier<AP + 5 + 2, true>();
+            } else wait_barrier<0, true>();
             mfmas(0, 2, 0, 0);
             bslot = (bslot + 1) & 3;
             // ---- tx = 1: main term + term 1 of columns 2, 3 + term 2 of column 0 ----
@@ -631,20 +676,19 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             ld_wr(qb, 0);
             if (!lastg) {
                 dma_b((bslot + 3) & 3);
-                if (wv == 0) { CV_END_LOAD(AP + 5 + 2 + 2) } else { CV_END_LOAD(AP + 5 + 2) }
-            } else { CV_END_LOAD(0) }
+                if (wv == 0) wait_barrier<AP + 5 + 2 + 2, true>(); else wait_barrier<AP + 5 + 2, true>();
+            } else wait_barrier<0, true>();
             mfmas(2, 4, 0, 1);
             bslot = (bslot + 1) & 3;
             // ---- tx = 2: main term + term 2 of columns 1, 2, 3 ----
             asm volatile("" ::: "memory");
             load_f16(win, bslot, 2);
             ld_wr(qb, 1); ld_wr(qb, 2); ld_wr(qb, 3);
-            if (!lastg) { dma_b((bslot + 3) & 3); CV_END_LOAD(2) }
-            else { CV_END_LOAD(0) }
+            if (!lastg) { dma_b((bslot + 3) & 3); wait_barrier<2, true>(); }
+            else wait_barrier<0, true>();
             mfmas(0, 0, 1, 4);
             bslot = (bslot + 1) & 3;
         }
-#undef CV_END_LOAD
         if (grp == 0) __builtin_amdgcn_s_barrier();                       // balance group 1's extra barrier
         __syncthreads();                                                  // nothing in flight; the ring is dead
     } else
@@ -657,78 +701,29 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         // slot is refilled in the L phase after the one whose reads of it retired before a barrier both groups passed.
         static_assert(NT == 512 && SPB == 1 && BN % RP == 0 && CV_BM % RP == 0, "8 waves, whole DMA passes");
         constexpr int BP = 2 * B_PT, AP = 2 * A_PT;
-        unsigned char* const a_win = smem;
-        unsigned char* const b_ring = smem + 2 * A_BYTES;
         const int aw = CV_BM + 2 * p.tap_sx;
         const int ngroups = 3 * ksteps_per_tap;
-        int g_ty = 0, g_k0 = 0, bs_tap = 0, bs_k0 = 0;
-        auto dma_a = [&]() {
-            unsigned char* sa_hi = a_win;
-            unsigned char* sa_lo = sa_hi + A_BYTES;
-            const int a_u = (((g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx) * p.in_ld + g_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < A_PT; ++i) {
-                CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-                CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-            }
-            if (wv == 0 && st_r < aw - CV_BM) {
-                const int ax = a_v[0] + CV_BM * p.in_ld * 2;
-                CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
-            }
-            if (++g_ty == 3) { g_ty = 0; g_k0 += CV_BK; }
-        };
-        auto dma_b = [&](int slot) {
-            unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            unsigned char* sb_lo = sb_hi + B_BYTES;
-            const int b_u = (bs_tap * p.cout_pad * p.cin + bs_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < B_PT; ++i) {
-                CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-            }
-            if (++bs_tap == 9) { bs_tap = 0; bs_k0 += CV_BK; }
-        };
-        int a_offx[3];
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
+        StepCounter gw, bs;                                   // next window (i = ty) / weight tile (i = tap) to fetch
+        auto dma_a = [&]() { stage_window(win_slot(0), a_step(gw.i, 0, gw.k0), aw); gw.advance(3); };
+        auto dma_b = [&](int slot) { stage_weights(wt_slot(slot), wt_slot(slot) + B_BYTES, (bs.i * p.cout_pad * p.cin + bs.k0) * 2); bs.advance(9); };
         bf16x8_t ah[3][MF], al[3][MF], fbh[NFW], fbl[NFW];
-        auto load_b = [&](int slot) {
-            const unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            const unsigned char* sb_lo = sb_hi + B_BYTES;
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                fbh[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-                fbl[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
-            }
-        };
-        auto load_win = [&]() {
+        auto load_win = [&]() {                               // window g -> registers, all three tx
 #pragma unroll
             for (int tx = 0; tx < 3; ++tx)
 #pragma unroll
                 for (int m = 0; m < MF; ++m) {
-                    ah[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + a_offx[tx] + m * 16 * CV_ROW));
-                    al[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + A_BYTES + a_offx[tx] + m * 16 * CV_ROW));
+                    ah[tx][m] = ld_frag(win_slot(0) + a_offx[tx] + m * 16 * CV_ROW);
+                    al[tx][m] = ld_frag(win_slot(0) + A_BYTES + a_offx[tx] + m * 16 * CV_ROW);
                 }
         };
         auto mfmas = [&](const bf16x8_t (&xh)[MF], const bf16x8_t (&xl)[MF]) {
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xl[m], fbh[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], fbl[n], acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], fbh[n], acc[m][n]);
-            }
+            for (int n = 0; n < NFW; ++n) mma3(n, xh, xl, fbh[n], fbl[n]);
             __builtin_amdgcn_s_setprio(0);
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
         };
-#define CV_END_LOAD(N)                                                                         \
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");                    \
-        __builtin_amdgcn_s_barrier();
         const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
         dma_a();
         dma_b(0);
@@ -741,26 +736,25 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             // ---- tx = 0 ----
             asm volatile("" ::: "memory");
             load_win();
-            load_b(0);
+            load_b(wt_slot(0), fbh, fbl);
             dma_b(2);                                         // stage 3g + 2
-            CV_END_LOAD(BP)                                   // stage 3g + 1 landed
+            wait_barrier<BP>();                               // stage 3g + 1 landed
             mfmas(ah[0], al[0]);
             // ---- tx = 1 ----
             asm volatile("" ::: "memory");
-            load_b(1);
+            load_b(wt_slot(1), fbh, fbl);
             if (!lastg) {
                 dma_b(0); dma_a();                            // stage 3g + 3, window g + 1
-                if (wv == 0) { CV_END_LOAD(BP + AP + 2) } else { CV_END_LOAD(BP + AP) }      // stage 3g + 2 landed
-            } else { CV_END_LOAD(0) }
+                if (wv == 0) wait_barrier<BP + AP + 2>(); else wait_barrier<BP + AP>();      // stage 3g + 2 landed
+            } else wait_barrier<0>();
             mfmas(ah[1], al[1]);
             // ---- tx = 2 ----
             asm volatile("" ::: "memory");
-            load_b(2);
-            if (!lastg) { dma_b(1); CV_END_LOAD(BP) }         // stage 3g + 4; stage 3g + 3 and window g + 1 landed
-            else { CV_END_LOAD(0) }
+            load_b(wt_slot(2), fbh, fbl);
+            if (!lastg) { dma_b(1); wait_barrier<BP>(); }     // stage 3g + 4; stage 3g + 3 and window g + 1 landed
+            else wait_barrier<0>();
             mfmas(ah[2], al[2]);
         }
-#undef CV_END_LOAD
         if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
         __syncthreads();                                      // nothing in flight; the ring is dead
     } else
@@ -779,164 +773,62 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         // ONE piece per wave, so the counted waits stay wave-uniform (row-pass staging would give waves 2 and 3 nothing to count)
         constexpr int BP = BN == 32 ? 1 : 2 * B_PT;           // weight-tile DMA instructions per wave and stage
         constexpr int AP = 2 * A_PT;                          // window DMA instructions per wave (wave 0: + 2 for the rows past the tile)
-        unsigned char* const a_win = smem;                    // [hi | lo], AW_ROWS rows each
-        unsigned char* const b_ring = smem + 2 * A_BYTES;     // 3 x [hi | lo]
         const int aw = CV_BM + 2 * p.tap_sx;
         const int ngroups = 3 * ksteps_per_tap;               // (K chunk, ty) pairs, ty inner
-        int g_ty = 0, g_k0 = 0, bs_tap = 0, bs_k0 = 0;
-        auto dma_a = [&]() {
-            unsigned char* sa_hi = a_win;
-            unsigned char* sa_lo = sa_hi + A_BYTES;
-            const int a_u = (((g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx) * p.in_ld + g_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < A_PT; ++i) {
-                CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-                CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-            }
-            if (wv == 0 && st_r < aw - CV_BM) {
-                const int ax = a_v[0] + CV_BM * p.in_ld * 2;
-                CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
-            }
-            if (++g_ty == 3) { g_ty = 0; g_k0 += CV_BK; }
-        };
+        StepCounter gw, bs;                                   // next window (i = ty) / weight tile (i = tap) to fetch
+        auto dma_a = [&]() { stage_window(win_slot(0), a_step(gw.i, 0, gw.k0), aw); gw.advance(3); };
         const int b_v32 = ((n0 + (wv >> 1) * 16 + (lane >> 2)) * p.cin + st_k) * 2;       // BN = 32: this wave's 16 weight rows
         auto dma_b = [&](int slot) {
-            unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            unsigned char* sb_lo = sb_hi + B_BYTES;
-            const int b_u = (bs_tap * p.cout_pad * p.cin + bs_k0) * 2;
+            unsigned char* sb_hi = wt_slot(slot);
+            const int b_u = (bs.i * p.cout_pad * p.cin + bs.k0) * 2;
             if constexpr (BN == 32) {
-                if (wv & 1) CV_BLDS(rb_lo, sb_lo + (wv >> 1) * 16 * CV_ROW, b_v32 + b_u);
+                if (wv & 1) CV_BLDS(rb_lo, sb_hi + B_BYTES + (wv >> 1) * 16 * CV_ROW, b_v32 + b_u);
                 else        CV_BLDS(rb_hi, sb_hi + (wv >> 1) * 16 * CV_ROW, b_v32 + b_u);
-            } else {
-#pragma unroll
-                for (int i = 0; i < B_PT; ++i) {
-                    CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                    CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                }
-            }
-            if (++bs_tap == 9) { bs_tap = 0; bs_k0 += CV_BK; }
+            } else stage_weights(sb_hi, sb_hi + B_BYTES, b_u);
+            bs.advance(9);
         };
-        int a_offx[3];
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
         bf16x8_t ah[3][MF], al[3][MF];
         auto mfma_b = [&](int slot, const bf16x8_t (&xh)[MF], const bf16x8_t (&xl)[MF]) {
-            const unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            const unsigned char* sb_lo = sb_hi + B_BYTES;
             bf16x8_t fbh[NFW], fbl[NFW];
+            load_b(wt_slot(slot), fbh, fbl);
 #pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                fbh[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-                fbl[n] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
-            }
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                const bf16x8_t bh = fbh[n], bl = fbl[n];
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xl[m], bh, acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], bl, acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(xh[m], bh, acc[m][n]);
-            }
+            for (int n = 0; n < NFW; ++n) mma3(n, xh, xl, fbh[n], fbl[n]);
         };
-#define CV_WAIT_BARRIER(N)                                                                     \
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");                    \
-        __builtin_amdgcn_s_barrier();                                                          \
-        asm volatile("" ::: "memory");
         dma_a();
         dma_b(0);
         dma_b(1);
         for (int g = 0; g < ngroups; ++g) {
             const bool lastg = g + 1 == ngroups;
             // ---- tx = 0: stage 3g (slot 0) and window g have landed; refill slot 2 with stage 3g + 2 ----
-            CV_WAIT_BARRIER(BP)
+            wait_barrier<BP, false, true>();
             dma_b(2);
+            // window g -> registers (spelled out here and a lambda in the 8-wave loop, as they were before the building blocks
+            // were shared: in the other form either loop is scheduled differently)
 #pragma unroll
             for (int tx = 0; tx < 3; ++tx)
 #pragma unroll
                 for (int m = 0; m < MF; ++m) {
-                    ah[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + a_offx[tx] + m * 16 * CV_ROW));
-                    al[tx][m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(a_win + A_BYTES + a_offx[tx] + m * 16 * CV_ROW));
+                    ah[tx][m] = ld_frag(win_slot(0) + a_offx[tx] + m * 16 * CV_ROW);
+                    al[tx][m] = ld_frag(win_slot(0) + A_BYTES + a_offx[tx] + m * 16 * CV_ROW);
                 }
             mfma_b(0, ah[0], al[0]);
             // ---- tx = 1: every wave holds window g in registers (lgkmcnt(0) before the barrier): fetch window g + 1 ----
-            CV_WAIT_BARRIER(BP)
+            wait_barrier<BP, false, true>();
             if (!lastg) { dma_b(0); dma_a(); }
             mfma_b(1, ah[1], al[1]);
             // ---- tx = 2 (the window's pieces, issued after the weight pieces, stay in flight) ----
-            if (!lastg) { CV_WAIT_BARRIER(BP + AP) dma_b(1); }
-            else { CV_WAIT_BARRIER(0) }
+            if (!lastg) { wait_barrier<BP + AP, false, true>(); dma_b(1); }
+            else wait_barrier<0, false, true>();
             mfma_b(2, ah[2], al[2]);
         }
-#undef CV_WAIT_BARRIER
         __syncthreads();                                      // nothing in flight; the ring is dead (the epilogue reuses it)
     } else if constexpr (WIN == 1) {
         static_assert(!PP && SPB == 1, "row-window loop: 2-slot ring");
-        // LDS: [A window slot 0 | A window slot 1 | B slot 0 | B slot 1], each hi + lo
-        unsigned char* const a_ring = smem;
-        unsigned char* const b_ring = smem + 2 * (2 * A_BYTES);
         const int aw = CV_BM + (p.tap_n - 1) * p.tap_sx;      // window rows of this layer
         const int ngroups = p.tap_n * ksteps_per_tap;         // (K chunk, ty) pairs, ty inner
-        int g_ty = 0, g_k0 = 0;                               // next window to fetch
-        int bs_tap = 0, bs_k0 = 0;                            // next weight tile to fetch: tap = ty*tap_n + tx, K chunk
-        auto dma_a = [&](int slot) {
-            unsigned char* sa_hi = a_ring + slot * (2 * A_BYTES);
-            unsigned char* sa_lo = sa_hi + A_BYTES;
-            const int a_u = (((g_ty + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx) * p.in_ld + g_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < A_PT; ++i) {
-                CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-                CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-            }
-            if (wv == 0 && st_r < aw - CV_BM) {               // the (tap_n-1)*tap_sx rows past the tile: a few lanes of wave 0
-                const int ax = a_v[0] + CV_BM * p.in_ld * 2;
-                CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
-            }
-            if (++g_ty == p.tap_n) { g_ty = 0; g_k0 += CV_BK; }
-        };
-        auto dma_b = [&](int slot) {
-            unsigned char* sb_hi = b_ring + slot * (2 * B_BYTES);
-            unsigned char* sb_lo = sb_hi + B_BYTES;
-            const int b_u = (bs_tap * p.cout_pad * p.cin + bs_k0) * 2;
-#pragma unroll
-            for (int i = 0; i < B_PT; ++i) {
-                if (st_r + i * RP < BN) {
-                    CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                    CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-                }
-            }
-            if (++bs_tap == p.taps) { bs_tap = 0; bs_k0 += CV_BK; }
-        };
-        // fragment rows shifted by tx*tap_sx: the swizzle term follows the ACTUAL LDS row, so one offset per tx
-        int a_offx[3];
-#pragma unroll
-        for (int tx = 0; tx < 3; ++tx) a_offx[tx] = cv_swz(wm * (MF * 16) + frow + tx * p.tap_sx, lane >> 4);
-        auto compute_w = [&](int aslot, int bslot, int a_of) {
-            const unsigned char* sa_hi = a_ring + aslot * (2 * A_BYTES);
-            const unsigned char* sa_lo = sa_hi + A_BYTES;
-            const unsigned char* sb_hi = b_ring + bslot * (2 * B_BYTES);
-            const unsigned char* sb_lo = sb_hi + B_BYTES;
-            bf16x8_t ah[MF], al[MF];
-#pragma unroll
-            for (int m = 0; m < MF; ++m) {
-                ah[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_hi + a_of + m * 16 * CV_ROW));
-                al[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa_lo + a_of + m * 16 * CV_ROW));
-            }
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                const bf16x8_t bh = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + b_off + n * 16 * CV_ROW));
-                const bf16x8_t bl = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + b_off + n * 16 * CV_ROW));
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(al[m], bh, acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ah[m], bl, acc[m][n]);
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma<(TAIL > 0)>(ah[m], bh, acc[m][n]);
-            }
-        };
+        StepCounter gw, bs;                                   // next window (i = ty) / weight tile (i = tap = ty*tap_n + tx) to fetch
+        auto dma_a = [&](int slot) { stage_window(win_slot(slot), a_step(gw.i, 0, gw.k0), aw); gw.advance(p.tap_n); };
+        auto dma_b = [&](int slot) { stage_weights(wt_slot(slot), wt_slot(slot) + B_BYTES, (bs.i * p.cout_pad * p.cin + bs.k0) * 2); bs.advance(p.taps); };
         dma_a(0);
         dma_b(0);
         __syncthreads();
@@ -949,29 +841,39 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             const bool last_tx = tx + 1 == p.tap_n;
             if (s + 1 < nsub) dma_b(bslot ^ 1);                                    // next sub-step's weights
             if (last_tx && s + 1 < nsub) dma_a(aslot ^ 1);                         // next group's window
-            compute_w(aslot, bslot, a_of);
+            compute(win_slot(aslot), wt_slot(bslot), a_of);
             __syncthreads();
             bslot ^= 1;
             if (last_tx) { tx = 0; aslot ^= 1; a_of = a_offx[0]; }
             else { ++tx; a_of = tx == 1 ? a_offx[1] : a_offx[2]; }
         }
     } else {
-#pragma unroll
-    for (int q = 0; q < SPB; ++q)
-        if (q < nsteps) CV_DMA(q, q)
-    __syncthreads();                                          // drains the DMA (vmcnt) and publishes the first half
-    for (int s = 0, half = 0; s < nsteps; s += SPB, half ^= 1) {
-        // the other half of the ring was last read one interval ago and every wave has passed that barrier:
-        // refill it now, the DMA flies during this interval's MFMAs
+        // the 4-wave / 2-slot loop over (K chunk, tap) stages, no window: stage = A tile of tap (ty, tx) + its weight tile
+        StepCounter pf;                                       // next stage to fetch: i = ty; with pf_tx, pf_tap = ty*tap_n + tx
+        int pf_tx = 0, pf_tap = 0;
+        auto dma = [&](int buf) {
+            stage_window(win_slot(buf), a_step(pf.i, pf_tx, pf.k0), CV_BM);
+            stage_weights(wt_slot(buf), wt_slot(buf) + B_BYTES, (pf_tap * p.cout_pad * p.cin + pf.k0) * 2);
+            ++pf_tap;
+            if (++pf_tx == p.tap_n) { pf_tx = 0; if (pf.advance(p.tap_n)) pf_tap = 0; }
+        };
 #pragma unroll
         for (int q = 0; q < SPB; ++q)
-            if (s + SPB + q < nsteps) CV_DMA(s + SPB + q, (half ^ 1) * SPB + q)
+            if (q < nsteps) dma(q);
+        __syncthreads();                                      // drains the DMA (vmcnt) and publishes the first half
+        for (int s = 0, half = 0; s < nsteps; s += SPB, half ^= 1) {
+            // the other half of the ring was last read one interval ago and every wave has passed that barrier:
+            // refill it now, the DMA flies during this interval's MFMAs
 #pragma unroll
-        for (int q = 0; q < SPB; ++q)
-            if (s + q < nsteps) compute(half * SPB + q);
-        __syncthreads();                                      // next half landed; everyone done with this half
+            for (int q = 0; q < SPB; ++q)
+                if (s + SPB + q < nsteps) dma((half ^ 1) * SPB + q);
+#pragma unroll
+            for (int q = 0; q < SPB; ++q)
+                if (s + q < nsteps) compute(win_slot(half * SPB + q), wt_slot(half * SPB + q), a_off);
+            __syncthreads();                                  // next half landed; everyone done with this half
+        }
     }
-    }
+#undef CV_BLDS
 
     if constexpr (TAIL > 0) {
         // ---- fused 1x1 tail: the 128 x 128 tile (bias, ReLU, re-split) becomes the LDS-resident input of three 1x1 layers ----
@@ -1128,13 +1030,7 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const ConvParams p) {
 }
 
 template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0>
-static size_t conv_lds_bytes() {
-    const size_t tiles = (WIN == 4 && PP) ? 2 * (2 * (size_t)(BM + 8) * CV_ROW + 512 * 4) + 4 * (size_t)(NF * 16) * CV_ROW + 2 * (3 * (size_t)(NF * 16) * CV_ROW + 512 * 4 + 16)
-                       : WIN == 2 ? 2 * (size_t)(BM + 8) * CV_ROW + 3 * 2 * (size_t)(NF * 16) * CV_ROW
-                                  : 2 * SPB * (2 * (size_t)(WIN ? BM + 8 : BM) * CV_ROW + 2 * (size_t)(NF * 16) * CV_ROW);
-    const size_t stage = (size_t)(NT / 64) * 16 * ((NF / WN) * 16 + 4) * 4;
-    return tiles > stage ? tiles : stage;
-}
+static size_t conv_lds_bytes() { return ConvLds<NF, WN, BM, SPB, NT, PP, WIN>::TOTAL; }
 
 template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0>
 static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
@@ -1162,6 +1058,17 @@ static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
     return hipGetLastError();
 }
 
+// The fused-tail instance of one K loop <BM, NT, PP, WIN> for the tail's last layer: 16 (G-Net head), 128 or 144 (mask head) channels
+template <int BM, int NT, bool PP, int WIN>
+static hipError_t launch_conv_tail(const ConvParams& p, hipStream_t s) {
+    switch (p.tail_cout) {
+    case 16:  return launch_conv_nf<8, 2, BM, 1, 1, NT, PP, WIN>(p, s);
+    case 128: return launch_conv_nf<8, 2, BM, 1, 8, NT, PP, WIN>(p, s);
+    case 144: return launch_conv_nf<8, 2, BM, 1, 9, NT, PP, WIN>(p, s);
+    default:  return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     // p.variant is 0 in the product library; the dev library takes it from MAGNET_CONV_VARIANT.  Each bit only moves a launch to an
     // instance that other shapes reach anyway: 1 = no row window, 8 = the 2-slot LDS window instead of the register window, 16 = the
@@ -1175,10 +1082,7 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
         if (p.cout_pad != 128) return hipErrorInvalidValue;
         if (p.in_sc) {                                          // round 4: fp16 + block-scaled e4m3 operand format (see the WIN == 4 loop)
             if (p.tap_n != 3 || !p.w_sc || p.rows < 256ll * 256 || p.addend) return hipErrorInvalidValue;
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 4>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 4>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 4>(p, s);
-            return hipErrorInvalidValue;
+            return launch_conv_tail<256, 512, true, 4>(p, s);
         }
         const bool win = p.tap_n > 1 && !(p.variant & 1);
         // default: ping-pong x register window, 256-row tile, 8 waves — when there is at least one such tile per CU (256 CUs);
@@ -1187,25 +1091,11 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
         // loops between an exposed 128 KB addend load and the tail, where two co-resident 4-wave workgroups overlap better than one
         // 8-wave workgroup (same-box A/B: 425 vs 464 us at K = 288, 766 vs 804 us at K = 576)
         // (MAGNET_TILING_BM256 of MagnetConvExArgs takes it at any row count: the tests reach its tile edges with small grids)
-        if (win && p.tap_n == 3 && !(p.variant & (16 | 8)) && (p.rows >= 256ll * 256 || (p.tiling & 2)) && (!p.addend || (p.variant & 256))) {
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 2>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 256, 1, 8, 512, true, 2>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 2>(p, s);
-        }
-        if (win && p.tap_n == 3 && !(p.variant & 8)) {
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 128, 1, 1, 256, false, 2>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 128, 1, 8, 256, false, 2>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 128, 1, 9, 256, false, 2>(p, s);
-        }
-        if (win) {
-            if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 128, 1, 1, 256, false, 1>(p, s);
-            if (p.tail_cout == 128) return launch_conv_nf<8, 2, 128, 1, 8, 256, false, 1>(p, s);
-            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 128, 1, 9, 256, false, 1>(p, s);
-        }
-        if (p.tail_cout == 16)  return launch_conv_nf<8, 2, 128, 1, 1>(p, s);
-        if (p.tail_cout == 128) return launch_conv_nf<8, 2, 128, 1, 8>(p, s);
-        if (p.tail_cout == 144) return launch_conv_nf<8, 2, 128, 1, 9>(p, s);
-        return hipErrorInvalidValue;
+        if (win && p.tap_n == 3 && !(p.variant & (16 | 8)) && (p.rows >= 256ll * 256 || (p.tiling & 2)) && (!p.addend || (p.variant & 256)))
+            return launch_conv_tail<256, 512, true, 2>(p, s);
+        if (win && p.tap_n == 3 && !(p.variant & 8)) return launch_conv_tail<128, 256, false, 2>(p, s);
+        if (win) return launch_conv_tail<128, 256, false, 1>(p, s);
+        return launch_conv_tail<128, 256, false, 0>(p, s);
     }
     // the loop-invariant x_d3 part of G-Net's first layer (fp32 partial sums, I >= 2): the fused-tail kernels' 8-wave ping-pong x
     // register-window loop (same-box: C3 step -1 %); on the F-Net's plain 128-wide layers (split-bf16 outputs) it is equal to the
@@ -1542,8 +1432,5 @@ hipError_t launch_pack_mx(const float* in, uint16_t* out_f16, uint8_t* out_qr, u
                        C, h, w, ctot, c_off, sc_rows, in_img_stride);
     return hipGetLastError();
 }
-
-#undef CV_DMA
-#undef CV_BLDS
 
 }  // namespace magnet
