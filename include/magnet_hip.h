@@ -594,7 +594,11 @@ enum {                                     /* MagnetConvExArgs.act */
 enum {                                     /* MagnetConvExArgs.tiling: bit flags, for tests and A/B runs; 0 = the library chooses */
     MAGNET_TILING_FLAT  = 1,               /* cut the flattened rows into tiles from row 0 on, also where per-image tiling (launches with
                                               base.gu_in / base.up_depth) would take fewer workgroups.  Same kernel, same interior results. */
-    MAGNET_TILING_BM256 = 2                /* fused-tail 3x3 launches: the 256-row 8-wave kernel also below 65 536 rows */
+    MAGNET_TILING_BM256 = 2,               /* fused-tail 3x3 launches: the 256-row 8-wave kernel also below 65 536 rows */
+    MAGNET_TILING_BM64  = 4                /* 64-row tiles of the 4-wave register-window kernel (latency mode: twice the workgroups of the
+                                              128-row form, bit-identical results): 3x3 launches (taps == 9) with cout_pad == 128 and a
+                                              fused tail, or plain with cout_pad % 128 == 0; not the fp16 + e4m3 format, not with BM256.
+                                              Any other launch is refused with MAGNET_E_DIM */
 };
 
 /* magnet_conv_mfma with an activation mode.  act = MAGNET_ACT_BASE and the other fields zero give exactly magnet_conv_mfma(&args->base). */
@@ -612,7 +616,8 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
  * Flat: tile t covers rows [t bm, (t + 1) bm) of the flattened buffer, ceil(n_img (h + 2) wp / bm) tiles.  Per image: tile t of image i
  * covers the bm rows from i (h + 2) wp + wp + t bm on, ceil(h wp / bm) tiles per image; the top and bottom border image rows get no
  * tile.  Per-image tiling is used only when it takes fewer tiles than flat and an image's last tile ends inside that image.  Host
- * arithmetic only (no GPU needed); returns 0 on bad dimensions.  bm is 256 for fused-tail 3x3 launches of at least 65 536 rows, else 128. */
+ * arithmetic only (no GPU needed); returns 0 on bad dimensions.  bm is 256 for fused-tail 3x3 launches of at least 65 536 rows, else 128
+ * (64 under MAGNET_TILING_BM64). */
 MAGNET_API int64_t magnet_conv_row_tiles(int32_t n_img, int32_t h, int32_t wp, int32_t bm, int32_t *tiles_per_img);
 
 /* The D-Net's Gaussian activation behind its depth head (activation_G_magnet, models/DNET.py:62-67): from the head's fp32 output

@@ -7,6 +7,8 @@ module keeps its reference state_dict and stays trainable through the torch path
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -46,6 +48,40 @@ def _cout_pad(c):
     return round_up(c, 128)
 
 
+# Latency mode.  Under small_tiles = "auto" a 3x3 launch of a stack whose 128-row tiling has fewer than SMALL_TILE_LIMIT tiles goes to
+# the 64-row instance (lib.TILING_BM64: twice the workgroups, bit-identical results).  The natural limit would be 256, the CUs of an MI355X:
+# below it the 128-row form leaves CUs without work and the others with one workgroup of a kernel built for two.  Measured
+# (profiles/latency/NOTES.md): at one frame of 120 x 160 (152 tiles) the replayed shipped step gains in 12 of 12 interleaved pairs
+# (0.2938 vs 0.2986 ms) and the C2 step in 1 (0.1882 vs 0.1874 ms), launched eagerly (host-bound) in 2 and 2; one KITTI frame (211 tiles)
+# loses in every pair, and so do two and three frames (304, 456 tiles) — a CU's critical path is 128 rows either way.
+# The bar is every pair at every workload measured, so the limit is 0: "auto" keeps the 128-row launches and the 64-row form is opt-in (small_tiles = True).
+SMALL_TILE_LIMIT = 0
+
+
+@functools.lru_cache(maxsize=None)
+def tiles_128(n_img, h, wp, by_image=True):
+    """128-row tiles of a 3x3 launch over n_img zero-bordered (h + 2, wp) grids: what magnet_conv_row_tiles says for the launches that
+    know their image geometry (fused Gaussian update / upsampling), the flat count ceil(rows / 128) for the others."""
+    if by_image:
+        return lib.conv_row_tiles(n_img, h, wp, 128)[0]
+    return (n_img * (h + 2) * wp + 127) // 128
+
+
+def use_small_tiles(n_img, h, wp, by_image=True):
+    """The rule of ConvStackMFMA.small_tiles == "auto": one threshold on the 128-row tile count.  Pure host arithmetic."""
+    return tiles_128(n_img, h, wp, by_image) < SMALL_TILE_LIMIT
+
+
+def _tile_rows(n, small, rows, wp, geom):
+    """Tile rows of a launch from the tile count n the library reported for it: 64 under TILING_BM64, else the one of the library's
+    own 128- and 256-row forms whose tiling of the launch (magnet_conv_row_tiles where the launch carries its image geometry, else
+    rows / tile rows rounded up) has n tiles.  Nothing of launch_conv_mfma's selection is restated here."""
+    for bm in ((64,) if small else (128, 256)):
+        if n == (lib.conv_row_tiles(*geom, wp, bm)[0] if geom is not None else -(-rows // bm)):
+            return bm
+    raise lib.MagnetError(f"ConvStackMFMA: {n} row tiles reported for {rows} rows match no tile form")
+
+
 def _buf(work, key, make):
     """work[key], made on first use."""
     if key not in work:
@@ -60,6 +96,38 @@ class ConvStackMFMA:
     # When set to a list, every layer launch appends (start_event, end_event, flops, taps) recorded on the launch
     # stream (bench.py's live timing of the convolution kernel).
     event_sink = None
+
+    # Tile form of the stack's 3x3 launches (class default; set on an instance to override): "auto" = 64-row tiles when
+    # use_small_tiles() says the 128-row form under-fills the chip, True = always where a 64-row instance exists, False = never.
+    # Results do not depend on it, bit for bit.
+    small_tiles = "auto"
+    # True: every 3x3 launch goes through magnet_conv_mfma_ex and last_tiles / last_invariant_tiles hold [(tile rows, row tiles)] of
+    # the last run() / run_invariant(), as the library reported them (tests, tools).  Off by default: a one-frame step launched eagerly
+    # is host-bound, and a launch that keeps its tile form is then exactly the magnet_conv_mfma call it was before the 64-row form
+    # existed.  A launch on 64-row tiles is recorded either way.
+    record_tiles = False
+    last_tiles = ()
+    last_invariant_tiles = ()
+
+    def _tiling(self, pk, rows, wp, gauss=None, upsample=None):
+        """(tiling, geom) of the launch of this stack's first layer `pk` over `rows` rows of pitch wp.  tiling, the argument of
+        lib.conv_mfma: lib.TILING_BM64, 0 (the library chooses; the count is reported) or None (magnet_conv_mfma: nothing reported).
+        geom = (n_img, h) where the launch carries its image geometry (gauss / upsample), else None.  The one place that says
+        whether there is anything to decide or record: in the common case (no) this is two attribute reads and a comparison."""
+        st = self.small_tiles
+        if pk["taps"] != 9 or not (self.record_tiles or st is True or (st == "auto" and SMALL_TILE_LIMIT > 0)):
+            return None, None
+        geom = (int(gauss[0].shape[0]), int(gauss[0].shape[2])) if gauss is not None else \
+            (int(upsample[0].shape[1]), int(upsample[0].shape[3])) if upsample is not None else None
+        if st is not False and pk["cout_pad"] % 128 == 0 and \
+                (st is True or (use_small_tiles(*geom, wp) if geom is not None else use_small_tiles(1, rows // wp - 2, wp, False))):
+            return lib.TILING_BM64, geom
+        return (0 if self.record_tiles else None), geom
+
+    @staticmethod
+    def _reported(n, tiling, rows, wp, geom):
+        """last_tiles of one launch whose tile count n the library reported: [(tile rows, row tiles)]."""
+        return [(_tile_rows(n, tiling, rows, wp, geom), n)]
 
     def __init__(self, seq: nn.Sequential, in_map=None):
         self.layers = []
@@ -180,8 +248,10 @@ class ConvStackMFMA:
         channel 0 of the buffer; the launch starts at channel inv_off."""
         _, inv = self.packed_first_split(in_hi.device, n_var, inv_off)
         out = _buf(work, ("partial", rows, inv["cout_pad"]), lambda: torch.empty((rows, inv["cout_pad"]), dtype=torch.float32, device=in_hi.device))
-        lib.conv_mfma(in_hi[:, inv_off:], in_lo[:, inv_off:], in_ld, inv["cin"], inv["w_hi"], inv["w_lo"], inv["bias"], inv["taps"], wp,
-                      False, rows, out_f32=out)
+        tiling, geom = self._tiling(inv, rows, wp)
+        n = lib.conv_mfma(in_hi[:, inv_off:], in_lo[:, inv_off:], in_ld, inv["cin"], inv["w_hi"], inv["w_lo"], inv["bias"], inv["taps"], wp,
+                          False, rows, out_f32=out, tiling=tiling)
+        self.last_invariant_tiles = () if n is None else self._reported(n, tiling, rows, wp, geom)
         return out
 
     def run(self, in_hi, in_lo, in_ld, rows, wp, work, first_addend=None, n_var=None, inv_off=None, upsample=None, gauss=None, mx=None):
@@ -198,6 +268,9 @@ class ConvStackMFMA:
             # first layer over the per-iteration channels only; the invariant part arrives as `first_addend`
             packs = [self.packed_first_split(dev, n_var, inv_off)[0]] + list(packs[1:])
         sink = ConvStackMFMA.event_sink
+        # the stack's first layer (its one 3x3 launch) takes its tile form from small_tiles; tiling None is the plain entry point
+        tiling, geom = (None, None) if mx is not None else self._tiling(packs[0], rows, wp, gauss, upsample)
+        self.last_tiles = ()
 
         def out_f32(c):
             return _buf(work, ("out", rows, c), lambda: torch.empty((rows, c), dtype=torch.float32, device=dev))
@@ -215,15 +288,18 @@ class ConvStackMFMA:
                 wm = self.packed_mx(dev)
                 w_hi, w_lo, form = wm["w_hi"], wm["w_lo"], dict(mx=(mx[0], wm["w_sc"], mx[1]))
             with timed(sink, flops(pk) + 2.0 * rows * 128 * (256 + ch["cout_pad"]), pk["taps"]):
-                lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], w_hi, w_lo, pk["bias"], pk["taps"], wp, pk["relu"], rows, out_f32=out,
-                              tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss, **form)
+                n = lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], w_hi, w_lo, pk["bias"], pk["taps"], wp, pk["relu"], rows, out_f32=out,
+                                  tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss, tiling=tiling,
+                                  **form)
+            self.last_tiles = () if n is None else self._reported(n, tiling, rows, wp, geom)
             return out, ch["cout_pad"]
         if self._chain is not None and self.fuse_tail and first_addend is None:
             pk, ch = packs[0], self._chain
             oh, ol = _buf(work, ("hid", 0, rows, 128), lambda: planes(rows, 128, dev))
             with timed(sink, flops(pk), pk["taps"]):
-                lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
-                              pk["relu"], rows, out_hi=oh, out_lo=ol)
+                n = lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
+                                  pk["relu"], rows, out_hi=oh, out_lo=ol, tiling=tiling)
+            self.last_tiles = () if n is None else self._reported(n, tiling, rows, wp, geom)
             out = out_f32(ch["cout_pad"])
             with timed(sink, 2.0 * rows * 128 * (256 + ch["cout_pad"]), 1):
                 lib.conv1x1_chain(oh, ol, ch["w_hi"], ch["w_lo"], ch["bias"], out, rows, ch["cout_pad"])
@@ -232,8 +308,11 @@ class ConvStackMFMA:
         for li, pk in enumerate(packs[:-1]):
             oh, ol = _buf(work, ("hid", li & 1, rows, pk["cout_pad"]), lambda: planes(rows, pk["cout_pad"], dev))
             with timed(sink, flops(pk), pk["taps"]):
-                lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
-                              pk["relu"], rows, out_hi=oh, out_lo=ol, addend=first_addend if li == 0 else None)
+                n = lib.conv_mfma(cur_hi, cur_lo, cur_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
+                                  pk["relu"], rows, out_hi=oh, out_lo=ol, addend=first_addend if li == 0 else None,
+                                  tiling=tiling if li == 0 else None)
+            if li == 0:
+                self.last_tiles = () if n is None else self._reported(n, tiling, rows, wp, geom)
             cur_hi, cur_lo, cur_ld = oh, ol, pk["cout_pad"]
         pk = packs[-1]
         out = out_f32(pk["cout_pad"])

@@ -412,7 +412,14 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
         if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
             return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: act_slope must be finite");
     }
-    if (a->tiling & ~(MAGNET_TILING_FLAT | MAGNET_TILING_BM256)) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: tiling=%d unknown", a->tiling);
+    if (a->tiling & ~(MAGNET_TILING_FLAT | MAGNET_TILING_BM256 | MAGNET_TILING_BM64)) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: tiling=%d unknown", a->tiling);
+    if (a->tiling & MAGNET_TILING_BM64) {                            // the 64-row instances: 3x3, 128-wide, bf16x3 operands
+        const MagnetConvArgs& b = a->base;
+        if (a->tiling & MAGNET_TILING_BM256) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: MAGNET_TILING_BM64 and MAGNET_TILING_BM256 exclude each other");
+        if (b.taps != 9 || b.in_sc || b.w_sc || (b.tail_w_hi ? b.cout_pad != 128 : (b.cout_pad <= 0 || b.cout_pad % 128 != 0)))
+            return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: MAGNET_TILING_BM64 serves 3x3 launches (taps == 9) with cout_pad == 128 and a fused tail, or plain "
+                                      "with cout_pad %% 128 == 0, bf16x3 operands only (taps=%d cout_pad=%d)", b.taps, b.cout_pad);
+    }
     return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream);
 }
 

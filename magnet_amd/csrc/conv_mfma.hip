@@ -52,7 +52,7 @@ __device__ __forceinline__ void split_bf16(float x, uint16_t& hi, uint16_t& lo) 
 }
 
 // NF = 16-column fragments of the workgroup tile (BN = NF*16: 128, 144 or 16 channels);
-// WN = waves along N (2: 2x2 waves; 1: 4x1 waves); CV_BM = rows of the workgroup tile (128 or 256)
+// WN = waves along N (2: 2x2 waves; 1: 4x1 waves); CV_BM = rows of the workgroup tile (64, 128 or 256)
 // SPB = K stages per barrier interval (the LDS ring holds 2*SPB stages)
 __device__ __forceinline__ int act_swz(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
 
@@ -77,9 +77,10 @@ __device__ __forceinline__ void tail_layer_cols(const uint16_t* __restrict__ w_h
                                                 const float* __restrict__ bias, unsigned char* act_hi, unsigned char* act_lo,
                                                 float* __restrict__ out, int out_ld, long long row0, long long rows, int lane, int wv,
                                                 const UpArgs up = UpArgs{nullptr, nullptr, 0, 0, 0, 0}) {
-    // NW waves: wave w owns output fragments w, w + NW, ...; MA row blocks, read from LDS 8 at a time
+    // NW waves: wave w owns output fragments w, w + NW, ...; MA row blocks, read from LDS MB = 8 at a time (all 4 of a 64-row tile)
     constexpr int NJ = TAILN / NW, REM = TAILN % NW, MA = ROWS / 16, MR = MA / NW;   // MR: remainder-fragment row blocks per wave
-    static_assert(REM <= 1 && MA % 8 == 0 && MA % NW == 0, "one row-split remainder fragment at most");
+    constexpr int MB = MA < 8 ? MA : 8;
+    static_assert(REM <= 1 && MA % MB == 0 && MA % NW == 0, "one row-split remainder fragment at most");
     f32x4_t acc[NJ > 0 ? NJ : 1][MA], accr[MR];
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
@@ -99,21 +100,21 @@ __device__ __forceinline__ void tail_layer_cols(const uint16_t* __restrict__ w_h
                 wl[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(w_lo + e));
             }
 #pragma unroll
-            for (int mb = 0; mb < MA; mb += 8) {
-                bf16x8_t xh[8], xl[8];
+            for (int mb = 0; mb < MA; mb += MB) {
+                bf16x8_t xh[MB], xl[MB];
 #pragma unroll
-                for (int m = 0; m < 8; ++m) {
+                for (int m = 0; m < MB; ++m) {
                     xh[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(act_hi + act_swz((mb + m) * 16 + frow, kk * 4 + kslot)));
                     xl[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(act_lo + act_swz((mb + m) * 16 + frow, kk * 4 + kslot)));
                 }
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) acc[j][mb + m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], xl[m], acc[j][mb + m], 0, 0, 0);
+                    for (int m = 0; m < MB; ++m) acc[j][mb + m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], xl[m], acc[j][mb + m], 0, 0, 0);
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) acc[j][mb + m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[j], xh[m], acc[j][mb + m], 0, 0, 0);
+                    for (int m = 0; m < MB; ++m) acc[j][mb + m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[j], xh[m], acc[j][mb + m], 0, 0, 0);
 #pragma unroll
-                    for (int m = 0; m < 8; ++m) acc[j][mb + m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], xh[m], acc[j][mb + m], 0, 0, 0);
+                    for (int m = 0; m < MB; ++m) acc[j][mb + m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], xh[m], acc[j][mb + m], 0, 0, 0);
                 }
             }
         }
@@ -134,23 +135,24 @@ __device__ __forceinline__ void tail_layer_cols(const uint16_t* __restrict__ w_h
     }
     if constexpr (UP) {
         // ---- learned convex upsampling (models/MAGNET.py:15-27) behind the mask head's last layer, column-owned: the 144 logits of a
-        // position sit in 9 different waves (fragment n = neighbour n of the 3x3 window), so they meet in LDS: 128 rows x 144 fp32 at
-        // a time in the (now dead) activation tile, then one thread per (position, sub-pixel row i) does what upsample_cl_kernel does
+        // position sit in 9 different waves (fragment n = neighbour n of the 3x3 window), so they meet in LDS: HR = 128 rows (a 64-row tile: all 64)
+        // x 144 fp32 at a time in the (now dead) activation tile and K ring, then one thread per (position, sub-pixel row i) does what upsample_cl_kernel does
         // — same arithmetic, same order: bit-identical — with the mask read from LDS instead of HBM.
-        static_assert(TAILN == 9 && LAST && ROWS % 128 == 0, "mask head's last layer");
+        static_assert(TAILN == 9 && LAST && (ROWS % 128 == 0 || ROWS == 64), "mask head's last layer");
+        constexpr int HR = ROWS < 128 ? ROWS : 128, HB = HR / 16;   // rows / 16-row blocks of one pass
         constexpr int SP = 148;                               // stage row pitch in floats: 16 rows x 4 quads of a fragment store hit distinct banks
-        float* stage = reinterpret_cast<float*>(act_hi);      // 128 x 148 x 4 B = 74 KB <= ROWS x 512 B
+        float* stage = reinterpret_cast<float*>(act_hi);      // HR x 148 x 4 B = 74 KB (37 KB at 64 rows) <= the launch's LDS (launch_conv_nf)
         const int wp = up.w + 2, img_rows = (up.h + 2) * wp;
         const size_t hw = (size_t)up.h * up.w;
         const int tid = wv * 64 + lane;
-        for (int half = 0; half < ROWS / 128; ++half) {
+        for (int half = 0; half < ROWS / HR; ++half) {
             __syncthreads();                                  // every wave is done with the activation tile / with the previous half's stage
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
 #pragma unroll
                 for (int m = 0; m < MA; ++m) {
-                    if (m / 8 != half) continue;
-                    const int ch = (wv + NW * j) * 16 + (lane >> 4) * 4, srow = (m & 7) * 16 + (lane & 15);
+                    if (m / HB != half) continue;
+                    const int ch = (wv + NW * j) * 16 + (lane >> 4) * 4, srow = (m % HB) * 16 + (lane & 15);
                     const float4 b4 = *reinterpret_cast<const float4*>(bias + ch);
                     *reinterpret_cast<float4*>(stage + srow * SP + ch) =
                         make_float4(acc[j][m][0] + b4.x, acc[j][m][1] + b4.y, acc[j][m][2] + b4.z, acc[j][m][3] + b4.w);
@@ -159,17 +161,17 @@ __device__ __forceinline__ void tail_layer_cols(const uint16_t* __restrict__ w_h
 #pragma unroll
                 for (int m = 0; m < MR; ++m) {
                     const int mrow = wv * MR + m;
-                    if (mrow / 8 != half) continue;
-                    const int ch = NJ * NW * 16 + (lane >> 4) * 4, srow = (mrow & 7) * 16 + (lane & 15);
+                    if (mrow / HB != half) continue;
+                    const int ch = NJ * NW * 16 + (lane >> 4) * 4, srow = (mrow % HB) * 16 + (lane & 15);
                     const float4 b4 = *reinterpret_cast<const float4*>(bias + ch);
                     *reinterpret_cast<float4*>(stage + srow * SP + ch) =
                         make_float4(accr[m][0] + b4.x, accr[m][1] + b4.y, accr[m][2] + b4.z, accr[m][3] + b4.w);
                 }
             }
             __syncthreads();
-            for (int t = tid; t < 128 * 4; t += NW * 64) {    // (position of this half, sub-pixel row i)
+            for (int t = tid; t < HR * 4; t += NW * 64) {     // (position of this half, sub-pixel row i): 2 per thread, 1 at 64 rows
                 const int srow = t >> 2, i = t & 3;
-                const long long row = row0 + half * 128 + srow;
+                const long long row = row0 + half * HR + srow;
                 const int b = (int)((unsigned)row / (unsigned)img_rows);                  // rows < 2^31 (checked by the API)
                 const int rem = (int)((unsigned)row - (unsigned)b * (unsigned)img_rows);
                 const int yy = rem / wp, xx = rem - yy * wp;
@@ -354,9 +356,9 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
     using L = ConvLds<NF, WN, CV_BM, SPB, NT, PP, WIN>;
     constexpr int BN = L::BN, A_BYTES = L::A_BYTES, B_BYTES = L::B_BYTES;
     constexpr int RP = NT / 4;                      // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
-    constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (2 or 4)
+    constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (1, 2 or 4)
     constexpr int WM = (NT / 64) / WN;                // waves along M
-    constexpr int MF = CV_BM / (WM * 16);             // M fragments per wave (2 or 4)
+    constexpr int MF = CV_BM / (WM * 16);             // M fragments per wave (2 or 4; 64-row tile: 2x2 waves of 32 rows)
     constexpr int NFW = NF / WN;                      // N fragments per wave
     static_assert(NF % WN == 0, "N fragments must split evenly over the waves");
     const int lane = tid & 63, wv = tid >> 6;
@@ -877,8 +879,8 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
 
     if constexpr (TAIL > 0) {
         // ---- fused 1x1 tail: the 128 x 128 tile (bias, ReLU, re-split) becomes the LDS-resident input of three 1x1 layers ----
-        static_assert(NF == 8 && WN == 2 && (CV_BM == 128 || CV_BM == 256) && CV_BM == (NT / 64) * 32,
-                      "the fused tail is written for 128-channel tiles with 32 rows per wave");
+        static_assert(NF == 8 && WN == 2 && ((CV_BM == 128 || CV_BM == 256) ? CV_BM == (NT / 64) * 32 : (CV_BM == 64 && NT == 256)),
+                      "the fused tail is written for 128-channel tiles with 32 rows per wave (64-row tile: 4 waves of 32 rows x 64 channels)");
         unsigned char* act_hi = smem;                                   // [CV_BM rows][256 B]; the K ring is dead (barrier above)
         unsigned char* act_lo = smem + CV_BM * 256;
 #pragma unroll
@@ -1047,7 +1049,8 @@ static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
     dim3 grid((unsigned)n_tiles, (unsigned)(p.cout_pad / (NF * 16))), block(NT);
     size_t lds = conv_lds_bytes<NF, WN, BM, SPB, NT, PP, WIN>();
     if (TAIL > 0 && lds < (size_t)BM * 512) lds = (size_t)BM * 512;     // the fused tail's activation tile: BM rows x 256 B x (hi, lo)
-    if (TAIL == 9 && lds < (size_t)128 * 148 * 4) lds = (size_t)128 * 148 * 4;   // fused upsampling: 128 rows x 144 logits (+4 pad) fp32 (two 4-wave workgroups still fit a CU)
+    constexpr size_t UP_STAGE = (size_t)(BM < 128 ? BM : 128) * 148 * 4;   // fused upsampling (tail_layer_cols: HR rows x SP floats): 128 (or BM = 64) rows x 144 logits (+4 pad) fp32
+    if (TAIL == 9 && lds < UP_STAGE) lds = UP_STAGE;                        // (two 4-wave workgroups still fit a CU)
     static bool attr_set = false;
     if (!attr_set && lds > 64 * 1024) {          // > 64 KiB of dynamic LDS needs the opt-in attribute
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>),
@@ -1085,6 +1088,11 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
             return launch_conv_tail<256, 512, true, 4>(p, s);
         }
         const bool win = p.tap_n > 1 && !(p.variant & 1);
+        // MAGNET_TILING_BM64 (latency mode): 64-row tiles of the 4-wave register-window loop.  One frame of 120x160 is 152 tiles of 128
+        // rows for 256 CUs; as 304 tiles of 64 rows every CU has work and part of the chip holds the two workgroups this loop is
+        // built around.  Same K order per output element and the same per-row tail arithmetic: bit-identical to the other tile sizes.
+        // The caller asks for it (ConvStackMFMA.small_tiles decides by tile count); the API has checked that this instance exists.
+        if (p.tiling & 4) return p.tap_n == 3 ? launch_conv_tail<64, 256, false, 2>(p, s) : hipErrorInvalidValue;
         // default: ping-pong x register window, 256-row tile, 8 waves — when there is at least one such tile per CU (256 CUs);
         // fewer rows (single-frame inference: 78 tiles at 120x160) spread better as 128-row tiles of the 4-wave kernel
         // — and not for the per-iteration launches of a hoisted first layer (fp32 addend, K = 9 x 32 .. 9 x 64): those are short K
@@ -1100,6 +1108,8 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     // the loop-invariant x_d3 part of G-Net's first layer (fp32 partial sums, I >= 2): the fused-tail kernels' 8-wave ping-pong x
     // register-window loop (same-box: C3 step -1 %); on the F-Net's plain 128-wide layers (split-bf16 outputs) it is equal to the
     // 4-wave loop (18.64 - 18.72 vs 18.69 - 18.75 ms per 40 images; dev MAGNET_CONV_VARIANT=2048 forces it there)
+    if (p.tiling & 4)                           // MAGNET_TILING_BM64: the plain 128-wide 3x3 layer on 64-row tiles (every output mode)
+        return (p.cout_pad % 128 == 0 && p.tap_n == 3) ? launch_conv_nf<8, 2, 64, 1, 0, 256, false, 2>(p, s) : hipErrorInvalidValue;
     if (p.cout_pad == 128 && p.tap_n == 3 && (p.out_mode == 1 || (p.variant & 2048)) && !(p.variant & (16 | 9)) && p.rows >= 256ll * 256 && !p.add_hi && !p.img_rows)
         return launch_conv_nf<8, 2, 256, 1, 0, 512, true, 2>(p, s);
     if (p.cout_pad % 128 == 0 && p.tap_n == 3 && !(p.variant & 9)) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 2>(p, s);

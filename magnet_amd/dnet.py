@@ -247,6 +247,7 @@ class DNetMFMA:
         with torch.no_grad():
             eye.weight.copy_(torch.eye(128).view(128, 128, 1, 1)); eye.bias.zero_()
         self._head = ConvStackMFMA(nn.Sequential(dh[0], nn.ReLU(), dh[2], nn.ReLU(), eye, nn.ReLU(), dh[4]))
+        self._head.small_tiles = False                              # the D-Net's own launches keep their 128-row tiles (not measured at one frame)
         self._eye = eye
         self._mask = None                                           # the mask head's stack: built by the first run_standalone()
         self._mask_work = {}
@@ -428,6 +429,7 @@ class DNetMFMA:
             mh = self.decoder.mask_head
             # as the depth head: the fused epilogue has two hidden 1x1 layers, the second is the identity behind a ReLU
             self._mask = ConvStackMFMA(nn.Sequential(mh[0], nn.ReLU(), mh[2], nn.ReLU(), self._eye, nn.ReLU(), mh[4]))
+            self._mask.small_tiles = False
         b = self._decode(xs, N, dims, dev)
         h, w = dims[3]
         wp = w + 2

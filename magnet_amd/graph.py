@@ -5,9 +5,12 @@ inter-operation gaps — 5.78 -> 5.69 ms per C2 step (11 067 -> 11 239 frames/s)
 replays the step this way by default, --no-graph: eager).  The reference's own evaluation loop feeds ONE frame at a time
 (test_MaGNet.py:166-170, batch size 1).  `GraphedRefine` captures `MAGNET.match_and_refine` for a fixed shape into a HIP graph once
 (torch.cuda.CUDAGraph: our kernels are launched on torch's capture stream, so they are recorded like torch's own) and replays it per
-frame: one launch from the host's point of view.  A small-batch step is bound by its serial chain of ~13 kernels that each under-fill
-the chip (one frame = 155 convolution tiles for 256 CUs), not by launch overhead — batching frames is what pays; the graph only removes
-the host from the loop.  Inputs are copied into the graph's static tensors (device-to-device,
+frame: one launch from the host's point of view.  At one frame the host is what an eager step waits for: the shipped step (D = 5,
+I = 3) takes 0.5365 ms launched eagerly and 0.3001 ms replayed, the C2 step 0.3640 and 0.1910 ms (bench.py --frames 1, medians of six
+fresh processes: profiles/latency/bench_frames1.jsonl).  What remains is the serial chain of ~13 kernels that each under-fill the chip
+(one frame = 152 convolution tiles of 128 rows for 256 CUs; on 64-row tiles, ConvStackMFMA.small_tiles = True, the replayed shipped
+step takes 0.2938 against 0.2986 ms and the C2 step 0.1882 against 0.1874 ms, not a gain in every pair at every workload, so it is opt-in:
+profiles/latency/NOTES.md) — batching frames is what pays.  Inputs are copied into the graph's static tensors (device-to-device,
 a few MB); outputs are the graph's static output tensors (clone them to keep a result across replays)."""
 from __future__ import annotations
 

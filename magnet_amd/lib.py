@@ -26,7 +26,7 @@ MAX_CANDIDATES = 256
 NLL_BLOCKS, NLL_MAX_ITER = 256, 16
 BN_BLOCKS = 256
 ACT_BASE, ACT_LEAKY_RELU = 0, 1
-TILING_FLAT, TILING_BM256 = 1, 2
+TILING_FLAT, TILING_BM256, TILING_BM64 = 1, 2, 4
 METRICS_SIGMA, METRICS_VARIANCE, METRICS_NONE = 0, 1, 2
 
 
@@ -657,6 +657,14 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
     _launch("magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
     return tiles.value
+
+
+def conv_row_tiles(n_img, h, wp, bm):
+    """magnet_conv_row_tiles: (row tiles, tiles per image or 0 for flat tiling) of a launch over n_img zero-bordered (h + 2, wp) grids
+    with bm-row tiles.  Host arithmetic: needs the library, not a GPU."""
+    per = ctypes.c_int32(0)
+    n = load().magnet_conv_row_tiles(int(n_img), int(h), int(wp), int(bm), ctypes.byref(per))
+    return int(n), per.value
 
 
 def pack_split(x_nchw, out_hi, out_lo, ctot, c_off):
