@@ -287,6 +287,15 @@ typedef struct MagnetConvArgs {
      * bf16x3 format and is clamped here — the one documented difference between the two formats.  `bias` is read with 16-byte loads in every format: 16-byte aligned, as all pointers of this struct. */
     const void  *in_sc, *w_sc;
     int64_t      sc_rows;
+    /* The SINGLE-PLANE FP16 format (magnet_conv_mfma_f16 below; an entry point of its own, no field of this struct): in_hi is ONE fp16
+     * plane (rows, in_ld), w_hi ONE fp16 plane (taps, cout_pad, cin); in_lo, w_lo, in_sc, w_sc are NULL.  The 3x3 layer issues one fp16
+     * matrix instruction per product (each fp16 x fp16 product is exact in the fp32 accumulator) instead of three bf16 ones; the
+     * operands carry 11 significant bits instead of 16.  It is a reduced-precision mode the caller opts into, not fp32-grade.
+     * DOMAIN: |x| <= 65504; relative rounding 2^-11 for |x| >= 2^-14, absolute 2^-25 below (fp16 denormals are kept).  magnet_pack_f16 and
+     * magnet_planes_to_f16 write the activation plane: round to nearest even, magnitudes that would round above 65504 (+-Inf included)
+     * become +-65504 as in magnet_pack_mx, NaN is written through, the sign of zero is kept.  The fused 1x1 tail layers, bias, addend,
+     * ReLU, the Gaussian update and the convex upsampling behind the 3x3 layer are those of the bf16x3 format (tail_w_hi / tail_w_lo stay
+     * bf16 planes). */
 } MagnetConvArgs;                          /* out_mode 2: one bf16 plane (round-to-nearest-even) at out_hi */
 
 MAGNET_API int magnet_conv_mfma(const MagnetConvArgs *args, void *stream);
@@ -610,6 +619,27 @@ typedef struct MagnetConvExArgs {
     int64_t       *tiles_out;              /* optional HOST pointer: receives the number of row tiles (workgroups along x) launched */
 } MagnetConvExArgs;
 MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
+
+/* The 3x3 layer of a G-Net / mask-head stack on the single-plane fp16 operand format (see MagnetConvArgs): base.in_hi / base.w_hi are
+ * the fp16 planes; base.in_lo, base.w_lo, base.in_sc, base.w_sc must be NULL (MAGNET_E_DIM otherwise: planes of another format are
+ * refused, not mis-read).  Serves what the inference loop launches and refuses the rest with MAGNET_E_DIM: taps == 9 without dilation,
+ * cout_pad == 128, and either the fused tail with tail_cout_pad 16 or 144 (tail_w_hi / tail_w_lo bf16 planes; with gu_in / gu_out,
+ * up_depth / up_out and addend as in magnet_conv_mfma) or the plain layer with fp32 output (out_mode 1, optional addend).  No residual,
+ * border, repad, other out_mode, MAGNET_ACT_LEAKY_RELU or MAGNET_TILING_BM64; MAGNET_TILING_FLAT, MAGNET_TILING_BM256 and tiles_out work
+ * as in magnet_conv_mfma_ex (256-row tiles from 65 536 rows on, for launches without an addend; else 128-row tiles). */
+MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs *args, void *stream);
+
+/* fp32 NCHW (N, C, h, w) (image stride `in_img_stride` elements, 0 = C*h*w) -> channels [c_off, c_off + round_up(C, 8)) of the interior
+ * of a zero-bordered (N, h+2, w+2, ctot) fp16 plane (the round-up lanes are written as zeros, as by magnet_pack_split).  ctot and c_off
+ * multiples of 8.  The border rows and every other channel are not written.  Conversion: see the single-plane fp16 format above. */
+MAGNET_API int magnet_pack_f16(const float *nchw, void *out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,
+                               int64_t in_img_stride, void *stream);
+
+/* Channels [c0, c1) of split-bf16 planes (rows, ld) -> the same channels of an fp16 plane (rows, ld16): f16(hi + lo), the sum formed in
+ * fp32, converted as by magnet_pack_f16.  c0, c1, ld, ld16 multiples of 8; every row is converted (a zero border stays zero); nothing
+ * outside [c0, c1) is written. */
+MAGNET_API int magnet_planes_to_f16(const void *in_hi, const void *in_lo, int32_t ld, void *out_f16, int32_t ld16, int64_t rows,
+                                    int32_t c0, int32_t c1, void *stream);
 
 /* Row tiling of the launches that know their image geometry (base.gu_in / base.up_depth): the number of bm-row tiles (workgroups
  * along x) for n_img zero-bordered (h + 2, wp) grids, and in *tiles_per_img (optional) the tiles per image, or 0 for flat tiling.

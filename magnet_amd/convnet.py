@@ -14,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import lib
-from .planes import PackCache, pack_taps, planes, round_up, split_bf16, timed
+from .planes import PackCache, pack_taps, pack_taps_f16, planes, round_up, split_bf16, timed
 
 
 def mx_quant(v: torch.Tensor):
@@ -173,6 +173,16 @@ class ConvStackMFMA:
             return round_up(c0, 32)
         return round_up(max(d + n for _, n, d in self.in_map), 32)
 
+    def _first_weight(self, device):
+        """The first layer's fp32 weight (cout, cin, kh, kw) with its input channels laid out as the input buffer has them (in_map)."""
+        W = self.layers[0][0].weight.detach().to(device=device, dtype=torch.float32)
+        if self.in_map is None:
+            return W
+        Wm = torch.zeros((W.shape[0], self.cin_pad()) + tuple(W.shape[2:]), dtype=torch.float32, device=device)
+        for src, n, dst in self.in_map:
+            Wm[:, dst:dst + n] = W[:, src:src + n]
+        return Wm
+
     def packed(self, device):
         """Per layer the padded split-bf16 weights, the bias and the launch geometry; the repack also rebuilds (or drops) _chain."""
         return self._cache.get(device, lambda: self._pack(device))
@@ -182,14 +192,9 @@ class ConvStackMFMA:
         out = []
         cin_p = self.cin_pad()
         for li, (conv, relu) in enumerate(self.layers):
-            W = conv.weight.detach().to(device=device, dtype=torch.float32)          # (Cout, Cin, kh, kw)
+            W = self._first_weight(device) if li == 0 else conv.weight.detach().to(device=device, dtype=torch.float32)   # (Cout, Cin, kh, kw)
             cout, cin, kh, kw = W.shape
             cp = _cout_pad(cout)
-            if li == 0 and self.in_map is not None:
-                Wm = torch.zeros((cout, cin_p, kh, kw), dtype=torch.float32, device=device)
-                for src, n, dst in self.in_map:
-                    Wm[:, dst:dst + n] = W[:, src:src + n]
-                W = Wm
             hi, lo = (F.pad(t, (0, 0, 0, cp - cout)) for t in pack_taps(W, cin_p))   # (tap, cout_pad, cin_pad)
             bias = torch.zeros(cp, dtype=torch.float32, device=device)
             if conv.bias is not None:
@@ -209,6 +214,28 @@ class ConvStackMFMA:
                 bias=torch.cat([o["bias"] for o in out[1:]]).contiguous(), cout_pad=out[3]["cout_pad"])
         return out
 
+    def _run_f16(self, in_hi, in_lo, in_ld, rows, wp, first_addend, n_var, inv_off, upsample, gauss, mx, work):
+        """run(f16=True): one launch of magnet_conv_mfma_f16 with the stack's fused tail."""
+        dev = in_hi.device
+        self._check_f16(in_hi, in_lo)
+        packs = self.packed(dev)
+        if mx is not None or self._chain is None or not self.fuse_epilogue or self._chain["cout_pad"] not in (16, 144):
+            raise lib.MagnetError("ConvStackMFMA.run(f16=True): needs the fused-epilogue stack of G-Net or the mask head, and no mx")
+        pk, ch = packs[0], self._chain
+        w16 = self.packed_f16(dev)
+        if first_addend is not None:
+            pk, w16 = self.packed_first_split(dev, n_var, inv_off)[0], self.packed_f16(dev, n_var, inv_off)[0]
+        out = None if (upsample is not None or gauss is not None) else \
+            _buf(work, ("out", rows, ch["cout_pad"]), lambda: torch.empty((rows, ch["cout_pad"]), dtype=torch.float32, device=dev))
+        geom = (int(gauss[0].shape[0]), int(gauss[0].shape[2])) if gauss is not None else \
+            (int(upsample[0].shape[1]), int(upsample[0].shape[3])) if upsample is not None else None
+        with timed(ConvStackMFMA.event_sink, 2.0 * rows * pk["cout_pad"] * pk["cin"] * pk["taps"] + 2.0 * rows * 128 * (256 + ch["cout_pad"]), pk["taps"]):
+            n = lib.conv_mfma(in_hi, None, in_ld, pk["cin"], w16, None, pk["bias"], pk["taps"], wp, pk["relu"], rows, out_f32=out,
+                              tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss, addend=first_addend,
+                              f16=True)
+        self.last_tiles = self._reported(n, False, rows, wp, geom) if self.record_tiles else ()
+        return out, ch["cout_pad"]
+
     def packed_mx(self, device):
         """First layer's weights in the fp16 + e4m3 operand format (conv_mfma.hip, WIN == 4 loop): (w_f16 (taps, cout_pad, cin), w_qr
         (taps, cout_pad, cin) int16 container, w_sc (taps, cin / 32, cout_pad) int32)."""
@@ -219,6 +246,21 @@ class ConvStackMFMA:
             hi, qr, sc = split_mx(w)
             return dict(w_hi=hi, w_lo=qr, w_sc=sc.permute(0, 2, 1).contiguous())
         return self._cache.get(device, build, "mx")
+
+    def packed_f16(self, device, n_var=None, inv_off=None):
+        """First layer's weights as ONE fp16 plane (taps, cout_pad, cin), rounded once from the fp32 parameter (planes.pack_taps_f16):
+        the weight operand of the single-plane fp16 format.  With n_var / inv_off: (variable part, invariant part) over the channels
+        packed_first_split() cuts — buffer channels [0, round_up(n_var, 32)) and [inv_off, cin_pad)."""
+        @torch.no_grad()
+        def build():
+            pk = self.packed(device)[0]
+            w = F.pad(pack_taps_f16(self._first_weight(device), pk["cin"]), (0, 0, 0, pk["cout_pad"] - pk["cout"]))
+            if n_var is None:
+                return w
+            cv = round_up(n_var, 32)
+            wv = w[:, :, :cv].clone(); wv[:, :, n_var:] = 0
+            return wv.contiguous(), w[:, :, inv_off:].contiguous()
+        return self._cache.get(device, build, "f16", n_var, inv_off)
 
     def packed_first_split(self, device, n_var, inv_off):
         """First layer split by input channels of the (padded) input buffer: channels [0, n_var) vary per refinement
@@ -243,26 +285,45 @@ class ConvStackMFMA:
             return var, inv
         return self._cache.get(device, build, "split", n_var, inv_off)
 
-    def run_invariant(self, in_hi, in_lo, in_ld, rows, wp, work, n_var, inv_off):
+    def run_invariant(self, in_hi, in_lo, in_ld, rows, wp, work, n_var, inv_off, f16=False):
         """Loop-invariant partial sums of the first layer: fp32 (rows, cout_pad), computed once per forward.  in_hi / in_lo:
-        channel 0 of the buffer; the launch starts at channel inv_off."""
+        channel 0 of the buffer; the launch starts at channel inv_off.
+        f16 = True: in_hi is the fp16 plane of the single-plane fp16 format and in_lo is None (see run())."""
+        if f16:
+            self._check_f16(in_hi, in_lo)
         _, inv = self.packed_first_split(in_hi.device, n_var, inv_off)
         out = _buf(work, ("partial", rows, inv["cout_pad"]), lambda: torch.empty((rows, inv["cout_pad"]), dtype=torch.float32, device=in_hi.device))
+        if f16:
+            n = lib.conv_mfma(in_hi[:, inv_off:], None, in_ld, inv["cin"], self.packed_f16(in_hi.device, n_var, inv_off)[1], None, inv["bias"],
+                              inv["taps"], wp, False, rows, out_f32=out, f16=True)
+            self.last_invariant_tiles = self._reported(n, False, rows, wp, None) if self.record_tiles else ()
+            return out
         tiling, geom = self._tiling(inv, rows, wp)
         n = lib.conv_mfma(in_hi[:, inv_off:], in_lo[:, inv_off:], in_ld, inv["cin"], inv["w_hi"], inv["w_lo"], inv["bias"], inv["taps"], wp,
                           False, rows, out_f32=out, tiling=tiling)
         self.last_invariant_tiles = () if n is None else self._reported(n, tiling, rows, wp, geom)
         return out
 
-    def run(self, in_hi, in_lo, in_ld, rows, wp, work, first_addend=None, n_var=None, inv_off=None, upsample=None, gauss=None, mx=None):
+    def _check_f16(self, in_hi, in_lo):
+        if self.small_tiles is True:
+            raise lib.MagnetError("ConvStackMFMA: the single-plane fp16 format has no 64-row tile form (small_tiles=True)")
+        if in_lo is not None or in_hi.dtype != torch.float16:
+            raise lib.MagnetError("ConvStackMFMA: f16=True takes one fp16 plane (in_hi) and in_lo=None")
+
+    def run(self, in_hi, in_lo, in_ld, rows, wp, work, first_addend=None, n_var=None, inv_off=None, upsample=None, gauss=None, mx=None,
+            f16=False):
         """in_hi/in_lo: bf16 views whose data_ptr is row 0, channel 0 of this stack's input; `work`: dict for cached
         hidden buffers.  Returns (fp32 tensor (rows, cout_pad_last), cout_pad_last).
         upsample = (depths (n,B,2,h,w), outs (n,B,2,4h,4w)): the mask head's stack only (144 outputs, fused tail) — the learned
         convex upsampling runs in the tail's last layer and only `outs` is written (returns (None, 144)); see can_fuse_upsample().
         gauss = (gmm_in, gmm_out): G-Net's stack only — the Gaussian update runs behind the head (returns (None, 16)); can_fuse_gauss().
         mx = (in_sc, sc_rows): the input planes are in the fp16 + e4m3 operand format (in_hi fp16, in_lo the e4m3 container, in_sc the
-        E8M0 plane of lib.pack_mx); fused-epilogue stacks with at least 65 536 rows only."""
+        E8M0 plane of lib.pack_mx); fused-epilogue stacks with at least 65 536 rows only.
+        f16 = True: the 3x3 layer on the single-plane fp16 format (lib.conv_mfma(f16=True)): in_hi is an fp16 plane, in_lo None; the
+        fused 1x1 tail stays bf16x3.  Fused-epilogue stacks only; with small_tiles=True a MagnetError (no 64-row form)."""
         dev = in_hi.device
+        if f16:
+            return self._run_f16(in_hi, in_lo, in_ld, rows, wp, first_addend, n_var, inv_off, upsample, gauss, mx, work)
         packs = self.packed(dev)
         if first_addend is not None:
             # first layer over the per-iteration channels only; the invariant part arrives as `first_addend`

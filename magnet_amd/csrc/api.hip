@@ -300,9 +300,10 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 }
 
 // magnet_conv_mfma and magnet_conv_mfma_ex: leaky != 0 selects LeakyReLU(leaky_slope) after bias (validated by the _ex entry point)
-static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream) {
+// f16: the single-plane fp16 operand format (magnet_conv_mfma_f16, which has checked what that format serves): no lo planes
+static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream, bool f16 = false) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
-    if (!a->in_hi || !a->in_lo || !a->w_hi || !a->w_lo || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
+    if (!a->in_hi || (!f16 && !a->in_lo) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
     if (a->out_mode < 0 || a->out_mode > 2) return fail(MAGNET_E_DIM, "magnet_conv_mfma: out_mode must be 0, 1 or 2");
     const bool tail = a->tail_w_hi != nullptr;
     if (tail) {
@@ -397,7 +398,7 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
-    hipError_t e = magnet::launch_conv_mfma(p, (hipStream_t)stream);
+    hipError_t e = f16 ? magnet::launch_conv_mfma_f16(p, (hipStream_t)stream) : magnet::launch_conv_mfma(p, (hipStream_t)stream);
     if (tiles_out) *tiles_out = tiles;
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv_mfma launch");
 }
@@ -421,6 +422,45 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
                                       "with cout_pad %% 128 == 0, bf16x3 operands only (taps=%d cout_pad=%d)", b.taps, b.cout_pad);
     }
     return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream);
+}
+
+MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs* a, void* stream) {
+    if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_f16: args is NULL");
+    const MagnetConvArgs& b = a->base;
+    // a caller that passes bf16x3 (or fp16 + e4m3) planes by mistake is refused rather than mis-read
+    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: in_lo, w_lo, in_sc and w_sc must be NULL (in_hi / w_hi are the only operand planes, fp16)");
+    if (a->act != MAGNET_ACT_BASE) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: act=%d (MAGNET_ACT_BASE only)", a->act);
+    if (a->tiling & ~(MAGNET_TILING_FLAT | MAGNET_TILING_BM256))
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: tiling=%d (MAGNET_TILING_FLAT and MAGNET_TILING_BM256 only)", a->tiling);
+    if (b.taps != 9 || b.dil > 1 || b.cout_pad != 128)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: 3x3 layers (taps == 9, no dilation) with cout_pad == 128 only (taps=%d dil=%d cout_pad=%d)", b.taps, b.dil, b.cout_pad);
+    if (b.add_hi || b.add_lo || b.border_hp || b.repad) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: no residual input, border or repad form");
+    if (b.tail_w_hi ? (b.tail_cout_pad != 16 && b.tail_cout_pad != 144) : b.out_mode != 1)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: a fused tail of 16 or 144 outputs, or the plain layer with fp32 output (out_mode 1)");
+    return conv_mfma_run(&a->base, 0, 0.f, a->tiling, a->tiles_out, stream, true);
+}
+
+MAGNET_API int magnet_pack_f16(const float* nchw, void* out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,
+                               int64_t in_img_stride, void* stream) {
+    if (!nchw || !out_f16) return fail(MAGNET_E_NULL, "magnet_pack_f16: NULL pointer");
+    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || (ctot % 8) != 0 || (c_off % 8) != 0 || c_off < 0 || c_off + ((C + 7) / 8) * 8 > ctot || in_img_stride < 0 ||
+        (int64_t)N * (h + 2) * (w + 2) >= ((int64_t)1 << 31))
+        return fail(MAGNET_E_DIM, "magnet_pack_f16: bad dims N=%d C=%d h=%d w=%d ctot=%d c_off=%d", N, C, h, w, ctot, c_off);
+    if (!aligned16(out_f16)) return fail(MAGNET_E_ALIGN, "magnet_pack_f16: output not 16-byte aligned");
+    hipError_t e = magnet::launch_pack_f16(nchw, (uint16_t*)out_f16, N, C, h, w, ctot, c_off,
+                                           in_img_stride ? (long long)in_img_stride : (long long)C * h * w, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_pack_f16 launch");
+}
+
+MAGNET_API int magnet_planes_to_f16(const void* in_hi, const void* in_lo, int32_t ld, void* out_f16, int32_t ld16, int64_t rows, int32_t c0,
+                                    int32_t c1, void* stream) {
+    if (!in_hi || !in_lo || !out_f16) return fail(MAGNET_E_NULL, "magnet_planes_to_f16: NULL pointer");
+    if (rows <= 0 || rows >= ((int64_t)1 << 31) || c0 < 0 || c1 <= c0 || (c0 % 8) != 0 || (c1 % 8) != 0 || (ld % 8) != 0 || (ld16 % 8) != 0 || c1 > ld || c1 > ld16)
+        return fail(MAGNET_E_DIM, "magnet_planes_to_f16: bad dims rows=%lld ld=%d ld16=%d c0=%d c1=%d (multiples of 8, c0 < c1 <= ld, ld16)", (long long)rows, ld, ld16, c0, c1);
+    if (!aligned16(in_hi) || !aligned16(in_lo) || !aligned16(out_f16)) return fail(MAGNET_E_ALIGN, "magnet_planes_to_f16: pointers not 16-byte aligned");
+    hipError_t e = magnet::launch_planes_to_f16((const uint16_t*)in_hi, (const uint16_t*)in_lo, (uint16_t*)out_f16, rows, ld, ld16, c0, c1, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_planes_to_f16 launch");
 }
 
 MAGNET_API int64_t magnet_conv_row_tiles(int32_t n_img, int32_t h, int32_t wp, int32_t bm, int32_t* tiles_per_img) {

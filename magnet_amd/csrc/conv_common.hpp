@@ -6,7 +6,8 @@
 namespace magnet {
 
 struct ConvParams {
-    const uint16_t* in_hi;  const uint16_t* in_lo;    // activations, row 0 of the flattened padded grid
+    const uint16_t* in_hi;  const uint16_t* in_lo;    // activations, row 0 of the flattened padded grid (launch_conv_mfma_f16: in_hi / w_hi
+                                                      // are fp16 planes, in_lo / w_lo NULL)
     const uint16_t* w_hi;   const uint16_t* w_lo;     // [taps][cout_pad][cin]
     const float*    bias;                             // [cout_pad]
     uint16_t* out_hi; uint16_t* out_lo;               // OUT mode 0: bf16 planes [rows][cout_pad]
@@ -78,7 +79,12 @@ struct ChainParams {
 };
 
 hipError_t launch_conv_mfma(const ConvParams&, hipStream_t);
+hipError_t launch_conv_mfma_f16(const ConvParams&, hipStream_t);       // single-plane fp16 operands: in_hi / w_hi fp16, in_lo / w_lo unused
 hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
+hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
+                           hipStream_t s);
+hipError_t launch_planes_to_f16(const uint16_t* in_hi, const uint16_t* in_lo, uint16_t* out, long long rows, int ld, int ld16, int c0, int c1,
+                                hipStream_t s);
 hipError_t launch_pack_mx(const float* in, uint16_t* out_f16, uint8_t* out_qr, uint32_t* out_sc, int N, int C, int h, int w, int ctot, int c_off,
                           long long sc_rows, long long in_img_stride, hipStream_t s);
 

@@ -72,13 +72,16 @@ struct UpArgs { const float* depth; float* out; int npred, h, w, B; };   // Gaus
 // weights through the vector-memory path, bit-identical results: 2.07 - 2.09 / 1.90 - 1.93 ms against 2.07 - 2.08 / 1.88 - 1.89 ms for
 // this form on the two stacks, same box (profiles/r4/conv_tail_ownership_ab.log).  Not kept: the tails, like the K loop, do not speed
 // up by moving load between pipes.)
-template <int TAILN, bool LAST, int ROWS, int NW = 4, bool UP = false>
+template <int TAILN, bool LAST, int ROWS, int NW = 4, bool UP = false, bool OPAQUE_LANE = false>
 __device__ __forceinline__ void tail_layer_cols(const uint16_t* __restrict__ w_hi, const uint16_t* __restrict__ w_lo,
                                                 const float* __restrict__ bias, unsigned char* act_hi, unsigned char* act_lo,
                                                 float* __restrict__ out, int out_ld, long long row0, long long rows, int lane, int wv,
                                                 const UpArgs up = UpArgs{nullptr, nullptr, 0, 0, 0, 0}) {
     // NW waves: wave w owns output fragments w, w + NW, ...; MA row blocks, read from LDS MB = 8 at a time (all 4 of a 64-row tile)
     constexpr int NJ = TAILN / NW, REM = TAILN % NW, MA = ROWS / 16, MR = MA / NW;   // MR: remainder-fragment row blocks per wave
+    // OPAQUE_LANE (the fp16 instances' upsampling layer): this call derives its fragment addresses itself instead of sharing them with
+    // the plain last layer in the other branch — kept alive across this one's 256-register peak, two of them went to scratch
+    if constexpr (OPAQUE_LANE) asm volatile("" : "+v"(lane));
     constexpr int MB = MA < 8 ? MA : 8;
     static_assert(REM <= 1 && MA % MB == 0 && MA % NW == 0, "one row-split remainder fragment at most");
     f32x4_t acc[NJ > 0 ? NJ : 1][MA], accr[MR];
@@ -271,6 +274,13 @@ __device__ __forceinline__ f32x4_t cv_mma(const bf16x8_t& a, const bf16x8_t& b, 
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
+// The same for the single-plane fp16 format: a, b are fp16 fragments
+template <bool SWAP>
+__device__ __forceinline__ f32x4_t cv_mma_f16(const f16x8_t& a, const f16x8_t& b, const f32x4_t& c) {
+    if constexpr (SWAP) return __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+
 // The 16-byte fragment read (LDS or global): 8 bf16 / fp16 of one row's K slot
 template <typename V = bf16x8_t>
 __device__ __forceinline__ V ld_frag(const void* ptr) { return __builtin_bit_cast(V, *reinterpret_cast<const uint4*>(ptr)); }
@@ -304,15 +314,17 @@ struct StepCounter {
 //   WIN == 0: 2*SPB stages of [window | weights], interleaved         WIN == 1: 2 window slots, then 2 weight slots
 //   WIN == 2: 1 window slot, then a 3-slot weight ring                 WIN == 4: 2 x {window, scales of its rows [512] u32}, a 4-slot ring
 //   of fp16 weight planes, then 2 x {3 taps x qr weight tile, weight scales [512] u32, 16 zero bytes (block 3 of the weight operand)}
-template <int NF, int WN, int BM, int SPB, int NT, bool PP, int WIN>
+//   F16 (the single-plane fp16 format, WIN == 2 only): the same slots with ONE plane each — no lo plane behind the window or a weight tile
+template <int NF, int WN, int BM, int SPB, int NT, bool PP, int WIN, bool F16 = false>
 struct ConvLds {
     static_assert(WIN != 4 || PP, "the fp16 + e4m3 format exists on the ping-pong loop only");
+    static_assert(!F16 || WIN == 2, "the single-plane fp16 format exists on the register-window loops only");
     static constexpr int BN = NF * 16;
     static constexpr int AW_ROWS = WIN ? BM + 8 : BM;             // window: up to (3-1)*2 extra rows (dilation 2), padded to 8
     static constexpr int A_BYTES = AW_ROWS * CV_ROW, B_BYTES = BN * CV_ROW;       // one plane of a window / of a weight tile
     static constexpr int SC_BYTES = WIN == 4 ? 512 * 4 : 0;
-    static constexpr int AW_BYTES = 2 * A_BYTES + SC_BYTES;       // window slot
-    static constexpr int BW_BYTES = WIN == 4 ? B_BYTES : 2 * B_BYTES;             // weight slot
+    static constexpr int AW_BYTES = (F16 ? 1 : 2) * A_BYTES + SC_BYTES;           // window slot
+    static constexpr int BW_BYTES = (WIN == 4 || F16) ? B_BYTES : 2 * B_BYTES;    // weight slot
     static constexpr int QB_ZERO = 3 * B_BYTES + SC_BYTES, QB_BYTES = WIN == 4 ? QB_ZERO + 16 : 0;
     static constexpr int A_SLOTS = WIN == 2 ? 1 : WIN == 0 ? 2 * SPB : 2;
     static constexpr int B_SLOTS = WIN == 4 ? 4 : WIN == 2 ? 3 : 2 * SPB;
@@ -348,12 +360,15 @@ struct ConvLds {
 // 5.91 ms per C2 step), with a 2-slot LDS window, with fragment double-buffering and with deeper prefetch (4 % slower: 2.19 vs 2.10 ms,
 // profiles/r4/conv_deeper_prefetch_vs_round3.log); persistent workgroups (0.7 % slower, profiles/r4/conv_persistent_ab.log); the 32x32x16 MFMA shape (5.5 %
 // slower, profiles/r5/conv_m32_ab.log); a row-owned fused tail (see tail_layer_cols).
-template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN>
+// F16 = the single-plane fp16 operand format (magnet_conv_mfma_f16): in_hi / w_hi are fp16 planes and there is no lo plane, so the
+// staging blocks issue the hi pieces only and the two F16 loops below (copies of the WIN == 2 schedules) issue one
+// v_mfma_f32_16x16x32_f16 per fragment pair; everything behind the K loop is the code of the bf16x3 instances.
+template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool F16 = false>
 __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsigned bid, const unsigned n_tiles, const unsigned by, const int tid) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-descriptor builtins do not exist in the host pass (which only needs the stub)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the K loop's ring (ConvLds; declared here, not passed in: a pointer
                                                                             // parameter is a generic pointer, and its casts to LDS pointers get null checks)
-    using L = ConvLds<NF, WN, CV_BM, SPB, NT, PP, WIN>;
+    using L = ConvLds<NF, WN, CV_BM, SPB, NT, PP, WIN, F16>;
     constexpr int BN = L::BN, A_BYTES = L::A_BYTES, B_BYTES = L::B_BYTES;
     constexpr int RP = NT / 4;                      // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
     constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (1, 2 or 4)
@@ -407,11 +422,11 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
     const uint32_t flags = 0x00020000u;
     const __amdgpu_buffer_rsrc_t ra_hi = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in_hi + base_row * p.in_ld), 0,
                                                                            (int)((end_row - base_row) * p.in_ld * 2), flags);
-    const __amdgpu_buffer_rsrc_t ra_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in_lo + base_row * p.in_ld), 0,
+    const __amdgpu_buffer_rsrc_t ra_lo = __builtin_amdgcn_make_buffer_rsrc((void*)((F16 ? p.in_hi : p.in_lo) + base_row * p.in_ld), 0,
                                                                            (int)((end_row - base_row) * p.in_ld * 2), flags);
     const int w_bytes = p.taps * p.cout_pad * p.cin * 2;
     const __amdgpu_buffer_rsrc_t rb_hi = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hi, 0, w_bytes, flags);
-    const __amdgpu_buffer_rsrc_t rb_lo = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_lo, 0, w_bytes, flags);
+    const __amdgpu_buffer_rsrc_t rb_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(F16 ? p.w_hi : p.w_lo), 0, w_bytes, flags);   // F16: never used
     int a_v[A_PT], b_v[B_PT];                                  // per-lane byte offsets, constant over the K loop
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) a_v[i] = (((int)(row0 - base_row) + st_r + i * RP) * p.in_ld + st_k) * 2;
@@ -429,17 +444,17 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
     // hi / lo DMA pieces of a row window of `aw` rows into the slot at sa_hi; the aw - CV_BM rows past the tile are a few lanes of wave 0
     // (two more pieces for its counted waits).  A plain A tile is a window of CV_BM rows.
     auto stage_window = [&](unsigned char* sa_hi, const int a_u, const int aw) {
-        unsigned char* sa_lo = sa_hi + A_BYTES;
+        [[maybe_unused]] unsigned char* sa_lo = sa_hi + A_BYTES;
 #pragma unroll
         for (int i = 0; i < A_PT; ++i) {
             CV_BLDS(ra_hi, sa_hi + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
-            CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
+            if constexpr (!F16) CV_BLDS(ra_lo, sa_lo + (wave_row + i * RP) * CV_ROW, a_v[i] + a_u);
         }
         if constexpr (WIN != 0) {
             if (wv == 0 && st_r < aw - CV_BM) {
                 const int ax = a_v[0] + CV_BM * p.in_ld * 2;
                 CV_BLDS(ra_hi, sa_hi + CV_BM * CV_ROW, ax + a_u);
-                CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
+                if constexpr (!F16) CV_BLDS(ra_lo, sa_lo + CV_BM * CV_ROW, ax + a_u);
             }
         }
     };
@@ -451,7 +466,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                 if (st_r + i * RP >= BN) continue;
             }
             CV_BLDS(rb_hi, sb_hi + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
-            CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
+            if constexpr (!F16) CV_BLDS(rb_lo, sb_lo + (wave_row + i * RP) * CV_ROW, b_v[i] + b_u);
         }
     };
 
@@ -518,6 +533,114 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         for (int n = 0; n < NFW; ++n) mma3(n, ah, al, ld_frag(sb_hi + b_off + n * 16 * CV_ROW), ld_frag(sb_hi + B_BYTES + b_off + n * 16 * CV_ROW));
     };
 
+    if constexpr (F16 && PP) {
+        // ---- single-plane fp16, 8 waves: the ping-pong x register-window schedule below with one DMA piece where it has a (hi, lo)
+        // pair — BP = B_PT, AP = A_PT, one extra window piece for wave 0 — 12 + 4 fragment reads per group / sub-step instead of 24 + 8,
+        // and 16 MFMAs per compute phase instead of 48.  Same phase order, same RAW / WAR argument.
+        static_assert(WIN == 2 && NT == 512 && SPB == 1 && BN % RP == 0 && CV_BM % RP == 0, "8 waves, whole DMA passes");
+        constexpr int BP = B_PT, AP = A_PT;
+        const int aw = CV_BM + 2 * p.tap_sx;
+        const int ngroups = 3 * ksteps_per_tap;
+        StepCounter gw, bs;                                   // next window (i = ty) / weight tile (i = tap) to fetch
+        auto dma_a = [&]() { stage_window(win_slot(0), a_step(gw.i, 0, gw.k0), aw); gw.advance(3); };
+        auto dma_b = [&](int slot) { stage_weights(wt_slot(slot), nullptr, (bs.i * p.cout_pad * p.cin + bs.k0) * 2); bs.advance(9); };
+        f16x8_t ah[3][MF], fbh[NFW];
+        auto load_b = [&](const unsigned char* sb) {
+#pragma unroll
+            for (int n = 0; n < NFW; ++n) fbh[n] = ld_frag<f16x8_t>(sb + b_off + n * 16 * CV_ROW);
+        };
+        auto mfmas = [&](const f16x8_t (&x)[MF]) {
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int n = 0; n < NFW; ++n)
+#pragma unroll
+                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma_f16<(TAIL > 0)>(x[m], fbh[n], acc[m][n]);
+            __builtin_amdgcn_s_setprio(0);
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        };
+        const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
+        dma_a();
+        dma_b(0);
+        dma_b(1);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP) : "memory");                 // window 0 and stage 0 landed (this wave's pieces)
+        __builtin_amdgcn_s_barrier();
+        if (grp == 1) __builtin_amdgcn_s_barrier();           // group 1 runs one barrier (= half a sub-step) behind group 0
+        for (int g = 0; g < ngroups; ++g) {
+            const bool lastg = g + 1 == ngroups;
+            // ---- tx = 0 ----
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int tx = 0; tx < 3; ++tx)
+#pragma unroll
+                for (int m = 0; m < MF; ++m) ah[tx][m] = ld_frag<f16x8_t>(win_slot(0) + a_offx[tx] + m * 16 * CV_ROW);
+            load_b(wt_slot(0));
+            dma_b(2);                                         // stage 3g + 2
+            wait_barrier<BP>();                               // stage 3g + 1 landed
+            mfmas(ah[0]);
+            // ---- tx = 1 ----
+            asm volatile("" ::: "memory");
+            load_b(wt_slot(1));
+            if (!lastg) {
+                dma_b(0); dma_a();                            // stage 3g + 3, window g + 1
+                if (wv == 0) wait_barrier<BP + AP + 1>(); else wait_barrier<BP + AP>();      // stage 3g + 2 landed
+            } else wait_barrier<0>();
+            mfmas(ah[1]);
+            // ---- tx = 2 ----
+            asm volatile("" ::: "memory");
+            load_b(wt_slot(2));
+            if (!lastg) { dma_b(1); wait_barrier<BP>(); }     // stage 3g + 4; stage 3g + 3 and window g + 1 landed
+            else wait_barrier<0>();
+            mfmas(ah[2]);
+        }
+        if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
+        __syncthreads();                                      // nothing in flight; the ring is dead
+    } else
+    if constexpr (F16) {
+        // ---- single-plane fp16, 4 waves: the register-window loop below (prefetch distance 2, slot tx holds stage 3g + tx) with one
+        // DMA piece per (hi, lo) pair; the window is 48 registers instead of 96
+        static_assert(WIN == 2 && !PP && SPB == 1 && NT == 256 && BN % RP == 0, "window loop with register-resident A: 4 waves, whole DMA passes");
+        constexpr int BP = B_PT, AP = A_PT;
+        const int aw = CV_BM + 2 * p.tap_sx;
+        const int ngroups = 3 * ksteps_per_tap;               // (K chunk, ty) pairs, ty inner
+        StepCounter gw, bs;
+        auto dma_a = [&]() { stage_window(win_slot(0), a_step(gw.i, 0, gw.k0), aw); gw.advance(3); };
+        auto dma_b = [&](int slot) { stage_weights(wt_slot(slot), nullptr, (bs.i * p.cout_pad * p.cin + bs.k0) * 2); bs.advance(9); };
+        f16x8_t ah[3][MF];
+        auto mfma_b = [&](int slot, const f16x8_t (&x)[MF]) {
+            f16x8_t fbh[NFW];
+#pragma unroll
+            for (int n = 0; n < NFW; ++n) fbh[n] = ld_frag<f16x8_t>(wt_slot(slot) + b_off + n * 16 * CV_ROW);
+#pragma unroll
+            for (int n = 0; n < NFW; ++n)
+#pragma unroll
+                for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma_f16<(TAIL > 0)>(x[m], fbh[n], acc[m][n]);
+        };
+        dma_a();
+        dma_b(0);
+        dma_b(1);
+        for (int g = 0; g < ngroups; ++g) {
+            const bool lastg = g + 1 == ngroups;
+            // ---- tx = 0: stage 3g (slot 0) and window g have landed; refill slot 2 with stage 3g + 2 ----
+            wait_barrier<BP, false, true>();
+            dma_b(2);
+#pragma unroll
+            for (int tx = 0; tx < 3; ++tx)
+#pragma unroll
+                for (int m = 0; m < MF; ++m) ah[tx][m] = ld_frag<f16x8_t>(win_slot(0) + a_offx[tx] + m * 16 * CV_ROW);
+            mfma_b(0, ah[0]);
+            // ---- tx = 1: every wave holds window g in registers (lgkmcnt(0) before the barrier): fetch window g + 1 ----
+            wait_barrier<BP, false, true>();
+            if (!lastg) { dma_b(0); dma_a(); }
+            mfma_b(1, ah[1]);
+            // ---- tx = 2 (the window's pieces, issued after the weight pieces, stay in flight; wave 0's extra piece makes its wait
+            // the stricter by one piece of stage 3g + 3, never the looser) ----
+            if (!lastg) { wait_barrier<BP + AP, false, true>(); dma_b(1); }
+            else wait_barrier<0, false, true>();
+            mfma_b(2, ah[2]);
+        }
+        __syncthreads();                                      // nothing in flight; the ring is dead (the epilogue reuses it)
+    } else
     if constexpr (WIN == 4 && PP) {
         // ---- round 4: the "2-unit" operand split on the 8-wave ping-pong loop (ConvParams::in_sc != nullptr) ----
         // x = hi + lo with hi = fp16(x): the main term hi_x * hi_w runs on v_mfma_f32_16x16x32_f16 (1 matrix-pipe unit per 32 K instead of
@@ -909,7 +1032,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                                              0, row0, p.rows, lane, wv);
         if constexpr (TAIL == 9) {
             if (p.up_out) {                           // fused convex upsampling: the 144 logits meet in LDS, never in HBM
-                tail_layer_cols<9, true, CV_BM, NW, true>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi,
+                tail_layer_cols<9, true, CV_BM, NW, true, F16>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi,
                                                           act_lo, nullptr, 0, row0, p.rows, lane, wv,
                                                           UpArgs{p.up_depth, p.up_out, p.up_npred, p.up_h, p.up_w, p.up_B});
                 return;
@@ -1031,10 +1154,16 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const ConvParams p) {
     conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
 }
 
-template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0>
-static size_t conv_lds_bytes() { return ConvLds<NF, WN, BM, SPB, NT, PP, WIN>::TOTAL; }
+// The instances of the single-plane fp16 format: kernels of their own name, so the bf16x3 instances keep theirs
+template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN>
+__global__ __launch_bounds__(NT, 2) void conv_mfma_f16_kernel(const ConvParams p) {
+    conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
+}
 
-template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0>
+template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
+static size_t conv_lds_bytes() { return ConvLds<NF, WN, BM, SPB, NT, PP, WIN, F16>::TOTAL; }
+
+template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
 static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
     // row tiles: the launches with a fused Gaussian update / upsampling know their image geometry (up_B, up_h, wp; rows checked by the
     // API) and write interior positions only, so each image can be tiled on its own without its top and bottom border image rows —
@@ -1047,17 +1176,20 @@ static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
         n_tiles = conv_row_tiles(p.up_B, p.up_h, p.wp, BM, &p.tiles_per_img);
     if (p.tiles_out) *p.tiles_out = n_tiles;
     dim3 grid((unsigned)n_tiles, (unsigned)(p.cout_pad / (NF * 16))), block(NT);
-    size_t lds = conv_lds_bytes<NF, WN, BM, SPB, NT, PP, WIN>();
+    size_t lds = conv_lds_bytes<NF, WN, BM, SPB, NT, PP, WIN, F16>();
     if (TAIL > 0 && lds < (size_t)BM * 512) lds = (size_t)BM * 512;     // the fused tail's activation tile: BM rows x 256 B x (hi, lo)
     constexpr size_t UP_STAGE = (size_t)(BM < 128 ? BM : 128) * 148 * 4;   // fused upsampling (tail_layer_cols: HR rows x SP floats): 128 (or BM = 64) rows x 144 logits (+4 pad) fp32
     if (TAIL == 9 && lds < UP_STAGE) lds = UP_STAGE;                        // (two 4-wave workgroups still fit a CU)
+    void (*const kernel)(const ConvParams) = [] {
+        if constexpr (F16) return &conv_mfma_f16_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>;
+        else return &conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>;
+    }();
     static bool attr_set = false;
     if (!attr_set && lds > 64 * 1024) {          // > 64 KiB of dynamic LDS needs the opt-in attribute
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>), grid, block, lds, s, p);
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, p);
     return hipGetLastError();
 }
 
@@ -1127,6 +1259,27 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     if (p.cout_pad == 32)  return launch_conv_nf<2, 1, 128, 1>(p, s);
     if (p.cout_pad == 64)  return launch_conv_nf<4, 1, 128, 1>(p, s);
     return hipErrorInvalidValue;
+}
+
+// The single-plane fp16 format (magnet_conv_mfma_f16): the launches MAGNET._refine_mfma makes and nothing else — the 3x3 layer with
+// the fused tail of G-Net (16 outputs) or the mask head (144), and the plain 128-wide 3x3 layer with fp32 output (the loop-invariant
+// part of G-Net's first layer).  The API has refused every other form.  Tile selection is launch_conv_mfma's: 256-row 8-wave tiles from
+// 65 536 rows on (or under MAGNET_TILING_BM256), except for the short per-iteration launches that carry an addend.
+hipError_t launch_conv_mfma_f16(const ConvParams& p, hipStream_t s) {
+    if (p.cout_pad != 128 || p.tap_n != 3) return hipErrorInvalidValue;
+    const bool big = p.rows >= 256ll * 256 || (p.tiling & 2);
+    if (p.tail_w_hi) {
+        if (big && !p.addend) {
+            if (p.tail_cout == 16) return launch_conv_nf<8, 2, 256, 1, 1, 512, true, 2, true>(p, s);
+            if (p.tail_cout == 144) return launch_conv_nf<8, 2, 256, 1, 9, 512, true, 2, true>(p, s);
+            return hipErrorInvalidValue;
+        }
+        if (p.tail_cout == 16) return launch_conv_nf<8, 2, 128, 1, 1, 256, false, 2, true>(p, s);
+        if (p.tail_cout == 144) return launch_conv_nf<8, 2, 128, 1, 9, 256, false, 2, true>(p, s);
+        return hipErrorInvalidValue;
+    }
+    if (big) return launch_conv_nf<8, 2, 256, 1, 0, 512, true, 2, true>(p, s);
+    return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 2, true>(p, s);
 }
 
 // =====================================================================================================

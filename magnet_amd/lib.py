@@ -262,6 +262,9 @@ _PROTOS = {
     "magnet_spp_pool_backward": (_C, [_S(MagnetSppBwdArgs), _P]),
     "magnet_fnet_stem_wgrad": (_C, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "magnet_conv_mfma_ex": (_C, [_S(MagnetConvExArgs), _P]),
+    "magnet_conv_mfma_f16": (_C, [_S(MagnetConvExArgs), _P]),
+    "magnet_pack_f16": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
+    "magnet_planes_to_f16": (_C, [_P, _P, _I, _P, _I, _L, _I, _I, _P]),
     "magnet_conv_row_tiles": (_L, [_I, _I, _I, _I, _S(_I)]),
     "magnet_dnet_gauss_head": (_C, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
@@ -582,7 +585,7 @@ def upsample_depth(depth, up_mask, k: int, out=None):
 # ---------------------------------------------------------------------------------------------------
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
-              mx=None, leaky=None, tiling=None):
+              mx=None, leaky=None, tiling=None, f16=False):
     """One convolution layer on the matrix cores.  in_hi/in_lo: bf16 tensors whose data_ptr is row 0 (possibly a
     channel-offset view of a wider buffer, `in_ld` = its row pitch in elements); weights (taps, cout_pad, cin) bf16.
     F-Net extras (include/magnet_hip.h): dil (3x3 dilation), out_ld (write a channel slice: out tensors may then be
@@ -595,9 +598,17 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     in the tail's last layer and only `gmm_out` is written.
     leaky = slope: LeakyReLU(slope) after bias instead of ReLU (magnet_conv_mfma_ex; relu must be False, no tail).
     tiling = TILING_* flags (magnet_conv_mfma_ex; tests and A/B runs).  Returns the number of row tiles launched when the launch went
-    through magnet_conv_mfma_ex, else None."""
+    through magnet_conv_mfma_ex, else None.
+    f16 = True: the single-plane fp16 operand format (magnet_conv_mfma_f16): in_hi / w_hi are fp16 tensors, in_lo / w_lo must be None;
+    3x3 layers with cout_pad 128, a fused tail of 16 / 144 outputs or out_f32.  Always returns the row tile count."""
     a = MagnetConvArgs()
-    if mx is not None:
+    if f16:
+        if in_lo is not None or w_lo is not None or mx is not None or leaky is not None:
+            raise MagnetError("conv_mfma (f16): one fp16 plane per operand — in_lo, w_lo, mx and leaky must be None")
+        for t, n in ((in_hi, "in_hi"), (w_hi, "w_hi")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float16:
+                raise MagnetError(f"conv_mfma (f16): {n} must be an fp16 GPU tensor")
+    elif mx is not None:
         # mx = (in_sc, w_sc, sc_rows): the fp16 + block-scaled e4m3 operand format (include/magnet_hip.h v302): in_hi / w_hi are fp16
         # planes, in_lo / w_lo the 2-byte-per-channel containers of the e4m3 hi | lo bytes (any 2-byte dtype), scales as int32 tensors
         for t, n in ((in_hi, "in_hi"), (w_hi, "w_hi")):
@@ -613,7 +624,9 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     else:
         for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo")):
             _bf16_ptr(t, f"conv_mfma: {n}")
-    a.in_hi, a.in_lo, a.w_hi, a.w_lo = in_hi.data_ptr(), in_lo.data_ptr(), w_hi.data_ptr(), w_lo.data_ptr()
+    a.in_hi, a.w_hi = in_hi.data_ptr(), w_hi.data_ptr()
+    if not f16:
+        a.in_lo, a.w_lo = in_lo.data_ptr(), w_lo.data_ptr()
     a.bias = _dev(bias, "bias", torch.float32).data_ptr()
     a.rows, a.cin, a.cout_pad, a.taps, a.wp = int(rows), int(cin), int(w_hi.shape[1]), int(taps), int(wp)
     a.relu, a.in_ld = int(bool(relu)), int(in_ld)
@@ -649,13 +662,13 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_hi = 2, _bf16_ptr(out_bf16, "out_bf16")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
-    if leaky is None and tiling is None:
+    if leaky is None and tiling is None and not f16:
         _launch("magnet_conv_mfma", in_hi, ctypes.byref(a))
         return None
     tiles = ctypes.c_int64(0)
     x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
-    _launch("magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
+    _launch("magnet_conv_mfma_f16" if f16 else "magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
     return tiles.value
 
 
@@ -698,6 +711,35 @@ def pack_mx(x_nchw, out_f16, out_qr, out_sc, ctot, c_off, sc_rows):
         raise MagnetError("pack_mx: ctot / c_off must be multiples of 32 with c_off + C <= ctot, and sc_rows >= N (h+2) (w+2)")
     _launch("magnet_pack_mx", x_nchw, x_nchw.data_ptr(), out_f16.data_ptr(), out_qr.data_ptr(), out_sc.data_ptr(), N, C, h, w, int(ctot),
             int(c_off), int(sc_rows), int(x_nchw.stride(0)) if N > 1 else 0)
+
+
+def pack_f16(x_nchw, out_f16, ctot, c_off):
+    """fp32 (N,C,h,w) (dense, or a leading-channel slice of a wider NCHW tensor) -> channels [c_off, c_off+C) of the interior of the
+    zero-bordered fp16 plane (N,h+2,w+2,ctot) of conv_mfma(f16=True).  Saturating round-to-nearest-even (include/magnet_hip.h)."""
+    if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
+        raise MagnetError("pack_f16: input must be a float32 GPU tensor")
+    N, C, h, w = x_nchw.shape
+    if x_nchw.stride()[1:] != (h * w, w, 1):
+        raise MagnetError(f"pack_f16: unsupported input strides {x_nchw.stride()}")
+    if not out_f16.is_cuda or out_f16.device != x_nchw.device or out_f16.dtype != torch.float16 or not out_f16.is_contiguous() or \
+            out_f16.numel() < N * (h + 2) * (w + 2) * int(ctot):
+        raise MagnetError(f"pack_f16: out_f16 must be a contiguous fp16 tensor on {x_nchw.device} with at least N (h+2) (w+2) ctot elements")
+    _launch("magnet_pack_f16", x_nchw, x_nchw.data_ptr(), out_f16.data_ptr(), N, C, h, w, int(ctot), int(c_off),
+            int(x_nchw.stride(0)) if N > 1 else 0)
+
+
+def planes_to_f16(in_hi, in_lo, out_f16, c0, c1):
+    """Channels [c0, c1) of the split-bf16 planes in_hi / in_lo (rows, ld) -> the same channels of the fp16 plane out_f16 (rows, ld16):
+    f16(hi + lo), every row.  c0, c1 multiples of 8."""
+    for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo")):
+        _bf16_ptr(t, f"planes_to_f16: {n}", contiguous=True)
+    if in_hi.dim() != 2 or in_lo.shape != in_hi.shape:
+        raise MagnetError("planes_to_f16: in_hi / in_lo must be (rows, ld) planes of one shape")
+    if not isinstance(out_f16, torch.Tensor) or out_f16.device != in_hi.device or out_f16.dtype != torch.float16 or out_f16.dim() != 2 or \
+            not out_f16.is_contiguous() or out_f16.shape[0] != in_hi.shape[0]:
+        raise MagnetError("planes_to_f16: out_f16 must be a contiguous fp16 (rows, ld16) plane on the inputs' device")
+    _launch("magnet_planes_to_f16", in_hi, in_hi.data_ptr(), in_lo.data_ptr(), int(in_hi.shape[1]), out_f16.data_ptr(), int(out_f16.shape[1]),
+            int(in_hi.shape[0]), int(c0), int(c1))
 
 
 def gaussian_update_cl(gnet_out_pad, ld, gmm_in, h, w, out=None):

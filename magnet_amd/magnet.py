@@ -4,7 +4,8 @@
 
 What runs where (inference, conv_backend='mfma'):
   * candidate sampling + warping + consistency-weighted score  -> HIP kernel (lib.cost_volume_cw, production matcher)
-  * G-Net / mask-head convolutions                              -> HIP matrix-core kernel (lib.conv_mfma, bf16x3 split)
+  * G-Net / mask-head convolutions                              -> HIP matrix-core kernel (lib.conv_mfma, bf16x3 split; with
+                                                                   conv_precision='fp16' the 3x3 layers on one fp16 plane)
   * Gaussian update tail, convex upsampling                     -> HIP kernels (lib.gaussian_update*/upsample_depth*)
   * a PSMNet-structured F-Net                                   -> HIP matrix-core path (magnet_amd/fnet.py)
   * D-Net                                                       -> caller-provided module; with dnet_backend='hip' its encoder runs
@@ -113,10 +114,19 @@ class MAGNET(nn.Module):
     `dnet_backend`: 'torch' (default) calls d_net as a module.  'hip' needs a D-Net with `.d_net.encoder` and `.d_net.decoder` (the
     reference's DNET or magnet_amd.dnet.DNET, DenseDepth_BN at downsample ratio 4, Gaussian output): the encoder runs as given, the
     decoder on the matrix-core path (magnet_amd.dnet.DNetMFMA), which writes the reference frames' x_d3 straight into
-    gnet_input_buffer(); needs conv_backend='mfma'.  While d_net is in training mode its own forward runs (batch-statistic BatchNorm)."""
+    gnet_input_buffer(); needs conv_backend='mfma'.  While d_net is in training mode its own forward runs (batch-statistic BatchNorm).
+    `conv_precision`: 'bf16x3' (default) or 'fp16', a reduced-precision inference mode the caller opts into.  'fp16' runs the 3x3
+    layer of g_net and of mask_head on ONE fp16 plane per operand (one matrix instruction per product instead of three; the fused 1x1
+    tails stay bf16x3): the replayed C2 step at 64 frames takes 3.96 instead of 5.67 ms, the shipped D = 5 / I = 3 step 6.43 instead
+    of 8.05 ms (profiles/precision/NOTES.md).  It is OUTSIDE this project's 1e-4 contract on final depth: abs_rel 5.2e-4 against the
+    oracle forward at the C3 shape (default path: 2.2e-5), 9.4e-6 and 3.3e-6 against the reference's own forward on the G6 and G13
+    fixtures (default: 2.9e-7, 1.4e-7) — measured with seeded weights, not trained ones (tests/test_gpu_magnet_f16.py).  Operands must
+    lie within fp16's range (|x| <= 65504; larger magnitudes are clamped).  Needs conv_backend='mfma'; it changes inference only
+    (_refine_mfma): under autograd, with either train_backend, nothing changes."""
 
     def __init__(self, args, d_net: nn.Module | None = None, f_net: nn.Module | None = None,
-                 feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch", dnet_backend: str = "torch"):
+                 feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch", dnet_backend: str = "torch",
+                 conv_precision: str = "bf16x3"):
         super().__init__()
         self.args = args
         if d_net is None or f_net is None:
@@ -162,6 +172,11 @@ class MAGNET(nn.Module):
         if train_backend not in ("torch", "hip"):
             raise lib.MagnetError(f"train_backend must be 'torch' or 'hip', got {train_backend!r}")
         self.train_backend = train_backend
+        if conv_precision not in ("bf16x3", "fp16"):
+            raise lib.MagnetError(f"conv_precision must be 'bf16x3' or 'fp16', got {conv_precision!r}")
+        if conv_precision == "fp16" and conv_backend != "mfma":
+            raise lib.MagnetError("conv_precision='fp16' is a mode of the matrix-core convolution path: it needs conv_backend='mfma'")
+        self.conv_precision = conv_precision
         if dnet_backend not in ("torch", "hip"):
             raise lib.MagnetError(f"dnet_backend must be 'torch' or 'hip', got {dnet_backend!r}")
         self.dnet_backend = dnet_backend
@@ -237,6 +252,16 @@ class MAGNET(nn.Module):
                 "cost": torch.empty((B, D, h, w), dtype=torch.float32, device=device)}
         return work["gin"][0], work["gin"][1], ctot, Dp
 
+    def _gnet_input_f16(self, B, h, w, device):
+        """conv_precision='fp16': the fp16 sibling of gnet_input_buffer(), same shape, cached next to it (zero border, zero padding
+        channels).  Nothing outside this class writes it: the split-bf16 buffer stays the one the matcher, the HIP D-Net and
+        magnet_gather_views fill, and _refine_mfma converts what they wrote."""
+        gin_hi = self.gnet_input_buffer(B, h, w, device)[0]
+        work = self._work[(str(device), B, h, w, gin_hi.shape[1])]
+        if "gin16" not in work:
+            work["gin16"] = torch.zeros(gin_hi.shape, dtype=torch.float16, device=device)
+        return work["gin16"]
+
     def match_and_refine(self, ref_gmms, x_d3, ref_feat_4, nghbr_feat_4, nghbr_gmms, nghbr_poses,
                          is_valid, cam_intrins, mode="test", packed_feats=None, x_d3_in_place=False):
         """MAGNET.py:146-175 from backbone outputs.  Returns the list of upsampled (B,2,H,W).
@@ -284,6 +309,12 @@ class MAGNET(nn.Module):
         D = self.n_samples
         dev = ref_gmms.device
         gin_hi, gin_lo, ctot, Dp = self.gnet_input_buffer(B, h, w, dev)
+        # conv_precision='fp16': the stacks' 3x3 layers read ONE fp16 plane (src, with in_lo None) that is filled from what arrives in the
+        # split-bf16 buffer: x_d3 once per forward, the cost channels [0, Dp) after every matcher launch
+        f16 = self.conv_precision == "fp16"
+        gin16 = self._gnet_input_f16(B, h, w, dev) if f16 else None
+        src_hi, src_lo, fkw = (gin16, None, dict(f16=True)) if f16 else (gin_hi, gin_lo, {})
+        m_src = (src_hi[:, Dp:], None if f16 else src_lo[:, Dp:])          # the mask head reads the x_d3 channels only
         g_stack, m_stack = self._stacks
         g_stack.fuse_epilogue = m_stack.fuse_epilogue = self.fuse_conv_tail
         rows, wp = B * (h + 2) * (w + 2), w + 2
@@ -301,12 +332,18 @@ class MAGNET(nn.Module):
             if pack_stream is not main:
                 x_d3.record_stream(pack_stream)
             with torch.cuda.stream(pack_stream):
-                lib.pack_split(x_d3, gin_hi, gin_lo, ctot, Dp)
+                if f16:
+                    lib.pack_f16(x_d3, gin16, ctot, Dp)
+                else:
+                    lib.pack_split(x_d3, gin_hi, gin_lo, ctot, Dp)
+        elif f16:
+            with torch.cuda.stream(pack_stream):
+                lib.planes_to_f16(gin_hi, gin_lo, gin16, Dp, Dp + 256)     # x_d3 written in place (HIP D-Net, gathered views)
         ev_pack.record(pack_stream)
         mask_out = None
         if self.overlap_mask_head:
             with torch.cuda.stream(pack_stream):
-                mask_out = m_stack.run(gin_hi[:, Dp:], gin_lo[:, Dp:], ctot, rows, wp, work.setdefault("mask", {}))  # MAGNET.py:172
+                mask_out = m_stack.run(*m_src, ctot, rows, wp, work.setdefault("mask", {}), **fkw)  # MAGNET.py:172
                 ev_mask = torch.cuda.Event(); ev_mask.record(pack_stream)
         pred_list = [ref_gmms.detach().float().contiguous()]
         # With more than one refinement iteration the x_d3 part of G-Net's first layer (256 of the 256+D input
@@ -317,7 +354,7 @@ class MAGNET(nn.Module):
             # the invariant convolution reads the x_d3 channels [Dp, Dp+256) only: nothing the matcher writes (a frame with a non-
             # finite cost cannot poison it), K = 9 * 256
             main.wait_event(ev_pack)
-            partial = g_stack.run_invariant(gin_hi, gin_lo, ctot, rows, wp, work, D, Dp)
+            partial = g_stack.run_invariant(src_hi, src_lo, ctot, rows, wp, work, D, Dp, **fkw)
         split_out = self.matcher_path in (0, 2, 4)
         for _ in range(n_iter):
             if split_out:
@@ -331,13 +368,15 @@ class MAGNET(nn.Module):
             if not split_out:
                 matcher(ref_gmm=pred_list[-1], k_list=self.k_list, out=work["cost"])
                 lib.pack_split(work["cost"], gin_hi, gin_lo, ctot, 0)
+            if f16:
+                lib.planes_to_f16(gin_hi, gin_lo, gin16, 0, Dp)
             main.wait_event(ev_pack)                                                                 # x_d3 channels are in place
             if self.fuse_upsample and g_stack.can_fuse_gauss(dev):
                 new_pred = torch.empty_like(pred_list[-1])                                           # MAGNET.py:62 + 60-69 in one launch
-                g_stack.run(gin_hi, gin_lo, ctot, rows, wp, work, first_addend=partial, n_var=D, inv_off=Dp, gauss=(pred_list[-1], new_pred))
+                g_stack.run(src_hi, src_lo, ctot, rows, wp, work, first_addend=partial, n_var=D, inv_off=Dp, gauss=(pred_list[-1], new_pred), **fkw)
                 pred_list.append(new_pred)
                 continue
-            g_out, g_ld = g_stack.run(gin_hi, gin_lo, ctot, rows, wp, work, first_addend=partial, n_var=D, inv_off=Dp)  # MAGNET.py:62
+            g_out, g_ld = g_stack.run(src_hi, src_lo, ctot, rows, wp, work, first_addend=partial, n_var=D, inv_off=Dp, **fkw)  # MAGNET.py:62
             pred_list.append(lib.gaussian_update_cl(g_out, g_ld, pred_list[-1], h, w))               # MAGNET.py:60-69
         if len(pred_list) == 1:                               # no refinement iteration: the reference returns [] (MAGNET.py:172-173)
             return []
@@ -348,9 +387,9 @@ class MAGNET(nn.Module):
                 # LDS) and writes every iteration's x4-upsampled prediction; the (B, 144, h, w) mask never reaches HBM
                 d = torch.stack(pred_list[1:])
                 outs = torch.empty((d.shape[0], B, 2, 4 * h, 4 * w), dtype=torch.float32, device=dev)
-                m_stack.run(gin_hi[:, Dp:], gin_lo[:, Dp:], ctot, rows, wp, work.setdefault("mask", {}), upsample=(d, outs))
+                m_stack.run(*m_src, ctot, rows, wp, work.setdefault("mask", {}), upsample=(d, outs), **fkw)
                 return [outs[i] for i in range(outs.shape[0])]
-            mask_out = m_stack.run(gin_hi[:, Dp:], gin_lo[:, Dp:], ctot, rows, wp, work.setdefault("mask", {}))      # MAGNET.py:172
+            mask_out = m_stack.run(*m_src, ctot, rows, wp, work.setdefault("mask", {}), **fkw)      # MAGNET.py:172
         else:
             main.wait_event(ev_mask)
         mask_pad, mask_ld = mask_out

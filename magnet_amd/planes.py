@@ -42,6 +42,22 @@ def pack_taps(w: torch.Tensor, cin_pad=None):
     return split_bf16(wt.contiguous())
 
 
+def to_f16_sat(x: torch.Tensor):
+    """fp32 -> fp16 as the single-plane fp16 format defines it (include/magnet_hip.h): round to nearest even, magnitudes that would
+    round above 65504 (+-Inf included) become +-65504, NaN stays NaN, the sign of zero is kept."""
+    return x.float().clamp(-65504.0, 65504.0).to(torch.float16)
+
+
+def pack_taps_f16(w: torch.Tensor, cin_pad=None):
+    """(cout, cin, kh, kw) fp32 -> ONE fp16 plane (kh*kw, cout, cin_pad or cin), cin contiguous, the padding channels zero: the weight
+    operand of lib.conv_mfma(f16=True)."""
+    cout, cin, kh, kw = w.shape
+    wt = w.float().permute(2, 3, 0, 1).reshape(kh * kw, cout, cin)
+    if cin_pad is not None and cin_pad != cin:
+        wt = torch.cat([wt, wt.new_zeros((kh * kw, cout, cin_pad - cin))], dim=2)
+    return to_f16_sat(wt).contiguous()
+
+
 def s2d_matrix(w: torch.Tensor):
     """3x3 stride-2 pad-1 weights (cout, C, 3, 3) -> the equivalent 2x2-window weights over a space-to-depth input: fp32
     (4, cout, 4*C); tap (ty,tx) in {-1,0}^2 -> index (ty+1)*2+(tx+1); channel (py*2+px)*C + c."""
