@@ -295,7 +295,12 @@ typedef struct MagnetConvArgs {
      * magnet_planes_to_f16 write the activation plane: round to nearest even, magnitudes that would round above 65504 (+-Inf included)
      * become +-65504 as in magnet_pack_mx, NaN is written through, the sign of zero is kept.  The fused 1x1 tail layers, bias, addend,
      * ReLU, the Gaussian update and the convex upsampling behind the 3x3 layer are those of the bf16x3 format (tail_w_hi / tail_w_lo stay
-     * bf16 planes). */
+     * bf16 planes).
+     * A SECOND entry point reads this format, magnet_conv_mfma_f16p ("plane to plane", the F-Net's layers): there the residual input
+     * (add_hi) is one fp16 plane too and out_mode 3 writes the result as ONE fp16 plane at out_hi, converted exactly as
+     * magnet_pack_f16 converts: every activation of a network then lives in this format from layer to layer.  Its domain is the
+     * format's, |x| <= 65504, CLAMPED: a layer output beyond it (an un-ReLU'd residual sum, say) is stored as +-65504 and not as Inf; a
+     * trained PSMNet's residual stream is bounded by its BatchNorms (seeded networks: below 10), but nothing checks it at run time.  NaN is written through. */
 } MagnetConvArgs;                          /* out_mode 2: one bf16 plane (round-to-nearest-even) at out_hi */
 
 MAGNET_API int magnet_conv_mfma(const MagnetConvArgs *args, void *stream);
@@ -629,6 +634,19 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
  * as in magnet_conv_mfma_ex (256-row tiles from 65 536 rows on, for launches without an addend; else 128-row tiles). */
 MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs *args, void *stream);
 
+/* The single-plane fp16 format, plane to plane: the launches of an F-Net whose every activation buffer is ONE zero-bordered
+ * channel-last fp16 plane (FNetMFMA(precision="fp16")).  The struct's fields mean, for this entry point only:
+ *   base.in_hi / base.w_hi   fp16 planes (rows, in_ld) / (taps, cout_pad, cin); base.in_lo, w_lo, in_sc, w_sc and add_lo must be NULL
+ *   base.add_hi              optional residual input, ONE fp16 plane with row pitch add_ld, added before bias / ReLU
+ *   base.out_mode            3: one fp16 plane at out_hi (saturating round-to-nearest-even, NaN written through: see MagnetConvArgs);
+ *                            1 (fp32 at out_f32) and 2 (one bf16 plane at out_hi) as in magnet_conv_mfma; 0 is refused
+ *   border_hp / border_pad / repad / dil / in_ld / out_ld   as in magnet_conv_mfma
+ * Serves taps 1, 4 and 9, cout_pad 32, 64 and 128, cin a multiple of 32, act == MAGNET_ACT_BASE, tiling 0 or MAGNET_TILING_FLAT (always
+ * 128-row tiles); tiles_out works.  A fused tail, an addend, the Gaussian update / upsampling, the e4m3 format and MAGNET_TILING_BM64 /
+ * MAGNET_TILING_BM256 are refused with MAGNET_E_DIM.  Each fp16 x fp16 product is exact in the fp32 accumulator; bias, residual and ReLU
+ * are fp32 arithmetic as in magnet_conv_mfma. */
+MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs *args, void *stream);
+
 /* fp32 NCHW (N, C, h, w) (image stride `in_img_stride` elements, 0 = C*h*w) -> channels [c_off, c_off + round_up(C, 8)) of the interior
  * of a zero-bordered (N, h+2, w+2, ctot) fp16 plane (the round-up lanes are written as zeros, as by magnet_pack_split).  ctot and c_off
  * multiples of 8.  The border rows and every other channel are not written.  Conversion: see the single-plane fp16 format above. */
@@ -640,6 +658,18 @@ MAGNET_API int magnet_pack_f16(const float *nchw, void *out_f16, int32_t N, int3
  * outside [c0, c1) is written. */
 MAGNET_API int magnet_planes_to_f16(const void *in_hi, const void *in_lo, int32_t ld, void *out_f16, int32_t ld16, int64_t rows,
                                     int32_t c0, int32_t c1, void *stream);
+
+/* The F-Net's non-GEMM layers on the single-plane fp16 format: magnet_fnet_stem, magnet_space_to_depth, magnet_avgpool_cl and
+ * magnet_upsample_bilinear_cl with ONE fp16 plane wherever those take a (hi, lo) pair.  Same geometry, same fp32 arithmetic; values
+ * are stored as magnet_pack_f16 stores them (space_to_depth moves 2-byte values unchanged). */
+MAGNET_API int magnet_fnet_stem_f16(const float *img, const float *wgt, const float *bias, void *out_f16, int32_t N, int32_t H, int32_t W,
+                                    void *stream);
+MAGNET_API int magnet_space_to_depth_f16(const void *in_f16, void *out_f16, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t opad,
+                                         void *stream);
+MAGNET_API int magnet_avgpool_cl_f16(const void *in_f16, int32_t ld, int32_t N, int32_t h, int32_t w, int32_t pad, int32_t k, int32_t C,
+                                     void *out_f16, void *stream);
+MAGNET_API int magnet_upsample_bilinear_cl_f16(const float *in, int32_t in_ld, int32_t ph, int32_t pw, int32_t C, void *out_f16,
+                                               int32_t out_ld, int32_t N, int32_t h, int32_t w, int32_t pad, void *stream);
 
 /* Row tiling of the launches that know their image geometry (base.gu_in / base.up_depth): the number of bm-row tiles (workgroups
  * along x) for n_img zero-bordered (h + 2, wp) grids, and in *tiles_per_img (optional) the tiles per image, or 0 for flat tiling.

@@ -21,6 +21,10 @@ hipError_t launch_fnet_stem(const float*, const float*, const float*, uint16_t*,
 hipError_t launch_space_to_depth(const uint16_t*, const uint16_t*, uint16_t*, uint16_t*, int, int, int, int, int, hipStream_t);
 hipError_t launch_avgpool_cl(const uint16_t*, const uint16_t*, int, int, int, int, int, int, int, uint16_t*, uint16_t*, hipStream_t);
 hipError_t launch_upsample_bilinear_cl(const float*, int, int, int, int, uint16_t*, uint16_t*, int, int, int, int, int, hipStream_t);
+hipError_t launch_fnet_stem_f16(const float*, const float*, const float*, uint16_t*, int, int, int, hipStream_t);
+hipError_t launch_space_to_depth_f16(const uint16_t*, uint16_t*, int, int, int, int, int, hipStream_t);
+hipError_t launch_avgpool_cl_f16(const uint16_t*, int, int, int, int, int, int, int, uint16_t*, hipStream_t);
+hipError_t launch_upsample_bilinear_cl_f16(const float*, int, int, int, int, uint16_t*, int, int, int, int, int, hipStream_t);
 hipError_t launch_depth_metrics(const float*, const float*, double*, int, int, int, float, float, int, int, int, int, hipStream_t);
 long long depth_metrics_workspace_bytes(int);
 hipError_t launch_depth_metrics_ex(const MagnetDepthMetricsArgs&, hipStream_t);
@@ -300,11 +304,16 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 }
 
 // magnet_conv_mfma and magnet_conv_mfma_ex: leaky != 0 selects LeakyReLU(leaky_slope) after bias (validated by the _ex entry point)
-// f16: the single-plane fp16 operand format (magnet_conv_mfma_f16, which has checked what that format serves): no lo planes
-static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream, bool f16 = false) {
+// mode: the operand format.  CONV_BF16X3: (hi, lo) planes (or the fp16 + e4m3 format).  CONV_F16: the single-plane fp16 operand format
+// (magnet_conv_mfma_f16, which has checked what that format serves): no lo planes.  CONV_F16P: the same operands, plane to plane
+// (magnet_conv_mfma_f16p): the residual is ONE fp16 plane (add_lo NULL) and out_mode 3 (one fp16 plane at out_hi) exists
+enum { CONV_BF16X3 = 0, CONV_F16 = 1, CONV_F16P = 2 };
+static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream, int mode = CONV_BF16X3) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
+    const bool f16 = mode != CONV_BF16X3;
     if (!a->in_hi || (!f16 && !a->in_lo) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
-    if (a->out_mode < 0 || a->out_mode > 2) return fail(MAGNET_E_DIM, "magnet_conv_mfma: out_mode must be 0, 1 or 2");
+    if (mode == CONV_F16P ? (a->out_mode < 1 || a->out_mode > 3) : (a->out_mode < 0 || a->out_mode > 2))
+        return fail(MAGNET_E_DIM, mode == CONV_F16P ? "magnet_conv_mfma_f16p: out_mode must be 1, 2 or 3" : "magnet_conv_mfma: out_mode must be 0, 1 or 2");
     const bool tail = a->tail_w_hi != nullptr;
     if (tail) {
         if (!a->tail_w_lo || !a->tail_bias || (!a->out_f32 && !a->up_out && !a->gu_out)) return fail(MAGNET_E_NULL, "magnet_conv_mfma: fused tail needs tail_w_lo, tail_bias and out_f32 (or up_out / gu_out)");
@@ -350,7 +359,7 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
     p.out_ld = a->out_ld ? a->out_ld : a->cout_pad;
     if (p.out_ld < a->cout_pad || (p.out_ld % 8) != 0) return fail(MAGNET_E_DIM, "magnet_conv_mfma: out_ld=%d must be >= cout_pad and a multiple of 8", p.out_ld);
     p.add_hi = (const uint16_t*)a->add_hi; p.add_lo = (const uint16_t*)a->add_lo; p.add_ld = a->add_ld ? a->add_ld : a->cout_pad;
-    if ((a->add_hi != nullptr) != (a->add_lo != nullptr)) return fail(MAGNET_E_NULL, "magnet_conv_mfma: add_hi and add_lo come together");
+    if (mode != CONV_F16P && (a->add_hi != nullptr) != (a->add_lo != nullptr)) return fail(MAGNET_E_NULL, "magnet_conv_mfma: add_hi and add_lo come together");
     if (a->add_hi && (!aligned16(a->add_hi) || !aligned16(a->add_lo) || (p.add_ld % 8) != 0 || p.add_ld < a->cout_pad))
         return fail(MAGNET_E_ALIGN, "magnet_conv_mfma: add_hi/add_lo must be 16-byte aligned with add_ld >= cout_pad, a multiple of 8");
     // the epilogue holds ONE pre-bias term per channel: with both, the addend would replace the residual (no caller passes both)
@@ -398,7 +407,8 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
-    hipError_t e = f16 ? magnet::launch_conv_mfma_f16(p, (hipStream_t)stream) : magnet::launch_conv_mfma(p, (hipStream_t)stream);
+    hipError_t e = mode == CONV_F16P ? magnet::launch_conv_mfma_f16p(p, (hipStream_t)stream)
+                 : mode == CONV_F16  ? magnet::launch_conv_mfma_f16(p, (hipStream_t)stream) : magnet::launch_conv_mfma(p, (hipStream_t)stream);
     if (tiles_out) *tiles_out = tiles;
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv_mfma launch");
 }
@@ -438,7 +448,23 @@ MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs* a, void* stream) {
     if (b.add_hi || b.add_lo || b.border_hp || b.repad) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: no residual input, border or repad form");
     if (b.tail_w_hi ? (b.tail_cout_pad != 16 && b.tail_cout_pad != 144) : b.out_mode != 1)
         return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: a fused tail of 16 or 144 outputs, or the plain layer with fp32 output (out_mode 1)");
-    return conv_mfma_run(&a->base, 0, 0.f, a->tiling, a->tiles_out, stream, true);
+    return conv_mfma_run(&a->base, 0, 0.f, a->tiling, a->tiles_out, stream, CONV_F16);
+}
+
+MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs* a, void* stream) {
+    if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_f16p: args is NULL");
+    const MagnetConvArgs& b = a->base;
+    // planes of another format are refused rather than mis-read
+    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc || b.add_lo)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: in_lo, w_lo, in_sc, w_sc and add_lo must be NULL (in_hi / w_hi / add_hi are single fp16 planes)");
+    if (a->act != MAGNET_ACT_BASE) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: act=%d (MAGNET_ACT_BASE only)", a->act);
+    if (a->tiling & ~MAGNET_TILING_FLAT)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", a->tiling);
+    if (b.tail_w_hi || b.tail_w_lo || b.addend || b.up_out || b.up_depth || b.gu_in || b.gu_out)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: no fused tail, addend, Gaussian update or upsampling");
+    if (b.cout_pad != 32 && b.cout_pad != 64 && b.cout_pad != 128)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: cout_pad=%d (32, 64 or 128)", b.cout_pad);
+    return conv_mfma_run(&a->base, 0, 0.f, a->tiling, a->tiles_out, stream, CONV_F16P);
 }
 
 MAGNET_API int magnet_pack_f16(const float* nchw, void* out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,
@@ -537,6 +563,45 @@ MAGNET_API int magnet_upsample_bilinear_cl(const float* in, int32_t in_ld, int32
     hipError_t e = magnet::launch_upsample_bilinear_cl(in, in_ld, ph, pw, C, (uint16_t*)out_hi, (uint16_t*)out_lo, out_ld, N, h, w, pad,
                                                        (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_upsample_bilinear_cl launch");
+}
+
+MAGNET_API int magnet_fnet_stem_f16(const float* img, const float* wgt, const float* bias, void* out_f16, int32_t N, int32_t H, int32_t W,
+                                    void* stream) {
+    if (!img || !wgt || !bias || !out_f16) return fail(MAGNET_E_NULL, "magnet_fnet_stem_f16: NULL pointer");
+    if (N <= 0 || H < 2 || W < 2) return fail(MAGNET_E_DIM, "magnet_fnet_stem_f16: bad dims N=%d H=%d W=%d", N, H, W);
+    if (!aligned16(out_f16)) return fail(MAGNET_E_ALIGN, "magnet_fnet_stem_f16: output must be 16-byte aligned");
+    hipError_t e = magnet::launch_fnet_stem_f16(img, wgt, bias, (uint16_t*)out_f16, N, H, W, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_stem_f16 launch");
+}
+
+MAGNET_API int magnet_space_to_depth_f16(const void* in_f16, void* out_f16, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t opad,
+                                         void* stream) {
+    if (!in_f16 || !out_f16) return fail(MAGNET_E_NULL, "magnet_space_to_depth_f16: NULL pointer");
+    if (N <= 0 || C <= 0 || (C % 8) != 0 || H2 <= 0 || W2 <= 0 || opad < 0)
+        return fail(MAGNET_E_DIM, "magnet_space_to_depth_f16: bad dims N=%d C=%d H2=%d W2=%d opad=%d", N, C, H2, W2, opad);
+    if (!aligned16(in_f16) || !aligned16(out_f16)) return fail(MAGNET_E_ALIGN, "magnet_space_to_depth_f16: pointers must be 16-byte aligned");
+    hipError_t e = magnet::launch_space_to_depth_f16((const uint16_t*)in_f16, (uint16_t*)out_f16, N, C, H2, W2, opad, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_space_to_depth_f16 launch");
+}
+
+MAGNET_API int magnet_avgpool_cl_f16(const void* in_f16, int32_t ld, int32_t N, int32_t h, int32_t w, int32_t pad, int32_t k, int32_t C,
+                                     void* out_f16, void* stream) {
+    if (!in_f16 || !out_f16) return fail(MAGNET_E_NULL, "magnet_avgpool_cl_f16: NULL pointer");
+    if (N <= 0 || C <= 0 || C > 128 || (C % 8) != 0 || ld < C || (ld % 8) != 0 || k <= 0 || h < k || w < k || pad < 0)
+        return fail(MAGNET_E_DIM, "magnet_avgpool_cl_f16: bad dims N=%d C=%d ld=%d h=%d w=%d k=%d pad=%d", N, C, ld, h, w, k, pad);
+    if (!aligned16(in_f16) || !aligned16(out_f16)) return fail(MAGNET_E_ALIGN, "magnet_avgpool_cl_f16: pointers must be 16-byte aligned");
+    hipError_t e = magnet::launch_avgpool_cl_f16((const uint16_t*)in_f16, ld, N, h, w, pad, k, C, (uint16_t*)out_f16, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_avgpool_cl_f16 launch");
+}
+
+MAGNET_API int magnet_upsample_bilinear_cl_f16(const float* in, int32_t in_ld, int32_t ph, int32_t pw, int32_t C, void* out_f16,
+                                               int32_t out_ld, int32_t N, int32_t h, int32_t w, int32_t pad, void* stream) {
+    if (!in || !out_f16) return fail(MAGNET_E_NULL, "magnet_upsample_bilinear_cl_f16: NULL pointer");
+    if (N <= 0 || C <= 0 || (C % 8) != 0 || in_ld < C || out_ld < C || (out_ld % 8) != 0 || ph <= 0 || pw <= 0 || h <= 0 || w <= 0 || pad < 0)
+        return fail(MAGNET_E_DIM, "magnet_upsample_bilinear_cl_f16: bad dims");
+    if (!aligned16(out_f16)) return fail(MAGNET_E_ALIGN, "magnet_upsample_bilinear_cl_f16: output must be 16-byte aligned");
+    hipError_t e = magnet::launch_upsample_bilinear_cl_f16(in, in_ld, ph, pw, C, (uint16_t*)out_f16, out_ld, N, h, w, pad, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_upsample_bilinear_cl_f16 launch");
 }
 
 MAGNET_API int magnet_conv1x1_chain(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias,

@@ -69,6 +69,25 @@ inline long long conv_row_tiles(long long n_img, long long h, long long wp, long
     return by_image ? n_img * per : flat;
 }
 
+// fp32 -> fp16 bits as the single-plane fp16 format defines it (include/magnet_hip.h): round to nearest even, a magnitude that would
+// round above 65504 (+-Inf included) becomes +-65504, NaN is written through, the sign of zero is kept.
+// v_med3_f32 returns a finite bound for a NaN operand, so NaN bypasses the clamp; med3(-0, -65504, 65504) = -0
+__device__ __forceinline__ uint32_t f16_bits_sat(float x) {
+    const float c = x != x ? x : __builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f);
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)c);               // v_cvt_f16_f32: RNE, fp16 denormals kept
+}
+__device__ __forceinline__ uint32_t f16x2_bits_sat(float a, float b) { return f16_bits_sat(a) | (f16_bits_sat(b) << 16); }
+// 8 fp32 -> one 16-byte vector of fp16 (f16_bits_sat each), and back (exact)
+__device__ __forceinline__ uint4 f16x8_pack_sat(const float* v) {
+    return make_uint4(f16x2_bits_sat(v[0], v[1]), f16x2_bits_sat(v[2], v[3]), f16x2_bits_sat(v[4], v[5]), f16x2_bits_sat(v[6], v[7]));
+}
+__device__ __forceinline__ void f16x8_unpack(const uint4 u, float* v) {
+    typedef __attribute__((ext_vector_type(8))) _Float16 h8_t;
+    const h8_t h = __builtin_bit_cast(h8_t, u);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
+}
+
 struct ChainParams {
     const uint16_t* in_hi;  const uint16_t* in_lo;    // (rows, 128)
     const uint16_t* w_hi;   const uint16_t* w_lo;     // [128][128], [128][128], [cout_pad][128] concatenated
@@ -80,6 +99,8 @@ struct ChainParams {
 
 hipError_t launch_conv_mfma(const ConvParams&, hipStream_t);
 hipError_t launch_conv_mfma_f16(const ConvParams&, hipStream_t);       // single-plane fp16 operands: in_hi / w_hi fp16, in_lo / w_lo unused
+hipError_t launch_conv_mfma_f16p(const ConvParams&, hipStream_t);      // the same operands, plane to plane (the F-Net): add_hi is ONE fp16 residual
+                                                                       // plane (add_lo unused), out_mode 3 = one fp16 plane at out_hi
 hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
 hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
                            hipStream_t s);

@@ -314,11 +314,12 @@ struct StepCounter {
 //   WIN == 0: 2*SPB stages of [window | weights], interleaved         WIN == 1: 2 window slots, then 2 weight slots
 //   WIN == 2: 1 window slot, then a 3-slot weight ring                 WIN == 4: 2 x {window, scales of its rows [512] u32}, a 4-slot ring
 //   of fp16 weight planes, then 2 x {3 taps x qr weight tile, weight scales [512] u32, 16 zero bytes (block 3 of the weight operand)}
-//   F16 (the single-plane fp16 format, WIN == 2 only): the same slots with ONE plane each — no lo plane behind the window or a weight tile
+//   F16 (the single-plane fp16 format, WIN == 2 and WIN == 0): the same slots with ONE plane each — no lo plane behind the window or a weight tile
 template <int NF, int WN, int BM, int SPB, int NT, bool PP, int WIN, bool F16 = false>
 struct ConvLds {
     static_assert(WIN != 4 || PP, "the fp16 + e4m3 format exists on the ping-pong loop only");
-    static_assert(!F16 || WIN == 2, "the single-plane fp16 format exists on the register-window loops only");
+    static_assert(!F16 || WIN == 2 || WIN == 0, "the single-plane fp16 format exists on the register-window loops and the windowless 4-wave loop");
+    static_assert(!F16 || WIN == 2 || (!PP && NT == 256 && SPB == 1), "windowless fp16: the 4-wave / 2-slot loop");
     static constexpr int BN = NF * 16;
     static constexpr int AW_ROWS = WIN ? BM + 8 : BM;             // window: up to (3-1)*2 extra rows (dilation 2), padded to 8
     static constexpr int A_BYTES = AW_ROWS * CV_ROW, B_BYTES = BN * CV_ROW;       // one plane of a window / of a weight tile
@@ -363,12 +364,16 @@ struct ConvLds {
 // F16 = the single-plane fp16 operand format (magnet_conv_mfma_f16): in_hi / w_hi are fp16 planes and there is no lo plane, so the
 // staging blocks issue the hi pieces only and the two F16 loops below (copies of the WIN == 2 schedules) issue one
 // v_mfma_f32_16x16x32_f16 per fragment pair; everything behind the K loop is the code of the bf16x3 instances.
-template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool F16 = false>
+// F16P = "plane to plane" (magnet_conv_mfma_f16p, the F-Net): F16 operands, and in the plain epilogue the residual input is ONE fp16
+// plane (add_hi) and out_mode 3 writes ONE fp16 plane (out_hi).  Besides the two WIN == 2 loops it runs the windowless loop at the
+// bottom with one fp16 MFMA per fragment pair (taps 1 and 4), and the 4-wave WIN == 2 loop at BN = 32 (one weight piece per wave).
+template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool F16 = false, bool F16P = false>
 __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsigned bid, const unsigned n_tiles, const unsigned by, const int tid) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-descriptor builtins do not exist in the host pass (which only needs the stub)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the K loop's ring (ConvLds; declared here, not passed in: a pointer
                                                                             // parameter is a generic pointer, and its casts to LDS pointers get null checks)
     using L = ConvLds<NF, WN, CV_BM, SPB, NT, PP, WIN, F16>;
+    static_assert(!F16P || (F16 && TAIL == 0 && !PP), "plane to plane: fp16 operands, plain epilogue, 4 waves");
     constexpr int BN = L::BN, A_BYTES = L::A_BYTES, B_BYTES = L::B_BYTES;
     constexpr int RP = NT / 4;                      // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
     constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (1, 2 or 4)
@@ -533,6 +538,19 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         for (int n = 0; n < NFW; ++n) mma3(n, ah, al, ld_frag(sb_hi + b_off + n * 16 * CV_ROW), ld_frag(sb_hi + B_BYTES + b_off + n * 16 * CV_ROW));
     };
 
+    // the same for the single-plane fp16 format: one MFMA per fragment pair
+    [[maybe_unused]] auto compute16 = [&](const unsigned char* sa, const unsigned char* sb, const int a_of) {
+        f16x8_t ah[MF];
+#pragma unroll
+        for (int m = 0; m < MF; ++m) ah[m] = ld_frag<f16x8_t>(sa + a_of + m * 16 * CV_ROW);
+#pragma unroll
+        for (int n = 0; n < NFW; ++n) {
+            const f16x8_t fb = ld_frag<f16x8_t>(sb + b_off + n * 16 * CV_ROW);
+#pragma unroll
+            for (int m = 0; m < MF; ++m) acc[m][n] = cv_mma_f16<(TAIL > 0)>(ah[m], fb, acc[m][n]);
+        }
+    };
+
     if constexpr (F16 && PP) {
         // ---- single-plane fp16, 8 waves: the ping-pong x register-window schedule below with one DMA piece where it has a (hi, lo)
         // pair — BP = B_PT, AP = A_PT, one extra window piece for wave 0 — 12 + 4 fragment reads per group / sub-step instead of 24 + 8,
@@ -596,16 +614,27 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
         __syncthreads();                                      // nothing in flight; the ring is dead
     } else
-    if constexpr (F16) {
+    if constexpr (F16 && WIN == 2) {
         // ---- single-plane fp16, 4 waves: the register-window loop below (prefetch distance 2, slot tx holds stage 3g + tx) with one
         // DMA piece per (hi, lo) pair; the window is 48 registers instead of 96
-        static_assert(WIN == 2 && !PP && SPB == 1 && NT == 256 && BN % RP == 0, "window loop with register-resident A: 4 waves, whole DMA passes");
+        // BN = 32 (F-Net's 32-wide trunk): the weight tile is 32 rows x 64 B = half a row pass; wave w stages rows 8 w .. 8 w + 7 with
+        // its lanes 0 .. 31 — ONE piece per wave, so the counted waits stay wave-uniform (as a row pass waves 2 and 3 had nothing to count)
+        static_assert(!PP && SPB == 1 && NT == 256 && (BN % RP == 0 || BN == 32), "window loop with register-resident A: 4 waves, whole DMA passes (or the 32-wide case)");
         constexpr int BP = B_PT, AP = A_PT;
+        static_assert(BN != 32 || BP == 1, "32-wide: one weight piece per wave and stage");
         const int aw = CV_BM + 2 * p.tap_sx;
         const int ngroups = 3 * ksteps_per_tap;               // (K chunk, ty) pairs, ty inner
         StepCounter gw, bs;
         auto dma_a = [&]() { stage_window(win_slot(0), a_step(gw.i, 0, gw.k0), aw); gw.advance(3); };
-        auto dma_b = [&](int slot) { stage_weights(wt_slot(slot), nullptr, (bs.i * p.cout_pad * p.cin + bs.k0) * 2); bs.advance(9); };
+        // BN = 32: row 8 w + (lane >> 2) of the tile; 8 w is a multiple of 8, so the swizzle term of st_k (from row 16 w + (lane >> 2)) is this row's
+        [[maybe_unused]] const int b_v32 = ((n0 + (wave_row >> 1) + (lane >> 2)) * p.cin + st_k) * 2;
+        auto dma_b = [&](int slot) {
+            const int b_u = (bs.i * p.cout_pad * p.cin + bs.k0) * 2;
+            if constexpr (BN == 32) {
+                if (lane < 32) CV_BLDS(rb_hi, wt_slot(slot) + (wave_row >> 1) * CV_ROW, b_v32 + b_u);
+            } else stage_weights(wt_slot(slot), nullptr, b_u);
+            bs.advance(9);
+        };
         f16x8_t ah[3][MF];
         auto mfma_b = [&](int slot, const f16x8_t (&x)[MF]) {
             f16x8_t fbh[NFW];
@@ -994,7 +1023,10 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                 if (s + SPB + q < nsteps) dma((half ^ 1) * SPB + q);
 #pragma unroll
             for (int q = 0; q < SPB; ++q)
-                if (s + q < nsteps) compute(win_slot(half * SPB + q), wt_slot(half * SPB + q), a_off);
+                if (s + q < nsteps) {
+                    if constexpr (F16) compute16(win_slot(half * SPB + q), wt_slot(half * SPB + q), a_off);
+                    else compute(win_slot(half * SPB + q), wt_slot(half * SPB + q), a_off);
+                }
             __syncthreads();                                  // next half landed; everyone done with this half
         }
     }
@@ -1107,6 +1139,9 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             }
             float v[8];
             float ad[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if constexpr (F16P) {                             // residual input: ONE fp16 plane, 8 channels per 16-byte load
+                if (p.add_hi) f16x8_unpack(*reinterpret_cast<const uint4*>(p.add_hi + (size_t)row * p.add_ld + ch), ad);
+            } else
             if (p.add_hi) {                                   // residual input, stored as split bf16 planes
                 const uint4 ah = *reinterpret_cast<const uint4*>(p.add_hi + (size_t)row * p.add_ld + ch);
                 const uint4 al = *reinterpret_cast<const uint4*>(p.add_lo + (size_t)row * p.add_ld + ch);
@@ -1129,6 +1164,12 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                 if (!interior) v[i] = 0.f;
             }
             const size_t e = (size_t)orow * p.out_ld + ch;
+            if constexpr (F16P) {
+                if (p.out_mode == 3) {                        // one fp16 plane, saturating RNE (f16_bits_sat): the next layer's operand
+                    *reinterpret_cast<uint4*>(p.out_hi + e) = f16x8_pack_sat(v);
+                    continue;
+                }
+            }
             if (p.out_mode == 2) {                            // single bf16 plane (RNE): the matcher's bf16 feature storage
                 uint32_t h[4];
 #pragma unroll
@@ -1160,10 +1201,16 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_f16_kernel(const ConvParams p
     conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
 }
 
+// The plane-to-plane instances (magnet_conv_mfma_f16p): again kernels of their own name
+template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN>
+__global__ __launch_bounds__(NT, 2) void conv_mfma_f16p_kernel(const ConvParams p) {
+    conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN, true, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
+}
+
 template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
 static size_t conv_lds_bytes() { return ConvLds<NF, WN, BM, SPB, NT, PP, WIN, F16>::TOTAL; }
 
-template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
+template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false, bool F16P = false>
 static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
     // row tiles: the launches with a fused Gaussian update / upsampling know their image geometry (up_B, up_h, wp; rows checked by the
     // API) and write interior positions only, so each image can be tiled on its own without its top and bottom border image rows —
@@ -1181,7 +1228,8 @@ static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
     constexpr size_t UP_STAGE = (size_t)(BM < 128 ? BM : 128) * 148 * 4;   // fused upsampling (tail_layer_cols: HR rows x SP floats): 128 (or BM = 64) rows x 144 logits (+4 pad) fp32
     if (TAIL == 9 && lds < UP_STAGE) lds = UP_STAGE;                        // (two 4-wave workgroups still fit a CU)
     void (*const kernel)(const ConvParams) = [] {
-        if constexpr (F16) return &conv_mfma_f16_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>;
+        if constexpr (F16P) return &conv_mfma_f16p_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>;
+        else if constexpr (F16) return &conv_mfma_f16_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>;
         else return &conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>;
     }();
     static bool attr_set = false;
@@ -1280,6 +1328,25 @@ hipError_t launch_conv_mfma_f16(const ConvParams& p, hipStream_t s) {
     }
     if (big) return launch_conv_nf<8, 2, 256, 1, 0, 512, true, 2, true>(p, s);
     return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 2, true>(p, s);
+}
+
+// The single-plane fp16 format, plane to plane (magnet_conv_mfma_f16p): the F-Net's launches — taps 9 (any dilation), 4 and 1 at 32,
+// 64 and 128 output channels, fp16 residual plane, fp16 / fp32 / single-bf16 output, channel slices, zero border, repad.  The API has
+// refused the fused tail, the addend, the e4m3 format and the BM64 / BM256 tilings.  Tiles are chosen as launch_conv_mfma chooses them
+// for the F-Net's launches (which carry img_rows, a residual or a 2-byte output: never the 256-row form): 128 rows, 4 waves; 3x3 on the
+// register-window loop, 1x1 and 2x2 windows on the windowless loop.
+hipError_t launch_conv_mfma_f16p(const ConvParams& p, hipStream_t s) {
+    if (p.tail_w_hi || p.addend || p.in_sc || (p.tiling & ~1)) return hipErrorInvalidValue;
+    if (p.tap_n == 3) {
+        if (p.cout_pad == 128) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 2, true, true>(p, s);
+        if (p.cout_pad == 64)  return launch_conv_nf<4, 1, 128, 1, 0, 256, false, 2, true, true>(p, s);
+        if (p.cout_pad == 32)  return launch_conv_nf<2, 1, 128, 1, 0, 256, false, 2, true, true>(p, s);
+        return hipErrorInvalidValue;
+    }
+    if (p.cout_pad == 128) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 0, true, true>(p, s);
+    if (p.cout_pad == 64)  return launch_conv_nf<4, 1, 128, 1, 0, 256, false, 0, true, true>(p, s);
+    if (p.cout_pad == 32)  return launch_conv_nf<2, 1, 128, 1, 0, 256, false, 0, true, true>(p, s);
+    return hipErrorInvalidValue;
 }
 
 // =====================================================================================================

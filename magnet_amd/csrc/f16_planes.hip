@@ -11,12 +11,7 @@
 
 namespace magnet {
 
-__device__ __forceinline__ uint32_t f16_bits_sat(float x) {
-    // v_med3_f32 returns a finite bound for a NaN operand, so NaN bypasses the clamp; med3(-0, -65504, 65504) = -0
-    const float c = x != x ? x : __builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f);
-    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)c);               // v_cvt_f16_f32: RNE, fp16 denormals kept
-}
-__device__ __forceinline__ uint32_t f16x2_bits_sat(float a, float b) { return f16_bits_sat(a) | (f16_bits_sat(b) << 16); }
+// f16_bits_sat / f16x2_bits_sat: conv_common.hpp (shared with the convolution epilogue and the F-Net's small kernels)
 
 // ---- fp32 NCHW (N, C, h, w) -> fp16 plane of the padded channel-last buffer (N, h+2, w+2, ctot), channels [c_off, c_off + C);
 // ---- 64 pixels x 64 channels per block through LDS; interior only (pack_split_kernel's structure, one output plane)

@@ -7,8 +7,11 @@
 //   upsample      bilinear, align_corners=True, back to H/4 into a channel slice of the 320-ch concat     (:108-122)
 // Activations are the conv kernel's format: zero-bordered channel-last grids stored as two bf16 planes
 // (hi = bf16(x), lo = bf16(x - hi)).  All four are HBM-bound element-wise kernels with 16-byte accesses.
+// Each body is a template on the plane format: F16 = the single-plane fp16 format of magnet_conv_mfma_f16p (the `_f16` entry points:
+// ONE fp16 plane where the default has a (hi, lo) pair, saturating round-to-nearest-even on store); the arithmetic is the same fp32.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "conv_common.hpp"
 
 namespace magnet {
 
@@ -42,13 +45,32 @@ __device__ __forceinline__ void fk_join8(const uint4 hi, const uint4 lo, float* 
     }
 }
 
+// 8 channels at element e of an activation buffer in either plane format (F16: `lo` is not touched)
+template <bool F16>
+__device__ __forceinline__ void fk_store8(uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, const size_t e, const float* v) {
+    if constexpr (F16) {
+        *reinterpret_cast<uint4*>(hi + e) = f16x8_pack_sat(v);
+    } else {
+        uint4 h, l;
+        fk_split8(v, h, l);
+        *reinterpret_cast<uint4*>(hi + e) = h;
+        *reinterpret_cast<uint4*>(lo + e) = l;
+    }
+}
+template <bool F16>
+__device__ __forceinline__ void fk_load8(const uint16_t* __restrict__ hi, const uint16_t* __restrict__ lo, const size_t e, float* v) {
+    if constexpr (F16) f16x8_unpack(*reinterpret_cast<const uint4*>(hi + e), v);
+    else fk_join8(*reinterpret_cast<const uint4*>(hi + e), *reinterpret_cast<const uint4*>(lo + e), v);
+}
+
 }  // namespace
 
 // ---- stem: out[n, y, x, co] = relu(b[co] + sum_{ci,dy,dx} W[co][ci][dy][dx] * img[n, ci, 2y+dy-1, 2x+dx-1]) ----
 // one thread per output pixel, 32 accumulators; the 864 weights are read with wave-uniform addresses (scalar loads)
-__global__ __launch_bounds__(256) void fnet_stem_kernel(const float* __restrict__ img, const float* __restrict__ wgt,
-                                                        const float* __restrict__ bias, uint16_t* __restrict__ out_hi,
-                                                        uint16_t* __restrict__ out_lo, int N, int H, int W, int H2, int W2) {
+template <bool F16>
+__device__ __forceinline__ void fnet_stem_body(const float* img, const float* wgt,
+                                               const float* bias, uint16_t* out_hi,
+                                               uint16_t* out_lo, int N, int H, int W, int H2, int W2) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)N * H2 * W2) return;
     const int x = (int)(idx % W2), y = (int)((idx / W2) % H2), n = (int)(idx / ((long long)W2 * H2));
@@ -76,17 +98,25 @@ __global__ __launch_bounds__(256) void fnet_stem_kernel(const float* __restrict_
             acc += bias[co];
             v[i] = acc < 0.f ? 0.f : acc;
         }
-        uint4 hi, lo;
-        fk_split8(v, hi, lo);
-        *reinterpret_cast<uint4*>(out_hi + row * 32 + c8 * 8) = hi;
-        *reinterpret_cast<uint4*>(out_lo + row * 32 + c8 * 8) = lo;
+        fk_store8<F16>(out_hi, out_lo, row * 32 + c8 * 8, v);
     }
+}
+__global__ __launch_bounds__(256) void fnet_stem_kernel(const float* __restrict__ img, const float* __restrict__ wgt,
+                                                        const float* __restrict__ bias, uint16_t* __restrict__ out_hi,
+                                                        uint16_t* __restrict__ out_lo, int N, int H, int W, int H2, int W2) {
+    fnet_stem_body<false>(img, wgt, bias, out_hi, out_lo, N, H, W, H2, W2);
+}
+__global__ __launch_bounds__(256) void fnet_stem_f16_kernel(const float* __restrict__ img, const float* __restrict__ wgt,
+                                                            const float* __restrict__ bias, uint16_t* __restrict__ out, int N, int H, int W,
+                                                            int H2, int W2) {
+    fnet_stem_body<true>(img, wgt, bias, out, nullptr, N, H, W, H2, W2);
 }
 
 // ---- space to depth: out[n, y, x, (py*2+px)*C + c] = in[n, 2y+py, 2x+px, c]; in border 1, out border `opad` ----
-__global__ __launch_bounds__(256) void space_to_depth_kernel(const uint16_t* __restrict__ in_hi, const uint16_t* __restrict__ in_lo,
-                                                             uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo,
-                                                             int N, int C, int H2, int W2, int H4, int W4, int opad) {
+template <bool F16>
+__device__ __forceinline__ void space_to_depth_body(const uint16_t* in_hi, const uint16_t* in_lo,
+                                                    uint16_t* out_hi, uint16_t* out_lo,
+                                                    int N, int C, int H2, int W2, int H4, int W4, int opad) {
     const int cpp = 4 * C / 8;                                  // 16-byte chunks per output pixel
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)N * H4 * W4 * cpp) return;
@@ -99,18 +129,28 @@ __global__ __launch_bounds__(256) void space_to_depth_kernel(const uint16_t* __r
     if (iy < H2 && ix < W2) {
         const size_t irow = ((size_t)n * (H2 + 2) + (iy + 1)) * (W2 + 2) + (ix + 1);
         hi = *reinterpret_cast<const uint4*>(in_hi + irow * C + c0);
-        lo = *reinterpret_cast<const uint4*>(in_lo + irow * C + c0);
+        if constexpr (!F16) lo = *reinterpret_cast<const uint4*>(in_lo + irow * C + c0);
     }
     const size_t orow = ((size_t)n * (H4 + 2 * opad) + (y + opad)) * (W4 + 2 * opad) + (x + opad);
     *reinterpret_cast<uint4*>(out_hi + orow * (4 * C) + cc * 8) = hi;
-    *reinterpret_cast<uint4*>(out_lo + orow * (4 * C) + cc * 8) = lo;
+    if constexpr (!F16) *reinterpret_cast<uint4*>(out_lo + orow * (4 * C) + cc * 8) = lo;
+}
+__global__ __launch_bounds__(256) void space_to_depth_kernel(const uint16_t* __restrict__ in_hi, const uint16_t* __restrict__ in_lo,
+                                                             uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo,
+                                                             int N, int C, int H2, int W2, int H4, int W4, int opad) {
+    space_to_depth_body<false>(in_hi, in_lo, out_hi, out_lo, N, C, H2, W2, H4, W4, opad);
+}
+__global__ __launch_bounds__(256) void space_to_depth_f16_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
+                                                                 int N, int C, int H2, int W2, int H4, int W4, int opad) {
+    space_to_depth_body<true>(in, nullptr, out, nullptr, N, C, H2, W2, H4, W4, opad);     // a pure 2-byte move
 }
 
 // ---- AvgPool2d(k, stride k), floor mode: in = channel slice (ld elements per row) of a grid with border `pad` ----
 // block = one pooled cell x 8 channel groups... : 256 threads = 16 channel chunks (C = 128) x 16 window slices
-__global__ __launch_bounds__(256) void avgpool_cl_kernel(const uint16_t* __restrict__ in_hi, const uint16_t* __restrict__ in_lo,
-                                                         int ld, int h, int w, int pad, int k, int ph, int pw, int C,
-                                                         uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo) {
+template <bool F16>
+__device__ __forceinline__ void avgpool_cl_body(const uint16_t* in_hi, const uint16_t* in_lo,
+                                                int ld, int h, int w, int pad, int k, int ph, int pw, int C,
+                                                uint16_t* out_hi, uint16_t* out_lo) {
     __shared__ float part[16][129];
     const int cell = blockIdx.x;
     const int px = cell % pw, py = (cell / pw) % ph, n = cell / (pw * ph);
@@ -122,8 +162,7 @@ __global__ __launch_bounds__(256) void avgpool_cl_kernel(const uint16_t* __restr
             const int yy = py * k + e / k, xx = px * k + e % k;
             const size_t row = ((size_t)n * Hp + (yy + pad)) * Wp + (xx + pad);
             float v[8];
-            fk_join8(*reinterpret_cast<const uint4*>(in_hi + row * ld + chunk * 8),
-                     *reinterpret_cast<const uint4*>(in_lo + row * ld + chunk * 8), v);
+            fk_load8<F16>(in_hi, in_lo, row * ld + chunk * 8, v);
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] += v[i];
         }
@@ -140,18 +179,25 @@ __global__ __launch_bounds__(256) void avgpool_cl_kernel(const uint16_t* __restr
             for (int sl = 0; sl < 16; ++sl) s += part[sl][threadIdx.x * 8 + i];
             v[i] = s * inv;
         }
-        uint4 hi, lo;
-        fk_split8(v, hi, lo);
-        *reinterpret_cast<uint4*>(out_hi + (size_t)cell * C + threadIdx.x * 8) = hi;
-        *reinterpret_cast<uint4*>(out_lo + (size_t)cell * C + threadIdx.x * 8) = lo;
+        fk_store8<F16>(out_hi, out_lo, (size_t)cell * C + threadIdx.x * 8, v);
     }
+}
+__global__ __launch_bounds__(256) void avgpool_cl_kernel(const uint16_t* __restrict__ in_hi, const uint16_t* __restrict__ in_lo,
+                                                         int ld, int h, int w, int pad, int k, int ph, int pw, int C,
+                                                         uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo) {
+    avgpool_cl_body<false>(in_hi, in_lo, ld, h, w, pad, k, ph, pw, C, out_hi, out_lo);
+}
+__global__ __launch_bounds__(256) void avgpool_cl_f16_kernel(const uint16_t* __restrict__ in, int ld, int h, int w, int pad, int k, int ph,
+                                                             int pw, int C, uint16_t* __restrict__ out) {
+    avgpool_cl_body<true>(in, nullptr, ld, h, w, pad, k, ph, pw, C, out, nullptr);
 }
 
 // ---- bilinear upsampling, align_corners=True (ATen upsample_bilinear2d): in fp32 (N*ph*pw, in_ld) -> split planes
 // ---- into channels [0, C) at `out_*` (pre-offset to the slice), row pitch out_ld, grid border `pad` ----
-__global__ __launch_bounds__(256) void upsample_bilinear_cl_kernel(const float* __restrict__ in, int in_ld, int ph, int pw, int C,
-                                                                   uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo,
-                                                                   int out_ld, int N, int h, int w, int pad) {
+template <bool F16>
+__device__ __forceinline__ void upsample_bilinear_cl_body(const float* in, int in_ld, int ph, int pw, int C,
+                                                          uint16_t* out_hi, uint16_t* out_lo,
+                                                          int out_ld, int N, int h, int w, int pad) {
     const int cpp = C / 8;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)N * h * w * cpp) return;
@@ -173,11 +219,17 @@ __global__ __launch_bounds__(256) void upsample_bilinear_cl_kernel(const float* 
         const float v10 = b[((size_t)y1 * pw + x0) * in_ld + i], v11 = b[((size_t)y1 * pw + x1) * in_ld + i];
         v[i] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
     }
-    uint4 hi, lo;
-    fk_split8(v, hi, lo);
     const size_t row = ((size_t)n * (h + 2 * pad) + (y + pad)) * (w + 2 * pad) + (x + pad);
-    *reinterpret_cast<uint4*>(out_hi + row * out_ld + cc * 8) = hi;
-    *reinterpret_cast<uint4*>(out_lo + row * out_ld + cc * 8) = lo;
+    fk_store8<F16>(out_hi, out_lo, row * out_ld + cc * 8, v);
+}
+__global__ __launch_bounds__(256) void upsample_bilinear_cl_kernel(const float* __restrict__ in, int in_ld, int ph, int pw, int C,
+                                                                   uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo,
+                                                                   int out_ld, int N, int h, int w, int pad) {
+    upsample_bilinear_cl_body<false>(in, in_ld, ph, pw, C, out_hi, out_lo, out_ld, N, h, w, pad);
+}
+__global__ __launch_bounds__(256) void upsample_bilinear_cl_f16_kernel(const float* __restrict__ in, int in_ld, int ph, int pw, int C,
+                                                                       uint16_t* __restrict__ out, int out_ld, int N, int h, int w, int pad) {
+    upsample_bilinear_cl_body<true>(in, in_ld, ph, pw, C, out, nullptr, out_ld, N, h, w, pad);
 }
 
 hipError_t launch_fnet_stem(const float* img, const float* wgt, const float* bias, uint16_t* out_hi, uint16_t* out_lo,
@@ -210,6 +262,35 @@ hipError_t launch_upsample_bilinear_cl(const float* in, int in_ld, int ph, int p
     const long long n = (long long)N * h * w * (C / 8);
     hipLaunchKernelGGL(upsample_bilinear_cl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, in_ld, ph, pw, C, out_hi,
                        out_lo, out_ld, N, h, w, pad);
+    return hipGetLastError();
+}
+
+// ---- the same four on the single-plane fp16 format ----
+hipError_t launch_fnet_stem_f16(const float* img, const float* wgt, const float* bias, uint16_t* out, int N, int H, int W, hipStream_t s) {
+    const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1;
+    const long long n = (long long)N * H2 * W2;
+    hipLaunchKernelGGL(fnet_stem_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, wgt, bias, out, N, H, W, H2, W2);
+    return hipGetLastError();
+}
+
+hipError_t launch_space_to_depth_f16(const uint16_t* in, uint16_t* out, int N, int C, int H2, int W2, int opad, hipStream_t s) {
+    const int H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
+    const long long n = (long long)N * H4 * W4 * (4 * C / 8);
+    hipLaunchKernelGGL(space_to_depth_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, N, C, H2, W2, H4, W4, opad);
+    return hipGetLastError();
+}
+
+hipError_t launch_avgpool_cl_f16(const uint16_t* in, int ld, int N, int h, int w, int pad, int k, int C, uint16_t* out, hipStream_t s) {
+    const int ph = h / k, pw = w / k;
+    hipLaunchKernelGGL(avgpool_cl_f16_kernel, dim3((unsigned)(N * ph * pw)), dim3(256), 0, s, in, ld, h, w, pad, k, ph, pw, C, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_upsample_bilinear_cl_f16(const float* in, int in_ld, int ph, int pw, int C, uint16_t* out, int out_ld, int N, int h, int w,
+                                           int pad, hipStream_t s) {
+    const long long n = (long long)N * h * w * (C / 8);
+    hipLaunchKernelGGL(upsample_bilinear_cl_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, in_ld, ph, pw, C, out, out_ld,
+                       N, h, w, pad);
     return hipGetLastError();
 }
 

@@ -13,6 +13,9 @@ Two things live here:
   writes); the last 1x1 layer writes the features **directly in the matcher's layouts** (reference features
   (B,h,w,F), source features (V*B,h+2,w+2,F) zero-bordered, fp32 or bf16) — the NCHW fp32 feature tensor of the
   reference and the pack pass over it never exist.
+  `FNetMFMA(psm, precision="fp16")` is the same chain on the single-plane fp16 format: every activation buffer is ONE fp16 plane,
+  every convolution issues one fp16 matrix instruction per product (`magnet_conv_mfma_f16p`).  A reduced-precision mode the caller
+  opts into; activations beyond +-65504 are clamped (include/magnet_hip.h).
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import lib
-from .planes import PackCache, fold_bn, pack_s2d, pack_taps, planes, timed
+from .planes import PackCache, fold_bn, pack_s2d, pack_s2d_f16, pack_taps, pack_taps_f16, plane_f16, planes, timed
 
 _pack_taps = pack_taps                                     # the name this packer had while it lived here; callers may still import it
 
@@ -48,6 +51,11 @@ def convs(psm):
         yield name, *getattr(psm, name)[1], False
     yield "lastconv.0", *psm.lastconv[0], False
     yield "lastconv.2", psm.lastconv[2], None, False
+
+
+def _cols(buf, a, b):
+    """Channels [a, b) of an activation buffer: a (hi, lo) pair of planes, or (plane, None) on the single-plane fp16 format."""
+    return tuple(None if t is None else t[:, a:b] for t in buf)
 
 
 def _conv_bn(cin, cout, k, stride=1, dilation=1):
@@ -131,7 +139,15 @@ class FNetMFMA:
     split_min_images = 8
     split_parts = 2
 
-    def __init__(self, psm: nn.Module):
+    PRECISIONS = ("bf16x3", "fp16")
+
+    def __init__(self, psm: nn.Module, precision: str = "bf16x3"):
+        """precision: 'bf16x3' (default: split-bf16 planes, three matrix instructions per product, fp32-grade) or 'fp16' (one fp16
+        plane per buffer, one matrix instruction per product; reduced precision, |activation| <= 65504 or clamped)."""
+        if precision not in self.PRECISIONS:
+            raise lib.MagnetError(f"FNetMFMA: precision must be 'bf16x3' or 'fp16', got {precision!r}")
+        self.precision = precision
+        self._f16 = "plane" if precision == "fp16" else False       # lib.conv_mfma's route
         self.psm = psm
         self._packed = None
         self._cache = PackCache(lambda: list(psm.parameters()) + list(psm.buffers()))
@@ -141,7 +157,7 @@ class FNetMFMA:
 
     # ---- weights ---------------------------------------------------------------------------------------------
     def packed(self, device):
-        self._packed = self._cache.get(device, lambda: self._pack(device))
+        self._packed = self._cache.get(device, lambda: self._pack(device), self.precision)   # one pack per precision
         return self._packed
 
     @torch.no_grad()
@@ -155,16 +171,18 @@ class FNetMFMA:
             w, b = w.to(device), b.to(device).contiguous()
             if name == "firstconv.0":
                 P["stem"] = (w.reshape(32, 27).contiguous(), b)
+            elif self._f16:                                        # folded in fp64, cast to fp32 above, ONE rounding to fp16 here
+                P[name] = ((pack_s2d_f16 if s2d else pack_taps_f16)(w), None, b, w.shape[0])
             else:
                 P[name] = (*(pack_s2d if s2d else pack_taps)(w), b, w.shape[0])
         self.feature_dim = P["lastconv.2"][3]
-        if self.feature_dim not in (16, 32, 64, 128):
-            raise lib.MagnetError(f"FNetMFMA: feature_dim {self.feature_dim} unsupported (16, 32, 64, 128)")
+        if self.feature_dim not in ((32, 64, 128) if self._f16 else (16, 32, 64, 128)):
+            raise lib.MagnetError(f"FNetMFMA: feature_dim {self.feature_dim} unsupported (16, 32, 64, 128; precision='fp16': 32, 64, 128)")
         return P
 
     # ---- activations -----------------------------------------------------------------------------------------
     def _buffers(self, dev, N, H, W, slot=0, sig=None):
-        sig = sig if sig is not None else (str(dev), N, H, W)
+        sig = sig if sig is not None else (str(dev), N, H, W, self.precision)
         if self._bufs_sig != sig:                                   # one batch shape at a time: the buffers are large
             self._bufs.clear()
             self._bufs_sig = sig
@@ -177,13 +195,14 @@ class FNetMFMA:
         if H4 < 64 or W4 < 64:
             raise lib.MagnetError(f"FNetMFMA: input {H}x{W} too small for the 64x64 pooling branch (needs H/4, W/4 >= 64)")
         rows_a, rows_b = N * (H2 + 2) * (W2 + 2), N * (H4 + 4) * (W4 + 4)
+        alloc = (lambda r, c: (plane_f16(r, c, dev, zero=True), None)) if self._f16 else (lambda r, c: planes(r, c, dev, zero=True))
         b = {"dims": (H2, W2, H4, W4, rows_a, rows_b),
-             "A": [planes(rows_a, 32, dev, zero=True) for _ in range(3)],
-             "S": planes(rows_b, 128, dev, zero=True),
-             "B": [planes(rows_b, 64, dev, zero=True) for _ in range(3)],
-             "C": [planes(rows_b, 128, dev, zero=True) for _ in range(3)],
-             "cat": planes(rows_b, 320, dev, zero=True),
-             "pool": {k: (planes(N * (H4 // k) * (W4 // k), 128, dev, zero=True),
+             "A": [alloc(rows_a, 32) for _ in range(3)],
+             "S": alloc(rows_b, 128),
+             "B": [alloc(rows_b, 64) for _ in range(3)],
+             "C": [alloc(rows_b, 128) for _ in range(3)],
+             "cat": alloc(rows_b, 320),
+             "pool": {k: (alloc(N * (H4 // k) * (W4 // k), 128),
                           torch.empty((N * (H4 // k) * (W4 // k), 32), dtype=torch.float32, device=dev)) for _, k in _SPP}}
         self._bufs[key] = b
         return b
@@ -193,7 +212,29 @@ class FNetMFMA:
         with timed(FNetMFMA.event_sink, 2.0 * rows * cin * taps * cout):
             lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, relu, rows,
                           out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1],
-                          out_ld=out_ld, add=add, border=border, dil=dil, **kw)
+                          out_ld=out_ld, add=add, border=border, dil=dil, f16=self._f16, **kw)
+
+    # the four non-GEMM layers on the runner's plane format (buffers are (hi, lo) pairs, or (plane, None) in fp16 mode)
+    def _stem(self, img, w, b, dst):
+        lib.fnet_stem_f16(img, w, b, dst[0]) if self._f16 else lib.fnet_stem(img, w, b, dst[0], dst[1])
+
+    def _space_to_depth(self, src, dst, N, C, H2, W2, opad):
+        if self._f16:
+            lib.space_to_depth_f16(src[0], dst[0], N, C, H2, W2, opad)
+        else:
+            lib.space_to_depth(src[0], src[1], dst[0], dst[1], N, C, H2, W2, opad)
+
+    def _avgpool(self, src, ld, N, h, w, pad, k, C, dst):
+        if self._f16:
+            lib.avgpool_cl_f16(src[0], ld, N, h, w, pad, k, C, dst[0])
+        else:
+            lib.avgpool_cl(src[0], src[1], ld, N, h, w, pad, k, C, dst[0], dst[1])
+
+    def _upsample(self, q, in_ld, ph, pw, C, dst, out_ld, N, h, w, pad):
+        if self._f16:
+            lib.upsample_bilinear_cl_f16(q, in_ld, ph, pw, C, dst[0], out_ld, N, h, w, pad)
+        else:
+            lib.upsample_bilinear_cl(q, in_ld, ph, pw, C, dst[0], dst[1], out_ld, N, h, w, pad)
 
     @torch.no_grad()
     def run(self, img: torch.Tensor, n_ref: int | None = None, feat_dtype="fp32"):
@@ -212,7 +253,7 @@ class FNetMFMA:
         self.packed(dev)
         H4, W4 = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
         Fd = self.feature_dim
-        sig = (str(dev), N, H, W)
+        sig = (str(dev), N, H, W, self.precision)
         if self._bufs_sig != sig:
             self._bufs.clear()
             self._bufs_sig = sig
@@ -275,7 +316,7 @@ class FNetMFMA:
         ba, bb = (H2 + 2, 1), (H4 + 4, 2)
 
         # ---- H/2 stage: firstconv + layer1 (32 channels, border 1) ----
-        lib.fnet_stem(img, P["stem"][0], P["stem"][1], A[0][0], A[0][1])                          # F_psmnet.py:40
+        self._stem(img, P["stem"][0], P["stem"][1], A[0])                                        # F_psmnet.py:40
         self._conv("firstconv.2", A[0], 32, 32, 9, wpa, rows_a, True, dst=A[1], border=ba)
         self._conv("firstconv.4", A[1], 32, 32, 9, wpa, rows_a, True, dst=A[0], border=ba)
         x = 0
@@ -285,13 +326,13 @@ class FNetMFMA:
             self._conv(f"layer1.{i}.conv2", A[t], 32, 32, 9, wpa, rows_a, False, dst=A[o], add=(A[x][0], A[x][1], 32), border=ba)
             x = o
         # ---- H/4 stage (border 2: layer4 is dilated) ----
-        lib.space_to_depth(A[x][0], A[x][1], S[0], S[1], N, 32, H2, W2, 2)
+        self._space_to_depth(A[x], S, N, 32, H2, W2, 2)
         self._conv("layer2.0.conv1", S, 128, 128, 4, wpb, rows_b, True, dst=Bb[0], border=bb)    # 3x3 stride 2
         self._conv("layer2.0.downsample", S, 128, 32, 1, wpb, rows_b, False, dst=Bb[1], border=bb)   # 1x1 stride 2 = phase 0
         self._conv("layer2.0.conv2", Bb[0], 64, 64, 9, wpb, rows_b, False, dst=Bb[2], add=(Bb[1][0], Bb[1][1], 64), border=bb)
         cur, ld = Bb[2], 64
         x = 2
-        raw = (cat[0][:, 0:64], cat[1][:, 0:64])
+        raw = _cols(cat, 0, 64)
         for i in range(1, 16):
             t, o = (x + 1) % 3, (x + 2) % 3
             self._conv(f"layer2.{i}.conv1", cur, ld, 64, 9, wpb, rows_b, True, dst=Bb[t], border=bb)
@@ -299,7 +340,7 @@ class FNetMFMA:
             self._conv(f"layer2.{i}.conv2", Bb[t], 64, 64, 9, wpb, rows_b, False, dst=raw if last else Bb[o],
                        out_ld=320 if last else 0, add=(cur[0], cur[1], ld), border=bb)
             cur, ld, x = (raw, 320, o) if last else (Bb[o], 64, o)
-        skip = (cat[0][:, 64:192], cat[1][:, 64:192])
+        skip = _cols(cat, 64, 192)
         x = 0
         units = [("layer3", i, 0) for i in range(3)] + [("layer4", i, 2) for i in range(3)]
         for n_unit, (name, i, dil) in enumerate(units):
@@ -317,13 +358,13 @@ class FNetMFMA:
             cur, ld, x = (skip, 320, o) if last else (C[o], 128, o)
         # ---- SPP branches: pool -> 1x1 conv + BN + ReLU -> bilinear back to H/4, into their concat slices ----
         for slot, (name, k) in enumerate(_SPP):                     # branch1 -> channels 288:320 ... branch4 -> 192:224
-            (p_hi, p_lo), q = buf["pool"][k]
+            pooled, q = buf["pool"][k]
             ph, pw = H4 // k, W4 // k
-            lib.avgpool_cl(skip[0], skip[1], 320, N, H4, W4, 2, k, 128, p_hi, p_lo)
+            self._avgpool(skip, 320, N, H4, W4, 2, k, 128, pooled)
             hi, lo, bias, _ = P[name]
-            lib.conv_mfma(p_hi, p_lo, 128, 128, hi, lo, bias, 1, 1, True, N * ph * pw, out_f32=q)
+            lib.conv_mfma(pooled[0], pooled[1], 128, 128, hi, lo, bias, 1, 1, True, N * ph * pw, out_f32=q, f16=self._f16)
             off = 288 - 32 * slot
-            lib.upsample_bilinear_cl(q, 32, ph, pw, 32, cat[0][:, off:off + 32], cat[1][:, off:off + 32], 320, N, H4, W4, 2)
+            self._upsample(q, 32, ph, pw, 32, _cols(cat, off, off + 32), 320, N, H4, W4, 2)
         # ---- lastconv ----
         self._conv("lastconv.0", cat, 320, 320, 9, wpb, rows_b, True, dst=C[0], border=bb)
         Fd = self.feature_dim
@@ -337,7 +378,7 @@ class FNetMFMA:
         if nr > 0:
             self._conv("lastconv.2", C[0], 128, 128, 1, wpb, nr * img_rows, False, border=bb, repad=1, out_ld=Fd, **okw(ref_cl[first:first + nr]))
         if N > nr:
-            tail = (C[0][0][nr * img_rows:], C[0][1][nr * img_rows:])
+            tail = tuple(None if t is None else t[nr * img_rows:] for t in C[0])
             s0 = first + nr - n_ref                                 # first source image of this part, counted among the source images
             self._conv("lastconv.2", tail, 128, 128, 1, wpb, (N - nr) * img_rows, False, border=bb, repad=2, out_ld=Fd,
                        **okw(src_pad[s0:s0 + (N - nr)]))

@@ -263,8 +263,13 @@ _PROTOS = {
     "magnet_fnet_stem_wgrad": (_C, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "magnet_conv_mfma_ex": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_conv_mfma_f16": (_C, [_S(MagnetConvExArgs), _P]),
+    "magnet_conv_mfma_f16p": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_pack_f16": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
     "magnet_planes_to_f16": (_C, [_P, _P, _I, _P, _I, _L, _I, _I, _P]),
+    "magnet_fnet_stem_f16": (_C, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "magnet_space_to_depth_f16": (_C, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "magnet_avgpool_cl_f16": (_C, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "magnet_upsample_bilinear_cl_f16": (_C, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "magnet_conv_row_tiles": (_L, [_I, _I, _I, _I, _S(_I)]),
     "magnet_dnet_gauss_head": (_C, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
@@ -329,6 +334,12 @@ def _dev(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
 def _bf16_ptr(t, name, contiguous=False):
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or (contiguous and not t.is_contiguous()):
         raise MagnetError(f"{name} must be a {'contiguous ' if contiguous else ''}bf16 GPU tensor")
+    return t.data_ptr()
+
+
+def _f16_ptr(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float16:
+        raise MagnetError(f"{name} must be an fp16 GPU tensor")
     return t.data_ptr()
 
 
@@ -600,8 +611,16 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     tiling = TILING_* flags (magnet_conv_mfma_ex; tests and A/B runs).  Returns the number of row tiles launched when the launch went
     through magnet_conv_mfma_ex, else None.
     f16 = True: the single-plane fp16 operand format (magnet_conv_mfma_f16): in_hi / w_hi are fp16 tensors, in_lo / w_lo must be None;
-    3x3 layers with cout_pad 128, a fused tail of 16 / 144 outputs or out_f32.  Always returns the row tile count."""
+    3x3 layers with cout_pad 128, a fused tail of 16 / 144 outputs or out_f32.  Always returns the row tile count.
+    f16 = "plane": the same operand format, plane to plane (magnet_conv_mfma_f16p, the F-Net's launches): `add` = (fp16 plane, None, ld),
+    the output is out_f16 (one fp16 plane, passed as out_hi with out_lo None), out_f32 or out_bf16; taps 1 / 4 / 9, cout_pad 32 / 64 /
+    128, dil, border, repad and channel slices as in the default format; no tail, addend, mx or leaky."""
     a = MagnetConvArgs()
+    plane = f16 == "plane"
+    if f16 not in (False, True, "plane"):
+        raise MagnetError(f"conv_mfma: f16 must be False, True or 'plane', got {f16!r}")
+    if plane and (tail is not None or addend is not None or out_lo is not None or (add is not None and add[1] is not None)):
+        raise MagnetError("conv_mfma (f16='plane'): one fp16 plane per buffer — out_lo and add[1] must be None; no tail, no addend")
     if f16:
         if in_lo is not None or w_lo is not None or mx is not None or leaky is not None:
             raise MagnetError("conv_mfma (f16): one fp16 plane per operand — in_lo, w_lo, mx and leaky must be None")
@@ -633,7 +652,9 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     if addend is not None:
         a.addend, a.addend_ld = _dev(addend, "addend", torch.float32).data_ptr(), int(addend.shape[1])
     a.dil, a.out_ld, a.repad = int(dil), int(out_ld), int(repad)
-    if add is not None:
+    if add is not None and plane:
+        a.add_hi, a.add_ld = _f16_ptr(add[0], "add (fp16 plane)"), int(add[2])
+    elif add is not None:
         a.add_hi, a.add_lo, a.add_ld = _bf16_ptr(add[0], "add_hi"), _bf16_ptr(add[1], "add_lo"), int(add[2])
     if border is not None:
         a.border_hp, a.border_pad = int(border[0]), int(border[1])
@@ -660,6 +681,8 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_f32 = 1, out_f32.data_ptr()
     elif out_bf16 is not None:
         a.out_mode, a.out_hi = 2, _bf16_ptr(out_bf16, "out_bf16")
+    elif plane:
+        a.out_mode, a.out_hi = 3, _f16_ptr(out_hi, "out_hi (fp16 plane)")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
     if leaky is None and tiling is None and not f16:
@@ -668,7 +691,7 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     tiles = ctypes.c_int64(0)
     x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
-    _launch("magnet_conv_mfma_f16" if f16 else "magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
+    _launch("magnet_conv_mfma_f16p" if plane else "magnet_conv_mfma_f16" if f16 else "magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
     return tiles.value
 
 
@@ -835,6 +858,29 @@ def avgpool_cl(in_hi, in_lo, ld, N, h, w, pad, k, C, out_hi, out_lo):
 def upsample_bilinear_cl(x, in_ld, ph, pw, C, out_hi, out_lo, out_ld, N, h, w, pad):
     _launch("magnet_upsample_bilinear_cl", x, _dev(x, "x", torch.float32).data_ptr(), in_ld, ph, pw, C, _bf16_ptr(out_hi, "out_hi"),
             _bf16_ptr(out_lo, "out_lo"), out_ld, N, h, w, pad)
+
+
+# the same four on the single-plane fp16 format (FNetMFMA(precision="fp16")): one fp16 plane wherever the above take a (hi, lo) pair
+def fnet_stem_f16(img, wgt, bias, out):
+    x = _dev(img, "img", torch.float32)
+    N, C, H, W = x.shape
+    if C != 3:
+        raise MagnetError(f"fnet_stem_f16: expected 3 input channels, got {C}")
+    _launch("magnet_fnet_stem_f16", x, x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(), _dev(bias, "bias", torch.float32).data_ptr(),
+            _f16_ptr(out, "out"), N, H, W)
+
+
+def space_to_depth_f16(x, out, N, C, H2, W2, opad):
+    _launch("magnet_space_to_depth_f16", x, _f16_ptr(x, "in"), _f16_ptr(out, "out"), N, C, H2, W2, opad)
+
+
+def avgpool_cl_f16(x, ld, N, h, w, pad, k, C, out):
+    _launch("magnet_avgpool_cl_f16", x, _f16_ptr(x, "in"), ld, N, h, w, pad, k, C, _f16_ptr(out, "out"))
+
+
+def upsample_bilinear_cl_f16(x, in_ld, ph, pw, C, out, out_ld, N, h, w, pad):
+    _launch("magnet_upsample_bilinear_cl_f16", x, _dev(x, "x", torch.float32).data_ptr(), in_ld, ph, pw, C, _f16_ptr(out, "out"), out_ld,
+            N, h, w, pad)
 
 
 # ---- training step of g_net / mask_head (include/magnet_hip.h: magnet_nll_loss_*, magnet_upsample_depth_backward,

@@ -122,11 +122,15 @@ class MAGNET(nn.Module):
     oracle forward at the C3 shape (default path: 2.2e-5), 9.4e-6 and 3.3e-6 against the reference's own forward on the G6 and G13
     fixtures (default: 2.9e-7, 1.4e-7) — measured with seeded weights, not trained ones (tests/test_gpu_magnet_f16.py).  Operands must
     lie within fp16's range (|x| <= 65504; larger magnitudes are clamped).  Needs conv_backend='mfma'; it changes inference only
-    (_refine_mfma): under autograd, with either train_backend, nothing changes."""
+    (_refine_mfma): under autograd, with either train_backend, nothing changes.
+    `fnet_precision`: 'bf16x3' (default) or 'fp16', the precision of the matrix-core F-Net runner (FNetMFMA(psm, precision=...)):
+    'fp16' keeps every F-Net activation as ONE fp16 plane and issues one matrix instruction per product.  Independent of
+    `conv_precision` (which stops at the backbone); needs conv_backend='mfma'; a reduced-precision inference mode the caller opts
+    into, measured in profiles/fnet_precision/NOTES.md.  Activations beyond +-65504 are clamped, not propagated as Inf."""
 
     def __init__(self, args, d_net: nn.Module | None = None, f_net: nn.Module | None = None,
                  feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch", dnet_backend: str = "torch",
-                 conv_precision: str = "bf16x3"):
+                 conv_precision: str = "bf16x3", fnet_precision: str = "bf16x3"):
         super().__init__()
         self.args = args
         if d_net is None or f_net is None:
@@ -177,6 +181,11 @@ class MAGNET(nn.Module):
         if conv_precision == "fp16" and conv_backend != "mfma":
             raise lib.MagnetError("conv_precision='fp16' is a mode of the matrix-core convolution path: it needs conv_backend='mfma'")
         self.conv_precision = conv_precision
+        if fnet_precision not in ("bf16x3", "fp16"):
+            raise lib.MagnetError(f"fnet_precision must be 'bf16x3' or 'fp16', got {fnet_precision!r}")
+        if fnet_precision == "fp16" and conv_backend != "mfma":
+            raise lib.MagnetError("fnet_precision='fp16' is a mode of the matrix-core F-Net runner: it needs conv_backend='mfma'")
+        self.fnet_precision = fnet_precision
         if dnet_backend not in ("torch", "hip"):
             raise lib.MagnetError(f"dnet_backend must be 'torch' or 'hip', got {dnet_backend!r}")
         self.dnet_backend = dnet_backend
@@ -446,7 +455,7 @@ class MAGNET(nn.Module):
             from .fnet import FNetMFMA
             psm = getattr(self.f_net, "f_net", self.f_net)
             ok = all(hasattr(psm, a) for a in ("firstconv", "layer1", "layer2", "layer3", "layer4", "branch1", "lastconv"))
-            self._fnet = FNetMFMA(psm) if ok else False
+            self._fnet = FNetMFMA(psm, precision=self.fnet_precision) if ok else False
         return self._fnet or None
 
 

@@ -24,6 +24,11 @@ def planes(rows, c, dev, zero=False):
     return new((rows, c), dtype=torch.bfloat16, device=dev), new((rows, c), dtype=torch.bfloat16, device=dev)
 
 
+def plane_f16(rows, c, dev, zero=False):
+    """ONE fp16 plane (rows, c): an activation buffer of the single-plane fp16 format (FNetMFMA(precision="fp16"))."""
+    return (torch.zeros if zero else torch.empty)((rows, c), dtype=torch.float16, device=dev)
+
+
 def fold_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     """Conv2d (with or without bias) followed by eval-mode BatchNorm2d -> (weight, bias) in fp64: w * s, (b - mean) * s + beta,
     s = gamma / sqrt(var + eps)."""
@@ -73,6 +78,11 @@ def s2d_matrix(w: torch.Tensor):
 
 def pack_s2d(w: torch.Tensor):
     return split_bf16(s2d_matrix(w))
+
+
+def pack_s2d_f16(w: torch.Tensor):
+    """pack_s2d on the single-plane fp16 format: ONE fp16 plane (4, cout, 4*C), each weight rounded once (to_f16_sat)."""
+    return to_f16_sat(s2d_matrix(w)).contiguous()
 
 
 class PackCache:

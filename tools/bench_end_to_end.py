@@ -1,7 +1,8 @@
 """End-to-end reference frames/s WITH the F-Net in the timed step (C2 shapes: 480x640 images, V = 4, D = 64, I = 1):
 images -> F-Net on the matrix cores (features land in the matcher's layouts) -> matcher -> G-Net -> update -> mask head ->
 upsampling.  The D-Net cannot be built offline (torch.hub), so its outputs ((mu,sigma) maps and x_d3) are resident
-synthetic tensors, exactly as in bench.py.  One JSON line; `--torch-fnet` runs the F-Net as the torch module (MIOpen)."""
+synthetic tensors, exactly as in bench.py.  One JSON line; `--torch-fnet` runs the F-Net as the torch module (MIOpen);
+`--fnet-precision` / `--conv-precision` are MAGNET's arguments of the same name."""
 import argparse
 import json
 import os
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--torch-fnet", action="store_true")
+    ap.add_argument("--fnet-precision", choices=("bf16x3", "fp16"), default="bf16x3")
+    ap.add_argument("--conv-precision", choices=("bf16x3", "fp16"), default="bf16x3")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     wl = synth.WORKLOADS["C2"]
@@ -46,7 +49,8 @@ def main():
     N = (1 + V) * B
     gmms = torch.cat([uni(*cam["mu"], N, 1, h, w), uni(*cam["sigma"], N, 1, h, w)], dim=1)
     x_d3 = torch.randn(N, 256, h, w, generator=g, device=dev) * 0.5
-    model = MAGNET(Args(), d_net=ResidentDNet(gmms, x_d3), f_net=fnet.FNET(Args()), feat_dtype="bf16").to(dev).eval()
+    model = MAGNET(Args(), d_net=ResidentDNet(gmms, x_d3), f_net=fnet.FNET(Args()), feat_dtype="bf16",
+                   fnet_precision=a.fnet_precision, conv_precision=a.conv_precision).to(dev).eval()
     model.fnet_mfma = not a.torch_fnet
     ref_img = torch.randn(B, 3, 4 * h, 4 * w, generator=g, device=dev)
     nb_img = torch.randn(V * B, 3, 4 * h, 4 * w, generator=g, device=dev)
@@ -65,7 +69,8 @@ def main():
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / a.steps
     print(json.dumps({"workload": "C2 + F-Net: 480x640 images, V=4, D=64, I=1, bf16 features; D-Net outputs resident",
                       "frames_per_step": B, "ms_per_step": dt * 1e3, "ref_frames_per_s": B / dt,
-                      "fnet": "torch (MIOpen fp32) + pack" if a.torch_fnet else "matrix-core path (magnet_amd/fnet.py)"}))
+                      "fnet": "torch (MIOpen fp32) + pack" if a.torch_fnet else "matrix-core path (magnet_amd/fnet.py)",
+                      "fnet_precision": a.fnet_precision, "conv_precision": a.conv_precision}))
 
 
 if __name__ == "__main__":
