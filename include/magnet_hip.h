@@ -647,6 +647,25 @@ MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs *args, void *stream);
  * are fp32 arithmetic as in magnet_conv_mfma. */
 MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs *args, void *stream);
 
+/* Split-K form of the plain bf16x3 layer, for launches with too few row tiles to fill the chip (the D-Net decoder at one to a few
+ * images): split s of split_k runs the K loop over the input-channel chunks [floor(s C / split_k), floor((s + 1) C / split_k)) of the
+ * C = cin / 32 chunks, all taps, and stores its raw fp32 accumulators to work[s][row][cout_pad] (rows < base.rows); a second launch on
+ * the same stream forms x = (((p_0 + p_1) + p_2) + ...) + bias in fp32, in ascending s, and applies magnet_conv_mfma_ex's epilogue:
+ * ReLU / MAGNET_ACT_LEAKY_RELU, zeros at border positions, repad, out_ld channel slices, out_mode 0 (split-bf16 planes) or 1 (fp32).
+ * No counters or atomics; deterministic.  A partial equals, to the bit, what magnet_conv_mfma writes to out_f32 for that channel range
+ * alone (channel-offset input view, weights packed for the range, zero bias, no activation), so the result differs from the unsplit
+ * launch by the order of split_k - 1 fp32 additions only.
+ * Serves: 2 <= split_k <= MAGNET_SPLITK_MAX; taps 1 or 9 (dil as in magnet_conv_mfma); cout_pad a multiple of 128; every split at least
+ * MAGNET_SPLITK_MIN_CHUNKS chunks ((cin / 32) / split_k >= MAGNET_SPLITK_MIN_CHUNKS; the K loop's ring itself runs from one chunk on —
+ * two keep its prefetch in use); out_mode 0 or 1; tiling 0 or MAGNET_TILING_FLAT (128-row tiles); tiles_out works.  A fused tail,
+ * addend, residual input, the e4m3 format, the Gaussian update / upsampling, MAGNET_TILING_BM64 / BM256 and any other out_mode are
+ * refused with MAGNET_E_DIM; `work` NULL: MAGNET_E_NULL, not 16-byte aligned: MAGNET_E_ALIGN, work_bytes too small: MAGNET_E_DIM.  A
+ * refused call writes nothing.  The workspace query returns split_k * rows * cout_pad * 4, or -(MAGNET_E_*) for a form that is refused. */
+#define MAGNET_SPLITK_MAX        8
+#define MAGNET_SPLITK_MIN_CHUNKS 2
+MAGNET_API int64_t magnet_conv_mfma_splitk_workspace(const MagnetConvExArgs *args, int32_t split_k);
+MAGNET_API int magnet_conv_mfma_splitk(const MagnetConvExArgs *args, int32_t split_k, float *work, int64_t work_bytes, void *stream);
+
 /* fp32 NCHW (N, C, h, w) (image stride `in_img_stride` elements, 0 = C*h*w) -> channels [c_off, c_off + round_up(C, 8)) of the interior
  * of a zero-bordered (N, h+2, w+2, ctot) fp16 plane (the round-up lanes are written as zeros, as by magnet_pack_split).  ctot and c_off
  * multiples of 8.  The border rows and every other channel are not written.  Conversion: see the single-plane fp16 format above. */

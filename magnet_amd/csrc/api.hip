@@ -308,7 +308,9 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 // (magnet_conv_mfma_f16, which has checked what that format serves): no lo planes.  CONV_F16P: the same operands, plane to plane
 // (magnet_conv_mfma_f16p): the residual is ONE fp16 plane (add_lo NULL) and out_mode 3 (one fp16 plane at out_hi) exists
 enum { CONV_BF16X3 = 0, CONV_F16 = 1, CONV_F16P = 2 };
-static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream, int mode = CONV_BF16X3) {
+// split_k >= 2 (magnet_conv_mfma_splitk, which has checked what that form serves): the split-K launches with workspace `work`
+static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream, int mode = CONV_BF16X3,
+                         int split_k = 0, float* work = nullptr) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
     const bool f16 = mode != CONV_BF16X3;
     if (!a->in_hi || (!f16 && !a->in_lo) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
@@ -407,7 +409,8 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
-    hipError_t e = mode == CONV_F16P ? magnet::launch_conv_mfma_f16p(p, (hipStream_t)stream)
+    hipError_t e = split_k          ? magnet::launch_conv_mfma_splitk(p, split_k, work, (hipStream_t)stream)
+                 : mode == CONV_F16P ? magnet::launch_conv_mfma_f16p(p, (hipStream_t)stream)
                  : mode == CONV_F16  ? magnet::launch_conv_mfma_f16(p, (hipStream_t)stream) : magnet::launch_conv_mfma(p, (hipStream_t)stream);
     if (tiles_out) *tiles_out = tiles;
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv_mfma launch");
@@ -465,6 +468,47 @@ MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs* a, void* stream) {
     if (b.cout_pad != 32 && b.cout_pad != 64 && b.cout_pad != 128)
         return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: cout_pad=%d (32, 64 or 128)", b.cout_pad);
     return conv_mfma_run(&a->base, 0, 0.f, a->tiling, a->tiles_out, stream, CONV_F16P);
+}
+
+// What the split-K form serves (both entry points): 0, or the MAGNET_E_* code with the message set.  *bytes: the workspace size.
+static int conv_splitk_check(const MagnetConvExArgs* a, int32_t split_k, int64_t* bytes) {
+    if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_splitk: args is NULL");
+    const MagnetConvArgs& b = a->base;
+    if (split_k < 2 || split_k > MAGNET_SPLITK_MAX) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: split_k=%d (2 .. %d)", split_k, MAGNET_SPLITK_MAX);
+    if (b.tail_w_hi || b.tail_w_lo || b.addend || b.add_hi || b.add_lo || b.in_sc || b.w_sc || b.up_out || b.up_depth || b.gu_in || b.gu_out)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: the plain bf16x3 layer only (no fused tail, addend, residual input, e4m3 format, Gaussian update or upsampling)");
+    if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", a->tiling);
+    if (b.taps != 1 && b.taps != 9) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: taps=%d (1 or 9)", b.taps);
+    if (b.cout_pad <= 0 || b.cout_pad % 128 != 0) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: cout_pad=%d must be a multiple of 128", b.cout_pad);
+    if (b.out_mode != 0 && b.out_mode != 1) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: out_mode=%d (0: split-bf16 planes, 1: fp32)", b.out_mode);
+    if (b.rows <= 0 || b.cin <= 0 || (b.cin % 32) != 0) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: rows > 0 and cin %% 32 == 0 required (cin=%d)", b.cin);
+    if ((b.cin / 32) / split_k < MAGNET_SPLITK_MIN_CHUNKS)
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: cin=%d gives a split fewer than %d 32-channel chunks at split_k=%d", b.cin, MAGNET_SPLITK_MIN_CHUNKS, split_k);
+    if (b.rows >= ((int64_t)1 << 31) || b.rows * (b.cout_pad / 8) / 256 >= ((int64_t)1 << 31))
+        return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: rows=%lld too large for the reduce launch", (long long)b.rows);
+    *bytes = (int64_t)split_k * b.rows * b.cout_pad * 4;
+    return 0;
+}
+
+MAGNET_API int64_t magnet_conv_mfma_splitk_workspace(const MagnetConvExArgs* a, int32_t split_k) {
+    int64_t bytes = 0;
+    const int rc = conv_splitk_check(a, split_k, &bytes);
+    return rc ? -(int64_t)rc : bytes;
+}
+
+MAGNET_API int magnet_conv_mfma_splitk(const MagnetConvExArgs* a, int32_t split_k, float* work, int64_t work_bytes, void* stream) {
+    int64_t bytes = 0;
+    if (const int rc = conv_splitk_check(a, split_k, &bytes)) return rc;
+    if (!work) return fail(MAGNET_E_NULL, "magnet_conv_mfma_splitk: work is NULL");
+    if (!aligned16(work)) return fail(MAGNET_E_ALIGN, "magnet_conv_mfma_splitk: work must be 16-byte aligned");
+    if (work_bytes < bytes) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: work_bytes=%lld < %lld", (long long)work_bytes, (long long)bytes);
+    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: act=%d unknown", a->act);
+    if (a->act == MAGNET_ACT_LEAKY_RELU) {
+        if (a->base.relu) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: LeakyReLU excludes relu");
+        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
+            return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: act_slope must be finite");
+    }
+    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream, CONV_BF16X3, split_k, work);
 }
 
 MAGNET_API int magnet_pack_f16(const float* nchw, void* out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,

@@ -101,6 +101,8 @@ hipError_t launch_conv_mfma(const ConvParams&, hipStream_t);
 hipError_t launch_conv_mfma_f16(const ConvParams&, hipStream_t);       // single-plane fp16 operands: in_hi / w_hi fp16, in_lo / w_lo unused
 hipError_t launch_conv_mfma_f16p(const ConvParams&, hipStream_t);      // the same operands, plane to plane (the F-Net): add_hi is ONE fp16 residual
                                                                        // plane (add_lo unused), out_mode 3 = one fp16 plane at out_hi
+// split-K over S input-channel ranges: the partials into work (S x rows x cout_pad fp32), then the fixed-order reduce + epilogue launch
+hipError_t launch_conv_mfma_splitk(const ConvParams&, int S, float* work, hipStream_t);
 hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
 hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
                            hipStream_t s);

@@ -367,13 +367,21 @@ struct ConvLds {
 // F16P = "plane to plane" (magnet_conv_mfma_f16p, the F-Net): F16 operands, and in the plain epilogue the residual input is ONE fp16
 // plane (add_hi) and out_mode 3 writes ONE fp16 plane (out_hi).  Besides the two WIN == 2 loops it runs the windowless loop at the
 // bottom with one fp16 MFMA per fragment pair (taps 1 and 4), and the 4-wave WIN == 2 loop at BN = 32 (one weight piece per wave).
-template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool F16 = false, bool F16P = false>
-__device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsigned bid, const unsigned n_tiles, const unsigned by, const int tid) {
+// SPLITK = the split-K form (magnet_conv_mfma_splitk): workgroup sk_z of sk_n runs the K loop over the input-channel chunks
+// [floor(sk_z C / sk_n), floor((sk_z + 1) C / sk_n)) of the C = cin / 32 chunks, all taps — the chunk range, the activation channel offset
+// and the weight offset change (the weight row pitch stays cin); the step order and the ring schedule are the plain loop's — and stores
+// its raw fp32 accumulator tile to sk_work[sk_z][row][cout_pad], rows < p.rows: no bias, activation or border logic (the reduce kernel's).
+// A partial therefore holds, to the bit, what the plain instance writes to out_f32 for that channel range alone with a zero bias.
+template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool F16 = false, bool F16P = false, bool SPLITK = false>
+__device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsigned bid, const unsigned n_tiles, const unsigned by, const int tid,
+                                               [[maybe_unused]] float* __restrict__ sk_work = nullptr, [[maybe_unused]] const unsigned sk_z = 0,
+                                               [[maybe_unused]] const unsigned sk_n = 1) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-descriptor builtins do not exist in the host pass (which only needs the stub)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the K loop's ring (ConvLds; declared here, not passed in: a pointer
                                                                             // parameter is a generic pointer, and its casts to LDS pointers get null checks)
     using L = ConvLds<NF, WN, CV_BM, SPB, NT, PP, WIN, F16>;
     static_assert(!F16P || (F16 && TAIL == 0 && !PP), "plane to plane: fp16 operands, plain epilogue, 4 waves");
+    static_assert(!SPLITK || (!F16 && TAIL == 0 && !PP && NT == 256 && (WIN == 2 || WIN == 0)), "split-K: the two 4-wave bf16x3 loops, no tail");
     constexpr int BN = L::BN, A_BYTES = L::A_BYTES, B_BYTES = L::B_BYTES;
     constexpr int RP = NT / 4;                      // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
     constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (1, 2 or 4)
@@ -405,7 +413,12 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
     // writes lane-linearly (wave-uniform base + lane*16), so the XOR swizzle is applied to the SOURCE: the lane
     // that fills physical slot ps of row r fetches logical K slot ps ^ ((r>>1)&3)  (cdna_hip_programming.md rule 21).
     constexpr int B_PT = (BN + RP - 1) / RP;                   // 16-byte vectors per thread per B plane
-    const int ksteps_per_tap = p.cin / CV_BK;
+    // split-K: this workgroup's chunks [sk_c0, sk_c0 + ksteps_per_tap) of the cin / 32
+    [[maybe_unused]] const int sk_c0 = SPLITK ? (int)((long long)sk_z * (p.cin / CV_BK) / sk_n) : 0;
+    const int ksteps_per_tap = [&] {
+        if constexpr (SPLITK) return (int)((long long)(sk_z + 1) * (p.cin / CV_BK) / sk_n) - sk_c0;
+        else return p.cin / CV_BK;
+    }();
     const int nsteps = p.taps * ksteps_per_tap;
     const int st_r = tid >> 2, st_q = tid & 3;
     const int st_k = (st_q ^ ((st_r >> 1) & 3)) * 8;          // logical K offset (elements) this lane fetches (cv_swz)
@@ -930,6 +943,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         const int aw = CV_BM + 2 * p.tap_sx;
         const int ngroups = 3 * ksteps_per_tap;               // (K chunk, ty) pairs, ty inner
         StepCounter gw, bs;                                   // next window (i = ty) / weight tile (i = tap) to fetch
+        if constexpr (SPLITK) gw.k0 = bs.k0 = sk_c0 * CV_BK;  // the range's first channel: offset into the activation rows and the weight rows
         auto dma_a = [&]() { stage_window(win_slot(0), a_step(gw.i, 0, gw.k0), aw); gw.advance(3); };
         const int b_v32 = ((n0 + (wv >> 1) * 16 + (lane >> 2)) * p.cin + st_k) * 2;       // BN = 32: this wave's 16 weight rows
         auto dma_b = [&](int slot) {
@@ -1005,6 +1019,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         // the 4-wave / 2-slot loop over (K chunk, tap) stages, no window: stage = A tile of tap (ty, tx) + its weight tile
         StepCounter pf;                                       // next stage to fetch: i = ty; with pf_tx, pf_tap = ty*tap_n + tx
         int pf_tx = 0, pf_tap = 0;
+        if constexpr (SPLITK) pf.k0 = sk_c0 * CV_BK;
         auto dma = [&](int buf) {
             stage_window(win_slot(buf), a_step(pf.i, pf_tx, pf.k0), CV_BM);
             stage_weights(wt_slot(buf), wt_slot(buf) + B_BYTES, (pf_tap * p.cout_pad * p.cin + pf.k0) * 2);
@@ -1073,6 +1088,33 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         tail_layer_cols<TAIL, true, CV_BM, NW>(p.tail_w_hi + 2 * 128 * 128, p.tail_w_lo + 2 * 128 * 128, p.tail_bias + 256, act_hi, act_lo,
                                                p.out_f32, p.tail_cout, row0, p.rows, lane, wv,
                                                (TAIL == 1 && p.gu_out) ? UpArgs{p.gu_in, p.gu_out, -1, p.up_h, p.up_w, p.up_B} : UpArgs{nullptr, nullptr, 0, 0, 0, 0});
+        return;
+    }
+
+    if constexpr (SPLITK) {
+        // ---- split-K: the raw accumulator tile -> sk_work[sk_z], through the plain epilogue's wave-private staging rows (16-byte stores
+        // of 8 consecutive channels); rows < p.rows only, channels n0 .. n0 + BN - 1 < cout_pad (the grid's y extent) ----
+        constexpr int WCOLS = NFW * 16, SROW = WCOLS + 4;
+        float* stage = reinterpret_cast<float*>(smem) + wv * (16 * SROW);
+        float* const wz = sk_work + (size_t)sk_z * (size_t)p.rows * p.cout_pad;
+#pragma unroll
+        for (int m = 0; m < MF; ++m) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int n = 0; n < NFW; ++n)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    stage[((lane >> 4) * 4 + r) * SROW + n * 16 + (lane & 15)] = acc[m][n][r];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int it = lane; it < 16 * (WCOLS / 8); it += 64) {
+                const int r = it / (WCOLS / 8), c8 = (it % (WCOLS / 8)) * 8;
+                const long long row = row0 + wm * (MF * 16) + m * 16 + r;
+                if (row >= p.rows) continue;
+                float* o = wz + (size_t)row * p.cout_pad + n0 + wn * WCOLS + c8;
+                *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(stage + r * SROW + c8);
+                *reinterpret_cast<float4*>(o + 4) = *reinterpret_cast<const float4*>(stage + r * SROW + c8 + 4);
+            }
+        }
         return;
     }
 
@@ -1207,6 +1249,68 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_f16p_kernel(const ConvParams 
     conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN, true, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
 }
 
+// The split-K instances (magnet_conv_mfma_splitk): the 4-wave 128-row x 128-channel loops, WIN = 2 (3x3) and WIN = 0 (1x1); blockIdx.z =
+// the split.  Kernels of their own name; the partials go to `work`, nothing else is written
+template <int WIN>
+__global__ __launch_bounds__(256, 2) void conv_mfma_splitk_kernel(const ConvParams p, float* __restrict__ work) {
+    conv_mfma_tile<8, 2, 128, 1, 0, 256, false, WIN, false, false, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x, work, blockIdx.z, gridDim.z);
+}
+
+// out = epilogue(((p_0 + p_1) + p_2 ... ) + bias): the fixed-order fp32 sum of the S partials work[z][row][cout_pad], then what the plain
+// epilogue applies — ReLU / LeakyReLU, zeros at border positions, repad re-addressing, out_ld channel slices — as split-bf16 planes
+// (out_mode 0) or fp32 (out_mode 1).  One thread = 8 channels of one row: 16-byte loads and stores, no LDS.
+__global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParams p, const float* __restrict__ work, const int S) {
+    const int c8n = p.cout_pad / 8;
+    const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long row = it / c8n;
+    if (row >= p.rows) return;
+    const int ch = (int)(it - row * c8n) * 8;
+    long long orow = row;
+    bool interior = true;
+    if (p.img_rows) {
+        const long long img = row / p.img_rows;
+        const int rem = (int)(row - img * p.img_rows), y = rem / p.wp, x = rem - y * p.wp;
+        interior = (y >= p.pad) && (y < p.hp - p.pad) && (x >= p.pad) && (x < p.wp - p.pad);
+        if (p.repad) {
+            if (!interior) return;
+            const int q = p.repad - 1, hh = p.hp - 2 * p.pad, ww = p.wp - 2 * p.pad;
+            orow = (img * (hh + 2 * q) + (y - p.pad + q)) * (ww + 2 * q) + (x - p.pad + q);
+        }
+    }
+    const size_t plane = (size_t)p.rows * p.cout_pad;
+    const float* src = work + (size_t)row * p.cout_pad + ch;
+    float4 q0[8], q1[8];                                      // every partial's loads are issued before the first addition
+#pragma unroll
+    for (int z = 0; z < 8; ++z)
+        if (z < S) { q0[z] = *reinterpret_cast<const float4*>(src + z * plane); q1[z] = *reinterpret_cast<const float4*>(src + z * plane + 4); }
+    float v[8] = {q0[0].x, q0[0].y, q0[0].z, q0[0].w, q1[0].x, q1[0].y, q1[0].z, q1[0].w};
+#pragma unroll
+    for (int z = 1; z < 8; ++z)
+        if (z < S) {
+            v[0] += q0[z].x; v[1] += q0[z].y; v[2] += q0[z].z; v[3] += q0[z].w;
+            v[4] += q1[z].x; v[5] += q1[z].y; v[6] += q1[z].z; v[7] += q1[z].w;
+        }
+    const float4 b0 = *reinterpret_cast<const float4*>(p.bias + ch), b1 = *reinterpret_cast<const float4*>(p.bias + ch + 4);
+    const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float x = v[i] + bv[i];
+        v[i] = (x < 0.f) ? (p.relu ? 0.f : (p.leaky ? x * p.leaky_slope : x)) : x;
+        if (!interior) v[i] = 0.f;
+    }
+    const size_t e = (size_t)orow * p.out_ld + ch;
+    if (p.out_mode == 0) {
+        uint32_t h[4], l[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) split_bf16x2(v[2 * i], v[2 * i + 1], h[i], l[i]);
+        *reinterpret_cast<uint4*>(p.out_hi + e) = make_uint4(h[0], h[1], h[2], h[3]);
+        *reinterpret_cast<uint4*>(p.out_lo + e) = make_uint4(l[0], l[1], l[2], l[3]);
+    } else {
+        *reinterpret_cast<float4*>(p.out_f32 + e) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(p.out_f32 + e + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
+}
+
 template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
 static size_t conv_lds_bytes() { return ConvLds<NF, WN, BM, SPB, NT, PP, WIN, F16>::TOTAL; }
 
@@ -1307,6 +1411,34 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     if (p.cout_pad == 32)  return launch_conv_nf<2, 1, 128, 1>(p, s);
     if (p.cout_pad == 64)  return launch_conv_nf<4, 1, 128, 1>(p, s);
     return hipErrorInvalidValue;
+}
+
+// Split-K (magnet_conv_mfma_splitk; the API has checked the form): S partial launches in one grid (z = the split) into `work`
+// (S x rows x cout_pad fp32), then the reduce launch on the same stream.  No counters, no atomics: two ordinary launches.
+template <int WIN>
+static hipError_t launch_splitk_partials(const ConvParams& p, int S, float* work, hipStream_t s) {
+    const long long n_tiles = (p.rows + 127) / 128;
+    const size_t lds = conv_lds_bytes<8, 2, 128, 1, 256, false, WIN>();
+    void (*const kernel)(const ConvParams, float*) = &conv_mfma_splitk_kernel<WIN>;
+    static bool attr_set = false;
+    if (!attr_set && lds > 64 * 1024) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_tiles, (unsigned)(p.cout_pad / 128), (unsigned)S), dim3(256), lds, s, p, work);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_mfma_splitk(const ConvParams& p_in, int S, float* work, hipStream_t s) {
+    if (p_in.cout_pad % 128 != 0 || (p_in.tap_n != 3 && p_in.tap_n != 1) || S < 2 || S > 8 || !work) return hipErrorInvalidValue;
+    ConvParams p = p_in;
+    p.tiles_per_img = 0;
+    if (p.tiles_out) *p.tiles_out = (p.rows + 127) / 128;
+    const hipError_t e = p.tap_n == 3 ? launch_splitk_partials<2>(p, S, work, s) : launch_splitk_partials<0>(p, S, work, s);
+    if (e != hipSuccess) return e;
+    const long long items = p.rows * (p.cout_pad / 8);
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, work, S);
+    return hipGetLastError();
 }
 
 // The single-plane fp16 format (magnet_conv_mfma_f16): the launches MAGNET._refine_mfma makes and nothing else — the 3x3 layer with

@@ -19,6 +19,11 @@ Three things live here:
   (`DNET(dnet=True)`, what test_DNet.py evaluates): the same decoder pass, then the depth head and the mask head as two fused launches
   and magnet_dnet_upsample_gauss (learned convex upsampling x4 of the raw (mu, v), activation_G behind it) -> (N, 2, H, W)
   [mu, variance].  `DNET(..., backend="hip")` routes an eval-mode forward through it.
+  `DNetMFMA(decoder, split_k="auto")` (opt-in; default 0 = off) runs conv2 and up1.0 .. up3.1 as split-K launches
+  (magnet_conv_mfma_splitk) where a launch has too few tiles to fill the chip — one to a few images; `split_factor` is the rule.
+  Under "auto" the factor S of a launch depends on its tile count, so the bits of one image can differ between batch sizes — by the
+  order of S - 1 fp32 additions per output only; with a forced dict {layer: S} they do not.  SequenceRunner's bit-equality with
+  MAGNET.forward holds when both ran the same factors.
 """
 from __future__ import annotations
 
@@ -36,6 +41,44 @@ from .planes import PackCache, fold_bn, pack_taps, planes, round_up, timed
 # (block, skip feature index, skip channels, output channels) at downsample ratio 4 (D_dense_depth.py:130-135,176-180)
 _UP = (("up1", 8, 176, 1024), ("up2", 6, 64, 512), ("up3", 5, 40, 256))
 _SKIP_IN = 11                                              # x_block4: 2048 channels at 1/32 (the input of conv2)
+SPLIT_LAYERS = ("conv2", "up1.0", "up1.1", "up2.0", "up2.1", "up3.0", "up3.1")    # the launches DNetMFMA(split_k=...) covers
+# constants of the "auto" rule (split_factor), from the sweep in profiles/splitk/NOTES.md
+SPLIT_CUS = 256                                            # a launch with a workgroup per CU is not split; a split fills at most one per CU ...
+SPLIT_SLOTS = 512                                          # ... or, from half the CUs on, the resident slots (two 4-wave workgroups per CU)
+SPLIT_AUTO_MIN_CHUNKS = 4                                  # 32-channel chunks per split under "auto" (>= lib.SPLITK_MIN_CHUNKS): the
+                                                           # shortest split the sweep still saw pay (up2.1 at S = 4)
+
+
+def split_factor(row_tiles, n_tiles, cin_chunks):
+    """The "auto" split-K factor of a plain decoder launch of row_tiles x n_tiles workgroups (128 rows x 128 channels each) whose input has
+    cin_chunks 32-channel chunks.  1 (no split) when the launch already has a workgroup per CU (SPLIT_CUS).  Below that, the largest S
+    that keeps ONE workgroup per CU (workgroups x S <= SPLIT_CUS) — measured faster than filling the second resident slot of a CU:
+    88 workgroups at K = 20 160 take 0.40 ms unsplit, 0.23 ms at S = 2 (176 workgroups) and 0.27 ms at S = 5 (440) — and S = 2 where
+    even that overfills the CUs (more than SPLIT_CUS / 2 workgroups; the split stays within SPLIT_SLOTS).  Never more than
+    lib.SPLITK_MAX, never fewer than SPLIT_AUTO_MIN_CHUNKS chunks per split.  Pure host arithmetic; non-increasing in the workgroup
+    count."""
+    wg = int(row_tiles) * int(n_tiles)
+    if wg <= 0 or cin_chunks <= 0:
+        raise lib.MagnetError(f"split_factor: row_tiles={row_tiles} n_tiles={n_tiles} cin_chunks={cin_chunks} must be positive")
+    if wg >= SPLIT_CUS:
+        return 1
+    s = SPLIT_CUS // wg
+    if s < 2:
+        s = min(2, SPLIT_SLOTS // wg)
+    s = min(s, lib.SPLITK_MAX, int(cin_chunks) // max(SPLIT_AUTO_MIN_CHUNKS, lib.SPLITK_MIN_CHUNKS))
+    return s if s >= 2 else 1
+
+
+def check_split_k(split_k, who="DNetMFMA"):
+    """0 (off), "auto" or {layer name: S} with S in 1 .. lib.SPLITK_MAX (1 = that layer unsplit); MagnetError otherwise."""
+    if isinstance(split_k, dict):
+        for k, v in split_k.items():
+            if k not in SPLIT_LAYERS or isinstance(v, bool) or not isinstance(v, int) or not (1 <= v <= lib.SPLITK_MAX):
+                raise lib.MagnetError(f"{who}: split_k[{k!r}] = {v!r}: layers are {SPLIT_LAYERS}, factors 1 .. {lib.SPLITK_MAX}")
+        return dict(split_k)
+    if split_k == "auto" or (split_k == 0 and isinstance(split_k, int) and not isinstance(split_k, bool)):
+        return split_k
+    raise lib.MagnetError(f"{who}: split_k must be 0 (off), 'auto' or a dict {{layer: S}}, got {split_k!r}")
 
 
 class UpSampleBN(nn.Module):
@@ -132,9 +175,10 @@ class DNET(nn.Module):
     for losses.DnetLoss's fused tail.  `encoder`: any module returning the reference's feature list
     (EfficientNet-B5's, or magnet_amd.standin.StandinEncoder).
     backend: 'torch' (default) runs the modules as they are; 'hip' runs the decoder, the heads and the tail of an eval-mode forward on
-    DNetMFMA (the caller's encoder stays a torch module); in .train() the torch forward runs, as MAGNET does for its D-Net."""
+    DNetMFMA (the caller's encoder stays a torch module); in .train() the torch forward runs, as MAGNET does for its D-Net.
+    split_k: DNetMFMA's split-K mode (0 = off, "auto", or {layer: S}); needs backend='hip'."""
 
-    def __init__(self, args, encoder: nn.Module, dnet: bool = False, backend: str = "torch"):
+    def __init__(self, args, encoder: nn.Module, dnet: bool = False, backend: str = "torch", split_k=0):
         super().__init__()
         self.args = args
         if getattr(args, "output_type", "G") != "G":
@@ -147,9 +191,12 @@ class DNET(nn.Module):
         self.backend = backend
         self.d_net = DenseDepth(encoder, getattr(args, "output_dim", 2), args.downsample_ratio, dnet)
         self._runner = None
+        split_k = check_split_k(split_k, "DNET")
+        if split_k != 0 and backend != "hip":
+            raise lib.MagnetError("DNET: split_k is a mode of the HIP decoder path: it needs backend='hip'")
         if backend == "hip":
             check_decoder(self.d_net.decoder, standalone=dnet)
-            self._runner = DNetMFMA(self.d_net.decoder)
+            self._runner = DNetMFMA(self.d_net.decoder, split_k=split_k)
 
     def forward(self, img, upsample=True):
         if not upsample:
@@ -236,9 +283,11 @@ class DNetMFMA:
     # every convolution launch appends (start_event, end_event, flops) when set to a list (tools/bench_dnet.py)
     event_sink = None
 
-    def __init__(self, decoder: nn.Module):
+    def __init__(self, decoder: nn.Module, split_k=0):
         check_decoder(decoder)
         self.decoder = decoder
+        self.split_k = check_split_k(split_k)                       # 0 = off (default), "auto" = split_factor per launch, {layer: S} = forced
+        self.factors_used = []                                      # (layer, rows, S) of every covered launch of the last run
         self.slope = float(decoder.up1._net[2].negative_slope)
         dh = decoder.depth_head
         # the depth head (3x3 256->128 ReLU, 1x1 128->128 ReLU, 1x1 128->2) on the stack runner's fused epilogue, which has two hidden
@@ -295,10 +344,25 @@ class DNetMFMA:
                 ok = t.is_contiguous() and ld == cout and t.numel() >= n_out * ld
             if not ok:
                 raise lib.MagnetError(f"DNetMFMA {name}: output {tuple(t.shape)} does not hold {n_out} rows of {cout} at pitch {ld}")
+        S = 1
+        if isinstance(self.split_k, dict):
+            S = self.split_k.get(name, 1)
+        elif self.split_k == "auto":
+            S = split_factor((rows + 127) // 128, cout // 128, cin // 32)
+        self.factors_used.append((name, rows, S))
+        work = None
+        if S > 1:
+            # one workspace for all launches (stream-ordered: a layer's reduce has read it before the next layer's partials are written),
+            # kept with the per-shape buffers and grown on demand
+            need = lib.conv_mfma_splitk_workspace(rows, cin, cout, taps, S) // 4
+            work = self._bufs.get("splitk.work")
+            if work is None or work.numel() < need:
+                work = self._bufs["splitk.work"] = torch.empty(need, dtype=torch.float32, device=src[0].device)
         with timed(DNetMFMA.event_sink, 2.0 * rows * cin * taps * cout):
             lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, False, rows,
                           out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1], out_f32=out_f32, out_ld=out_ld,
-                          border=border, repad=repad, leaky=None if name == "conv2" else self.slope)
+                          border=border, repad=repad, leaky=None if name == "conv2" else self.slope,
+                          split_k=S if S > 1 else None, work=work)
 
     def _buffers(self, dev, N, dims):
         sig = (str(dev), N, dims)
@@ -345,6 +409,7 @@ class DNetMFMA:
     def _decode(self, xs, N, dims, dev):
         """conv2 and up1..up3 up to the input planes of up3's second convolution (buffers()["up3.mid"]); returns the buffer dict."""
         (h32, w32) = dims[0]
+        self.factors_used = []
         self.packed(dev)
         b = self._buffers(dev, N, dims)
 

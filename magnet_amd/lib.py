@@ -27,6 +27,7 @@ NLL_BLOCKS, NLL_MAX_ITER = 256, 16
 BN_BLOCKS = 256
 ACT_BASE, ACT_LEAKY_RELU = 0, 1
 TILING_FLAT, TILING_BM256, TILING_BM64 = 1, 2, 4
+SPLITK_MAX, SPLITK_MIN_CHUNKS = 8, 2
 METRICS_SIGMA, METRICS_VARIANCE, METRICS_NONE = 0, 1, 2
 
 
@@ -264,6 +265,8 @@ _PROTOS = {
     "magnet_conv_mfma_ex": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_conv_mfma_f16": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_conv_mfma_f16p": (_C, [_S(MagnetConvExArgs), _P]),
+    "magnet_conv_mfma_splitk_workspace": (_L, [_S(MagnetConvExArgs), _I]),
+    "magnet_conv_mfma_splitk": (_C, [_S(MagnetConvExArgs), _I, _P, _L, _P]),
     "magnet_pack_f16": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
     "magnet_planes_to_f16": (_C, [_P, _P, _I, _P, _I, _L, _I, _I, _P]),
     "magnet_fnet_stem_f16": (_C, [_P, _P, _P, _P, _I, _I, _I, _P]),
@@ -596,7 +599,7 @@ def upsample_depth(depth, up_mask, k: int, out=None):
 # ---------------------------------------------------------------------------------------------------
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
-              mx=None, leaky=None, tiling=None, f16=False):
+              mx=None, leaky=None, tiling=None, f16=False, split_k=None, work=None):
     """One convolution layer on the matrix cores.  in_hi/in_lo: bf16 tensors whose data_ptr is row 0 (possibly a
     channel-offset view of a wider buffer, `in_ld` = its row pitch in elements); weights (taps, cout_pad, cin) bf16.
     F-Net extras (include/magnet_hip.h): dil (3x3 dilation), out_ld (write a channel slice: out tensors may then be
@@ -614,7 +617,19 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     3x3 layers with cout_pad 128, a fused tail of 16 / 144 outputs or out_f32.  Always returns the row tile count.
     f16 = "plane": the same operand format, plane to plane (magnet_conv_mfma_f16p, the F-Net's launches): `add` = (fp16 plane, None, ld),
     the output is out_f16 (one fp16 plane, passed as out_hi with out_lo None), out_f32 or out_bf16; taps 1 / 4 / 9, cout_pad 32 / 64 /
-    128, dil, border, repad and channel slices as in the default format; no tail, addend, mx or leaky."""
+    128, dil, border, repad and channel slices as in the default format; no tail, addend, mx or leaky.
+    split_k = S (2 .. SPLITK_MAX) with work = a float32 GPU tensor of at least conv_mfma_splitk_workspace(...) bytes: the split-K form
+    (magnet_conv_mfma_splitk) of the plain bf16x3 layer, taps 1 / 9, cout_pad % 128 == 0, out_hi / out_lo or out_f32; not with f16, tail,
+    addend, add or mx.  Returns the row tile count."""
+    if split_k is not None:
+        if f16 or tail is not None or addend is not None or add is not None or mx is not None:
+            raise MagnetError("conv_mfma (split_k): the plain bf16x3 layer only — not with f16, tail, addend, add or mx")
+        if isinstance(split_k, bool) or not isinstance(split_k, int):
+            raise MagnetError(f"conv_mfma: split_k must be an int, got {split_k!r}")
+        if not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous():
+            raise MagnetError("conv_mfma (split_k): work must be a contiguous float32 GPU tensor")
+    elif work is not None:
+        raise MagnetError("conv_mfma: work goes with split_k")
     a = MagnetConvArgs()
     plane = f16 == "plane"
     if f16 not in (False, True, "plane"):
@@ -685,14 +700,28 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_hi = 3, _f16_ptr(out_hi, "out_hi (fp16 plane)")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
-    if leaky is None and tiling is None and not f16:
+    if leaky is None and tiling is None and not f16 and split_k is None:
         _launch("magnet_conv_mfma", in_hi, ctypes.byref(a))
         return None
     tiles = ctypes.c_int64(0)
     x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
+    if split_k is not None:
+        _launch("magnet_conv_mfma_splitk", in_hi, ctypes.byref(x), int(split_k), work.data_ptr(), work.numel() * 4)
+        return tiles.value
     _launch("magnet_conv_mfma_f16p" if plane else "magnet_conv_mfma_f16" if f16 else "magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
     return tiles.value
+
+
+def conv_mfma_splitk_workspace(rows, cin, cout_pad, taps, split_k):
+    """magnet_conv_mfma_splitk_workspace: the bytes of `work` for a split-K launch of this shape (split_k x rows x cout_pad fp32);
+    MagnetError for a form the entry point refuses.  Host arithmetic: needs the library, not a GPU."""
+    x = MagnetConvExArgs()
+    x.base.rows, x.base.cin, x.base.cout_pad, x.base.taps, x.base.out_mode = int(rows), int(cin), int(cout_pad), int(taps), 1
+    nbytes = int(load().magnet_conv_mfma_splitk_workspace(ctypes.byref(x), int(split_k)))
+    if nbytes < 0:
+        _check(-nbytes, "magnet_conv_mfma_splitk_workspace")
+    return nbytes
 
 
 def conv_row_tiles(n_img, h, wp, bm):

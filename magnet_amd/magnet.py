@@ -126,11 +126,15 @@ class MAGNET(nn.Module):
     `fnet_precision`: 'bf16x3' (default) or 'fp16', the precision of the matrix-core F-Net runner (FNetMFMA(psm, precision=...)):
     'fp16' keeps every F-Net activation as ONE fp16 plane and issues one matrix instruction per product.  Independent of
     `conv_precision` (which stops at the backbone); needs conv_backend='mfma'; a reduced-precision inference mode the caller opts
-    into, measured in profiles/fnet_precision/NOTES.md.  Activations beyond +-65504 are clamped, not propagated as Inf."""
+    into, measured in profiles/fnet_precision/NOTES.md.  Activations beyond +-65504 are clamped, not propagated as Inf.
+    `dnet_split_k`: 0 (default, off), 'auto' or {layer: S}: DNetMFMA's split-K mode for the decoder's plain layers at one to a few
+    images (magnet_amd/dnet.py, profiles/splitk/NOTES.md); needs dnet_backend='hip'.  Under 'auto' the factor depends on the batch's
+    tile count, so an image's bits can differ between batch sizes by fp32 summation order; SequenceRunner's bit-equality with forward()
+    holds when both ran the same factors."""
 
     def __init__(self, args, d_net: nn.Module | None = None, f_net: nn.Module | None = None,
                  feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch", dnet_backend: str = "torch",
-                 conv_precision: str = "bf16x3", fnet_precision: str = "bf16x3"):
+                 conv_precision: str = "bf16x3", fnet_precision: str = "bf16x3", dnet_split_k=0):
         super().__init__()
         self.args = args
         if d_net is None or f_net is None:
@@ -190,6 +194,10 @@ class MAGNET(nn.Module):
             raise lib.MagnetError(f"dnet_backend must be 'torch' or 'hip', got {dnet_backend!r}")
         self.dnet_backend = dnet_backend
         self._dnet = None
+        from .dnet import check_split_k
+        self.dnet_split_k = check_split_k(dnet_split_k, "MAGNET (dnet_split_k)")
+        if self.dnet_split_k != 0 and dnet_backend != "hip":
+            raise lib.MagnetError("dnet_split_k is a mode of the HIP D-Net decoder: it needs dnet_backend='hip'")
         if dnet_backend == "hip":
             if conv_backend != "mfma":
                 raise lib.MagnetError("dnet_backend='hip' runs the D-Net decoder on the matrix-core path: it needs conv_backend='mfma'")
@@ -205,7 +213,7 @@ class MAGNET(nn.Module):
             if getattr(d_net, "dnet", False):
                 raise lib.MagnetError("dnet_backend='hip' needs the D-Net built with dnet=False (mean, sigma and x_feat at 1/4)")
             from .dnet import DNetMFMA
-            self._dnet = DNetMFMA(inner.decoder)          # checks the decoder: BatchNorm, LeakyReLU, 2-output head
+            self._dnet = DNetMFMA(inner.decoder, split_k=self.dnet_split_k)          # checks the decoder: BatchNorm, LeakyReLU, 2-output head
         self._work = {}                # cached device workspaces of the MFMA conv path, keyed by shape
         self.fuse_upsample = True      # the stacks' tails finish the job: G-Net's head applies the Gaussian update, the mask head
                                        # writes the upsampled predictions itself (no (B,144,h,w) mask in HBM); False: separate launches

@@ -11,7 +11,15 @@ activation_G, encoder not timed): torch fp32 against DNetMFMA.run_standalone at 
 N = 4 and at KITTI with N = 1, plus the per-launch event times and the time of everything behind x_feat (the two head launches and
 magnet_dnet_upsample_gauss).  Each timing is the median of --repeats timed loops of --steps calls.
 
+--split_k sweep times every plain decoder launch (event-bracketed, the reduce launch included) with the split-K factor S forced to 1, 2, 3,
+4, 5, 6 and 8 on all layers (a layer whose input has too few chunks for S keeps its largest allowed factor) at 480 x 640 with N = 1, 2, 4
+and 352 x 1216 with N = 1, 3, and prints what dnet.split_factor would choose.  --split_k auto --pairs P times P interleaved pairs, in this
+process, of DNetMFMA(split_k=0) against DNetMFMA(split_k="auto") for run_standalone and run at N = 1 (both shapes) and N = 4, checks that
+split_k=0 gives the default runner's bits and reports how far "auto" is from them.
+
     python tools/bench_dnet.py [--steps 10] [--warmup 3] [--out profiles/dnet/bench_dnet.jsonl]
+    python tools/bench_dnet.py --split_k sweep [--repeats 7] [--out profiles/splitk/bench_splitk.jsonl]
+    python tools/bench_dnet.py --split_k auto --pairs 12 [--steps 20] [--out profiles/splitk/bench_splitk.jsonl]
     python tools/bench_dnet.py --standalone [--steps 20] [--warmup 5] [--repeats 5] [--out profiles/dnet/bench_dnet_standalone.jsonl]
 """
 import argparse
@@ -34,6 +42,8 @@ def main():
     ap.add_argument("--skip-magnet", action="store_true")
     ap.add_argument("--standalone", action="store_true")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--split_k", default=None, choices=["sweep", "auto"])
+    ap.add_argument("--pairs", type=int, default=12)
     a = ap.parse_args()
     from magnet_amd import fnet, lib, synth
     from magnet_amd.dnet import DNetMFMA, gaussian_activation
@@ -67,6 +77,79 @@ def main():
             with open(a.out, "a") as fh:
                 for d_ in lines:
                     fh.write(json.dumps(d_) + "\n")
+
+    if a.split_k:
+        import statistics
+        from magnet_amd.dnet import SPLIT_LAYERS, split_factor
+        d = make_dnet(dnet=True).to(dev)
+        dec = d.d_net.decoder
+        chunks = dict(zip(SPLIT_LAYERS, (64, 70, 32, 34, 16, 18, 8)))
+        n_tiles = dict(zip(SPLIT_LAYERS, (16, 8, 8, 4, 4, 2, 2)))
+
+        def layer_ms(runner, feats, reps):
+            """median event time per plain decoder launch of run_standalone (the first len(SPLIT_LAYERS) brackets), and the rows of each"""
+            per = []
+            for _ in range(reps + 2):
+                sink = []
+                DNetMFMA.event_sink = sink
+                runner.run_standalone(feats)
+                torch.cuda.synchronize()
+                DNetMFMA.event_sink = None
+                per.append([e0.elapsed_time(e1) for e0, e1, _ in sink])
+            ms = [round(statistics.median(col), 4) for col in zip(*per[2:])]
+            return dict(zip(SPLIT_LAYERS, ms)), round(sum(ms[:len(SPLIT_LAYERS)]), 4), {n: r for n, r, _ in runner.factors_used}
+
+        if a.split_k == "sweep":
+            for name, H, W, N in (("C2", 480, 640, 1), ("C2", 480, 640, 2), ("C2", 480, 640, 4), ("KITTI", 352, 1216, 1), ("KITTI", 352, 1216, 3)):
+                with torch.no_grad():
+                    feats = d.d_net.encoder(images(N, H, W, N))
+                    for S in (1, 2, 3, 4, 5, 6, 8):
+                        forced = {n: min(S, max(1, chunks[n] // lib.SPLITK_MIN_CHUNKS)) for n in SPLIT_LAYERS}
+                        ms, total, rows = layer_ms(DNetMFMA(dec, split_k=forced), feats, a.repeats)
+                        emit(dict(bench="dnet_splitk_sweep", shape=name, H=H, W=W, N=N, S=S, forced=forced, ms_per_layer=ms,
+                                  ms_all_launches=total, repeats=a.repeats,
+                                  workgroups={n: (rows[n] + 127) // 128 * n_tiles[n] for n in SPLIT_LAYERS},
+                                  auto={n: split_factor((rows[n] + 127) // 128, n_tiles[n], chunks[n]) for n in SPLIT_LAYERS}))
+                del feats
+                torch.cuda.empty_cache()
+            write_out()
+            return
+
+        def once(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / a.steps
+
+        for name, H, W, N in (("C2", 480, 640, 1), ("KITTI", 352, 1216, 1), ("C2", 480, 640, 4)):
+            with torch.no_grad():
+                feats = d.d_net.encoder(images(N, H, W, N))
+                r_def, r0, r1 = DNetMFMA(dec), DNetMFMA(dec, split_k=0), DNetMFMA(dec, split_k="auto")
+                base, o0, o1 = r_def.run_standalone(feats), r0.run_standalone(feats), r1.run_standalone(feats)
+                used = {n: S for n, _, S in r1.factors_used}
+                rel = float((o1.double() - base.double()).abs().max() / base.double().abs().max())
+                for form, f0, f1 in (("run_standalone", lambda: r0.run_standalone(feats), lambda: r1.run_standalone(feats)),
+                                     ("run", lambda: r0.run(feats), lambda: r1.run(feats))):
+                    for _ in range(a.warmup):
+                        f0(); f1()
+                    t0s, t1s = [], []
+                    for _ in range(a.pairs):
+                        t0s.append(once(f0)); t1s.append(once(f1))
+                    emit(dict(bench="dnet_splitk_pairs", shape=name, H=H, W=W, N=N, form=form, pairs=a.pairs, steps=a.steps,
+                              factors=used, ms_split0=[round(t, 4) for t in t0s], ms_auto=[round(t, 4) for t in t1s],
+                              median_split0=round(statistics.median(t0s), 4), median_auto=round(statistics.median(t1s), 4),
+                              auto_faster_pairs=sum(b < a_ for a_, b in zip(t0s, t1s)),
+                              split0_bits_equal_default=bool(torch.equal(base, o0)), auto_rel_diff_to_default=rel))
+                ms0, tot0, _ = layer_ms(r0, feats, a.repeats)
+                ms1, tot1, _ = layer_ms(r1, feats, a.repeats)
+                emit(dict(bench="dnet_splitk_layers", shape=name, H=H, W=W, N=N, factors=used, ms_split0=ms0, ms_auto=ms1,
+                          ms_split0_launches=tot0, ms_auto_launches=tot1))
+            del feats
+            torch.cuda.empty_cache()
+        write_out()
+        return
 
     if a.standalone:
         import statistics
