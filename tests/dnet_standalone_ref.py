@@ -24,6 +24,33 @@ def _grids(head, head_ld, mask, mask_ld, N, h, w):
     return Hp, M[:, 1:-1, 1:-1, :144].reshape(N, h, w, 9, 4, 4)
 
 
+def softmax_tap_terms(M, axis, d_err=1.0, exp_err=ULP1 / U):
+    """The softmax over the 9 taps along `axis` of the logits M (fp64) as the kernels form it, and the rounding count of one tap's term:
+    returns (d, wgt, K) with d = M - max (<= 0, the largest tap exactly 0), wgt = exp(d) / sum exp(d), and K[t] the number of roundings,
+    in units of U, that the term w[t] * v[t] of the sum of 9 passes through (Higham's gamma_k, first order k U):
+        d = x - max        1, an ABSOLUTE error U |d| in the exponent -> relative |d| U after exp           (d_err |d|)
+        the exponential    2 = a 1-ulp expf                                                                (exp_err)
+        the denominator    8 additions + the exp errors of its own terms, sum_m w[m] (d_err |d[m]| + exp_err)
+        1 / den            1
+        e * inv            1
+        w * v              1
+        the sum of 9       8 additions (the first one adds to zero and is exact)
+    d_err and exp_err describe the exponential: the defaults are the device maths library's expf (dnet_upsample_gauss_kernel); the
+    native exponential of upsample_kernel / upsample_cl_kernel passes its own (tests/elementwise_fwd_ref.py)."""
+    d = M - M.max(axis=axis, keepdims=True)
+    e = np.exp(d)
+    wgt = e / e.sum(axis=axis, keepdims=True)
+    a = d_err * np.abs(d) + exp_err
+    K = a + 8.0 + (wgt * a).sum(axis=axis, keepdims=True) + 1.0 + 1.0 + 1.0 + 8.0
+    return d, wgt, K
+
+
+def convex_sum_bound(S, K, vmax):
+    """S = sum_t w[t] |v[t]| K[t] -> the bound on the sum of 9: the first-order mass, Higham's 1 / (1 - k U) for the higher orders, plus
+    9 taps whose exponential may have underflowed (each loses at most FMIN of weight, times the largest |v| of the neighbourhood)."""
+    return S * U / (1.0 - float(K.max()) * U) + 9.0 * FMIN * vmax
+
+
 def _elu1(v):
     return np.where(v > 0, v, np.expm1(np.minimum(v, 0.0))) + 1.0 + 1e-10
 
@@ -35,20 +62,9 @@ def upsample_gauss_ref(head, head_ld, mask, mask_ld, N, h, w, defect=None, with_
     if defect == "act_first":
         Hp = Hp.copy()
         Hp[:, 1:-1, 1:-1, 1] = _elu1(Hp[:, 1:-1, 1:-1, 1])
-    d = M - M.max(axis=3, keepdims=True)                                # <= 0, the largest tap exactly 0
-    e = np.exp(d)
-    wgt = e / e.sum(axis=3, keepdims=True)                              # (N, h, w, 9, 4, 4)
+    d, wgt, K = softmax_tap_terms(M, axis=3)                            # wgt (N, h, w, 9, 4, 4)
     up = np.zeros((N, 2, h, w, 4, 4))
     S = np.zeros((N, 2, h, w, 4, 4))                                    # sum_t w[t] |v[t]| K[t], the first-order error mass
-    # Rounding steps a tap's term w[t] * v[t] passes through, each of relative size <= U unless stated (Higham's gamma_k, first order k U):
-    #   d = x - max        1, an ABSOLUTE error U |d| in the exponent -> relative |d| U after exp
-    #   expf               2 (1 ulp)
-    #   the denominator    8 additions + the exp errors of its own terms, sum_m w[m] (|d[m]| + 2)
-    #   1 / den            1
-    #   e * inv            1
-    #   w * v              1
-    #   the sum of 9       8 additions (the first one adds to zero and is exact)
-    K = np.abs(d) + 2.0 + 8.0 + (wgt * (np.abs(d) + 2.0)).sum(axis=3, keepdims=True) + 1.0 + 1.0 + 1.0 + 8.0
     vmax = np.zeros((N, 2, h, w, 1, 1))
     for t in range(9):
         ty, tx = (t % 3, t // 3) if defect == "taps_transposed" else (t // 3, t % 3)
@@ -62,9 +78,7 @@ def upsample_gauss_ref(head, head_ld, mask, mask_ld, N, h, w, defect=None, with_
     out = up.transpose(0, 1, 2, 4, 3, 5).reshape(N, 2, 4 * h, 4 * w)
     if not with_bound:
         return out
-    kmax = float(K.max())
-    # first-order mass, Higham's 1 / (1 - k U) for the higher orders, plus 9 taps whose exp may have underflowed
-    E = S * U / (1.0 - kmax * U) + 9.0 * FMIN * vmax
+    E = convex_sum_bound(S, K, vmax)
     Eb = np.empty_like(E)
     Eb[:, 0] = E[:, 0]
     # variance: elu is 1-Lipschitz, so the error of its argument passes through at most unchanged (across the knee too); expm1f is 1 ulp

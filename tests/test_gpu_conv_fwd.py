@@ -36,7 +36,11 @@ Not repeated here, because existing tests tie them bit for bit to launches that 
   the fused Gaussian update and the fused upsampling     test_gpu_conv.py::test_gnet_with_fused_gaussian_update_equals_the_two_launch_form,
                                                          ::test_mask_head_with_fused_upsampling_equals_the_two_launch_form (= the plain
                                                          tail + the stand-alone kernel), and test_gpu_conv_image_tiles.py (per-image ==
-                                                         flat tiling)
+                                                         flat tiling).  The stand-alone kernels (magnet_gaussian_update_cl,
+                                                         magnet_upsample_depth_cl / _cl_n) are the anchor of that chain: they are
+                                                         checked against fp64 with derived pointwise bounds, at block-edge shapes
+                                                         and edge inputs, in tests/test_gpu_elementwise_fwd.py (restatements and
+                                                         bounds: tests/elementwise_fwd_ref.py)
   the fp16 + e4m3 operand format (opt-in)                test_gpu_conv.py::test_conv_stack_mx_format_matches_fp32 keeps its max-norm check;
                                                          a pointwise bound for its e4m3 correction terms is a separate piece of work.
 """

@@ -4,15 +4,9 @@ The four non-GEMM kernels (`magnet_*_f16`) at the shapes of tests/test_gpu_fnet.
 runner: equalities that must hold bit for bit, the default path untouched, and the accuracy of the mode, measured against the same
 module's torch fp32 forward (never against the default HIP path) and recorded in the docstrings below.
 
-Bounds of the small kernels.  u = 2^-24, gamma(L) = L u / (1 - L u).  Each kernel computes in fp32 and stores ONE fp16 rounding of
-the result: 2^-11 |ref| where |ref| >= 2^-14, else 2^-25 (fp16 denormals are kept).
-    stem        27 fused multiply-adds and the bias addition: gamma(28) (|w| conv |x| + |b|); ReLU is 1-Lipschitz
-    avgpool     fp16 inputs are exact in fp32; k^2 terms summed in fp32 (any order: gamma(k^2 - 1) sum|x|), then times fl(1 / k^2)
-                (two more roundings): gamma(k^2 + 2) mean|x|
-    upsample    the interpolation weights are formed in fp32 from the integer coordinates exactly as the kernel forms them (IEEE
-                operations, no contraction: the reference repeats them in torch fp32 and promotes them to fp64), then
-                ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11): 4 terms, at most 5 roundings on any path: gamma(6) sum w_i |v_i|
-    space to depth   a move: bit-exact
+Bounds of the small kernels: tests/elementwise_fwd_ref.py (stem_ref, avgpool_ref, bilinear_ref with fmt="f16"; derived in its
+docstring); space to depth is a move: bit-exact.  tests/test_gpu_elementwise_fwd.py runs the same restatements at the edge shapes, in
+both plane formats.
 """
 import numpy as np
 import pytest
@@ -21,17 +15,13 @@ import torch.nn.functional as F
 
 from magnet_amd import fnet, lib
 from magnet_amd.planes import to_f16_sat
-from tests.conv_fwd_ref import check, gamma_l
+from tests.conv_fwd_ref import check
+from tests.elementwise_fwd_ref import avgpool_ref, bilinear_ref, stem_ref
 from tests.stubs import StubDNet, make_args, procedural_images, seeded_fnet_state, seeded_magnet_weights
 
 pytestmark = pytest.mark.gpu
 
 FILL = -7.0                                                          # finite sentinel of the fp16 buffers (a border must stay 0, not this)
-
-
-def _f16_round(ref):
-    a = ref.abs()
-    return torch.where(a >= 2.0 ** -14, a * 2.0 ** -11, torch.full_like(a, 2.0 ** -25))
 
 
 def _filled(shape, gpu):
@@ -49,10 +39,7 @@ def test_stem_f16(hip_lib, gpu):
     H2, W2 = 19, 25
     out = _filled((2, H2 + 2, W2 + 2, 32), gpu)
     lib.fnet_stem_f16(img.to(gpu), w.reshape(32, 27).contiguous().to(gpu), b.to(gpu), out.view(-1, 32))
-    pre = F.conv2d(img.double(), w.double(), b.double(), stride=2, padding=1)
-    mag = F.conv2d(img.double().abs(), w.double().abs(), b.double().abs(), stride=2, padding=1)
-    ref = pre.clamp_min(0).permute(0, 2, 3, 1)
-    bound = gamma_l(28) * mag.permute(0, 2, 3, 1) + _f16_round(ref)
+    ref, bound = stem_ref(img, w.reshape(32, 27), b, "f16")
     got = out.cpu()
     worst = check("stem_f16", got[:, 1:-1, 1:-1], ref, bound)
     m = torch.zeros(got.shape, dtype=torch.bool); m[:, 1:-1, 1:-1] = True
@@ -84,11 +71,9 @@ def test_avgpool_f16(hip_lib, gpu, k):
     ph, pw = 64 // k, 80 // k
     out = _filled((2 * ph * pw + 8, 128), gpu)
     lib.avgpool_cl_f16(buf.reshape(-1, 320).to(gpu)[:, 64:192], 320, 2, 64, 80, 2, k, 128, out)
-    xr = x.double().permute(0, 3, 1, 2)
-    ref = F.avg_pool2d(xr, k, k).permute(0, 2, 3, 1).reshape(-1, 128)
-    mag = F.avg_pool2d(xr.abs(), k, k).permute(0, 2, 3, 1).reshape(-1, 128)
+    ref, bound = avgpool_ref(x, k, "f16")
     got = out.cpu()
-    worst = check(f"avgpool_f16 k={k}", got[:2 * ph * pw], ref, gamma_l(k * k + 2) * mag + _f16_round(ref))
+    worst = check(f"avgpool_f16 k={k}", got[:2 * ph * pw], ref, bound)
     assert bool((got[2 * ph * pw:] == FILL).all())
     print(f"[avgpool_f16 k={k}] worst ratio {worst:.4f}")
 
@@ -99,24 +84,9 @@ def test_upsample_bilinear_f16(hip_lib, gpu, ph, pw):
     h, w = 60, 80
     out = _filled((2, h + 4, w + 4, 320), gpu)
     lib.upsample_bilinear_cl_f16(q.reshape(-1, 32).to(gpu), 32, ph, pw, 32, out.view(-1, 320)[:, 224:256], 320, 2, h, w, 2)
-
-    def axis(n_in, n_out):                                            # the kernel's fp32 coordinate arithmetic, operation by operation
-        s = (torch.tensor(float(n_in - 1)) / torch.tensor(float(n_out - 1))) if n_out > 1 else torch.tensor(0.0)
-        f = s * torch.arange(n_out, dtype=torch.float32)
-        i0 = f.to(torch.int64)
-        i1 = i0 + (i0 < n_in - 1).to(torch.int64)
-        l1 = f - i0.float()
-        return i0, i1, (1.0 - l1).double(), l1.double()
-
-    y0, y1, ly0, ly1 = axis(ph, h)
-    x0, x1, lx0, lx1 = axis(pw, w)
-    qd = q.double()
-    terms = [(ly0[:, None] * lx0[None, :], qd[:, y0][:, :, x0]), (ly0[:, None] * lx1[None, :], qd[:, y0][:, :, x1]),
-             (ly1[:, None] * lx0[None, :], qd[:, y1][:, :, x0]), (ly1[:, None] * lx1[None, :], qd[:, y1][:, :, x1])]
-    ref = sum(wt[None, :, :, None] * v for wt, v in terms)
-    mag = sum(wt[None, :, :, None] * v.abs() for wt, v in terms)
+    ref, bound = bilinear_ref(q, h, w, "f16")
     got = out.cpu()
-    worst = check(f"upsample_f16 {ph}x{pw}", got[:, 2:-2, 2:-2, 224:256], ref, gamma_l(6) * mag + _f16_round(ref))
+    worst = check(f"upsample_f16 {ph}x{pw}", got[:, 2:-2, 2:-2, 224:256], ref, bound)
     # the reference itself against ATen's bilinear (fp32 arithmetic on both sides: the existing test's tolerance)
     exp = F.interpolate(q.permute(0, 3, 1, 2), size=(h, w), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
     np.testing.assert_allclose(ref.float().numpy(), exp.numpy(), rtol=0, atol=2e-5)
