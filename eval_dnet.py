@@ -100,6 +100,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--split_k", default="0", choices=["0", "auto"],
                     help="split-K launches for the decoder's plain layers (DNetMFMA(split_k=...)); needs --backend hip")
+    ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "fp16"],
+                    help="operand format of the HIP decoder (DNetMFMA(precision=...)): fp16 = one fp16 plane per buffer, reduced precision, "
+                         "|activation| <= 65504 or clamped; needs --backend hip")
     ap.add_argument("--dataset_path", default="", help="root of ScanNet-format scene folders (magnet_amd/data.py) instead of synthetic frames")
     ap.add_argument("--split", default="", help="text file of '<scene> <frame index>' lines (data_split/scannet_*.txt format)")
     ap.add_argument("--dataset_format", default="scannet", choices=["scannet", "7scenes"],
@@ -111,7 +114,7 @@ def main():
     rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.standin import make_dnet
     args = argparse.Namespace(min_depth=a.min_depth, max_depth=a.max_depth, garg_crop=a.garg_crop, eigen_crop=a.eigen_crop)
-    model = make_dnet(dnet=True, backend=a.backend, split_k="auto" if a.split_k == "auto" else 0).to(device).eval()    # seeded weights unless the caller loads a checkpoint
+    model = make_dnet(dnet=True, backend=a.backend, split_k="auto" if a.split_k == "auto" else 0, precision=a.precision).to(device).eval()    # seeded weights unless the caller loads a checkpoint
     if a.dataset_path:
         from magnet_amd import data
         with open(a.split) as f:

@@ -666,6 +666,30 @@ MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs *args, void *stream)
 MAGNET_API int64_t magnet_conv_mfma_splitk_workspace(const MagnetConvExArgs *args, int32_t split_k);
 MAGNET_API int magnet_conv_mfma_splitk(const MagnetConvExArgs *args, int32_t split_k, float *work, int64_t work_bytes, void *stream);
 
+/* The single-plane fp16 format, plane to plane and WIDE: the plain layers of a D-Net decoder whose activation buffers are ONE
+ * zero-bordered channel-last fp16 plane each (DNetMFMA(precision="fp16")).  The struct's fields mean, for this entry point only:
+ *   base.in_hi / base.w_hi   fp16 planes (rows, in_ld) / (taps, cout_pad, cin); base.in_lo, w_lo, in_sc, w_sc, add_hi and add_lo must
+ *                            be NULL (planes of another format are refused, not mis-read; there is no residual input)
+ *   act                      MAGNET_ACT_BASE (base.relu 0 or 1) or MAGNET_ACT_LEAKY_RELU(act_slope), as in magnet_conv_mfma_ex
+ *   base.out_mode            3: one fp16 plane at out_hi (saturating round-to-nearest-even, NaN written through: see MagnetConvArgs);
+ *                            1: fp32 at out_f32; 0: split-bf16 planes at out_hi / out_lo (x_feat for G-Net's buffer and the heads); 2 is
+ *                            refused
+ *   border_hp / border_pad / repad / in_ld / out_ld   as in magnet_conv_mfma
+ * Serves taps 1 and 9 without dilation, cout_pad a multiple of 128 (128-row x 128-channel tiles, one grid column per 128 channels), cin
+ * a multiple of 32, tiling 0 or MAGNET_TILING_FLAT; tiles_out works.  A fused tail, an addend, a residual input, the Gaussian update /
+ * upsampling, the e4m3 format, dilation, any other cout_pad and MAGNET_TILING_BM64 / MAGNET_TILING_BM256 are refused with MAGNET_E_DIM;
+ * a refused call writes nothing.  Each fp16 x fp16 product is exact in the fp32 accumulator; bias and activation are fp32 arithmetic
+ * as in magnet_conv_mfma.  Domain: |activation|, |weight| <= 65504 (stores clamp; the caller rounds its weights). */
+MAGNET_API int magnet_conv_mfma_f16d(const MagnetConvExArgs *args, void *stream);
+
+/* Split-K form of magnet_conv_mfma_f16d: the contract of magnet_conv_mfma_splitk (chunk ranges, work[s][row][cout_pad] raw fp32
+ * partials, the second launch summing in ascending s, then bias and the epilogue; limits, refusals, error codes and workspace query the
+ * same; no counters or atomics) on the fp16 operand planes of magnet_conv_mfma_f16d, whose own refusals apply too.  The reduce also
+ * serves out_mode 3 (one fp16 plane).  A partial equals, to the bit, what magnet_conv_mfma_f16d writes to out_f32 for that channel range
+ * alone (channel-offset input view, weights packed for the range, zero bias, no activation). */
+MAGNET_API int64_t magnet_conv_mfma_f16d_splitk_workspace(const MagnetConvExArgs *args, int32_t split_k);
+MAGNET_API int magnet_conv_mfma_f16d_splitk(const MagnetConvExArgs *args, int32_t split_k, float *work, int64_t work_bytes, void *stream);
+
 /* fp32 NCHW (N, C, h, w) (image stride `in_img_stride` elements, 0 = C*h*w) -> channels [c_off, c_off + round_up(C, 8)) of the interior
  * of a zero-bordered (N, h+2, w+2, ctot) fp16 plane (the round-up lanes are written as zeros, as by magnet_pack_split).  ctot and c_off
  * multiples of 8.  The border rows and every other channel are not written.  Conversion: see the single-plane fp16 format above. */

@@ -307,13 +307,17 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 // mode: the operand format.  CONV_BF16X3: (hi, lo) planes (or the fp16 + e4m3 format).  CONV_F16: the single-plane fp16 operand format
 // (magnet_conv_mfma_f16, which has checked what that format serves): no lo planes.  CONV_F16P: the same operands, plane to plane
 // (magnet_conv_mfma_f16p): the residual is ONE fp16 plane (add_lo NULL) and out_mode 3 (one fp16 plane at out_hi) exists
-enum { CONV_BF16X3 = 0, CONV_F16 = 1, CONV_F16P = 2 };
+// CONV_F16D: plane to plane, wide (magnet_conv_mfma_f16d, the D-Net decoder's plain layers): no residual; out_mode 0, 1 or 3
+enum { CONV_BF16X3 = 0, CONV_F16 = 1, CONV_F16P = 2, CONV_F16D = 3 };
 // split_k >= 2 (magnet_conv_mfma_splitk, which has checked what that form serves): the split-K launches with workspace `work`
 static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream, int mode = CONV_BF16X3,
                          int split_k = 0, float* work = nullptr) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
     const bool f16 = mode != CONV_BF16X3;
     if (!a->in_hi || (!f16 && !a->in_lo) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
+    if (mode == CONV_F16D) {
+        if (a->out_mode != 0 && a->out_mode != 1 && a->out_mode != 3) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16d: out_mode must be 0, 1 or 3");
+    } else
     if (mode == CONV_F16P ? (a->out_mode < 1 || a->out_mode > 3) : (a->out_mode < 0 || a->out_mode > 2))
         return fail(MAGNET_E_DIM, mode == CONV_F16P ? "magnet_conv_mfma_f16p: out_mode must be 1, 2 or 3" : "magnet_conv_mfma: out_mode must be 0, 1 or 2");
     const bool tail = a->tail_w_hi != nullptr;
@@ -409,7 +413,9 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
-    hipError_t e = split_k          ? magnet::launch_conv_mfma_splitk(p, split_k, work, (hipStream_t)stream)
+    hipError_t e = mode == CONV_F16D ? (split_k ? magnet::launch_conv_mfma_f16d_splitk(p, split_k, work, (hipStream_t)stream)
+                                                : magnet::launch_conv_mfma_f16d(p, (hipStream_t)stream))
+                 : split_k          ? magnet::launch_conv_mfma_splitk(p, split_k, work, (hipStream_t)stream)
                  : mode == CONV_F16P ? magnet::launch_conv_mfma_f16p(p, (hipStream_t)stream)
                  : mode == CONV_F16  ? magnet::launch_conv_mfma_f16(p, (hipStream_t)stream) : magnet::launch_conv_mfma(p, (hipStream_t)stream);
     if (tiles_out) *tiles_out = tiles;
@@ -471,21 +477,24 @@ MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs* a, void* stream) {
 }
 
 // What the split-K form serves (both entry points): 0, or the MAGNET_E_* code with the message set.  *bytes: the workspace size.
-static int conv_splitk_check(const MagnetConvExArgs* a, int32_t split_k, int64_t* bytes) {
-    if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_splitk: args is NULL");
+// f16d: the form on fp16 planes (magnet_conv_mfma_f16d_splitk, `who`): the same limits, and out_mode 3 exists.
+static int conv_splitk_check(const MagnetConvExArgs* a, int32_t split_k, int64_t* bytes, const char* who = "magnet_conv_mfma_splitk", bool f16d = false) {
+    if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
     const MagnetConvArgs& b = a->base;
-    if (split_k < 2 || split_k > MAGNET_SPLITK_MAX) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: split_k=%d (2 .. %d)", split_k, MAGNET_SPLITK_MAX);
+    if (split_k < 2 || split_k > MAGNET_SPLITK_MAX) return fail(MAGNET_E_DIM, "%s: split_k=%d (2 .. %d)", who, split_k, MAGNET_SPLITK_MAX);
     if (b.tail_w_hi || b.tail_w_lo || b.addend || b.add_hi || b.add_lo || b.in_sc || b.w_sc || b.up_out || b.up_depth || b.gu_in || b.gu_out)
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: the plain bf16x3 layer only (no fused tail, addend, residual input, e4m3 format, Gaussian update or upsampling)");
-    if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", a->tiling);
-    if (b.taps != 1 && b.taps != 9) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: taps=%d (1 or 9)", b.taps);
-    if (b.cout_pad <= 0 || b.cout_pad % 128 != 0) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: cout_pad=%d must be a multiple of 128", b.cout_pad);
-    if (b.out_mode != 0 && b.out_mode != 1) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: out_mode=%d (0: split-bf16 planes, 1: fp32)", b.out_mode);
-    if (b.rows <= 0 || b.cin <= 0 || (b.cin % 32) != 0) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: rows > 0 and cin %% 32 == 0 required (cin=%d)", b.cin);
+        return fail(MAGNET_E_DIM, "%s: the plain %s layer only (no fused tail, addend, residual input, e4m3 format, Gaussian update or upsampling)", who,
+                    f16d ? "fp16" : "bf16x3");
+    if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", who, a->tiling);
+    if (b.taps != 1 && b.taps != 9) return fail(MAGNET_E_DIM, "%s: taps=%d (1 or 9)", who, b.taps);
+    if (b.cout_pad <= 0 || b.cout_pad % 128 != 0) return fail(MAGNET_E_DIM, "%s: cout_pad=%d must be a multiple of 128", who, b.cout_pad);
+    if (b.out_mode != 0 && b.out_mode != 1 && !(f16d && b.out_mode == 3))
+        return fail(MAGNET_E_DIM, f16d ? "%s: out_mode=%d (0: split-bf16 planes, 1: fp32, 3: one fp16 plane)" : "%s: out_mode=%d (0: split-bf16 planes, 1: fp32)", who, b.out_mode);
+    if (b.rows <= 0 || b.cin <= 0 || (b.cin % 32) != 0) return fail(MAGNET_E_DIM, "%s: rows > 0 and cin %% 32 == 0 required (cin=%d)", who, b.cin);
     if ((b.cin / 32) / split_k < MAGNET_SPLITK_MIN_CHUNKS)
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: cin=%d gives a split fewer than %d 32-channel chunks at split_k=%d", b.cin, MAGNET_SPLITK_MIN_CHUNKS, split_k);
+        return fail(MAGNET_E_DIM, "%s: cin=%d gives a split fewer than %d 32-channel chunks at split_k=%d", who, b.cin, MAGNET_SPLITK_MIN_CHUNKS, split_k);
     if (b.rows >= ((int64_t)1 << 31) || b.rows * (b.cout_pad / 8) / 256 >= ((int64_t)1 << 31))
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: rows=%lld too large for the reduce launch", (long long)b.rows);
+        return fail(MAGNET_E_DIM, "%s: rows=%lld too large for the reduce launch", who, (long long)b.rows);
     *bytes = (int64_t)split_k * b.rows * b.cout_pad * 4;
     return 0;
 }
@@ -496,19 +505,67 @@ MAGNET_API int64_t magnet_conv_mfma_splitk_workspace(const MagnetConvExArgs* a, 
     return rc ? -(int64_t)rc : bytes;
 }
 
+// workspace pointer and activation of a split-K call (both forms), after conv_splitk_check
+static int conv_splitk_call_check(const MagnetConvExArgs* a, const float* work, int64_t work_bytes, int64_t bytes, const char* who) {
+    if (!work) return fail(MAGNET_E_NULL, "%s: work is NULL", who);
+    if (!aligned16(work)) return fail(MAGNET_E_ALIGN, "%s: work must be 16-byte aligned", who);
+    if (work_bytes < bytes) return fail(MAGNET_E_DIM, "%s: work_bytes=%lld < %lld", who, (long long)work_bytes, (long long)bytes);
+    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "%s: act=%d unknown", who, a->act);
+    if (a->act == MAGNET_ACT_LEAKY_RELU) {
+        if (a->base.relu) return fail(MAGNET_E_DIM, "%s: LeakyReLU excludes relu", who);
+        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
+            return fail(MAGNET_E_DIM, "%s: act_slope must be finite", who);
+    }
+    return 0;
+}
+
 MAGNET_API int magnet_conv_mfma_splitk(const MagnetConvExArgs* a, int32_t split_k, float* work, int64_t work_bytes, void* stream) {
     int64_t bytes = 0;
     if (const int rc = conv_splitk_check(a, split_k, &bytes)) return rc;
-    if (!work) return fail(MAGNET_E_NULL, "magnet_conv_mfma_splitk: work is NULL");
-    if (!aligned16(work)) return fail(MAGNET_E_ALIGN, "magnet_conv_mfma_splitk: work must be 16-byte aligned");
-    if (work_bytes < bytes) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: work_bytes=%lld < %lld", (long long)work_bytes, (long long)bytes);
-    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: act=%d unknown", a->act);
-    if (a->act == MAGNET_ACT_LEAKY_RELU) {
-        if (a->base.relu) return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: LeakyReLU excludes relu");
-        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
-            return fail(MAGNET_E_DIM, "magnet_conv_mfma_splitk: act_slope must be finite");
-    }
+    if (const int rc = conv_splitk_call_check(a, work, work_bytes, bytes, "magnet_conv_mfma_splitk")) return rc;
     return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream, CONV_BF16X3, split_k, work);
+}
+
+// What magnet_conv_mfma_f16d and its split-K form serve (`who`), before conv_mfma_run's checks of the common fields
+static int conv_f16d_check(const MagnetConvExArgs* a, const char* who) {
+    if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
+    const MagnetConvArgs& b = a->base;
+    // planes of another format are refused rather than mis-read
+    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc || b.add_hi || b.add_lo)
+        return fail(MAGNET_E_DIM, "%s: in_lo, w_lo, in_sc, w_sc, add_hi and add_lo must be NULL (in_hi / w_hi are single fp16 planes; no residual input)", who);
+    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "%s: act=%d unknown", who, a->act);
+    if (a->act == MAGNET_ACT_LEAKY_RELU) {
+        if (b.relu) return fail(MAGNET_E_DIM, "%s: LeakyReLU excludes relu", who);
+        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f) return fail(MAGNET_E_DIM, "%s: act_slope must be finite", who);
+    }
+    if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", who, a->tiling);
+    if (b.tail_w_hi || b.tail_w_lo || b.addend || b.up_out || b.up_depth || b.gu_in || b.gu_out)
+        return fail(MAGNET_E_DIM, "%s: no fused tail, addend, Gaussian update or upsampling", who);
+    if ((b.taps != 1 && b.taps != 9) || b.dil > 1) return fail(MAGNET_E_DIM, "%s: taps=%d dil=%d (taps 1 or 9, no dilation)", who, b.taps, b.dil);
+    if (b.cout_pad <= 0 || b.cout_pad % 128 != 0) return fail(MAGNET_E_DIM, "%s: cout_pad=%d must be a multiple of 128", who, b.cout_pad);
+    if (b.out_mode != 0 && b.out_mode != 1 && b.out_mode != 3)
+        return fail(MAGNET_E_DIM, "%s: out_mode=%d (0: split-bf16 planes, 1: fp32, 3: one fp16 plane)", who, b.out_mode);
+    return 0;
+}
+
+MAGNET_API int magnet_conv_mfma_f16d(const MagnetConvExArgs* a, void* stream) {
+    if (const int rc = conv_f16d_check(a, "magnet_conv_mfma_f16d")) return rc;
+    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream, CONV_F16D);
+}
+
+MAGNET_API int64_t magnet_conv_mfma_f16d_splitk_workspace(const MagnetConvExArgs* a, int32_t split_k) {
+    int64_t bytes = 0;
+    int rc = conv_f16d_check(a, "magnet_conv_mfma_f16d_splitk");
+    if (!rc) rc = conv_splitk_check(a, split_k, &bytes, "magnet_conv_mfma_f16d_splitk", true);
+    return rc ? -(int64_t)rc : bytes;
+}
+
+MAGNET_API int magnet_conv_mfma_f16d_splitk(const MagnetConvExArgs* a, int32_t split_k, float* work, int64_t work_bytes, void* stream) {
+    int64_t bytes = 0;
+    if (const int rc = conv_f16d_check(a, "magnet_conv_mfma_f16d_splitk")) return rc;
+    if (const int rc = conv_splitk_check(a, split_k, &bytes, "magnet_conv_mfma_f16d_splitk", true)) return rc;
+    if (const int rc = conv_splitk_call_check(a, work, work_bytes, bytes, "magnet_conv_mfma_f16d_splitk")) return rc;
+    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream, CONV_F16D, split_k, work);
 }
 
 MAGNET_API int magnet_pack_f16(const float* nchw, void* out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,

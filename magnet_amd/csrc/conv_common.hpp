@@ -103,6 +103,9 @@ hipError_t launch_conv_mfma_f16p(const ConvParams&, hipStream_t);      // the sa
                                                                        // plane (add_lo unused), out_mode 3 = one fp16 plane at out_hi
 // split-K over S input-channel ranges: the partials into work (S x rows x cout_pad fp32), then the fixed-order reduce + epilogue launch
 hipError_t launch_conv_mfma_splitk(const ConvParams&, int S, float* work, hipStream_t);
+// the D-Net decoder's wide plane-to-plane layers (cout_pad % 128 == 0, LeakyReLU, out_mode 0 / 1 / 3) and their split-K form
+hipError_t launch_conv_mfma_f16d(const ConvParams&, hipStream_t);
+hipError_t launch_conv_mfma_f16d_splitk(const ConvParams&, int S, float* work, hipStream_t);
 hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
 hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
                            hipStream_t s);

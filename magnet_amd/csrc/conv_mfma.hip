@@ -367,7 +367,10 @@ struct ConvLds {
 // F16P = "plane to plane" (magnet_conv_mfma_f16p, the F-Net): F16 operands, and in the plain epilogue the residual input is ONE fp16
 // plane (add_hi) and out_mode 3 writes ONE fp16 plane (out_hi).  Besides the two WIN == 2 loops it runs the windowless loop at the
 // bottom with one fp16 MFMA per fragment pair (taps 1 and 4), and the 4-wave WIN == 2 loop at BN = 32 (one weight piece per wave).
-// SPLITK = the split-K form (magnet_conv_mfma_splitk): workgroup sk_z of sk_n runs the K loop over the input-channel chunks
+// The decoder's wide instances (magnet_conv_mfma_f16d, the D-Net's plain layers) are F16 && F16P at 128 rows x 128 channels with
+// gridDim.y = cout_pad / 128 channel blocks: the same two loops (WIN == 2 for 3x3, WIN == 0 for 1x1); their epilogue also takes LeakyReLU
+// and the split-bf16 output (out_mode 0), which this template serves for every plain instance.
+// SPLITK = the split-K form (magnet_conv_mfma_splitk; on fp16 planes magnet_conv_mfma_f16d_splitk): workgroup sk_z of sk_n runs the K loop over the input-channel chunks
 // [floor(sk_z C / sk_n), floor((sk_z + 1) C / sk_n)) of the C = cin / 32 chunks, all taps — the chunk range, the activation channel offset
 // and the weight offset change (the weight row pitch stays cin); the step order and the ring schedule are the plain loop's — and stores
 // its raw fp32 accumulator tile to sk_work[sk_z][row][cout_pad], rows < p.rows: no bias, activation or border logic (the reduce kernel's).
@@ -381,7 +384,8 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                                                                             // parameter is a generic pointer, and its casts to LDS pointers get null checks)
     using L = ConvLds<NF, WN, CV_BM, SPB, NT, PP, WIN, F16>;
     static_assert(!F16P || (F16 && TAIL == 0 && !PP), "plane to plane: fp16 operands, plain epilogue, 4 waves");
-    static_assert(!SPLITK || (!F16 && TAIL == 0 && !PP && NT == 256 && (WIN == 2 || WIN == 0)), "split-K: the two 4-wave bf16x3 loops, no tail");
+    static_assert(!SPLITK || ((!F16 || F16P) && TAIL == 0 && !PP && NT == 256 && (WIN == 2 || WIN == 0)),
+                  "split-K: the two 4-wave loops (bf16x3, or fp16 plane to plane), no tail");
     constexpr int BN = L::BN, A_BYTES = L::A_BYTES, B_BYTES = L::B_BYTES;
     constexpr int RP = NT / 4;                      // tile rows filled by one DMA instruction per wave set (4 lanes per 64-byte row)
     constexpr int A_PT = CV_BM / RP;                           // 16-byte vectors per thread per A plane (1, 2 or 4)
@@ -638,6 +642,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         const int aw = CV_BM + 2 * p.tap_sx;
         const int ngroups = 3 * ksteps_per_tap;               // (K chunk, ty) pairs, ty inner
         StepCounter gw, bs;
+        if constexpr (SPLITK) gw.k0 = bs.k0 = sk_c0 * CV_BK;  // the range's first channel (magnet_conv_mfma_f16d_splitk), as in the bf16x3 loop below
         auto dma_a = [&]() { stage_window(win_slot(0), a_step(gw.i, 0, gw.k0), aw); gw.advance(3); };
         // BN = 32: row 8 w + (lane >> 2) of the tile; 8 w is a multiple of 8, so the swizzle term of st_k (from row 16 w + (lane >> 2)) is this row's
         [[maybe_unused]] const int b_v32 = ((n0 + (wave_row >> 1) + (lane >> 2)) * p.cin + st_k) * 2;
@@ -1256,6 +1261,17 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_splitk_kernel(const ConvPara
     conv_mfma_tile<8, 2, 128, 1, 0, 256, false, WIN, false, false, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x, work, blockIdx.z, gridDim.z);
 }
 
+// The D-Net decoder's wide fp16 instances (magnet_conv_mfma_f16d): plane to plane at 128 rows x 128 channels, blockIdx.y = the channel
+// block; and their split-K form (magnet_conv_mfma_f16d_splitk).  Kernels of their own name again
+template <int WIN>
+__global__ __launch_bounds__(256, 2) void conv_mfma_f16d_kernel(const ConvParams p) {
+    conv_mfma_tile<8, 2, 128, 1, 0, 256, false, WIN, true, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
+}
+template <int WIN>
+__global__ __launch_bounds__(256, 2) void conv_mfma_f16d_splitk_kernel(const ConvParams p, float* __restrict__ work) {
+    conv_mfma_tile<8, 2, 128, 1, 0, 256, false, WIN, true, true, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x, work, blockIdx.z, gridDim.z);
+}
+
 // out = epilogue(((p_0 + p_1) + p_2 ... ) + bias): the fixed-order fp32 sum of the S partials work[z][row][cout_pad], then what the plain
 // epilogue applies — ReLU / LeakyReLU, zeros at border positions, repad re-addressing, out_ld channel slices — as split-bf16 planes
 // (out_mode 0) or fp32 (out_mode 1).  One thread = 8 channels of one row: 16-byte loads and stores, no LDS.
@@ -1299,6 +1315,64 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
         if (!interior) v[i] = 0.f;
     }
     const size_t e = (size_t)orow * p.out_ld + ch;
+    if (p.out_mode == 0) {
+        uint32_t h[4], l[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) split_bf16x2(v[2 * i], v[2 * i + 1], h[i], l[i]);
+        *reinterpret_cast<uint4*>(p.out_hi + e) = make_uint4(h[0], h[1], h[2], h[3]);
+        *reinterpret_cast<uint4*>(p.out_lo + e) = make_uint4(l[0], l[1], l[2], l[3]);
+    } else {
+        *reinterpret_cast<float4*>(p.out_f32 + e) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(p.out_f32 + e + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
+}
+
+// The reduce of magnet_conv_mfma_f16d_splitk: conv_splitk_reduce_kernel's statements, and out_mode 3 (one fp16 plane at out_hi) besides.
+// A kernel of its own and a copy, not a shared body: behind a shared inlined body the bf16x3 reduce above compiled to other code.
+__global__ __launch_bounds__(256) void conv_splitk_reduce_f16_kernel(const ConvParams p, const float* __restrict__ work, const int S) {
+    const int c8n = p.cout_pad / 8;
+    const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long row = it / c8n;
+    if (row >= p.rows) return;
+    const int ch = (int)(it - row * c8n) * 8;
+    long long orow = row;
+    bool interior = true;
+    if (p.img_rows) {
+        const long long img = row / p.img_rows;
+        const int rem = (int)(row - img * p.img_rows), y = rem / p.wp, x = rem - y * p.wp;
+        interior = (y >= p.pad) && (y < p.hp - p.pad) && (x >= p.pad) && (x < p.wp - p.pad);
+        if (p.repad) {
+            if (!interior) return;
+            const int q = p.repad - 1, hh = p.hp - 2 * p.pad, ww = p.wp - 2 * p.pad;
+            orow = (img * (hh + 2 * q) + (y - p.pad + q)) * (ww + 2 * q) + (x - p.pad + q);
+        }
+    }
+    const size_t plane = (size_t)p.rows * p.cout_pad;
+    const float* src = work + (size_t)row * p.cout_pad + ch;
+    float4 q0[8], q1[8];                                      // every partial's loads are issued before the first addition
+#pragma unroll
+    for (int z = 0; z < 8; ++z)
+        if (z < S) { q0[z] = *reinterpret_cast<const float4*>(src + z * plane); q1[z] = *reinterpret_cast<const float4*>(src + z * plane + 4); }
+    float v[8] = {q0[0].x, q0[0].y, q0[0].z, q0[0].w, q1[0].x, q1[0].y, q1[0].z, q1[0].w};
+#pragma unroll
+    for (int z = 1; z < 8; ++z)
+        if (z < S) {
+            v[0] += q0[z].x; v[1] += q0[z].y; v[2] += q0[z].z; v[3] += q0[z].w;
+            v[4] += q1[z].x; v[5] += q1[z].y; v[6] += q1[z].z; v[7] += q1[z].w;
+        }
+    const float4 b0 = *reinterpret_cast<const float4*>(p.bias + ch), b1 = *reinterpret_cast<const float4*>(p.bias + ch + 4);
+    const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float x = v[i] + bv[i];
+        v[i] = (x < 0.f) ? (p.relu ? 0.f : (p.leaky ? x * p.leaky_slope : x)) : x;
+        if (!interior) v[i] = 0.f;
+    }
+    const size_t e = (size_t)orow * p.out_ld + ch;
+    if (p.out_mode == 3) {                                    // one fp16 plane, saturating RNE (f16_bits_sat), as the plain epilogue's
+        *reinterpret_cast<uint4*>(p.out_hi + e) = f16x8_pack_sat(v);
+        return;
+    }
     if (p.out_mode == 0) {
         uint32_t h[4], l[4];
 #pragma unroll
@@ -1479,6 +1553,48 @@ hipError_t launch_conv_mfma_f16p(const ConvParams& p, hipStream_t s) {
     if (p.cout_pad == 64)  return launch_conv_nf<4, 1, 128, 1, 0, 256, false, 0, true, true>(p, s);
     if (p.cout_pad == 32)  return launch_conv_nf<2, 1, 128, 1, 0, 256, false, 0, true, true>(p, s);
     return hipErrorInvalidValue;
+}
+
+// The D-Net decoder's plain layers on fp16 planes (magnet_conv_mfma_f16d): taps 9 / 1, any cout_pad % 128 == 0 (blockIdx.y = the channel
+// block), LeakyReLU, fp16 / fp32 / split-bf16 output.  The API has refused everything else.  128-row tiles, 4 waves, flat tiling.
+template <int WIN>
+static hipError_t launch_f16d(const ConvParams& p, hipStream_t s) {
+    const size_t lds = conv_lds_bytes<8, 2, 128, 1, 256, false, WIN, true>();     // 33 280 / 32 768 bytes: no opt-in attribute
+    static_assert(ConvLds<8, 2, 128, 1, 256, false, WIN, true>::TOTAL <= 64 * 1024, "dynamic LDS within the default limit");
+    hipLaunchKernelGGL(conv_mfma_f16d_kernel<WIN>, dim3((unsigned)((p.rows + 127) / 128), (unsigned)(p.cout_pad / 128)), dim3(256), lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_mfma_f16d(const ConvParams& p_in, hipStream_t s) {
+    if (p_in.tail_w_hi || p_in.addend || p_in.add_hi || p_in.in_sc || (p_in.tiling & ~1) || p_in.cout_pad % 128 != 0 || (p_in.tap_n != 3 && p_in.tap_n != 1))
+        return hipErrorInvalidValue;
+    ConvParams p = p_in;
+    p.tiles_per_img = 0;
+    if (p.tiles_out) *p.tiles_out = (p.rows + 127) / 128;
+    return p.tap_n == 3 ? launch_f16d<2>(p, s) : launch_f16d<0>(p, s);
+}
+
+// Its split-K form (magnet_conv_mfma_f16d_splitk): launch_conv_mfma_splitk's two launches on the fp16 loops; the reduce also writes out_mode 3
+template <int WIN>
+static hipError_t launch_f16d_splitk_partials(const ConvParams& p, int S, float* work, hipStream_t s) {
+    const size_t lds = conv_lds_bytes<8, 2, 128, 1, 256, false, WIN, true>();
+    hipLaunchKernelGGL(conv_mfma_f16d_splitk_kernel<WIN>, dim3((unsigned)((p.rows + 127) / 128), (unsigned)(p.cout_pad / 128), (unsigned)S), dim3(256),
+                       lds, s, p, work);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_mfma_f16d_splitk(const ConvParams& p_in, int S, float* work, hipStream_t s) {
+    if (p_in.tail_w_hi || p_in.addend || p_in.add_hi || p_in.in_sc || (p_in.tiling & ~1) || p_in.cout_pad % 128 != 0 ||
+        (p_in.tap_n != 3 && p_in.tap_n != 1) || S < 2 || S > 8 || !work)
+        return hipErrorInvalidValue;
+    ConvParams p = p_in;
+    p.tiles_per_img = 0;
+    if (p.tiles_out) *p.tiles_out = (p.rows + 127) / 128;
+    const hipError_t e = p.tap_n == 3 ? launch_f16d_splitk_partials<2>(p, S, work, s) : launch_f16d_splitk_partials<0>(p, S, work, s);
+    if (e != hipSuccess) return e;
+    const long long items = p.rows * (p.cout_pad / 8);
+    hipLaunchKernelGGL(conv_splitk_reduce_f16_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, work, S);
+    return hipGetLastError();
 }
 
 // =====================================================================================================

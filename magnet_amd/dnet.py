@@ -24,9 +24,18 @@ Three things live here:
   Under "auto" the factor S of a launch depends on its tile count, so the bits of one image can differ between batch sizes — by the
   order of S - 1 fp32 additions per output only; with a forced dict {layer: S} they do not.  SequenceRunner's bit-equality with
   MAGNET.forward holds when both ran the same factors.
+  `DNetMFMA(decoder, precision="fp16")` (opt-in; default "bf16x3") runs conv2 and up1.0 .. up3.1 on the single-plane fp16 format
+  (magnet_conv_mfma_f16d, one matrix instruction per product instead of three): the folded weights are rounded once to fp16, every
+  activation buffer between conv2 and up3's second convolution is ONE zero-bordered fp16 plane (magnet_pack_f16,
+  magnet_upsample_bilinear_cl_f16, out_mode 3), the compact hand-overs to the bilinear upsampling stay fp32 and x_feat leaves as the
+  split-bf16 planes (or NCHW fp32) of the default mode, so the heads, G-Net and SequenceRunner see today's formats.  A reduced-precision
+  mode: |activation| and |folded weight| <= 65504 — activation stores clamp (NaN passes through), a larger folded weight raises at
+  pack time; relative rounding 2^-11 per stored value.  It composes with split_k (magnet_conv_mfma_f16d_splitk).  Measured in
+  profiles/dnet_precision/NOTES.md.
 """
 from __future__ import annotations
 
+import contextlib
 import zlib
 
 import numpy as np
@@ -36,7 +45,7 @@ import torch.nn.functional as F
 
 from . import lib
 from .convnet import ConvStackMFMA
-from .planes import PackCache, fold_bn, pack_taps, planes, round_up, timed
+from .planes import PackCache, fold_bn, pack_taps, pack_taps_f16, plane_f16, planes, round_up, timed
 
 # (block, skip feature index, skip channels, output channels) at downsample ratio 4 (D_dense_depth.py:130-135,176-180)
 _UP = (("up1", 8, 176, 1024), ("up2", 6, 64, 512), ("up3", 5, 40, 256))
@@ -45,6 +54,8 @@ SPLIT_LAYERS = ("conv2", "up1.0", "up1.1", "up2.0", "up2.1", "up3.0", "up3.1")  
 # constants of the "auto" rule (split_factor), from the sweep in profiles/splitk/NOTES.md
 SPLIT_CUS = 256                                            # a launch with a workgroup per CU is not split; a split fills at most one per CU ...
 SPLIT_SLOTS = 512                                          # ... or, from half the CUs on, the resident slots (two 4-wave workgroups per CU)
+PRECISIONS = ("bf16x3", "fp16")                            # DNetMFMA(precision=...): the decoder's operand format
+F16_MAX = 65504.0                                          # largest finite fp16: the domain of precision="fp16"
 SPLIT_AUTO_MIN_CHUNKS = 4                                  # 32-channel chunks per split under "auto" (>= lib.SPLITK_MIN_CHUNKS): the
                                                            # shortest split the sweep still saw pay (up2.1 at S = 4)
 
@@ -67,6 +78,13 @@ def split_factor(row_tiles, n_tiles, cin_chunks):
         s = min(2, SPLIT_SLOTS // wg)
     s = min(s, lib.SPLITK_MAX, int(cin_chunks) // max(SPLIT_AUTO_MIN_CHUNKS, lib.SPLITK_MIN_CHUNKS))
     return s if s >= 2 else 1
+
+
+def check_precision(precision, who="DNetMFMA", what="precision"):
+    """'bf16x3' or 'fp16'; MagnetError otherwise."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise lib.MagnetError(f"{who}: {what} must be 'bf16x3' or 'fp16', got {precision!r}")
+    return precision
 
 
 def check_split_k(split_k, who="DNetMFMA"):
@@ -176,9 +194,11 @@ class DNET(nn.Module):
     (EfficientNet-B5's, or magnet_amd.standin.StandinEncoder).
     backend: 'torch' (default) runs the modules as they are; 'hip' runs the decoder, the heads and the tail of an eval-mode forward on
     DNetMFMA (the caller's encoder stays a torch module); in .train() the torch forward runs, as MAGNET does for its D-Net.
-    split_k: DNetMFMA's split-K mode (0 = off, "auto", or {layer: S}); needs backend='hip'."""
+    split_k: DNetMFMA's split-K mode (0 = off, "auto", or {layer: S}); needs backend='hip'.
+    precision: DNetMFMA's operand format, 'bf16x3' (default) or 'fp16' (reduced precision, opt-in: see DNetMFMA); 'fp16' needs
+    backend='hip'; in .train() the torch forward runs whatever the value."""
 
-    def __init__(self, args, encoder: nn.Module, dnet: bool = False, backend: str = "torch", split_k=0):
+    def __init__(self, args, encoder: nn.Module, dnet: bool = False, backend: str = "torch", split_k=0, precision: str = "bf16x3"):
         super().__init__()
         self.args = args
         if getattr(args, "output_type", "G") != "G":
@@ -194,9 +214,12 @@ class DNET(nn.Module):
         split_k = check_split_k(split_k, "DNET")
         if split_k != 0 and backend != "hip":
             raise lib.MagnetError("DNET: split_k is a mode of the HIP decoder path: it needs backend='hip'")
+        self.precision = check_precision(precision, "DNET")
+        if precision == "fp16" and backend != "hip":
+            raise lib.MagnetError("DNET: precision='fp16' is a mode of the HIP decoder path: it needs backend='hip'")
         if backend == "hip":
             check_decoder(self.d_net.decoder, standalone=dnet)
-            self._runner = DNetMFMA(self.d_net.decoder, split_k=split_k)
+            self._runner = DNetMFMA(self.d_net.decoder, split_k=split_k, precision=precision)
 
     def forward(self, img, upsample=True):
         if not upsample:
@@ -283,9 +306,14 @@ class DNetMFMA:
     # every convolution launch appends (start_event, end_event, flops) when set to a list (tools/bench_dnet.py)
     event_sink = None
 
-    def __init__(self, decoder: nn.Module, split_k=0):
+    def __init__(self, decoder: nn.Module, split_k=0, precision: str = "bf16x3"):
+        """precision: 'bf16x3' (default: split-bf16 planes, three matrix instructions per product, fp32-grade) or 'fp16' (conv2 and
+        up1.0 .. up3.1 on one fp16 plane per buffer, one matrix instruction per product; reduced precision, |activation| <= 65504 or
+        clamped, a folded weight beyond 65504 raises when the weights are packed)."""
         check_decoder(decoder)
         self.decoder = decoder
+        self.precision = check_precision(precision)
+        self.launch_log = []                                        # (layer, entry point) of every convolution launch of the last run
         self.split_k = check_split_k(split_k)                       # 0 = off (default), "auto" = split_factor per launch, {layer: S} = forced
         self.factors_used = []                                      # (layer, rows, S) of every covered launch of the last run
         self.slope = float(decoder.up1._net[2].negative_slope)
@@ -307,7 +335,7 @@ class DNetMFMA:
         self._head_work = {}
 
     def packed(self, device):
-        self._packed = self._cache.get(device, lambda: self._pack(device))
+        self._packed = self._cache.get(device, lambda: self._pack(device), self.precision)   # one pack per precision
         return self._packed
 
     @torch.no_grad()
@@ -315,8 +343,20 @@ class DNetMFMA:
         d = self.decoder
         P = {}
 
+        f16 = self.precision == "fp16"
+
         def put(name, w, b, cin_pad):
-            hi, lo = pack_taps(w.to(device), cin_pad)
+            if f16:
+                # the fp64 fold, cast to fp32, rounded ONCE to fp16; a weight outside fp16's range is an error, never a silent clamp.
+                # The check runs on a host copy of the folded weights (a decoder that lives on the GPU is copied once per pack)
+                wf = w.float()
+                peak = float(wf.detach().abs().max().cpu()) if wf.numel() else 0.0
+                if not peak <= F16_MAX:
+                    raise lib.MagnetError(f"DNetMFMA {name}: folded weight magnitude {peak:.6g} is outside fp16's range (|w| <= {F16_MAX:.0f}): "
+                                          "precision='fp16' cannot hold this decoder; use precision='bf16x3'")
+                hi, lo = pack_taps_f16(wf.to(device), cin_pad), None
+            else:
+                hi, lo = pack_taps(w.to(device), cin_pad)
             P[name] = (hi, lo, b.float().to(device).contiguous(), hi.shape[0], cin_pad)
 
         put("conv2", d.conv2.weight.detach().double(), d.conv2.bias.detach().double(), 2048)
@@ -332,6 +372,11 @@ class DNetMFMA:
         hi, lo, bias, taps, cin = self._packed[name]
         cout = hi.shape[1]
         # every operand must hold what the launch touches (planes may be row / channel views of wider buffers)
+        f16 = self.precision == "fp16"
+        if f16:                                                     # ONE fp16 plane where the default mode has a (hi, lo) pair
+            src = (src,)
+            if dst is not None and not isinstance(dst, tuple):
+                dst = (dst,)
         for t in src:
             if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) != in_ld or t.shape[0] < rows or t.shape[1] < cin:
                 raise lib.MagnetError(f"DNetMFMA {name}: input view {tuple(t.shape)} / pitch {t.stride(0)} does not hold {rows} x {cin} at {in_ld}")
@@ -354,18 +399,37 @@ class DNetMFMA:
         if S > 1:
             # one workspace for all launches (stream-ordered: a layer's reduce has read it before the next layer's partials are written),
             # kept with the per-shape buffers and grown on demand
-            need = lib.conv_mfma_splitk_workspace(rows, cin, cout, taps, S) // 4
+            need = lib.conv_mfma_splitk_workspace(rows, cin, cout, taps, S, f16="wide" if f16 else False) // 4
             work = self._bufs.get("splitk.work")
             if work is None or work.numel() < need:
                 work = self._bufs["splitk.work"] = torch.empty(need, dtype=torch.float32, device=src[0].device)
-        with timed(DNetMFMA.event_sink, 2.0 * rows * cin * taps * cout):
-            lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, False, rows,
-                          out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1], out_f32=out_f32, out_ld=out_ld,
-                          border=border, repad=repad, leaky=None if name == "conv2" else self.slope,
-                          split_k=S if S > 1 else None, work=work)
+        leaky = None if name == "conv2" else self.slope
+        with self._logged(name), timed(DNetMFMA.event_sink, 2.0 * rows * cin * taps * cout):
+            if f16:
+                # dst of one plane: the fp16 plane (out_mode 3); of two: the split-bf16 pair (out_mode 0: x_feat)
+                lib.conv_mfma(src[0], None, in_ld, cin, hi, None, bias, taps, wp, False, rows,
+                              out_hi=None if dst is None else dst[0], out_lo=None if dst is None or len(dst) == 1 else dst[1], out_f32=out_f32,
+                              out_ld=out_ld, border=border, repad=repad, leaky=leaky, f16="wide", split_k=S if S > 1 else None, work=work)
+            else:
+                lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, taps, wp, False, rows,
+                              out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1], out_f32=out_f32, out_ld=out_ld,
+                              border=border, repad=repad, leaky=leaky,
+                              split_k=S if S > 1 else None, work=work)
+
+    @contextlib.contextmanager
+    def _logged(self, layer):
+        """The convolution entry points lib calls inside the block are appended to launch_log as (layer, entry point)."""
+        prev, lib.entry_log = lib.entry_log, []
+        try:
+            yield
+        finally:
+            got, lib.entry_log = lib.entry_log, prev
+            self.launch_log += [(layer, e) for e in got if e.startswith("magnet_conv_mfma")]
+            if prev is not None:
+                prev += got
 
     def _buffers(self, dev, N, dims):
-        sig = (str(dev), N, dims)
+        sig = (str(dev), N, dims, self.precision)
         if self._bufs_sig == sig:
             return self._bufs
         self._bufs.clear()                                          # one shape at a time: the buffers are large
@@ -375,12 +439,14 @@ class DNetMFMA:
         (h32, w32), (h16, w16), (h8, w8), (h4, w4) = dims
         r = lambda h, w: N * (h + 2) * (w + 2)
         b = self._bufs
-        b["x4"] = planes(r(h32, w32), 2048, dev, zero=True)
+        # precision="fp16": ONE fp16 plane for every buffer the decoder's convolutions read; `feat` (x_feat, the heads' input) stays split-bf16
+        act = plane_f16 if self.precision == "fp16" else planes
+        b["x4"] = act(r(h32, w32), 2048, dev, zero=True)
         b["d0"] = torch.empty((N * h32 * w32, 2048), dtype=torch.float32, device=dev)
         cin = 2048
         for (name, _, skip_c, cout), (h, w) in zip(_UP, ((h16, w16), (h8, w8), (h4, w4))):
-            b[name + ".in"] = planes(r(h, w), round_up(cin + skip_c, 32), dev, zero=True)     # [upsampled | skip | zero pad], zero border
-            b[name + ".mid"] = planes(r(h, w), cout, dev, zero=True)
+            b[name + ".in"] = act(r(h, w), round_up(cin + skip_c, 32), dev, zero=True)        # [upsampled | skip | zero pad], zero border
+            b[name + ".mid"] = act(r(h, w), cout, dev, zero=True)
             if name != "up3":
                 b[name + ".out"] = torch.empty((N * h * w, cout), dtype=torch.float32, device=dev)
             cin = cout
@@ -410,11 +476,16 @@ class DNetMFMA:
         """conv2 and up1..up3 up to the input planes of up3's second convolution (buffers()["up3.mid"]); returns the buffer dict."""
         (h32, w32) = dims[0]
         self.factors_used = []
+        self.launch_log = []
         self.packed(dev)
         b = self._buffers(dev, N, dims)
 
         # conv2 (1x1 2048 -> 2048, no activation; D_dense_depth.py:177) -> compact fp32 for the bilinear upsampling
-        lib.pack_split(xs[_SKIP_IN], b["x4"][0], b["x4"][1], 2048, 0)
+        f16 = self.precision == "fp16"
+        if f16:
+            lib.pack_f16(xs[_SKIP_IN], b["x4"], 2048, 0)
+        else:
+            lib.pack_split(xs[_SKIP_IN], b["x4"][0], b["x4"][1], 2048, 0)
         wp = w32 + 2
         self._conv("conv2", b["x4"], 2048, wp, N * (h32 + 2) * wp, out_f32=b["d0"], border=(h32 + 2, 1), repad=1)
         prev, ph, pw, pc = b["d0"], h32, w32, 2048
@@ -422,9 +493,13 @@ class DNetMFMA:
             h, w = xs[idx].shape[2:]
             wp, rows = w + 2, N * (h + 2) * (w + 2)
             cat = b[name + ".in"]
-            cat_ld = cat[0].shape[1]
-            lib.upsample_bilinear_cl(prev, pc, ph, pw, pc, cat[0], cat[1], cat_ld, N, h, w, 1)     # channels [0, pc)
-            lib.pack_split(xs[idx], cat[0], cat[1], cat_ld, pc)                                    # channels [pc, pc + skip_c)
+            cat_ld = cat.shape[1] if f16 else cat[0].shape[1]
+            if f16:
+                lib.upsample_bilinear_cl_f16(prev, pc, ph, pw, pc, cat, cat_ld, N, h, w, 1)        # channels [0, pc)
+                lib.pack_f16(xs[idx], cat, cat_ld, pc)                                             # channels [pc, pc + skip_c)
+            else:
+                lib.upsample_bilinear_cl(prev, pc, ph, pw, pc, cat[0], cat[1], cat_ld, N, h, w, 1)     # channels [0, pc)
+                lib.pack_split(xs[idx], cat[0], cat[1], cat_ld, pc)                                    # channels [pc, pc + skip_c)
             self._conv(name + ".0", cat, cat_ld, wp, rows, dst=b[name + ".mid"], border=(h + 2, 1))
             if name != "up3":
                 self._conv(name + ".1", b[name + ".mid"], cout, wp, rows, out_f32=b[name + ".out"], border=(h + 2, 1), repad=1)
@@ -465,7 +540,7 @@ class DNetMFMA:
         else:
             n_ref = 0
         if N > n_ref:
-            src = (mid[0][n_ref * img_rows:], mid[1][n_ref * img_rows:])
+            src = mid[n_ref * img_rows:] if self.precision == "fp16" else (mid[0][n_ref * img_rows:], mid[1][n_ref * img_rows:])
             dst = (b["feat"][0][n_ref * img_rows:], b["feat"][1][n_ref * img_rows:])
             self._conv("up3.1", src, 256, wp, (N - n_ref) * img_rows, dst=dst, border=(h + 2, 1))
             parts.append((n_ref, N - n_ref, dst, 256))
@@ -474,7 +549,7 @@ class DNetMFMA:
             if any(t.stride(0) != ld or t.shape[0] < n * img_rows or t.shape[1] < 256 for t in (fhi, flo)):
                 raise lib.MagnetError(f"DNetMFMA: depth-head input view {tuple(fhi.shape)} does not hold {n * img_rows} x 256 at pitch {ld}")
             work = self._head_work.setdefault(n, {})
-            with timed(DNetMFMA.event_sink, 2.0 * n * img_rows * (9 * 256 * 128 + 128 * 128 + 128 * 2)):
+            with timed(DNetMFMA.event_sink, 2.0 * n * img_rows * (9 * 256 * 128 + 128 * 128 + 128 * 2)), self._logged("depth_head"):
                 out, out_ld = self._head.run(fhi, flo, ld, n * img_rows, wp, work)
             lib.dnet_gauss_head(out, out_ld, n, h, w, 1, mono[first:first + n])
         if x_d3_out is not None:
@@ -504,7 +579,7 @@ class DNetMFMA:
         sink = DNetMFMA.event_sink
         outs = []
         for stack, work, cout in ((self._head, self._head_work, 2), (self._mask, self._mask_work, 144)):
-            with timed(sink, 2.0 * rows * (9 * 256 * 128 + 128 * 128 + 128 * cout)):
+            with timed(sink, 2.0 * rows * (9 * 256 * 128 + 128 * 128 + 128 * cout)), self._logged("depth_head" if cout == 2 else "mask_head"):
                 outs.append(stack.run(feat[0], feat[1], 256, rows, wp, work.setdefault(N, {})))
         (head, head_ld), (mask, mask_ld) = outs
         out = torch.empty((N, 2, 4 * h, 4 * w), dtype=torch.float32, device=dev)

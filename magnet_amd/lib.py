@@ -267,6 +267,9 @@ _PROTOS = {
     "magnet_conv_mfma_f16p": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_conv_mfma_splitk_workspace": (_L, [_S(MagnetConvExArgs), _I]),
     "magnet_conv_mfma_splitk": (_C, [_S(MagnetConvExArgs), _I, _P, _L, _P]),
+    "magnet_conv_mfma_f16d": (_C, [_S(MagnetConvExArgs), _P]),
+    "magnet_conv_mfma_f16d_splitk_workspace": (_L, [_S(MagnetConvExArgs), _I]),
+    "magnet_conv_mfma_f16d_splitk": (_C, [_S(MagnetConvExArgs), _I, _P, _L, _P]),
     "magnet_pack_f16": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
     "magnet_planes_to_f16": (_C, [_P, _P, _I, _P, _I, _L, _I, _I, _P]),
     "magnet_fnet_stem_f16": (_C, [_P, _P, _P, _P, _I, _I, _I, _P]),
@@ -351,9 +354,14 @@ def _stream(t) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(getattr(t, "device", t)).cuda_stream)
 
 
+entry_log = None                # when set to a list: _launch appends the name of every entry point it calls (DNetMFMA.launch_log)
+
+
 def _launch(name: str, on, *args):
     """Call the entry point `name` with `args` and, as its last argument, the current stream of `on` (a tensor or a
     torch.device), with that device current; a non-zero return raises MagnetError."""
+    if entry_log is not None:
+        entry_log.append(name)
     with torch.cuda.device(getattr(on, "device", on)):
         _check(getattr(load(), name)(*args, _stream(on)), name)
 
@@ -620,10 +628,15 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     128, dil, border, repad and channel slices as in the default format; no tail, addend, mx or leaky.
     split_k = S (2 .. SPLITK_MAX) with work = a float32 GPU tensor of at least conv_mfma_splitk_workspace(...) bytes: the split-K form
     (magnet_conv_mfma_splitk) of the plain bf16x3 layer, taps 1 / 9, cout_pad % 128 == 0, out_hi / out_lo or out_f32; not with f16, tail,
-    addend, add or mx.  Returns the row tile count."""
+    addend, add or mx.  Returns the row tile count.
+    f16 = "wide": the same operand format, plane to plane at any cout_pad % 128 == 0 (magnet_conv_mfma_f16d, the D-Net decoder's plain
+    layers): taps 1 / 9, relu or leaky, border, repad and channel slices; the output is out_f16 (passed as out_hi with out_lo None),
+    out_f32 or the split-bf16 pair out_hi / out_lo; no tail, addend, add, mx, dil or out_bf16.  split_k / work are allowed on this route
+    (magnet_conv_mfma_f16d_splitk).  Returns the row tile count."""
+    wide = isinstance(f16, str) and f16 == "wide"
     if split_k is not None:
-        if f16 or tail is not None or addend is not None or add is not None or mx is not None:
-            raise MagnetError("conv_mfma (split_k): the plain bf16x3 layer only — not with f16, tail, addend, add or mx")
+        if (f16 and not wide) or tail is not None or addend is not None or add is not None or mx is not None:
+            raise MagnetError("conv_mfma (split_k): the plain bf16x3 layer (or f16='wide') only — not with f16=True / 'plane', tail, addend, add or mx")
         if isinstance(split_k, bool) or not isinstance(split_k, int):
             raise MagnetError(f"conv_mfma: split_k must be an int, got {split_k!r}")
         if not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous():
@@ -631,14 +644,16 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     elif work is not None:
         raise MagnetError("conv_mfma: work goes with split_k")
     a = MagnetConvArgs()
-    plane = f16 == "plane"
-    if f16 not in (False, True, "plane"):
-        raise MagnetError(f"conv_mfma: f16 must be False, True or 'plane', got {f16!r}")
+    plane = isinstance(f16, str) and f16 == "plane"
+    if f16 not in (False, True, "plane", "wide"):
+        raise MagnetError(f"conv_mfma: f16 must be False, True, 'plane' or 'wide', got {f16!r}")
+    if wide and (tail is not None or addend is not None or add is not None or out_bf16 is not None or dil):
+        raise MagnetError("conv_mfma (f16='wide'): the plain layer — no tail, addend, add, out_bf16 or dil")
     if plane and (tail is not None or addend is not None or out_lo is not None or (add is not None and add[1] is not None)):
         raise MagnetError("conv_mfma (f16='plane'): one fp16 plane per buffer — out_lo and add[1] must be None; no tail, no addend")
     if f16:
-        if in_lo is not None or w_lo is not None or mx is not None or leaky is not None:
-            raise MagnetError("conv_mfma (f16): one fp16 plane per operand — in_lo, w_lo, mx and leaky must be None")
+        if in_lo is not None or w_lo is not None or mx is not None or (leaky is not None and not wide):
+            raise MagnetError("conv_mfma (f16): one fp16 plane per operand — in_lo, w_lo, mx and leaky (but for f16='wide') must be None")
         for t, n in ((in_hi, "in_hi"), (w_hi, "w_hi")):
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float16:
                 raise MagnetError(f"conv_mfma (f16): {n} must be an fp16 GPU tensor")
@@ -696,7 +711,7 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_f32 = 1, out_f32.data_ptr()
     elif out_bf16 is not None:
         a.out_mode, a.out_hi = 2, _bf16_ptr(out_bf16, "out_bf16")
-    elif plane:
+    elif plane or (wide and out_lo is None):
         a.out_mode, a.out_hi = 3, _f16_ptr(out_hi, "out_hi (fp16 plane)")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
@@ -707,20 +722,25 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
     if split_k is not None:
-        _launch("magnet_conv_mfma_splitk", in_hi, ctypes.byref(x), int(split_k), work.data_ptr(), work.numel() * 4)
+        _launch("magnet_conv_mfma_f16d_splitk" if wide else "magnet_conv_mfma_splitk", in_hi, ctypes.byref(x), int(split_k), work.data_ptr(),
+                work.numel() * 4)
         return tiles.value
-    _launch("magnet_conv_mfma_f16p" if plane else "magnet_conv_mfma_f16" if f16 else "magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
+    _launch("magnet_conv_mfma_f16d" if wide else "magnet_conv_mfma_f16p" if plane else "magnet_conv_mfma_f16" if f16 else "magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
     return tiles.value
 
 
-def conv_mfma_splitk_workspace(rows, cin, cout_pad, taps, split_k):
+def conv_mfma_splitk_workspace(rows, cin, cout_pad, taps, split_k, f16=False):
     """magnet_conv_mfma_splitk_workspace: the bytes of `work` for a split-K launch of this shape (split_k x rows x cout_pad fp32);
-    MagnetError for a form the entry point refuses.  Host arithmetic: needs the library, not a GPU."""
+    MagnetError for a form the entry point refuses.  f16 = "wide": the query of magnet_conv_mfma_f16d_splitk (conv_mfma(f16="wide",
+    split_k=...)).  Host arithmetic: needs the library, not a GPU."""
+    if not (f16 is False or (isinstance(f16, str) and f16 == "wide")):
+        raise MagnetError(f"conv_mfma_splitk_workspace: f16 must be False or 'wide', got {f16!r}")
+    name = "magnet_conv_mfma_f16d_splitk_workspace" if f16 else "magnet_conv_mfma_splitk_workspace"
     x = MagnetConvExArgs()
     x.base.rows, x.base.cin, x.base.cout_pad, x.base.taps, x.base.out_mode = int(rows), int(cin), int(cout_pad), int(taps), 1
-    nbytes = int(load().magnet_conv_mfma_splitk_workspace(ctypes.byref(x), int(split_k)))
+    nbytes = int(getattr(load(), name)(ctypes.byref(x), int(split_k)))
     if nbytes < 0:
-        _check(-nbytes, "magnet_conv_mfma_splitk_workspace")
+        _check(-nbytes, name)
     return nbytes
 
 

@@ -130,11 +130,18 @@ class MAGNET(nn.Module):
     `dnet_split_k`: 0 (default, off), 'auto' or {layer: S}: DNetMFMA's split-K mode for the decoder's plain layers at one to a few
     images (magnet_amd/dnet.py, profiles/splitk/NOTES.md); needs dnet_backend='hip'.  Under 'auto' the factor depends on the batch's
     tile count, so an image's bits can differ between batch sizes by fp32 summation order; SequenceRunner's bit-equality with forward()
-    holds when both ran the same factors."""
+    holds when both ran the same factors.
+    `dnet_precision`: 'bf16x3' (default) or 'fp16', the operand format of the HIP D-Net decoder (DNetMFMA(decoder, precision=...)):
+    'fp16' runs conv2 and up1.0 .. up3.1 on ONE fp16 plane per buffer with one matrix instruction per product; the heads, x_d3 and
+    everything behind the decoder keep their formats.  Needs dnet_backend='hip'; independent of `conv_precision` and `fnet_precision`;
+    composes with `dnet_split_k`.  A reduced-precision inference mode the caller opts into, measured in
+    profiles/dnet_precision/NOTES.md: activations beyond +-65504 are clamped (encoder features included), a folded weight beyond it
+    raises when the weights are packed.  In .train() the D-Net's torch forward runs as before."""
 
     def __init__(self, args, d_net: nn.Module | None = None, f_net: nn.Module | None = None,
                  feat_dtype: str = "fp32", conv_backend: str = "mfma", train_backend: str = "torch", dnet_backend: str = "torch",
-                 conv_precision: str = "bf16x3", fnet_precision: str = "bf16x3", dnet_split_k=0):
+                 conv_precision: str = "bf16x3", fnet_precision: str = "bf16x3", dnet_split_k=0,
+                 dnet_precision: str = "bf16x3"):
         super().__init__()
         self.args = args
         if d_net is None or f_net is None:
@@ -194,10 +201,13 @@ class MAGNET(nn.Module):
             raise lib.MagnetError(f"dnet_backend must be 'torch' or 'hip', got {dnet_backend!r}")
         self.dnet_backend = dnet_backend
         self._dnet = None
-        from .dnet import check_split_k
+        from .dnet import check_precision, check_split_k
         self.dnet_split_k = check_split_k(dnet_split_k, "MAGNET (dnet_split_k)")
         if self.dnet_split_k != 0 and dnet_backend != "hip":
             raise lib.MagnetError("dnet_split_k is a mode of the HIP D-Net decoder: it needs dnet_backend='hip'")
+        self.dnet_precision = check_precision(dnet_precision, "MAGNET", "dnet_precision")
+        if dnet_precision == "fp16" and dnet_backend != "hip":
+            raise lib.MagnetError("dnet_precision='fp16' is a mode of the HIP D-Net decoder: it needs dnet_backend='hip'")
         if dnet_backend == "hip":
             if conv_backend != "mfma":
                 raise lib.MagnetError("dnet_backend='hip' runs the D-Net decoder on the matrix-core path: it needs conv_backend='mfma'")
@@ -213,7 +223,7 @@ class MAGNET(nn.Module):
             if getattr(d_net, "dnet", False):
                 raise lib.MagnetError("dnet_backend='hip' needs the D-Net built with dnet=False (mean, sigma and x_feat at 1/4)")
             from .dnet import DNetMFMA
-            self._dnet = DNetMFMA(inner.decoder, split_k=self.dnet_split_k)          # checks the decoder: BatchNorm, LeakyReLU, 2-output head
+            self._dnet = DNetMFMA(inner.decoder, split_k=self.dnet_split_k, precision=self.dnet_precision)   # checks the decoder: BatchNorm, LeakyReLU, 2-output head
         self._work = {}                # cached device workspaces of the MFMA conv path, keyed by shape
         self.fuse_upsample = True      # the stacks' tails finish the job: G-Net's head applies the Gaussian update, the mask head
                                        # writes the upsampled predictions itself (no (B,144,h,w) mask in HBM); False: separate launches

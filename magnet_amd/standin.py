@@ -101,14 +101,14 @@ def make_dnet_args(downsample_ratio=4):
                            DNET_fix_encoder_weights="None")
 
 
-def make_dnet(seed=0, enc_seed=0, depth_prior=True, dnet=False, backend="torch", split_k=0):
+def make_dnet(seed=0, enc_seed=0, depth_prior=True, dnet=False, backend="torch", split_k=0, precision="bf16x3"):
     """magnet_amd.dnet.DNET with the stand-in encoder and seeded decoder weights (magnet_amd.dnet.seeded_decoder_state), in eval mode.
-    dnet=False: MaGNet's D-Net; dnet=True: the stand-alone D-Net (img -> (N, 2, H, W) [mu, variance]); backend, split_k: see DNET.
+    dnet=False: MaGNet's D-Net; dnet=True: the stand-alone D-Net (img -> (N, 2, H, W) [mu, variance]); backend, split_k, precision: see DNET.
     depth_prior: the depth head's last layer is scaled by 1/4 and its bias set to (2.5, -3) so that the stand-in predicts
     plausible scenes for the matcher, mu around 2.5 m (+-1.5) and sigma around 0.2 m (StubDNet's ranges); the raw recipe's mu is
     centred on zero, where depth candidates cross the camera plane."""
     from .dnet import DNET, load_seeded_decoder
-    d = DNET(make_dnet_args(), StandinEncoder(enc_seed), dnet=dnet, backend=backend, split_k=split_k)
+    d = DNET(make_dnet_args(), StandinEncoder(enc_seed), dnet=dnet, backend=backend, split_k=split_k, precision=precision)
     load_seeded_decoder(d.d_net.decoder, seed)
     if depth_prior:
         with torch.no_grad():

@@ -17,9 +17,17 @@ and 352 x 1216 with N = 1, 3, and prints what dnet.split_factor would choose.  -
 process, of DNetMFMA(split_k=0) against DNetMFMA(split_k="auto") for run_standalone and run at N = 1 (both shapes) and N = 4, checks that
 split_k=0 gives the default runner's bits and reports how far "auto" is from them.
 
+--precision fp16 --pairs P times P interleaved pairs, in this process, of DNetMFMA(precision="bf16x3") against DNetMFMA(precision="fp16")
+for run and run_standalone, each with split_k 0 and "auto", at 480 x 640 with N = 1, 5, 20 and 352 x 1216 with N = 1, 3, with the
+per-launch event times of both; then x_feat / mu / sigma of both modes against a float64 decoder at C2 (N = 5) and KITTI (N = 3), the
+peak activation and folded-weight magnitudes (the headroom to 65504), and MAGNET.forward's final depth at C2 / I = 3 under
+dnet_precision 'fp16' against the default mode and against the torch decoder, per refinement.  Every line carries the SHA-256 of the
+default mode's outputs, so two builds can be compared on the default path.
+
     python tools/bench_dnet.py [--steps 10] [--warmup 3] [--out profiles/dnet/bench_dnet.jsonl]
     python tools/bench_dnet.py --split_k sweep [--repeats 7] [--out profiles/splitk/bench_splitk.jsonl]
     python tools/bench_dnet.py --split_k auto --pairs 12 [--steps 20] [--out profiles/splitk/bench_splitk.jsonl]
+    python tools/bench_dnet.py --precision fp16 --pairs 12 [--steps 20] [--out profiles/dnet_precision/bench_dnet_precision.jsonl]
     python tools/bench_dnet.py --standalone [--steps 20] [--warmup 5] [--repeats 5] [--out profiles/dnet/bench_dnet_standalone.jsonl]
 """
 import argparse
@@ -44,6 +52,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--split_k", default=None, choices=["sweep", "auto"])
     ap.add_argument("--pairs", type=int, default=12)
+    ap.add_argument("--precision", default=None, choices=["fp16"])
     a = ap.parse_args()
     from magnet_amd import fnet, lib, synth
     from magnet_amd.dnet import DNetMFMA, gaussian_activation
@@ -77,6 +86,124 @@ def main():
             with open(a.out, "a") as fh:
                 for d_ in lines:
                     fh.write(json.dumps(d_) + "\n")
+
+    if a.precision:
+        import copy
+        import hashlib
+        import statistics
+        from magnet_amd.planes import fold_bn
+        d = make_dnet(dnet=True).to(dev)
+        dec = d.d_net.decoder
+
+        def sha(*ts):
+            h = hashlib.sha256()
+            for t in ts:
+                h.update(t.detach().contiguous().cpu().numpy().tobytes())
+            return h.hexdigest()[:16]
+
+        def once(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / a.steps
+
+        def launches_ms(runner, feats):
+            """median event time of every bracketed launch of run_standalone, keyed by launch_log's layer names (+ the tail kernel)"""
+            per = []
+            for _ in range(a.repeats + 2):
+                sink = []
+                DNetMFMA.event_sink = sink
+                runner.run_standalone(feats)
+                torch.cuda.synchronize()
+                DNetMFMA.event_sink = None
+                per.append([e0.elapsed_time(e1) for e0, e1, _ in sink])
+            names = [l for l, _ in runner.launch_log] + ["upsample_gauss"]
+            return {n: round(statistics.median(col), 4) for n, col in zip(names, zip(*per[2:]))}
+
+        for name, H, W, N in (("C2", 480, 640, 1), ("C2", 480, 640, 5), ("C2", 480, 640, 20), ("KITTI", 352, 1216, 1), ("KITTI", 352, 1216, 3)):
+            with torch.no_grad():
+                feats = d.d_net.encoder(images(N, H, W, N))
+                for sk in (0, "auto"):
+                    r3, r16 = DNetMFMA(dec, split_k=sk), DNetMFMA(dec, split_k=sk, precision="fp16")
+                    o3, o16 = r3.run_standalone(feats), r16.run_standalone(feats)
+                    g3, f3 = r3.run(feats)
+                    used = {n: S for n, _, S in r16.factors_used}
+                    for form, f_3, f_16 in (("run_standalone", lambda: r3.run_standalone(feats), lambda: r16.run_standalone(feats)),
+                                            ("run", lambda: r3.run(feats), lambda: r16.run(feats))):
+                        for _ in range(a.warmup):
+                            f_3(); f_16()
+                        t3, t16 = [], []
+                        for _ in range(a.pairs):
+                            t3.append(once(f_3)); t16.append(once(f_16))
+                        emit(dict(bench="dnet_precision_pairs", shape=name, H=H, W=W, N=N, form=form, split_k=sk, pairs=a.pairs, steps=a.steps,
+                                  factors=used, ms_bf16x3=[round(t, 4) for t in t3], ms_fp16=[round(t, 4) for t in t16],
+                                  median_bf16x3=round(statistics.median(t3), 4), median_fp16=round(statistics.median(t16), 4),
+                                  fp16_faster_pairs=sum(b < a_ for a_, b in zip(t3, t16)),
+                                  sha_default_standalone=sha(o3), sha_default_run=sha(g3, f3),
+                                  standalone_rel_diff_to_default=float((o16.double() - o3.double()).abs().max() / o3.double().abs().max())))
+                    emit(dict(bench="dnet_precision_layers", shape=name, H=H, W=W, N=N, split_k=sk, factors=used,
+                              ms_bf16x3=launches_ms(r3, feats), ms_fp16=launches_ms(r16, feats)))
+                    del r3, r16, o3, o16, g3, f3
+            del feats
+            torch.cuda.empty_cache()
+
+        # accuracy against a float64 decoder, seeded weights; headroom to 65504
+        rel = lambda x, y: float((x.double() - y.double()).abs().max() / y.double().abs().max())
+        dm = make_dnet().to(dev)
+        decm = dm.d_net.decoder
+        for name, H, W, N in (("C2", 480, 640, 5), ("KITTI", 352, 1216, 3)):
+            with torch.no_grad():
+                feats = dm.d_net.encoder(images(N, H, W, N))
+                dec64 = copy.deepcopy(decm).double().eval()
+                ref_g, ref_f = gaussian_activation(dec64([None if f is None else f.double() for f in feats]))
+                del dec64
+                out = {}
+                for prec in ("bf16x3", "fp16"):
+                    r = DNetMFMA(decm, precision=prec)
+                    g, f = r(feats)
+                    out[prec] = dict(x_feat=rel(f, ref_f), mu=rel(g[:, 0], ref_g[:, 0]), sigma=rel(g[:, 1], ref_g[:, 1]))
+                    if prec == "fp16":
+                        b = r._bufs
+                        peaks = {k: float(v.float().abs().max()) for k, v in b.items() if isinstance(v, torch.Tensor) and k != "splitk.work"}
+                emit(dict(bench="dnet_precision_accuracy", shape=name, H=H, W=W, N=N, rel_to_fp64=out, peak_activation=peaks,
+                          peak_encoder_feature=max(float(feats[i].abs().max()) for i in (5, 6, 8, 11))))
+            del feats, ref_g, ref_f
+            torch.cuda.empty_cache()
+        wmax = {"conv2": float(decm.conv2.weight.abs().max())}
+        for up in ("up1", "up2", "up3"):
+            net = getattr(decm, up)._net
+            wmax[up + ".0"] = float(fold_bn(net[0], net[1])[0].abs().max())
+            wmax[up + ".1"] = float(fold_bn(net[3], net[4])[0].abs().max())
+        emit(dict(bench="dnet_precision_weights", peak_folded_weight=wmax, limit=65504.0))
+
+        # MAGNET.forward at C2 / I = 3: final depth per refinement, fp16 decoder against the default HIP decoder and the torch decoder
+        args = make_args(D=64, iters=3, dpv_h=120, dpv_w=160, fdim=64, V=4)
+        args.FNET_architecture, args.FNET_feature_dim = "PSM-Net", 64
+        torch.manual_seed(0)
+        f = fnet.FNET(args)
+        wl = synth.Workload("C2", "scannet", 120, 160, V=4, D=64, iters=3)
+        inp = synth.make_inputs(wl, B=1, seed=5)
+        ref_img, nb = images(1, 480, 640, 1), images(4, 480, 640, 2)
+        poses = inp["nghbr_poses"].to(dev)
+        preds, ms = {}, {}
+        for key, kw in (("torch", dict(dnet_backend="torch")), ("hip", dict(dnet_backend="hip")),
+                        ("hip_fp16", dict(dnet_backend="hip", dnet_precision="fp16"))):
+            model = MAGNET(args, d_net=dm, f_net=f, **kw).to(dev).eval()
+            seeded_magnet_weights(model, seed=4)
+            with torch.no_grad():
+                preds[key] = [p.clone() for p in model(ref_img, nb, poses, inp["is_valid"], inp["cam_intrins"], mode="test")]
+                ms[key] = timed(lambda: model(ref_img, nb, poses, inp["is_valid"], inp["cam_intrins"], mode="test"))
+            del model
+            torch.cuda.empty_cache()
+        abs_rel = lambda x, y: [float(((g[:, 0] - r[:, 0]).abs() / r[:, 0].abs()).mean()) for g, r in zip(x, y)]
+        emit(dict(bench="dnet_precision_magnet", shape="C2", B=1, V=4, D=64, iters=3, ms_forward=ms,
+                  abs_rel_fp16_vs_default_hip=abs_rel(preds["hip_fp16"], preds["hip"]),
+                  abs_rel_fp16_vs_torch=abs_rel(preds["hip_fp16"], preds["torch"]),
+                  abs_rel_default_hip_vs_torch=abs_rel(preds["hip"], preds["torch"]), sha_default_hip=sha(*preds["hip"])))
+        write_out()
+        return
 
     if a.split_k:
         import statistics
