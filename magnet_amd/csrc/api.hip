@@ -303,15 +303,12 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_upsample_depth launch");
 }
 
-// magnet_conv_mfma and magnet_conv_mfma_ex: leaky != 0 selects LeakyReLU(leaky_slope) after bias (validated by the _ex entry point)
-// mode: the operand format.  CONV_BF16X3: (hi, lo) planes (or the fp16 + e4m3 format).  CONV_F16: the single-plane fp16 operand format
-// (magnet_conv_mfma_f16, which has checked what that format serves): no lo planes.  CONV_F16P: the same operands, plane to plane
-// (magnet_conv_mfma_f16p): the residual is ONE fp16 plane (add_lo NULL) and out_mode 3 (one fp16 plane at out_hi) exists
-// CONV_F16D: plane to plane, wide (magnet_conv_mfma_f16d, the D-Net decoder's plain layers): no residual; out_mode 0, 1 or 3
-enum { CONV_BF16X3 = 0, CONV_F16 = 1, CONV_F16P = 2, CONV_F16D = 3 };
-// split_k >= 2 (magnet_conv_mfma_splitk, which has checked what that form serves): the split-K launches with workspace `work`
-static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, void* stream, int mode = CONV_BF16X3,
-                         int split_k = 0, float* work = nullptr) {
+// Every convolution entry point ends here: the checks of the common fields, then the launch on `mode` (magnet::ConvRoute, conv_common.hpp).
+// leaky != 0 selects LeakyReLU(leaky_slope) after bias (validated by the entry point)
+// split_k >= 2 (the split-K entry points, which have checked what that form serves): the split-K launches with workspace `work`; else 0
+using magnet::ConvRoute; using magnet::CONV_BF16X3; using magnet::CONV_F16; using magnet::CONV_F16P; using magnet::CONV_F16D;
+static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, int split_k, float* work,
+                         void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
     const bool f16 = mode != CONV_BF16X3;
     if (!a->in_hi || (!f16 && !a->in_lo) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
@@ -413,25 +410,54 @@ static int conv_mfma_run(const MagnetConvArgs* a, int leaky, float leaky_slope, 
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
-    hipError_t e = mode == CONV_F16D ? (split_k ? magnet::launch_conv_mfma_f16d_splitk(p, split_k, work, (hipStream_t)stream)
-                                                : magnet::launch_conv_mfma_f16d(p, (hipStream_t)stream))
-                 : split_k          ? magnet::launch_conv_mfma_splitk(p, split_k, work, (hipStream_t)stream)
-                 : mode == CONV_F16P ? magnet::launch_conv_mfma_f16p(p, (hipStream_t)stream)
-                 : mode == CONV_F16  ? magnet::launch_conv_mfma_f16(p, (hipStream_t)stream) : magnet::launch_conv_mfma(p, (hipStream_t)stream);
+    const hipError_t e = magnet::launch_conv(p, mode, split_k, work, (hipStream_t)stream);
     if (tiles_out) *tiles_out = tiles;
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv_mfma launch");
 }
 
-MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) { return conv_mfma_run(a, 0, 0.f, 0, nullptr, stream); }
+// conv_mfma_run with the activation, tiling and tiles_out of an _ex argument struct (whose entry point has checked them)
+static int conv_mfma_run(const MagnetConvExArgs* a, ConvRoute mode, int split_k, float* work, void* stream) {
+    return conv_mfma_run(&a->base, mode, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, split_k, work, stream);
+}
+
+// The checks that several entry points (`who`) make, each stated once: 0, or the MAGNET_E_* code with the message set.
+// The activation: act is known, LeakyReLU excludes relu (excludes_tail: and the fused tail) and takes a finite slope
+static int conv_act_check(const MagnetConvExArgs* a, const char* who, bool excludes_tail) {
+    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "%s: act=%d unknown", who, a->act);
+    if (a->act == MAGNET_ACT_LEAKY_RELU) {
+        if (a->base.relu || (excludes_tail && a->base.tail_w_hi))
+            return fail(MAGNET_E_DIM, excludes_tail ? "%s: LeakyReLU excludes relu and the fused tail" : "%s: LeakyReLU excludes relu", who);
+        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f) return fail(MAGNET_E_DIM, "%s: act_slope must be finite", who);
+    }
+    return 0;
+}
+
+// The single-plane fp16 routes: planes of another format (bf16x3 lo planes, fp16 + e4m3 scales) are refused rather than mis-read.
+// res_planes: the residual planes the route takes.  1: ONE fp16 plane at add_hi (add_lo NULL); 0: no residual input (both NULL);
+// 2: add_hi / add_lo are not this check's matter (magnet_conv_mfma_f16 refuses them with its border and repad forms)
+static int conv_f16_planes_check(const MagnetConvArgs& b, const char* who, int res_planes) {
+    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc || (res_planes < 2 && b.add_lo) || (res_planes < 1 && b.add_hi))
+        return fail(MAGNET_E_DIM, "%s: in_lo, w_lo, in_sc%s must be NULL (every operand is ONE fp16 plane)", who,
+                    res_planes == 0 ? ", w_sc, add_hi and add_lo" : res_planes == 1 ? ", w_sc and add_lo" : " and w_sc");
+    return 0;
+}
+
+// The plain layer on 128-row tiles only: no fused tail, addend, Gaussian update or upsampling; excludes_planes: no residual input or e4m3 format either
+static int conv_plain_check(const MagnetConvExArgs* a, const char* who, const char* format, bool excludes_planes) {
+    const MagnetConvArgs& b = a->base;
+    if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", who, a->tiling);
+    if (b.tail_w_hi || b.tail_w_lo || b.addend || b.up_out || b.up_depth || b.gu_in || b.gu_out ||
+        (excludes_planes && (b.add_hi || b.add_lo || b.in_sc || b.w_sc)))
+        return fail(MAGNET_E_DIM, "%s: the plain %s layer only (no fused tail, addend, %sGaussian update or upsampling)", who, format,
+                    excludes_planes ? "residual input, e4m3 format, " : "");
+    return 0;
+}
+
+MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) { return conv_mfma_run(a, CONV_BF16X3, 0, 0.f, 0, nullptr, 0, nullptr, stream); }
 
 MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_ex: args is NULL");
-    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: act=%d unknown", a->act);
-    if (a->act == MAGNET_ACT_LEAKY_RELU) {
-        if (a->base.relu || a->base.tail_w_hi) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: LeakyReLU excludes relu and the fused tail");
-        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
-            return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: act_slope must be finite");
-    }
+    if (const int rc = conv_act_check(a, "magnet_conv_mfma_ex", true)) return rc;
     if (a->tiling & ~(MAGNET_TILING_FLAT | MAGNET_TILING_BM256 | MAGNET_TILING_BM64)) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: tiling=%d unknown", a->tiling);
     if (a->tiling & MAGNET_TILING_BM64) {                            // the 64-row instances: 3x3, 128-wide, bf16x3 operands
         const MagnetConvArgs& b = a->base;
@@ -440,15 +466,13 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
             return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: MAGNET_TILING_BM64 serves 3x3 launches (taps == 9) with cout_pad == 128 and a fused tail, or plain "
                                       "with cout_pad %% 128 == 0, bf16x3 operands only (taps=%d cout_pad=%d)", b.taps, b.cout_pad);
     }
-    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream);
+    return conv_mfma_run(a, CONV_BF16X3, 0, nullptr, stream);
 }
 
 MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs* a, void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_f16: args is NULL");
     const MagnetConvArgs& b = a->base;
-    // a caller that passes bf16x3 (or fp16 + e4m3) planes by mistake is refused rather than mis-read
-    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc)
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: in_lo, w_lo, in_sc and w_sc must be NULL (in_hi / w_hi are the only operand planes, fp16)");
+    if (const int rc = conv_f16_planes_check(b, "magnet_conv_mfma_f16", 2)) return rc;
     if (a->act != MAGNET_ACT_BASE) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: act=%d (MAGNET_ACT_BASE only)", a->act);
     if (a->tiling & ~(MAGNET_TILING_FLAT | MAGNET_TILING_BM256))
         return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: tiling=%d (MAGNET_TILING_FLAT and MAGNET_TILING_BM256 only)", a->tiling);
@@ -457,39 +481,46 @@ MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs* a, void* stream) {
     if (b.add_hi || b.add_lo || b.border_hp || b.repad) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: no residual input, border or repad form");
     if (b.tail_w_hi ? (b.tail_cout_pad != 16 && b.tail_cout_pad != 144) : b.out_mode != 1)
         return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16: a fused tail of 16 or 144 outputs, or the plain layer with fp32 output (out_mode 1)");
-    return conv_mfma_run(&a->base, 0, 0.f, a->tiling, a->tiles_out, stream, CONV_F16);
+    return conv_mfma_run(a, CONV_F16, 0, nullptr, stream);
 }
 
 MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs* a, void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_f16p: args is NULL");
     const MagnetConvArgs& b = a->base;
-    // planes of another format are refused rather than mis-read
-    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc || b.add_lo)
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: in_lo, w_lo, in_sc, w_sc and add_lo must be NULL (in_hi / w_hi / add_hi are single fp16 planes)");
+    if (const int rc = conv_f16_planes_check(b, "magnet_conv_mfma_f16p", 1)) return rc;
     if (a->act != MAGNET_ACT_BASE) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: act=%d (MAGNET_ACT_BASE only)", a->act);
-    if (a->tiling & ~MAGNET_TILING_FLAT)
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", a->tiling);
-    if (b.tail_w_hi || b.tail_w_lo || b.addend || b.up_out || b.up_depth || b.gu_in || b.gu_out)
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: no fused tail, addend, Gaussian update or upsampling");
-    if (b.cout_pad != 32 && b.cout_pad != 64 && b.cout_pad != 128)
-        return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: cout_pad=%d (32, 64 or 128)", b.cout_pad);
-    return conv_mfma_run(&a->base, 0, 0.f, a->tiling, a->tiles_out, stream, CONV_F16P);
+    if (const int rc = conv_plain_check(a, "magnet_conv_mfma_f16p", "fp16", false)) return rc;
+    if (b.cout_pad != 32 && b.cout_pad != 64 && b.cout_pad != 128) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: cout_pad=%d (32, 64 or 128)", b.cout_pad);
+    return conv_mfma_run(a, CONV_F16P, 0, nullptr, stream);
 }
 
-// What the split-K form serves (both entry points): 0, or the MAGNET_E_* code with the message set.  *bytes: the workspace size.
-// f16d: the form on fp16 planes (magnet_conv_mfma_f16d_splitk, `who`): the same limits, and out_mode 3 exists.
-static int conv_splitk_check(const MagnetConvExArgs* a, int32_t split_k, int64_t* bytes, const char* who = "magnet_conv_mfma_splitk", bool f16d = false) {
+// What magnet_conv_mfma_f16d and its split-K form serve (`who`), before conv_mfma_run's checks of the common fields
+static int conv_f16d_check(const MagnetConvExArgs* a, const char* who) {
     if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
     const MagnetConvArgs& b = a->base;
+    if (const int rc = conv_f16_planes_check(b, who, 0)) return rc;
+    if (const int rc = conv_act_check(a, who, false)) return rc;
+    if (const int rc = conv_plain_check(a, who, "fp16", false)) return rc;
+    if ((b.taps != 1 && b.taps != 9) || b.dil > 1) return fail(MAGNET_E_DIM, "%s: taps=%d dil=%d (taps 1 or 9, no dilation)", who, b.taps, b.dil);
+    if (b.cout_pad <= 0 || b.cout_pad % 128 != 0) return fail(MAGNET_E_DIM, "%s: cout_pad=%d must be a multiple of 128", who, b.cout_pad);
+    if (b.out_mode != 0 && b.out_mode != 1 && b.out_mode != 3)
+        return fail(MAGNET_E_DIM, "%s: out_mode=%d (0: split-bf16 planes, 1: fp32, 3: one fp16 plane)", who, b.out_mode);
+    return 0;
+}
+
+// What the split-K form serves (both entry points and their workspace queries): 0, or the MAGNET_E_* code with the message set.
+// *bytes: the workspace size.  f16d: the form on fp16 planes: conv_f16d_check first (out_mode 3 exists there), then the same limits
+static const char* conv_splitk_who(bool f16d) { return f16d ? "magnet_conv_mfma_f16d_splitk" : "magnet_conv_mfma_splitk"; }
+static int conv_splitk_check(const MagnetConvExArgs* a, int32_t split_k, int64_t* bytes, bool f16d) {
+    const char* who = conv_splitk_who(f16d);
+    if (f16d) { if (const int rc = conv_f16d_check(a, who)) return rc; }
+    else if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
+    const MagnetConvArgs& b = a->base;
     if (split_k < 2 || split_k > MAGNET_SPLITK_MAX) return fail(MAGNET_E_DIM, "%s: split_k=%d (2 .. %d)", who, split_k, MAGNET_SPLITK_MAX);
-    if (b.tail_w_hi || b.tail_w_lo || b.addend || b.add_hi || b.add_lo || b.in_sc || b.w_sc || b.up_out || b.up_depth || b.gu_in || b.gu_out)
-        return fail(MAGNET_E_DIM, "%s: the plain %s layer only (no fused tail, addend, residual input, e4m3 format, Gaussian update or upsampling)", who,
-                    f16d ? "fp16" : "bf16x3");
-    if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", who, a->tiling);
+    if (const int rc = conv_plain_check(a, who, f16d ? "fp16" : "bf16x3", true)) return rc;
     if (b.taps != 1 && b.taps != 9) return fail(MAGNET_E_DIM, "%s: taps=%d (1 or 9)", who, b.taps);
     if (b.cout_pad <= 0 || b.cout_pad % 128 != 0) return fail(MAGNET_E_DIM, "%s: cout_pad=%d must be a multiple of 128", who, b.cout_pad);
-    if (b.out_mode != 0 && b.out_mode != 1 && !(f16d && b.out_mode == 3))
-        return fail(MAGNET_E_DIM, f16d ? "%s: out_mode=%d (0: split-bf16 planes, 1: fp32, 3: one fp16 plane)" : "%s: out_mode=%d (0: split-bf16 planes, 1: fp32)", who, b.out_mode);
+    if (!f16d && b.out_mode != 0 && b.out_mode != 1) return fail(MAGNET_E_DIM, "%s: out_mode=%d (0: split-bf16 planes, 1: fp32)", who, b.out_mode);
     if (b.rows <= 0 || b.cin <= 0 || (b.cin % 32) != 0) return fail(MAGNET_E_DIM, "%s: rows > 0 and cin %% 32 == 0 required (cin=%d)", who, b.cin);
     if ((b.cin / 32) / split_k < MAGNET_SPLITK_MIN_CHUNKS)
         return fail(MAGNET_E_DIM, "%s: cin=%d gives a split fewer than %d 32-channel chunks at split_k=%d", who, b.cin, MAGNET_SPLITK_MIN_CHUNKS, split_k);
@@ -499,73 +530,36 @@ static int conv_splitk_check(const MagnetConvExArgs* a, int32_t split_k, int64_t
     return 0;
 }
 
-MAGNET_API int64_t magnet_conv_mfma_splitk_workspace(const MagnetConvExArgs* a, int32_t split_k) {
+static int64_t conv_splitk_bytes(const MagnetConvExArgs* a, bool f16d, int32_t split_k) {
     int64_t bytes = 0;
-    const int rc = conv_splitk_check(a, split_k, &bytes);
+    const int rc = conv_splitk_check(a, split_k, &bytes, f16d);
     return rc ? -(int64_t)rc : bytes;
 }
 
-// workspace pointer and activation of a split-K call (both forms), after conv_splitk_check
-static int conv_splitk_call_check(const MagnetConvExArgs* a, const float* work, int64_t work_bytes, int64_t bytes, const char* who) {
+// A split-K call: the form, the workspace pointer, the activation, then the launch
+static int conv_splitk_run(const MagnetConvExArgs* a, bool f16d, int32_t split_k, float* work, int64_t work_bytes, void* stream) {
+    const char* who = conv_splitk_who(f16d);
+    int64_t bytes = 0;
+    if (const int rc = conv_splitk_check(a, split_k, &bytes, f16d)) return rc;
     if (!work) return fail(MAGNET_E_NULL, "%s: work is NULL", who);
     if (!aligned16(work)) return fail(MAGNET_E_ALIGN, "%s: work must be 16-byte aligned", who);
     if (work_bytes < bytes) return fail(MAGNET_E_DIM, "%s: work_bytes=%lld < %lld", who, (long long)work_bytes, (long long)bytes);
-    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "%s: act=%d unknown", who, a->act);
-    if (a->act == MAGNET_ACT_LEAKY_RELU) {
-        if (a->base.relu) return fail(MAGNET_E_DIM, "%s: LeakyReLU excludes relu", who);
-        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f)
-            return fail(MAGNET_E_DIM, "%s: act_slope must be finite", who);
-    }
-    return 0;
+    if (const int rc = conv_act_check(a, who, false)) return rc;
+    return conv_mfma_run(a, f16d ? CONV_F16D : CONV_BF16X3, split_k, work, stream);
 }
 
+MAGNET_API int64_t magnet_conv_mfma_splitk_workspace(const MagnetConvExArgs* a, int32_t split_k) { return conv_splitk_bytes(a, false, split_k); }
 MAGNET_API int magnet_conv_mfma_splitk(const MagnetConvExArgs* a, int32_t split_k, float* work, int64_t work_bytes, void* stream) {
-    int64_t bytes = 0;
-    if (const int rc = conv_splitk_check(a, split_k, &bytes)) return rc;
-    if (const int rc = conv_splitk_call_check(a, work, work_bytes, bytes, "magnet_conv_mfma_splitk")) return rc;
-    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream, CONV_BF16X3, split_k, work);
-}
-
-// What magnet_conv_mfma_f16d and its split-K form serve (`who`), before conv_mfma_run's checks of the common fields
-static int conv_f16d_check(const MagnetConvExArgs* a, const char* who) {
-    if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
-    const MagnetConvArgs& b = a->base;
-    // planes of another format are refused rather than mis-read
-    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc || b.add_hi || b.add_lo)
-        return fail(MAGNET_E_DIM, "%s: in_lo, w_lo, in_sc, w_sc, add_hi and add_lo must be NULL (in_hi / w_hi are single fp16 planes; no residual input)", who);
-    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "%s: act=%d unknown", who, a->act);
-    if (a->act == MAGNET_ACT_LEAKY_RELU) {
-        if (b.relu) return fail(MAGNET_E_DIM, "%s: LeakyReLU excludes relu", who);
-        if (!(a->act_slope == a->act_slope) || a->act_slope > 1e30f || a->act_slope < -1e30f) return fail(MAGNET_E_DIM, "%s: act_slope must be finite", who);
-    }
-    if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", who, a->tiling);
-    if (b.tail_w_hi || b.tail_w_lo || b.addend || b.up_out || b.up_depth || b.gu_in || b.gu_out)
-        return fail(MAGNET_E_DIM, "%s: no fused tail, addend, Gaussian update or upsampling", who);
-    if ((b.taps != 1 && b.taps != 9) || b.dil > 1) return fail(MAGNET_E_DIM, "%s: taps=%d dil=%d (taps 1 or 9, no dilation)", who, b.taps, b.dil);
-    if (b.cout_pad <= 0 || b.cout_pad % 128 != 0) return fail(MAGNET_E_DIM, "%s: cout_pad=%d must be a multiple of 128", who, b.cout_pad);
-    if (b.out_mode != 0 && b.out_mode != 1 && b.out_mode != 3)
-        return fail(MAGNET_E_DIM, "%s: out_mode=%d (0: split-bf16 planes, 1: fp32, 3: one fp16 plane)", who, b.out_mode);
-    return 0;
+    return conv_splitk_run(a, false, split_k, work, work_bytes, stream);
 }
 
 MAGNET_API int magnet_conv_mfma_f16d(const MagnetConvExArgs* a, void* stream) {
     if (const int rc = conv_f16d_check(a, "magnet_conv_mfma_f16d")) return rc;
-    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream, CONV_F16D);
+    return conv_mfma_run(a, CONV_F16D, 0, nullptr, stream);
 }
-
-MAGNET_API int64_t magnet_conv_mfma_f16d_splitk_workspace(const MagnetConvExArgs* a, int32_t split_k) {
-    int64_t bytes = 0;
-    int rc = conv_f16d_check(a, "magnet_conv_mfma_f16d_splitk");
-    if (!rc) rc = conv_splitk_check(a, split_k, &bytes, "magnet_conv_mfma_f16d_splitk", true);
-    return rc ? -(int64_t)rc : bytes;
-}
-
+MAGNET_API int64_t magnet_conv_mfma_f16d_splitk_workspace(const MagnetConvExArgs* a, int32_t split_k) { return conv_splitk_bytes(a, true, split_k); }
 MAGNET_API int magnet_conv_mfma_f16d_splitk(const MagnetConvExArgs* a, int32_t split_k, float* work, int64_t work_bytes, void* stream) {
-    int64_t bytes = 0;
-    if (const int rc = conv_f16d_check(a, "magnet_conv_mfma_f16d_splitk")) return rc;
-    if (const int rc = conv_splitk_check(a, split_k, &bytes, "magnet_conv_mfma_f16d_splitk", true)) return rc;
-    if (const int rc = conv_splitk_call_check(a, work, work_bytes, bytes, "magnet_conv_mfma_f16d_splitk")) return rc;
-    return conv_mfma_run(&a->base, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, stream, CONV_F16D, split_k, work);
+    return conv_splitk_run(a, true, split_k, work, work_bytes, stream);
 }
 
 MAGNET_API int magnet_pack_f16(const float* nchw, void* out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,

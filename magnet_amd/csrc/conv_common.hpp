@@ -6,7 +6,7 @@
 namespace magnet {
 
 struct ConvParams {
-    const uint16_t* in_hi;  const uint16_t* in_lo;    // activations, row 0 of the flattened padded grid (launch_conv_mfma_f16: in_hi / w_hi
+    const uint16_t* in_hi;  const uint16_t* in_lo;    // activations, row 0 of the flattened padded grid (the fp16 routes: in_hi / w_hi
                                                       // are fp16 planes, in_lo / w_lo NULL)
     const uint16_t* w_hi;   const uint16_t* w_lo;     // [taps][cout_pad][cin]
     const float*    bias;                             // [cout_pad]
@@ -97,15 +97,17 @@ struct ChainParams {
     int cout_pad;
 };
 
-hipError_t launch_conv_mfma(const ConvParams&, hipStream_t);
-hipError_t launch_conv_mfma_f16(const ConvParams&, hipStream_t);       // single-plane fp16 operands: in_hi / w_hi fp16, in_lo / w_lo unused
-hipError_t launch_conv_mfma_f16p(const ConvParams&, hipStream_t);      // the same operands, plane to plane (the F-Net): add_hi is ONE fp16 residual
-                                                                       // plane (add_lo unused), out_mode 3 = one fp16 plane at out_hi
-// split-K over S input-channel ranges: the partials into work (S x rows x cout_pad fp32), then the fixed-order reduce + epilogue launch
-hipError_t launch_conv_mfma_splitk(const ConvParams&, int S, float* work, hipStream_t);
-// the D-Net decoder's wide plane-to-plane layers (cout_pad % 128 == 0, LeakyReLU, out_mode 0 / 1 / 3) and their split-K form
-hipError_t launch_conv_mfma_f16d(const ConvParams&, hipStream_t);
-hipError_t launch_conv_mfma_f16d_splitk(const ConvParams&, int S, float* work, hipStream_t);
+// The route of a convolution launch: the operand format and what it serves.  CONV_BF16X3: (hi, lo) planes (or the fp16 + e4m3 format):
+// magnet_conv_mfma and magnet_conv_mfma_ex.  CONV_F16: the single-plane fp16 operand format (magnet_conv_mfma_f16, which has checked
+// what that format serves): no lo planes.  CONV_F16P: the same operands, plane to plane (magnet_conv_mfma_f16p): the residual is ONE
+// fp16 plane (add_lo NULL) and out_mode 3 (one fp16 plane at out_hi) exists.  CONV_F16D: plane to plane, wide (magnet_conv_mfma_f16d,
+// the D-Net decoder's plain layers, cout_pad % 128 == 0, LeakyReLU): no residual; out_mode 0, 1 or 3
+enum ConvRoute { CONV_BF16X3, CONV_F16, CONV_F16P, CONV_F16D };
+
+// One convolution launch on `route`.  split_k = 0: the plain launch.  split_k = S in 2 .. 8 (CONV_BF16X3 and CONV_F16D: magnet_conv_mfma_splitk,
+// magnet_conv_mfma_f16d_splitk): split-K over S input-channel ranges, the partials into work (S x rows x cout_pad fp32), then the
+// fixed-order reduce + epilogue launch.  hipErrorInvalidValue for a (route, split_k) pair or a form that has no kernel instance
+hipError_t launch_conv(const ConvParams&, ConvRoute route, int split_k, float* work, hipStream_t);
 hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
 hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
                            hipStream_t s);

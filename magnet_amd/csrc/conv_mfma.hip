@@ -1274,7 +1274,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_f16d_splitk_kernel(const Con
 
 // out = epilogue(((p_0 + p_1) + p_2 ... ) + bias): the fixed-order fp32 sum of the S partials work[z][row][cout_pad], then what the plain
 // epilogue applies — ReLU / LeakyReLU, zeros at border positions, repad re-addressing, out_ld channel slices — as split-bf16 planes
-// (out_mode 0) or fp32 (out_mode 1).  One thread = 8 channels of one row: 16-byte loads and stores, no LDS.
+// (out_mode 0) or fp32 (out_mode 1); F16OUT (the reduce of magnet_conv_mfma_f16d_splitk): out_mode 3 (one fp16 plane at out_hi) besides.
+// One thread = 8 channels of one row: 16-byte loads and stores, no LDS.
+template <bool F16OUT>
 __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParams p, const float* __restrict__ work, const int S) {
     const int c8n = p.cout_pad / 8;
     const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1315,63 +1317,11 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
         if (!interior) v[i] = 0.f;
     }
     const size_t e = (size_t)orow * p.out_ld + ch;
-    if (p.out_mode == 0) {
-        uint32_t h[4], l[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) split_bf16x2(v[2 * i], v[2 * i + 1], h[i], l[i]);
-        *reinterpret_cast<uint4*>(p.out_hi + e) = make_uint4(h[0], h[1], h[2], h[3]);
-        *reinterpret_cast<uint4*>(p.out_lo + e) = make_uint4(l[0], l[1], l[2], l[3]);
-    } else {
-        *reinterpret_cast<float4*>(p.out_f32 + e) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(p.out_f32 + e + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
-}
-
-// The reduce of magnet_conv_mfma_f16d_splitk: conv_splitk_reduce_kernel's statements, and out_mode 3 (one fp16 plane at out_hi) besides.
-// A kernel of its own and a copy, not a shared body: behind a shared inlined body the bf16x3 reduce above compiled to other code.
-__global__ __launch_bounds__(256) void conv_splitk_reduce_f16_kernel(const ConvParams p, const float* __restrict__ work, const int S) {
-    const int c8n = p.cout_pad / 8;
-    const long long it = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long row = it / c8n;
-    if (row >= p.rows) return;
-    const int ch = (int)(it - row * c8n) * 8;
-    long long orow = row;
-    bool interior = true;
-    if (p.img_rows) {
-        const long long img = row / p.img_rows;
-        const int rem = (int)(row - img * p.img_rows), y = rem / p.wp, x = rem - y * p.wp;
-        interior = (y >= p.pad) && (y < p.hp - p.pad) && (x >= p.pad) && (x < p.wp - p.pad);
-        if (p.repad) {
-            if (!interior) return;
-            const int q = p.repad - 1, hh = p.hp - 2 * p.pad, ww = p.wp - 2 * p.pad;
-            orow = (img * (hh + 2 * q) + (y - p.pad + q)) * (ww + 2 * q) + (x - p.pad + q);
+    if constexpr (F16OUT) {
+        if (p.out_mode == 3) {                                // one fp16 plane, saturating RNE (f16_bits_sat), as the plain epilogue's
+            *reinterpret_cast<uint4*>(p.out_hi + e) = f16x8_pack_sat(v);
+            return;
         }
-    }
-    const size_t plane = (size_t)p.rows * p.cout_pad;
-    const float* src = work + (size_t)row * p.cout_pad + ch;
-    float4 q0[8], q1[8];                                      // every partial's loads are issued before the first addition
-#pragma unroll
-    for (int z = 0; z < 8; ++z)
-        if (z < S) { q0[z] = *reinterpret_cast<const float4*>(src + z * plane); q1[z] = *reinterpret_cast<const float4*>(src + z * plane + 4); }
-    float v[8] = {q0[0].x, q0[0].y, q0[0].z, q0[0].w, q1[0].x, q1[0].y, q1[0].z, q1[0].w};
-#pragma unroll
-    for (int z = 1; z < 8; ++z)
-        if (z < S) {
-            v[0] += q0[z].x; v[1] += q0[z].y; v[2] += q0[z].z; v[3] += q0[z].w;
-            v[4] += q1[z].x; v[5] += q1[z].y; v[6] += q1[z].z; v[7] += q1[z].w;
-        }
-    const float4 b0 = *reinterpret_cast<const float4*>(p.bias + ch), b1 = *reinterpret_cast<const float4*>(p.bias + ch + 4);
-    const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float x = v[i] + bv[i];
-        v[i] = (x < 0.f) ? (p.relu ? 0.f : (p.leaky ? x * p.leaky_slope : x)) : x;
-        if (!interior) v[i] = 0.f;
-    }
-    const size_t e = (size_t)orow * p.out_ld + ch;
-    if (p.out_mode == 3) {                                    // one fp16 plane, saturating RNE (f16_bits_sat), as the plain epilogue's
-        *reinterpret_cast<uint4*>(p.out_hi + e) = f16x8_pack_sat(v);
-        return;
     }
     if (p.out_mode == 0) {
         uint32_t h[4], l[4];
@@ -1387,6 +1337,14 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_f16_kernel(const ConvP
 
 template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
 static size_t conv_lds_bytes() { return ConvLds<NF, WN, BM, SPB, NT, PP, WIN, F16>::TOTAL; }
+
+// > 64 KiB of dynamic LDS needs the opt-in attribute: set once per kernel and process (`done`: the launching instance's static flag)
+static void lds_opt_in(const void* kernel, size_t lds, bool& done) {
+    if (!done && lds > 64 * 1024) {
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        done = true;
+    }
+}
 
 template <int NF, int WN, int BM, int SPB, int TAIL = 0, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false, bool F16P = false>
 static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
@@ -1411,10 +1369,7 @@ static hipError_t launch_conv_nf(const ConvParams& p_in, hipStream_t s) {
         else return &conv_mfma_kernel<NF, WN, BM, SPB, TAIL, NT, PP, WIN>;
     }();
     static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {          // > 64 KiB of dynamic LDS needs the opt-in attribute
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    lds_opt_in(reinterpret_cast<const void*>(kernel), lds, attr_set);
     hipLaunchKernelGGL(kernel, grid, block, lds, s, p);
     return hipGetLastError();
 }
@@ -1430,7 +1385,8 @@ static hipError_t launch_conv_tail(const ConvParams& p, hipStream_t s) {
     }
 }
 
-hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
+// The (hi, lo) plane format (CONV_BF16X3; magnet_conv_mfma and magnet_conv_mfma_ex)
+static hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     // p.variant is 0 in the product library; the dev library takes it from MAGNET_CONV_VARIANT.  Each bit only moves a launch to an
     // instance that other shapes reach anyway: 1 = no row window, 8 = the 2-slot LDS window instead of the register window, 16 = the
     // 4-wave register-window loop where the 8-wave one is the default, 256 / 2048 = the 8-wave loop for addend / split-bf16 launches,
@@ -1487,40 +1443,11 @@ hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-// Split-K (magnet_conv_mfma_splitk; the API has checked the form): S partial launches in one grid (z = the split) into `work`
-// (S x rows x cout_pad fp32), then the reduce launch on the same stream.  No counters, no atomics: two ordinary launches.
-template <int WIN>
-static hipError_t launch_splitk_partials(const ConvParams& p, int S, float* work, hipStream_t s) {
-    const long long n_tiles = (p.rows + 127) / 128;
-    const size_t lds = conv_lds_bytes<8, 2, 128, 1, 256, false, WIN>();
-    void (*const kernel)(const ConvParams, float*) = &conv_mfma_splitk_kernel<WIN>;
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)n_tiles, (unsigned)(p.cout_pad / 128), (unsigned)S), dim3(256), lds, s, p, work);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_mfma_splitk(const ConvParams& p_in, int S, float* work, hipStream_t s) {
-    if (p_in.cout_pad % 128 != 0 || (p_in.tap_n != 3 && p_in.tap_n != 1) || S < 2 || S > 8 || !work) return hipErrorInvalidValue;
-    ConvParams p = p_in;
-    p.tiles_per_img = 0;
-    if (p.tiles_out) *p.tiles_out = (p.rows + 127) / 128;
-    const hipError_t e = p.tap_n == 3 ? launch_splitk_partials<2>(p, S, work, s) : launch_splitk_partials<0>(p, S, work, s);
-    if (e != hipSuccess) return e;
-    const long long items = p.rows * (p.cout_pad / 8);
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, work, S);
-    return hipGetLastError();
-}
-
 // The single-plane fp16 format (magnet_conv_mfma_f16): the launches MAGNET._refine_mfma makes and nothing else — the 3x3 layer with
 // the fused tail of G-Net (16 outputs) or the mask head (144), and the plain 128-wide 3x3 layer with fp32 output (the loop-invariant
 // part of G-Net's first layer).  The API has refused every other form.  Tile selection is launch_conv_mfma's: 256-row 8-wave tiles from
 // 65 536 rows on (or under MAGNET_TILING_BM256), except for the short per-iteration launches that carry an addend.
-hipError_t launch_conv_mfma_f16(const ConvParams& p, hipStream_t s) {
-    if (p.cout_pad != 128 || p.tap_n != 3) return hipErrorInvalidValue;
+static hipError_t launch_conv_mfma_f16(const ConvParams& p, hipStream_t s) {
     const bool big = p.rows >= 256ll * 256 || (p.tiling & 2);
     if (p.tail_w_hi) {
         if (big && !p.addend) {
@@ -1541,8 +1468,7 @@ hipError_t launch_conv_mfma_f16(const ConvParams& p, hipStream_t s) {
 // refused the fused tail, the addend, the e4m3 format and the BM64 / BM256 tilings.  Tiles are chosen as launch_conv_mfma chooses them
 // for the F-Net's launches (which carry img_rows, a residual or a 2-byte output: never the 256-row form): 128 rows, 4 waves; 3x3 on the
 // register-window loop, 1x1 and 2x2 windows on the windowless loop.
-hipError_t launch_conv_mfma_f16p(const ConvParams& p, hipStream_t s) {
-    if (p.tail_w_hi || p.addend || p.in_sc || (p.tiling & ~1)) return hipErrorInvalidValue;
+static hipError_t launch_conv_mfma_f16p(const ConvParams& p, hipStream_t s) {
     if (p.tap_n == 3) {
         if (p.cout_pad == 128) return launch_conv_nf<8, 2, 128, 1, 0, 256, false, 2, true, true>(p, s);
         if (p.cout_pad == 64)  return launch_conv_nf<4, 1, 128, 1, 0, 256, false, 2, true, true>(p, s);
@@ -1555,46 +1481,74 @@ hipError_t launch_conv_mfma_f16p(const ConvParams& p, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-// The D-Net decoder's plain layers on fp16 planes (magnet_conv_mfma_f16d): taps 9 / 1, any cout_pad % 128 == 0 (blockIdx.y = the channel
-// block), LeakyReLU, fp16 / fp32 / split-bf16 output.  The API has refused everything else.  128-row tiles, 4 waves, flat tiling.
-template <int WIN>
-static hipError_t launch_f16d(const ConvParams& p, hipStream_t s) {
-    const size_t lds = conv_lds_bytes<8, 2, 128, 1, 256, false, WIN, true>();     // 33 280 / 32 768 bytes: no opt-in attribute
-    static_assert(ConvLds<8, 2, 128, 1, 256, false, WIN, true>::TOTAL <= 64 * 1024, "dynamic LDS within the default limit");
-    hipLaunchKernelGGL(conv_mfma_f16d_kernel<WIN>, dim3((unsigned)((p.rows + 127) / 128), (unsigned)(p.cout_pad / 128)), dim3(256), lds, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_mfma_f16d(const ConvParams& p_in, hipStream_t s) {
-    if (p_in.tail_w_hi || p_in.addend || p_in.add_hi || p_in.in_sc || (p_in.tiling & ~1) || p_in.cout_pad % 128 != 0 || (p_in.tap_n != 3 && p_in.tap_n != 1))
-        return hipErrorInvalidValue;
+// The fixed tile <8, 2, 128, 1, 0, 256, false, WIN> on the (row tiles, cout_pad / 128[, S]) grid, flat tiling.  S == 0: the plain launch
+// of the D-Net decoder's wide fp16 layers.  S >= 2: the split-K partials of either operand format, S launches in one grid (z = the
+// split) into `work` (S x rows x cout_pad fp32); the (hi, lo) format has no plain launch here (launch_conv_mfma serves it)
+template <bool F16, int WIN>
+static hipError_t launch_wide(const ConvParams& p_in, int S, float* work, hipStream_t s) {
+    if (!F16 && !S) return hipErrorInvalidValue;                   // no plain (hi, lo) instance here; launch_conv never asks for one
     ConvParams p = p_in;
     p.tiles_per_img = 0;
     if (p.tiles_out) *p.tiles_out = (p.rows + 127) / 128;
-    return p.tap_n == 3 ? launch_f16d<2>(p, s) : launch_f16d<0>(p, s);
-}
-
-// Its split-K form (magnet_conv_mfma_f16d_splitk): launch_conv_mfma_splitk's two launches on the fp16 loops; the reduce also writes out_mode 3
-template <int WIN>
-static hipError_t launch_f16d_splitk_partials(const ConvParams& p, int S, float* work, hipStream_t s) {
-    const size_t lds = conv_lds_bytes<8, 2, 128, 1, 256, false, WIN, true>();
-    hipLaunchKernelGGL(conv_mfma_f16d_splitk_kernel<WIN>, dim3((unsigned)((p.rows + 127) / 128), (unsigned)(p.cout_pad / 128), (unsigned)S), dim3(256),
-                       lds, s, p, work);
+    const size_t lds = conv_lds_bytes<8, 2, 128, 1, 256, false, WIN, F16>();     // fp16: 33 280 / 32 768 bytes, no opt-in attribute
+    static_assert(!F16 || ConvLds<8, 2, 128, 1, 256, false, WIN, true>::TOTAL <= 64 * 1024, "dynamic LDS within the default limit");
+    const dim3 grid((unsigned)((p.rows + 127) / 128), (unsigned)(p.cout_pad / 128), (unsigned)(S ? S : 1));
+    if constexpr (F16) {
+        if (!S) {                                                  // the plain launch
+            hipLaunchKernelGGL(conv_mfma_f16d_kernel<WIN>, grid, dim3(256), lds, s, p);
+            return hipGetLastError();
+        }
+    }
+    void (*const kernel)(const ConvParams, float*) = [] {
+        if constexpr (F16) return &conv_mfma_f16d_splitk_kernel<WIN>;
+        else return &conv_mfma_splitk_kernel<WIN>;
+    }();
+    static bool attr_set = false;
+    lds_opt_in(reinterpret_cast<const void*>(kernel), lds, attr_set);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, p, work);
     return hipGetLastError();
 }
 
-hipError_t launch_conv_mfma_f16d_splitk(const ConvParams& p_in, int S, float* work, hipStream_t s) {
-    if (p_in.tail_w_hi || p_in.addend || p_in.add_hi || p_in.in_sc || (p_in.tiling & ~1) || p_in.cout_pad % 128 != 0 ||
-        (p_in.tap_n != 3 && p_in.tap_n != 1) || S < 2 || S > 8 || !work)
-        return hipErrorInvalidValue;
-    ConvParams p = p_in;
-    p.tiles_per_img = 0;
-    if (p.tiles_out) *p.tiles_out = (p.rows + 127) / 128;
-    const hipError_t e = p.tap_n == 3 ? launch_f16d_splitk_partials<2>(p, S, work, s) : launch_f16d_splitk_partials<0>(p, S, work, s);
+// Split-K (magnet_conv_mfma_splitk, magnet_conv_mfma_f16d_splitk; the API has checked the form): the partials, then the reduce launch
+// on the same stream.  No counters, no atomics: two ordinary launches.
+template <bool F16>
+static hipError_t launch_splitk(const ConvParams& p, int S, float* work, hipStream_t s) {
+    const hipError_t e = p.tap_n == 3 ? launch_wide<F16, 2>(p, S, work, s) : launch_wide<F16, 0>(p, S, work, s);
     if (e != hipSuccess) return e;
     const long long items = p.rows * (p.cout_pad / 8);
-    hipLaunchKernelGGL(conv_splitk_reduce_f16_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, work, S);
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel<F16>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, work, S);
     return hipGetLastError();
+}
+
+// The D-Net decoder's plain layers on fp16 planes (magnet_conv_mfma_f16d): taps 9 / 1, any cout_pad % 128 == 0 (blockIdx.y = the channel
+// block), LeakyReLU, fp16 / fp32 / split-bf16 output.  The API has refused everything else.  128-row tiles, 4 waves, flat tiling.
+static hipError_t launch_conv_mfma_f16d(const ConvParams& p, hipStream_t s) {
+    return p.tap_n == 3 ? launch_wide<true, 2>(p, 0, nullptr, s) : launch_wide<true, 0>(p, 0, nullptr, s);
+}
+
+// What each route's instances serve, as the API has checked it before: the launchers' own refusal of anything else
+static bool route_serves(const ConvParams& p, ConvRoute route, int S, const float* work) {
+    if (S && (S < 2 || S > 8 || !work)) return false;
+    const bool plain = !(p.tail_w_hi || p.addend || p.in_sc || (p.tiling & ~1));
+    const bool wide = p.cout_pad % 128 == 0 && (p.tap_n == 3 || p.tap_n == 1);           // the shapes of launch_wide
+    switch (route) {
+    case CONV_BF16X3: return !S || wide;                           // S == 0: launch_conv_mfma refuses what has no instance
+    case CONV_F16:    return !S && p.cout_pad == 128 && p.tap_n == 3;
+    case CONV_F16P:   return !S && plain;
+    case CONV_F16D:   return plain && !p.add_hi && wide;
+    }
+    return false;
+}
+
+hipError_t launch_conv(const ConvParams& p, ConvRoute route, int S, float* work, hipStream_t s) {
+    if (!route_serves(p, route, S, work)) return hipErrorInvalidValue;
+    switch (route) {
+    case CONV_BF16X3: return S ? launch_splitk<false>(p, S, work, s) : launch_conv_mfma(p, s);
+    case CONV_F16:    return S ? hipErrorInvalidValue : launch_conv_mfma_f16(p, s);
+    case CONV_F16P:   return S ? hipErrorInvalidValue : launch_conv_mfma_f16p(p, s);
+    case CONV_F16D:   return S ? launch_splitk<true>(p, S, work, s) : launch_conv_mfma_f16d(p, s);
+    }
+    return hipErrorInvalidValue;
 }
 
 // =====================================================================================================

@@ -366,9 +366,10 @@ def _launch(name: str, on, *args):
         _check(getattr(load(), name)(*args, _stream(on)), name)
 
 
-def _workspace(name: str, args) -> int:
-    """A `*_workspace` query: the bytes the call described by `args` needs; the library answers -(MAGNET_E_*) on bad arguments."""
-    nbytes = int(getattr(load(), name)(ctypes.byref(args)))
+def _workspace(name: str, args, *more) -> int:
+    """A `*_workspace` query: the bytes the call described by `args` (and `more`, the query's other arguments) needs; the library
+    answers -(MAGNET_E_*) on bad arguments."""
+    nbytes = int(getattr(load(), name)(ctypes.byref(args), *more))
     if nbytes < 0:
         _check(-nbytes, name)
     return nbytes
@@ -605,6 +606,16 @@ def upsample_depth(depth, up_mask, k: int, out=None):
 # ---------------------------------------------------------------------------------------------------
 # G-Net / mask-head convolutions on the matrix cores (include/magnet_hip.h: magnet_conv_mfma & friends)
 # ---------------------------------------------------------------------------------------------------
+# the routes of conv_mfma, by its `f16` value: (entry point, split-K entry point or None, workspace query or None); magnet_conv_mfma itself
+# serves the default route when nothing needs the _ex struct.  A new route is one row here (and one case of launch_conv, conv_mfma.hip)
+_CONV_ROUTES = {
+    False: ("magnet_conv_mfma_ex", "magnet_conv_mfma_splitk", "magnet_conv_mfma_splitk_workspace"),
+    True: ("magnet_conv_mfma_f16", None, None),
+    "plane": ("magnet_conv_mfma_f16p", None, None),
+    "wide": ("magnet_conv_mfma_f16d", "magnet_conv_mfma_f16d_splitk", "magnet_conv_mfma_f16d_splitk_workspace"),
+}
+
+
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
               mx=None, leaky=None, tiling=None, f16=False, split_k=None, work=None):
@@ -644,9 +655,10 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     elif work is not None:
         raise MagnetError("conv_mfma: work goes with split_k")
     a = MagnetConvArgs()
-    plane = isinstance(f16, str) and f16 == "plane"
-    if f16 not in (False, True, "plane", "wide"):
+    if f16 not in tuple(_CONV_ROUTES):
         raise MagnetError(f"conv_mfma: f16 must be False, True, 'plane' or 'wide', got {f16!r}")
+    entry, entry_splitk, _ = _CONV_ROUTES[f16]                          # the route, looked up once
+    plane = isinstance(f16, str) and f16 == "plane"
     if wide and (tail is not None or addend is not None or add is not None or out_bf16 is not None or dil):
         raise MagnetError("conv_mfma (f16='wide'): the plain layer — no tail, addend, add, out_bf16 or dil")
     if plane and (tail is not None or addend is not None or out_lo is not None or (add is not None and add[1] is not None)):
@@ -721,11 +733,8 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     tiles = ctypes.c_int64(0)
     x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
-    if split_k is not None:
-        _launch("magnet_conv_mfma_f16d_splitk" if wide else "magnet_conv_mfma_splitk", in_hi, ctypes.byref(x), int(split_k), work.data_ptr(),
-                work.numel() * 4)
-        return tiles.value
-    _launch("magnet_conv_mfma_f16d" if wide else "magnet_conv_mfma_f16p" if plane else "magnet_conv_mfma_f16" if f16 else "magnet_conv_mfma_ex", in_hi, ctypes.byref(x))
+    more = () if split_k is None else (int(split_k), work.data_ptr(), work.numel() * 4)
+    _launch(entry_splitk if more else entry, in_hi, ctypes.byref(x), *more)
     return tiles.value
 
 
@@ -735,13 +744,10 @@ def conv_mfma_splitk_workspace(rows, cin, cout_pad, taps, split_k, f16=False):
     split_k=...)).  Host arithmetic: needs the library, not a GPU."""
     if not (f16 is False or (isinstance(f16, str) and f16 == "wide")):
         raise MagnetError(f"conv_mfma_splitk_workspace: f16 must be False or 'wide', got {f16!r}")
-    name = "magnet_conv_mfma_f16d_splitk_workspace" if f16 else "magnet_conv_mfma_splitk_workspace"
+    name = _CONV_ROUTES[f16][2]
     x = MagnetConvExArgs()
     x.base.rows, x.base.cin, x.base.cout_pad, x.base.taps, x.base.out_mode = int(rows), int(cin), int(cout_pad), int(taps), 1
-    nbytes = int(getattr(load(), name)(ctypes.byref(x), int(split_k)))
-    if nbytes < 0:
-        _check(-nbytes, name)
-    return nbytes
+    return _workspace(name, x, int(split_k))
 
 
 def conv_row_tiles(n_img, h, wp, bm):
