@@ -27,6 +27,7 @@
 #include "../../include/magnet_hip.h"
 #include "conv_common.hpp"
 #include "warp_math.hpp"
+#include "pack_tile.hpp"
 
 namespace magnet {
 
@@ -1726,28 +1727,21 @@ __global__ __launch_bounds__(256) void pack_split_kernel(const float* __restrict
     }
 }
 
-// Wide variant (h*w % 4 == 0, C % 8 == 0): 128 pixels x 64 channels per workgroup, 8 independent 16-byte loads per thread
-// (512-byte runs along the pixel axis), tile rows of 132 floats with the pixel index XOR-swizzled in 4-word blocks by the channel
-// octet: the float4 tile writes and the transposed channel reads (8 lanes = one pixel's 8 octets) are both conflict-free.
-constexpr int PW_PIX = 128, PW_S = 132;
-__device__ __forceinline__ int pw_idx(int c, int q) { return c * PW_S + (q ^ (((c >> 3) & 7) << 2)); }
+// Wide variant (h*w % 4 == 0, C % 8 == 0): pack_tile.hpp's 128-pixel x 64-channel tile, streaming loads and stores.  1-D grid with
+// the channel group as the fastest index: the workgroups that write one row's channel run (128 bytes each per plane) are neighbours in
+// dispatch order, not a quarter of the launch apart as with the channel group in grid.y (x_d3 of 64 frames: 0.483 -> 0.469 ms; with
+// the streaming accesses 0.448 ms).  One workgroup per row run was measured and is slower: looping over 4 groups 0.469 ms, a
+// 32-pixel x 256-channel tile 0.484 ms, 64 x 128 0.459 ms, all streaming (profiles/pack_phase/NOTES.md).
 __global__ __launch_bounds__(256) void pack_split_wide_kernel(const float* __restrict__ in, uint16_t* __restrict__ out_hi,
                                                                uint16_t* __restrict__ out_lo, int C, int h, int w,
                                                                int ctot, int c_off, long long in_img_stride) {
     __shared__ __attribute__((aligned(16))) float tile[64 * PW_S];
     const int hw = h * w;
-    const int bpi = (hw + PW_PIX - 1) / PW_PIX;
-    const int n = blockIdx.x / bpi, p0 = (blockIdx.x % bpi) * PW_PIX, f0 = blockIdx.y * 64;
-    const int tid = threadIdx.x, l4 = (tid & 31) * 4, cr = tid >> 5;          // 32 lanes x float4 = one channel row of the tile
-    float4 v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int c = cr + 8 * k, f = f0 + c, pp = p0 + l4;
-        v[k] = (pp < hw && f < C) ? *reinterpret_cast<const float4*>(in + (size_t)n * in_img_stride + (size_t)f * hw + pp)
-                                  : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) *reinterpret_cast<float4*>(&tile[pw_idx(cr + 8 * k, l4)]) = v[k];
+    const int bpi = (hw + PW_PIX - 1) / PW_PIX, ng = (C + 63) / 64;
+    const int pt = blockIdx.x / ng, f0 = (blockIdx.x - pt * ng) * 64;
+    const int n = pt / bpi, p0 = (pt - n * bpi) * PW_PIX;
+    const int tid = threadIdx.x;
+    pw_fill_tile<PACK_STREAM>(tile, in + (size_t)n * in_img_stride, C, hw, p0, f0);
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < 4; ++it) {                          // 128 pixels x 8 octets
@@ -1762,8 +1756,8 @@ __global__ __launch_bounds__(256) void pack_split_wide_kernel(const float* __res
             split_bf16x2(tile[pw_idx(vc + 2 * k, q)], tile[pw_idx(vc + 2 * k + 1, q)], hh[k], ll[k]);
         }
         const size_t e = row * ctot + c_off + f0 + vc;
-        *reinterpret_cast<uint4*>(out_hi + e) = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-        *reinterpret_cast<uint4*>(out_lo + e) = make_uint4(ll[0], ll[1], ll[2], ll[3]);
+        pk_store4<PACK_STREAM>(out_hi + e, hh[0], hh[1], hh[2], hh[3]);
+        pk_store4<PACK_STREAM>(out_lo + e, ll[0], ll[1], ll[2], ll[3]);
     }
 }
 
@@ -1775,8 +1769,9 @@ hipError_t launch_pack_split(const float* in, uint16_t* out_hi, uint16_t* out_lo
     constexpr bool narrow = false;
 #endif
     if (!narrow && (h * w) % 4 == 0 && C % 8 == 0 && in_img_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
-        const int bpw = (h * w + PW_PIX - 1) / PW_PIX;
-        hipLaunchKernelGGL(pack_split_wide_kernel, dim3((unsigned)(N * bpw), (unsigned)((C + 63) / 64)), dim3(256), 0, s, in, out_hi, out_lo,
+        const long long blocks = (long long)N * ((h * w + PW_PIX - 1) / PW_PIX) * ((C + 63) / 64);
+        if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(pack_split_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, out_hi, out_lo,
                            C, h, w, ctot, c_off, in_img_stride);
         return hipGetLastError();
     }
