@@ -19,7 +19,7 @@ from .planes import PackCache, pack_taps, pack_taps_f16, planes, round_up, split
 
 def mx_quant(v: torch.Tensor):
     """Block-scaled OCP e4m3 (MX-fp8) of v (..., nblk, 32) fp32: one E8M0 exponent per block with max |v| / 2^e in [128, 256) (<= 448), e = -127
-    for an all-zero block.  Returns (bytes uint8 (..., nblk, 32), e + 127 int32 (..., nblk)).  The rule of magnet_pack_mx (conv_mfma.hip)."""
+    for an all-zero block.  Returns (bytes uint8 (..., nblk, 32), e + 127 int32 (..., nblk)).  The rule of magnet_pack_mx (pack.hip)."""
     m = v.abs().amax(-1)
     _, ex = torch.frexp(m)
     e = (ex.to(torch.int32) - 8).clamp(min=-127)

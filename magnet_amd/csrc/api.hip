@@ -7,14 +7,13 @@
 #include <stdlib.h>
 #include "cv_common.hpp"
 #include "conv_common.hpp"
+#include "pack.hpp"
 
 namespace magnet {
-hipError_t launch_pack(const float*, void*, int, int, int, int, bool, int, hipStream_t);
 hipError_t launch_pack_gmm(const float*, float*, int, int, int, hipStream_t);
 hipError_t launch_pack_gmm_quad(const float*, float*, int, int, int, hipStream_t);
 hipError_t launch_gaussian_update(const float*, const float*, float*, int, int, hipStream_t);
 hipError_t launch_upsample(const float*, const float*, float*, int, int, int, int, int, hipStream_t);
-hipError_t launch_pack_split(const float*, uint16_t*, uint16_t*, int, int, int, int, int, int, long long, hipStream_t);
 hipError_t launch_gaussian_update_cl(const float*, int, const float*, float*, int, int, int, hipStream_t);
 hipError_t launch_upsample_cl(const float*, const float*, int, float*, int, int, int, int, hipStream_t);
 hipError_t launch_fnet_stem(const float*, const float*, const float*, uint16_t*, uint16_t*, int, int, int, hipStream_t);
@@ -562,15 +561,40 @@ MAGNET_API int magnet_conv_mfma_f16d_splitk(const MagnetConvExArgs* a, int32_t s
     return conv_splitk_run(a, true, split_k, work, work_bytes, stream);
 }
 
+// What magnet_pack_split, magnet_pack_f16 and magnet_pack_mx check alike, in their common order: NULL pointers, the dimensions
+// with the c_off / ctot granule (8 channels, the 16-byte vector; 32 for mx, its block), then 16-byte alignment.  `out` holds the
+// entry point's n_out outputs.  Where they differ, and stay different because each refusal is part of its entry point's contract:
+//   split  takes any in_img_stride and any row count;
+//   f16    refuses in_img_stride < 0 and N (h+2) (w+2) >= 2^31 as bad dims;
+//   mx     has no round-up lanes (C itself a multiple of 32) and no narrow kernel (h*w a multiple of 4), and says so in its
+//          message; checks sc_rows after the dimensions; counts the source and its image stride in the alignment, not out_sc.
+// The alignment messages name "outputs", "output" and "pointers" accordingly.  *stride receives the image stride in floats.
+enum PackKind { PACK_SPLIT, PACK_F16, PACK_MX };
+static int pack_check(PackKind kind, const char* who, const float* nchw, void* const* out, int n_out, int32_t N, int32_t C, int32_t h,
+                      int32_t w, int32_t ctot, int32_t c_off, int64_t in_img_stride, int64_t sc_rows, long long* stride) {
+    const bool mx = kind == PACK_MX;
+    const int g = mx ? 32 : 8;
+    bool null = !nchw;
+    for (int i = 0; i < n_out; ++i) null = null || !out[i];
+    if (null) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || (ctot % g) != 0 || (c_off % g) != 0 || c_off < 0 || (mx && (C % g) != 0) ||
+        c_off + ((C + g - 1) / g) * g > ctot || (mx && ((h * w) % 4) != 0) ||
+        (kind == PACK_F16 && (in_img_stride < 0 || (int64_t)N * (h + 2) * (w + 2) >= ((int64_t)1 << 31))))
+        return fail(MAGNET_E_DIM, "%s: bad dims N=%d C=%d h=%d w=%d ctot=%d c_off=%d%s", who, N, C, h, w, ctot, c_off,
+                    mx ? " (C, c_off, ctot multiples of 32; h*w of 4)" : "");
+    if (mx && sc_rows < (int64_t)N * (h + 2) * (w + 2)) return fail(MAGNET_E_DIM, "%s: sc_rows smaller than N*(h+2)*(w+2)", who);
+    *stride = in_img_stride ? (long long)in_img_stride : (long long)C * h * w;
+    bool misaligned = mx && (!aligned16(nchw) || (*stride % 4) != 0);
+    for (int i = 0; i < n_out && i < 2; ++i) misaligned = misaligned || !aligned16(out[i]);
+    if (misaligned) return fail(MAGNET_E_ALIGN, "%s: %s not 16-byte aligned", who, mx ? "pointers" : n_out == 2 ? "outputs" : "output");
+    return 0;
+}
+
 MAGNET_API int magnet_pack_f16(const float* nchw, void* out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,
                                int64_t in_img_stride, void* stream) {
-    if (!nchw || !out_f16) return fail(MAGNET_E_NULL, "magnet_pack_f16: NULL pointer");
-    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || (ctot % 8) != 0 || (c_off % 8) != 0 || c_off < 0 || c_off + ((C + 7) / 8) * 8 > ctot || in_img_stride < 0 ||
-        (int64_t)N * (h + 2) * (w + 2) >= ((int64_t)1 << 31))
-        return fail(MAGNET_E_DIM, "magnet_pack_f16: bad dims N=%d C=%d h=%d w=%d ctot=%d c_off=%d", N, C, h, w, ctot, c_off);
-    if (!aligned16(out_f16)) return fail(MAGNET_E_ALIGN, "magnet_pack_f16: output not 16-byte aligned");
-    hipError_t e = magnet::launch_pack_f16(nchw, (uint16_t*)out_f16, N, C, h, w, ctot, c_off,
-                                           in_img_stride ? (long long)in_img_stride : (long long)C * h * w, (hipStream_t)stream);
+    long long stride;
+    if (const int rc = pack_check(PACK_F16, "magnet_pack_f16", nchw, &out_f16, 1, N, C, h, w, ctot, c_off, in_img_stride, 0, &stride)) return rc;
+    hipError_t e = magnet::launch_pack_f16(nchw, (uint16_t*)out_f16, N, C, h, w, ctot, c_off, stride, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_pack_f16 launch");
 }
 
@@ -715,23 +739,18 @@ MAGNET_API int magnet_conv1x1_chain(const void* in_hi, const void* in_lo, const 
 
 MAGNET_API int magnet_pack_split(const float* nchw, void* out_hi, void* out_lo, int32_t N, int32_t C, int32_t h, int32_t w,
                                  int32_t ctot, int32_t c_off, int64_t in_img_stride, void* stream) {
-    if (!nchw || !out_hi || !out_lo) return fail(MAGNET_E_NULL, "magnet_pack_split: NULL pointer");
-    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || (c_off % 8) || c_off < 0 || c_off + ((C + 7) / 8) * 8 > ctot || (ctot % 8))
-        return fail(MAGNET_E_DIM, "magnet_pack_split: bad dims N=%d C=%d h=%d w=%d ctot=%d c_off=%d", N, C, h, w, ctot, c_off);
-    if (!aligned16(out_hi) || !aligned16(out_lo)) return fail(MAGNET_E_ALIGN, "magnet_pack_split: outputs not 16-byte aligned");
-    hipError_t e = magnet::launch_pack_split(nchw, (uint16_t*)out_hi, (uint16_t*)out_lo, N, C, h, w, ctot, c_off,
-                                             in_img_stride ? in_img_stride : (long long)C * h * w, (hipStream_t)stream);
+    void* const out[2] = {out_hi, out_lo};
+    long long stride;
+    if (const int rc = pack_check(PACK_SPLIT, "magnet_pack_split", nchw, out, 2, N, C, h, w, ctot, c_off, in_img_stride, 0, &stride)) return rc;
+    hipError_t e = magnet::launch_pack_split(nchw, (uint16_t*)out_hi, (uint16_t*)out_lo, N, C, h, w, ctot, c_off, stride, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_pack_split launch");
 }
 
 MAGNET_API int magnet_pack_mx(const float* nchw, void* out_f16, void* out_qr, void* out_sc, int32_t N, int32_t C, int32_t h, int32_t w,
                               int32_t ctot, int32_t c_off, int64_t sc_rows, int64_t in_img_stride, void* stream) {
-    if (!nchw || !out_f16 || !out_qr || !out_sc) return fail(MAGNET_E_NULL, "magnet_pack_mx: NULL pointer");
-    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || (C % 32) || (c_off % 32) || c_off < 0 || c_off + C > ctot || (ctot % 32) || ((h * w) % 4))
-        return fail(MAGNET_E_DIM, "magnet_pack_mx: bad dims N=%d C=%d h=%d w=%d ctot=%d c_off=%d (C, c_off, ctot multiples of 32; h*w of 4)", N, C, h, w, ctot, c_off);
-    if (sc_rows < (int64_t)N * (h + 2) * (w + 2)) return fail(MAGNET_E_DIM, "magnet_pack_mx: sc_rows smaller than N*(h+2)*(w+2)");
-    const int64_t stride = in_img_stride ? in_img_stride : (int64_t)C * h * w;
-    if (!aligned16(out_f16) || !aligned16(out_qr) || !aligned16(nchw) || (stride % 4)) return fail(MAGNET_E_ALIGN, "magnet_pack_mx: pointers not 16-byte aligned");
+    void* const out[3] = {out_f16, out_qr, out_sc};
+    long long stride;
+    if (const int rc = pack_check(PACK_MX, "magnet_pack_mx", nchw, out, 3, N, C, h, w, ctot, c_off, in_img_stride, sc_rows, &stride)) return rc;
     hipError_t e = magnet::launch_pack_mx(nchw, (uint16_t*)out_f16, (uint8_t*)out_qr, (uint32_t*)out_sc, N, C, h, w, ctot, c_off, sc_rows, stride,
                                           (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_pack_mx launch");

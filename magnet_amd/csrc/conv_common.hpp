@@ -109,11 +109,5 @@ enum ConvRoute { CONV_BF16X3, CONV_F16, CONV_F16P, CONV_F16D };
 // fixed-order reduce + epilogue launch.  hipErrorInvalidValue for a (route, split_k) pair or a form that has no kernel instance
 hipError_t launch_conv(const ConvParams&, ConvRoute route, int split_k, float* work, hipStream_t);
 hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
-hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
-                           hipStream_t s);
-hipError_t launch_planes_to_f16(const uint16_t* in_hi, const uint16_t* in_lo, uint16_t* out, long long rows, int ld, int ld16, int c0, int c1,
-                                hipStream_t s);
-hipError_t launch_pack_mx(const float* in, uint16_t* out_f16, uint8_t* out_qr, uint32_t* out_sc, int N, int C, int h, int w, int ctot, int c_off,
-                          long long sc_rows, long long in_img_stride, hipStream_t s);
 
 }  // namespace magnet

@@ -27,7 +27,6 @@
 #include "../../include/magnet_hip.h"
 #include "conv_common.hpp"
 #include "warp_math.hpp"
-#include "pack_tile.hpp"
 
 namespace magnet {
 
@@ -1693,171 +1692,6 @@ hipError_t launch_conv1x1_chain(const ChainParams& p, hipStream_t s) {
     if (p.cout_pad == 144) return launch_chain_nf<9>(p, s);
     if (p.cout_pad == 128) return launch_chain_nf<8>(p, s);
     return hipErrorInvalidValue;
-}
-
-// ---- fp32 NCHW (N, C, h, w) -> split bf16 planes of the padded channel-last buffer (N, h+2, w+2, Ctot),
-// ---- channels [c_off, c_off + C); 64 pixels x 64 channels per block through LDS; interior only
-// ---- (the zero border is written once by magnet_zero_fill / hipMemsetAsync when the buffer is created)
-__global__ __launch_bounds__(256) void pack_split_kernel(const float* __restrict__ in, uint16_t* __restrict__ out_hi,
-                                                          uint16_t* __restrict__ out_lo, int C, int h, int w,
-                                                          int ctot, int c_off, long long in_img_stride) {
-    __shared__ float tile[64][65];
-    const int hw = h * w;
-    const int bpi = (hw + 63) / 64;
-    const int n = blockIdx.x / bpi, p0 = (blockIdx.x % bpi) * 64, f0 = blockIdx.y * 64;
-    const int tid = threadIdx.x, px = tid & 63, cs = tid >> 6;
-    for (int c = cs; c < 64; c += 4) {
-        const int f = f0 + c, pp = p0 + px;
-        tile[c][px] = (pp < hw && f < C) ? in[(size_t)n * in_img_stride + (size_t)f * hw + pp] : 0.f;
-    }
-    __syncthreads();
-    for (int i = tid; i < 64 * 8; i += 256) {                 // 64 pixels x 8 vectors of 8 channels
-        const int q = i >> 3, vc = (i & 7) * 8, pq = p0 + q;
-        if (pq >= hw || f0 + vc >= C) continue;
-        const int y = pq / w, x = pq % w;
-        const size_t row = ((size_t)n * (h + 2) + (y + 1)) * (w + 2) + (x + 1);
-        uint32_t hh[4], ll[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            split_bf16x2(tile[vc + 2 * k][q], tile[vc + 2 * k + 1][q], hh[k], ll[k]);
-        }
-        const size_t e = row * ctot + c_off + f0 + vc;
-        *reinterpret_cast<uint4*>(out_hi + e) = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-        *reinterpret_cast<uint4*>(out_lo + e) = make_uint4(ll[0], ll[1], ll[2], ll[3]);
-    }
-}
-
-// Wide variant (h*w % 4 == 0, C % 8 == 0): pack_tile.hpp's 128-pixel x 64-channel tile, streaming loads and stores.  1-D grid with
-// the channel group as the fastest index: the workgroups that write one row's channel run (128 bytes each per plane) are neighbours in
-// dispatch order, not a quarter of the launch apart as with the channel group in grid.y (x_d3 of 64 frames: 0.483 -> 0.469 ms; with
-// the streaming accesses 0.448 ms).  One workgroup per row run was measured and is slower: looping over 4 groups 0.469 ms, a
-// 32-pixel x 256-channel tile 0.484 ms, 64 x 128 0.459 ms, all streaming (profiles/pack_phase/NOTES.md).
-__global__ __launch_bounds__(256) void pack_split_wide_kernel(const float* __restrict__ in, uint16_t* __restrict__ out_hi,
-                                                               uint16_t* __restrict__ out_lo, int C, int h, int w,
-                                                               int ctot, int c_off, long long in_img_stride) {
-    __shared__ __attribute__((aligned(16))) float tile[64 * PW_S];
-    const int hw = h * w;
-    const int bpi = (hw + PW_PIX - 1) / PW_PIX, ng = (C + 63) / 64;
-    const int pt = blockIdx.x / ng, f0 = (blockIdx.x - pt * ng) * 64;
-    const int n = pt / bpi, p0 = (pt - n * bpi) * PW_PIX;
-    const int tid = threadIdx.x;
-    pw_fill_tile<PACK_STREAM>(tile, in + (size_t)n * in_img_stride, C, hw, p0, f0);
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {                          // 128 pixels x 8 octets
-        const int i = tid + it * 256;
-        const int q = i >> 3, vc = (i & 7) * 8, pq = p0 + q;
-        if (pq >= hw || f0 + vc >= C) continue;
-        const int y = pq / w, x = pq - y * w;
-        const size_t row = ((size_t)n * (h + 2) + (y + 1)) * (w + 2) + (x + 1);
-        uint32_t hh[4], ll[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            split_bf16x2(tile[pw_idx(vc + 2 * k, q)], tile[pw_idx(vc + 2 * k + 1, q)], hh[k], ll[k]);
-        }
-        const size_t e = row * ctot + c_off + f0 + vc;
-        pk_store4<PACK_STREAM>(out_hi + e, hh[0], hh[1], hh[2], hh[3]);
-        pk_store4<PACK_STREAM>(out_lo + e, ll[0], ll[1], ll[2], ll[3]);
-    }
-}
-
-hipError_t launch_pack_split(const float* in, uint16_t* out_hi, uint16_t* out_lo, int N, int C, int h, int w,
-                             int ctot, int c_off, long long in_img_stride, hipStream_t s) {
-#ifdef MAGNET_DEV
-    static const bool narrow = getenv("MAGNET_PACK_NARROW") != nullptr;      // dev A/B: the 64-pixel kernel
-#else
-    constexpr bool narrow = false;
-#endif
-    if (!narrow && (h * w) % 4 == 0 && C % 8 == 0 && in_img_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
-        const long long blocks = (long long)N * ((h * w + PW_PIX - 1) / PW_PIX) * ((C + 63) / 64);
-        if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(pack_split_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, out_hi, out_lo,
-                           C, h, w, ctot, c_off, in_img_stride);
-        return hipGetLastError();
-    }
-    const int bpi = (h * w + 63) / 64;
-    const dim3 grid((unsigned)(N * bpi), (unsigned)((C + 63) / 64)), block(256);
-    hipLaunchKernelGGL(pack_split_kernel, grid, block, 0, s, in, out_hi, out_lo, C, h, w, ctot, c_off, in_img_stride);
-    return hipGetLastError();
-}
-
-
-// ---- round 4: NCHW fp32 -> the "2-unit" operand format of the 128-wide 3x3 layers (ConvParams::in_sc) -----------------------------------
-// Per interior position (row) and 32-channel block: out_f16 = fp16(x) (64 B); out_qr = 32 e4m3 bytes of hi / 2^e_h, then 32 e4m3 bytes of
-// lo / 2^e_l with lo = x - fp16(x) (exact in fp32); out_sc [block][row] = {e_h + 127, e_l + 127, 0, 0}: E8M0 exponents with
-// max |.| / 2^e in [128, 256) (<= 448, the e4m3 maximum), 0 for an all-zero block.  Same tile / transposition as pack_split_wide_kernel;
-// one thread = one (pixel, block).
-__device__ __forceinline__ int mx_block_exp(float m) {                        // m = max |v| >= 0
-    if (!(m > 0.f)) return -127;
-    const int e = (int)((__float_as_uint(m) >> 23) & 0xff) - 127 - 7;        // floor(log2 m) - 7 (denormal m: exponent field 0 -> -134 -> clamped)
-    return e < -127 ? -127 : e;
-}
-__global__ __launch_bounds__(256) void pack_mx_kernel(const float* __restrict__ in, uint16_t* __restrict__ out_f16, uint8_t* __restrict__ out_qr,
-                                                       uint32_t* __restrict__ out_sc, int C, int h, int w, int ctot, int c_off,
-                                                       long long sc_rows, long long in_img_stride) {
-    __shared__ __attribute__((aligned(16))) float tile[64 * PW_S];
-    const int hw = h * w;
-    const int bpi = (hw + PW_PIX - 1) / PW_PIX;
-    const int n = blockIdx.x / bpi, p0 = (blockIdx.x % bpi) * PW_PIX, f0 = blockIdx.y * 64;
-    const int tid = threadIdx.x, l4 = (tid & 31) * 4, cr = tid >> 5;
-    float4 v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int c = cr + 8 * k, f = f0 + c, pp = p0 + l4;
-        v[k] = (pp < hw && f < C) ? *reinterpret_cast<const float4*>(in + (size_t)n * in_img_stride + (size_t)f * hw + pp)
-                                  : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) *reinterpret_cast<float4*>(&tile[pw_idx(cr + 8 * k, l4)]) = v[k];
-    __syncthreads();
-    const int q = tid & 127, blk = tid >> 7, pq = p0 + q;
-    if (pq >= hw || f0 + blk * 32 >= C) return;
-    const int y = pq / w, x = pq - y * w;
-    const size_t row = ((size_t)n * (h + 2) + (y + 1)) * (w + 2) + (x + 1);
-    float hi[32], lo[32], mh = 0.f, ml = 0.f;
-    uint32_t hw16[16];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) {
-        // domain of the format: |x| <= 65504 (the fp16 plane); larger magnitudes are clamped — an Inf in the fp16 plane would make the
-        // residual -Inf and poison the block exponent (the bf16x3 format has no such limit; include/magnet_hip.h states the domain)
-        // NaN is not laundered by the clamp (v_med3_f32 would return a finite bound): it goes through to the fp16 plane and both
-        // e4m3 planes and propagates through the matrix instructions exactly as in the bf16x3 format
-        const float tv = tile[pw_idx(blk * 32 + c, q)];
-        const float xv = tv != tv ? tv : __builtin_amdgcn_fmed3f(tv, -65504.0f, 65504.0f);
-        const _Float16 hh = (_Float16)xv;
-        hi[c] = (float)hh; lo[c] = xv - hi[c];
-        mh = fmaxf(mh, fabsf(hi[c])); ml = fmaxf(ml, fabsf(lo[c]));
-        const uint32_t hb = (uint32_t)__builtin_bit_cast(uint16_t, hh);
-        if (c & 1) hw16[c >> 1] |= hb << 16; else hw16[c >> 1] = hb;
-    }
-    const int eh = mx_block_exp(mh), el = mx_block_exp(ml);
-    const float ih = __uint_as_float((uint32_t)(127 - eh) << 23), il = __uint_as_float((uint32_t)(127 - el) << 23);   // 2^-e (e = -127: 2^127 x 0)
-    uint32_t qw[8], rw[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        int a = 0, b = 0;
-        a = __builtin_amdgcn_cvt_pk_fp8_f32(hi[4 * k] * ih, hi[4 * k + 1] * ih, a, false);
-        a = __builtin_amdgcn_cvt_pk_fp8_f32(hi[4 * k + 2] * ih, hi[4 * k + 3] * ih, a, true);
-        b = __builtin_amdgcn_cvt_pk_fp8_f32(lo[4 * k] * il, lo[4 * k + 1] * il, b, false);
-        b = __builtin_amdgcn_cvt_pk_fp8_f32(lo[4 * k + 2] * il, lo[4 * k + 3] * il, b, true);
-        qw[k] = (uint32_t)a; rw[k] = (uint32_t)b;
-    }
-    const size_t e = row * ctot + c_off + f0 + blk * 32;
-    uint4* o16 = reinterpret_cast<uint4*>(out_f16 + e);
-    uint4* oqr = reinterpret_cast<uint4*>(out_qr + e * 2);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o16[k] = make_uint4(hw16[4 * k], hw16[4 * k + 1], hw16[4 * k + 2], hw16[4 * k + 3]);
-    oqr[0] = make_uint4(qw[0], qw[1], qw[2], qw[3]); oqr[1] = make_uint4(qw[4], qw[5], qw[6], qw[7]);
-    oqr[2] = make_uint4(rw[0], rw[1], rw[2], rw[3]); oqr[3] = make_uint4(rw[4], rw[5], rw[6], rw[7]);
-    out_sc[(size_t)((c_off + f0) / 32 + blk) * sc_rows + row] = (uint32_t)(eh + 127) | ((uint32_t)(el + 127) << 8);
-}
-
-hipError_t launch_pack_mx(const float* in, uint16_t* out_f16, uint8_t* out_qr, uint32_t* out_sc, int N, int C, int h, int w, int ctot, int c_off,
-                          long long sc_rows, long long in_img_stride, hipStream_t s) {
-    const int bpw = (h * w + PW_PIX - 1) / PW_PIX;
-    hipLaunchKernelGGL(pack_mx_kernel, dim3((unsigned)(N * bpw), (unsigned)((C + 63) / 64)), dim3(256), 0, s, in, out_f16, out_qr, out_sc,
-                       C, h, w, ctot, c_off, sc_rows, in_img_stride);
-    return hipGetLastError();
 }
 
 }  // namespace magnet

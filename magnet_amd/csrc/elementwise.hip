@@ -1,107 +1,13 @@
 // elementwise.hip — the HBM-bound helpers around the matcher:
-//   pack_features  : F-Net's NCHW fp32 -> channel-last fp32/bf16 (the cost-volume kernels' storage)
+//   pack_gmm       : (mu, sigma) planes -> the matcher's zero-bordered interleaved / quad forms (the feature packs: pack.hip)
 //   gaussian_update: GNET.forward's tail (models/MAGNET.py:60-69)
 //   upsample_depth : upsample_depth_via_mask (models/MAGNET.py:15-27)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "warp_math.hpp"
-#include "pack_tile.hpp"
 #include "../../include/magnet_hip.h"
 
 namespace magnet {
-
-// ---- pack: (N,F,hw) fp32 -> (N,hw,F) OutT, 64 pixels x FT channels per block through LDS ------
-// Reads are 256-B rows along the pixel axis, writes are 16-B vectors along the channel axis.
-constexpr int PK_PIX = 64;
-template <typename OutT, int FT>
-__global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ in, OutT* __restrict__ out,
-                                                    int F, int hw, int blocks_per_img, int w, int pad) {
-    __shared__ float tile[FT][PK_PIX + 1];
-    const int n = blockIdx.x / blocks_per_img;
-    const int p0 = (blockIdx.x % blocks_per_img) * PK_PIX;
-    const int f0 = blockIdx.y * FT;
-    const int tid = threadIdx.x, px = tid & 63, cs = tid >> 6;
-    const int p = p0 + px;
-    for (int c = cs; c < FT; c += 4) {
-        const int f = f0 + c;
-        tile[c][px] = (p < hw && f < F) ? in[((size_t)n * F + f) * hw + p] : 0.f;
-    }
-    __syncthreads();
-    constexpr int VEC = 16 / sizeof(OutT);           // channels per 16-byte store
-    constexpr int VPP = FT / VEC;                    // vectors per pixel
-    for (int i = tid; i < PK_PIX * VPP; i += 256) {
-        const int q = i / VPP, vc = (i % VPP) * VEC;
-        const int pq = p0 + q;
-        if (pq >= hw || f0 + vc >= F) continue;
-        // destination texel inside the (h+2*pad) x (w+2*pad) image
-        const int h_ = hw / w, py = pq / w, px_ = pq % w;
-        const size_t tex = (size_t)n * (h_ + 2 * pad) * (w + 2 * pad) + (size_t)(py + pad) * (w + 2 * pad) + (px_ + pad);
-        OutT* dst = out + tex * F + f0 + vc;
-        if constexpr (sizeof(OutT) == 4) {
-            float4 o = make_float4(tile[vc][q], tile[vc + 1][q], tile[vc + 2][q], tile[vc + 3][q]);
-            *reinterpret_cast<float4*>(dst) = o;
-        } else {
-            uint32_t w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                w[k] = f32x2_to_bf16x2_rne(tile[vc + 2 * k][q], tile[vc + 2 * k + 1][q]);
-            *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-}
-
-// Wide variant (hw % 4 == 0, F % 8 == 0): pack_tile.hpp's tile, 128 pixels x 64 channels per workgroup, streaming loads and stores
-template <typename OutT>
-__global__ __launch_bounds__(256) void pack_wide_kernel(const float* __restrict__ in, OutT* __restrict__ out,
-                                                         int F, int hw, int blocks_per_img, int w, int pad) {
-    __shared__ __attribute__((aligned(16))) float tile[64 * PW_S];
-    const int n = blockIdx.x / blocks_per_img;
-    const int p0 = (blockIdx.x % blocks_per_img) * PW_PIX;
-    const int f0 = blockIdx.y * 64;
-    const int tid = threadIdx.x;
-    pw_fill_tile<PACK_STREAM>(tile, in + (size_t)n * F * hw, F, hw, p0, f0);
-    __syncthreads();
-    const int h_ = hw / w;
-    constexpr int VEC = 16 / sizeof(OutT);           // channels per 16-byte store
-    constexpr int VPP = 64 / VEC;                    // vectors per pixel (8 or 16)
-#pragma unroll
-    for (int it = 0; it < PW_PIX * VPP / 256; ++it) {
-        const int i = tid + it * 256;
-        const int q = i / VPP, vc = (i % VPP) * VEC, pq = p0 + q;
-        if (pq >= hw || f0 + vc >= F) continue;
-        const int py = pq / w, px_ = pq - py * w;
-        const size_t tex = (size_t)n * (h_ + 2 * pad) * (w + 2 * pad) + (size_t)(py + pad) * (w + 2 * pad) + (px_ + pad);
-        OutT* dst = out + tex * F + f0 + vc;
-        if constexpr (sizeof(OutT) == 4) {
-            pk_store4<PACK_STREAM>(dst, __float_as_uint(tile[pw_idx(vc, q)]), __float_as_uint(tile[pw_idx(vc + 1, q)]),
-                                   __float_as_uint(tile[pw_idx(vc + 2, q)]), __float_as_uint(tile[pw_idx(vc + 3, q)]));
-        } else {
-            uint32_t wd[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                wd[k] = f32x2_to_bf16x2_rne(tile[pw_idx(vc + 2 * k, q)], tile[pw_idx(vc + 2 * k + 1, q)]);
-            pk_store4<PACK_STREAM>(dst, wd[0], wd[1], wd[2], wd[3]);
-        }
-    }
-}
-
-// zero the one-texel border of (N, h+2, w+2, F) images: 16-byte vectors
-__global__ __launch_bounds__(256) void zero_border_kernel(uint4* __restrict__ out, int N, int h, int w, int vec_per_tex) {
-    const int Wp = w + 2, Hp = h + 2;
-    const int per_img = 2 * Wp + 2 * h;                      // border texels of one image
-    const size_t total = (size_t)N * per_img * vec_per_tex;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % vec_per_tex);
-        const size_t t = i / vec_per_tex;
-        const int n = (int)(t / per_img), k = (int)(t % per_img);
-        int y, x;
-        if (k < Wp) { y = 0; x = k; }
-        else if (k < 2 * Wp) { y = Hp - 1; x = k - Wp; }
-        else { const int m = k - 2 * Wp; y = 1 + (m >> 1); x = (m & 1) ? Wp - 1 : 0; }
-        out[(((size_t)n * Hp + y) * Wp + x) * vec_per_tex + c] = make_uint4(0, 0, 0, 0);
-    }
-}
 
 // (N,2,h,w) planar [mu,sigma] -> (N,h+2,w+2,2) interleaved, zero border (one thread per padded texel)
 __global__ __launch_bounds__(256) void pack_gmm_kernel(const float* __restrict__ in, float2* __restrict__ out,
@@ -155,34 +61,6 @@ hipError_t launch_pack_gmm_quad(const float* in, float* out, int N, int h, int w
     const size_t total = (size_t)N * (h + 2) * (w + 2);
     hipLaunchKernelGGL(pack_gmm_quad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in,
                        reinterpret_cast<float4*>(out), N, h, w);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack(const float* in, void* out, int N, int F, int h, int w, bool bf16, int pad, hipStream_t s) {
-    const int hw = h * w;
-    const int bpi = (hw + PK_PIX - 1) / PK_PIX;
-    constexpr int FT = 64;
-    const dim3 grid((unsigned)(N * bpi), (unsigned)((F + FT - 1) / FT)), block(256);
-    if (pad) {
-        const int vec_per_tex = F * (bf16 ? 2 : 4) / 16;
-        const size_t total = (size_t)N * (2 * (w + 2) + 2 * h) * vec_per_tex;
-        const unsigned nb = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(zero_border_kernel, dim3(nb), dim3(256), 0, s, reinterpret_cast<uint4*>(out), N, h, w, vec_per_tex);
-    }
-#ifdef MAGNET_DEV
-    static const bool narrow = getenv("MAGNET_PACK_NARROW") != nullptr;      // dev A/B: the 64-pixel kernel
-#else
-    constexpr bool narrow = false;
-#endif
-    if (!narrow && hw % 4 == 0 && F % 8 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
-        const int bpw = (hw + PW_PIX - 1) / PW_PIX;
-        const dim3 gw((unsigned)(N * bpw), (unsigned)((F + 63) / 64));
-        if (bf16) hipLaunchKernelGGL((pack_wide_kernel<uint16_t>), gw, block, 0, s, in, (uint16_t*)out, F, hw, bpw, w, pad);
-        else      hipLaunchKernelGGL((pack_wide_kernel<float>),    gw, block, 0, s, in, (float*)out, F, hw, bpw, w, pad);
-        return hipGetLastError();
-    }
-    if (bf16) hipLaunchKernelGGL((pack_kernel<uint16_t, FT>), grid, block, 0, s, in, (uint16_t*)out, F, hw, bpi, w, pad);
-    else      hipLaunchKernelGGL((pack_kernel<float, FT>),    grid, block, 0, s, in, (float*)out, F, hw, bpi, w, pad);
     return hipGetLastError();
 }
 

@@ -758,27 +758,29 @@ def conv_row_tiles(n_img, h, wp, bm):
     return int(n), per.value
 
 
+def _nchw_source(who, x_nchw):
+    """The source of pack_split / pack_f16 / pack_mx: a float32 GPU tensor (N,C,h,w) whose images are dense (a leading-channel slice of a
+    wider NCHW tensor is).  Returns N, C, h, w and the in_img_stride argument: 0 (= dense) for one image, whose stride(0) is arbitrary."""
+    if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
+        raise MagnetError(f"{who}: input must be a float32 GPU tensor")
+    N, C, h, w = x_nchw.shape
+    if x_nchw.stride()[1:] != (h * w, w, 1):
+        raise MagnetError(f"{who}: unsupported input strides {x_nchw.stride()}")
+    return N, C, h, w, int(x_nchw.stride(0)) if N > 1 else 0
+
+
 def pack_split(x_nchw, out_hi, out_lo, ctot, c_off):
     """fp32 (N,C,h,w) (dense, or a leading-channel slice of a wider NCHW tensor) -> interior of the split-bf16
     padded channel-last buffer (N,h+2,w+2,ctot), channels [c_off, c_off+C)."""
-    if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
-        raise MagnetError("pack_split: input must be a float32 GPU tensor")
-    N, C, h, w = x_nchw.shape
-    if x_nchw.stride()[1:] != (h * w, w, 1):
-        raise MagnetError(f"pack_split: unsupported input strides {x_nchw.stride()}")
-    _launch("magnet_pack_split", x_nchw, x_nchw.data_ptr(), out_hi.data_ptr(), out_lo.data_ptr(), N, C, h, w, int(ctot), int(c_off),
-            int(x_nchw.stride(0)) if N > 1 else 0)
+    N, C, h, w, img_stride = _nchw_source("pack_split", x_nchw)
+    _launch("magnet_pack_split", x_nchw, x_nchw.data_ptr(), out_hi.data_ptr(), out_lo.data_ptr(), N, C, h, w, int(ctot), int(c_off), img_stride)
 
 
 def pack_mx(x_nchw, out_f16, out_qr, out_sc, ctot, c_off, sc_rows):
     """fp32 (N,C,h,w) -> channels [c_off, c_off+C) of the interior of a padded channel-last buffer (N,h+2,w+2,ctot) in the fp16 + e4m3
     operand format of conv_mfma(mx=...): out_f16 fp16 plane, out_qr 2-byte container plane (hi | lo e4m3 bytes per 32-channel block),
     out_sc int32 [ctot / 32][sc_rows] E8M0 pairs."""
-    if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
-        raise MagnetError("pack_mx: input must be a float32 GPU tensor")
-    N, C, h, w = x_nchw.shape
-    if x_nchw.stride()[1:] != (h * w, w, 1):
-        raise MagnetError(f"pack_mx: unsupported input strides {x_nchw.stride()}")
+    N, C, h, w, img_stride = _nchw_source("pack_mx", x_nchw)
     if out_f16.dtype != torch.float16 or out_qr.element_size() != 2 or out_sc.dtype != torch.int32:
         raise MagnetError("pack_mx: out_f16 fp16, out_qr a 2-byte dtype, out_sc int32")
     rows = N * (h + 2) * (w + 2)
@@ -788,22 +790,17 @@ def pack_mx(x_nchw, out_f16, out_qr, out_sc, ctot, c_off, sc_rows):
     if int(ctot) % 32 or int(c_off) % 32 or int(c_off) + C > int(ctot) or int(sc_rows) < rows:
         raise MagnetError("pack_mx: ctot / c_off must be multiples of 32 with c_off + C <= ctot, and sc_rows >= N (h+2) (w+2)")
     _launch("magnet_pack_mx", x_nchw, x_nchw.data_ptr(), out_f16.data_ptr(), out_qr.data_ptr(), out_sc.data_ptr(), N, C, h, w, int(ctot),
-            int(c_off), int(sc_rows), int(x_nchw.stride(0)) if N > 1 else 0)
+            int(c_off), int(sc_rows), img_stride)
 
 
 def pack_f16(x_nchw, out_f16, ctot, c_off):
     """fp32 (N,C,h,w) (dense, or a leading-channel slice of a wider NCHW tensor) -> channels [c_off, c_off+C) of the interior of the
     zero-bordered fp16 plane (N,h+2,w+2,ctot) of conv_mfma(f16=True).  Saturating round-to-nearest-even (include/magnet_hip.h)."""
-    if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
-        raise MagnetError("pack_f16: input must be a float32 GPU tensor")
-    N, C, h, w = x_nchw.shape
-    if x_nchw.stride()[1:] != (h * w, w, 1):
-        raise MagnetError(f"pack_f16: unsupported input strides {x_nchw.stride()}")
+    N, C, h, w, img_stride = _nchw_source("pack_f16", x_nchw)
     if not out_f16.is_cuda or out_f16.device != x_nchw.device or out_f16.dtype != torch.float16 or not out_f16.is_contiguous() or \
             out_f16.numel() < N * (h + 2) * (w + 2) * int(ctot):
         raise MagnetError(f"pack_f16: out_f16 must be a contiguous fp16 tensor on {x_nchw.device} with at least N (h+2) (w+2) ctot elements")
-    _launch("magnet_pack_f16", x_nchw, x_nchw.data_ptr(), out_f16.data_ptr(), N, C, h, w, int(ctot), int(c_off),
-            int(x_nchw.stride(0)) if N > 1 else 0)
+    _launch("magnet_pack_f16", x_nchw, x_nchw.data_ptr(), out_f16.data_ptr(), N, C, h, w, int(ctot), int(c_off), img_stride)
 
 
 def planes_to_f16(in_hi, in_lo, out_f16, c0, c1):

@@ -48,6 +48,17 @@ import torch
 
 from tests.fnet_bwd_ref import LOLO, U, check, check_planes_exact, conv_ref, gamma_l, join, ratio, tap_offsets  # noqa: F401
 
+GUARD = 4096                                      # sentinel elements in front of and behind every output buffer of the GPU tests
+
+
+def guarded(shape, gpu, dtype=torch.float32, fill=float("nan")):
+    """A sentinel-filled tensor with GUARD sentinel elements on either side of it (same allocation)."""
+    n = 1
+    for d in shape:
+        n *= int(d)
+    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=gpu)
+    return buf, buf[GUARD:GUARD + n].view(shape)
+
 TAIL_K = 128
 
 

@@ -252,7 +252,8 @@ def test_f16_refusals(hip_lib, gpu):
     assert bool(_is_sentinel(buf).all())
 
 
-# ---- magnet_pack_f16 and magnet_planes_to_f16, bit for bit against the host restatement -------------------------------------------
+# ---- magnet_pack_f16 (csrc/pack.hip: pack_nchw_kernel<PackF16, 128> in the "wide" cases, <PackF16, 64> in the "narrow" ones) and
+# ---- magnet_planes_to_f16, bit for bit against the host restatement
 PACK_FILL = -7.0                                  # a finite sentinel: NaN is an input here
 PACK = [
     # id                       N  C   h   w   ctot c_off

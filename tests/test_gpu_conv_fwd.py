@@ -29,8 +29,8 @@ library reports (rows / BM rounded up) is asserted, which tells the 128-row from
     cout_pad 32 / 64, taps 9                                                <2|4,1,128,0,256,-,2>   nf2_win2-*, nf4_win2-*
     cout_pad 32 / 64 (taps 4, 1)                                            <2|4,1,128,0,256,-,0>   nf2_flat-*, nf4_flat-*
   launch_conv1x1_chain: cout_pad 16 / 128 / 144 -> conv1x1_chain_kernel<1 / 8 / 9>                  test_conv1x1_chain
-  launch_pack_split: h*w % 4 == 0, C % 8 == 0, in_img_stride % 4 == 0, 16-byte aligned input -> pack_split_wide_kernel, else
-    pack_split_kernel                                                                               test_pack_split
+  launch_pack_split (csrc/pack.hip): h*w % 4 == 0, C % 8 == 0, in_img_stride % 4 == 0, 16-byte aligned input ->
+    pack_nchw_kernel<PackSplit, 128>, else pack_nchw_kernel<PackSplit, 64>                          test_pack_split
 
 Not repeated here, because existing tests tie them bit for bit to launches that ARE checked here:
   the fused Gaussian update and the fused upsampling     test_gpu_conv.py::test_gnet_with_fused_gaussian_update_equals_the_two_launch_form,
@@ -44,13 +44,12 @@ Not repeated here, because existing tests tie them bit for bit to launches that 
   the fp16 + e4m3 operand format (opt-in)                test_gpu_conv.py::test_conv_stack_mx_format_matches_fp32 keeps its max-norm check;
                                                          a pointwise bound for its e4m3 correction terms is a separate piece of work.
 """
-import numpy as np
 import pytest
 import torch
 
 from tests import conv_fwd_ref as C
+from tests.conv_fwd_ref import GUARD, guarded as _guarded  # noqa: F401  (other test modules import them from here)
 
-GUARD = 4096                                      # sentinel elements in front of and behind every output buffer
 EXTRA = 40                                        # sentinel rows behind the last row a launch may write
 NAN_BITS = {torch.float32: 0x7FC00000, torch.bfloat16: 0x7FC0}
 INT_OF = {torch.float32: torch.int32, torch.bfloat16: torch.int16}
@@ -62,13 +61,6 @@ def _g(seed):
 
 def _heavy(shape, seed, scale=1.0):
     return torch.randn(shape, generator=_g(seed)) ** 3 * scale
-
-
-def _guarded(shape, gpu, dtype=torch.float32, fill=float("nan")):
-    """A sentinel-filled tensor with GUARD sentinel elements on either side of it (same allocation)."""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=gpu)
-    return buf, buf[GUARD:GUARD + n].view(shape)
 
 
 def _is_sentinel(t):

@@ -1,13 +1,21 @@
-"""-m gpu: magnet_pack_split's wide kernel (1-D grid, channel group fastest, streaming accesses), bit for bit.
+"""-m gpu: the layout packs' one kernel template (pack.hip: 1-D grid, channel group fastest), bit for bit, in every format.
 
-The planes against convnet.split_bf16 through tests/conv_fwd_ref.py's check_planes_exact, as tests/test_gpu_conv_fwd.py checks the
-pack kernels, at the shapes where the block index is decoded differently: a pixel tile with a tail, exactly one tile, many channel
-groups over less than one tile (the D-Net's skip packs), a ragged last channel group, and a batch-strided input.  Every element the
-call does not own (border rows, the other channels) still holds the sentinel the planes were filled with."""
+magnet_pack_split's planes against convnet.split_bf16 through tests/conv_fwd_ref.py's check_planes_exact, as tests/test_gpu_conv_fwd.py
+checks the pack kernels, at the shapes where the block index is decoded differently: a pixel tile with a tail, exactly one tile, many
+channel groups over less than one tile (the D-Net's skip packs), a ragged last channel group, and a batch-strided input.  Every element
+the call does not own (border rows, the other channels) still holds the sentinel the planes were filled with.
+
+The other formats share that decode, and their own tests never reach a wide launch with several channel groups, so each runs at the
+same shapes where its entry point accepts them, against the restatement its own test uses: magnet_pack_f16 against the numpy fp16
+saturation (tests/test_conv_precision_host.py), magnet_pack_mx against convnet.split_mx (C a multiple of 32: not ragged-C72),
+magnet_pack_features against permute + .to(bfloat16) (ctot = C, c_off = 0, dense input, pad 0 and 1; the border of pad 1 is zero).
+Their destinations lie between guard bands of the sentinel."""
+import numpy as np
 import pytest
 import torch
 
 from tests import conv_fwd_ref as C
+from tests.test_conv_precision_host import assert_f16_bits_equal, f16_sat_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -32,15 +40,26 @@ PACK = [
 ]
 
 
+def _source(gpu, N, Cn, h, w, strided):
+    """The fp32 NCHW source of a PACK row on the GPU: dense, or x[:N, :Cn] of a tensor with one more image and 8 more channels."""
+    full = torch.randn((N + 1 if strided else N, Cn + 8 if strided else Cn, h, w), generator=_g(11 + Cn + h * w)).to(gpu)
+    x = full[:N, :Cn] if strided else full
+    if strided:
+        assert not x.is_contiguous() and x.stride(0) == (Cn + 8) * h * w
+    return x
+
+
+def _assert_guards(name, buf, fill):
+    g = torch.full((C.GUARD,), fill, dtype=buf.dtype, device=buf.device)
+    assert torch.equal(buf[:C.GUARD], g) and torch.equal(buf[-C.GUARD:], g), f"{name}: write outside the buffer"
+
+
 @pytest.mark.parametrize("N,Cn,h,w,ctot,c_off,strided", [p[1:] for p in PACK], ids=[p[0] for p in PACK])
 def test_pack_split_row_dense(hip_lib, gpu, request, N, Cn, h, w, ctot, c_off, strided):
     from magnet_amd import lib
     from magnet_amd.convnet import split_bf16
     name = request.node.callspec.id
-    full = torch.randn((N + 1 if strided else N, Cn + 8 if strided else Cn, h, w), generator=_g(11 + Cn + h * w)).to(gpu)
-    x = full[:N, :Cn] if strided else full
-    if strided:
-        assert not x.is_contiguous() and x.stride(0) == (Cn + 8) * h * w
+    x = _source(gpu, N, Cn, h, w, strided)
     hi, lo = (_sent((N, h + 2, w + 2, ctot), torch.bfloat16, gpu) for _ in range(2))
     lib.pack_split(x, hi, lo, ctot, c_off)
     torch.cuda.synchronize()
@@ -49,3 +68,62 @@ def test_pack_split_row_dense(hip_lib, gpu, request, N, Cn, h, w, ctot, c_off, s
     for e, pl in zip(exp, (eh, el)):
         e[:, 1:-1, 1:-1, c_off:c_off + Cn] = pl
     C.check_planes_exact(name, hi, lo, exp[0], exp[1])                 # interior rows, border rows and the other channels
+
+
+@pytest.mark.parametrize("N,Cn,h,w,ctot,c_off,strided", [p[1:] for p in PACK], ids=[p[0] for p in PACK])
+def test_pack_f16_row_dense(hip_lib, gpu, request, N, Cn, h, w, ctot, c_off, strided):
+    from magnet_amd import lib
+    name = request.node.callspec.id
+    x = _source(gpu, N, Cn, h, w, strided)
+    buf, body = C.guarded((N, h + 2, w + 2, ctot), gpu, torch.float16, SENT)
+    lib.pack_f16(x, body, ctot, c_off)
+    torch.cuda.synchronize()
+    bits = lambda t: t.contiguous().cpu().view(torch.int16).numpy().view(np.uint16)
+    exp = bits(torch.full((N, h + 2, w + 2, ctot), SENT, dtype=torch.float16))
+    exp[:, 1:-1, 1:-1, c_off:c_off + Cn] = f16_sat_bits(x.permute(0, 2, 3, 1).cpu().numpy())      # Cn % 8 == 0: no round-up lanes
+    assert_f16_bits_equal(name, bits(body), exp)                       # interior rows, border rows and the other channels
+    _assert_guards(name, buf, SENT)
+
+
+@pytest.mark.parametrize("N,Cn,h,w,ctot,c_off,strided", [p[1:] for p in PACK if p[2] % 32 == 0], ids=[p[0] for p in PACK if p[2] % 32 == 0])
+def test_pack_mx_row_dense(hip_lib, gpu, request, N, Cn, h, w, ctot, c_off, strided):
+    from magnet_amd import lib
+    from magnet_amd.convnet import split_mx
+    name = request.node.callspec.id
+    x = _source(gpu, N, Cn, h, w, strided)
+    rows = N * (h + 2) * (w + 2)
+    fills = (SENT, int(torch.tensor(SENT, dtype=torch.float16).view(torch.int16)), -7)             # the qr container holds the fp16 pattern of -7
+    shapes = ((N, h + 2, w + 2, ctot), (N, h + 2, w + 2, ctot), (ctot // 32, N, h + 2, w + 2))
+    dtypes = (torch.float16, torch.int16, torch.int32)
+    bufs, bodies = zip(*(C.guarded(sh, gpu, dt, fl) for sh, dt, fl in zip(shapes, dtypes, fills)))
+    lib.pack_mx(x, *bodies, ctot, c_off, rows)                         # sc_rows: the buffer's rows
+    torch.cuda.synchronize()
+    hi, qr, sc = split_mx(x.permute(0, 2, 3, 1).contiguous().cpu())
+    exp = [torch.full(sh, fl, dtype=dt) for sh, dt, fl in zip(shapes, dtypes, fills)]
+    exp[0][:, 1:-1, 1:-1, c_off:c_off + Cn] = hi
+    exp[1][:, 1:-1, 1:-1, c_off:c_off + Cn] = qr
+    exp[2][c_off // 32:(c_off + Cn) // 32, :, 1:-1, 1:-1] = sc.permute(3, 0, 1, 2)
+    for what, got, e, buf, fl in zip(("f16", "qr", "sc"), bodies, exp, bufs, fills):
+        got = got.cpu()
+        same = got.view(torch.int16) == e.view(torch.int16) if what == "f16" else got == e
+        assert bool(same.all()), f"{name}: {what} differs at {int((~same).sum())} elements, first {(~same).nonzero()[0].tolist()}"
+        _assert_guards(f"{name} {what}", buf, fl)
+
+
+FEATURES = [p for p in PACK if not p[7]]                              # ctot = C, c_off = 0, dense input: the strided row drops out
+
+
+@pytest.mark.parametrize("pad", [0, 1])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("N,Cn,h,w", [p[1:5] for p in FEATURES], ids=[p[0] for p in FEATURES])
+def test_pack_features_row_dense(hip_lib, gpu, request, N, Cn, h, w, dtype, pad):
+    from magnet_amd import lib
+    name = request.node.callspec.id
+    x = _source(gpu, N, Cn, h, w, False)
+    dt = lib.feat_torch_dtype(lib.feat_enum(dtype))
+    buf, body = C.guarded((N, h + 2 * pad, w + 2 * pad, Cn), gpu, dt, SENT)
+    got = lib.pack_features(x, lib.feat_enum(dtype), pad=pad, out=body)
+    torch.cuda.synchronize()
+    exp = torch.nn.functional.pad(x, (pad, pad, pad, pad)).permute(0, 2, 3, 1).contiguous().to(dt)  # RNE for bf16; pad 1: a zero border
+    assert got.dtype == exp.dtype and torch.equal(got, exp), f"{name}: {int((got != exp).sum())} elements differ"
+    _assert_guards(name, buf, SENT)

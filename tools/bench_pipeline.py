@@ -1,6 +1,6 @@
 """Software-pipelined batches (C2 shapes): the layout packs of batch i + 1 on a side stream beside the matcher / convolution kernels
 of batch i (two buffer sets, events where the chains meet).  Every step does one full pack set and one full refinement; prints the
-sequential and the pipelined ms per step.  `--dev-lib` + MAGNET_PACK_NARROW=1 selects the 64-pixel pack kernels (small footprint)."""
+sequential and the pipelined ms per step.  `--dev-lib` + MAGNET_PACK_NARROW=1 selects the 64-pixel instance of every layout pack (pack.hip's one switch; small footprint)."""
 import argparse
 import copy
 import json
