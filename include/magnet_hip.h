@@ -807,6 +807,33 @@ typedef struct MagnetFnetLossArgs {
 MAGNET_API int magnet_fnet_loss_forward(const MagnetFnetLossArgs *args, void *stream);
 MAGNET_API int magnet_fnet_loss_backward(const MagnetFnetLossArgs *args, void *stream);
 
+/* ---- Synchronised BatchNorm (nn.SyncBatchNorm: train_FNet.py:220-222 converts every BatchNorm and trains under DDP): the statistics
+ * of magnet_bn_train_stats / magnet_bn_train_backward taken over the shards of several ranks.  The library runs the device arithmetic
+ * before and after the collective; the caller all-gathers the fp64 buffer in between (one all-gather per BatchNorm and direction).
+ * Additive to v400: the existing argument structs plus plain parameters.  All four take C a multiple of 8 up to 2048 and a rank with
+ * at least ONE interior position (magnet_bn_train_apply accepts one position too; only magnet_bn_train_stats needs two).
+ * Every sum runs in fp64 in a fixed order (positions, then ranks in rank order) with no atomics, and the merge reads the same gathered
+ * bytes on every rank: mean, invstd, n_tot and the running statistics are bit-identical across ranks and from run to run.
+ *
+ * magnet_bn_sync_moments: over the grid of MagnetBnTrainArgs (x, x_ld, N, hp, wp, pad, C, work as for magnet_bn_train_stats; the
+ *   other fields are ignored) writes the rank's record, record[(3, C)] = (n, mean, M2): n the local count, M2 = sum (x - mean)^2.
+ *   Writes neither mean / invstd nor the running statistics.
+ * magnet_bn_sync_merge: records (world, 3, C), the ranks' records in rank order.  n_tot = sum n_r, mean = sum n_r mean_r / n_tot,
+ *   M2 = sum (M2_r + n_r (mean_r - mean)^2).  Writes args->mean, args->invstd = 1 / sqrt(M2 / n_tot + eps), n_tot[0] (a device
+ *   double, read by the backward) and updates running_mean / running_var / num_batches_tracked as magnet_bn_train_stats does, with
+ *   the global unbiased variance M2 / (n_tot - 1).  Uses C, mean, invstd, eps, momentum and the running buffers of args; n_tot >= 2
+ *   is the caller's to ensure (two ranks with a position each do).  magnet_bn_train_apply then runs on the shard unchanged.
+ * magnet_bn_sync_backward_sums: over MagnetBnBwdArgs (mean / invstd the GLOBAL ones; dx_* ignored) writes sums[(2, C)] = (sum g',
+ *   sum g' xhat) of the rank, and dgamma / dbeta as these LOCAL sums (torch.nn.SyncBatchNorm does the same; DDP averages them).
+ * magnet_bn_sync_backward_apply: sums (world, 2, C) in rank order, added in that order; dx = gamma invstd (g' - sum g' / n_tot -
+ *   xhat sum g' xhat / n_tot) with the device-side n_tot, written as magnet_bn_train_backward writes it (dgamma / dbeta ignored).
+ *   work: MAGNET_BN_BLOCKS * C * 2 + 2 * C doubles, as for magnet_bn_train_backward. */
+MAGNET_API int magnet_bn_sync_moments(const MagnetBnTrainArgs *args, double *record, void *stream);
+MAGNET_API int magnet_bn_sync_merge(const MagnetBnTrainArgs *args, const double *records, int32_t world, double *n_tot, void *stream);
+MAGNET_API int magnet_bn_sync_backward_sums(const MagnetBnBwdArgs *args, double *sums, void *stream);
+MAGNET_API int magnet_bn_sync_backward_apply(const MagnetBnBwdArgs *args, const double *sums, int32_t world, const double *n_tot,
+                                             void *stream);
+
 /* DnetLoss: the tail of the stand-alone D-Net's training step behind the two head convolutions (upsample_depth_via_mask,
  * models/submodules/D_dense_depth.py:86-100; activation_G, models/DNET.py:56-60; DnetLoss 'gaussian', utils/losses.py:8-24) in
  * fused kernels.  depth (B, 2, h, w) is the RAW head output [mu, v]; the mask logit (b, ch, y, x), ch = t*16 + i*4 + j < 144 with

@@ -50,6 +50,10 @@ hipError_t launch_dnet_gauss_head(const float*, int, int, int, int, int, float*,
 hipError_t launch_dnet_upsample_gauss(const float*, int, const float*, int, int, int, int, float*, hipStream_t);
 hipError_t launch_fnet_loss_forward(const MagnetFnetLossArgs&, hipStream_t);
 hipError_t launch_fnet_loss_backward(const MagnetFnetLossArgs&, hipStream_t);
+hipError_t launch_bn_sync_moments(const MagnetBnTrainArgs&, double*, hipStream_t);
+hipError_t launch_bn_sync_merge(const MagnetBnTrainArgs&, const double*, int, double*, hipStream_t);
+hipError_t launch_bn_sync_backward_sums(const MagnetBnBwdArgs&, double*, hipStream_t);
+hipError_t launch_bn_sync_backward_apply(const MagnetBnBwdArgs&, const double*, int, const double*, hipStream_t);
 long long dnet_loss_workspace_bytes(const MagnetDnetLossArgs&);
 hipError_t launch_dnet_loss_forward(const MagnetDnetLossArgs&, hipStream_t);
 hipError_t launch_dnet_loss_backward(const MagnetDnetLossArgs&, hipStream_t);
@@ -902,11 +906,13 @@ MAGNET_API int magnet_fnet_stem_raw(const float* img, const float* wgt, float* o
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_stem_raw launch");
 }
 
-static int bn_train_check(const MagnetBnTrainArgs* a, const char* who) {
-    if (!a || !a->x || !a->mean || !a->invstd) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+// min_pos: 2 where the launch takes the variance of these positions alone, 1 where the statistics come from elsewhere
+static int bn_train_check(const MagnetBnTrainArgs* a, const char* who, int min_pos = 2, bool stats_out = true) {
+    if (!a || !a->x || (stats_out && (!a->mean || !a->invstd))) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
     if (a->N <= 0 || a->C <= 0 || a->C > 2048 || (a->C % 8) || a->pad < 0 || a->hp <= 2 * a->pad || a->wp <= 2 * a->pad || a->x_ld < a->C ||
-        (a->x_ld % 4) || (long long)a->N * (a->hp - 2 * a->pad) * (a->wp - 2 * a->pad) < 2)
-        return fail(MAGNET_E_DIM, "%s: bad dims (C a multiple of 8 up to 2048, x_ld >= C a multiple of 4, at least 2 positions)", who);
+        (a->x_ld % 4) || (long long)a->N * (a->hp - 2 * a->pad) * (a->wp - 2 * a->pad) < min_pos)
+        return fail(MAGNET_E_DIM, "%s: bad dims (C a multiple of 8 up to 2048, x_ld >= C a multiple of 4, at least %d position(s))", who,
+                    min_pos);
     if (!aligned16(a->x)) return fail(MAGNET_E_ALIGN, "%s: x must be 16-byte aligned", who);
     return 0;
 }
@@ -920,7 +926,7 @@ MAGNET_API int magnet_bn_train_stats(const MagnetBnTrainArgs* a, void* stream) {
 }
 
 MAGNET_API int magnet_bn_train_apply(const MagnetBnTrainArgs* a, void* stream) {
-    if (int rc = bn_train_check(a, "magnet_bn_train_apply")) return rc;
+    if (int rc = bn_train_check(a, "magnet_bn_train_apply", 1)) return rc;
     if (!a->gamma || !a->beta || (!a->out_f32 && (!a->out_hi || !a->out_lo))) return fail(MAGNET_E_NULL, "magnet_bn_train_apply: NULL pointer");
     if ((a->res_hi == nullptr) != (a->res_lo == nullptr)) return fail(MAGNET_E_NULL, "magnet_bn_train_apply: res_hi and res_lo come together");
     if (a->out_ld < a->C || (a->out_f32 ? (a->out_ld % 4) : (a->out_ld % 8)) || (a->res_hi && (a->res_ld < a->C || (a->res_ld % 8))))
@@ -1033,6 +1039,49 @@ MAGNET_API int magnet_fnet_loss_backward(const MagnetFnetLossArgs* a, void* stre
     if (int rc = fnet_loss_dims(a, "magnet_fnet_loss_backward")) return rc;
     hipError_t e = magnet::launch_fnet_loss_backward(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_fnet_loss_backward launch");
+}
+
+// ---- synchronised BatchNorm (train_fnet_fwd.hip, train_fnet_bwd.hip): the device arithmetic around the caller's all-gather ----
+MAGNET_API int magnet_bn_sync_moments(const MagnetBnTrainArgs* a, double* record, void* stream) {
+    if (!record) return fail(MAGNET_E_NULL, "magnet_bn_sync_moments: NULL record");
+    if (int rc = bn_train_check(a, "magnet_bn_sync_moments", 1, false)) return rc;
+    if (!a->work) return fail(MAGNET_E_NULL, "magnet_bn_sync_moments: NULL workspace");
+    hipError_t e = magnet::launch_bn_sync_moments(*a, record, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_bn_sync_moments launch");
+}
+
+MAGNET_API int magnet_bn_sync_merge(const MagnetBnTrainArgs* a, const double* records, int32_t world, double* n_tot, void* stream) {
+    if (!a || !records || !n_tot || !a->mean || !a->invstd) return fail(MAGNET_E_NULL, "magnet_bn_sync_merge: NULL pointer");
+    if (world < 1 || a->C <= 0 || a->C > 2048 || (a->C % 8))
+        return fail(MAGNET_E_DIM, "magnet_bn_sync_merge: bad dims (world >= 1, C a multiple of 8 up to 2048), world=%d C=%d", world, a->C);
+    if (!(a->eps >= 0.0) || a->momentum > 1.0) return fail(MAGNET_E_DIM, "magnet_bn_sync_merge: eps >= 0 and momentum <= 1 required");
+    hipError_t e = magnet::launch_bn_sync_merge(*a, records, world, n_tot, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_bn_sync_merge launch");
+}
+
+static int bn_sync_bwd_check(const MagnetBnBwdArgs* a, const char* who) {
+    if (!a || !a->x || !a->mean || !a->invstd || !a->gamma || !a->beta || !a->g || !a->work) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (a->N <= 0 || a->C <= 0 || a->C > 2048 || (a->C % 8) || a->pad < 0 || a->hp <= 2 * a->pad || a->wp <= 2 * a->pad || a->x_ld < a->C ||
+        a->g_ld < a->C)
+        return fail(MAGNET_E_DIM, "%s: bad dims (C a multiple of 8 up to 2048, x_ld / g_ld >= C, at least 1 position)", who);
+    return 0;
+}
+
+MAGNET_API int magnet_bn_sync_backward_sums(const MagnetBnBwdArgs* a, double* sums, void* stream) {
+    if (!sums) return fail(MAGNET_E_NULL, "magnet_bn_sync_backward_sums: NULL sums");
+    if (int rc = bn_sync_bwd_check(a, "magnet_bn_sync_backward_sums")) return rc;
+    if (!a->dgamma || !a->dbeta) return fail(MAGNET_E_NULL, "magnet_bn_sync_backward_sums: NULL dgamma / dbeta");
+    hipError_t e = magnet::launch_bn_sync_backward_sums(*a, sums, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_bn_sync_backward_sums launch");
+}
+
+MAGNET_API int magnet_bn_sync_backward_apply(const MagnetBnBwdArgs* a, const double* sums, int32_t world, const double* n_tot, void* stream) {
+    if (!sums || !n_tot) return fail(MAGNET_E_NULL, "magnet_bn_sync_backward_apply: NULL sums / n_tot");
+    if (int rc = bn_sync_bwd_check(a, "magnet_bn_sync_backward_apply")) return rc;
+    if (!a->dx_hi || !a->dx_lo) return fail(MAGNET_E_NULL, "magnet_bn_sync_backward_apply: NULL dx");
+    if (world < 1 || a->dx_ld < a->C) return fail(MAGNET_E_DIM, "magnet_bn_sync_backward_apply: world >= 1 and dx_ld >= C required");
+    hipError_t e = magnet::launch_bn_sync_backward_apply(*a, sums, world, n_tot, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_bn_sync_backward_apply launch");
 }
 
 // ---- DnetLoss (dnet_loss.hip) ----

@@ -5,6 +5,8 @@
 //   bn_bwd       BatchNorm2d backward with batch statistics: fp64 two-stage sums of g' and g' xhat (fixed order, no atomics), then
 //                dx = gamma invstd (g' - mean g' - xhat mean g' xhat) as split-bf16 planes with zero borders; g' = g masked by
 //                the forward's ReLU, recomputed from the saved pre-BN activations with the apply's own arithmetic
+//   bn_bwd_sync  the same over several ranks (nn.SyncBatchNorm): the rank's two sums for the caller's all-gather, then the gathered
+//                sums added in rank order, divided by the global count, and the same dx
 //   grad_pack    the feature gradient (NCHW fp32) into the bordered split-bf16 grid of the last 1x1 layer
 //   d2s_bwd      backward of the space-to-depth rearrangement (a gather)
 //   spp_up_bwd   backward of the align_corners bilinear upsampling: per pooled cell, its weighted window gathered in a fixed order
@@ -100,6 +102,33 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const MagnetBnBwdArgs
         for (int b = 0; b < BB; ++b) { t1 += a.work[((size_t)b * a.C + c) * 2]; t2 += a.work[((size_t)b * a.C + c) * 2 + 1]; }
         a.dbeta[c] = (float)t1;
         a.dgamma[c] = (float)t2;
+        m[2 * c] = t1 / n;
+        m[2 * c + 1] = t2 / n;
+    }
+}
+
+// ---- synchronised backward, local stage 2: this rank's sums of g' and g' xhat (xhat from the global mean / invstd) as
+// ---- sums[(2, C)] in fp64; dgamma / dbeta are the local sums, as torch.nn.SyncBatchNorm leaves them to DDP's averaging ----
+__global__ __launch_bounds__(256) void bn_bwd_sums_final_kernel(const MagnetBnBwdArgs a, double* __restrict__ sums) {
+    for (int c = threadIdx.x; c < a.C; c += 256) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int b = 0; b < BB; ++b) { t1 += a.work[((size_t)b * a.C + c) * 2]; t2 += a.work[((size_t)b * a.C + c) * 2 + 1]; }
+        a.dbeta[c] = (float)t1;
+        a.dgamma[c] = (float)t2;
+        sums[c] = t1;
+        sums[a.C + c] = t2;
+    }
+}
+
+// ---- synchronised backward, after the all-gather: sums (world, 2, C) added in rank order and divided by the global count on the
+// ---- device: the two means bn_bwd_apply_kernel reads ----
+__global__ __launch_bounds__(256) void bn_bwd_sync_means_kernel(const MagnetBnBwdArgs a, const double* __restrict__ sums, int world,
+                                                                const double* __restrict__ n_tot) {
+    const double n = n_tot[0];
+    double* m = a.work + (size_t)BB * a.C * 2;
+    for (int c = threadIdx.x; c < a.C; c += 256) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int r = 0; r < world; ++r) { t1 += sums[((size_t)r * 2) * a.C + c]; t2 += sums[((size_t)r * 2 + 1) * a.C + c]; }
         m[2 * c] = t1 / n;
         m[2 * c + 1] = t2 / n;
     }
@@ -252,6 +281,19 @@ __global__ __launch_bounds__(256) void stem_wgrad_final_kernel(const double* __r
 hipError_t launch_bn_train_backward(const MagnetBnBwdArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(BB), dim3(256), 0, s, a);
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(1), dim3(256), 0, s, a);
+    const long long n = (long long)a.N * a.hp * a.wp * a.C;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_backward_sums(const MagnetBnBwdArgs& a, double* sums, hipStream_t s) {
+    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(BB), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(bn_bwd_sums_final_kernel, dim3(1), dim3(256), 0, s, a, sums);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_backward_apply(const MagnetBnBwdArgs& a, const double* sums, int world, const double* n_tot, hipStream_t s) {
+    hipLaunchKernelGGL(bn_bwd_sync_means_kernel, dim3(1), dim3(256), 0, s, a, sums, world, n_tot);
     const long long n = (long long)a.N * a.hp * a.wp * a.C;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();

@@ -7,6 +7,8 @@
 //               reduction in fp64 (MAGNET_BN_BLOCKS workgroups over the positions -> partial sums -> one fixed-order final sum,
 //               no atomics), shifted by the channel's first value so that the variance does not cancel; the final stage writes
 //               mean, 1/sqrt(var + eps) and the running-statistics update on the device
+//   bn_sync     the same statistics over several ranks (nn.SyncBatchNorm): stage 1 as above, a final stage that writes the rank's
+//               (n, mean, M2) record instead, and, after the caller's all-gather, a merge of the records in rank order
 //   bn_apply    y = (x - mean) * invstd * gamma + beta, + an optional split-bf16 residual, optional ReLU, written as split-bf16
 //               planes (border rows zeroed; the output may be a channel slice of a wider buffer) or as fp32
 #include <hip/hip_runtime.h>
@@ -134,6 +136,55 @@ __global__ __launch_bounds__(512) void bn_stats_final_kernel(const MagnetBnTrain
     if (threadIdx.x == 0 && a.num_batches_tracked) a.num_batches_tracked[0] += 1;
 }
 
+// ---- synchronised statistics, local stage 2 (after bn_stats_partial_kernel): thread c sums the BN_BLOCKS partials in order and
+// ---- writes this rank's record (n, mean, M2 = sum (x - mean)^2) as rec[(3, C)].  Unlike the shifted sums, whose shift is the
+// ---- shard's own first value, the record means the same on every rank.  mean / invstd / the running statistics: untouched ----
+__global__ __launch_bounds__(512) void bn_moments_final_kernel(const MagnetBnTrainArgs a, double* __restrict__ rec) {
+    const int h = a.hp - 2 * a.pad, w = a.wp - 2 * a.pad;
+    const double n = (double)((long long)a.N * h * w);
+    for (int c = threadIdx.x; c < a.C; c += 512) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int b = 0; b < BN_BLOCKS; ++b) { t1 += a.work[((size_t)b * a.C + c) * 2]; t2 += a.work[((size_t)b * a.C + c) * 2 + 1]; }
+        const double shift = (double)a.x[tf_row(0, h, w, a.hp, a.wp, a.pad) * a.x_ld + c];
+        const double m2 = t2 - t1 * (t1 / n);
+        rec[c] = n;
+        rec[a.C + c] = shift + t1 / n;
+        rec[2 * a.C + c] = m2 > 0.0 ? m2 : 0.0;
+    }
+}
+
+// ---- synchronised statistics, merge: recs (world, 3, C), the ranks' records in rank order (the all-gather's output, the same
+// ---- bytes on every rank).  Thread c: n_tot = sum n_r, mean = sum n_r mean_r / n_tot, M2 = sum (M2_r + n_r (mean_r - mean)^2), every
+// ---- sum in rank order in fp64; then mean / invstd / n_tot and the running update of bn_stats_final_kernel with the global count ----
+__global__ __launch_bounds__(512) void bn_sync_merge_kernel(const MagnetBnTrainArgs a, const double* __restrict__ recs, int world,
+                                                            double* __restrict__ n_tot) {
+    double m = a.momentum;
+    if (m < 0.0) m = 1.0 / (double)((a.num_batches_tracked ? a.num_batches_tracked[0] : 0) + 1);
+    __syncthreads();                                    // every thread has read num_batches_tracked before it is updated
+    for (int c = threadIdx.x; c < a.C; c += 512) {
+        double n = 0.0, s = 0.0;
+        for (int r = 0; r < world; ++r) {
+            const double* q = recs + (size_t)r * 3 * a.C;
+            n += q[c];
+            s += q[c] * q[a.C + c];
+        }
+        const double mean = s / n;
+        double M2 = 0.0;
+        for (int r = 0; r < world; ++r) {
+            const double* q = recs + (size_t)r * 3 * a.C;
+            const double d = q[a.C + c] - mean;
+            M2 += q[2 * a.C + c] + q[c] * (d * d);
+        }
+        const double var = M2 / n;
+        a.mean[c] = (float)mean;
+        a.invstd[c] = (float)(1.0 / sqrt(var + a.eps));
+        if (a.running_mean) a.running_mean[c] = (float)((1.0 - m) * (double)a.running_mean[c] + m * mean);
+        if (a.running_var) a.running_var[c] = (float)((1.0 - m) * (double)a.running_var[c] + m * var * n / (n - 1.0));
+        if (c == 0) n_tot[0] = n;
+    }
+    if (threadIdx.x == 0 && a.num_batches_tracked) a.num_batches_tracked[0] += 1;
+}
+
 // ---- apply: one thread per (grid row, 8 channels); rows outside the interior write zeros (split output) ----
 __global__ __launch_bounds__(256) void bn_apply_kernel(const MagnetBnTrainArgs a) {
     const int cpr = a.C / 8;
@@ -199,6 +250,17 @@ hipError_t launch_fnet_stem_raw(const float* img, const float* wgt, float* out, 
 hipError_t launch_bn_train_stats(const MagnetBnTrainArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(BN_BLOCKS), dim3(256), 0, s, a);
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3(1), dim3(512), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_moments(const MagnetBnTrainArgs& a, double* rec, hipStream_t s) {
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(BN_BLOCKS), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(bn_moments_final_kernel, dim3(1), dim3(512), 0, s, a, rec);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_merge(const MagnetBnTrainArgs& a, const double* recs, int world, double* n_tot, hipStream_t s) {
+    hipLaunchKernelGGL(bn_sync_merge_kernel, dim3(1), dim3(512), 0, s, a, recs, world, n_tot);
     return hipGetLastError();
 }
 

@@ -282,6 +282,10 @@ _PROTOS = {
     "magnet_gather_views": (_C, [_S(MagnetGatherViewsArgs), _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_fnet_loss_backward": (_C, [_S(MagnetFnetLossArgs), _P]),
+    "magnet_bn_sync_moments": (_C, [_S(MagnetBnTrainArgs), _P, _P]),
+    "magnet_bn_sync_merge": (_C, [_S(MagnetBnTrainArgs), _P, _I, _P, _P]),
+    "magnet_bn_sync_backward_sums": (_C, [_S(MagnetBnBwdArgs), _P, _P]),
+    "magnet_bn_sync_backward_apply": (_C, [_S(MagnetBnBwdArgs), _P, _I, _P, _P]),
     "magnet_dnet_loss_workspace": (_L, [_S(MagnetDnetLossArgs)]),
     "magnet_dnet_loss_forward": (_C, [_S(MagnetDnetLossArgs), _P]),
     "magnet_dnet_loss_backward": (_C, [_S(MagnetDnetLossArgs), _P]),
@@ -1251,23 +1255,87 @@ def wgrad_ex(dy_hi, dy_lo, x_hi, x_lo, rows, wp, taps, cout, cin, grad_w, dil=1,
     _launch("magnet_wgrad_ex", grad_w, ctypes.byref(a))
 
 
-def bn_train_backward(x, grid, mean, invstd, gamma, beta, relu, g, dgamma, dbeta, dx, work):
-    """BatchNorm2d backward (batch statistics).  x: the saved fp32 pre-BN grid; g: fp32 gradient grid (views allowed, unit channel
-    stride); dx = (hi, lo) split planes written over the whole grid."""
+def _bn_bwd_args(who, x, grid, mean, invstd, gamma, beta, relu, g, work, dgamma=None, dbeta=None, dx=None):
+    """The MagnetBnBwdArgs of one BatchNorm backward launch, with the buffer-size checks; dgamma / dbeta / dx as the launch takes them."""
     N, hp, wp, pad, C = (int(v) for v in grid)
     rows = N * hp * wp
     for t, n in ((x, "x"), (g, "g")):
         if not t.is_cuda or t.dtype != torch.float32 or t.stride(1) != 1 or t.shape[0] < rows or t.shape[1] < C:
-            raise MagnetError(f"bn_train_backward: {n} must be a (>= {rows}, >= {C}) float32 GPU tensor with unit channel stride")
-    if dx[0].shape[0] < rows or work.numel() < (BN_BLOCKS * 2 + 2) * C:
-        raise MagnetError("bn_train_backward: dx or the workspace too small")
+            raise MagnetError(f"{who}: {n} must be a (>= {rows}, >= {C}) float32 GPU tensor with unit channel stride")
+    if (dx is not None and dx[0].shape[0] < rows) or work.numel() < (BN_BLOCKS * 2 + 2) * C:
+        raise MagnetError(f"{who}: dx or the workspace too small")
     a = MagnetBnBwdArgs(x=x.data_ptr(), x_ld=x.stride(0), N=N, hp=hp, wp=wp, pad=pad, C=C, relu=int(bool(relu)),
                         mean=_dev(mean, "mean", torch.float32).data_ptr(), invstd=_dev(invstd, "invstd", torch.float32).data_ptr(),
                         gamma=_dev(gamma, "gamma", torch.float32).data_ptr(), beta=_dev(beta, "beta", torch.float32).data_ptr(),
-                        g=g.data_ptr(), g_ld=g.stride(0), work=_dev(work, "work", torch.float64).data_ptr(),
-                        dgamma=_dev(dgamma, "dgamma", torch.float32).data_ptr(), dbeta=_dev(dbeta, "dbeta", torch.float32).data_ptr(),
-                        dx_hi=_bf16_ptr(dx[0], "dx_hi"), dx_lo=_bf16_ptr(dx[1], "dx_lo"), dx_ld=dx[0].stride(0))
+                        g=g.data_ptr(), g_ld=g.stride(0), work=_dev(work, "work", torch.float64).data_ptr())
+    if dgamma is not None:
+        a.dgamma, a.dbeta = _dev(dgamma, "dgamma", torch.float32).data_ptr(), _dev(dbeta, "dbeta", torch.float32).data_ptr()
+    if dx is not None:
+        a.dx_hi, a.dx_lo, a.dx_ld = _bf16_ptr(dx[0], "dx_hi"), _bf16_ptr(dx[1], "dx_lo"), dx[0].stride(0)
+    return a
+
+
+def bn_train_backward(x, grid, mean, invstd, gamma, beta, relu, g, dgamma, dbeta, dx, work):
+    """BatchNorm2d backward (batch statistics).  x: the saved fp32 pre-BN grid; g: fp32 gradient grid (views allowed, unit channel
+    stride); dx = (hi, lo) split planes written over the whole grid."""
+    a = _bn_bwd_args("bn_train_backward", x, grid, mean, invstd, gamma, beta, relu, g, work, dgamma, dbeta, dx)
     _launch("magnet_bn_train_backward", x, ctypes.byref(a))
+
+
+# ---- synchronised BatchNorm (include/magnet_hip.h: magnet_bn_sync_*): the launches before and after the caller's all-gather ----
+def _f64_buf(t, name, numel):
+    if _dev(t, name, torch.float64).numel() < numel:
+        raise MagnetError(f"{name} holds fewer than {numel} doubles")
+    return t.data_ptr()
+
+
+def bn_sync_moments(x, grid, work, record):
+    """This rank's (n, mean, M2) per channel over the interior of the grid (as bn_train's x and grid) -> record, fp64 (3, C)."""
+    N, hp, wp, pad, C = (int(v) for v in grid)
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] < C:
+        raise MagnetError("bn_sync_moments: x must be a (rows, >= C) float32 GPU tensor with unit channel stride")
+    if x.shape[0] < N * hp * wp:
+        raise MagnetError(f"bn_sync_moments: x holds fewer than the grid's {N * hp * wp} rows")
+    a = MagnetBnTrainArgs(x=x.data_ptr(), x_ld=x.stride(0), N=N, hp=hp, wp=wp, pad=pad, C=C, work=_f64_buf(work, "work", BN_BLOCKS * C * 2))
+    _launch("magnet_bn_sync_moments", x, ctypes.byref(a), _f64_buf(record, "record", 3 * C))
+
+
+def bn_sync_merge(records, C, mean, invstd, n_tot, eps, momentum, running_mean=None, running_var=None, num_batches_tracked=None):
+    """records: fp64 (world, 3, C), the ranks' bn_sync_moments records in rank order -> the global mean, invstd (fp32 (C)) and
+    n_tot (fp64, one element), and the running-statistics update of bn_train with the global count.  momentum None: cumulative."""
+    C = int(C)
+    if not isinstance(records, torch.Tensor) or records.dim() != 3 or tuple(records.shape[1:]) != (3, C):
+        raise MagnetError(f"bn_sync_merge: records must be (world, 3, {C})")
+    world = records.shape[0]
+    a = MagnetBnTrainArgs(C=C, mean=_dev(mean, "mean", torch.float32).data_ptr(), invstd=_dev(invstd, "invstd", torch.float32).data_ptr(),
+                          eps=float(eps), momentum=-1.0 if momentum is None else float(momentum))
+    if mean.numel() < C or invstd.numel() < C:
+        raise MagnetError("bn_sync_merge: mean / invstd hold fewer than C values")
+    for t, n in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            if t.numel() < C:
+                raise MagnetError(f"bn_sync_merge: {n} holds fewer than C values")
+            setattr(a, n, _dev(t, n, torch.float32).data_ptr())
+    if num_batches_tracked is not None:
+        a.num_batches_tracked = _dev(num_batches_tracked, "num_batches_tracked", torch.int64).data_ptr()
+    _launch("magnet_bn_sync_merge", records, ctypes.byref(a), _f64_buf(records, "records", world * 3 * C), world, _f64_buf(n_tot, "n_tot", 1))
+
+
+def bn_sync_backward_sums(x, grid, mean, invstd, gamma, beta, relu, g, dgamma, dbeta, work, sums):
+    """This rank's (sum g', sum g' xhat) per channel, xhat from the global mean / invstd -> sums, fp64 (2, C); dgamma / dbeta get
+    the same local sums.  Arguments as bn_train_backward."""
+    a = _bn_bwd_args("bn_sync_backward_sums", x, grid, mean, invstd, gamma, beta, relu, g, work, dgamma, dbeta)
+    _launch("magnet_bn_sync_backward_sums", x, ctypes.byref(a), _f64_buf(sums, "sums", 2 * a.C))
+
+
+def bn_sync_backward_apply(x, grid, mean, invstd, gamma, beta, relu, g, dx, work, sums, n_tot):
+    """sums: fp64 (world, 2, C), the ranks' bn_sync_backward_sums in rank order; n_tot: bn_sync_merge's -> dx = (hi, lo) split
+    planes over the whole grid of this rank."""
+    a = _bn_bwd_args("bn_sync_backward_apply", x, grid, mean, invstd, gamma, beta, relu, g, work, dx=dx)
+    if not isinstance(sums, torch.Tensor) or sums.dim() != 3 or tuple(sums.shape[1:]) != (2, a.C):
+        raise MagnetError(f"bn_sync_backward_apply: sums must be (world, 2, {a.C})")
+    world = sums.shape[0]
+    _launch("magnet_bn_sync_backward_apply", x, ctypes.byref(a), _f64_buf(sums, "sums", world * 2 * a.C), world, _f64_buf(n_tot, "n_tot", 1))
 
 
 def fnet_grad_pack(g_nchw, out_hi, out_lo, pad):

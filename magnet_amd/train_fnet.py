@@ -18,6 +18,17 @@ magnet_fnet_d2s_backward.  Gradient fan-in (unit input = conv1 + shortcut, raw =
 is summed in a fixed order, in the convolution epilogue (addend) or in magnet_spp_pool_backward.  The stem's weight gradient is
 magnet_fnet_stem_wgrad.  Every sum has a fixed order and no atomics: two identical steps give bit-identical .grad.
 
+Synchronised BatchNorm (the reference's multi-GPU pattern, train_FNet.py:220-222: nn.SyncBatchNorm.convert_sync_batchnorm, then
+DistributedDataParallel): a slot that holds an nn.SyncBatchNorm in training mode, with torch.distributed initialised and more than
+one rank in the module's process group (sync_group), takes its statistics over all ranks' shards.  Forward: the rank's fp64
+(n, mean, M2) record per channel (magnet_bn_sync_moments), one all-gather on the module's group, the records merged in rank order
+(magnet_bn_sync_merge: every rank does the same arithmetic on the same bytes, so mean, invstd and the running statistics are
+bit-identical across ranks), then the same apply.  Backward: the rank's sums of g' and g' xhat (magnet_bn_sync_backward_sums), one
+all-gather, the sums added in rank order and dx (magnet_bn_sync_backward_apply).  dgamma / dbeta stay the rank's own sums, as
+torch.nn.SyncBatchNorm leaves them: DDP averages parameter gradients.  Ranks may hold different numbers of images (H, W agree);
+a rank needs one pooled cell, not two.  Every other case (BatchNorm2d, no process group, one rank, .eval()) runs the launches
+above unchanged.
+
 Memory kept for the backward per image (P2 = (H/2+2)(W/2+2), P4 = (H/4+4)(W/4+4) grid rows): every layer's fp32 pre-BN output
 and split-bf16 output, P2 x 8 layers x 32 ch x 8 B + P4 x (34 x 64 + 12 x 128 + 128 + 320 + 128) ch x 8 B: about 0.9 GB at
 480 x 640.  Under no_grad nothing is kept.
@@ -25,6 +36,7 @@ and split-bf16 output, P2 x 8 layers x 32 ch x 8 B + P4 x (34 x 64 + 12 x 128 + 
 from __future__ import annotations
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 
 from . import lib
@@ -32,22 +44,51 @@ from .fnet import _SPP, convs
 from .planes import PackCache, pack_s2d, pack_taps, planes, s2d_matrix, split_bf16
 
 
-def check_input(img: torch.Tensor, psm: nn.Module):
-    """The shapes the training forward supports (those FNetMFMA accepts): raises MagnetError before any launch."""
+def sync_group(bn: nn.Module):
+    """The process group over which the BatchNorm slot `bn` synchronises its statistics, or None for the single-process launches:
+    an nn.SyncBatchNorm in training mode, torch.distributed initialised, and more than one rank in the module's process_group
+    (None: the default group) - the conditions under which torch's own SyncBatchNorm synchronises."""
+    if not isinstance(bn, nn.SyncBatchNorm) or not bn.training:
+        return None
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    group = bn.process_group if bn.process_group is not None else dist.group.WORLD
+    return group if dist.get_world_size(group) > 1 else None
+
+
+def bn_merge_records(records):
+    """The merge of magnet_bn_sync_merge in Python floats (fp64), in rank order: records = [(n_r, mean_r, M2_r), ...] of one channel,
+    M2_r = sum (x - mean_r)^2 over the shard -> (n_tot, mean, M2) of the concatenated data (Chan et al.'s pairwise update, stated
+    for all ranks at once): n_tot = sum n_r, mean = sum n_r mean_r / n_tot, M2 = sum (M2_r + n_r (mean_r - mean)^2)."""
+    n_tot, s = 0.0, 0.0
+    for n, mean, _ in records:
+        n_tot += n
+        s += n * mean
+    mean_tot = s / n_tot
+    M2 = 0.0
+    for n, mean, m2 in records:
+        d = mean - mean_tot
+        M2 += m2 + n * (d * d)
+    return n_tot, mean_tot, M2
+
+
+def check_input(img: torch.Tensor, psm: nn.Module, sync: bool = False):
+    """The shapes the training forward supports (those FNetMFMA accepts): raises MagnetError before any launch.  sync: the
+    statistics are taken over several ranks (sync_group), so one pooled cell on this rank is enough."""
     if img.dim() != 4 or img.shape[1] != 3:
         raise lib.MagnetError(f"F-Net training forward: image batch must be (N, 3, H, W), got {tuple(img.shape)}")
     N, _, H, W = img.shape
     H4, W4 = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
     if H4 < 64 or W4 < 64:
         raise lib.MagnetError(f"F-Net training forward: input {H}x{W} too small for the 64x64 pooling branch (needs H/4, W/4 >= 64)")
-    if N * (H4 // 64) * (W4 // 64) < 2:
+    if N * (H4 // 64) * (W4 // 64) < (1 if sync else 2):
         raise lib.MagnetError("F-Net training forward: BatchNorm with batch statistics needs at least 2 values per channel, and "
                               f"branch1 pools {N} image(s) of {H}x{W} to {N * (H4 // 64) * (W4 // 64)} cell(s)")
     fd = psm.lastconv[2].weight.shape[0]
     if fd not in (16, 32, 64, 128):
         raise lib.MagnetError(f"F-Net training forward: feature_dim {fd} unsupported (16, 32, 64, 128)")
     for m in psm.modules():
-        if isinstance(m, nn.BatchNorm2d) and not m.affine:
+        if isinstance(m, (nn.BatchNorm2d, nn.SyncBatchNorm)) and not m.affine:
             raise lib.MagnetError("F-Net training forward: BatchNorm2d without affine parameters is not supported")
     if not img.is_cuda:
         raise lib.MagnetError("F-Net training forward: image must be on the GPU (no CPU fallback)")
@@ -82,6 +123,17 @@ def dgrad_pack_s2d(w: torch.Tensor):
     """Input-gradient weights of the space-to-depth 2x2 window: tap t takes the window's tap 3 - t, transposed -> (4, 4C, cout).
     Run over the gradient read wp + 1 rows further, the window's offsets (-wp-1, -wp, -1, 0) become (0, 1, wp, wp+1): the mirror."""
     return split_bf16(s2d_matrix(w).flip(0).transpose(1, 2).contiguous())
+
+
+def _all_gather(t: torch.Tensor, group):
+    """(world, *t.shape): t of every rank of `group`, in rank order, on every rank.  One collective; gloo has no
+    all_gather_into_tensor, so there the ranks' slices of the one output buffer go as a tensor list (as torch's SyncBatchNorm does)."""
+    out = torch.empty((dist.get_world_size(group),) + tuple(t.shape), dtype=t.dtype, device=t.device)
+    if dist.get_backend(group) == "gloo":
+        dist.all_gather(list(out.unbind(0)), t, group=group)
+    else:
+        dist.all_gather_into_tensor(out, t, group=group)
+    return out
 
 
 class FNetTrainHIP:
@@ -121,11 +173,22 @@ class FNetTrainHIP:
         bn = self._bn_mods[name]
         C = grid[-1]
         stats = torch.empty(2, C, dtype=torch.float32, device=z.device)
-        lib.bn_train(z, grid, stats[0], stats[1], self._ws(z.device, lib.BN_BLOCKS * 320 * 2), bn.weight.detach(), bn.bias.detach(),
+        work = self._ws(z.device, lib.BN_BLOCKS * 320 * 2)
+        group = sync_group(bn)
+        sync = {}
+        if group is not None:
+            # the rank's record -> every rank's records, in rank order -> the global statistics; the apply below is the same launch
+            record = torch.empty(3, C, dtype=torch.float64, device=z.device)
+            lib.bn_sync_moments(z, grid, work, record)
+            n_tot = torch.empty(1, dtype=torch.float64, device=z.device)
+            lib.bn_sync_merge(_all_gather(record, group), C, stats[0], stats[1], n_tot, bn.eps, bn.momentum, running_mean=bn.running_mean,
+                              running_var=bn.running_var, num_batches_tracked=bn.num_batches_tracked)
+            sync = dict(n_tot=n_tot, group=group)
+        lib.bn_train(z, grid, stats[0], stats[1], work, bn.weight.detach(), bn.bias.detach(),
                      bn.eps, bn.momentum, running_mean=bn.running_mean, running_var=bn.running_var,
-                     num_batches_tracked=bn.num_batches_tracked, res=res, relu=relu, out=out, out_f32=out_f32)
+                     num_batches_tracked=bn.num_batches_tracked, res=res, relu=relu, out=out, out_f32=out_f32, stats=group is None)
         if self.rec is not None:
-            self.rec[name].update(z=z, stats=stats, grid=grid, relu=relu)
+            self.rec[name].update(z=z, stats=stats, grid=grid, relu=relu, **sync)
 
     def _layer(self, name, src, in_ld, cin, taps, wp, rows, grid, relu, dst, res=None, dil=0):
         hi, lo, zb, cout = self._packed[name]
@@ -140,7 +203,7 @@ class FNetTrainHIP:
         """img (N,3,H,W) fp32 on the GPU -> the (N,F,H/4,W/4) fp32 NCHW features of the module in training mode; every
         BatchNorm2d's running statistics and num_batches_tracked are updated once.  save: keep what backward() needs."""
         psm = self.psm
-        check_input(img, psm)
+        check_input(img, psm, sync=sync_group(psm.branch1[1][1]) is not None)  # branch1 pools to the fewest cells
         img = img.detach().float().contiguous()
         N, _, H, W = img.shape
         dev = img.device
@@ -248,8 +311,14 @@ class FNetTrainHIP:
         dz = planes(rows, grid[4], g.device)
         dgamma = torch.empty_like(bn.weight, dtype=torch.float32)
         dbeta = torch.empty_like(bn.bias, dtype=torch.float32)
-        lib.bn_train_backward(r["z"], grid, r["stats"][0], r["stats"][1], bn.weight.detach(), bn.bias.detach(), r["relu"], g, dgamma,
-                              dbeta, dz, self._ws(g.device, (lib.BN_BLOCKS * 2 + 2) * 320))
+        work = self._ws(g.device, (lib.BN_BLOCKS * 2 + 2) * 320)
+        bn_args = (r["z"], grid, r["stats"][0], r["stats"][1], bn.weight.detach(), bn.bias.detach(), r["relu"], g)
+        if "group" in r:                                            # the forward synchronised: so does the backward
+            sums = torch.empty(2, grid[4], dtype=torch.float64, device=g.device)
+            lib.bn_sync_backward_sums(*bn_args, dgamma, dbeta, work, sums)
+            lib.bn_sync_backward_apply(*bn_args, dz, work, _all_gather(sums, r["group"]), r["n_tot"])
+        else:
+            lib.bn_train_backward(*bn_args, dgamma, dbeta, dz, work)
         self.grads[id(bn.weight)], self.grads[id(bn.bias)] = dgamma, dbeta
         return dz
 
