@@ -8,7 +8,7 @@ the backbones are caller-provided (stub D-Net/F-Net here), and the metric reduct
 
     python eval_synthetic.py --frames 8 --batch 2 [--D 5] [--iters 3] [--V 4] [--log out.txt]
     python eval_synthetic.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
-    python eval_synthetic.py --dataset_path ROOT --split split.txt --reuse_backbones [--pool_frames 64]
+    python eval_synthetic.py --dataset_path ROOT --split split.txt --reuse_backbones [--pool_frames 64] [--graph]
 """
 import argparse
 import os
@@ -143,8 +143,13 @@ def main():
                          "(magnet_amd/sequence.py); frame ids are the loader's (scene_name, img_idx).  The torch stand-in backbones round differently "
                          "in a batch of another size, so the metrics agree with the default run's to about 7 digits, not to the bit")
     ap.add_argument("--pool_frames", type=int, default=64, help="with --reuse_backbones: frames the pool holds (least recently used go first)")
+    ap.add_argument("--graph", action="store_true",
+                    help="with --reuse_backbones: replay every step as HIP graphs (SequenceRunner(graph=True)): the same metrics, fewer launches "
+                         "from the host; pays when few frames are new per call")
     E.add_arguments(ap)
     a = ap.parse_args()
+    if a.graph and not a.reuse_backbones:
+        ap.error("--graph is a mode of --reuse_backbones (SequenceRunner(graph=True)): give both")
     if a.reuse_backbones and not a.dataset_path:
         raise SystemExit("--reuse_backbones needs --dataset_path: the synthetic windows share no frames")
     rank, world, device, sharded = E.start(a, __file__)
@@ -171,7 +176,7 @@ def main():
         loader = FolderBatches(ds, a.batch)
         if a.reuse_backbones:
             from magnet_amd.sequence import SequenceRunner
-            runner = SequenceRunner(model, a.pool_frames)
+            runner = SequenceRunner(model, a.pool_frames, graph=True) if a.graph else SequenceRunner(model, a.pool_frames)
         title = "scannet-format folder %s (%d windows) V=%d D=%d iters=%d" % (a.dataset_path, len(ds), a.V, a.D, a.iters)
     else:
         loader = SyntheticWindows((a.frames + a.batch - 1) // a.batch, a.batch, a.V, a.input_height, a.input_width, nan_every=3)

@@ -780,6 +780,35 @@ typedef struct MagnetGatherViewsArgs {
 } MagnetGatherViewsArgs;
 MAGNET_API int magnet_gather_views(const MagnetGatherViewsArgs *args, void *stream);
 
+/* magnet_scatter_frames is the inverse of magnet_gather_views: it writes the staged backbone outputs of n frames into the pool in one
+ * launch.  `slots` (n int32, on the device): entry [j] is the destination slot of staged frame j, so the launch has the same
+ * arguments whatever slots the host picked (a captured HIP graph replays it with another table).  Sources, each optional (NULL skips
+ * it and leaves its pool tensor untouched; xd3_hi and xd3_lo go together); a source that is given needs its pool tensor:
+ *   feat            (n, h+2, w+2, F) padded channel-last features in feat_dtype
+ *   gmm             (n, 2, h, w) fp32 [mu, sigma]
+ *   xd3_hi / xd3_lo (n, (h+2)(w+2), 256) split-bf16 planes
+ * Whole frames are copied bit for bit, borders included.  An entry < 0 or >= n_slots means "skip this frame": nothing is written for
+ * it.  Every destination offset is slot x frame + (offset inside one frame): the kernel never writes outside the pool whatever the
+ * table holds.  Two entries that name the same slot are the caller's error: one of the two frames wins, per 32 KiB piece of the frame
+ * (the slot may end up holding pieces of both).
+ * feat, the x_d3 planes and their pool tensors 16-byte aligned, F % 8 == 0; gmm, pool_gmm and slots only 4-byte (16-byte vectors are
+ * used where a source frame and its destination are misaligned alike, single floats otherwise). */
+typedef struct MagnetScatterFramesArgs {
+    const int32_t *slots;                  /* (n) int32 on the device: destination slot of staged frame j */
+    int32_t        n_slots;
+    int32_t        n, h, w, F;
+    int32_t        feat_dtype;             /* MAGNET_FEAT_* */
+    const void    *feat;
+    const float   *gmm;
+    const void    *xd3_hi;
+    const void    *xd3_lo;
+    void          *pool_feat;
+    float         *pool_gmm;
+    void          *pool_xd3_hi;
+    void          *pool_xd3_lo;
+} MagnetScatterFramesArgs;
+MAGNET_API int magnet_scatter_frames(const MagnetScatterFramesArgs *args, void *stream);
+
 /* FnetLoss: the tail of the F-Net training step (train_FNet.py:95-104) on the raw volume x (B, D, h, w) of
  * magnet_cost_volume_cw(mode = 1): p = softmax over the D bins, pred = sum_j p_j d_j, loss = mean over the valid pixels of
  * |pred - gt|, valid iff gt > min_depth && !(gt > max_depth) (the driver's gt[gt > max_depth] = 0; mask = gt > min_depth, which needs

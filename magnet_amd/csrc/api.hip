@@ -60,6 +60,7 @@ hipError_t launch_dnet_loss_backward(const MagnetDnetLossArgs&, hipStream_t);
 hipError_t launch_dnet_nll_forward(const MagnetDnetNllArgs&, hipStream_t);
 hipError_t launch_dnet_nll_backward(const MagnetDnetNllArgs&, hipStream_t);
 hipError_t launch_gather_views(const MagnetGatherViewsArgs&, hipStream_t);
+hipError_t launch_scatter_frames(const MagnetScatterFramesArgs&, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -1165,6 +1166,30 @@ MAGNET_API int magnet_gather_views(const MagnetGatherViewsArgs* a, void* stream)
         return fail(MAGNET_E_ALIGN, "magnet_gather_views: slots and the (mu, sigma) tensors must be 4-byte aligned");
     hipError_t e = magnet::launch_gather_views(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_gather_views launch");
+}
+
+MAGNET_API int magnet_scatter_frames(const MagnetScatterFramesArgs* a, void* stream) {
+    if (!a || !a->slots) return fail(MAGNET_E_NULL, "magnet_scatter_frames: NULL pointer");
+    if (a->feat && !a->pool_feat) return fail(MAGNET_E_NULL, "magnet_scatter_frames: feat needs pool_feat");
+    if (a->gmm && !a->pool_gmm) return fail(MAGNET_E_NULL, "magnet_scatter_frames: gmm needs pool_gmm");
+    if ((a->xd3_hi != nullptr) != (a->xd3_lo != nullptr))
+        return fail(MAGNET_E_DIM, "magnet_scatter_frames: xd3_hi and xd3_lo go together");
+    if (a->xd3_hi && (!a->pool_xd3_hi || !a->pool_xd3_lo))
+        return fail(MAGNET_E_NULL, "magnet_scatter_frames: the x_d3 planes need both x_d3 pool planes");
+    if (a->feat_dtype != MAGNET_FEAT_F32 && a->feat_dtype != MAGNET_FEAT_BF16)
+        return fail(MAGNET_E_DTYPE, "magnet_scatter_frames: unknown dtype %d", a->feat_dtype);
+    const long long R = ((long long)a->h + 2) * ((long long)a->w + 2);
+    if (a->n_slots <= 0 || a->n <= 0 || a->h <= 0 || a->w <= 0 || a->F <= 0 || (a->F % 8) != 0 || 2LL * a->n > 0x7fffffffLL ||
+        R * 32 > 0x7fffffffLL || R * a->F / 4 > 0x7fffffffLL)
+        return fail(MAGNET_E_DIM, "magnet_scatter_frames: bad dims n_slots=%d n=%d h=%d w=%d F=%d (F must be a multiple of 8)",
+                    a->n_slots, a->n, a->h, a->w, a->F);
+    if (!aligned16(a->feat) || !aligned16(a->xd3_hi) || !aligned16(a->xd3_lo) || !aligned16(a->pool_feat) ||
+        !aligned16(a->pool_xd3_hi) || !aligned16(a->pool_xd3_lo))
+        return fail(MAGNET_E_ALIGN, "magnet_scatter_frames: features, x_d3 planes and their pool tensors must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(a->gmm) | reinterpret_cast<uintptr_t>(a->pool_gmm) | reinterpret_cast<uintptr_t>(a->slots)) & 3u)
+        return fail(MAGNET_E_ALIGN, "magnet_scatter_frames: slots and the (mu, sigma) tensors must be 4-byte aligned");
+    hipError_t e = magnet::launch_scatter_frames(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_scatter_frames launch");
 }
 
 }  // extern "C"

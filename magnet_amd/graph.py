@@ -11,7 +11,10 @@ fresh processes: profiles/latency/bench_frames1.jsonl).  What remains is the ser
 (one frame = 152 convolution tiles of 128 rows for 256 CUs; on 64-row tiles, ConvStackMFMA.small_tiles = True, the replayed shipped
 step takes 0.2938 against 0.2986 ms and the C2 step 0.1882 against 0.1874 ms, not a gain in every pair at every workload, so it is opt-in:
 profiles/latency/NOTES.md) — batching frames is what pays.  Inputs are copied into the graph's static tensors (device-to-device,
-a few MB); outputs are the graph's static output tensors (clone them to keep a result across replays)."""
+a few MB); outputs are the graph's static output tensors (clone them to keep a result across replays).
+
+`GraphedRefine` covers `match_and_refine` on NCHW tensors alone.  A stream of frames, with the backbones, the frame pool's gather and
+the packed / in-place forms inside the replayed step, is `magnet_amd.sequence.SequenceRunner(model, capacity, graph=True)`."""
 from __future__ import annotations
 
 import torch

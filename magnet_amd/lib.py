@@ -213,6 +213,14 @@ class MagnetGatherViewsArgs(ctypes.Structure):
                 ("gin_hi", ctypes.c_void_p), ("gin_lo", ctypes.c_void_p), ("gin_ld", ctypes.c_int64), ("gin_c_off", ctypes.c_int32)]
 
 
+class MagnetScatterFramesArgs(ctypes.Structure):
+    """Mirror of `struct MagnetScatterFramesArgs` (include/magnet_hip.h)."""
+    _fields_ = [("slots", ctypes.c_void_p), ("n_slots", ctypes.c_int32),
+                ("n", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("F", ctypes.c_int32), ("feat_dtype", ctypes.c_int32),
+                ("feat", ctypes.c_void_p), ("gmm", ctypes.c_void_p), ("xd3_hi", ctypes.c_void_p), ("xd3_lo", ctypes.c_void_p),
+                ("pool_feat", ctypes.c_void_p), ("pool_gmm", ctypes.c_void_p), ("pool_xd3_hi", ctypes.c_void_p), ("pool_xd3_lo", ctypes.c_void_p)]
+
+
 # (restype, argtypes) of every MAGNET_API declaration of include/magnet_hip.h, in header order; load() applies them all
 _C, _L, _F, _I, _P, _S = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER
 _PROTOS = {
@@ -280,6 +288,7 @@ _PROTOS = {
     "magnet_dnet_gauss_head": (_C, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
     "magnet_gather_views": (_C, [_S(MagnetGatherViewsArgs), _P]),
+    "magnet_scatter_frames": (_C, [_S(MagnetScatterFramesArgs), _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_fnet_loss_backward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_bn_sync_moments": (_C, [_S(MagnetBnTrainArgs), _P, _P]),
@@ -1414,7 +1423,7 @@ def dnet_upsample_gauss(head_out, head_ld, mask_out, mask_ld, N, h, w, out):
     return out
 
 
-# ---- sequence inference (include/magnet_hip.h: magnet_gather_views; csrc/frame_pool.hip; magnet_amd/sequence.py) -------------------
+# ---- sequence inference (include/magnet_hip.h: magnet_gather_views, magnet_scatter_frames; csrc/frame_pool.hip; magnet_amd/sequence.py) -------------------
 def gather_views(slots, B, V, pool_feat=None, pool_gmm=None, pool_xd3=None, ref_cl=None, src_pad=None, ref_gmm=None, src_gmm=None,
                  gin=None):
     """One launch from the frame pool into a step's input buffers through the device slot table `slots` ((1 + V) B int32: [b] the
@@ -1500,3 +1509,64 @@ def gather_views(slots, B, V, pool_feat=None, pool_gmm=None, pool_xd3=None, ref_
     if any(x.device != t.device for x in used):
         raise MagnetError("gather_views: all tensors must be on the same device")
     _launch("magnet_gather_views", t, ctypes.byref(a))
+
+
+def scatter_frames(slots, pool_feat=None, pool_gmm=None, pool_xd3=None, feat=None, gmm=None, xd3=None):
+    """The inverse of gather_views, one launch: staged frame j of every source that is given goes to slot slots[j] of its pool tensor
+    (`slots`: (n,) int32 on the device; an entry outside [0, n_slots) skips the frame; two entries naming one slot are the caller's
+    error).  feat (n, h+2, w+2, F) in pool_feat's dtype, gmm (n, 2, h, w) fp32, xd3 = (hi, lo) bf16 planes (n, (h+2)(w+2), 256) — or
+    (n (h+2)(w+2), 256), the staging planes as the D-Net writes them.  Whole frames are copied bit for bit, borders included; a source
+    left out leaves its pool tensor untouched."""
+    t = _dev(slots, "slots", torch.int32)
+    if t.dim() != 1 or t.shape[0] < 1:
+        raise MagnetError(f"scatter_frames: slots has shape {tuple(t.shape)}, expected (n,) with n >= 1")
+    n = int(t.shape[0])
+    a = MagnetScatterFramesArgs(slots=t.data_ptr(), n=n, F=8)
+    used = [t]
+    geom = None                                                  # (n_slots, h, w)
+    if feat is not None:
+        if pool_feat is None:
+            raise MagnetError("scatter_frames: feat needs pool_feat")
+        p = _dev(pool_feat, "pool_feat")
+        if p.dim() != 4 or p.shape[1] < 3 or p.shape[2] < 3:
+            raise MagnetError(f"scatter_frames: pool_feat must be (n_slots, h+2, w+2, F), got {tuple(p.shape)}")
+        f = _dev(feat, "feat", p.dtype)
+        if tuple(f.shape) != (n,) + tuple(p.shape[1:]):
+            raise MagnetError(f"scatter_frames: feat has shape {tuple(f.shape)}, expected {(n,) + tuple(p.shape[1:])}")
+        geom = (int(p.shape[0]), int(p.shape[1]) - 2, int(p.shape[2]) - 2)
+        a.feat, a.pool_feat, a.F, a.feat_dtype = f.data_ptr(), p.data_ptr(), int(p.shape[3]), feat_enum(p.dtype)
+        used += [p, f]
+    if gmm is not None:
+        if pool_gmm is None:
+            raise MagnetError("scatter_frames: gmm needs pool_gmm")
+        p = _dev(pool_gmm, "pool_gmm", torch.float32)
+        if p.dim() != 4 or p.shape[1] != 2:
+            raise MagnetError(f"scatter_frames: pool_gmm must be (n_slots, 2, h, w), got {tuple(p.shape)}")
+        g = _dev(gmm, "gmm", torch.float32)
+        if tuple(g.shape) != (n,) + tuple(p.shape[1:]):
+            raise MagnetError(f"scatter_frames: gmm has shape {tuple(g.shape)}, expected {(n,) + tuple(p.shape[1:])}")
+        here = (int(p.shape[0]), int(p.shape[2]), int(p.shape[3]))
+        if geom is not None and geom != here:
+            raise MagnetError(f"scatter_frames: pool_gmm is for {here[0]} slots of {here[1]} x {here[2]}, pool_feat for {geom[0]} of {geom[1]} x {geom[2]}")
+        geom = here
+        a.gmm, a.pool_gmm = g.data_ptr(), p.data_ptr()
+        used += [p, g]
+    if xd3 is not None:
+        if pool_xd3 is None:
+            raise MagnetError("scatter_frames: xd3 needs pool_xd3")
+        if geom is None:
+            raise MagnetError("scatter_frames: the x_d3 planes do not carry h and w: pass feat or gmm (and their pool tensor) with them")
+        R = (geom[1] + 2) * (geom[2] + 2)
+        for x, name in zip(tuple(pool_xd3) + tuple(xd3), ("pool_xd3 hi plane", "pool_xd3 lo plane", "xd3 hi plane", "xd3 lo plane")):
+            x = _dev(x, name, torch.bfloat16)
+            ok = ((geom[0], R, 256),) if name.startswith("pool") else ((n, R, 256), (n * R, 256))
+            if tuple(x.shape) not in ok:
+                raise MagnetError(f"scatter_frames: {name} has shape {tuple(x.shape)}, expected {ok[0]}")
+            used.append(x)
+        a.pool_xd3_hi, a.pool_xd3_lo, a.xd3_hi, a.xd3_lo = (x.data_ptr() for x in tuple(pool_xd3) + tuple(xd3))
+    if geom is None:
+        raise MagnetError("scatter_frames: no source given")
+    a.n_slots, a.h, a.w = geom
+    if any(x.device != t.device for x in used):
+        raise MagnetError("scatter_frames: all tensors must be on the same device")
+    _launch("magnet_scatter_frames", t, ctypes.byref(a))
