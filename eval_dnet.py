@@ -109,12 +109,18 @@ def main():
                     help="folder layout; the split file has '<scene> <frame>' or '<scene> <sequence> <frame>' lines")
     ap.add_argument("--garg_crop", action="store_true", help="KITTI: evaluate inside the Garg ECCV16 window (test_DNet.py:56-58)")
     ap.add_argument("--eigen_crop", action="store_true", help="KITTI: evaluate inside the Eigen NIPS14 window (test_DNet.py:59-61)")
+    ap.add_argument("--encoder", default="standin", choices=["standin", "b5"],
+                    help="'standin' (default): the seeded stand-in encoder; 'b5': the EfficientNet-B5 encoder (magnet_amd/encoder.py), calibrated seeded weights")
+    ap.add_argument("--encoder_backend", default="torch", choices=["torch", "hip"], help="with --encoder b5: run the encoder's torch modules or EncoderMFMA")
     E.add_arguments(ap)
     a = ap.parse_args()
+    if a.encoder_backend == "hip" and a.encoder != "b5":
+        ap.error("--encoder_backend hip is a mode of --encoder b5")
     rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.standin import make_dnet
     args = argparse.Namespace(min_depth=a.min_depth, max_depth=a.max_depth, garg_crop=a.garg_crop, eigen_crop=a.eigen_crop)
-    model = make_dnet(dnet=True, backend=a.backend, split_k="auto" if a.split_k == "auto" else 0, precision=a.precision).to(device).eval()    # seeded weights unless the caller loads a checkpoint
+    model = make_dnet(dnet=True, backend=a.backend, split_k="auto" if a.split_k == "auto" else 0, precision=a.precision,
+                      encoder=a.encoder, encoder_backend=a.encoder_backend).to(device).eval()    # seeded weights unless the caller loads a checkpoint
     if a.dataset_path:
         from magnet_amd import data
         with open(a.split) as f:

@@ -146,8 +146,14 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="with --reuse_backbones: replay every step as HIP graphs (SequenceRunner(graph=True)): the same metrics, fewer launches "
                          "from the host; pays when few frames are new per call")
+    ap.add_argument("--encoder", default="standin", choices=["standin", "b5"],
+                    help="the D-Net: 'standin' (default) is the seeded stub D-Net; 'b5' is the DenseDepth D-Net on the HIP decoder path behind "
+                         "the EfficientNet-B5 encoder (magnet_amd/encoder.py), seeded weights unless a checkpoint is loaded by the caller")
+    ap.add_argument("--encoder_backend", default="torch", choices=["torch", "hip"], help="with --encoder b5: run the encoder's torch modules or EncoderMFMA")
     E.add_arguments(ap)
     a = ap.parse_args()
+    if a.encoder_backend == "hip" and a.encoder != "b5":
+        ap.error("--encoder_backend hip is a mode of --encoder b5")
     if a.graph and not a.reuse_backbones:
         ap.error("--graph is a mode of --reuse_backbones (SequenceRunner(graph=True)): give both")
     if a.reuse_backbones and not a.dataset_path:
@@ -162,7 +168,12 @@ def main():
         from magnet_amd.fnet import FNET
         args.FNET_architecture, args.FNET_feature_dim = "PSM-Net", 64
         f_net = FNET(args)                                   # random init unless a checkpoint is loaded by the caller
-    model = MAGNET(args, d_net=StubDNet(1), f_net=f_net, feat_dtype=a.feat_dtype)
+    if a.encoder == "b5":
+        from magnet_amd.standin import make_dnet
+        model = MAGNET(args, d_net=make_dnet(backend="hip", encoder="b5", encoder_backend=a.encoder_backend), f_net=f_net,
+                       feat_dtype=a.feat_dtype, dnet_backend="hip")
+    else:
+        model = MAGNET(args, d_net=StubDNet(1), f_net=f_net, feat_dtype=a.feat_dtype)
     seeded_magnet_weights(model, 3)
     model = model.to(device).eval()
     runner = None

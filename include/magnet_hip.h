@@ -600,9 +600,14 @@ MAGNET_API int magnet_fnet_stem_wgrad(const float *img, const void *dz_hi, const
 
 enum {                                     /* MagnetConvExArgs.act */
     MAGNET_ACT_BASE       = 0,             /* as magnet_conv_mfma: base.relu decides */
-    MAGNET_ACT_LEAKY_RELU = 1              /* LeakyReLU(act_slope) after bias / addend / residual (UpSampleBN._net, D_dense_depth.py:29-43):
+    MAGNET_ACT_LEAKY_RELU = 1,             /* LeakyReLU(act_slope) after bias / addend / residual (UpSampleBN._net, D_dense_depth.py:29-43):
                                               x < 0 -> x * act_slope.  Needs base.relu == 0 and no fused tail; every other output form
                                               (bf16 planes, fp32, single bf16 plane, channel slices, zero border, repad) applies it */
+    MAGNET_ACT_SILU       = 2              /* SiLU after bias / addend / residual (the EfficientNet encoder's expand layers): x * sigmoid(x)
+                                              = x / (1 + e), e = 2^(-x log2 e) on the hardware exponential (1 ulp), one fp32 add, one
+                                              correctly rounded divide: |got - silu(x)| <= 2^-21 |silu(x)| + 2^-22.  Needs base.relu == 0
+                                              and no fused tail; every output form MAGNET_ACT_LEAKY_RELU serves applies it.  Served by
+                                              magnet_conv_mfma_ex only: the fp16 entry points and the split-K forms refuse it (MAGNET_E_DIM) */
 };
 
 enum {                                     /* MagnetConvExArgs.tiling: bit flags, for tests and A/B runs; 0 = the library chooses */
@@ -740,6 +745,54 @@ MAGNET_API int magnet_dnet_gauss_head(const float *in, int32_t in_ld, int32_t N,
  * k = 4 only.  head_ld even and >= 2, `head` 8-byte aligned; mask_ld >= 144 and a multiple of 4, `mask` and `out` 16-byte aligned. */
 MAGNET_API int magnet_dnet_upsample_gauss(const float *head, int32_t head_ld, const float *mask, int32_t mask_ld, int32_t N,
                                           int32_t h, int32_t w, float *out, void *stream);
+
+/* ---- the D-Net's encoder (EfficientNet-B5, models/submodules/D_dense_depth.py:7-25; magnet_amd/encoder.py) ----
+ * Its 1x1 layers run on magnet_conv_mfma_ex (MAGNET_ACT_SILU for the expand layers, add_hi / add_lo for the skip connection); the stem,
+ * the depthwise convolutions and squeeze-excite are the entry points below.  Activations are the convolution kernel's format
+ * throughout: zero-bordered channel-last grids (N, h+2, w+2, C_pad) as split-bf16 planes (hi, lo), C_pad a multiple of 32, pad
+ * channels zero in both planes, border rows zero.  sigmoid and SiLU are MAGNET_ACT_SILU's forms (|sigmoid error| <= 2^-21).  Every
+ * entry point checks its arguments on the host before any launch; a refused call writes nothing.  No atomics: results are deterministic. */
+
+/* The stem: NCHW fp32 image (N, 3, H, W) -> the interior of planes (N, H2+2, W2+2, 64), H2 = ceil(H / 2), W2 = ceil(W / 2):
+ * silu(bias[co] + sum W[co][ci][dy][dx] img[ci][2y + dy - pt][2x + dx - pl]), 3x3 stride 2 with TF "SAME" padding (total = max((H2 - 1) 2
+ * + 3 - H, 0), pt = total / 2: 0 on an even H, 1 on an odd one; out-of-image taps decided by index).  wgt (48, 27) fp32 with BatchNorm
+ * folded, bias (48); fp32 fmaf in the order ci, dy, dx.  Channels 48..63 are written zero; border rows are not written. */
+MAGNET_API int magnet_enc_stem(const float *img, const float *wgt, const float *bias, void *out_hi, void *out_lo, int32_t N, int32_t H,
+                               int32_t W, void *stream);
+
+/* Depthwise k x k convolution + bias + SiLU, and the partial channel sums of its outputs for the squeeze.
+ * out[n][oy][ox][c] = silu(bias[c] + sum_{ky,kx} wgt[ky k + kx][c] in[n][oy stride + ky - pad_top][ox stride + kx - pad_left][c]) for
+ * oy < ho = ceil(h / stride), ox < wo = ceil(w / stride); taps outside the (h, w) image are skipped by index (the input grid's border is
+ * never read); fp32 fmaf in the order ky, kx.  The interior of the output grid (N, ho+2, wo+2, out_ld) is written, all c_pad channels
+ * (wgt and bias are zero in the pad lanes, so these stay zero).  part (N, n_part, c_pad) fp32: row t of image n holds the sum of the
+ * fp32 outputs (after SiLU, before the bf16 split) of output tile t (8 rows x 16 columns, row-major over the image) — each owned by one
+ * workgroup and written exactly once, in a fixed order.  n_part must equal magnet_dwconv_cl_parts(ho, wo). */
+typedef struct MagnetDwConvArgs {
+    const void  *in_hi, *in_lo;            /* (N, h+2, w+2, in_ld) split-bf16 planes */
+    const float *wgt;                      /* [k*k][c_pad] fp32 */
+    const float *bias;                     /* [c_pad] */
+    void        *out_hi, *out_lo;          /* (N, ho+2, wo+2, out_ld) split-bf16 planes */
+    float       *part;                     /* (N, n_part, c_pad) */
+    int32_t      N, h, w, c_pad;           /* c_pad % 32 == 0 */
+    int32_t      in_ld, out_ld;            /* row pitches in elements: >= c_pad, multiples of 8 */
+    int32_t      k, stride;                /* 3 or 5; 1 or 2 */
+    int32_t      pad_top, pad_left;        /* 0 .. k - 1 */
+    int32_t      n_part;
+} MagnetDwConvArgs;
+MAGNET_API int64_t magnet_dwconv_cl_parts(int32_t ho, int32_t wo);
+MAGNET_API int magnet_dwconv_cl(const MagnetDwConvArgs *args, void *stream);
+
+/* The squeeze-excite gate, one workgroup per image: mean[c] = (part[n][0][c] + part[n][1][c] + ... in ascending order) / hw;
+ * r[j] = silu(b_reduce[j] + sum_c w_reduce[j][c] mean[c]); gate[n][c] = sigmoid(b_expand[c] + sum_j w_expand_t[j][c] r[j]) for c < C,
+ * 0 for C <= c < c_pad.  Both matrices are (R, C) fp32 (the expand matrix transposed).  1 <= C <= c_pad <= 8192, 1 <= R <= 1024; part is
+ * 16-byte aligned.  The reduce sum of one j is formed by 64 lanes (lane l: channel quads 4 (l + 64 i), i ascending) and a fixed tree. */
+MAGNET_API int magnet_se_gate(const float *part, int32_t n_part, int64_t hw, const float *w_reduce, const float *b_reduce,
+                              const float *w_expand_t, const float *b_expand, int32_t C, int32_t R, int32_t c_pad, float *gate, int32_t N,
+                              void *stream);
+
+/* out = split(float(hi + lo) * gate[n][c]) over the interior of a grid (N, h+2, w+2, .), channels [0, c_pad); out may be the input. */
+MAGNET_API int magnet_se_scale(const void *in_hi, const void *in_lo, int32_t in_ld, const float *gate, int32_t N, int32_t h, int32_t w,
+                               int32_t c_pad, void *out_hi, void *out_lo, int32_t out_ld, void *stream);
 
 /* Sequence inference (magnet_amd/sequence.py): a frame pool of n_slots slots keeps one frame's backbone outputs per slot, in the
  * layouts the kernels read:

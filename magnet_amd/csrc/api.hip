@@ -8,6 +8,7 @@
 #include "cv_common.hpp"
 #include "conv_common.hpp"
 #include "pack.hpp"
+#include "enc_common.hpp"
 
 namespace magnet {
 hipError_t launch_pack_gmm(const float*, float*, int, int, int, hipStream_t);
@@ -308,7 +309,7 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 }
 
 // Every convolution entry point ends here: the checks of the common fields, then the launch on `mode` (magnet::ConvRoute, conv_common.hpp).
-// leaky != 0 selects LeakyReLU(leaky_slope) after bias (validated by the entry point)
+// leaky: 1 selects LeakyReLU(leaky_slope) after bias, 2 SiLU (validated by the entry point)
 // split_k >= 2 (the split-K entry points, which have checked what that form serves): the split-K launches with workspace `work`; else 0
 using magnet::ConvRoute; using magnet::CONV_BF16X3; using magnet::CONV_F16; using magnet::CONV_F16P; using magnet::CONV_F16D;
 static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, int split_k, float* work,
@@ -421,12 +422,19 @@ static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, flo
 
 // conv_mfma_run with the activation, tiling and tiles_out of an _ex argument struct (whose entry point has checked them)
 static int conv_mfma_run(const MagnetConvExArgs* a, ConvRoute mode, int split_k, float* work, void* stream) {
-    return conv_mfma_run(&a->base, mode, a->act == MAGNET_ACT_LEAKY_RELU, a->act_slope, a->tiling, a->tiles_out, split_k, work, stream);
+    return conv_mfma_run(&a->base, mode, a->act == MAGNET_ACT_LEAKY_RELU ? 1 : (a->act == MAGNET_ACT_SILU ? 2 : 0), a->act_slope, a->tiling, a->tiles_out,
+                         split_k, work, stream);
 }
 
 // The checks that several entry points (`who`) make, each stated once: 0, or the MAGNET_E_* code with the message set.
 // The activation: act is known, LeakyReLU excludes relu (excludes_tail: and the fused tail) and takes a finite slope
-static int conv_act_check(const MagnetConvExArgs* a, const char* who, bool excludes_tail) {
+// serves_silu: MAGNET_ACT_SILU is this entry point's (magnet_conv_mfma_ex alone): relu and the fused tail exclude it too
+static int conv_act_check(const MagnetConvExArgs* a, const char* who, bool excludes_tail, bool serves_silu = false) {
+    if (a->act == MAGNET_ACT_SILU) {
+        if (!serves_silu) return fail(MAGNET_E_DIM, "%s: act=%d (MAGNET_ACT_SILU is served by magnet_conv_mfma_ex only)", who, a->act);
+        if (a->base.relu || a->base.tail_w_hi) return fail(MAGNET_E_DIM, "%s: SiLU excludes relu and the fused tail", who);
+        return 0;
+    }
     if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_LEAKY_RELU) return fail(MAGNET_E_DIM, "%s: act=%d unknown", who, a->act);
     if (a->act == MAGNET_ACT_LEAKY_RELU) {
         if (a->base.relu || (excludes_tail && a->base.tail_w_hi))
@@ -461,7 +469,7 @@ MAGNET_API int magnet_conv_mfma(const MagnetConvArgs* a, void* stream) { return 
 
 MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma_ex: args is NULL");
-    if (const int rc = conv_act_check(a, "magnet_conv_mfma_ex", true)) return rc;
+    if (const int rc = conv_act_check(a, "magnet_conv_mfma_ex", true, true)) return rc;
     if (a->tiling & ~(MAGNET_TILING_FLAT | MAGNET_TILING_BM256 | MAGNET_TILING_BM64)) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: tiling=%d unknown", a->tiling);
     if (a->tiling & MAGNET_TILING_BM64) {                            // the 64-row instances: 3x3, 128-wide, bf16x3 operands
         const MagnetConvArgs& b = a->base;
@@ -1190,6 +1198,71 @@ MAGNET_API int magnet_scatter_frames(const MagnetScatterFramesArgs* a, void* str
         return fail(MAGNET_E_ALIGN, "magnet_scatter_frames: slots and the (mu, sigma) tensors must be 4-byte aligned");
     hipError_t e = magnet::launch_scatter_frames(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_scatter_frames launch");
+}
+
+// ---- the D-Net's encoder (enc_kernels.hip) ----
+MAGNET_API int magnet_enc_stem(const float* img, const float* wgt, const float* bias, void* out_hi, void* out_lo, int32_t N, int32_t H, int32_t W,
+                               void* stream) {
+    if (!img || !wgt || !bias || !out_hi || !out_lo) return fail(MAGNET_E_NULL, "magnet_enc_stem: NULL pointer");
+    if (N <= 0 || H < 2 || W < 2 || (int64_t)N * ((H + 1) / 2 + 2) * ((W + 1) / 2 + 2) >= ((int64_t)1 << 31))
+        return fail(MAGNET_E_DIM, "magnet_enc_stem: bad dims N=%d H=%d W=%d", N, H, W);
+    if (!aligned16(out_hi) || !aligned16(out_lo)) return fail(MAGNET_E_ALIGN, "magnet_enc_stem: outputs not 16-byte aligned");
+    const hipError_t e = magnet::launch_enc_stem(img, wgt, bias, (uint16_t*)out_hi, (uint16_t*)out_lo, N, H, W, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_enc_stem launch");
+}
+
+MAGNET_API int64_t magnet_dwconv_cl_parts(int32_t ho, int32_t wo) { return (ho <= 0 || wo <= 0) ? 0 : (int64_t)magnet::enc_dw_parts(ho, wo); }
+
+MAGNET_API int magnet_dwconv_cl(const MagnetDwConvArgs* a, void* stream) {
+    if (!a) return fail(MAGNET_E_NULL, "magnet_dwconv_cl: args is NULL");
+    if (!a->in_hi || !a->in_lo || !a->wgt || !a->bias || !a->out_hi || !a->out_lo || !a->part) return fail(MAGNET_E_NULL, "magnet_dwconv_cl: NULL pointer");
+    if (a->k != 3 && a->k != 5) return fail(MAGNET_E_DIM, "magnet_dwconv_cl: k=%d (3 or 5)", a->k);
+    if (a->stride != 1 && a->stride != 2) return fail(MAGNET_E_DIM, "magnet_dwconv_cl: stride=%d (1 or 2)", a->stride);
+    if (a->N <= 0 || a->N > 65535 || a->h <= 0 || a->w <= 0 || a->c_pad <= 0 || (a->c_pad % 32) != 0)
+        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: bad dims N=%d h=%d w=%d c_pad=%d (c_pad %% 32 == 0, N <= 65535)", a->N, a->h, a->w, a->c_pad);
+    if (a->in_ld < a->c_pad || (a->in_ld % 8) != 0 || a->out_ld < a->c_pad || (a->out_ld % 8) != 0)
+        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: in_ld=%d / out_ld=%d must be >= c_pad and multiples of 8", a->in_ld, a->out_ld);
+    if (a->pad_top < 0 || a->pad_top >= a->k || a->pad_left < 0 || a->pad_left >= a->k)
+        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: pad_top=%d pad_left=%d outside [0, k)", a->pad_top, a->pad_left);
+    const int ho = (a->h + a->stride - 1) / a->stride, wo = (a->w + a->stride - 1) / a->stride;
+    if ((int64_t)a->N * (a->h + 2) * (a->w + 2) >= ((int64_t)1 << 31)) return fail(MAGNET_E_DIM, "magnet_dwconv_cl: N (h+2) (w+2) must be < 2^31");
+    if (a->n_part != magnet::enc_dw_parts(ho, wo))
+        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: n_part=%d, expected magnet_dwconv_cl_parts(%d, %d) = %lld", a->n_part, ho, wo, magnet::enc_dw_parts(ho, wo));
+    if (!aligned16(a->in_hi) || !aligned16(a->in_lo) || !aligned16(a->out_hi) || !aligned16(a->out_lo) || !aligned16(a->wgt) || !aligned16(a->bias))
+        return fail(MAGNET_E_ALIGN, "magnet_dwconv_cl: planes, wgt and bias must be 16-byte aligned");
+    if ((uintptr_t)a->part & 3) return fail(MAGNET_E_ALIGN, "magnet_dwconv_cl: part must be 4-byte aligned");
+    magnet::EncDwParams p;
+    memset(&p, 0, sizeof(p));
+    p.in_hi = (const uint16_t*)a->in_hi; p.in_lo = (const uint16_t*)a->in_lo; p.in_ld = a->in_ld; p.hi = a->h; p.wi = a->w; p.c_pad = a->c_pad;
+    p.wgt = a->wgt; p.bias = a->bias; p.k = a->k; p.stride = a->stride; p.pad_top = a->pad_top; p.pad_left = a->pad_left;
+    p.out_hi = (uint16_t*)a->out_hi; p.out_lo = (uint16_t*)a->out_lo; p.out_ld = a->out_ld; p.ho = ho; p.wo = wo; p.part = a->part;
+    const hipError_t e = magnet::launch_enc_dwconv(p, a->N, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dwconv_cl launch");
+}
+
+MAGNET_API int magnet_se_gate(const float* part, int32_t n_part, int64_t hw, const float* w_reduce, const float* b_reduce, const float* w_expand_t,
+                              const float* b_expand, int32_t C, int32_t R, int32_t c_pad, float* gate, int32_t N, void* stream) {
+    if (!part || !w_reduce || !b_reduce || !w_expand_t || !b_expand || !gate) return fail(MAGNET_E_NULL, "magnet_se_gate: NULL pointer");
+    if (N <= 0 || n_part <= 0 || hw <= 0 || hw >= ((int64_t)1 << 31) || C <= 0 || c_pad > 8192 || R <= 0 || R > 1024 || c_pad < C || (c_pad % 32) != 0)
+        return fail(MAGNET_E_DIM, "magnet_se_gate: bad dims N=%d n_part=%d hw=%lld C=%d R=%d c_pad=%d (C <= c_pad <= 8192, R <= 1024, c_pad %% 32 == 0)", N,
+                    n_part, (long long)hw, C, R, c_pad);
+    if (!aligned16(part) || ((uintptr_t)gate & 3)) return fail(MAGNET_E_ALIGN, "magnet_se_gate: part must be 16-byte aligned, gate 4-byte aligned");
+    const hipError_t e = magnet::launch_enc_se_gate(part, n_part, hw, w_reduce, b_reduce, w_expand_t, b_expand, C, R, c_pad, gate, N, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_se_gate launch");
+}
+
+MAGNET_API int magnet_se_scale(const void* in_hi, const void* in_lo, int32_t in_ld, const float* gate, int32_t N, int32_t h, int32_t w, int32_t c_pad,
+                               void* out_hi, void* out_lo, int32_t out_ld, void* stream) {
+    if (!in_hi || !in_lo || !gate || !out_hi || !out_lo) return fail(MAGNET_E_NULL, "magnet_se_scale: NULL pointer");
+    if (N <= 0 || h <= 0 || w <= 0 || c_pad <= 0 || (c_pad % 32) != 0 || in_ld < c_pad || (in_ld % 8) != 0 || out_ld < c_pad || (out_ld % 8) != 0 ||
+        (int64_t)N * (h + 2) * (w + 2) >= ((int64_t)1 << 31))
+        return fail(MAGNET_E_DIM, "magnet_se_scale: bad dims N=%d h=%d w=%d c_pad=%d in_ld=%d out_ld=%d (c_pad %% 32 == 0; pitches >= c_pad, multiples of 8)", N, h,
+                    w, c_pad, in_ld, out_ld);
+    if (!aligned16(in_hi) || !aligned16(in_lo) || !aligned16(out_hi) || !aligned16(out_lo) || !aligned16(gate))
+        return fail(MAGNET_E_ALIGN, "magnet_se_scale: planes and gate must be 16-byte aligned");
+    const hipError_t e = magnet::launch_enc_se_scale((const uint16_t*)in_hi, (const uint16_t*)in_lo, in_ld, gate, N, h, w, c_pad, (uint16_t*)out_hi,
+                                                     (uint16_t*)out_lo, out_ld, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_se_scale launch");
 }
 
 }  // extern "C"

@@ -46,8 +46,10 @@ struct ConvParams {
     // its E8M0 exponent: in_sc [cin / 32][sc_rows] u32 {E8M0 of the hi block, E8M0 of the lo block, 0, 0}, w_sc [taps][cin / 32][cout_pad] u32
     const uint32_t* in_sc; const uint32_t* w_sc;
     long long sc_rows;                                // rows of one chunk plane of in_sc (>= rows)
-    // LeakyReLU (magnet_conv_mfma_ex; the D-Net decoder, D_dense_depth.py:29-43): leaky != 0 and relu == 0 -> negative outputs are
+    // LeakyReLU (magnet_conv_mfma_ex; the D-Net decoder, D_dense_depth.py:29-43): leaky == 1 and relu == 0 -> negative outputs are
     // multiplied by leaky_slope after bias / addend.  Plain epilogue only (not with the fused tail)
+    // leaky == 2: SiLU (MAGNET_ACT_SILU, magnet_conv_mfma_ex only; the EfficientNet encoder's expand layers): x * sigmoid(x) in the same
+    // place (silu_f32 below)
     int leaky;
     float leaky_slope;
     // row tiling (launch_conv_mfma decides; see conv_mfma_tile).  tiles_per_img = 0: tile t starts at row t * BM of the flat buffer.
@@ -87,6 +89,13 @@ __device__ __forceinline__ void f16x8_unpack(const uint4 u, float* v) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
 }
+
+// sigmoid(x) = 1 / (1 + e), e = 2^(-x log2 e) on the hardware exponential (v_exp_f32: 1 ulp; the rounding of its argument and of the constant add a
+// relative 1.3 |x| 2^-24 to e), one fp32 add and one correctly rounded divide; silu(x) = x / (1 + e).  e overflows to +Inf below x = -88.7 (result
+// -0 for silu, +0 for sigmoid) and flushes to 0 above x = 87.3 (result x, 1): both within the bound.  Accuracy, stated for the tests
+// (include/magnet_hip.h): |sigmoid_f32(x) - sigmoid(x)| <= 2^-21, |silu_f32(x) - silu(x)| <= 2^-21 |silu(x)| + 2^-22.
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(-x * 1.44269504088896341f)); }
+__device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + __builtin_amdgcn_exp2f(-x * 1.44269504088896341f)); }
 
 struct ChainParams {
     const uint16_t* in_hi;  const uint16_t* in_lo;    // (rows, 128)

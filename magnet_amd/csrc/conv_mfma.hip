@@ -1207,8 +1207,12 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 float x = (stage[r * SROW + c8 + i] + ad[i]) + (BIAS_INV ? bv[i] : p.bias[ch + i]);
-                v[i] = (x < 0.f) ? (p.relu ? 0.f : (p.leaky ? x * p.leaky_slope : x)) : x;
+                v[i] = (x < 0.f) ? (p.relu ? 0.f : (p.leaky == 1 ? x * p.leaky_slope : x)) : x;
                 if (!interior) v[i] = 0.f;
+            }
+            if (p.leaky == 2) {                               // SiLU (launch-uniform): silu(0) = 0 keeps the border rows zero
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = silu_f32(v[i]);
             }
             const size_t e = (size_t)orow * p.out_ld + ch;
             if constexpr (F16P) {

@@ -25,7 +25,7 @@ E_NULL, E_DIM, E_DTYPE, E_ALIGN, E_NODEVICE, E_SHAPE = 1, 2, 3, 4, 5, 6
 MAX_CANDIDATES = 256
 NLL_BLOCKS, NLL_MAX_ITER = 256, 16
 BN_BLOCKS = 256
-ACT_BASE, ACT_LEAKY_RELU = 0, 1
+ACT_BASE, ACT_LEAKY_RELU, ACT_SILU = 0, 1, 2
 TILING_FLAT, TILING_BM256, TILING_BM64 = 1, 2, 4
 SPLITK_MAX, SPLITK_MIN_CHUNKS = 8, 2
 METRICS_SIGMA, METRICS_VARIANCE, METRICS_NONE = 0, 1, 2
@@ -221,6 +221,15 @@ class MagnetScatterFramesArgs(ctypes.Structure):
                 ("pool_feat", ctypes.c_void_p), ("pool_gmm", ctypes.c_void_p), ("pool_xd3_hi", ctypes.c_void_p), ("pool_xd3_lo", ctypes.c_void_p)]
 
 
+class MagnetDwConvArgs(ctypes.Structure):
+    """Mirror of `struct MagnetDwConvArgs` (include/magnet_hip.h)."""
+    _fields_ = [("in_hi", ctypes.c_void_p), ("in_lo", ctypes.c_void_p), ("wgt", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p), ("part", ctypes.c_void_p),
+                ("N", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("c_pad", ctypes.c_int32),
+                ("in_ld", ctypes.c_int32), ("out_ld", ctypes.c_int32), ("k", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("pad_top", ctypes.c_int32), ("pad_left", ctypes.c_int32), ("n_part", ctypes.c_int32)]
+
+
 # (restype, argtypes) of every MAGNET_API declaration of include/magnet_hip.h, in header order; load() applies them all
 _C, _L, _F, _I, _P, _S = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER
 _PROTOS = {
@@ -287,6 +296,11 @@ _PROTOS = {
     "magnet_conv_row_tiles": (_L, [_I, _I, _I, _I, _S(_I)]),
     "magnet_dnet_gauss_head": (_C, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "magnet_dnet_upsample_gauss": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "magnet_enc_stem": (_C, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "magnet_dwconv_cl_parts": (_L, [_I, _I]),
+    "magnet_dwconv_cl": (_C, [_S(MagnetDwConvArgs), _P]),
+    "magnet_se_gate": (_C, [_P, _I, _L, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
+    "magnet_se_scale": (_C, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "magnet_gather_views": (_C, [_S(MagnetGatherViewsArgs), _P]),
     "magnet_scatter_frames": (_C, [_S(MagnetScatterFramesArgs), _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
@@ -631,7 +645,7 @@ _CONV_ROUTES = {
 
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
-              mx=None, leaky=None, tiling=None, f16=False, split_k=None, work=None):
+              mx=None, leaky=None, tiling=None, f16=False, split_k=None, work=None, silu=False):
     """One convolution layer on the matrix cores.  in_hi/in_lo: bf16 tensors whose data_ptr is row 0 (possibly a
     channel-offset view of a wider buffer, `in_ld` = its row pitch in elements); weights (taps, cout_pad, cin) bf16.
     F-Net extras (include/magnet_hip.h): dil (3x3 dilation), out_ld (write a channel slice: out tensors may then be
@@ -643,6 +657,8 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     gauss = (gmm_in (B,2,h,w), gmm_out): with tail cout_pad 16 (G-Net's head) the Gaussian update of models/MAGNET.py:60-69 runs
     in the tail's last layer and only `gmm_out` is written.
     leaky = slope: LeakyReLU(slope) after bias instead of ReLU (magnet_conv_mfma_ex; relu must be False, no tail).
+    silu = True: SiLU after bias / residual instead of ReLU (MAGNET_ACT_SILU, magnet_conv_mfma_ex only; relu must be False, no leaky, tail,
+    f16 or split_k).
     tiling = TILING_* flags (magnet_conv_mfma_ex; tests and A/B runs).  Returns the number of row tiles launched when the launch went
     through magnet_conv_mfma_ex, else None.
     f16 = True: the single-plane fp16 operand format (magnet_conv_mfma_f16): in_hi / w_hi are fp16 tensors, in_lo / w_lo must be None;
@@ -667,6 +683,8 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
             raise MagnetError("conv_mfma (split_k): work must be a contiguous float32 GPU tensor")
     elif work is not None:
         raise MagnetError("conv_mfma: work goes with split_k")
+    if silu and (relu or leaky is not None or tail is not None or f16 or split_k is not None):
+        raise MagnetError("conv_mfma (silu): the bf16x3 layer without relu, leaky, tail, f16 or split_k")
     a = MagnetConvArgs()
     if f16 not in tuple(_CONV_ROUTES):
         raise MagnetError(f"conv_mfma: f16 must be False, True, 'plane' or 'wide', got {f16!r}")
@@ -740,11 +758,11 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_hi = 3, _f16_ptr(out_hi, "out_hi (fp16 plane)")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
-    if leaky is None and tiling is None and not f16 and split_k is None:
+    if leaky is None and tiling is None and not f16 and split_k is None and not silu:
         _launch("magnet_conv_mfma", in_hi, ctypes.byref(a))
         return None
     tiles = ctypes.c_int64(0)
-    x = MagnetConvExArgs(base=a, act=ACT_BASE if leaky is None else ACT_LEAKY_RELU, act_slope=float(leaky or 0.0),
+    x = MagnetConvExArgs(base=a, act=ACT_SILU if silu else (ACT_BASE if leaky is None else ACT_LEAKY_RELU), act_slope=float(leaky or 0.0),
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
     more = () if split_k is None else (int(split_k), work.data_ptr(), work.numel() * 4)
     _launch(entry_splitk if more else entry, in_hi, ctypes.byref(x), *more)
@@ -1570,3 +1588,82 @@ def scatter_frames(slots, pool_feat=None, pool_gmm=None, pool_xd3=None, feat=Non
     if any(x.device != t.device for x in used):
         raise MagnetError("scatter_frames: all tensors must be on the same device")
     _launch("magnet_scatter_frames", t, ctypes.byref(a))
+
+
+# ---- the D-Net's encoder (EfficientNet-B5): stem, depthwise convolution, squeeze-excite --------------------------------
+def enc_stem(img, wgt, bias, out_hi, out_lo):
+    """(N,3,H,W) fp32 image -> the interior of the 64-channel split planes (N,H2+2,W2+2,64), H2 = ceil(H/2): 3x3/s2 conv with TF "SAME"
+    padding + folded BN + SiLU, 48 channels + 16 zero lanes.  wgt (48, 27), bias (48)."""
+    x = _dev(img, "img", torch.float32)
+    N, C, H, W = x.shape
+    if C != 3:
+        raise MagnetError(f"enc_stem: expected 3 input channels, got {C}")
+    if tuple(wgt.shape) != (48, 27) or tuple(bias.shape) != (48,):
+        raise MagnetError(f"enc_stem: wgt (48, 27) and bias (48,), got {tuple(wgt.shape)} / {tuple(bias.shape)}")
+    rows = N * ((H + 1) // 2 + 2) * ((W + 1) // 2 + 2)
+    for t, n in ((out_hi, "out_hi"), (out_lo, "out_lo")):
+        _bf16_ptr(t, f"enc_stem: {n}", contiguous=True)
+        if t.numel() < rows * 64:
+            raise MagnetError(f"enc_stem: {n} holds {t.numel()} elements, needs {rows * 64}")
+    _launch("magnet_enc_stem", x, x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(), _dev(bias, "bias", torch.float32).data_ptr(),
+            out_hi.data_ptr(), out_lo.data_ptr(), N, H, W)
+
+
+def dwconv_parts(ho, wo) -> int:
+    """magnet_dwconv_cl_parts: rows of the partial-sum scratch per image for an (ho, wo) output.  Host arithmetic: no GPU needed."""
+    return int(load().magnet_dwconv_cl_parts(int(ho), int(wo)))
+
+
+def _grid_planes(who, t, N, h, w, ld):
+    """A plane of a zero-bordered (N, h+2, w+2, ld) grid: a bf16 GPU tensor that holds it at row pitch ld (its data_ptr is row 0)."""
+    _bf16_ptr(t, who, contiguous=True)
+    if t.numel() < N * (h + 2) * (w + 2) * ld:
+        raise MagnetError(f"{who} holds {t.numel()} elements, needs {N * (h + 2) * (w + 2) * ld}")
+    return t.data_ptr()
+
+
+def dwconv_cl(in_hi, in_lo, in_ld, N, h, w, c_pad, wgt, bias, k, stride, pad_top, pad_left, out_hi, out_lo, out_ld, part):
+    """Depthwise k x k convolution + bias + SiLU on split planes, with the per-tile partial channel sums (include/magnet_hip.h):
+    in (N,h+2,w+2,in_ld) -> interior of out (N,ho+2,wo+2,out_ld), ho = ceil(h / stride); wgt (k*k, c_pad) fp32, bias (c_pad);
+    part (N, dwconv_parts(ho, wo), c_pad) fp32."""
+    ho, wo = -(-int(h) // int(stride)), -(-int(w) // int(stride))
+    n_part = dwconv_parts(ho, wo)
+    a = MagnetDwConvArgs()
+    a.in_hi, a.in_lo = (_grid_planes(f"dwconv_cl: {n}", t, N, h, w, in_ld) for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo")))
+    a.out_hi, a.out_lo = (_grid_planes(f"dwconv_cl: {n}", t, N, ho, wo, out_ld) for t, n in ((out_hi, "out_hi"), (out_lo, "out_lo")))
+    if tuple(wgt.shape) != (k * k, c_pad) or tuple(bias.shape) != (c_pad,):
+        raise MagnetError(f"dwconv_cl: wgt ({k * k}, {c_pad}) and bias ({c_pad},), got {tuple(wgt.shape)} / {tuple(bias.shape)}")
+    a.wgt, a.bias = _dev(wgt, "wgt", torch.float32).data_ptr(), _dev(bias, "bias", torch.float32).data_ptr()
+    if _dev(part, "part", torch.float32).numel() < N * n_part * c_pad:
+        raise MagnetError(f"dwconv_cl: part holds {part.numel()} elements, needs {N * n_part * c_pad}")
+    a.part = part.data_ptr()
+    a.N, a.h, a.w, a.c_pad, a.in_ld, a.out_ld = int(N), int(h), int(w), int(c_pad), int(in_ld), int(out_ld)
+    a.k, a.stride, a.pad_top, a.pad_left, a.n_part = int(k), int(stride), int(pad_top), int(pad_left), n_part
+    _launch("magnet_dwconv_cl", in_hi, ctypes.byref(a))
+    return n_part
+
+
+def se_gate(part, n_part, hw, w_reduce, b_reduce, w_expand_t, b_expand, C, R, gate):
+    """part (N, n_part, c_pad) -> gate (N, c_pad) fp32: mean over hw, reduce FC + SiLU, expand FC + sigmoid; zero for channels >= C.
+    w_reduce, w_expand_t (R, C) fp32; b_reduce (R,), b_expand (C,)."""
+    g = _dev(gate, "gate", torch.float32)
+    if g.dim() != 2:
+        raise MagnetError(f"se_gate: gate must be (N, c_pad), got {tuple(g.shape)}")
+    N, c_pad = g.shape
+    if _dev(part, "part", torch.float32).numel() < N * int(n_part) * c_pad:
+        raise MagnetError(f"se_gate: part holds {part.numel()} elements, needs {N * int(n_part) * c_pad}")
+    for t, n, shape in ((w_reduce, "w_reduce", (R, C)), (w_expand_t, "w_expand_t", (R, C)), (b_reduce, "b_reduce", (R,)), (b_expand, "b_expand", (C,))):
+        if tuple(_dev(t, n, torch.float32).shape) != shape:
+            raise MagnetError(f"se_gate: {n} must be {shape}, got {tuple(t.shape)}")
+    _launch("magnet_se_gate", g, part.data_ptr(), int(n_part), int(hw), w_reduce.data_ptr(), b_reduce.data_ptr(), w_expand_t.data_ptr(),
+            b_expand.data_ptr(), int(C), int(R), int(c_pad), g.data_ptr(), int(N))
+
+
+def se_scale(in_hi, in_lo, in_ld, gate, N, h, w, c_pad, out_hi, out_lo, out_ld):
+    """out = split((hi + lo) * gate[n][c]) over the interior of the (N,h+2,w+2,.) grid, channels [0, c_pad); out may be the input."""
+    g = _dev(gate, "gate", torch.float32)
+    if tuple(g.shape) != (N, c_pad):
+        raise MagnetError(f"se_scale: gate must be {(N, c_pad)}, got {tuple(g.shape)}")
+    ih, il = (_grid_planes(f"se_scale: {n}", t, N, h, w, in_ld) for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo")))
+    oh, ol = (_grid_planes(f"se_scale: {n}", t, N, h, w, out_ld) for t, n in ((out_hi, "out_hi"), (out_lo, "out_lo")))
+    _launch("magnet_se_scale", in_hi, ih, il, int(in_ld), g.data_ptr(), int(N), int(h), int(w), int(c_pad), oh, ol, int(out_ld))

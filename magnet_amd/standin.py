@@ -101,14 +101,26 @@ def make_dnet_args(downsample_ratio=4):
                            DNET_fix_encoder_weights="None")
 
 
-def make_dnet(seed=0, enc_seed=0, depth_prior=True, dnet=False, backend="torch", split_k=0, precision="bf16x3"):
+def make_dnet(seed=0, enc_seed=0, depth_prior=True, dnet=False, backend="torch", split_k=0, precision="bf16x3", encoder="standin",
+              encoder_backend="torch"):
     """magnet_amd.dnet.DNET with the stand-in encoder and seeded decoder weights (magnet_amd.dnet.seeded_decoder_state), in eval mode.
+    encoder: "standin" (default: StandinEncoder(enc_seed)) or "b5": magnet_amd.encoder.Encoder(backend=encoder_backend), the real
+    EfficientNet-B5 with calibrated seeded weights (magnet_amd.encoder.load_seeded_encoder(enc_seed)).
     dnet=False: MaGNet's D-Net; dnet=True: the stand-alone D-Net (img -> (N, 2, H, W) [mu, variance]); backend, split_k, precision: see DNET.
     depth_prior: the depth head's last layer is scaled by 1/4 and its bias set to (2.5, -3) so that the stand-in predicts
     plausible scenes for the matcher, mu around 2.5 m (+-1.5) and sigma around 0.2 m (StubDNet's ranges); the raw recipe's mu is
     centred on zero, where depth candidates cross the camera plane."""
     from .dnet import DNET, load_seeded_decoder
-    d = DNET(make_dnet_args(), StandinEncoder(enc_seed), dnet=dnet, backend=backend, split_k=split_k, precision=precision)
+    if encoder == "b5":
+        from .encoder import Encoder, load_seeded_encoder
+        enc = load_seeded_encoder(Encoder(backend=encoder_backend), enc_seed)
+    elif encoder == "standin":
+        if encoder_backend != "torch":
+            raise ValueError("make_dnet: encoder_backend='hip' goes with encoder='b5' (the stand-in is a torch module)")
+        enc = StandinEncoder(enc_seed)
+    else:
+        raise ValueError(f"make_dnet: encoder must be 'standin' or 'b5', got {encoder!r}")
+    d = DNET(make_dnet_args(), enc, dnet=dnet, backend=backend, split_k=split_k, precision=precision)
     load_seeded_decoder(d.d_net.decoder, seed)
     if depth_prior:
         with torch.no_grad():
