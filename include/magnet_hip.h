@@ -630,6 +630,24 @@ typedef struct MagnetConvExArgs {
 } MagnetConvExArgs;
 MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
 
+/* The fused 3x3 launches of the inference step with part of their input read in place from an NCHW fp32 tensor: input channels
+ * [src_c0, cin) are taken from `src` and split to (hi, lo) bf16 inside the kernel (hi = bf16(x), lo = bf16(x - hi), round to nearest
+ * even: what magnet_pack_split writes), so no packed copy of them exists; channels [0, src_c0) come from ex.base.in_hi / in_lo as in
+ * magnet_conv_mfma_ex (row pitch in_ld; the planes' channels from src_c0 on are never read, and in_hi / in_lo may be NULL when
+ * src_c0 == 0).  The result is, bit for bit, that of magnet_conv_mfma_ex on planes that hold magnet_pack_split(src) in those channels.
+ * Serves exactly: bf16x3 operands, taps == 9 without dilation, cout_pad == 128, the fused tail of 16 outputs with gu_in / gu_out or of
+ * 144 outputs with up_depth / up_out, the 256-row kernel (rows >= 65 536 or MAGNET_TILING_BM256), no addend, act == MAGNET_ACT_BASE,
+ * and per-image row tiling in effect (magnet_conv_row_tiles(up_B, up_h, wp, 256) reports tiles per image > 0; MAGNET_TILING_FLAT is
+ * refused).  Everything else — MAGNET_TILING_BM64, the fp16 and e4m3 formats, a residual, border or repad form among it — is refused
+ * with MAGNET_E_DIM, a NULL src with MAGNET_E_NULL, a misaligned one with MAGNET_E_ALIGN, before any launch.  tiles_out works. */
+typedef struct MagnetConvNchwArgs {
+    MagnetConvExArgs ex;
+    const float   *src;                    /* (up_B, src_C, up_h, up_w) fp32, contiguous, 16-byte-aligned base */
+    int32_t        src_c0;                 /* first input channel taken from src: multiple of 32, src_c0 + src_C == base.cin */
+    int32_t        src_C;                  /* multiple of 32 */
+} MagnetConvNchwArgs;
+MAGNET_API int magnet_conv_mfma_nchw(const MagnetConvNchwArgs *args, void *stream);
+
 /* The 3x3 layer of a G-Net / mask-head stack on the single-plane fp16 operand format (see MagnetConvArgs): base.in_hi / base.w_hi are
  * the fp16 planes; base.in_lo, base.w_lo, base.in_sc, base.w_sc must be NULL (MAGNET_E_DIM otherwise: planes of another format are
  * refused, not mis-read).  Serves what the inference loop launches and refuses the rest with MAGNET_E_DIM: taps == 9 without dilation,

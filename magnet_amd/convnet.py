@@ -106,6 +106,9 @@ class ConvStackMFMA:
     # is host-bound, and a launch that keeps its tile form is then exactly the magnet_conv_mfma call it was before the 64-row form
     # existed.  A launch on 64-row tiles is recorded either way.
     record_tiles = False
+    # True: the fused-tail 3x3 launches take the 256-row 8-wave kernel at any row count (lib.TILING_BM256), which the library itself
+    # selects from 65 536 rows on: the tests reach that kernel, and run(src_nchw=...), with small grids.  Not with small_tiles=True.
+    tile_256 = False
     last_tiles = ()
     last_invariant_tiles = ()
 
@@ -115,19 +118,21 @@ class ConvStackMFMA:
         geom = (n_img, h) where the launch carries its image geometry (gauss / upsample), else None.  The one place that says
         whether there is anything to decide or record: in the common case (no) this is two attribute reads and a comparison."""
         st = self.small_tiles
-        if pk["taps"] != 9 or not (self.record_tiles or st is True or (st == "auto" and SMALL_TILE_LIMIT > 0)):
+        if pk["taps"] != 9 or not (self.record_tiles or self.tile_256 or st is True or (st == "auto" and SMALL_TILE_LIMIT > 0)):
             return None, None
         geom = (int(gauss[0].shape[0]), int(gauss[0].shape[2])) if gauss is not None else \
             (int(upsample[0].shape[1]), int(upsample[0].shape[3])) if upsample is not None else None
         if st is not False and pk["cout_pad"] % 128 == 0 and \
                 (st is True or (use_small_tiles(*geom, wp) if geom is not None else use_small_tiles(1, rows // wp - 2, wp, False))):
             return lib.TILING_BM64, geom
+        if self.tile_256 and (gauss is not None or upsample is not None):
+            return lib.TILING_BM256, geom
         return (0 if self.record_tiles else None), geom
 
     @staticmethod
     def _reported(n, tiling, rows, wp, geom):
         """last_tiles of one launch whose tile count n the library reported: [(tile rows, row tiles)]."""
-        return [(_tile_rows(n, tiling, rows, wp, geom), n)]
+        return [(_tile_rows(n, bool(tiling) and bool(tiling & lib.TILING_BM64), rows, wp, geom), n)]
 
     def __init__(self, seq: nn.Sequential, in_map=None):
         self.layers = []
@@ -311,7 +316,7 @@ class ConvStackMFMA:
             raise lib.MagnetError("ConvStackMFMA: f16=True takes one fp16 plane (in_hi) and in_lo=None")
 
     def run(self, in_hi, in_lo, in_ld, rows, wp, work, first_addend=None, n_var=None, inv_off=None, upsample=None, gauss=None, mx=None,
-            f16=False):
+            f16=False, src_nchw=None):
         """in_hi/in_lo: bf16 views whose data_ptr is row 0, channel 0 of this stack's input; `work`: dict for cached
         hidden buffers.  Returns (fp32 tensor (rows, cout_pad_last), cout_pad_last).
         upsample = (depths (n,B,2,h,w), outs (n,B,2,4h,4w)): the mask head's stack only (144 outputs, fused tail) — the learned
@@ -320,8 +325,16 @@ class ConvStackMFMA:
         mx = (in_sc, sc_rows): the input planes are in the fp16 + e4m3 operand format (in_hi fp16, in_lo the e4m3 container, in_sc the
         E8M0 plane of lib.pack_mx); fused-epilogue stacks with at least 65 536 rows only.
         f16 = True: the 3x3 layer on the single-plane fp16 format (lib.conv_mfma(f16=True)): in_hi is an fp16 plane, in_lo None; the
-        fused 1x1 tail stays bf16x3.  Fused-epilogue stacks only; with small_tiles=True a MagnetError (no 64-row form)."""
-        dev = in_hi.device
+        fused 1x1 tail stays bf16x3.  Fused-epilogue stacks only; with small_tiles=True a MagnetError (no 64-row form).
+        src_nchw = (x (B, C, h, w) fp32, c0): the first layer's input channels [c0, c0 + C) are read in place from x
+        (lib.conv_mfma(src_nchw=...): the planes' channels from c0 on are not read; in_hi / in_lo may be None when c0 == 0).  Fused-
+        epilogue stacks with gauss or upsample, bf16x3, no first_addend; the library refuses what its entry point does not serve."""
+        dev = in_hi.device if in_hi is not None else src_nchw[0].device
+        if src_nchw is not None:
+            self.packed(dev)
+            if f16 or mx is not None or first_addend is not None or (gauss is None and upsample is None) or self._chain is None or \
+                    not self.fuse_epilogue:
+                raise lib.MagnetError("ConvStackMFMA.run (src_nchw): the bf16x3 fused-epilogue launch with gauss or upsample only")
         if f16:
             return self._run_f16(in_hi, in_lo, in_ld, rows, wp, first_addend, n_var, inv_off, upsample, gauss, mx, work)
         packs = self.packed(dev)
@@ -351,8 +364,9 @@ class ConvStackMFMA:
             with timed(sink, flops(pk) + 2.0 * rows * 128 * (256 + ch["cout_pad"]), pk["taps"]):
                 n = lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], w_hi, w_lo, pk["bias"], pk["taps"], wp, pk["relu"], rows, out_f32=out,
                                   tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss, tiling=tiling,
-                                  **form)
-            self.last_tiles = () if n is None else self._reported(n, tiling, rows, wp, geom)
+                                  src_nchw=src_nchw, **form)
+            # (the src_nchw entry point always reports its tile count; it is recorded where the plain launch's would be)
+            self.last_tiles = () if n is None or tiling is None else self._reported(n, tiling, rows, wp, geom)
             return out, ch["cout_pad"]
         if self._chain is not None and self.fuse_tail and first_addend is None:
             pk, ch = packs[0], self._chain

@@ -312,11 +312,13 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 // leaky: 1 selects LeakyReLU(leaky_slope) after bias, 2 SiLU (validated by the entry point)
 // split_k >= 2 (the split-K entry points, which have checked what that form serves): the split-K launches with workspace `work`; else 0
 using magnet::ConvRoute; using magnet::CONV_BF16X3; using magnet::CONV_F16; using magnet::CONV_F16P; using magnet::CONV_F16D;
+// src / src_c0 (magnet_conv_mfma_nchw, which has checked them): input channels [src_c0, cin) come from the NCHW fp32 tensor `src`
 static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, int split_k, float* work,
-                         void* stream) {
+                         void* stream, const float* src = nullptr, int src_c0 = 0) {
     if (!a) return fail(MAGNET_E_NULL, "magnet_conv_mfma: args is NULL");
     const bool f16 = mode != CONV_BF16X3;
-    if (!a->in_hi || (!f16 && !a->in_lo) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
+    const bool planes = !src || src_c0 > 0;                          // the launch reads the activation planes
+    if ((planes && (!a->in_hi || (!f16 && !a->in_lo))) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
     if (mode == CONV_F16D) {
         if (a->out_mode != 0 && a->out_mode != 1 && a->out_mode != 3) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16d: out_mode must be 0, 1 or 3");
     } else
@@ -415,7 +417,8 @@ static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, flo
 #ifdef MAGNET_DEV
     { static const int dev_variant = getenv("MAGNET_CONV_VARIANT") ? atoi(getenv("MAGNET_CONV_VARIANT")) : 0; p.variant = dev_variant; }   // dev A/B switch (dev build only)
 #endif
-    const hipError_t e = magnet::launch_conv(p, mode, split_k, work, (hipStream_t)stream);
+    const magnet::ConvSrc nchw{src, src_c0};
+    const hipError_t e = magnet::launch_conv(p, mode, split_k, work, (hipStream_t)stream, src ? &nchw : nullptr);
     if (tiles_out) *tiles_out = tiles;
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv_mfma launch");
 }
@@ -479,6 +482,35 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
                                       "with cout_pad %% 128 == 0, bf16x3 operands only (taps=%d cout_pad=%d)", b.taps, b.cout_pad);
     }
     return conv_mfma_run(a, CONV_BF16X3, 0, nullptr, stream);
+}
+
+// The fused 3x3 launches of the 256-row kernel with x_d3 read in place: every refusal is made here, before conv_mfma_run's common checks
+MAGNET_API int magnet_conv_mfma_nchw(const MagnetConvNchwArgs* a, void* stream) {
+    const char* who = "magnet_conv_mfma_nchw";
+    if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
+    const MagnetConvExArgs& x = a->ex;
+    const MagnetConvArgs& b = x.base;
+    if (!a->src) return fail(MAGNET_E_NULL, "%s: src is NULL", who);
+    if (x.act != MAGNET_ACT_BASE) return fail(MAGNET_E_DIM, "%s: act=%d (MAGNET_ACT_BASE only)", who, x.act);
+    if (x.tiling & ~MAGNET_TILING_BM256) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_BM256: per-image 256-row tiles only)", who, x.tiling);
+    if (b.taps != 9 || b.dil > 1 || b.cout_pad != 128 || b.in_sc || b.w_sc || b.addend || b.add_hi || b.add_lo || b.border_hp || b.repad)
+        return fail(MAGNET_E_DIM, "%s: bf16x3 3x3 layers (taps == 9, no dilation) with cout_pad == 128; no addend, residual, border, repad or e4m3 format", who);
+    if (!b.tail_w_hi || !((b.tail_cout_pad == 16 && b.gu_in && b.gu_out && !b.up_out && !b.up_depth) ||
+                          (b.tail_cout_pad == 144 && b.up_depth && b.up_out && !b.gu_in && !b.gu_out)))
+        return fail(MAGNET_E_DIM, "%s: the fused tail of 16 outputs with gu_in / gu_out, or of 144 outputs with up_depth / up_out", who);
+    if (b.rows < 256ll * 256 && !(x.tiling & MAGNET_TILING_BM256))
+        return fail(MAGNET_E_DIM, "%s: the 256-row kernel only (rows >= 65536 or MAGNET_TILING_BM256; rows=%lld)", who, (long long)b.rows);
+    if (a->src_c0 < 0 || a->src_c0 % 32 || a->src_C <= 0 || a->src_C % 32 || (long long)a->src_c0 + a->src_C != b.cin)
+        return fail(MAGNET_E_DIM, "%s: src_c0=%d and src_C=%d must be multiples of 32 with src_c0 + src_C == cin=%d", who, a->src_c0, a->src_C, b.cin);
+    if (!aligned16(a->src)) return fail(MAGNET_E_ALIGN, "%s: src must be 16-byte aligned", who);
+    if (b.up_B <= 0 || b.up_h <= 0 || b.up_w <= 0 || b.wp != b.up_w + 2 || b.rows != (long long)b.up_B * (b.up_h + 2) * (b.up_w + 2))
+        return fail(MAGNET_E_DIM, "%s: up_B=%d up_h=%d up_w=%d do not describe rows=%lld, wp=%d", who, b.up_B, b.up_h, b.up_w, (long long)b.rows, b.wp);
+    if ((long long)(b.up_h + 2) * b.wp >= (1 << 24) || (long long)a->src_C * b.up_h * b.up_w * 4 >= ((long long)1 << 31))
+        return fail(MAGNET_E_DIM, "%s: an image of src exceeds 2 GiB, or its padded grid 2^24 positions", who);
+    int per_img = 0;
+    magnet::conv_row_tiles(b.up_B, b.up_h, b.wp, 256, &per_img);
+    if (!per_img) return fail(MAGNET_E_DIM, "%s: per-image tiling is not in effect for %d images of %d x %d (flat tiling launches no more tiles)", who, b.up_B, b.up_h, b.up_w);
+    return conv_mfma_run(&b, CONV_BF16X3, 0, 0.f, x.tiling, x.tiles_out, 0, nullptr, stream, a->src, a->src_c0);
 }
 
 MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs* a, void* stream) {

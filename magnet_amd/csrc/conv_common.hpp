@@ -113,10 +113,16 @@ struct ChainParams {
 // the D-Net decoder's plain layers, cout_pad % 128 == 0, LeakyReLU): no residual; out_mode 0, 1 or 3
 enum ConvRoute { CONV_BF16X3, CONV_F16, CONV_F16P, CONV_F16D };
 
+// magnet_conv_mfma_nchw: input channels [c0, cin) of the launch are read from ptr, (up_B, cin - c0, up_h, up_w) fp32, and split to
+// (hi, lo) in LDS; the planes hold channels [0, c0) only (in_hi / in_lo may be NULL when c0 == 0).  Kernel arguments of the two
+// fp32-source instances alone, so ConvParams — every other instance's argument block — is what it was
+struct ConvSrc { const float* ptr; int c0; };
+
 // One convolution launch on `route`.  split_k = 0: the plain launch.  split_k = S in 2 .. 8 (CONV_BF16X3 and CONV_F16D: magnet_conv_mfma_splitk,
 // magnet_conv_mfma_f16d_splitk): split-K over S input-channel ranges, the partials into work (S x rows x cout_pad fp32), then the
 // fixed-order reduce + epilogue launch.  hipErrorInvalidValue for a (route, split_k) pair or a form that has no kernel instance
-hipError_t launch_conv(const ConvParams&, ConvRoute route, int split_k, float* work, hipStream_t);
+// nchw != NULL (CONV_BF16X3, split_k = 0 only): the fp32-source form of the 256-row fused-tail launches
+hipError_t launch_conv(const ConvParams&, ConvRoute route, int split_k, float* work, hipStream_t, const ConvSrc* nchw = nullptr);
 hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
 
 }  // namespace magnet

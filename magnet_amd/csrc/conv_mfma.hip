@@ -375,10 +375,10 @@ struct ConvLds {
 // and the weight offset change (the weight row pitch stays cin); the step order and the ring schedule are the plain loop's — and stores
 // its raw fp32 accumulator tile to sk_work[sk_z][row][cout_pad], rows < p.rows: no bias, activation or border logic (the reduce kernel's).
 // A partial therefore holds, to the bit, what the plain instance writes to out_f32 for that channel range alone with a zero bias.
-template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool F16 = false, bool F16P = false, bool SPLITK = false>
+template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN, bool F16 = false, bool F16P = false, bool SPLITK = false, bool NCHW = false>
 __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsigned bid, const unsigned n_tiles, const unsigned by, const int tid,
                                                [[maybe_unused]] float* __restrict__ sk_work = nullptr, [[maybe_unused]] const unsigned sk_z = 0,
-                                               [[maybe_unused]] const unsigned sk_n = 1) {
+                                               [[maybe_unused]] const unsigned sk_n = 1, [[maybe_unused]] const ConvSrc nchw = ConvSrc{nullptr, 0}) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-descriptor builtins do not exist in the host pass (which only needs the stub)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the K loop's ring (ConvLds; declared here, not passed in: a pointer
                                                                             // parameter is a generic pointer, and its casts to LDS pointers get null checks)
@@ -897,6 +897,153 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             __builtin_amdgcn_s_barrier();
         };
         const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
+        if constexpr (NCHW) {
+            // ---- the same loop with the K chunks k0 >= nchw.c0 taken from nchw.ptr, (B, cin - c0, h, w) fp32 (magnet_conv_mfma_nchw):
+            // the window of such a (chunk, ty) is not DMA'd from the (hi, lo) planes.  Wave wv owns window rows 32 wv .. 32 wv + 31
+            // (wave 7 also rows 256, 257).  Per-image tiling is in effect, so those consecutive padded rows are ONE run of consecutive
+            // pixels of the tile's image (the border columns are simply absent from it).  FETCH: the wave copies that run, for the
+            // chunk's 32 channels, into its own fp32 staging area [32 channels][40 floats] by NP = 5 LDS-DMA pieces of 64 x 16 bytes;
+            // a channel's run starts at its first pixel's address rounded down to 16 bytes (<= 34 pixels + 3 <= 40).  CONVERT, two
+            // sub-steps later: lane item = (window row, 16-byte slot) as in stage_window — 8 ds_read_b32, split_bf16x2 as the pack
+            // does, and ds_write_b128 of hi and lo to the swizzled position the plane DMA would have filled; border positions and rows
+            // outside the image's padded grid read a zeroed area instead and become 16 zero bytes in both planes.  A wave converts
+            // only what it fetched itself, so the counted vmcnt orders the two and the staging area needs no barrier.
+            // The staging area is LDS the launch owns anyway (the fused tail's 128 KB) behind the ring.  Staging order of the channels:
+            // channel 8 ql + i sits at index 4 i + ql, so the four 8-channel slots of a row read banks 40 apart (= 8 mod 32) and the
+            // eight rows of a ds_read_b32 lane group consecutive ones: conflict-free.
+            // Schedule: FETCH of window g + 1 in the tx = 0 L phase behind dma_b(2); CONVERT split over the tx = 1 L phase (behind
+            // dma_b(0) and vmcnt(BP): the wave's first 16 rows) and the tx = 2 L phase (the rest) — the two phases in which the plane
+            // DMA's bytes land today: WAR (both groups' load_win retired behind a barrier both passed) and RAW (lgkmcnt(0) and the L
+            // phase's barrier before the next load_win) hold as they do for the DMA.  (All of it in the tx = 2 phase: that phase
+            // outgrew the other group's MFMA phase, each launch +9 %; profiles/xd3_nchw/NOTES.md.)
+            static_assert(TAIL > 0 && CV_BM == 256 && A_PT == 2 && B_PT == 1, "the fp32-source form exists for the 256-row fused-tail instances");
+            constexpr int NP = 5, ST_WAVE = NP * 1024, ST_BASE = L::RING_BYTES, ZERO_BASE = ST_BASE + 8 * ST_WAVE, ZERO_BYTES = 4608;
+            static_assert(ZERO_BASE + ZERO_BYTES <= CV_BM * 512, "staging fits the fused tail's LDS request");
+            static_assert(ZERO_BYTES >= 7 * 640 + 16, "a zero read at every channel offset");
+            const int h = p.up_h, w = p.up_w, hw = h * w, hwm = hw & 3;
+            const unsigned img = (unsigned)tile_id / (unsigned)p.tiles_per_img, t_in = (unsigned)tile_id - img * (unsigned)p.tiles_per_img;
+            const int src_C = p.cin - nchw.c0;
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(nchw.ptr + (size_t)img * src_C * hw), 0, src_C * hw * 4, flags);
+            // window row r of tap row ty is position e + ty * wp of the image's padded grid, e = 256 t - 1 + r (>= -1)
+            const int e_w = __builtin_amdgcn_readfirstlane((int)t_in * CV_BM - 1 + wv * 32);
+            const int n_ys = (int)((unsigned)(e_w + p.wp) / (unsigned)p.wp) - 1, n_xs = e_w - n_ys * p.wp;
+            const int n_xcl = n_xs - 1 < 0 ? 0 : (n_xs - 1 > w ? w : n_xs - 1);     // interior pixels of the run's first image row before it
+            int f_cl[NP], f_j[NP];                                                  // fetch item -> channel * hw, 4-pixel group
+#pragma unroll
+            for (int pc = 0; pc < NP; ++pc) {
+                const int it = pc * 64 + lane, idx = it / 10;
+                f_j[pc] = it - idx * 10;
+                f_cl[pc] = ((idx & 3) * 8 + (idx >> 2)) * hw;
+            }
+            const int ql = (lane & 3) ^ ((lane >> 3) & 3);                          // logical K slot of this lane's physical slot (cv_swz)
+            int c_y[3], c_lb[3];                                                    // convert item -> image row at ty = 0, staging byte offset at pix0 = 0
+#pragma unroll
+            for (int ps = 0; ps < 3; ++ps) {
+                const int e = (int)t_in * CV_BM - 1 + (ps < 2 ? wv * 32 + ps * 16 : CV_BM) + (lane >> 2);
+                const int y = (int)((unsigned)(e + p.wp) / (unsigned)p.wp) - 1, x = e - y * p.wp;
+                c_y[ps] = (x >= 1 && x <= w) ? y : -(1 << 20);
+                c_lb[ps] = ST_BASE + wv * ST_WAVE + ql * 160 + ((y - 1) * w + x - 1) * 4;
+            }
+            // first pixel of the wave's run at tap row ty, then the pieces; returns that pixel
+            auto fetch = [&](const int ty, const int k0) {
+                const int yp = n_ys + ty;
+                const int pix0 = yp < 1 ? 0 : (yp > h ? hw : (yp - 1) * w + n_xcl);
+                const int u = (k0 - nchw.c0) * hw + pix0;
+#pragma unroll
+                for (int pc = 0; pc < NP; ++pc)
+                    CV_BLDS(rs, smem + ST_BASE + wv * ST_WAVE + pc * 1024, (((f_cl[pc] + u) >> 2) + f_j[pc]) << 4);
+                return pix0;
+            };
+            // part 1: the wave's first 16 rows; part 2: its other 16 (and wave 7's two extra rows)
+            auto convert = [&](const int ty, const int pix0, const int part) {
+                const int uc = (ty * w - pix0) * 4;
+                int so[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) so[i] = i * 640 + (((pix0 + (i & 3) * hwm) & 3) << 2);
+                auto pass = [&](const int cy, const int lb, unsigned char* dst) {
+                    const int base = (unsigned)(cy + ty - 1) < (unsigned)h ? lb + uc : ZERO_BASE;
+                    float v[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const float*>(smem + base + so[i]);
+                    uint32_t hh[4], ll[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {             // split_bf16x2 with its two subtractions spelled as statements: as plain
+                        // C++ hipcc pairs them into one v_pk_add_f32 (half rate) behind four v_mov into aligned register pairs, and this
+                        // phase's VALU time is MFMA time of the other wave group (profiles/xd3_nchw/NOTES.md)
+                        hh[k] = f32x2_to_bf16x2_rne(v[2 * k], v[2 * k + 1]);
+                        float d0, d1;
+                        asm("v_sub_f32 %0, %1, %2" : "=v"(d0) : "v"(v[2 * k]), "v"(hh[k] << 16));
+                        asm("v_sub_f32 %0, %1, %2" : "=v"(d1) : "v"(v[2 * k + 1]), "v"(hh[k] & 0xffff0000u));
+                        ll[k] = f32x2_to_bf16x2_rne(d0, d1);
+                    }
+                    // stores as statements: before a store hipcc can see it drains every LDS-DMA piece in flight (vmcnt(0)), the two
+                    // weight stages included; the L phase's own lgkmcnt(0) covers them
+                    typedef uint32_t __attribute__((ext_vector_type(4))) u32x4_t;
+                    const u32x4_t vh = {hh[0], hh[1], hh[2], hh[3]}, vl = {ll[0], ll[1], ll[2], ll[3]};
+                    asm volatile("ds_write_b128 %0, %1\n\tds_write_b128 %0, %2 offset:%3"
+                                 :: "v"((uint32_t)(uintptr_t)(lptr_t)dst), "v"(vh), "v"(vl), "n"(A_BYTES) : "memory");
+                };
+                unsigned char* dst = win_slot(0) + wv * 32 * CV_ROW + lane * 16;
+                if (part & 1) pass(c_y[0], c_lb[0], dst);
+                if (part & 2) {
+                    pass(c_y[1], c_lb[1], dst + 16 * CV_ROW);
+                    if (wv == 7 && lane < 8) pass(c_y[2], c_lb[2], win_slot(0) + CV_BM * CV_ROW + lane * 16);
+                }
+            };
+            for (int i = tid; i < ZERO_BYTES / 4; i += NT) reinterpret_cast<uint32_t*>(smem + ZERO_BASE)[i] = 0u;
+            const bool w0_src = nchw.c0 == 0;                // window 0 comes from src
+            int c_ty = 0, c_p0 = 0;                           // tap row and first pixel of the fetch in flight
+            if (w0_src) { c_p0 = fetch(0, 0); gw.advance(3); } else dma_a();
+            dma_b(0);
+            dma_b(1);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                     // the zeroed area is every wave's to read
+            if (w0_src) {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * BP) : "memory");
+                convert(0, c_p0, 3);
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(BP) : "memory");
+            } else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP) : "memory");
+            __builtin_amdgcn_s_barrier();
+            if (grp == 1) __builtin_amdgcn_s_barrier();
+            for (int g = 0; g < ngroups; ++g) {
+                const bool lastg = g + 1 == ngroups;
+                const bool nx = !lastg && gw.k0 >= nchw.c0;  // window g + 1 comes from src
+                // ---- tx = 0 ----
+                asm volatile("" ::: "memory");
+                load_win();
+                load_b(wt_slot(0), fbh, fbl);
+                dma_b(2);                                     // stage 3g + 2
+                if (nx) {
+                    c_ty = gw.i; c_p0 = fetch(gw.i, gw.k0); gw.advance(3);
+                    wait_barrier<BP + NP>();                  // stage 3g + 1 landed
+                } else wait_barrier<BP>();
+                mfmas(ah[0], al[0]);
+                // ---- tx = 1 ----
+                asm volatile("" ::: "memory");
+                load_b(wt_slot(1), fbh, fbl);
+                if (!lastg) {
+                    dma_b(0);                                 // stage 3g + 3
+                    if (nx) {                                 // the fetch (and stage 3g + 2, issued before it) landed
+                        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BP) : "memory");
+                        convert(c_ty, c_p0, 1);
+                        wait_barrier<BP>();
+                    } else {
+                        dma_a();
+                        if (wv == 0) wait_barrier<BP + AP + 2>(); else wait_barrier<BP + AP>();
+                    }
+                } else wait_barrier<0>();
+                mfmas(ah[1], al[1]);
+                // ---- tx = 2 ----
+                asm volatile("" ::: "memory");
+                load_b(wt_slot(2), fbh, fbl);
+                if (!lastg) {
+                    dma_b(1);                                 // stage 3g + 4
+                    if (nx) convert(c_ty, c_p0, 2);
+                    wait_barrier<BP>();                       // stage 3g + 3 landed, window g + 1 written
+                } else wait_barrier<0>();
+                mfmas(ah[2], al[2]);
+            }
+        } else {                                              // every other instance: the loop as it was (its lines left where they were)
         dma_a();
         dma_b(0);
         dma_b(1);
@@ -926,6 +1073,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
             if (!lastg) { dma_b(1); wait_barrier<BP>(); }     // stage 3g + 4; stage 3g + 3 and window g + 1 landed
             else wait_barrier<0>();
             mfmas(ah[2], al[2]);
+        }
         }
         if (grp == 0) __builtin_amdgcn_s_barrier();           // balance group 1's extra barrier
         __syncthreads();                                      // nothing in flight; the ring is dead
@@ -1246,6 +1394,12 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const ConvParams p) {
     conv_mfma_tile<NF, WN, CV_BM, SPB, TAIL, NT, PP, WIN>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x);
 }
 
+// The fp32-source instances (magnet_conv_mfma_nchw): the 8-wave 256-row fused-tail loop with the NCHW flag, under a name of their own
+template <int TAIL>
+__global__ __launch_bounds__(512, 2) void conv_mfma_nchw_kernel(const ConvParams p, const ConvSrc src) {
+    conv_mfma_tile<8, 2, 256, 1, TAIL, 512, true, 2, false, false, false, true>(p, blockIdx.x, gridDim.x, blockIdx.y, threadIdx.x, nullptr, 0, 1, src);
+}
+
 // The instances of the single-plane fp16 format: kernels of their own name, so the bf16x3 instances keep theirs
 template <int NF, int WN, int CV_BM, int SPB, int TAIL, int NT, bool PP, int WIN>
 __global__ __launch_bounds__(NT, 2) void conv_mfma_f16_kernel(const ConvParams p) {
@@ -1340,6 +1494,8 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
 }
 
 template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
+constexpr size_t conv_lds_bytes_c = ConvLds<NF, WN, BM, SPB, NT, PP, WIN, F16>::TOTAL;
+template <int NF, int WN, int BM, int SPB, int NT = 256, bool PP = false, int WIN = 0, bool F16 = false>
 static size_t conv_lds_bytes() { return ConvLds<NF, WN, BM, SPB, NT, PP, WIN, F16>::TOTAL; }
 
 // > 64 KiB of dynamic LDS needs the opt-in attribute: set once per kernel and process (`done`: the launching instance's static flag)
@@ -1387,6 +1543,32 @@ static hipError_t launch_conv_tail(const ConvParams& p, hipStream_t s) {
     case 144: return launch_conv_nf<8, 2, BM, 1, 9, NT, PP, WIN>(p, s);
     default:  return hipErrorInvalidValue;
     }
+}
+
+// The fp32-source form (magnet_conv_mfma_nchw, which has checked what it serves): the 256-row 8-wave loop with the fused tail of G-Net
+// (Gaussian update) or the mask head (upsampling), per-image tiling in effect.  The LDS request is launch_conv_nf's for these tails,
+// BM * 512 bytes: the staging area lives behind the ring inside it (conv_mfma_tile asserts that it fits)
+template <int TAIL>
+static hipError_t launch_conv_nchw_tail(const ConvParams& p_in, const ConvSrc& src, hipStream_t s) {
+    ConvParams p = p_in;
+    const long long n_tiles = conv_row_tiles(p.up_B, p.up_h, p.wp, 256, &p.tiles_per_img);
+    if (!p.tiles_per_img) return hipErrorInvalidValue;             // a tile must lie inside ONE image
+    if (p.tiles_out) *p.tiles_out = n_tiles;
+    constexpr size_t lds = 256 * 512;
+    static_assert(lds >= conv_lds_bytes_c<8, 2, 256, 1, 512, true, 2>, "the ring fits the fused tail's request");
+    static bool attr_set = false;
+    lds_opt_in(reinterpret_cast<const void*>(&conv_mfma_nchw_kernel<TAIL>), lds, attr_set);
+    hipLaunchKernelGGL(conv_mfma_nchw_kernel<TAIL>, dim3((unsigned)n_tiles, 1), dim3(512), lds, s, p, src);
+    return hipGetLastError();
+}
+
+static hipError_t launch_conv_nchw(const ConvParams& p, const ConvSrc& src, hipStream_t s) {
+    if (!src.ptr || !p.tail_w_hi || p.cout_pad != 128 || p.tap_n != 3 || p.tap_sx != 1 || p.in_sc || p.addend || p.variant || (p.tiling & ~2) ||
+        !(p.rows >= 256ll * 256 || (p.tiling & 2)) || p.up_B <= 0 || src.c0 < 0 || src.c0 >= p.cin)
+        return hipErrorInvalidValue;
+    if (p.tail_cout == 16 && p.gu_out) return launch_conv_nchw_tail<1>(p, src, s);
+    if (p.tail_cout == 144 && p.up_out) return launch_conv_nchw_tail<9>(p, src, s);
+    return hipErrorInvalidValue;
 }
 
 // The (hi, lo) plane format (CONV_BF16X3; magnet_conv_mfma and magnet_conv_mfma_ex)
@@ -1544,8 +1726,9 @@ static bool route_serves(const ConvParams& p, ConvRoute route, int S, const floa
     return false;
 }
 
-hipError_t launch_conv(const ConvParams& p, ConvRoute route, int S, float* work, hipStream_t s) {
+hipError_t launch_conv(const ConvParams& p, ConvRoute route, int S, float* work, hipStream_t s, const ConvSrc* nchw) {
     if (!route_serves(p, route, S, work)) return hipErrorInvalidValue;
+    if (nchw) return (route == CONV_BF16X3 && !S) ? launch_conv_nchw(p, *nchw, s) : hipErrorInvalidValue;
     switch (route) {
     case CONV_BF16X3: return S ? launch_splitk<false>(p, S, work, s) : launch_conv_mfma(p, s);
     case CONV_F16:    return S ? hipErrorInvalidValue : launch_conv_mfma_f16(p, s);

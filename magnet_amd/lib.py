@@ -177,6 +177,11 @@ class MagnetConvExArgs(ctypes.Structure):
                 ("tiling", ctypes.c_int32), ("tiles_out", ctypes.POINTER(ctypes.c_int64))]
 
 
+class MagnetConvNchwArgs(ctypes.Structure):
+    """Mirror of `struct MagnetConvNchwArgs` (include/magnet_hip.h)."""
+    _fields_ = [("ex", MagnetConvExArgs), ("src", ctypes.c_void_p), ("src_c0", ctypes.c_int32), ("src_C", ctypes.c_int32)]
+
+
 class MagnetFnetLossArgs(ctypes.Structure):
     """Mirror of `struct MagnetFnetLossArgs` (include/magnet_hip.h)."""
     _fields_ = [("x", ctypes.c_void_p), ("d", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("pred", ctypes.c_void_p),
@@ -280,6 +285,7 @@ _PROTOS = {
     "magnet_spp_pool_backward": (_C, [_S(MagnetSppBwdArgs), _P]),
     "magnet_fnet_stem_wgrad": (_C, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "magnet_conv_mfma_ex": (_C, [_S(MagnetConvExArgs), _P]),
+    "magnet_conv_mfma_nchw": (_C, [_S(MagnetConvNchwArgs), _P]),
     "magnet_conv_mfma_f16": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_conv_mfma_f16p": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_conv_mfma_splitk_workspace": (_L, [_S(MagnetConvExArgs), _I]),
@@ -645,7 +651,7 @@ _CONV_ROUTES = {
 
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
-              mx=None, leaky=None, tiling=None, f16=False, split_k=None, work=None, silu=False):
+              mx=None, leaky=None, tiling=None, f16=False, split_k=None, work=None, silu=False, src_nchw=None):
     """One convolution layer on the matrix cores.  in_hi/in_lo: bf16 tensors whose data_ptr is row 0 (possibly a
     channel-offset view of a wider buffer, `in_ld` = its row pitch in elements); weights (taps, cout_pad, cin) bf16.
     F-Net extras (include/magnet_hip.h): dil (3x3 dilation), out_ld (write a channel slice: out tensors may then be
@@ -672,7 +678,16 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     f16 = "wide": the same operand format, plane to plane at any cout_pad % 128 == 0 (magnet_conv_mfma_f16d, the D-Net decoder's plain
     layers): taps 1 / 9, relu or leaky, border, repad and channel slices; the output is out_f16 (passed as out_hi with out_lo None),
     out_f32 or the split-bf16 pair out_hi / out_lo; no tail, addend, add, mx, dil or out_bf16.  split_k / work are allowed on this route
-    (magnet_conv_mfma_f16d_splitk).  Returns the row tile count."""
+    (magnet_conv_mfma_f16d_splitk).  Returns the row tile count.
+    src_nchw = (x (B, C, h, w) fp32 contiguous, c0): input channels [c0, c0 + C) with c0 + C == cin are read in place from x and split
+    inside the kernel (magnet_conv_mfma_nchw: the fused-tail 3x3 launches on 256-row tiles under per-image tiling, nothing else); the
+    planes hold channels [0, c0) and may be None when c0 == 0.  Returns the row tile count."""
+    if src_nchw is not None:
+        if f16 or mx is not None or split_k is not None or leaky is not None or silu:
+            raise MagnetError("conv_mfma (src_nchw): the bf16x3 fused-tail launch only — not with f16, mx, split_k, leaky or silu")
+        _dev(src_nchw[0], "src_nchw", torch.float32)
+        if src_nchw[0].dim() != 4:
+            raise MagnetError("conv_mfma (src_nchw): src must be (B, C, h, w)")
     wide = isinstance(f16, str) and f16 == "wide"
     if split_k is not None:
         if (f16 and not wide) or tail is not None or addend is not None or add is not None or mx is not None:
@@ -714,11 +729,12 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
             raise MagnetError("conv_mfma (mx): scale planes must be int32 GPU tensors")
         a.in_sc, a.w_sc, a.sc_rows = isc.data_ptr(), wsc.data_ptr(), int(sc_rows)
     else:
-        for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo")):
+        no_planes = src_nchw is not None and int(src_nchw[1]) == 0 and in_hi is None and in_lo is None
+        for t, n in ((w_hi, "w_hi"), (w_lo, "w_lo")) if no_planes else ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo")):
             _bf16_ptr(t, f"conv_mfma: {n}")
-    a.in_hi, a.w_hi = in_hi.data_ptr(), w_hi.data_ptr()
+    a.in_hi, a.w_hi = (in_hi.data_ptr() if in_hi is not None else None), w_hi.data_ptr()
     if not f16:
-        a.in_lo, a.w_lo = in_lo.data_ptr(), w_lo.data_ptr()
+        a.in_lo, a.w_lo = (in_lo.data_ptr() if in_lo is not None else None), w_lo.data_ptr()
     a.bias = _dev(bias, "bias", torch.float32).data_ptr()
     a.rows, a.cin, a.cout_pad, a.taps, a.wp = int(rows), int(cin), int(w_hi.shape[1]), int(taps), int(wp)
     a.relu, a.in_ld = int(bool(relu)), int(in_ld)
@@ -758,10 +774,16 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_hi = 3, _f16_ptr(out_hi, "out_hi (fp16 plane)")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
-    if leaky is None and tiling is None and not f16 and split_k is None and not silu:
+    if leaky is None and tiling is None and not f16 and split_k is None and not silu and src_nchw is None:
         _launch("magnet_conv_mfma", in_hi, ctypes.byref(a))
         return None
     tiles = ctypes.c_int64(0)
+    if src_nchw is not None:
+        src, c0 = src_nchw
+        n = MagnetConvNchwArgs(ex=MagnetConvExArgs(base=a, act=ACT_BASE, tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles)),
+                               src=src.data_ptr(), src_c0=int(c0), src_C=int(src.shape[1]))
+        _launch("magnet_conv_mfma_nchw", src, ctypes.byref(n))
+        return tiles.value
     x = MagnetConvExArgs(base=a, act=ACT_SILU if silu else (ACT_BASE if leaky is None else ACT_LEAKY_RELU), act_slope=float(leaky or 0.0),
                          tiling=int(tiling or 0), tiles_out=ctypes.pointer(tiles))
     more = () if split_k is None else (int(split_k), work.data_ptr(), work.numel() * 4)

@@ -40,6 +40,26 @@ def depth_sampling(sampling_range, n_samples) -> list:
     return [(k[i + 1] + k[i]) / 2 for i in range(n_samples)]
 
 
+def x_d3_route(*, x_d3_is_tensor, aligned16, source, conv_precision, fuse_conv_tail, fuse_upsample, can_fuse_gauss, can_fuse_upsample,
+               n_iter, hoist_invariant, downsample_ratio, overlap_pack, overlap_mask_head, B, h, w, tile_256=False, small_tiles=False):
+    """How _refine_mfma feeds x_d3 to the two fused 3x3 launches: "nchw" = both read the NCHW fp32 tensor in place
+    (magnet_conv_mfma_nchw) and its pack_split pass is skipped, "pack" = it is packed into the G-Net input buffer first.  "nchw" only
+    where that entry point serves BOTH launches of the step: the default bf16x3 step with both fused tails, no hoisted invariant
+    launch (which reads the packed planes), no side streams, the 256-row kernel (65 536 rows or more, or stacks with tile_256 set;
+    never a stack forced to 64-row tiles, small_tiles) and per-image row tiling in effect.  Host arithmetic only."""
+    if source == "pack" or not x_d3_is_tensor or not aligned16:
+        return "pack"
+    if source != "auto":
+        raise lib.MagnetError(f"x_d3_source must be 'auto' or 'pack', got {source!r}")
+    if conv_precision != "bf16x3" or not (fuse_conv_tail and fuse_upsample and can_fuse_gauss and can_fuse_upsample):
+        return "pack"
+    if (n_iter >= 2 and hoist_invariant) or n_iter < 1 or downsample_ratio != 4 or overlap_pack or overlap_mask_head:
+        return "pack"
+    if small_tiles or (B * (h + 2) * (w + 2) < 65536 and not tile_256):
+        return "pack"
+    return "nchw" if lib.conv_row_tiles(B, h, w + 2, 256)[1] > 0 else "pack"
+
+
 def _upsample_depth_torch(depth, up_mask, k):
     """Differentiable form of the learned convex upsampling (reference models/MAGNET.py:15-27): per low-resolution
     pixel, softmax over the 9 neighbours of each of the k*k sub-pixels, convex combination of the zero-padded 3x3 patch."""
@@ -237,6 +257,9 @@ class MAGNET(nn.Module):
         self.overlap_pack = False      # measured: 8.01 vs 8.08 ms per C2 step, and it stretches the matcher launch 1.06 -> 1.57 ms
         self._side = {}
         self.fuse_conv_tail = True     # 1x1 layers of g_net / mask_head fused into their 3x3 layer's epilogue
+        # "auto": where x_d3_route() says so, the two fused 3x3 launches read x_d3 as the NCHW fp32 tensor it arrives as and split it in
+        # LDS: no pack_split pass over it.  "pack": always pack it first (A/B runs, tests).  Results do not depend on it, bit for bit.
+        self.x_d3_source = "auto"
         self.fnet_mfma = True          # run a PSMNet-structured f_net on the matrix-core path (magnet_amd/fnet.py)
         self._fnet = None
 
@@ -354,14 +377,22 @@ class MAGNET(nn.Module):
         ev_pack = torch.cuda.Event()
         if pack_stream is not main:
             pack_stream.wait_stream(main)            # the packed features exist; the previous forward no longer reads `gin`
+        nchw = False
         if x_d3 is not None:
             x_d3 = x_d3.detach().float().contiguous()
+            nchw = x_d3_route(x_d3_is_tensor=True, aligned16=x_d3.data_ptr() % 16 == 0, source=self.x_d3_source,
+                              conv_precision=self.conv_precision, fuse_conv_tail=self.fuse_conv_tail, fuse_upsample=self.fuse_upsample,
+                              can_fuse_gauss=g_stack.can_fuse_gauss(dev), can_fuse_upsample=m_stack.can_fuse_upsample(dev), n_iter=n_iter,
+                              hoist_invariant=self.hoist_invariant, downsample_ratio=self.downsample_ratio, overlap_pack=self.overlap_pack,
+                              overlap_mask_head=self.overlap_mask_head, B=B, h=h, w=w,
+                              tile_256=g_stack.tile_256 and m_stack.tile_256,
+                              small_tiles=g_stack.small_tiles is True or m_stack.small_tiles is True) == "nchw"
             if pack_stream is not main:
                 x_d3.record_stream(pack_stream)
             with torch.cuda.stream(pack_stream):
                 if f16:
                     lib.pack_f16(x_d3, gin16, ctot, Dp)
-                else:
+                elif not nchw:
                     lib.pack_split(x_d3, gin_hi, gin_lo, ctot, Dp)
         elif f16:
             with torch.cuda.stream(pack_stream):
@@ -400,6 +431,16 @@ class MAGNET(nn.Module):
             main.wait_event(ev_pack)                                                                 # x_d3 channels are in place
             if self.fuse_upsample and g_stack.can_fuse_gauss(dev):
                 new_pred = torch.empty_like(pred_list[-1])                                           # MAGNET.py:62 + 60-69 in one launch
+                if nchw:
+                    try:                                      # x_d3 read in place: the planes hold the cost channels [0, Dp) only
+                        g_stack.run(gin_hi, gin_lo, ctot, rows, wp, work, gauss=(pred_list[-1], new_pred), src_nchw=(x_d3, Dp))
+                        pred_list.append(new_pred)
+                        continue
+                    except lib.MagnetError as e:
+                        if e.code != lib.E_DIM:
+                            raise
+                        nchw = False                          # a form the entry point does not serve after all: pack, today's path
+                        lib.pack_split(x_d3, gin_hi, gin_lo, ctot, Dp)
                 g_stack.run(src_hi, src_lo, ctot, rows, wp, work, first_addend=partial, n_var=D, inv_off=Dp, gauss=(pred_list[-1], new_pred), **fkw)
                 pred_list.append(new_pred)
                 continue
@@ -414,6 +455,9 @@ class MAGNET(nn.Module):
                 # LDS) and writes every iteration's x4-upsampled prediction; the (B, 144, h, w) mask never reaches HBM
                 d = torch.stack(pred_list[1:])
                 outs = torch.empty((d.shape[0], B, 2, 4 * h, 4 * w), dtype=torch.float32, device=dev)
+                if nchw:
+                    m_stack.run(None, None, ctot, rows, wp, work.setdefault("mask", {}), upsample=(d, outs), src_nchw=(x_d3, 0))
+                    return [outs[i] for i in range(outs.shape[0])]
                 m_stack.run(*m_src, ctot, rows, wp, work.setdefault("mask", {}), upsample=(d, outs), **fkw)
                 return [outs[i] for i in range(outs.shape[0])]
             mask_out = m_stack.run(*m_src, ctot, rows, wp, work.setdefault("mask", {}), **fkw)      # MAGNET.py:172
