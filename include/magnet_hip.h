@@ -42,12 +42,14 @@ extern "C" {
 
 #define MAGNET_API __attribute__((visibility("default")))
 
-#define MAGNET_HIP_VERSION 400            /* major*10000 + minor*100 + patch.
+#define MAGNET_HIP_VERSION 500            /* major*10000 + minor*100 + patch.
                                            * BINARY COMPATIBILITY: the argument structs below carry no size field and have grown at their END between versions
-                                           * (MagnetConvArgs: v300 up_*, v301 gu_*, v302 in_sc / w_sc / sc_rows).  A caller must be compiled against the header whose
+                                           * (MagnetConvArgs: v300 up_*, v301 gu_*).  A caller must be compiled against the header whose
                                            * MAGNET_HIP_VERSION equals magnet_version() of the library it loads, and must check that at load time (INTEGRATION.md;
                                            * magnet_amd/lib.py mirrors the structs field for field and tests/test_abi.py compares the layouts with a gcc probe).
-                                           * From v400 on a struct change bumps the MINOR number, never only the patch. */
+                                           * From v400 on a struct change bumps the MINOR number, never only the patch.
+                                           * v500 REMOVED the v302 fp16 + block-scaled e4m3 operand format (the last three fields of MagnetConvArgs and its
+                                           * pack entry point) and magnet_conv1x1_chain: MagnetConvArgs, and with it every struct that embeds it, is shorter. */
 
 enum {                                     /* storage dtype of channel-last feature maps */
     MAGNET_FEAT_F32  = 0,
@@ -256,7 +258,8 @@ typedef struct MagnetConvArgs {
     const void  *tail_w_hi, *tail_w_lo;    /* optional fused 1x1 tail (models/MAGNET.py:53-55, :113-115): after THIS layer (cout_pad
                                               must be 128; bias / relu / addend apply) the workgroup's 128-row tile stays in LDS and
                                               relu(1x1 128->128), relu(1x1 128->128), 1x1 128->tail_cout_pad run in the same kernel.
-                                              Weights / bias laid out as for magnet_conv1x1_chain.  The only output is fp32
+                                              Weights: the three layers' [cout][128] bf16 planes concatenated; bias: 128 + 128 +
+                                              tail_cout_pad floats.  The only output is fp32
                                               (rows, tail_cout_pad) at out_f32 (out_mode, out_hi/lo, out_ld are ignored): the three
                                               hidden (rows,128) tensors never reach HBM. */
     const float *tail_bias;
@@ -274,26 +277,14 @@ typedef struct MagnetConvArgs {
      * up_h / up_w as above, out_f32 is not written.  NULL = plain tail (magnet_gaussian_update_cl then does this step). */
     const float *gu_in;
     float       *gu_out;
-    /* v302 — the "2-unit" operand format of the 128-wide 3x3 layers with a fused tail (taps = 9, rows >= 65536, no addend): in_hi / w_hi
-     * are FP16 planes (same shapes as the bf16 hi planes), in_lo / w_lo hold per 64-byte (row, 32-channel block) slice the 32 OCP e4m3
-     * bytes of hi / 2^e_h followed by the 32 e4m3 bytes of (x - fp16(x)) / 2^e_l, and the E8M0 exponents travel separately:
-     * in_sc [cin / 32][sc_rows] uint32 {e_h + 127, e_l + 127, 0, 0} per (block, row), w_sc [taps][cin / 32][cout_pad] uint32 likewise per
-     * (tap, block, output channel).  magnet_pack_mx writes the activation planes; magnet_amd/convnet.py prepares the weights.  The kernel
-     * runs hi*hi on the fp16 matrix instruction and lo*hi + hi*lo on the block-scaled fp8 one (x*w to ~1e-5 relative, as the bf16x3 form):
-     * 2 matrix-pipe units per product term instead of 3.  NULL / 0 = the bf16x3 format described above.
-     * DOMAIN of this format: |x| <= 65504 (the fp16 plane); magnet_pack_mx clamps larger magnitudes, +-Inf included, to +-65504 (the
-     * bf16x3 format has no such limit).  NON-FINITE inputs: a NaN is written through to every plane (fp16 NaN, e4m3 NaN; the block
-     * exponents are taken over the finite entries) and the outputs that read it are NaN in BOTH formats; +-Inf propagates as Inf in the
-     * bf16x3 format and is clamped here — the one documented difference between the two formats.  `bias` is read with 16-byte loads in every format: 16-byte aligned, as all pointers of this struct. */
-    const void  *in_sc, *w_sc;
-    int64_t      sc_rows;
+    /* `bias` is read with 16-byte loads in every format: 16-byte aligned, as all pointers of this struct. */
     /* The SINGLE-PLANE FP16 format (magnet_conv_mfma_f16 below; an entry point of its own, no field of this struct): in_hi is ONE fp16
-     * plane (rows, in_ld), w_hi ONE fp16 plane (taps, cout_pad, cin); in_lo, w_lo, in_sc, w_sc are NULL.  The 3x3 layer issues one fp16
+     * plane (rows, in_ld), w_hi ONE fp16 plane (taps, cout_pad, cin); in_lo, w_lo are NULL.  The 3x3 layer issues one fp16
      * matrix instruction per product (each fp16 x fp16 product is exact in the fp32 accumulator) instead of three bf16 ones; the
      * operands carry 11 significant bits instead of 16.  It is a reduced-precision mode the caller opts into, not fp32-grade.
      * DOMAIN: |x| <= 65504; relative rounding 2^-11 for |x| >= 2^-14, absolute 2^-25 below (fp16 denormals are kept).  magnet_pack_f16 and
      * magnet_planes_to_f16 write the activation plane: round to nearest even, magnitudes that would round above 65504 (+-Inf included)
-     * become +-65504 as in magnet_pack_mx, NaN is written through, the sign of zero is kept.  The fused 1x1 tail layers, bias, addend,
+     * become +-65504 (never Inf), NaN is written through, the sign of zero is kept.  The fused 1x1 tail layers, bias, addend,
      * ReLU, the Gaussian update and the convex upsampling behind the 3x3 layer are those of the bf16x3 format (tail_w_hi / tail_w_lo stay
      * bf16 planes).
      * A SECOND entry point reads this format, magnet_conv_mfma_f16p ("plane to plane", the F-Net's layers): there the residual input
@@ -304,12 +295,6 @@ typedef struct MagnetConvArgs {
 } MagnetConvArgs;                          /* out_mode 2: one bf16 plane (round-to-nearest-even) at out_hi */
 
 MAGNET_API int magnet_conv_mfma(const MagnetConvArgs *args, void *stream);
-
-/* fp32 NCHW (N, C, h, w) -> channels [c_off, c_off + C) of the interior of a (N, h+2, w+2, ctot) buffer in the v302 operand format of
- * magnet_conv_mfma: out_f16 (fp16 plane), out_qr (e4m3 hi | lo bytes, 64 B per (row, 32-channel block)), out_sc [ctot / 32][sc_rows]
- * uint32 E8M0 pairs.  C, c_off, ctot multiples of 32; h*w a multiple of 4; the border rows are not written (zero them once). */
-MAGNET_API int magnet_pack_mx(const float *nchw, void *out_f16, void *out_qr, void *out_sc, int32_t N, int32_t C, int32_t h, int32_t w,
-                              int32_t ctot, int32_t c_off, int64_t sc_rows, int64_t in_img_stride, void *stream);
 
 /* ---- the F-Net's non-GEMM layers (PSMNet feature extractor, models/submodules/F_psmnet.py:37-124; row N3) ----
  * Activations are conv_mfma's format: zero-bordered channel-last grids as two bf16 planes (hi, lo). */
@@ -337,13 +322,6 @@ MAGNET_API int magnet_avgpool_cl(const void *in_hi, const void *in_lo, int32_t l
 MAGNET_API int magnet_upsample_bilinear_cl(const float *in, int32_t in_ld, int32_t ph, int32_t pw, int32_t C, void *out_hi,
                                            void *out_lo, int32_t out_ld, int32_t N, int32_t h, int32_t w, int32_t pad,
                                            void *stream);
-
-/* The 1x1 tail of a stack in one launch: relu(conv1x1 128->128), relu(conv1x1 128->128), conv1x1 128->cout_pad.
- * in: split-bf16 (rows,128) planes (the 3x3 layer's out_mode-0 output); w_hi/w_lo: the three layers' [cout][128]
- * bf16 planes concatenated; bias: 128 + 128 + cout_pad floats; out: fp32 (rows, cout_pad).  cout_pad in {16,128,144}.
- * (models/MAGNET.py:53-55 and :113-115.) */
-MAGNET_API int magnet_conv1x1_chain(const void *in_hi, const void *in_lo, const void *w_hi, const void *w_lo,
-                                    const float *bias, float *out, int64_t rows, int32_t cout_pad, void *stream);
 
 /* fp32 NCHW (N, C, h, w) (image stride `in_img_stride` elements, 0 = C*h*w) -> the interior of the split-bf16
  * padded channel-last buffer (N, h+2, w+2, ctot), channels [c_off, c_off+round_up(C,8)) (the round-up lanes are
@@ -616,7 +594,7 @@ enum {                                     /* MagnetConvExArgs.tiling: bit flags
     MAGNET_TILING_BM256 = 2,               /* fused-tail 3x3 launches: the 256-row 8-wave kernel also below 65 536 rows */
     MAGNET_TILING_BM64  = 4                /* 64-row tiles of the 4-wave register-window kernel (latency mode: twice the workgroups of the
                                               128-row form, bit-identical results): 3x3 launches (taps == 9) with cout_pad == 128 and a
-                                              fused tail, or plain with cout_pad % 128 == 0; not the fp16 + e4m3 format, not with BM256.
+                                              fused tail, or plain with cout_pad % 128 == 0; not with BM256.
                                               Any other launch is refused with MAGNET_E_DIM */
 };
 
@@ -638,7 +616,7 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs *args, void *stream);
  * Serves exactly: bf16x3 operands, taps == 9 without dilation, cout_pad == 128, the fused tail of 16 outputs with gu_in / gu_out or of
  * 144 outputs with up_depth / up_out, the 256-row kernel (rows >= 65 536 or MAGNET_TILING_BM256), no addend, act == MAGNET_ACT_BASE,
  * and per-image row tiling in effect (magnet_conv_row_tiles(up_B, up_h, wp, 256) reports tiles per image > 0; MAGNET_TILING_FLAT is
- * refused).  Everything else — MAGNET_TILING_BM64, the fp16 and e4m3 formats, a residual, border or repad form among it — is refused
+ * refused).  Everything else — MAGNET_TILING_BM64, the fp16 formats, a residual, border or repad form among it — is refused
  * with MAGNET_E_DIM, a NULL src with MAGNET_E_NULL, a misaligned one with MAGNET_E_ALIGN, before any launch.  tiles_out works. */
 typedef struct MagnetConvNchwArgs {
     MagnetConvExArgs ex;
@@ -649,7 +627,7 @@ typedef struct MagnetConvNchwArgs {
 MAGNET_API int magnet_conv_mfma_nchw(const MagnetConvNchwArgs *args, void *stream);
 
 /* The 3x3 layer of a G-Net / mask-head stack on the single-plane fp16 operand format (see MagnetConvArgs): base.in_hi / base.w_hi are
- * the fp16 planes; base.in_lo, base.w_lo, base.in_sc, base.w_sc must be NULL (MAGNET_E_DIM otherwise: planes of another format are
+ * the fp16 planes; base.in_lo, base.w_lo must be NULL (MAGNET_E_DIM otherwise: planes of another format are
  * refused, not mis-read).  Serves what the inference loop launches and refuses the rest with MAGNET_E_DIM: taps == 9 without dilation,
  * cout_pad == 128, and either the fused tail with tail_cout_pad 16 or 144 (tail_w_hi / tail_w_lo bf16 planes; with gu_in / gu_out,
  * up_depth / up_out and addend as in magnet_conv_mfma) or the plain layer with fp32 output (out_mode 1, optional addend).  No residual,
@@ -659,13 +637,13 @@ MAGNET_API int magnet_conv_mfma_f16(const MagnetConvExArgs *args, void *stream);
 
 /* The single-plane fp16 format, plane to plane: the launches of an F-Net whose every activation buffer is ONE zero-bordered
  * channel-last fp16 plane (FNetMFMA(precision="fp16")).  The struct's fields mean, for this entry point only:
- *   base.in_hi / base.w_hi   fp16 planes (rows, in_ld) / (taps, cout_pad, cin); base.in_lo, w_lo, in_sc, w_sc and add_lo must be NULL
+ *   base.in_hi / base.w_hi   fp16 planes (rows, in_ld) / (taps, cout_pad, cin); base.in_lo, w_lo and add_lo must be NULL
  *   base.add_hi              optional residual input, ONE fp16 plane with row pitch add_ld, added before bias / ReLU
  *   base.out_mode            3: one fp16 plane at out_hi (saturating round-to-nearest-even, NaN written through: see MagnetConvArgs);
  *                            1 (fp32 at out_f32) and 2 (one bf16 plane at out_hi) as in magnet_conv_mfma; 0 is refused
  *   border_hp / border_pad / repad / dil / in_ld / out_ld   as in magnet_conv_mfma
  * Serves taps 1, 4 and 9, cout_pad 32, 64 and 128, cin a multiple of 32, act == MAGNET_ACT_BASE, tiling 0 or MAGNET_TILING_FLAT (always
- * 128-row tiles); tiles_out works.  A fused tail, an addend, the Gaussian update / upsampling, the e4m3 format and MAGNET_TILING_BM64 /
+ * 128-row tiles); tiles_out works.  A fused tail, an addend, the Gaussian update / upsampling and MAGNET_TILING_BM64 /
  * MAGNET_TILING_BM256 are refused with MAGNET_E_DIM.  Each fp16 x fp16 product is exact in the fp32 accumulator; bias, residual and ReLU
  * are fp32 arithmetic as in magnet_conv_mfma. */
 MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs *args, void *stream);
@@ -681,7 +659,7 @@ MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs *args, void *stream)
  * Serves: 2 <= split_k <= MAGNET_SPLITK_MAX; taps 1 or 9 (dil as in magnet_conv_mfma); cout_pad a multiple of 128; every split at least
  * MAGNET_SPLITK_MIN_CHUNKS chunks ((cin / 32) / split_k >= MAGNET_SPLITK_MIN_CHUNKS; the K loop's ring itself runs from one chunk on —
  * two keep its prefetch in use); out_mode 0 or 1; tiling 0 or MAGNET_TILING_FLAT (128-row tiles); tiles_out works.  A fused tail,
- * addend, residual input, the e4m3 format, the Gaussian update / upsampling, MAGNET_TILING_BM64 / BM256 and any other out_mode are
+ * addend, residual input, the Gaussian update / upsampling, MAGNET_TILING_BM64 / BM256 and any other out_mode are
  * refused with MAGNET_E_DIM; `work` NULL: MAGNET_E_NULL, not 16-byte aligned: MAGNET_E_ALIGN, work_bytes too small: MAGNET_E_DIM.  A
  * refused call writes nothing.  The workspace query returns split_k * rows * cout_pad * 4, or -(MAGNET_E_*) for a form that is refused. */
 #define MAGNET_SPLITK_MAX        8
@@ -691,7 +669,7 @@ MAGNET_API int magnet_conv_mfma_splitk(const MagnetConvExArgs *args, int32_t spl
 
 /* The single-plane fp16 format, plane to plane and WIDE: the plain layers of a D-Net decoder whose activation buffers are ONE
  * zero-bordered channel-last fp16 plane each (DNetMFMA(precision="fp16")).  The struct's fields mean, for this entry point only:
- *   base.in_hi / base.w_hi   fp16 planes (rows, in_ld) / (taps, cout_pad, cin); base.in_lo, w_lo, in_sc, w_sc, add_hi and add_lo must
+ *   base.in_hi / base.w_hi   fp16 planes (rows, in_ld) / (taps, cout_pad, cin); base.in_lo, w_lo, add_hi and add_lo must
  *                            be NULL (planes of another format are refused, not mis-read; there is no residual input)
  *   act                      MAGNET_ACT_BASE (base.relu 0 or 1) or MAGNET_ACT_LEAKY_RELU(act_slope), as in magnet_conv_mfma_ex
  *   base.out_mode            3: one fp16 plane at out_hi (saturating round-to-nearest-even, NaN written through: see MagnetConvArgs);
@@ -700,7 +678,7 @@ MAGNET_API int magnet_conv_mfma_splitk(const MagnetConvExArgs *args, int32_t spl
  *   border_hp / border_pad / repad / in_ld / out_ld   as in magnet_conv_mfma
  * Serves taps 1 and 9 without dilation, cout_pad a multiple of 128 (128-row x 128-channel tiles, one grid column per 128 channels), cin
  * a multiple of 32, tiling 0 or MAGNET_TILING_FLAT; tiles_out works.  A fused tail, an addend, a residual input, the Gaussian update /
- * upsampling, the e4m3 format, dilation, any other cout_pad and MAGNET_TILING_BM64 / MAGNET_TILING_BM256 are refused with MAGNET_E_DIM;
+ * upsampling, dilation, any other cout_pad and MAGNET_TILING_BM64 / MAGNET_TILING_BM256 are refused with MAGNET_E_DIM;
  * a refused call writes nothing.  Each fp16 x fp16 product is exact in the fp32 accumulator; bias and activation are fp32 arithmetic
  * as in magnet_conv_mfma.  Domain: |activation|, |weight| <= 65504 (stores clamp; the caller rounds its weights). */
 MAGNET_API int magnet_conv_mfma_f16d(const MagnetConvExArgs *args, void *stream);

@@ -17,29 +17,6 @@ from . import lib
 from .planes import PackCache, pack_taps, pack_taps_f16, planes, round_up, split_bf16, timed
 
 
-def mx_quant(v: torch.Tensor):
-    """Block-scaled OCP e4m3 (MX-fp8) of v (..., nblk, 32) fp32: one E8M0 exponent per block with max |v| / 2^e in [128, 256) (<= 448), e = -127
-    for an all-zero block.  Returns (bytes uint8 (..., nblk, 32), e + 127 int32 (..., nblk)).  The rule of magnet_pack_mx (pack.hip)."""
-    m = v.abs().amax(-1)
-    _, ex = torch.frexp(m)
-    e = (ex.to(torch.int32) - 8).clamp(min=-127)
-    e = torch.where(m > 0, e, torch.full_like(e, -127))
-    q = (v * torch.exp2(-e.float()).unsqueeze(-1)).to(torch.float8_e4m3fn)
-    return q.view(torch.uint8), e + 127
-
-
-def split_mx(x: torch.Tensor):
-    """x (..., K) fp32, K % 32 == 0 -> the fp16 + e4m3 operand format of magnet_conv_mfma v302: (hi (..., K) fp16, qr (..., K) int16 container of
-    the [32 hi bytes | 32 lo bytes] per 32-element block, sc (..., K / 32) int32 = E8M0(hi) | E8M0(lo) << 8)."""
-    hi = x.to(torch.float16)
-    lo = x - hi.float()
-    shp = x.shape[:-1] + (x.shape[-1] // 32, 32)
-    q, eq = mx_quant(hi.float().reshape(shp))
-    r, er = mx_quant(lo.reshape(shp))
-    qr = torch.cat([q, r], dim=-1).contiguous().view(torch.int16).reshape(x.shape)
-    return hi.contiguous(), qr, (eq | (er << 8)).to(torch.int32).contiguous()
-
-
 def _cout_pad(c):
     if c <= 16:
         return 16
@@ -120,14 +97,19 @@ class ConvStackMFMA:
         st = self.small_tiles
         if pk["taps"] != 9 or not (self.record_tiles or self.tile_256 or st is True or (st == "auto" and SMALL_TILE_LIMIT > 0)):
             return None, None
-        geom = (int(gauss[0].shape[0]), int(gauss[0].shape[2])) if gauss is not None else \
-            (int(upsample[0].shape[1]), int(upsample[0].shape[3])) if upsample is not None else None
+        geom = self._geom(gauss, upsample)
         if st is not False and pk["cout_pad"] % 128 == 0 and \
                 (st is True or (use_small_tiles(*geom, wp) if geom is not None else use_small_tiles(1, rows // wp - 2, wp, False))):
             return lib.TILING_BM64, geom
         if self.tile_256 and (gauss is not None or upsample is not None):
             return lib.TILING_BM256, geom
         return (0 if self.record_tiles else None), geom
+
+    @staticmethod
+    def _geom(gauss, upsample):
+        """(n_img, h) of a launch that carries its image geometry (gauss / upsample), else None."""
+        return (int(gauss[0].shape[0]), int(gauss[0].shape[2])) if gauss is not None else \
+            (int(upsample[0].shape[1]), int(upsample[0].shape[3])) if upsample is not None else None
 
     @staticmethod
     def _reported(n, tiling, rows, wp, geom):
@@ -150,13 +132,9 @@ class ConvStackMFMA:
             self.layers.append((conv, relu))
             i += 2 if relu else 1
         self.in_map = in_map
-        # Fused 1x1-chain kernel (magnet_conv1x1_chain): bit-identical results, but MEASURED SLOWER on MI355X
-        # (1.41 + 1.04 ms vs 0.94 + 0.79 ms per 64-frame step for the two stacks): its 101 KB LDS tile allows one
-        # workgroup per CU, so its load phase is not overlapped, whereas the separate launches are HBM-bound at
-        # high occupancy.  Off by default; kept (and tested) as the starting point for a 64-row-tile variant.
-        self.fuse_tail = False
-        # The same three 1x1 layers fused into the EPILOGUE of the stack's first (3x3) layer: the 128 x 128 tile is already
+        # The stack's three 1x1 layers fused into the EPILOGUE of its first (3x3) layer: the 128 x 128 tile is already
         # on the CU, weights come straight from L2, LDS need stays at the K ring's 64 KB (2 workgroups per CU).
+        # False: one launch per layer.
         self.fuse_epilogue = True
         self._chain = None
         self._cache = PackCache(lambda: [p for conv, _ in self.layers for p in conv.parameters()])
@@ -208,7 +186,7 @@ class ConvStackMFMA:
             cin_p = cp                                                                 # next layer reads all padded channels
             if li + 1 < len(self.layers) and cp % 32 != 0:
                 raise lib.MagnetError("hidden layer width must be a multiple of 32")
-        # the reference's stacks end in 1x1(128->128)+ReLU, 1x1(128->128)+ReLU, 1x1(128->cout): fused into one launch
+        # the reference's stacks end in 1x1(128->128)+ReLU, 1x1(128->128)+ReLU, 1x1(128->cout): the fused tail's weights
         self._chain = None
         if len(out) == 4 and all(o["taps"] == 1 for o in out[1:]) and out[1]["relu"] and out[2]["relu"] and \
                 not out[3]["relu"] and out[0]["cout_pad"] == 128 and out[1]["cout_pad"] == 128 and \
@@ -218,39 +196,6 @@ class ConvStackMFMA:
                 w_lo=torch.cat([o["w_lo"].reshape(-1) for o in out[1:]]).contiguous(),
                 bias=torch.cat([o["bias"] for o in out[1:]]).contiguous(), cout_pad=out[3]["cout_pad"])
         return out
-
-    def _run_f16(self, in_hi, in_lo, in_ld, rows, wp, first_addend, n_var, inv_off, upsample, gauss, mx, work):
-        """run(f16=True): one launch of magnet_conv_mfma_f16 with the stack's fused tail."""
-        dev = in_hi.device
-        self._check_f16(in_hi, in_lo)
-        packs = self.packed(dev)
-        if mx is not None or self._chain is None or not self.fuse_epilogue or self._chain["cout_pad"] not in (16, 144):
-            raise lib.MagnetError("ConvStackMFMA.run(f16=True): needs the fused-epilogue stack of G-Net or the mask head, and no mx")
-        pk, ch = packs[0], self._chain
-        w16 = self.packed_f16(dev)
-        if first_addend is not None:
-            pk, w16 = self.packed_first_split(dev, n_var, inv_off)[0], self.packed_f16(dev, n_var, inv_off)[0]
-        out = None if (upsample is not None or gauss is not None) else \
-            _buf(work, ("out", rows, ch["cout_pad"]), lambda: torch.empty((rows, ch["cout_pad"]), dtype=torch.float32, device=dev))
-        geom = (int(gauss[0].shape[0]), int(gauss[0].shape[2])) if gauss is not None else \
-            (int(upsample[0].shape[1]), int(upsample[0].shape[3])) if upsample is not None else None
-        with timed(ConvStackMFMA.event_sink, 2.0 * rows * pk["cout_pad"] * pk["cin"] * pk["taps"] + 2.0 * rows * 128 * (256 + ch["cout_pad"]), pk["taps"]):
-            n = lib.conv_mfma(in_hi, None, in_ld, pk["cin"], w16, None, pk["bias"], pk["taps"], wp, pk["relu"], rows, out_f32=out,
-                              tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss, addend=first_addend,
-                              f16=True)
-        self.last_tiles = self._reported(n, False, rows, wp, geom) if self.record_tiles else ()
-        return out, ch["cout_pad"]
-
-    def packed_mx(self, device):
-        """First layer's weights in the fp16 + e4m3 operand format (conv_mfma.hip, WIN == 4 loop): (w_f16 (taps, cout_pad, cin), w_qr
-        (taps, cout_pad, cin) int16 container, w_sc (taps, cin / 32, cout_pad) int32)."""
-        @torch.no_grad()
-        def build():
-            pk = self.packed(device)[0]
-            w = (pk["w_hi"].float() + pk["w_lo"].float())                   # the 16-bit-mantissa weights the bf16x3 path multiplies by
-            hi, qr, sc = split_mx(w)
-            return dict(w_hi=hi, w_lo=qr, w_sc=sc.permute(0, 2, 1).contiguous())
-        return self._cache.get(device, build, "mx")
 
     def packed_f16(self, device, n_var=None, inv_off=None):
         """First layer's weights as ONE fp16 plane (taps, cout_pad, cin), rounded once from the fp32 parameter (planes.pack_taps_f16):
@@ -315,15 +260,13 @@ class ConvStackMFMA:
         if in_lo is not None or in_hi.dtype != torch.float16:
             raise lib.MagnetError("ConvStackMFMA: f16=True takes one fp16 plane (in_hi) and in_lo=None")
 
-    def run(self, in_hi, in_lo, in_ld, rows, wp, work, first_addend=None, n_var=None, inv_off=None, upsample=None, gauss=None, mx=None,
-            f16=False, src_nchw=None):
+    def run(self, in_hi, in_lo, in_ld, rows, wp, work, first_addend=None, n_var=None, inv_off=None, upsample=None, gauss=None, f16=False,
+            src_nchw=None):
         """in_hi/in_lo: bf16 views whose data_ptr is row 0, channel 0 of this stack's input; `work`: dict for cached
         hidden buffers.  Returns (fp32 tensor (rows, cout_pad_last), cout_pad_last).
         upsample = (depths (n,B,2,h,w), outs (n,B,2,4h,4w)): the mask head's stack only (144 outputs, fused tail) — the learned
         convex upsampling runs in the tail's last layer and only `outs` is written (returns (None, 144)); see can_fuse_upsample().
         gauss = (gmm_in, gmm_out): G-Net's stack only — the Gaussian update runs behind the head (returns (None, 16)); can_fuse_gauss().
-        mx = (in_sc, sc_rows): the input planes are in the fp16 + e4m3 operand format (in_hi fp16, in_lo the e4m3 container, in_sc the
-        E8M0 plane of lib.pack_mx); fused-epilogue stacks with at least 65 536 rows only.
         f16 = True: the 3x3 layer on the single-plane fp16 format (lib.conv_mfma(f16=True)): in_hi is an fp16 plane, in_lo None; the
         fused 1x1 tail stays bf16x3.  Fused-epilogue stacks only; with small_tiles=True a MagnetError (no 64-row form).
         src_nchw = (x (B, C, h, w) fp32, c0): the first layer's input channels [c0, c0 + C) are read in place from x
@@ -332,18 +275,21 @@ class ConvStackMFMA:
         dev = in_hi.device if in_hi is not None else src_nchw[0].device
         if src_nchw is not None:
             self.packed(dev)
-            if f16 or mx is not None or first_addend is not None or (gauss is None and upsample is None) or self._chain is None or \
+            if f16 or first_addend is not None or (gauss is None and upsample is None) or self._chain is None or \
                     not self.fuse_epilogue:
                 raise lib.MagnetError("ConvStackMFMA.run (src_nchw): the bf16x3 fused-epilogue launch with gauss or upsample only")
-        if f16:
-            return self._run_f16(in_hi, in_lo, in_ld, rows, wp, first_addend, n_var, inv_off, upsample, gauss, mx, work)
         packs = self.packed(dev)
+        if f16:
+            self._check_f16(in_hi, in_lo)
+            if self._chain is None or not self.fuse_epilogue or self._chain["cout_pad"] not in (16, 144):
+                raise lib.MagnetError("ConvStackMFMA.run(f16=True): needs the fused-epilogue stack of G-Net or the mask head")
         if first_addend is not None:
             # first layer over the per-iteration channels only; the invariant part arrives as `first_addend`
             packs = [self.packed_first_split(dev, n_var, inv_off)[0]] + list(packs[1:])
         sink = ConvStackMFMA.event_sink
-        # the stack's first layer (its one 3x3 launch) takes its tile form from small_tiles; tiling None is the plain entry point
-        tiling, geom = (None, None) if mx is not None else self._tiling(packs[0], rows, wp, gauss, upsample)
+        # the stack's first layer (its one 3x3 launch) takes its tile form from small_tiles; tiling None is the plain entry point.
+        # The fp16 entry point takes no tiling and always reports its tile count: recorded under record_tiles
+        tiling, geom = (None, self._geom(gauss, upsample)) if f16 else self._tiling(packs[0], rows, wp, gauss, upsample)
         self.last_tiles = ()
 
         def out_f32(c):
@@ -355,29 +301,16 @@ class ConvStackMFMA:
         if self._chain is not None and self.fuse_epilogue:
             pk, ch = packs[0], self._chain
             out = None if (upsample is not None or gauss is not None) else out_f32(ch["cout_pad"])
-            w_hi, w_lo, form = pk["w_hi"], pk["w_lo"], dict(addend=first_addend)
-            if mx is not None:
-                if first_addend is not None:
-                    raise lib.MagnetError("ConvStackMFMA.run: the fp16 + e4m3 format has no addend form")
-                wm = self.packed_mx(dev)
-                w_hi, w_lo, form = wm["w_hi"], wm["w_lo"], dict(mx=(mx[0], wm["w_sc"], mx[1]))
+            w_hi, w_lo = pk["w_hi"], pk["w_lo"]
+            if f16:                                       # one fp16 weight plane; the fused 1x1 tail stays bf16x3
+                w_hi, w_lo = (self.packed_f16(dev) if first_addend is None else self.packed_f16(dev, n_var, inv_off)[0]), None
             with timed(sink, flops(pk) + 2.0 * rows * 128 * (256 + ch["cout_pad"]), pk["taps"]):
                 n = lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], w_hi, w_lo, pk["bias"], pk["taps"], wp, pk["relu"], rows, out_f32=out,
                                   tail=(ch["w_hi"], ch["w_lo"], ch["bias"], ch["cout_pad"]), upsample=upsample, gauss=gauss, tiling=tiling,
-                                  src_nchw=src_nchw, **form)
+                                  src_nchw=src_nchw, addend=first_addend, f16=bool(f16))
             # (the src_nchw entry point always reports its tile count; it is recorded where the plain launch's would be)
-            self.last_tiles = () if n is None or tiling is None else self._reported(n, tiling, rows, wp, geom)
-            return out, ch["cout_pad"]
-        if self._chain is not None and self.fuse_tail and first_addend is None:
-            pk, ch = packs[0], self._chain
-            oh, ol = _buf(work, ("hid", 0, rows, 128), lambda: planes(rows, 128, dev))
-            with timed(sink, flops(pk), pk["taps"]):
-                n = lib.conv_mfma(in_hi, in_lo, in_ld, pk["cin"], pk["w_hi"], pk["w_lo"], pk["bias"], pk["taps"], wp,
-                                  pk["relu"], rows, out_hi=oh, out_lo=ol, tiling=tiling)
-            self.last_tiles = () if n is None else self._reported(n, tiling, rows, wp, geom)
-            out = out_f32(ch["cout_pad"])
-            with timed(sink, 2.0 * rows * 128 * (256 + ch["cout_pad"]), 1):
-                lib.conv1x1_chain(oh, ol, ch["w_hi"], ch["w_lo"], ch["bias"], out, rows, ch["cout_pad"])
+            recorded = self.record_tiles if f16 else tiling is not None
+            self.last_tiles = self._reported(n, tiling, rows, wp, geom) if n is not None and recorded else ()
             return out, ch["cout_pad"]
         cur_hi, cur_lo, cur_ld = in_hi, in_lo, in_ld
         for li, pk in enumerate(packs[:-1]):

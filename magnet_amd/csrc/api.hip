@@ -385,13 +385,6 @@ static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, flo
     p.repad = a->repad;
     p.tail_w_hi = (const uint16_t*)a->tail_w_hi; p.tail_w_lo = (const uint16_t*)a->tail_w_lo; p.tail_bias = a->tail_bias;
     p.tail_cout = a->tail_cout_pad;
-    if (a->in_sc || a->w_sc) {                                       // v302: fp16 + block-scaled e4m3 operand format
-        if (!a->in_sc || !a->w_sc) return fail(MAGNET_E_NULL, "magnet_conv_mfma: in_sc and w_sc come together");
-        if (!tail || a->taps != 9 || a->dil > 1 || a->addend || a->rows < 256ll * 256 || a->sc_rows < a->rows || ((uintptr_t)a->in_sc & 3) || ((uintptr_t)a->w_sc & 3) ||
-            ((int64_t)(a->cin / 32) * a->sc_rows * 4 >= ((int64_t)1 << 31)))
-            return fail(MAGNET_E_SHAPE, "magnet_conv_mfma: the fp16 + e4m3 operand format serves the 3x3 layers with a fused tail, rows >= 65536, no addend");
-        p.in_sc = (const uint32_t*)a->in_sc; p.w_sc = (const uint32_t*)a->w_sc; p.sc_rows = a->sc_rows;
-    }
     if (a->up_out || a->up_depth) {                                  // fused convex upsampling in the tail's last layer
         if (!a->up_out || !a->up_depth) return fail(MAGNET_E_NULL, "magnet_conv_mfma: up_depth and up_out come together");
         if (!tail || a->tail_cout_pad != 144) return fail(MAGNET_E_DIM, "magnet_conv_mfma: the fused upsampling needs the 144-channel fused tail");
@@ -447,24 +440,24 @@ static int conv_act_check(const MagnetConvExArgs* a, const char* who, bool exclu
     return 0;
 }
 
-// The single-plane fp16 routes: planes of another format (bf16x3 lo planes, fp16 + e4m3 scales) are refused rather than mis-read.
+// The single-plane fp16 routes: planes of another format (bf16x3 lo planes) are refused rather than mis-read.
 // res_planes: the residual planes the route takes.  1: ONE fp16 plane at add_hi (add_lo NULL); 0: no residual input (both NULL);
 // 2: add_hi / add_lo are not this check's matter (magnet_conv_mfma_f16 refuses them with its border and repad forms)
 static int conv_f16_planes_check(const MagnetConvArgs& b, const char* who, int res_planes) {
-    if (b.in_lo || b.w_lo || b.in_sc || b.w_sc || (res_planes < 2 && b.add_lo) || (res_planes < 1 && b.add_hi))
-        return fail(MAGNET_E_DIM, "%s: in_lo, w_lo, in_sc%s must be NULL (every operand is ONE fp16 plane)", who,
-                    res_planes == 0 ? ", w_sc, add_hi and add_lo" : res_planes == 1 ? ", w_sc and add_lo" : " and w_sc");
+    if (b.in_lo || b.w_lo || (res_planes < 2 && b.add_lo) || (res_planes < 1 && b.add_hi))
+        return fail(MAGNET_E_DIM, "%s: in_lo%s must be NULL (every operand is ONE fp16 plane)", who,
+                    res_planes == 0 ? ", w_lo, add_hi and add_lo" : res_planes == 1 ? ", w_lo and add_lo" : " and w_lo");
     return 0;
 }
 
-// The plain layer on 128-row tiles only: no fused tail, addend, Gaussian update or upsampling; excludes_planes: no residual input or e4m3 format either
+// The plain layer on 128-row tiles only: no fused tail, addend, Gaussian update or upsampling; excludes_planes: no residual input either
 static int conv_plain_check(const MagnetConvExArgs* a, const char* who, const char* format, bool excludes_planes) {
     const MagnetConvArgs& b = a->base;
     if (a->tiling & ~MAGNET_TILING_FLAT) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_FLAT: 128-row tiles only)", who, a->tiling);
     if (b.tail_w_hi || b.tail_w_lo || b.addend || b.up_out || b.up_depth || b.gu_in || b.gu_out ||
-        (excludes_planes && (b.add_hi || b.add_lo || b.in_sc || b.w_sc)))
+        (excludes_planes && (b.add_hi || b.add_lo)))
         return fail(MAGNET_E_DIM, "%s: the plain %s layer only (no fused tail, addend, %sGaussian update or upsampling)", who, format,
-                    excludes_planes ? "residual input, e4m3 format, " : "");
+                    excludes_planes ? "residual input, " : "");
     return 0;
 }
 
@@ -477,7 +470,7 @@ MAGNET_API int magnet_conv_mfma_ex(const MagnetConvExArgs* a, void* stream) {
     if (a->tiling & MAGNET_TILING_BM64) {                            // the 64-row instances: 3x3, 128-wide, bf16x3 operands
         const MagnetConvArgs& b = a->base;
         if (a->tiling & MAGNET_TILING_BM256) return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: MAGNET_TILING_BM64 and MAGNET_TILING_BM256 exclude each other");
-        if (b.taps != 9 || b.in_sc || b.w_sc || (b.tail_w_hi ? b.cout_pad != 128 : (b.cout_pad <= 0 || b.cout_pad % 128 != 0)))
+        if (b.taps != 9 || (b.tail_w_hi ? b.cout_pad != 128 : (b.cout_pad <= 0 || b.cout_pad % 128 != 0)))
             return fail(MAGNET_E_DIM, "magnet_conv_mfma_ex: MAGNET_TILING_BM64 serves 3x3 launches (taps == 9) with cout_pad == 128 and a fused tail, or plain "
                                       "with cout_pad %% 128 == 0, bf16x3 operands only (taps=%d cout_pad=%d)", b.taps, b.cout_pad);
     }
@@ -493,8 +486,8 @@ MAGNET_API int magnet_conv_mfma_nchw(const MagnetConvNchwArgs* a, void* stream) 
     if (!a->src) return fail(MAGNET_E_NULL, "%s: src is NULL", who);
     if (x.act != MAGNET_ACT_BASE) return fail(MAGNET_E_DIM, "%s: act=%d (MAGNET_ACT_BASE only)", who, x.act);
     if (x.tiling & ~MAGNET_TILING_BM256) return fail(MAGNET_E_DIM, "%s: tiling=%d (0 or MAGNET_TILING_BM256: per-image 256-row tiles only)", who, x.tiling);
-    if (b.taps != 9 || b.dil > 1 || b.cout_pad != 128 || b.in_sc || b.w_sc || b.addend || b.add_hi || b.add_lo || b.border_hp || b.repad)
-        return fail(MAGNET_E_DIM, "%s: bf16x3 3x3 layers (taps == 9, no dilation) with cout_pad == 128; no addend, residual, border, repad or e4m3 format", who);
+    if (b.taps != 9 || b.dil > 1 || b.cout_pad != 128 || b.addend || b.add_hi || b.add_lo || b.border_hp || b.repad)
+        return fail(MAGNET_E_DIM, "%s: bf16x3 3x3 layers (taps == 9, no dilation) with cout_pad == 128; no addend, residual, border or repad", who);
     if (!b.tail_w_hi || !((b.tail_cout_pad == 16 && b.gu_in && b.gu_out && !b.up_out && !b.up_depth) ||
                           (b.tail_cout_pad == 144 && b.up_depth && b.up_out && !b.gu_in && !b.gu_out)))
         return fail(MAGNET_E_DIM, "%s: the fused tail of 16 outputs with gu_in / gu_out, or of 144 outputs with up_depth / up_out", who);
@@ -606,39 +599,32 @@ MAGNET_API int magnet_conv_mfma_f16d_splitk(const MagnetConvExArgs* a, int32_t s
     return conv_splitk_run(a, true, split_k, work, work_bytes, stream);
 }
 
-// What magnet_pack_split, magnet_pack_f16 and magnet_pack_mx check alike, in their common order: NULL pointers, the dimensions
-// with the c_off / ctot granule (8 channels, the 16-byte vector; 32 for mx, its block), then 16-byte alignment.  `out` holds the
-// entry point's n_out outputs.  Where they differ, and stay different because each refusal is part of its entry point's contract:
+// What magnet_pack_split and magnet_pack_f16 check alike, in their common order: NULL pointers, the dimensions with the c_off / ctot
+// granule (8 channels, the 16-byte vector), then 16-byte alignment.  `out` holds the entry point's n_out outputs.  Where they differ,
+// and stay different because each refusal is part of its entry point's contract:
 //   split  takes any in_img_stride and any row count;
-//   f16    refuses in_img_stride < 0 and N (h+2) (w+2) >= 2^31 as bad dims;
-//   mx     has no round-up lanes (C itself a multiple of 32) and no narrow kernel (h*w a multiple of 4), and says so in its
-//          message; checks sc_rows after the dimensions; counts the source and its image stride in the alignment, not out_sc.
-// The alignment messages name "outputs", "output" and "pointers" accordingly.  *stride receives the image stride in floats.
-enum PackKind { PACK_SPLIT, PACK_F16, PACK_MX };
-static int pack_check(PackKind kind, const char* who, const float* nchw, void* const* out, int n_out, int32_t N, int32_t C, int32_t h,
-                      int32_t w, int32_t ctot, int32_t c_off, int64_t in_img_stride, int64_t sc_rows, long long* stride) {
-    const bool mx = kind == PACK_MX;
-    const int g = mx ? 32 : 8;
+//   f16    refuses in_img_stride < 0 and N (h+2) (w+2) >= 2^31 as bad dims.
+// The alignment messages name "outputs" and "output" accordingly.  *stride receives the image stride in floats.
+static int pack_check(bool f16, const char* who, const float* nchw, void* const* out, int n_out, int32_t N, int32_t C, int32_t h,
+                      int32_t w, int32_t ctot, int32_t c_off, int64_t in_img_stride, long long* stride) {
+    const int g = 8;
     bool null = !nchw;
     for (int i = 0; i < n_out; ++i) null = null || !out[i];
     if (null) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
-    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || (ctot % g) != 0 || (c_off % g) != 0 || c_off < 0 || (mx && (C % g) != 0) ||
-        c_off + ((C + g - 1) / g) * g > ctot || (mx && ((h * w) % 4) != 0) ||
-        (kind == PACK_F16 && (in_img_stride < 0 || (int64_t)N * (h + 2) * (w + 2) >= ((int64_t)1 << 31))))
-        return fail(MAGNET_E_DIM, "%s: bad dims N=%d C=%d h=%d w=%d ctot=%d c_off=%d%s", who, N, C, h, w, ctot, c_off,
-                    mx ? " (C, c_off, ctot multiples of 32; h*w of 4)" : "");
-    if (mx && sc_rows < (int64_t)N * (h + 2) * (w + 2)) return fail(MAGNET_E_DIM, "%s: sc_rows smaller than N*(h+2)*(w+2)", who);
+    if (N <= 0 || C <= 0 || h <= 0 || w <= 0 || (ctot % g) != 0 || (c_off % g) != 0 || c_off < 0 || c_off + ((C + g - 1) / g) * g > ctot ||
+        (f16 && (in_img_stride < 0 || (int64_t)N * (h + 2) * (w + 2) >= ((int64_t)1 << 31))))
+        return fail(MAGNET_E_DIM, "%s: bad dims N=%d C=%d h=%d w=%d ctot=%d c_off=%d", who, N, C, h, w, ctot, c_off);
     *stride = in_img_stride ? (long long)in_img_stride : (long long)C * h * w;
-    bool misaligned = mx && (!aligned16(nchw) || (*stride % 4) != 0);
-    for (int i = 0; i < n_out && i < 2; ++i) misaligned = misaligned || !aligned16(out[i]);
-    if (misaligned) return fail(MAGNET_E_ALIGN, "%s: %s not 16-byte aligned", who, mx ? "pointers" : n_out == 2 ? "outputs" : "output");
+    bool misaligned = false;
+    for (int i = 0; i < n_out; ++i) misaligned = misaligned || !aligned16(out[i]);
+    if (misaligned) return fail(MAGNET_E_ALIGN, "%s: %s not 16-byte aligned", who, n_out == 2 ? "outputs" : "output");
     return 0;
 }
 
 MAGNET_API int magnet_pack_f16(const float* nchw, void* out_f16, int32_t N, int32_t C, int32_t h, int32_t w, int32_t ctot, int32_t c_off,
                                int64_t in_img_stride, void* stream) {
     long long stride;
-    if (const int rc = pack_check(PACK_F16, "magnet_pack_f16", nchw, &out_f16, 1, N, C, h, w, ctot, c_off, in_img_stride, 0, &stride)) return rc;
+    if (const int rc = pack_check(true, "magnet_pack_f16", nchw, &out_f16, 1, N, C, h, w, ctot, c_off, in_img_stride, &stride)) return rc;
     hipError_t e = magnet::launch_pack_f16(nchw, (uint16_t*)out_f16, N, C, h, w, ctot, c_off, stride, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_pack_f16 launch");
 }
@@ -768,37 +754,13 @@ MAGNET_API int magnet_upsample_bilinear_cl_f16(const float* in, int32_t in_ld, i
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_upsample_bilinear_cl_f16 launch");
 }
 
-MAGNET_API int magnet_conv1x1_chain(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias,
-                                    float* out, int64_t rows, int32_t cout_pad, void* stream) {
-    if (!in_hi || !in_lo || !w_hi || !w_lo || !bias || !out) return fail(MAGNET_E_NULL, "magnet_conv1x1_chain: NULL pointer");
-    if (rows <= 0 || (cout_pad != 16 && cout_pad != 144 && cout_pad != 128))
-        return fail(MAGNET_E_DIM, "magnet_conv1x1_chain: rows > 0 and cout_pad in {16, 128, 144} required (got %d)", cout_pad);
-    if (!aligned16(in_hi) || !aligned16(in_lo) || !aligned16(w_hi) || !aligned16(w_lo) || !aligned16(out) || !aligned16(bias))
-        return fail(MAGNET_E_ALIGN, "magnet_conv1x1_chain: pointers must be 16-byte aligned");
-    magnet::ChainParams p;
-    p.in_hi = (const uint16_t*)in_hi; p.in_lo = (const uint16_t*)in_lo; p.w_hi = (const uint16_t*)w_hi; p.w_lo = (const uint16_t*)w_lo;
-    p.bias = bias; p.out = out; p.rows = rows; p.cout_pad = cout_pad;
-    hipError_t e = magnet::launch_conv1x1_chain(p, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "magnet_conv1x1_chain launch");
-}
-
 MAGNET_API int magnet_pack_split(const float* nchw, void* out_hi, void* out_lo, int32_t N, int32_t C, int32_t h, int32_t w,
                                  int32_t ctot, int32_t c_off, int64_t in_img_stride, void* stream) {
     void* const out[2] = {out_hi, out_lo};
     long long stride;
-    if (const int rc = pack_check(PACK_SPLIT, "magnet_pack_split", nchw, out, 2, N, C, h, w, ctot, c_off, in_img_stride, 0, &stride)) return rc;
+    if (const int rc = pack_check(false, "magnet_pack_split", nchw, out, 2, N, C, h, w, ctot, c_off, in_img_stride, &stride)) return rc;
     hipError_t e = magnet::launch_pack_split(nchw, (uint16_t*)out_hi, (uint16_t*)out_lo, N, C, h, w, ctot, c_off, stride, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_pack_split launch");
-}
-
-MAGNET_API int magnet_pack_mx(const float* nchw, void* out_f16, void* out_qr, void* out_sc, int32_t N, int32_t C, int32_t h, int32_t w,
-                              int32_t ctot, int32_t c_off, int64_t sc_rows, int64_t in_img_stride, void* stream) {
-    void* const out[3] = {out_f16, out_qr, out_sc};
-    long long stride;
-    if (const int rc = pack_check(PACK_MX, "magnet_pack_mx", nchw, out, 3, N, C, h, w, ctot, c_off, in_img_stride, sc_rows, &stride)) return rc;
-    hipError_t e = magnet::launch_pack_mx(nchw, (uint16_t*)out_f16, (uint8_t*)out_qr, (uint32_t*)out_sc, N, C, h, w, ctot, c_off, sc_rows, stride,
-                                          (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "magnet_pack_mx launch");
 }
 
 MAGNET_API int magnet_gaussian_update_cl(const float* gnet_out_pad, int32_t ld, const float* gmm_in, float* gmm_out,

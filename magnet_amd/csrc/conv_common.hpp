@@ -41,11 +41,6 @@ struct ConvParams {
     // position update (mu, sigma) in place of the (rows, 16) fp32 write: gu_in (up_B, 2, up_h, up_w) -> gu_out, same layout
     const float* gu_in; float* gu_out;
     int variant;                                      // host side only (launch_conv_mfma): 0; the dev library sets it from MAGNET_CONV_VARIANT
-    // round 4, "2-unit" operand format of the 128-wide 3x3 layers (in_sc != nullptr): in_hi / w_hi = fp16 planes, in_lo / w_lo = per
-    // 64-byte (row, 32-channel chunk) slice the 32 e4m3 bytes of hi then the 32 e4m3 bytes of lo = x - fp16(x), each block scaled by
-    // its E8M0 exponent: in_sc [cin / 32][sc_rows] u32 {E8M0 of the hi block, E8M0 of the lo block, 0, 0}, w_sc [taps][cin / 32][cout_pad] u32
-    const uint32_t* in_sc; const uint32_t* w_sc;
-    long long sc_rows;                                // rows of one chunk plane of in_sc (>= rows)
     // LeakyReLU (magnet_conv_mfma_ex; the D-Net decoder, D_dense_depth.py:29-43): leaky == 1 and relu == 0 -> negative outputs are
     // multiplied by leaky_slope after bias / addend.  Plain epilogue only (not with the fused tail)
     // leaky == 2: SiLU (MAGNET_ACT_SILU, magnet_conv_mfma_ex only; the EfficientNet encoder's expand layers): x * sigmoid(x) in the same
@@ -97,16 +92,7 @@ __device__ __forceinline__ void f16x8_unpack(const uint4 u, float* v) {
 __device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(-x * 1.44269504088896341f)); }
 __device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + __builtin_amdgcn_exp2f(-x * 1.44269504088896341f)); }
 
-struct ChainParams {
-    const uint16_t* in_hi;  const uint16_t* in_lo;    // (rows, 128)
-    const uint16_t* w_hi;   const uint16_t* w_lo;     // [128][128], [128][128], [cout_pad][128] concatenated
-    const float*    bias;                             // 128 + 128 + cout_pad
-    float*          out;                              // (rows, cout_pad) fp32
-    long long rows;
-    int cout_pad;
-};
-
-// The route of a convolution launch: the operand format and what it serves.  CONV_BF16X3: (hi, lo) planes (or the fp16 + e4m3 format):
+// The route of a convolution launch: the operand format and what it serves.  CONV_BF16X3: (hi, lo) planes:
 // magnet_conv_mfma and magnet_conv_mfma_ex.  CONV_F16: the single-plane fp16 operand format (magnet_conv_mfma_f16, which has checked
 // what that format serves): no lo planes.  CONV_F16P: the same operands, plane to plane (magnet_conv_mfma_f16p): the residual is ONE
 // fp16 plane (add_lo NULL) and out_mode 3 (one fp16 plane at out_hi) exists.  CONV_F16D: plane to plane, wide (magnet_conv_mfma_f16d,
@@ -123,6 +109,5 @@ struct ConvSrc { const float* ptr; int c0; };
 // fixed-order reduce + epilogue launch.  hipErrorInvalidValue for a (route, split_k) pair or a form that has no kernel instance
 // nchw != NULL (CONV_BF16X3, split_k = 0 only): the fp32-source form of the 256-row fused-tail launches
 hipError_t launch_conv(const ConvParams&, ConvRoute route, int split_k, float* work, hipStream_t, const ConvSrc* nchw = nullptr);
-hipError_t launch_conv1x1_chain(const ChainParams&, hipStream_t);
 
 }  // namespace magnet

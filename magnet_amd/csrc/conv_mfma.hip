@@ -33,7 +33,6 @@ namespace magnet {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 
 [[maybe_unused]] constexpr int CV_BK = 32;
 constexpr int CV_ROW = 64;                            // bytes per staged row (32 bf16), unpadded
@@ -286,14 +285,12 @@ template <typename V = bf16x8_t>
 __device__ __forceinline__ V ld_frag(const void* ptr) { return __builtin_bit_cast(V, *reinterpret_cast<const uint4*>(ptr)); }
 
 // The step between a LOAD phase and the reads of what it waited for: all but the N newest DMA pieces of this wave have landed and its
-// LDS reads have returned, then the workgroup barrier.  SCHED: nothing may be scheduled across the step in either direction (WIN == 4);
+// LDS reads have returned, then the workgroup barrier.
 // FENCE: a trailing compiler fence, so that no LDS access is hoisted above the barrier (WIN == 2, 4 waves).
-template <int N, bool SCHED = false, bool FENCE = false>
+template <int N, bool FENCE = false>
 __device__ __forceinline__ void wait_barrier() {
-    if constexpr (SCHED) __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
     __builtin_amdgcn_s_barrier();
-    if constexpr (SCHED) __builtin_amdgcn_sched_barrier(0);
     if constexpr (FENCE) asm volatile("" ::: "memory");
 }
 
@@ -312,28 +309,23 @@ struct StepCounter {
 // asks for TOTAL bytes, so the launcher's byte count is the kernel's by construction (a mismatch would be an out-of-bounds LDS-DMA).
 // A window slot is the [hi | lo] planes of AW_ROWS rows (a plain A tile: CV_BM rows); a weight slot the [hi | lo] planes of BN rows.
 //   WIN == 0: 2*SPB stages of [window | weights], interleaved         WIN == 1: 2 window slots, then 2 weight slots
-//   WIN == 2: 1 window slot, then a 3-slot weight ring                 WIN == 4: 2 x {window, scales of its rows [512] u32}, a 4-slot ring
-//   of fp16 weight planes, then 2 x {3 taps x qr weight tile, weight scales [512] u32, 16 zero bytes (block 3 of the weight operand)}
+//   WIN == 2: 1 window slot, then a 3-slot weight ring
 //   F16 (the single-plane fp16 format, WIN == 2 and WIN == 0): the same slots with ONE plane each — no lo plane behind the window or a weight tile
 template <int NF, int WN, int BM, int SPB, int NT, bool PP, int WIN, bool F16 = false>
 struct ConvLds {
-    static_assert(WIN != 4 || PP, "the fp16 + e4m3 format exists on the ping-pong loop only");
     static_assert(!F16 || WIN == 2 || WIN == 0, "the single-plane fp16 format exists on the register-window loops and the windowless 4-wave loop");
     static_assert(!F16 || WIN == 2 || (!PP && NT == 256 && SPB == 1), "windowless fp16: the 4-wave / 2-slot loop");
     static constexpr int BN = NF * 16;
     static constexpr int AW_ROWS = WIN ? BM + 8 : BM;             // window: up to (3-1)*2 extra rows (dilation 2), padded to 8
     static constexpr int A_BYTES = AW_ROWS * CV_ROW, B_BYTES = BN * CV_ROW;       // one plane of a window / of a weight tile
-    static constexpr int SC_BYTES = WIN == 4 ? 512 * 4 : 0;
-    static constexpr int AW_BYTES = (F16 ? 1 : 2) * A_BYTES + SC_BYTES;           // window slot
-    static constexpr int BW_BYTES = (WIN == 4 || F16) ? B_BYTES : 2 * B_BYTES;    // weight slot
-    static constexpr int QB_ZERO = 3 * B_BYTES + SC_BYTES, QB_BYTES = WIN == 4 ? QB_ZERO + 16 : 0;
+    static constexpr int AW_BYTES = (F16 ? 1 : 2) * A_BYTES;                      // window slot
+    static constexpr int BW_BYTES = (F16 ? 1 : 2) * B_BYTES;                      // weight slot
     static constexpr int A_SLOTS = WIN == 2 ? 1 : WIN == 0 ? 2 * SPB : 2;
-    static constexpr int B_SLOTS = WIN == 4 ? 4 : WIN == 2 ? 3 : 2 * SPB;
+    static constexpr int B_SLOTS = WIN == 2 ? 3 : 2 * SPB;
     static constexpr int A_STRIDE = WIN ? AW_BYTES : AW_BYTES + BW_BYTES;         // bytes from a window slot to the next
     static constexpr int B_STRIDE = WIN ? BW_BYTES : AW_BYTES + BW_BYTES;         // bytes from a weight slot to the next
     static constexpr int B_RING = WIN ? A_SLOTS * AW_BYTES : AW_BYTES;            // first weight slot
-    static constexpr int RING_BYTES = A_SLOTS * AW_BYTES + B_SLOTS * BW_BYTES + 2 * QB_BYTES;
-    static constexpr int QB_BASE = RING_BYTES - 2 * QB_BYTES;
+    static constexpr int RING_BYTES = A_SLOTS * AW_BYTES + B_SLOTS * BW_BYTES;
     static constexpr int EPI_BYTES = (NT / 64) * 16 * ((NF / WN) * 16 + 4) * 4;   // the plain epilogue's staging rows (SROW floats per row)
     static constexpr int TOTAL = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
 };
@@ -342,14 +334,14 @@ struct ConvLds {
 // PP = "ping-pong" K loop: NT = 512 threads = 8 waves = two wave groups (waves 0-3 / 4-7: one wave of each group per SIMD) that
 // run the same program half a K step apart — while one group issues its fragment reads and the LDS-DMA of the stage two steps
 // ahead, the other owns the matrix pipe — with counted vmcnt waits and raw s_barriers (no DMA drain at a barrier); it exists with a
-// row window only (WIN = 2, WIN = 4).  The 4-wave / 2-slot loop (PP = false) drains the DMA queue (vmcnt(0)) at every step's
+// row window only (WIN = 2).  The 4-wave / 2-slot loop (PP = false) drains the DMA queue (vmcnt(0)) at every step's
 // __syncthreads and relies on a second workgroup per CU to fill the gap: 41 % of the matrix pipe; see DESIGN.md §4.3.
 // WIN = row-window K loop: the taps of one tap ROW (ty fixed, tx = 0..tap_n-1) read the same activation rows shifted by tap_sx, so
 // their A operand is staged ONCE per (K chunk, ty) as a window of CV_BM + (tap_n-1)*tap_sx rows and the tx sub-steps read their
 // fragments at a row offset; only the weight tile changes per sub-step.  L2 requests per 3x3 tap row: 272 + 3*256 instead of
 // 3*(256 + 256).  WIN = 1: two window slots + two weight slots in LDS, one flat loop over the sub-steps (2x2 taps).
 // WIN = 2 (3x3 layers, default): the window's fragments for all three tx are held in registers, one window slot + a 3-slot weight
-// ring with counted vmcnt waits (prefetch distance 2).  WIN = 4: the fp16 + block-scaled e4m3 operand format (ConvParams::in_sc).
+// ring with counted vmcnt waits (prefetch distance 2).
 // __launch_bounds__(NT, 2): two waves per SIMD is what the LDS budget allows anyway, and with <= 256 registers hipcc selects the
 // VGPR form of the MFMAs — with the default bound it kept the accumulators in AGPRs and moved all 64 of them through VGPRs
 // (64 v_accvgpr_read + 64 v_accvgpr_write) on every trip of the K loop.
@@ -669,7 +661,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         for (int g = 0; g < ngroups; ++g) {
             const bool lastg = g + 1 == ngroups;
             // ---- tx = 0: stage 3g (slot 0) and window g have landed; refill slot 2 with stage 3g + 2 ----
-            wait_barrier<BP, false, true>();
+            wait_barrier<BP, true>();
             dma_b(2);
 #pragma unroll
             for (int tx = 0; tx < 3; ++tx)
@@ -677,192 +669,16 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                 for (int m = 0; m < MF; ++m) ah[tx][m] = ld_frag<f16x8_t>(win_slot(0) + a_offx[tx] + m * 16 * CV_ROW);
             mfma_b(0, ah[0]);
             // ---- tx = 1: every wave holds window g in registers (lgkmcnt(0) before the barrier): fetch window g + 1 ----
-            wait_barrier<BP, false, true>();
+            wait_barrier<BP, true>();
             if (!lastg) { dma_b(0); dma_a(); }
             mfma_b(1, ah[1]);
             // ---- tx = 2 (the window's pieces, issued after the weight pieces, stay in flight; wave 0's extra piece makes its wait
             // the stricter by one piece of stage 3g + 3, never the looser) ----
-            if (!lastg) { wait_barrier<BP + AP, false, true>(); dma_b(1); }
-            else wait_barrier<0, false, true>();
+            if (!lastg) { wait_barrier<BP + AP, true>(); dma_b(1); }
+            else wait_barrier<0, true>();
             mfma_b(2, ah[2]);
         }
         __syncthreads();                                      // nothing in flight; the ring is dead (the epilogue reuses it)
-    } else
-    if constexpr (WIN == 4 && PP) {
-        // ---- round 4: the "2-unit" operand split on the 8-wave ping-pong loop (ConvParams::in_sc != nullptr) ----
-        // x = hi + lo with hi = fp16(x): the main term hi_x * hi_w runs on v_mfma_f32_16x16x32_f16 (1 matrix-pipe unit per 32 K instead of
-        // 3 bf16 ones); the two correction terms lo_x * hi_w + hi_x * lo_w are 2^-12 of the result, so OCP e4m3 operands with one E8M0
-        // scale per (row, 32 channels) suffice: v_mfma_scale_f32_16x16x128_f8f6f4.  That instruction contracts 128 K, but its four
-        // 32-K blocks sit in different lane groups (lane = (row l & 15, group g = l >> 4): bytes 0..15 = K 16 g + t, bytes 16..31 =
-        // K 64 + 16 g + t; tools/ubench/mx_split.hip), i.e. each block can come from its own LDS row: block tx = the 32 channels of tap
-        // (ty, tx), block 3 = zeros.  ONE scaled MFMA per term and accumulator covers the three taps of a tap row, and the K loop keeps
-        // its 32-channel chunks: the "lo" plane of the activation / weight buffers holds, per 64-byte (row, chunk) slice, the 32 e4m3
-        // bytes of hi ("q") and the 32 of lo ("r"), staged by the same DMA pieces as the bf16 lo plane was.
-        // Per group (chunk, ty) and accumulator: 3 f16 MFMAs + 2 scaled MFMAs (~127 matrix-pipe cycles) instead of 9 bf16 ones (~175).
-        // Registers decide the schedule here (64 accumulators + 8-register e4m3 operands): the window is DOUBLE-buffered in LDS, so every
-        // sub-step reads only the fragments it multiplies — tx = 0: f16; tx = 1: f16 + term lo_x * hi_w; tx = 2: f16 + term hi_x * lo_w.
-        static_assert(NT == 512 && SPB == 1 && BN % RP == 0 && CV_BM % RP == 0 && B_PT == 1, "8 waves, whole DMA passes");
-        constexpr int AP = 2 * A_PT;
-        constexpr int QB_ZERO = L::QB_ZERO, QB_BYTES = L::QB_BYTES;
-        unsigned char* const qb_base = smem + L::QB_BASE;
-        const int aw = CV_BM + 2 * p.tap_sx;
-        const int ngroups = 3 * ksteps_per_tap;
-        StepCounter gw, bs, gq;                                             // next window (i = ty) / f16 weight tile (i = tap) / qr weights (i = ty)
-        // buffers of the scales: activations [chunk][rows] u32 {E8M0 of q, E8M0 of r, 0, 0}; weights [tap][chunk][cout_pad] u32
-        const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in_sc + base_row), 0,
-                                                                              (int)(((long long)(p.cin / 32 - 1) * p.sc_rows + (end_row - base_row)) * 4), flags);
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_sc, 0, p.taps * (p.cin / 32) * p.cout_pad * 4, flags);
-        auto dma_a = [&](int buf) {                                       // window of group gw: f16 plane, qr plane, scales
-            unsigned char* sa_hi = win_slot(buf);
-            stage_window(sa_hi, a_step(gw.i, 0, gw.k0), aw);
-            // scales of window rows [0, 512): one dword per lane, wave w rows 64 w .. 64 w + 63 (rows past the window read as 0 or are never used)
-            const int srow = (int)(row0 - base_row) + (gw.i + p.tap_o0) * p.tap_sy + p.tap_o0 * p.tap_sx + wv * 64 + lane;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lptr_t)(sa_hi + 2 * A_BYTES + wv * 256), 4, (srow + (gw.k0 / 32) * (int)p.sc_rows) * 4, 0, 0, 0);
-            gw.advance(3);
-        };
-        auto dma_b = [&](int slot) {                                      // f16 weight tile of the next sub-step (no lo plane: see dma_q)
-            CV_BLDS(rb_hi, wt_slot(slot) + wave_row * CV_ROW, b_v[0] + (bs.i * p.cout_pad * p.cin + bs.k0) * 2);
-            bs.advance(9);
-        };
-        auto dma_q = [&](int buf) {                                       // qr weight tiles of the three taps of group gq + their scales
-            unsigned char* qb = qb_base + buf * QB_BYTES;
-#pragma unroll
-            for (int tx = 0; tx < 3; ++tx) CV_BLDS(rb_lo, qb + tx * B_BYTES + wave_row * CV_ROW, b_v[0] + ((gq.i * 3 + tx) * p.cout_pad * p.cin + gq.k0) * 2);
-            // scales [3][BN]: 3 * BN dwords of the 512-dword field; wave w fetches entries 64 w .. 64 w + 63 (past 3 * BN: out of range -> 0)
-            const int e = wv * 64 + lane, tx = e / BN, col = e - tx * BN;
-            const int so = e < 3 * BN ? (((gq.i * 3 + tx) * (p.cin / 32) + gq.k0 / 32) * p.cout_pad + n0 + col) * 4 : 0x7ffffff0;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lptr_t)(qb + 3 * B_BYTES + wv * 256), 4, so, 0, 0, 0);
-            gq.advance(3);
-        };
-        // fragment addresses.  f16 window / weights: as the bf16 hi plane.  Correction operands: lane (r = lane & 15, g = lane >> 4)
-        // holds 16 bytes of block g >> 1 (tap tx = g >> 1, channels 16 (g & 1) ..) and 16 bytes of block 2 + (g >> 1) (g < 2: tap 2;
-        // g >= 2: block 3 — the weight side reads zeros, the activation side re-reads its first half: finite bytes x 0)
-        const int g4 = lane >> 4, gh = g4 >> 1, gl = g4 & 1;
-        int xq_off[2], xr_off[2];                                         // [half] within the qr window (slots 0, 1 = q; 2, 3 = r)
-        {
-            const int r1 = wm * (MF * 16) + frow + gh * p.tap_sx, r2 = g4 < 2 ? wm * (MF * 16) + frow + 2 * p.tap_sx : r1;
-            xq_off[0] = A_BYTES + cv_swz(r1, gl); xq_off[1] = A_BYTES + cv_swz(r2, gl);
-            xr_off[0] = A_BYTES + cv_swz(r1, 2 + gl); xr_off[1] = A_BYTES + cv_swz(r2, 2 + gl);
-        }
-        const int xs_off = 2 * A_BYTES + (wm * (MF * 16) + frow + (g4 < 3 ? g4 : 2) * p.tap_sx) * 4;   // scale of this lane's block (block 3: a valid one)
-        const int wcol = wn * (NFW * 16) + frow;
-        const int wq_off0 = gh * B_BYTES + cv_swz(wcol, gl), wr_off0 = gh * B_BYTES + cv_swz(wcol, 2 + gl);
-        // second half: lanes g < 2 tap 2; lanes g >= 2 the zero bytes (an address independent of the fragment column: the column stride is folded in)
-        const int wq_off1 = g4 < 2 ? 2 * B_BYTES + cv_swz(wcol, gl) : QB_ZERO, wr_off1 = g4 < 2 ? 2 * B_BYTES + cv_swz(wcol, 2 + gl) : QB_ZERO;
-        const int wn_str = g4 < 2 ? 16 * CV_ROW : 0;
-        const int ws_off = 3 * B_BYTES + ((g4 < 3 ? g4 : 2) * BN + wcol) * 4;
-        f16x8_t ah[MF], fbh[NFW];
-        i32x8_t xr[MF], xq[MF], wq[NFW], wr[NFW];                          // correction operands: e4m3 lo / hi of the window rows, hi / lo of the weights
-        int xsc[MF], wsc[NFW];
-        auto ld8 = [&](const unsigned char* p0, const unsigned char* p1) {
-            const uint4 u0 = *reinterpret_cast<const uint4*>(p0), u1 = *reinterpret_cast<const uint4*>(p1);
-            return i32x8_t{(int)u0.x, (int)u0.y, (int)u0.z, (int)u0.w, (int)u1.x, (int)u1.y, (int)u1.z, (int)u1.w};
-        };
-        auto load_f16 = [&](const unsigned char* win, int slot, int tx) {
-            const unsigned char* sb_hi = wt_slot(slot);
-#pragma unroll
-            for (int m = 0; m < MF; ++m) ah[m] = ld_frag<f16x8_t>(win + a_offx[tx] + m * 16 * CV_ROW);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) fbh[n] = ld_frag<f16x8_t>(sb_hi + b_off + n * 16 * CV_ROW);
-        };
-        // 16 f16 MFMAs (main term of this tap) + the correction MFMAs of fragment columns [a0, a1) of term 1 (hi_w x lo_x) and [b0, b1) of
-        // term 2 (lo_w x hi_x).  Operands swapped as in cv_mma<true> (weights = A): C^T accumulators.  Scale bytes: 0 = hi (q), 1 = lo (r).
-        // The 32 correction MFMAs of a group are spread 8 / 12 / 12 over its three compute phases: a LOAD phase costs ~400 cycles + ~14 per
-        // fragment read whatever the other wave group computes, so the compute phases must be as even as the reads allow.
-        auto mfmas = [&](const int a0, const int a1, const int b0, const int b1) {
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n)
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fbh[n], ah[m], acc[m][n], 0, 0, 0);
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                if (n < a0 || n >= a1) continue;
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wq[n], xr[m], acc[m][n], 0, 0, 0, wsc[n], 1, xsc[m]);
-            }
-#pragma unroll
-            for (int n = 0; n < NFW; ++n) {
-                if (n < b0 || n >= b1) continue;
-#pragma unroll
-                for (int m = 0; m < MF; ++m) acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wr[n], xq[m], acc[m][n], 0, 0, 1, wsc[n], 0, xsc[m]);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            // (an MFMA may not leave its phase: without pinning the accumulators here hipcc sank correction MFMAs behind the barrier into the
-            // next compute phase — operand registers of two phases live at once, spills, unbalanced phases)
-            static_assert(MF == 4 && NFW == 4, "the accumulator pin below lists 16 accumulators");
-            asm volatile("" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[1][2]), "+v"(acc[1][3]),
-                              "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[2][2]), "+v"(acc[2][3]), "+v"(acc[3][0]), "+v"(acc[3][1]), "+v"(acc[3][2]), "+v"(acc[3][3]));
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        auto ld_wq = [&](const unsigned char* qb, const int n) {
-            wq[n] = ld8(qb + wq_off0 + n * 16 * CV_ROW, qb + wq_off1 + n * wn_str);
-            wsc[n] = *reinterpret_cast<const int*>(qb + ws_off + n * 16 * 4);
-        };
-        auto ld_wr = [&](const unsigned char* qb, const int n) { wr[n] = ld8(qb + wr_off0 + n * 16 * CV_ROW, qb + wr_off1 + n * wn_str); };
-        const int grp = __builtin_amdgcn_readfirstlane(wv >> 2);
-        if (tid < 8) reinterpret_cast<uint32_t*>(qb_base + (tid >> 2) * QB_BYTES + QB_ZERO)[tid & 3] = 0u;
-        // Prefetch distances.  The compute phases are short now (tx = 0: 16 MFMAs), so an f16 weight tile is fetched THREE sub-steps
-        // ahead (4-slot ring) and the window / qr weights of group g + 1 at the first sub-step of group g.  Issue order per LOAD phase:
-        // L0: window + qr weights of g + 1, then stage 3g + 3;  L1: stage 3g + 4;  L2: stage 3g + 5.  Needed at the end of L_s: stage
-        // s + 1 (and, at L2, everything of group g + 1) — loads retire in order, so the waits count what may still be outstanding:
-        //   L0: stage 3g+2 | window, qr | stage 3g+3  -> AP + 5 (+ 2 for wave 0) + 2;   L1: the same + stage 3g+4 minus stage 3g+2 (landed);
-        //   L2: stages 3g+4, 3g+5 -> 2.
-        dma_a(0);
-        dma_q(0);
-        dma_b(0);
-        dma_b(1);
-        dma_b(2);
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                  // window 0, qr weights 0 and stage 0 landed (this wave's pieces)
-        __syncthreads();
-        if (grp == 1) __builtin_amdgcn_s_barrier();                       // group 1 runs one barrier (= half a sub-step) behind group 0
-        int bslot = 0;                                                    // ring slot of the sub-step being read
-        for (int g = 0; g < ngroups; ++g) {
-            const bool lastg = g + 1 == ngroups;
-            const unsigned char* win = win_slot(g & 1);
-            const unsigned char* qb = qb_base + (g & 1) * QB_BYTES;
-            // ---- tx = 0: main term + term 1 of columns 0, 1 ----
-            asm volatile("" ::: "memory");
-            load_f16(win, bslot, 0);
-#pragma unroll
-            for (int m = 0; m < MF; ++m) {
-                xr[m] = ld8(win + xr_off[0] + m * 16 * CV_ROW, win + xr_off[1] + m * 16 * CV_ROW);
-                xsc[m] = *reinterpret_cast<const int*>(win + xs_off + m * 64);
-            }
-            ld_wq(qb, 0); ld_wq(qb, 1);
-            if (!lastg) {
-                dma_a((g + 1) & 1); dma_q((g + 1) & 1); dma_b((bslot + 3) & 3);
-                if (wv == 0) wait_barrier<AP + 5 + 2 + 2, true>(); else wait_barrier<AP + 5 + 2, true>();
-            } else wait_barrier<0, true>();
-            mfmas(0, 2, 0, 0);
-            bslot = (bslot + 1) & 3;
-            // ---- tx = 1: main term + term 1 of columns 2, 3 + term 2 of column 0 ----
-            asm volatile("" ::: "memory");
-            load_f16(win, bslot, 1);
-            ld_wq(qb, 2); ld_wq(qb, 3);
-#pragma unroll
-            for (int m = 0; m < MF; ++m) xq[m] = ld8(win + xq_off[0] + m * 16 * CV_ROW, win + xq_off[1] + m * 16 * CV_ROW);
-            ld_wr(qb, 0);
-            if (!lastg) {
-                dma_b((bslot + 3) & 3);
-                if (wv == 0) wait_barrier<AP + 5 + 2 + 2, true>(); else wait_barrier<AP + 5 + 2, true>();
-            } else wait_barrier<0, true>();
-            mfmas(2, 4, 0, 1);
-            bslot = (bslot + 1) & 3;
-            // ---- tx = 2: main term + term 2 of columns 1, 2, 3 ----
-            asm volatile("" ::: "memory");
-            load_f16(win, bslot, 2);
-            ld_wr(qb, 1); ld_wr(qb, 2); ld_wr(qb, 3);
-            if (!lastg) { dma_b((bslot + 3) & 3); wait_barrier<2, true>(); }
-            else wait_barrier<0, true>();
-            mfmas(0, 0, 1, 4);
-            bslot = (bslot + 1) & 3;
-        }
-        if (grp == 0) __builtin_amdgcn_s_barrier();                       // balance group 1's extra barrier
-        __syncthreads();                                                  // nothing in flight; the ring is dead
     } else
     if constexpr (WIN == 2 && PP) {
         // ---- ping-pong x register window (DEFAULT for 128-wide 3x3 layers): 256-row tile, two wave groups half a step apart as in the PP
@@ -1121,7 +937,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
         for (int g = 0; g < ngroups; ++g) {
             const bool lastg = g + 1 == ngroups;
             // ---- tx = 0: stage 3g (slot 0) and window g have landed; refill slot 2 with stage 3g + 2 ----
-            wait_barrier<BP, false, true>();
+            wait_barrier<BP, true>();
             dma_b(2);
             // window g -> registers (spelled out here and a lambda in the 8-wave loop, as they were before the building blocks
             // were shared: in the other form either loop is scheduled differently)
@@ -1134,12 +950,12 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams& p, const unsign
                 }
             mfma_b(0, ah[0], al[0]);
             // ---- tx = 1: every wave holds window g in registers (lgkmcnt(0) before the barrier): fetch window g + 1 ----
-            wait_barrier<BP, false, true>();
+            wait_barrier<BP, true>();
             if (!lastg) { dma_b(0); dma_a(); }
             mfma_b(1, ah[1], al[1]);
             // ---- tx = 2 (the window's pieces, issued after the weight pieces, stay in flight) ----
-            if (!lastg) { wait_barrier<BP + AP, false, true>(); dma_b(1); }
-            else wait_barrier<0, false, true>();
+            if (!lastg) { wait_barrier<BP + AP, true>(); dma_b(1); }
+            else wait_barrier<0, true>();
             mfma_b(2, ah[2], al[2]);
         }
         __syncthreads();                                      // nothing in flight; the ring is dead (the epilogue reuses it)
@@ -1563,7 +1379,7 @@ static hipError_t launch_conv_nchw_tail(const ConvParams& p_in, const ConvSrc& s
 }
 
 static hipError_t launch_conv_nchw(const ConvParams& p, const ConvSrc& src, hipStream_t s) {
-    if (!src.ptr || !p.tail_w_hi || p.cout_pad != 128 || p.tap_n != 3 || p.tap_sx != 1 || p.in_sc || p.addend || p.variant || (p.tiling & ~2) ||
+    if (!src.ptr || !p.tail_w_hi || p.cout_pad != 128 || p.tap_n != 3 || p.tap_sx != 1 || p.addend || p.variant || (p.tiling & ~2) ||
         !(p.rows >= 256ll * 256 || (p.tiling & 2)) || p.up_B <= 0 || src.c0 < 0 || src.c0 >= p.cin)
         return hipErrorInvalidValue;
     if (p.tail_cout == 16 && p.gu_out) return launch_conv_nchw_tail<1>(p, src, s);
@@ -1583,10 +1399,6 @@ static hipError_t launch_conv_mfma(const ConvParams& p, hipStream_t s) {
     // (1 workgroup per CU) 3.45 ms.  The kernel lives on inter-workgroup overlap: keep 2 workgroups per CU.
     if (p.tail_w_hi) {                           // 3x3 (or 1x1) 128-wide layer + its three 1x1 successors in one kernel
         if (p.cout_pad != 128) return hipErrorInvalidValue;
-        if (p.in_sc) {                                          // round 4: fp16 + block-scaled e4m3 operand format (see the WIN == 4 loop)
-            if (p.tap_n != 3 || !p.w_sc || p.rows < 256ll * 256 || p.addend) return hipErrorInvalidValue;
-            return launch_conv_tail<256, 512, true, 4>(p, s);
-        }
         const bool win = p.tap_n > 1 && !(p.variant & 1);
         // MAGNET_TILING_BM64 (latency mode): 64-row tiles of the 4-wave register-window loop.  One frame of 120x160 is 152 tiles of 128
         // rows for 256 CUs; as 304 tiles of 64 rows every CU has work and part of the chip holds the two workgroups this loop is
@@ -1651,7 +1463,7 @@ static hipError_t launch_conv_mfma_f16(const ConvParams& p, hipStream_t s) {
 
 // The single-plane fp16 format, plane to plane (magnet_conv_mfma_f16p): the F-Net's launches — taps 9 (any dilation), 4 and 1 at 32,
 // 64 and 128 output channels, fp16 residual plane, fp16 / fp32 / single-bf16 output, channel slices, zero border, repad.  The API has
-// refused the fused tail, the addend, the e4m3 format and the BM64 / BM256 tilings.  Tiles are chosen as launch_conv_mfma chooses them
+// refused the fused tail, the addend and the BM64 / BM256 tilings.  Tiles are chosen as launch_conv_mfma chooses them
 // for the F-Net's launches (which carry img_rows, a residual or a 2-byte output: never the 256-row form): 128 rows, 4 waves; 3x3 on the
 // register-window loop, 1x1 and 2x2 windows on the windowless loop.
 static hipError_t launch_conv_mfma_f16p(const ConvParams& p, hipStream_t s) {
@@ -1715,7 +1527,7 @@ static hipError_t launch_conv_mfma_f16d(const ConvParams& p, hipStream_t s) {
 // What each route's instances serve, as the API has checked it before: the launchers' own refusal of anything else
 static bool route_serves(const ConvParams& p, ConvRoute route, int S, const float* work) {
     if (S && (S < 2 || S > 8 || !work)) return false;
-    const bool plain = !(p.tail_w_hi || p.addend || p.in_sc || (p.tiling & ~1));
+    const bool plain = !(p.tail_w_hi || p.addend || (p.tiling & ~1));
     const bool wide = p.cout_pad % 128 == 0 && (p.tap_n == 3 || p.tap_n == 1);           // the shapes of launch_wide
     switch (route) {
     case CONV_BF16X3: return !S || wide;                           // S == 0: launch_conv_mfma refuses what has no instance
@@ -1735,149 +1547,6 @@ hipError_t launch_conv(const ConvParams& p, ConvRoute route, int S, float* work,
     case CONV_F16P:   return S ? hipErrorInvalidValue : launch_conv_mfma_f16p(p, s);
     case CONV_F16D:   return S ? launch_splitk<true>(p, S, work, s) : launch_conv_mfma_f16d(p, s);
     }
-    return hipErrorInvalidValue;
-}
-
-// =====================================================================================================
-// Fused tail of a stack: Conv1x1(128->128)+ReLU, Conv1x1(128->128)+ReLU, Conv1x1(128->cout) in ONE kernel.
-// As separate launches these layers are HBM-bound (each reads and writes a (rows,128) split-bf16 tensor:
-// 1.3 GB per layer per 64-frame launch).  Here a workgroup keeps its 128-row activation tile in LDS across
-// the three layers; only the (rows,128) input is read and the (rows,cout) fp32 result written.
-//   * 4 waves, each owns 32 rows of the tile for all layers (rows are wave-private: no barrier is needed
-//     to hand a layer's output to the next layer, only for the shared weight tiles);
-//   * operands are swapped (weights as the MFMA A operand, activations as B), so the accumulator layout is
-//     C^T: a lane holds 4 CONSECUTIVE output channels of one row -> 8-byte bf16x4 LDS writes for hidden
-//     layers, 16-byte fp32 global stores for the last one;
-//   * activation tile rows are 256 B with slot ^= (row & 15) (conflict-free fragment reads); weight tiles are
-//     streamed per 32-wide K chunk through the same double-buffered swizzled image as conv_mfma_kernel.
-// one layer: acc[n][m] over K = 128 for this wave's 32 rows; NF = output fragments (channels / 16)
-template <int NF, bool LAST>
-__device__ __forceinline__ void chain_layer(const ChainParams& p, const uint16_t* __restrict__ w_hi,
-                                            const uint16_t* __restrict__ w_lo, const float* __restrict__ bias,
-                                            unsigned char* act_hi, unsigned char* act_lo, unsigned char* wst,
-                                            long long row0, int tid, int lane, int wv) {
-    constexpr int BN = NF * 16;
-    constexpr int B_BYTES = BN * CV_ROW, WSTAGE = 2 * B_BYTES;
-    constexpr int B_PT = (BN * 4 + 255) / 256;
-    static_assert(B_PT <= 3, "weight staging registers are spelled out for these sizes");
-    const int st_r = tid >> 2, st_q = tid & 3;
-    uint4 bh0, bh1, bh2, bl0, bl1, bl2;
-    bh1 = bh2 = bl1 = bl2 = make_uint4(0, 0, 0, 0);
-#define CH_ISSUE(KK)                                                                               \
-    {                                                                                              \
-        const size_t e0 = (size_t)(st_r < BN ? st_r : 0) * 128 + (KK) * 32 + st_q * 8;             \
-        bh0 = *reinterpret_cast<const uint4*>(w_hi + e0); bl0 = *reinterpret_cast<const uint4*>(w_lo + e0); \
-        if constexpr (B_PT >= 2) { const size_t e1 = (size_t)(st_r + 64 < BN ? st_r + 64 : 0) * 128 + (KK) * 32 + st_q * 8;  \
-            bh1 = *reinterpret_cast<const uint4*>(w_hi + e1); bl1 = *reinterpret_cast<const uint4*>(w_lo + e1); }            \
-        if constexpr (B_PT >= 3) { const size_t e2 = (size_t)(st_r + 128 < BN ? st_r + 128 : 0) * 128 + (KK) * 32 + st_q * 8; \
-            bh2 = *reinterpret_cast<const uint4*>(w_hi + e2); bl2 = *reinterpret_cast<const uint4*>(w_lo + e2); }            \
-    }
-#define CH_COMMIT(BUF)                                                                             \
-    {                                                                                              \
-        unsigned char* sb_hi = wst + (BUF) * WSTAGE; unsigned char* sb_lo = sb_hi + B_BYTES;       \
-        if (st_r < BN) { *reinterpret_cast<uint4*>(sb_hi + cv_swz(st_r, st_q)) = bh0;             \
-                         *reinterpret_cast<uint4*>(sb_lo + cv_swz(st_r, st_q)) = bl0; }            \
-        if constexpr (B_PT >= 2) if (st_r + 64 < BN) { *reinterpret_cast<uint4*>(sb_hi + cv_swz(st_r + 64, st_q)) = bh1;    \
-                                                       *reinterpret_cast<uint4*>(sb_lo + cv_swz(st_r + 64, st_q)) = bl1; }  \
-        if constexpr (B_PT >= 3) if (st_r + 128 < BN) { *reinterpret_cast<uint4*>(sb_hi + cv_swz(st_r + 128, st_q)) = bh2;  \
-                                                        *reinterpret_cast<uint4*>(sb_lo + cv_swz(st_r + 128, st_q)) = bl2; } \
-    }
-    f32x4_t acc[NF][2];
-#pragma unroll
-    for (int n = 0; n < NF; ++n) { acc[n][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[n][1] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
-    const int frow = lane & 15, kslot = lane >> 4;
-    const int w_off = cv_swz(frow, kslot);                              // + n*16*CV_ROW
-    CH_ISSUE(0)
-    __syncthreads();                                                    // previous layer is done with the weight stage
-    CH_COMMIT(0)
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        if (kk + 1 < 4) CH_ISSUE(kk + 1)
-        const unsigned char* sb_hi = wst + (kk & 1) * WSTAGE;
-        const unsigned char* sb_lo = sb_hi + B_BYTES;
-        bf16x8_t xh[2], xl[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int row = wv * 32 + m * 16 + frow;
-            xh[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(act_hi + act_swz(row, kk * 4 + kslot)));
-            xl[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(act_lo + act_swz(row, kk * 4 + kslot)));
-        }
-#pragma unroll
-        for (int n = 0; n < NF; ++n) {
-            const bf16x8_t wh = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_hi + w_off + n * 16 * CV_ROW));
-            const bf16x8_t wl = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sb_lo + w_off + n * 16 * CV_ROW));
-            // swapped operands: D = W_frag (rows = channels) x act_frag (cols = tile rows)  ->  C^T
-            acc[n][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[0], acc[n][0], 0, 0, 0);
-            acc[n][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[1], acc[n][1], 0, 0, 0);
-            acc[n][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh[0], acc[n][0], 0, 0, 0);
-            acc[n][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh[1], acc[n][1], 0, 0, 0);
-            acc[n][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[0], acc[n][0], 0, 0, 0);
-            acc[n][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[1], acc[n][1], 0, 0, 0);
-        }
-        if (kk + 1 < 4) CH_COMMIT((kk + 1) & 1)
-        __syncthreads();
-    }
-    // epilogue: C^T layout — lane: channels n*16 + (lane>>4)*4 + r (r = 0..3), tile row m*16 + (lane & 15)
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int ch = n * 16 + (lane >> 4) * 4;
-            const int trow = wv * 32 + m * 16 + (lane & 15);
-            const float4 b4 = *reinterpret_cast<const float4*>(bias + ch);
-            float v[4] = {acc[n][m][0] + b4.x, acc[n][m][1] + b4.y, acc[n][m][2] + b4.z, acc[n][m][3] + b4.w};
-            if constexpr (!LAST) {
-                uint32_t h01, l01, h23, l23;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = v[r] < 0.f ? 0.f : v[r];
-                split_bf16x2(v[0], v[1], h01, l01); split_bf16x2(v[2], v[3], h23, l23);
-                const int off = act_swz(trow, ch >> 3) + (ch & 7) * 2;          // 8 bytes: channels ch..ch+3
-                *reinterpret_cast<uint2*>(act_hi + off) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(act_lo + off) = make_uint2(l01, l23);
-            } else {
-                const long long row = row0 + trow;
-                if (row < p.rows)
-                    *reinterpret_cast<float4*>(p.out + (size_t)row * p.cout_pad + ch) = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        }
-#undef CH_ISSUE
-#undef CH_COMMIT
-}
-
-template <int NFL>
-__global__ __launch_bounds__(256) void conv1x1_chain_kernel(const ChainParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* act_hi = smem;                      // [128 rows][256 B]
-    unsigned char* act_lo = smem + 128 * 256;
-    unsigned char* wst    = smem + 2 * 128 * 256;      // 2 stages x (hi, lo) x [max(128, NFL*16) rows][64 B]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const long long row0 = (long long)blockIdx.x * 128;
-    // each wave loads its own 32 rows (x 16 slots x 2 planes)
-    for (int i = lane; i < 32 * 16; i += 64) {
-        const int r = wv * 32 + (i >> 4), slot = i & 15;
-        long long row = row0 + r; row = row < p.rows ? row : p.rows - 1;
-        const size_t e = (size_t)row * 128 + slot * 8;
-        *reinterpret_cast<uint4*>(act_hi + act_swz(r, slot)) = *reinterpret_cast<const uint4*>(p.in_hi + e);
-        *reinterpret_cast<uint4*>(act_lo + act_swz(r, slot)) = *reinterpret_cast<const uint4*>(p.in_lo + e);
-    }
-    chain_layer<8, false>(p, p.w_hi, p.w_lo, p.bias, act_hi, act_lo, wst, row0, tid, lane, wv);
-    chain_layer<8, false>(p, p.w_hi + 128 * 128, p.w_lo + 128 * 128, p.bias + 128, act_hi, act_lo, wst, row0, tid, lane, wv);
-    chain_layer<NFL, true>(p, p.w_hi + 2 * 128 * 128, p.w_lo + 2 * 128 * 128, p.bias + 256, act_hi, act_lo, wst, row0, tid, lane, wv);
-}
-
-template <int NFL>
-static hipError_t launch_chain_nf(const ChainParams& p, hipStream_t s) {
-    constexpr int BNMAX = (NFL * 16 > 128) ? NFL * 16 : 128;
-    const size_t lds = 2 * 128 * 256 + 2 * 2 * (size_t)BNMAX * CV_ROW;
-    hipLaunchKernelGGL((conv1x1_chain_kernel<NFL>), dim3((unsigned)((p.rows + 127) / 128)), dim3(256), lds, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv1x1_chain(const ChainParams& p, hipStream_t s) {
-    if (p.cout_pad == 16)  return launch_chain_nf<1>(p, s);
-    if (p.cout_pad == 144) return launch_chain_nf<9>(p, s);
-    if (p.cout_pad == 128) return launch_chain_nf<8>(p, s);
     return hipErrorInvalidValue;
 }
 

@@ -11,18 +11,15 @@
 //   BF16   magnet_pack_features (bf16)          8  yes     -1   16 bytes of bf16 (round to nearest even)
 //   SPLIT  magnet_pack_split                    8  yes      1   16 bytes in the hi plane + 16 in the lo plane (split_bf16x2)
 //   F16    magnet_pack_f16                      8  no       1   16 bytes of saturated fp16 (f16x2_bits_sat)
-//   MX     magnet_pack_mx                      32  no       1   64 bytes of fp16, 64 of e4m3 (hi | lo), one E8M0 pair
 //
-// PAD is the destination border as a compile-time constant, -1 where the caller chooses it at run time.  Two more constants exist for
-// MX alone: NARROW (false: it has no 64-pixel instance) and PIXEL_FASTEST (true: its store loop walks pixels, not channel vectors,
-// with consecutive threads).
+// PAD is the destination border as a compile-time constant, -1 where the caller chooses it at run time.
 // STREAM marks the 16-byte loads and stores of the wide form non-temporal: a pack reads every source element once and writes every
 // destination element once.  At 64 frames of 120 x 160 on one MI355X: x_d3 pack 0.469 -> 0.448 ms, source features 0.329 -> 0.308 ms,
-// reference features 0.083 -> 0.074 ms; it is no gain for small or cache-resident packs, which is why F16 and MX stay without
+// reference features 0.083 -> 0.074 ms; it is no gain for small or cache-resident packs, which is why F16 stays without
 // (profiles/pack_phase/NOTES.md §1 and §5).
 //
 // The fp16 conversion (F16 and planes_to_f16): round to nearest even; a magnitude that would round above 65504 (+-Inf included)
-// becomes +-65504, as MX clamps its fp16 plane; NaN is written through; the sign of zero is kept.  tests/test_conv_precision_host.py
+// becomes +-65504; NaN is written through; the sign of zero is kept.  tests/test_conv_precision_host.py
 // restates it in numpy and the GPU tests compare bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,7 +59,7 @@ struct PackF32 {
     float* out;
     static constexpr int VEC = 4;
     static constexpr int PAD = -1;                            // the features' border is the caller's: 0 or 1 at run time
-    static constexpr bool STREAM = true, NARROW = true, PIXEL_FASTEST = false;
+    static constexpr bool STREAM = true;
     template <bool NT, class V> __device__ __forceinline__ void store(size_t row, int ctot, int ch, const V& v) const {
         pk_store4<NT>(out + row * ctot + ch, __float_as_uint(v(0)), __float_as_uint(v(1)), __float_as_uint(v(2)), __float_as_uint(v(3)));
     }
@@ -71,7 +68,7 @@ struct PackF32 {
 struct PackBF16 {
     uint16_t* out;
     static constexpr int VEC = 8, PAD = -1;
-    static constexpr bool STREAM = true, NARROW = true, PIXEL_FASTEST = false;
+    static constexpr bool STREAM = true;
     template <bool NT, class V> __device__ __forceinline__ void store(size_t row, int ctot, int ch, const V& v) const {
         uint32_t wd[4];
 #pragma unroll
@@ -83,7 +80,7 @@ struct PackBF16 {
 struct PackSplit {
     uint16_t* hi; uint16_t* lo;
     static constexpr int VEC = 8, PAD = 1;
-    static constexpr bool STREAM = true, NARROW = true, PIXEL_FASTEST = false;
+    static constexpr bool STREAM = true;
     template <bool NT, class V> __device__ __forceinline__ void store(size_t row, int ctot, int ch, const V& v) const {
         uint32_t hh[4], ll[4];
 #pragma unroll
@@ -97,65 +94,12 @@ struct PackSplit {
 struct PackF16 {
     uint16_t* out;
     static constexpr int VEC = 8, PAD = 1;
-    static constexpr bool STREAM = false, NARROW = true, PIXEL_FASTEST = false;
+    static constexpr bool STREAM = false;
     template <bool NT, class V> __device__ __forceinline__ void store(size_t row, int ctot, int ch, const V& v) const {
         uint32_t hh[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) hh[k] = f16x2_bits_sat(v(2 * k), v(2 * k + 1));
         pk_store4<NT>(out + row * ctot + ch, hh[0], hh[1], hh[2], hh[3]);
-    }
-};
-
-// The "2-unit" operand format of the 128-wide 3x3 layers (ConvParams::in_sc).  Per interior position (row) and 32-channel block:
-// f16 = fp16(x) (64 B); qr = 32 e4m3 bytes of hi / 2^e_h, then 32 e4m3 bytes of lo / 2^e_l with lo = x - fp16(x) (exact in fp32);
-// sc [block][row] = {e_h + 127, e_l + 127, 0, 0}: E8M0 exponents with max |.| / 2^e in [128, 256) (<= 448, the e4m3 maximum), 0 for an
-// all-zero block.  Its emit stage is its own: one thread = one (pixel, block), consecutive threads on consecutive pixels
-// (PIXEL_FASTEST), so VEC is the block and the store is five vectors and a word.  The entry point admits only what the wide form
-// takes, so there is no narrow instance.
-__device__ __forceinline__ int mx_block_exp(float m) {                        // m = max |v| >= 0
-    if (!(m > 0.f)) return -127;
-    const int e = (int)((__float_as_uint(m) >> 23) & 0xff) - 127 - 7;        // floor(log2 m) - 7 (denormal m: exponent field 0 -> -134 -> clamped)
-    return e < -127 ? -127 : e;
-}
-struct PackMX {
-    uint16_t* f16; uint8_t* qr; uint32_t* sc; long long sc_rows;
-    static constexpr int VEC = 32, PAD = 1;
-    static constexpr bool STREAM = false, NARROW = false, PIXEL_FASTEST = true;
-    template <bool NT, class V> __device__ __forceinline__ void store(size_t row, int ctot, int ch, const V& v) const {
-        float hi[32], lo[32], mh = 0.f, ml = 0.f;
-        uint32_t hw16[16];
-#pragma unroll
-        for (int c = 0; c < 32; ++c) {
-            // domain of the format: |x| <= 65504 (the fp16 plane); larger magnitudes are clamped — an Inf in the fp16 plane would make the
-            // residual -Inf and poison the block exponent (the bf16x3 format has no such limit; include/magnet_hip.h states the domain)
-            // NaN is not laundered by the clamp (v_med3_f32 would return a finite bound): it goes through to the fp16 plane and both
-            // e4m3 planes and propagates through the matrix instructions exactly as in the bf16x3 format
-            const float tv = v(c);
-            const float xv = tv != tv ? tv : __builtin_amdgcn_fmed3f(tv, -65504.0f, 65504.0f);
-            const _Float16 hh = (_Float16)xv;
-            hi[c] = (float)hh; lo[c] = xv - hi[c];
-            mh = fmaxf(mh, fabsf(hi[c])); ml = fmaxf(ml, fabsf(lo[c]));
-            const uint32_t hb = (uint32_t)__builtin_bit_cast(uint16_t, hh);
-            if (c & 1) hw16[c >> 1] |= hb << 16; else hw16[c >> 1] = hb;
-        }
-        const size_t e = row * ctot + ch;                     // the fp16 plane leaves as soon as it is whole: its 16 registers are free
-#pragma unroll                                                // for the e4m3 words (90 VGPRs; 104 with this store at the end)
-        for (int k = 0; k < 4; ++k) pk_store4<NT>(f16 + e + 8 * k, hw16[4 * k], hw16[4 * k + 1], hw16[4 * k + 2], hw16[4 * k + 3]);
-        const int eh = mx_block_exp(mh), el = mx_block_exp(ml);
-        const float ih = __uint_as_float((uint32_t)(127 - eh) << 23), il = __uint_as_float((uint32_t)(127 - el) << 23);   // 2^-e (e = -127: 2^127 x 0)
-        uint32_t qw[8], rw[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            int a = 0, b = 0;
-            a = __builtin_amdgcn_cvt_pk_fp8_f32(hi[4 * k] * ih, hi[4 * k + 1] * ih, a, false);
-            a = __builtin_amdgcn_cvt_pk_fp8_f32(hi[4 * k + 2] * ih, hi[4 * k + 3] * ih, a, true);
-            b = __builtin_amdgcn_cvt_pk_fp8_f32(lo[4 * k] * il, lo[4 * k + 1] * il, b, false);
-            b = __builtin_amdgcn_cvt_pk_fp8_f32(lo[4 * k + 2] * il, lo[4 * k + 3] * il, b, true);
-            qw[k] = (uint32_t)a; rw[k] = (uint32_t)b;
-        }
-        pk_store4<NT>(qr + e * 2, qw[0], qw[1], qw[2], qw[3]);      pk_store4<NT>(qr + e * 2 + 16, qw[4], qw[5], qw[6], qw[7]);
-        pk_store4<NT>(qr + e * 2 + 32, rw[0], rw[1], rw[2], rw[3]); pk_store4<NT>(qr + e * 2 + 48, rw[4], rw[5], rw[6], rw[7]);
-        sc[(size_t)(ch / 32) * sc_rows + row] = (uint32_t)(eh + 127) | ((uint32_t)(el + 127) << 8);
     }
 };
 
@@ -222,7 +166,7 @@ __global__ __launch_bounds__(256) void pack_nchw_kernel(const float* __restrict_
 #pragma unroll
     for (int it = 0; it < PIX * VPP / 256; ++it) {
         const int i = tid + it * 256;
-        const int q = Fmt::PIXEL_FASTEST ? i % PIX : i / VPP, vc = (Fmt::PIXEL_FASTEST ? i / PIX : i % VPP) * VEC, pq = p0 + q;
+        const int q = i / VPP, vc = (i % VPP) * VEC, pq = p0 + q;
         if (pq >= hw || f0 + vc >= g.C) continue;
         const int y = pq / g.w, x = pq - y * g.w;
         const size_t row = ((size_t)n * (g.h + 2 * pad) + (y + pad)) * (g.w + 2 * pad) + (x + pad);
@@ -231,7 +175,7 @@ __global__ __launch_bounds__(256) void pack_nchw_kernel(const float* __restrict_
 }
 
 // The one launcher.  Wide where the float4 loads can read the source, else narrow; the dev library's MAGNET_PACK_NARROW (read once
-// per process, pack_force_narrow) forces narrow for A/B runs.  A format without a narrow instance is wide by its entry point's own checks.
+// per process, pack_force_narrow) forces narrow for A/B runs.
 static bool pack_force_narrow() {
 #ifdef MAGNET_DEV
     static const bool narrow = getenv("MAGNET_PACK_NARROW") != nullptr;      // dev A/B: the 64-pixel kernel
@@ -245,12 +189,12 @@ template <class Fmt>
 static hipError_t launch_pack_nchw(const float* in, const Fmt& fmt, int N, const PackGeom& g, hipStream_t s) {
     const bool narrow = pack_force_narrow();
     const int hw = g.h * g.w;
-    const bool wide = !Fmt::NARROW || (!narrow && hw % 4 == 0 && g.C % 8 == 0 && g.in_img_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0);
+    const bool wide = !narrow && hw % 4 == 0 && g.C % 8 == 0 && g.in_img_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
     const int pix = wide ? 128 : 64;
     const long long blocks = (long long)N * ((hw + pix - 1) / pix) * ((g.C + 63) / 64);
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     if (wide) hipLaunchKernelGGL((pack_nchw_kernel<Fmt, 128>), dim3((unsigned)blocks), dim3(256), 0, s, in, fmt, g);
-    else if constexpr (Fmt::NARROW) hipLaunchKernelGGL((pack_nchw_kernel<Fmt, 64>), dim3((unsigned)blocks), dim3(256), 0, s, in, fmt, g);
+    else hipLaunchKernelGGL((pack_nchw_kernel<Fmt, 64>), dim3((unsigned)blocks), dim3(256), 0, s, in, fmt, g);
     return hipGetLastError();
 }
 
@@ -290,11 +234,6 @@ hipError_t launch_pack_split(const float* in, uint16_t* out_hi, uint16_t* out_lo
 hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
                            hipStream_t s) {
     return launch_pack_nchw(in, PackF16{out}, N, PackGeom{C, h, w, in_img_stride, ctot, c_off, 1}, s);
-}
-
-hipError_t launch_pack_mx(const float* in, uint16_t* out_f16, uint8_t* out_qr, uint32_t* out_sc, int N, int C, int h, int w, int ctot, int c_off,
-                          long long sc_rows, long long in_img_stride, hipStream_t s) {
-    return launch_pack_nchw(in, PackMX{out_f16, out_qr, out_sc, sc_rows}, N, PackGeom{C, h, w, in_img_stride, ctot, c_off, 1}, s);
 }
 
 // ---- split-bf16 planes (rows, ld), channels [c0, c0 + 8 nv) -> the same channels of an fp16 plane (rows, ld16): f16(hi + lo), the sum

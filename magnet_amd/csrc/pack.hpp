@@ -12,8 +12,6 @@ hipError_t launch_pack_split(const float* in, uint16_t* out_hi, uint16_t* out_lo
                              long long in_img_stride, hipStream_t s);
 hipError_t launch_pack_f16(const float* in, uint16_t* out, int N, int C, int h, int w, int ctot, int c_off, long long in_img_stride,
                            hipStream_t s);
-hipError_t launch_pack_mx(const float* in, uint16_t* out_f16, uint8_t* out_qr, uint32_t* out_sc, int N, int C, int h, int w, int ctot, int c_off,
-                          long long sc_rows, long long in_img_stride, hipStream_t s);
 hipError_t launch_planes_to_f16(const uint16_t* in_hi, const uint16_t* in_lo, uint16_t* out, long long rows, int ld, int ld16, int c0, int c1,
                                 hipStream_t s);
 

@@ -80,7 +80,6 @@ class MagnetConvArgs(ctypes.Structure):
         ("up_depth", ctypes.c_void_p), ("up_out", ctypes.c_void_p),
         ("up_npred", ctypes.c_int32), ("up_B", ctypes.c_int32), ("up_h", ctypes.c_int32), ("up_w", ctypes.c_int32),
         ("gu_in", ctypes.c_void_p), ("gu_out", ctypes.c_void_p),
-        ("in_sc", ctypes.c_void_p), ("w_sc", ctypes.c_void_p), ("sc_rows", ctypes.c_int64),
     ]
 
 
@@ -253,12 +252,10 @@ _PROTOS = {
     "magnet_gaussian_update": (_C, [_P, _P, _P, _I, _I, _P]),
     "magnet_upsample_depth": (_C, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "magnet_conv_mfma": (_C, [_S(MagnetConvArgs), _P]),
-    "magnet_pack_mx": (_C, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _P]),
     "magnet_fnet_stem": (_C, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "magnet_space_to_depth": (_C, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "magnet_avgpool_cl": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "magnet_upsample_bilinear_cl": (_C, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "magnet_conv1x1_chain": (_C, [_P, _P, _P, _P, _P, _P, _L, _I, _P]),
     "magnet_pack_split": (_C, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
     "magnet_gaussian_update_cl": (_C, [_P, _I, _P, _P, _I, _I, _I, _P]),
     "magnet_upsample_depth_cl": (_C, [_P, _P, _I, _P, _I, _I, _I, _P]),
@@ -651,7 +648,7 @@ _CONV_ROUTES = {
 
 def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, out_hi=None, out_lo=None, out_f32=None,
               addend=None, dil=0, out_ld=0, add=None, border=None, repad=0, out_bf16=None, tail=None, upsample=None, gauss=None,
-              mx=None, leaky=None, tiling=None, f16=False, split_k=None, work=None, silu=False, src_nchw=None):
+              leaky=None, tiling=None, f16=False, split_k=None, work=None, silu=False, src_nchw=None):
     """One convolution layer on the matrix cores.  in_hi/in_lo: bf16 tensors whose data_ptr is row 0 (possibly a
     channel-offset view of a wider buffer, `in_ld` = its row pitch in elements); weights (taps, cout_pad, cin) bf16.
     F-Net extras (include/magnet_hip.h): dil (3x3 dilation), out_ld (write a channel slice: out tensors may then be
@@ -671,27 +668,27 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     3x3 layers with cout_pad 128, a fused tail of 16 / 144 outputs or out_f32.  Always returns the row tile count.
     f16 = "plane": the same operand format, plane to plane (magnet_conv_mfma_f16p, the F-Net's launches): `add` = (fp16 plane, None, ld),
     the output is out_f16 (one fp16 plane, passed as out_hi with out_lo None), out_f32 or out_bf16; taps 1 / 4 / 9, cout_pad 32 / 64 /
-    128, dil, border, repad and channel slices as in the default format; no tail, addend, mx or leaky.
+    128, dil, border, repad and channel slices as in the default format; no tail, addend or leaky.
     split_k = S (2 .. SPLITK_MAX) with work = a float32 GPU tensor of at least conv_mfma_splitk_workspace(...) bytes: the split-K form
     (magnet_conv_mfma_splitk) of the plain bf16x3 layer, taps 1 / 9, cout_pad % 128 == 0, out_hi / out_lo or out_f32; not with f16, tail,
-    addend, add or mx.  Returns the row tile count.
+    addend or add.  Returns the row tile count.
     f16 = "wide": the same operand format, plane to plane at any cout_pad % 128 == 0 (magnet_conv_mfma_f16d, the D-Net decoder's plain
     layers): taps 1 / 9, relu or leaky, border, repad and channel slices; the output is out_f16 (passed as out_hi with out_lo None),
-    out_f32 or the split-bf16 pair out_hi / out_lo; no tail, addend, add, mx, dil or out_bf16.  split_k / work are allowed on this route
+    out_f32 or the split-bf16 pair out_hi / out_lo; no tail, addend, add, dil or out_bf16.  split_k / work are allowed on this route
     (magnet_conv_mfma_f16d_splitk).  Returns the row tile count.
     src_nchw = (x (B, C, h, w) fp32 contiguous, c0): input channels [c0, c0 + C) with c0 + C == cin are read in place from x and split
     inside the kernel (magnet_conv_mfma_nchw: the fused-tail 3x3 launches on 256-row tiles under per-image tiling, nothing else); the
     planes hold channels [0, c0) and may be None when c0 == 0.  Returns the row tile count."""
     if src_nchw is not None:
-        if f16 or mx is not None or split_k is not None or leaky is not None or silu:
-            raise MagnetError("conv_mfma (src_nchw): the bf16x3 fused-tail launch only — not with f16, mx, split_k, leaky or silu")
+        if f16 or split_k is not None or leaky is not None or silu:
+            raise MagnetError("conv_mfma (src_nchw): the bf16x3 fused-tail launch only — not with f16, split_k, leaky or silu")
         _dev(src_nchw[0], "src_nchw", torch.float32)
         if src_nchw[0].dim() != 4:
             raise MagnetError("conv_mfma (src_nchw): src must be (B, C, h, w)")
     wide = isinstance(f16, str) and f16 == "wide"
     if split_k is not None:
-        if (f16 and not wide) or tail is not None or addend is not None or add is not None or mx is not None:
-            raise MagnetError("conv_mfma (split_k): the plain bf16x3 layer (or f16='wide') only — not with f16=True / 'plane', tail, addend, add or mx")
+        if (f16 and not wide) or tail is not None or addend is not None or add is not None:
+            raise MagnetError("conv_mfma (split_k): the plain bf16x3 layer (or f16='wide') only — not with f16=True / 'plane', tail, addend or add")
         if isinstance(split_k, bool) or not isinstance(split_k, int):
             raise MagnetError(f"conv_mfma: split_k must be an int, got {split_k!r}")
         if not isinstance(work, torch.Tensor) or not work.is_cuda or work.dtype != torch.float32 or not work.is_contiguous():
@@ -710,24 +707,11 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     if plane and (tail is not None or addend is not None or out_lo is not None or (add is not None and add[1] is not None)):
         raise MagnetError("conv_mfma (f16='plane'): one fp16 plane per buffer — out_lo and add[1] must be None; no tail, no addend")
     if f16:
-        if in_lo is not None or w_lo is not None or mx is not None or (leaky is not None and not wide):
-            raise MagnetError("conv_mfma (f16): one fp16 plane per operand — in_lo, w_lo, mx and leaky (but for f16='wide') must be None")
+        if in_lo is not None or w_lo is not None or (leaky is not None and not wide):
+            raise MagnetError("conv_mfma (f16): one fp16 plane per operand — in_lo, w_lo and leaky (but for f16='wide') must be None")
         for t, n in ((in_hi, "in_hi"), (w_hi, "w_hi")):
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float16:
                 raise MagnetError(f"conv_mfma (f16): {n} must be an fp16 GPU tensor")
-    elif mx is not None:
-        # mx = (in_sc, w_sc, sc_rows): the fp16 + block-scaled e4m3 operand format (include/magnet_hip.h v302): in_hi / w_hi are fp16
-        # planes, in_lo / w_lo the 2-byte-per-channel containers of the e4m3 hi | lo bytes (any 2-byte dtype), scales as int32 tensors
-        for t, n in ((in_hi, "in_hi"), (w_hi, "w_hi")):
-            if not t.is_cuda or t.dtype != torch.float16:
-                raise MagnetError(f"conv_mfma (mx): {n} must be an fp16 GPU tensor")
-        for t, n in ((in_lo, "in_lo"), (w_lo, "w_lo")):
-            if not t.is_cuda or t.element_size() != 2:
-                raise MagnetError(f"conv_mfma (mx): {n} must be a 2-byte GPU tensor (e4m3 hi | lo bytes per 32-channel block)")
-        isc, wsc, sc_rows = mx
-        if isc.dtype != torch.int32 or wsc.dtype != torch.int32 or not isc.is_cuda or not wsc.is_cuda:
-            raise MagnetError("conv_mfma (mx): scale planes must be int32 GPU tensors")
-        a.in_sc, a.w_sc, a.sc_rows = isc.data_ptr(), wsc.data_ptr(), int(sc_rows)
     else:
         no_planes = src_nchw is not None and int(src_nchw[1]) == 0 and in_hi is None and in_lo is None
         for t, n in ((w_hi, "w_hi"), (w_lo, "w_lo")) if no_planes else ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo")):
@@ -812,7 +796,7 @@ def conv_row_tiles(n_img, h, wp, bm):
 
 
 def _nchw_source(who, x_nchw):
-    """The source of pack_split / pack_f16 / pack_mx: a float32 GPU tensor (N,C,h,w) whose images are dense (a leading-channel slice of a
+    """The source of pack_split / pack_f16: a float32 GPU tensor (N,C,h,w) whose images are dense (a leading-channel slice of a
     wider NCHW tensor is).  Returns N, C, h, w and the in_img_stride argument: 0 (= dense) for one image, whose stride(0) is arbitrary."""
     if not x_nchw.is_cuda or x_nchw.dtype != torch.float32:
         raise MagnetError(f"{who}: input must be a float32 GPU tensor")
@@ -827,23 +811,6 @@ def pack_split(x_nchw, out_hi, out_lo, ctot, c_off):
     padded channel-last buffer (N,h+2,w+2,ctot), channels [c_off, c_off+C)."""
     N, C, h, w, img_stride = _nchw_source("pack_split", x_nchw)
     _launch("magnet_pack_split", x_nchw, x_nchw.data_ptr(), out_hi.data_ptr(), out_lo.data_ptr(), N, C, h, w, int(ctot), int(c_off), img_stride)
-
-
-def pack_mx(x_nchw, out_f16, out_qr, out_sc, ctot, c_off, sc_rows):
-    """fp32 (N,C,h,w) -> channels [c_off, c_off+C) of the interior of a padded channel-last buffer (N,h+2,w+2,ctot) in the fp16 + e4m3
-    operand format of conv_mfma(mx=...): out_f16 fp16 plane, out_qr 2-byte container plane (hi | lo e4m3 bytes per 32-channel block),
-    out_sc int32 [ctot / 32][sc_rows] E8M0 pairs."""
-    N, C, h, w, img_stride = _nchw_source("pack_mx", x_nchw)
-    if out_f16.dtype != torch.float16 or out_qr.element_size() != 2 or out_sc.dtype != torch.int32:
-        raise MagnetError("pack_mx: out_f16 fp16, out_qr a 2-byte dtype, out_sc int32")
-    rows = N * (h + 2) * (w + 2)
-    for name, t, need in (("out_f16", out_f16, rows * int(ctot)), ("out_qr", out_qr, rows * int(ctot)), ("out_sc", out_sc, (int(ctot) // 32) * int(sc_rows))):
-        if not t.is_cuda or t.device != x_nchw.device or not t.is_contiguous() or t.numel() < need:
-            raise MagnetError(f"pack_mx: {name} must be a contiguous tensor on {x_nchw.device} with at least {need} elements")
-    if int(ctot) % 32 or int(c_off) % 32 or int(c_off) + C > int(ctot) or int(sc_rows) < rows:
-        raise MagnetError("pack_mx: ctot / c_off must be multiples of 32 with c_off + C <= ctot, and sc_rows >= N (h+2) (w+2)")
-    _launch("magnet_pack_mx", x_nchw, x_nchw.data_ptr(), out_f16.data_ptr(), out_qr.data_ptr(), out_sc.data_ptr(), N, C, h, w, int(ctot),
-            int(c_off), int(sc_rows), img_stride)
 
 
 def pack_f16(x_nchw, out_f16, ctot, c_off):
@@ -904,14 +871,6 @@ def upsample_depth_cl_n(depths, mask_pad, ld):
     _launch("magnet_upsample_depth_cl_n", d, d.data_ptr(), _dev(mask_pad, "mask_pad", torch.float32).data_ptr(), int(ld), out.data_ptr(),
             n, B, h, w)
     return [out[i] for i in range(n)]
-
-
-def conv1x1_chain(in_hi, in_lo, w_hi, w_lo, bias, out, rows, cout_pad):
-    """relu(1x1 128->128), relu(1x1 128->128), 1x1 128->cout_pad in one launch (see include/magnet_hip.h)."""
-    planes = [_bf16_ptr(t, f"conv1x1_chain: {n}", contiguous=True)
-              for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo"), (w_hi, "w_hi"), (w_lo, "w_lo"))]
-    _launch("magnet_conv1x1_chain", in_hi, *planes, _dev(bias, "bias", torch.float32).data_ptr(),
-            _dev(out, "out", torch.float32).data_ptr(), int(rows), int(cout_pad))
 
 
 def make_rays(ray_params, h: int, w: int):

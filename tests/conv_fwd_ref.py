@@ -1,5 +1,5 @@
-"""fp64 restatements of conv_mfma's FORWARD launches (csrc/conv_mfma.hip: the plain epilogue, the border / repad addressing, the fused
-1x1 tail, and magnet_conv1x1_chain), each with a pointwise error bound derived from the kernel's arithmetic.  The checker, the tap
+"""fp64 restatements of conv_mfma's FORWARD launches (csrc/conv_mfma.hip: the plain epilogue, the border / repad addressing, and the fused
+1x1 tail), each with a pointwise error bound derived from the kernel's arithmetic.  The checker, the tap
 offsets and the fp64 contraction are those of tests/fnet_bwd_ref.py (imported, not copied); the notation is the same: u = 2^-24,
 gamma_L = L u / (1 - L u), 2^-16 = LOLO, a bound of 0 means bit-exact.
 
@@ -28,7 +28,7 @@ counted as error), works on the device of its inputs in float64 and uses matrix 
   border, repad                border=(hp, pad): outputs at the border positions of the (N, hp, wp) grids are written as +0 exactly.
   (border_and_repad)           repad = q + 1: only interior positions are written, at row (n (h + 2q) + y + q) (w + 2q) + x + q of
                                an (N, h + 2q, w + 2q) grid; every other element of the output buffer is never touched.
-  fused tail, 1x1 chain        three 1x1 layers over K = 128 on an LDS-resident activation that is re-split to hi + lo between
+  fused tail                   three 1x1 layers over K = 128 on an LDS-resident activation that is re-split to hi + lo between
   (tail_ref)                   layers.  For an input activation a known to e pointwise: ref' = W a + b and
                                    bound' = |W| e + c_K (|W| (|a| + e) + |b|),   c_K = 1.01 LOLO + 1.02 gamma(3 * 128 + 4):
                                the first term is the propagated input error (interval arithmetic), the second the layer's own
@@ -36,11 +36,7 @@ counted as error), works on the device of its inputs in float64 and uses matrix 
                                and the bias addition, inside the plain form's L.  A hidden layer applies ReLU (1-Lipschitz) and
                                re-splits its output v to hi + lo: |v - (hi + lo)| <= LOLO |v| <= LOLO (|relu(ref')| + bound').
                                The tail's input is the first layer's fp32 result split the same way: bound0 = bound + LOLO (|a0| +
-                               bound); the chain's input ARE planes (a0 = hi + lo): bound0 = 0.
-
-Not restated here: the fp16 + block-scaled e4m3 operand format (MagnetConvArgs.in_sc) — its correction terms are e4m3 products with a
-shared exponent per 32 channels, which needs its own derivation (a separate piece of work);
-tests/test_gpu_conv.py::test_conv_stack_mx_format_matches_fp32 keeps its check.
+                               bound); for an input that IS planes (a0 = hi + lo): bound0 = 0.
 """
 from __future__ import annotations
 

@@ -5,7 +5,8 @@
 LIBRARY is the libmagnet_hip.so whose behaviour is to be pinned: the one built in a checkout of the parent commit (python -m
 magnet_amd.build there), on a machine without a GPU.  It is named on the command line and loaded in place of this tree's own, because
 this script imports magnet_amd.lib (the ctypes mirrors and prototypes, which an unchanged ABI shares) from the tree it lies in, and
-would otherwise record the code under test.  Besides that it needs ctypes only.  Every case is a valid base argument set of its entry point (fake 16-aligned pointers, small dimensions, as
+would otherwise record the code under test.  (After a change of MagnetConvArgs the mirrors no longer fit the parent's library: then this
+tree's library is recorded and the new file compared with the old one case by case, as profiles/retire_mx/NOTES.md did.)  Besides that it needs ctypes only.  Every case is a valid base argument set of its entry point (fake 16-aligned pointers, small dimensions, as
 tests/test_splitk_host.py builds its own) with the fields of `set` overridden and the call arguments of `call` replaced, so that one
 rule is violated (two in the cases named "two: ...", which pin the order of checks whose codes differ).  Recorded per case: the
 MAGNET_E_* code (the workspace queries answer its negative), magnet_last_error(), `exact` = the message comes from conv_mfma_run's
@@ -73,8 +74,6 @@ COMMON = [
     ("border_hp 7", {"base.border_hp": 7, "base.border_pad": 1}),
     ("border_hp * wp 2^24", {"base.border_hp": 1 << 20, "base.border_pad": 1, "base.rows": 17 << 20}),
     ("repad without border_hp", {"base.repad": 1}),
-    ("in_sc without w_sc", {"base.in_sc": P}),
-    ("e4m3 without a tail", {"base.in_sc": P, "base.w_sc": P, "base.sc_rows": 510}),
     ("up_out without up_depth", {"base.up_out": P}),
     ("upsampling without a tail", {"base.up_out": P, "base.up_depth": P}),
     ("upsampling with bad dims", {**TAIL, **GRID, "base.tail_cout_pad": 144, "base.up_out": P, "base.up_depth": P, "base.up_npred": 1, "base.up_h": 27}),
@@ -86,7 +85,7 @@ COMMON = [
 ]
 
 LEAKY = {"act": lib.ACT_LEAKY_RELU, "act_slope": 0.01}
-PLANES = [(f, {"base." + f: P}, f) for f in ("in_lo", "w_lo", "in_sc", "w_sc")]
+PLANES = [(f, {"base." + f: P}, f) for f in ("in_lo", "w_lo")]
 ACT = [("act 7", {"act": 7}, "act"), ("LeakyReLU with relu", {**LEAKY, "base.relu": 1}, "relu"), ("act_slope 1e38", {**LEAKY, "act_slope": 1e38}, "act_slope")]
 FUSED = [("tail_w_hi", {"base.tail_w_hi": P}, "fused tail"), ("tail_w_lo", {"base.tail_w_lo": P}, "fused tail"), ("addend", {"base.addend": P}, "addend"),
          ("up_out", {"base.up_out": P}, "upsampling"), ("up_depth", {"base.up_depth": P}, "upsampling"), ("gu_in", {"base.gu_in": P}, "Gaussian update"),
@@ -94,8 +93,7 @@ FUSED = [("tail_w_hi", {"base.tail_w_hi": P}, "fused tail"), ("tail_w_lo", {"bas
 SPLITK_FORM = [
     ("split_k 1", {}, {"split_k": 1}, "split_k"), ("split_k 9", {}, {"split_k": 9}, "split_k"), ("split_k -1", {}, {"split_k": -1}, "split_k"),
     *[(n, s, {}, w) for n, s, w in FUSED],
-    ("add_hi", {"base.add_hi": P}, {}, "residual input"), ("add_lo", {"base.add_lo": P}, {}, "residual input"), ("in_sc", {"base.in_sc": P}, {}, "e4m3 format"),
-    ("w_sc", {"base.w_sc": P}, {}, "e4m3 format"),
+    ("add_hi", {"base.add_hi": P}, {}, "residual input"), ("add_lo", {"base.add_lo": P}, {}, "residual input"),
     ("tiling BM256", {"tiling": lib.TILING_BM256}, {}, "tiling"), ("tiling BM64", {"tiling": lib.TILING_BM64}, {}, "tiling"), ("tiling 8", {"tiling": 8}, {}, "tiling"),
     ("taps 4", {"base.taps": 4}, {}, "taps"), ("cout_pad 64", {"base.cout_pad": 64}, {}, "cout_pad"), ("cout_pad 144", {"base.cout_pad": 144}, {}, "cout_pad"),
     ("out_mode 2", {"base.out_mode": 2, "base.out_hi": P}, {}, "out_mode"), ("rows 0", {"base.rows": 0}, {}, "rows"), ("cin 176", {"base.cin": 176}, {}, "cin"),
@@ -119,7 +117,6 @@ OWN = {
         NULL_ARGS, *[(n, s, {}, w) for n, s, w in ACT], ("LeakyReLU with a tail", {**LEAKY, **TAIL, "base.tail_cout_pad": 16}, {}, "tail"),
         ("tiling 8", {"tiling": 8}, {}, "tiling"), ("BM64 with BM256", {"tiling": lib.TILING_BM64 | lib.TILING_BM256}, {}, "MAGNET_TILING_BM256"),
         ("BM64 at taps 1", {"tiling": lib.TILING_BM64, "base.taps": 1}, {}, "taps"), ("BM64 at cout_pad 64", {"tiling": lib.TILING_BM64, "base.cout_pad": 64}, {}, "cout_pad"),
-        ("BM64 with e4m3", {"tiling": lib.TILING_BM64, "base.in_sc": P, "base.w_sc": P}, {}, "bf16x3"),
     ],
     "magnet_conv_mfma_f16": [
         NULL_ARGS, *[(n, s, {}, w) for n, s, w in PLANES], ("act LeakyReLU", LEAKY, {}, "act"), ("tiling BM64", {"tiling": lib.TILING_BM64}, {}, "tiling"),
@@ -149,7 +146,6 @@ TWO = [
     ("magnet_conv_mfma", "two: in_hi misaligned, dil 9", {"base.in_hi": 24, "base.dil": 9}, {}, "aligned"),
     ("magnet_conv_mfma", "two: out_f32 NULL, cin 16", {"base.out_f32": None, "base.cin": 16}, {}, "NULL output"),
     ("magnet_conv_mfma", "two: addend misaligned, in_ld 100", {"base.addend": 24, "base.in_ld": 100}, {}, "addend"),
-    ("magnet_conv_mfma", "two: e4m3 without a tail, up_out without up_depth", {"base.in_sc": P, "base.w_sc": P, "base.sc_rows": 510, "base.up_out": P}, {}, "e4m3"),
     ("magnet_conv_mfma_ex", "two: act 7, in_hi NULL", {"act": 7, "base.in_hi": None}, {}, "act"),
     ("magnet_conv_mfma_ex", "two: tiling 8, bias misaligned", {"tiling": 8, "base.bias": 24}, {}, "tiling"),
     ("magnet_conv_mfma_f16", "two: in_lo, in_hi NULL", {"base.in_lo": P, "base.in_hi": None}, {}, "in_lo"),

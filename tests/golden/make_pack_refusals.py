@@ -1,12 +1,12 @@
-"""Record what the four layout-pack entry points answer to refused argument sets: tests/golden/pack_refusals.json.
+"""Record what the three layout-pack entry points answer to refused argument sets: tests/golden/pack_refusals.json.
 
     python tests/golden/make_pack_refusals.py LIBRARY [out.json]
 
 LIBRARY is the libmagnet_hip.so whose behaviour is to be pinned: the one built in a checkout of the parent commit (python -m
 magnet_amd.build there), on a machine without a GPU.  It is loaded in place of this tree's own, as tests/golden/make_conv_refusals.py
 does and for its reason.  Every case is the valid base argument set of its entry point (fake 16-aligned pointers, small dimensions)
-with the arguments of `set` replaced, so that one rule is violated: every fail(...) site of magnet_pack_features, magnet_pack_split,
-magnet_pack_f16 and magnet_pack_mx, each condition of a site once.  The cases named "two: ..." violate two rules and pin the order of
+with the arguments of `set` replaced, so that one rule is violated: every fail(...) site of magnet_pack_features, magnet_pack_split
+and magnet_pack_f16, each condition of a site once.  The cases named "two: ..." violate two rules and pin the order of
 the checks.  Recorded per case: the MAGNET_E_* code and magnet_last_error(), which the replay compares byte for byte.  Only refusals are
 written, since replaying an accepted call on a machine with a GPU would launch on fake pointers; a case marked MAYBE is one the
 entry point may accept (magnet_pack_split takes a negative in_img_stride), tried and kept only if it is refused.
@@ -24,7 +24,6 @@ BASES = {
     "magnet_pack_features": dict(nchw=P, out_cl=P, N=2, F=16, h=4, w=6, out_dtype=lib.FEAT_F32, pad=0),
     "magnet_pack_split": dict(nchw=P, out_hi=P, out_lo=P, N=2, C=16, h=4, w=6, ctot=32, c_off=8, in_img_stride=0),
     "magnet_pack_f16": dict(nchw=P, out_f16=P, N=2, C=16, h=4, w=6, ctot=32, c_off=8, in_img_stride=0),
-    "magnet_pack_mx": dict(nchw=P, out_f16=P, out_qr=P, out_sc=P, N=2, C=32, h=4, w=6, ctot=64, c_off=32, sc_rows=2 * 6 * 8, in_img_stride=0),
 }
 MAYBE = "maybe"
 DIMS = [(f"{d} 0", {d: 0}) for d in "Nhw"] + [(f"{d} -1", {d: -1}) for d in "Nhw"]
@@ -50,15 +49,6 @@ CASES = {
         ("nchw NULL", {"nchw": None}), ("out_f16 NULL", {"out_f16": None}), *DIMS, *SLICE, ("in_img_stride -4", {"in_img_stride": -4}),
         ("rows 2^31", {"N": 1 << 20, "h": 46, "w": 46}), ("out_f16 misaligned", {"out_f16": ODD}),
         ("two: nchw NULL, c_off 4", {"nchw": None, "c_off": 4}), ("two: in_img_stride -4, out_f16 misaligned", {"in_img_stride": -4, "out_f16": ODD}),
-    ],
-    "magnet_pack_mx": [
-        ("nchw NULL", {"nchw": None}), ("out_f16 NULL", {"out_f16": None}), ("out_qr NULL", {"out_qr": None}), ("out_sc NULL", {"out_sc": None}),
-        *DIMS, ("C 0", {"C": 0}), ("C 16", {"C": 16, "c_off": 0}), ("c_off 16", {"c_off": 16}), ("c_off -32", {"c_off": -32}), ("ctot 80", {"ctot": 80}),
-        ("c_off + C over ctot", {"c_off": 64}), ("h*w 15", {"h": 3, "w": 5, "sc_rows": 1 << 20}), ("sc_rows short", {"sc_rows": 2 * 6 * 8 - 1}),
-        ("sc_rows -1", {"sc_rows": -1}), ("out_f16 misaligned", {"out_f16": ODD}), ("out_qr misaligned", {"out_qr": ODD}),
-        ("nchw misaligned", {"nchw": ODD}), ("in_img_stride 770", {"in_img_stride": 770}), ("out_sc 8-aligned", {"out_sc": ODD}, MAYBE),
-        ("two: out_sc NULL, C 16", {"out_sc": None, "C": 16}), ("two: c_off 16, sc_rows short", {"c_off": 16, "sc_rows": 1}),
-        ("two: sc_rows short, out_qr misaligned", {"sc_rows": 1, "out_qr": ODD}),
     ],
 }
 

@@ -142,7 +142,7 @@ def test_prototype_comparison_rejects_wrong_tables():
         argtypes[argtypes.index(ctypes.c_int64)] = ctypes.c_int32
         return argtypes
 
-    for name in ("magnet_pack_split", "magnet_conv1x1_chain", "magnet_cost_volume_f_backward_ws"):
+    for name in ("magnet_pack_split", "magnet_pack_f16", "magnet_cost_volume_f_backward_ws"):
         errs = _proto_mismatches(changed(name, narrow), L)
         assert len(errs) == 1 and name in errs[0] and "int64_t" in errs[0], errs
     errs = _proto_mismatches(changed("magnet_upsample_depth", lambda a: a[:-1]), L)

@@ -174,7 +174,7 @@ def emulate_conv(xh, xl, wh, wl, bias, taps, wp, rows, dil=1, addend=None, add=N
 
 
 def emulate_tail(a0, tail_wh, tail_wl, tail_bias, tail_cout, defect=None):
-    """The fused tail / the 1x1 chain in fp32 from the fp32 activation a0 (rows, 128) (split here, as the first layer's epilogue does;
+    """The fused tail in fp32 from the fp32 activation a0 (rows, 128) (split here, as the first layer's epilogue does;
     planes split again are unchanged): per layer and 32-wide chunk hi_w lo_a, lo_w hi_a, hi_w hi_a, then bias, ReLU, re-split."""
     hi, lo = split_bf16(a0.float())
     wo = bo = 0
@@ -271,10 +271,10 @@ def test_fp32_emulation_of_the_tail_stays_inside_the_bound(tail_cout, heavy):
         ref, bound = _tail_ref_of(c, addend)
         got = emulate_tail(_emu_of(c, relu=True, addend=addend), c["twh"], c["twl"], c["tb"], tail_cout)
         worst[name] = C.check(name, got, ref, bound)
-    # the chain: its input ARE planes, bound0 = 0
+    # the tail on an input that IS planes: bound0 = 0
     a_hi, a_lo = split_bf16(_emu_of(c, relu=True))
     ref, bound = C.tail_ref(C.join(a_hi, a_lo), torch.zeros(a_hi.shape, dtype=torch.float64), C.join(c["twh"], c["twl"]), c["tb"], tail_cout)
-    worst["chain"] = C.check("chain", emulate_tail(a_hi.float() + a_lo.float(), c["twh"], c["twl"], c["tb"], tail_cout), ref, bound)
+    worst["planes"] = C.check("planes", emulate_tail(a_hi.float() + a_lo.float(), c["twh"], c["twl"], c["tb"], tail_cout), ref, bound)
     print(f"[emulation tail_cout={tail_cout} heavy={heavy}] worst ratio " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
     assert min(worst.values()) > 0
 

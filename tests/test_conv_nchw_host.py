@@ -66,8 +66,6 @@ def test_refusals_are_codes_before_any_launch(hip_lib, kind):
     _refused(hip_lib, n, lib.E_NULL, "src is NULL")
     n = _args(kind=kind); n.ex.act = lib.ACT_LEAKY_RELU
     _refused(hip_lib, n, lib.E_DIM, "act=1")
-    n = _args(kind=kind); n.ex.base.in_sc = n.ex.base.w_sc = PTR                          # the fp16 + e4m3 format
-    _refused(hip_lib, n, lib.E_DIM, "e4m3")
     n = _args(kind=kind); n.ex.base.dil = 2
     _refused(hip_lib, n, lib.E_DIM, "no dilation")
     n = _args(kind=kind); n.ex.base.tail_cout_pad = 128                                    # a tail without Gaussian update / upsampling

@@ -1,5 +1,5 @@
 """What the nine convolution entry points refuse, and with which MAGNET_E_* code and message, is part of their contract: every case of
-tests/golden/conv_refusals.json (368 refused argument sets recorded by tests/golden/make_conv_refusals.py from the library before the
+tests/golden/conv_refusals.json (348 refused argument sets recorded by tests/golden/make_conv_refusals.py from the library before the
 entry points were routed through one launcher: every fail(...) site of conv_mfma_run, of the entry points and of their shared checks once
 per entry point that reaches it, and 18 two-violation cases that pin the order where the codes differ) is replayed against the current
 library.  No GPU needed, and none wanted: the argument sets hold fake pointers, so the test skips itself where a device is visible."""
@@ -28,7 +28,7 @@ def test_every_recorded_refusal_is_refused_alike(hip_lib):
     gen = _generator()
     with open(os.path.join(GOLDEN, "conv_refusals.json")) as f:
         cases = json.load(f)["cases"]
-    assert len(cases) == 368 and {c["entry"] for c in cases} == set(gen.BASES)
+    assert len(cases) == 348 and {c["entry"] for c in cases} == set(gen.BASES)
     bad = []
     for c in cases:
         assert 0 < c["code"] <= lib.E_SHAPE, f"{c['entry']} / {c['name']}: the file holds a call that is not a refusal"

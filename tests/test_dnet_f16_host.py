@@ -163,7 +163,7 @@ def test_workspace_query_of_the_fp16_split_k_form(hip_lib):
     assert ws(None, 2) == -lib.E_NULL
     for S in (0, 1, 9):
         assert ws(ctypes.byref(_valid()), S) == -lib.E_DIM
-    for field in ("in_lo", "w_lo", "in_sc", "w_sc", "add_hi", "add_lo", "tail_w_hi", "tail_w_lo", "addend", "up_out", "up_depth", "gu_in",
+    for field in ("in_lo", "w_lo", "add_hi", "add_lo", "tail_w_hi", "tail_w_lo", "addend", "up_out", "up_depth", "gu_in",
                   "gu_out"):
         x = _valid(); setattr(x.base, field, 16)
         assert ws(ctypes.byref(x), 2) == -lib.E_DIM, field
@@ -191,7 +191,7 @@ def test_entry_point_refusals_come_before_a_launch(hip_lib):
     run, sk = L.magnet_conv_mfma_f16d, L.magnet_conv_mfma_f16d_splitk
     need = 2 * 330 * 256 * 4
     assert run(None, None) == lib.E_NULL and sk(None, 2, 16, need, None) == lib.E_NULL
-    for field in ("in_lo", "w_lo", "in_sc", "w_sc", "add_hi", "add_lo", "tail_w_hi", "addend", "up_out", "gu_in"):
+    for field in ("in_lo", "w_lo", "add_hi", "add_lo", "tail_w_hi", "addend", "up_out", "gu_in"):
         x = _valid(); setattr(x.base, field, 16)
         assert run(ctypes.byref(x), None) == lib.E_DIM and sk(ctypes.byref(x), 2, 16, need, None) == lib.E_DIM, field
     for tiling in (lib.TILING_BM64, lib.TILING_BM256):

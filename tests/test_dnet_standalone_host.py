@@ -76,7 +76,7 @@ def test_abi_grows_by_one_symbol(hip_lib):
     text = open(HEADER).read()
     assert re.search(r"MAGNET_API int magnet_dnet_upsample_gauss\(const float \*head, int32_t head_ld, const float \*mask, int32_t mask_ld,"
                      r"\s*int32_t N,\s*int32_t h, int32_t w, float \*out, void \*stream\);", text)
-    assert re.search(r"#define MAGNET_HIP_VERSION 400\b", text)
+    assert re.search(r"#define MAGNET_HIP_VERSION 500\b", text)
     assert hasattr(hip_lib, "magnet_dnet_upsample_gauss")
     L = hip_lib
     assert L.magnet_dnet_upsample_gauss(None, 16, 16, 144, 1, 4, 4, 16, None) == 1             # NULL

@@ -135,7 +135,7 @@ def test_f16p_argument_errors_are_codes_not_crashes(hip_lib):
     f = hip_lib.magnet_conv_mfma_f16p
     assert f(None, None) == lib.E_NULL
     for name, over in (("in_lo", dict(in_lo=16)), ("w_lo", dict(w_lo=16)), ("add_lo", dict(add_hi=16, add_lo=16)),
-                       ("add_lo alone", dict(add_lo=16)), ("in_sc", dict(in_sc=16, w_sc=16)),
+                       ("add_lo alone", dict(add_lo=16)),
                        ("fused tail", dict(tail_w_hi=16, tail_w_lo=16, tail_bias=16, tail_cout_pad=16, out_f32=16, cout_pad=128)),
                        ("addend", dict(addend=16)), ("BM64", dict(tiling=lib.TILING_BM64)), ("BM256", dict(tiling=lib.TILING_BM256)),
                        ("out_mode 0", dict(out_mode=0, out_lo=16)), ("out_mode 4", dict(out_mode=4)),

@@ -1,6 +1,6 @@
 """Every forward conv_mfma instance, one direct launch each, against the fp64 restatement of tests/conv_fwd_ref.py, pointwise.
 
-Each test makes ONE lib.conv_mfma / lib.conv1x1_chain / lib.pack_split call on planes split with convnet.split_bf16 and weights packed
+Each test makes ONE lib.conv_mfma / lib.pack_split call on planes split with convnet.split_bf16 and weights packed
 with planes.pack_taps, and compares it with the reference of exactly the planes the kernel received through `check` (|got - ref| <=
 bound at every element; the bound is derived in conv_fwd_ref.py, not measured).  Outputs live inside one allocation with NaN guard
 bands on both sides; rows at or past `rows`, channels outside a written slice and (under repad) the target grid's border must keep
@@ -14,7 +14,6 @@ threads, PP the 8-wave ping-pong loop, WIN 2 = register row window, 1 = 2-slot L
 library reports (rows / BM rounded up) is asserted, which tells the 128-row from the 256-row instances.
 
   fused tail (tail_w_hi; cout_pad must be 128; T = tail_cout / 16 = 1, 8, 9)
-    in_sc (fp16 + e4m3 operands), taps 9, rows >= 65536, no addend        <8,2,256,T,512,PP,4>    not here (see below)
     taps 9 and (rows >= 65536 or TILING_BM256) and no addend                <8,2,256,T,512,PP,2>    test_fused_tail[bm256-*]
     taps 9 (so also: addend under TILING_BM256, the hoisted first layer)    <8,2,128,T,256,-,2>     test_fused_tail[t9-*], [addend*-*]
     taps 4                                                                  <8,2,128,T,256,-,1>     test_fused_tail[t4-*]
@@ -28,7 +27,6 @@ library reports (rows / BM rounded up) is asserted, which tells the 128-row from
     cout_pad 16 (any taps)                                                  <1,1,128,0,256,-,0>     nf1_flat-*
     cout_pad 32 / 64, taps 9                                                <2|4,1,128,0,256,-,2>   nf2_win2-*, nf4_win2-*
     cout_pad 32 / 64 (taps 4, 1)                                            <2|4,1,128,0,256,-,0>   nf2_flat-*, nf4_flat-*
-  launch_conv1x1_chain: cout_pad 16 / 128 / 144 -> conv1x1_chain_kernel<1 / 8 / 9>                  test_conv1x1_chain
   launch_pack_split (csrc/pack.hip): h*w % 4 == 0, C % 8 == 0, in_img_stride % 4 == 0, 16-byte aligned input ->
     pack_nchw_kernel<PackSplit, 128>, else pack_nchw_kernel<PackSplit, 64>                          test_pack_split
 
@@ -41,8 +39,6 @@ Not repeated here, because existing tests tie them bit for bit to launches that 
                                                          checked against fp64 with derived pointwise bounds, at block-edge shapes
                                                          and edge inputs, in tests/test_gpu_elementwise_fwd.py (restatements and
                                                          bounds: tests/elementwise_fwd_ref.py)
-  the fp16 + e4m3 operand format (opt-in)                test_gpu_conv.py::test_conv_stack_mx_format_matches_fp32 keeps its max-norm check;
-                                                         a pointwise bound for its e4m3 correction terms is a separate piece of work.
 """
 import pytest
 import torch
@@ -259,7 +255,7 @@ def test_output_modes(hip_lib, gpu, form, cout):
     print(f"[conv fwd output modes {form}] worst ratio (fp32) {worst:.3f}; planes and bf16 plane bit-exact")
 
 
-# ---- the fused tail and the 1x1 chain ------------------------------------------------------------------------------------------------
+# ---- the fused tail --------------------------------------------------------------------------------------------------------------
 def _tail_pack(gpu, tail_cout, seed=0):
     key = ("tail", tail_cout, seed)
     if key not in _CACHE:
@@ -305,25 +301,6 @@ def test_fused_tail(hip_lib, gpu, request, taps, cin, addend, bm256, bm, tail_co
     inner = c["inner"]
     worst = C.check(name, body[:c["rows"]][inner], ref[inner], bound[inner])
     print(f"[conv fwd tail {name}] tiles={tiles} worst ratio {worst:.4f}")
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("rows", [330, 100])
-@pytest.mark.parametrize("cout_pad", [16, 128, 144])
-def test_conv1x1_chain(hip_lib, gpu, cout_pad, rows):
-    """magnet_conv1x1_chain on planes: bound0 = 0 (the planes ARE the input)."""
-    from magnet_amd import lib
-    from magnet_amd.convnet import split_bf16
-    t = _tail_pack(gpu, cout_pad)
-    hi, lo = split_bf16(_heavy((rows, 128), 60 + rows).abs().to(gpu))
-    a0 = C.join(hi, lo)
-    ref, bound = C.tail_ref(a0, torch.zeros_like(a0), t["w64"], t["bias"], cout_pad)
-    buf, body = _guarded((rows + EXTRA, cout_pad), gpu)
-    lib.conv1x1_chain(hi, lo, t["wh"], t["wl"], t["bias"], body, rows, cout_pad)
-    torch.cuda.synchronize()
-    _assert_untouched(f"chain {cout_pad}", buf, body, 0, cout_pad, rows)
-    worst = C.check(f"chain {cout_pad} rows {rows}", body[:rows], ref, bound)
-    print(f"[conv fwd chain cout_pad={cout_pad} rows={rows}] worst ratio {worst:.4f}")
 
 
 # ---- addend + residual: rejected ----------------------------------------------------------------------------------------------------

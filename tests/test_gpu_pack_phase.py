@@ -7,7 +7,7 @@ the call does not own (border rows, the other channels) still holds the sentinel
 
 The other formats share that decode, and their own tests never reach a wide launch with several channel groups, so each runs at the
 same shapes where its entry point accepts them, against the restatement its own test uses: magnet_pack_f16 against the numpy fp16
-saturation (tests/test_conv_precision_host.py), magnet_pack_mx against convnet.split_mx (C a multiple of 32: not ragged-C72),
+saturation (tests/test_conv_precision_host.py),
 magnet_pack_features against permute + .to(bfloat16) (ctot = C, c_off = 0, dense input, pad 0 and 1; the border of pad 1 is zero).
 Their destinations lie between guard bands of the sentinel."""
 import numpy as np
@@ -83,31 +83,6 @@ def test_pack_f16_row_dense(hip_lib, gpu, request, N, Cn, h, w, ctot, c_off, str
     exp[:, 1:-1, 1:-1, c_off:c_off + Cn] = f16_sat_bits(x.permute(0, 2, 3, 1).cpu().numpy())      # Cn % 8 == 0: no round-up lanes
     assert_f16_bits_equal(name, bits(body), exp)                       # interior rows, border rows and the other channels
     _assert_guards(name, buf, SENT)
-
-
-@pytest.mark.parametrize("N,Cn,h,w,ctot,c_off,strided", [p[1:] for p in PACK if p[2] % 32 == 0], ids=[p[0] for p in PACK if p[2] % 32 == 0])
-def test_pack_mx_row_dense(hip_lib, gpu, request, N, Cn, h, w, ctot, c_off, strided):
-    from magnet_amd import lib
-    from magnet_amd.convnet import split_mx
-    name = request.node.callspec.id
-    x = _source(gpu, N, Cn, h, w, strided)
-    rows = N * (h + 2) * (w + 2)
-    fills = (SENT, int(torch.tensor(SENT, dtype=torch.float16).view(torch.int16)), -7)             # the qr container holds the fp16 pattern of -7
-    shapes = ((N, h + 2, w + 2, ctot), (N, h + 2, w + 2, ctot), (ctot // 32, N, h + 2, w + 2))
-    dtypes = (torch.float16, torch.int16, torch.int32)
-    bufs, bodies = zip(*(C.guarded(sh, gpu, dt, fl) for sh, dt, fl in zip(shapes, dtypes, fills)))
-    lib.pack_mx(x, *bodies, ctot, c_off, rows)                         # sc_rows: the buffer's rows
-    torch.cuda.synchronize()
-    hi, qr, sc = split_mx(x.permute(0, 2, 3, 1).contiguous().cpu())
-    exp = [torch.full(sh, fl, dtype=dt) for sh, dt, fl in zip(shapes, dtypes, fills)]
-    exp[0][:, 1:-1, 1:-1, c_off:c_off + Cn] = hi
-    exp[1][:, 1:-1, 1:-1, c_off:c_off + Cn] = qr
-    exp[2][c_off // 32:(c_off + Cn) // 32, :, 1:-1, 1:-1] = sc.permute(3, 0, 1, 2)
-    for what, got, e, buf, fl in zip(("f16", "qr", "sc"), bodies, exp, bufs, fills):
-        got = got.cpu()
-        same = got.view(torch.int16) == e.view(torch.int16) if what == "f16" else got == e
-        assert bool(same.all()), f"{name}: {what} differs at {int((~same).sum())} elements, first {(~same).nonzero()[0].tolist()}"
-        _assert_guards(f"{name} {what}", buf, fl)
 
 
 FEATURES = [p for p in PACK if not p[7]]                              # ctot = C, c_off = 0, dense input: the strided row drops out

@@ -1,6 +1,6 @@
-"""What magnet_pack_features, magnet_pack_split, magnet_pack_f16 and magnet_pack_mx refuse, with which MAGNET_E_* code and which
+"""What magnet_pack_features, magnet_pack_split and magnet_pack_f16 refuse, with which MAGNET_E_* code and which
 message, is part of their contract: every case of tests/golden/pack_refusals.json (recorded by tests/golden/make_pack_refusals.py from
-the library before the packs' checks were stated once: every fail(...) site of the four entry points, each of its conditions, and the
+the library before the packs' checks were stated once: every fail(...) site of the three entry points, each of its conditions, and the
 two-violation cases that pin the order of the checks) is replayed against the current library: equal codes, equal bytes.  No GPU
 needed, and none wanted: the argument sets hold fake pointers, so the test skips itself where a device is visible."""
 import importlib.util
@@ -28,7 +28,7 @@ def test_every_recorded_pack_refusal_is_refused_alike(hip_lib):
     gen = _generator()
     with open(os.path.join(GOLDEN, "pack_refusals.json")) as f:
         cases = json.load(f)["cases"]
-    assert len(cases) == 86 and {c["entry"] for c in cases} == set(gen.BASES)
+    assert len(cases) == 60 and {c["entry"] for c in cases} == set(gen.BASES)
     recorded = {(c["entry"], c["name"]) for c in cases}
     for entry, own in gen.CASES.items():                              # the file is the generator's: every case that is not a "maybe" is in it
         assert all((entry, name) in recorded for name, _, *maybe in own if not maybe), entry

@@ -101,7 +101,7 @@ def test_splitk_argument_errors_are_codes(hip_lib):
     both(x, 2, lib.E_DIM)
     x = _valid(); x.base.rows = 0
     both(x, 2, lib.E_DIM)
-    for field in ("tail_w_hi", "addend", "add_hi", "add_lo", "in_sc", "w_sc", "up_out", "gu_in"):
+    for field in ("tail_w_hi", "addend", "add_hi", "add_lo", "up_out", "gu_in"):
         x = _valid(); setattr(x.base, field, 16)
         both(x, 2, lib.E_DIM, b"plain bf16x3 layer only")
     for tiling in (lib.TILING_BM64, lib.TILING_BM256, 8):
@@ -132,7 +132,7 @@ def test_splitk_argument_errors_are_codes(hip_lib):
 def test_lib_conv_mfma_refuses_split_k_with_other_forms():
     t = torch.zeros(1)
     base = dict(in_hi=t, in_lo=t, in_ld=64, cin=64, w_hi=t, w_lo=t, bias=t, taps=9, wp=10, relu=False, rows=100, out_f32=t)
-    for kw in (dict(f16=True), dict(f16="plane"), dict(tail=(t, t, t, 16)), dict(addend=t), dict(add=(t, t, 128)), dict(mx=(t, t, 100))):
+    for kw in (dict(f16=True), dict(f16="plane"), dict(tail=(t, t, t, 16)), dict(addend=t), dict(add=(t, t, 128))):
         with pytest.raises(lib.MagnetError, match="split_k"):
             lib.conv_mfma(**base, split_k=2, work=t, **kw)
     with pytest.raises(lib.MagnetError, match="work"):

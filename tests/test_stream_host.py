@@ -20,7 +20,7 @@ def test_abi_grows_by_scatter_frames(hip_lib):
     assert "magnet_scatter_frames" in lib.API_SYMBOLS
     text = open(HEADER).read()
     assert re.search(r"MAGNET_API int magnet_scatter_frames\(const MagnetScatterFramesArgs \*args, void \*stream\);", text)
-    assert re.search(r"#define MAGNET_HIP_VERSION 400\b", text)
+    assert re.search(r"#define MAGNET_HIP_VERSION 500\b", text)
     assert hasattr(hip_lib, "magnet_scatter_frames")
     assert lib.API_SYMBOLS.index("magnet_scatter_frames") == lib.API_SYMBOLS.index("magnet_gather_views") + 1
 

@@ -25,7 +25,7 @@ def test_exports_are_declared_and_bound(hip_lib):
         assert hasattr(hip_lib, name), name
     syms = list(lib.API_SYMBOLS)
     assert syms.index(NEW[-1]) + 1 == syms.index("magnet_dnet_loss_workspace")            # in front of the D-Net loss entries
-    assert int(re.search(r"#define\s+MAGNET_HIP_VERSION\s+(\d+)", hdr).group(1)) == 400 == hip_lib.magnet_version()
+    assert int(re.search(r"#define\s+MAGNET_HIP_VERSION\s+(\d+)", hdr).group(1)) == 500 == hip_lib.magnet_version()
 
 
 def _fwd_args():

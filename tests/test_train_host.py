@@ -47,7 +47,7 @@ def test_new_entry_points_declared_and_exported(hip_lib):
     declared = set(re.findall(r"MAGNET_API\s+[\w\s\*]+?\b(magnet_\w+)\s*\(", src))
     for s in NEW:
         assert s in declared and s in lib.API_SYMBOLS and hasattr(hip_lib, s), s
-    assert hip_lib.magnet_version() == 400
+    assert hip_lib.magnet_version() == 500
 
 
 def test_new_entry_points_return_null_codes(hip_lib):
