@@ -112,15 +112,20 @@ def main():
     ap.add_argument("--encoder", default="standin", choices=["standin", "b5"],
                     help="'standin' (default): the seeded stand-in encoder; 'b5': the EfficientNet-B5 encoder (magnet_amd/encoder.py), calibrated seeded weights")
     ap.add_argument("--encoder_backend", default="torch", choices=["torch", "hip"], help="with --encoder b5: run the encoder's torch modules or EncoderMFMA")
+    ap.add_argument("--encoder_precision", default="bf16x3", choices=["bf16x3", "fp16"],
+                    help="with --encoder b5 --encoder_backend hip: EncoderMFMA's format; fp16 = one fp16 plane per activation grid, reduced "
+                         "precision, |activation| <= 65504 or clamped")
     E.add_arguments(ap)
     a = ap.parse_args()
     if a.encoder_backend == "hip" and a.encoder != "b5":
         ap.error("--encoder_backend hip is a mode of --encoder b5")
+    if a.encoder_precision != "bf16x3" and not (a.encoder == "b5" and a.encoder_backend == "hip"):
+        ap.error("--encoder_precision fp16 is a mode of --encoder b5 --encoder_backend hip")
     rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.standin import make_dnet
     args = argparse.Namespace(min_depth=a.min_depth, max_depth=a.max_depth, garg_crop=a.garg_crop, eigen_crop=a.eigen_crop)
     model = make_dnet(dnet=True, backend=a.backend, split_k="auto" if a.split_k == "auto" else 0, precision=a.precision,
-                      encoder=a.encoder, encoder_backend=a.encoder_backend).to(device).eval()    # seeded weights unless the caller loads a checkpoint
+                      encoder=a.encoder, encoder_backend=a.encoder_backend, encoder_precision=a.encoder_precision).to(device).eval()    # seeded weights unless the caller loads a checkpoint
     if a.dataset_path:
         from magnet_amd import data
         with open(a.split) as f:

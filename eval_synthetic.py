@@ -150,10 +150,15 @@ def main():
                     help="the D-Net: 'standin' (default) is the seeded stub D-Net; 'b5' is the DenseDepth D-Net on the HIP decoder path behind "
                          "the EfficientNet-B5 encoder (magnet_amd/encoder.py), seeded weights unless a checkpoint is loaded by the caller")
     ap.add_argument("--encoder_backend", default="torch", choices=["torch", "hip"], help="with --encoder b5: run the encoder's torch modules or EncoderMFMA")
+    ap.add_argument("--encoder_precision", default="bf16x3", choices=["bf16x3", "fp16"],
+                    help="with --encoder b5 --encoder_backend hip: EncoderMFMA's format; fp16 = one fp16 plane per activation grid, reduced "
+                         "precision, |activation| <= 65504 or clamped")
     E.add_arguments(ap)
     a = ap.parse_args()
     if a.encoder_backend == "hip" and a.encoder != "b5":
         ap.error("--encoder_backend hip is a mode of --encoder b5")
+    if a.encoder_precision != "bf16x3" and not (a.encoder == "b5" and a.encoder_backend == "hip"):
+        ap.error("--encoder_precision fp16 is a mode of --encoder b5 --encoder_backend hip")
     if a.graph and not a.reuse_backbones:
         ap.error("--graph is a mode of --reuse_backbones (SequenceRunner(graph=True)): give both")
     if a.reuse_backbones and not a.dataset_path:
@@ -170,7 +175,8 @@ def main():
         f_net = FNET(args)                                   # random init unless a checkpoint is loaded by the caller
     if a.encoder == "b5":
         from magnet_amd.standin import make_dnet
-        model = MAGNET(args, d_net=make_dnet(backend="hip", encoder="b5", encoder_backend=a.encoder_backend), f_net=f_net,
+        model = MAGNET(args, d_net=make_dnet(backend="hip", encoder="b5", encoder_backend=a.encoder_backend, encoder_precision=a.encoder_precision),
+                       f_net=f_net,
                        feat_dtype=a.feat_dtype, dnet_backend="hip")
     else:
         model = MAGNET(args, d_net=StubDNet(1), f_net=f_net, feat_dtype=a.feat_dtype)

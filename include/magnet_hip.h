@@ -49,7 +49,9 @@ extern "C" {
                                            * magnet_amd/lib.py mirrors the structs field for field and tests/test_abi.py compares the layouts with a gcc probe).
                                            * From v400 on a struct change bumps the MINOR number, never only the patch.
                                            * v500 REMOVED the v302 fp16 + block-scaled e4m3 operand format (the last three fields of MagnetConvArgs and its
-                                           * pack entry point) and magnet_conv1x1_chain: MagnetConvArgs, and with it every struct that embeds it, is shorter. */
+                                           * pack entry point) and magnet_conv1x1_chain: MagnetConvArgs, and with it every struct that embeds it, is shorter.
+                                           * Added since, with no struct change and therefore under the same number: magnet_conv_mfma_f16e,
+                                           * magnet_enc_stem_f16, magnet_dwconv_cl_f16, magnet_se_scale_f16 (the encoder's fp16 single-plane mode). */
 
 enum {                                     /* storage dtype of channel-last feature maps */
     MAGNET_FEAT_F32  = 0,
@@ -691,6 +693,22 @@ MAGNET_API int magnet_conv_mfma_f16d(const MagnetConvExArgs *args, void *stream)
 MAGNET_API int64_t magnet_conv_mfma_f16d_splitk_workspace(const MagnetConvExArgs *args, int32_t split_k);
 MAGNET_API int magnet_conv_mfma_f16d_splitk(const MagnetConvExArgs *args, int32_t split_k, float *work, int64_t work_bytes, void *stream);
 
+/* The single-plane fp16 format, plane to plane, for the 1x1 layers of the EfficientNet encoder (EncoderMFMA(precision="fp16")): what
+ * magnet_conv_mfma_f16p refuses (SiLU) and what magnet_conv_mfma_f16d refuses (SiLU, a residual input), on the kernel instances of those
+ * two — it adds no kernel.  The struct's fields mean, for this entry point only:
+ *   base.in_hi / base.w_hi   fp16 planes (rows, in_ld) / (1, cout_pad, cin); base.in_lo, w_lo and add_lo must be NULL
+ *   base.add_hi              optional residual input: ONE fp16 plane (rows, add_ld), added before the bias
+ *   act                      MAGNET_ACT_BASE with base.relu == 0 (a linear layer), or MAGNET_ACT_SILU
+ *   base.out_mode            3: one fp16 plane at out_hi (saturating round-to-nearest-even, NaN written through); 1: fp32 at out_f32
+ *   border_hp / border_pad / repad / in_ld / out_ld   as in magnet_conv_mfma
+ * Serves taps == 1, cout_pad 32, 64 or a multiple of 128, cin a multiple of 32, tiling 0 or MAGNET_TILING_FLAT; tiles_out works.  A fused
+ * tail, an addend, the Gaussian update / upsampling, MAGNET_TILING_BM64 / MAGNET_TILING_BM256, every other value of taps, act and
+ * out_mode, any other cout_pad (144 included: issue such a layer as launches on channel slices, out_ld) and relu == 1 are refused with
+ * MAGNET_E_DIM before any launch; a refused call writes nothing.  With MAGNET_ACT_BASE the result equals, to the bit, what
+ * magnet_conv_mfma_f16p (cout_pad 32 / 64) or magnet_conv_mfma_f16d (cout_pad % 128 == 0, no residual) writes.  Domain: |activation|,
+ * |weight| <= 65504 (stores clamp; the caller rounds its weights). */
+MAGNET_API int magnet_conv_mfma_f16e(const MagnetConvExArgs *args, void *stream);
+
 /* fp32 NCHW (N, C, h, w) (image stride `in_img_stride` elements, 0 = C*h*w) -> channels [c_off, c_off + round_up(C, 8)) of the interior
  * of a zero-bordered (N, h+2, w+2, ctot) fp16 plane (the round-up lanes are written as zeros, as by magnet_pack_split).  ctot and c_off
  * multiples of 8.  The border rows and every other channel are not written.  Conversion: see the single-plane fp16 format above. */
@@ -789,6 +807,22 @@ MAGNET_API int magnet_se_gate(const float *part, int32_t n_part, int64_t hw, con
 /* out = split(float(hi + lo) * gate[n][c]) over the interior of a grid (N, h+2, w+2, .), channels [0, c_pad); out may be the input. */
 MAGNET_API int magnet_se_scale(const void *in_hi, const void *in_lo, int32_t in_ld, const float *gate, int32_t N, int32_t h, int32_t w,
                                int32_t c_pad, void *out_hi, void *out_lo, int32_t out_ld, void *stream);
+
+/* The same three layers on the single-plane fp16 format (EncoderMFMA(precision="fp16")): every grid is ONE zero-bordered channel-last
+ * fp16 plane where the entry points above take a (hi, lo) pair.  Same geometry, tiling, fp32 arithmetic and order; a value is read
+ * exactly (fp16 -> fp32) and stored as magnet_pack_f16 stores it (saturating round-to-nearest-even: the stored value is within 2^-11
+ * of the fp32 value, relative, inside the domain |x| <= 65504).  The depthwise partial sums are taken from the fp32 values BEFORE the
+ * store, so magnet_se_gate is used unchanged and the squeeze mean does not see the fp16 rounding.
+ *   magnet_enc_stem_f16    out_f16 (N, H2+2, W2+2, 64)
+ *   magnet_dwconv_cl_f16   MagnetDwConvArgs with in_hi / out_hi the fp16 planes; in_lo and out_lo must be NULL (MAGNET_E_DIM otherwise:
+ *                          planes of the other format are refused, not mis-read)
+ *   magnet_se_scale_f16    out = f16(float(in) * gate[n][c]); out may be the input
+ * Refusals and error codes are those of the (hi, lo) forms, under these names. */
+MAGNET_API int magnet_enc_stem_f16(const float *img, const float *wgt, const float *bias, void *out_f16, int32_t N, int32_t H, int32_t W,
+                                   void *stream);
+MAGNET_API int magnet_dwconv_cl_f16(const MagnetDwConvArgs *args, void *stream);
+MAGNET_API int magnet_se_scale_f16(const void *in_f16, int32_t in_ld, const float *gate, int32_t N, int32_t h, int32_t w, int32_t c_pad,
+                                   void *out_f16, int32_t out_ld, void *stream);
 
 /* Sequence inference (magnet_amd/sequence.py): a frame pool of n_slots slots keeps one frame's backbone outputs per slot, in the
  * layouts the kernels read:

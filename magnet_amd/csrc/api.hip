@@ -311,7 +311,7 @@ MAGNET_API int magnet_upsample_depth(const float* depth, const float* mask, floa
 // Every convolution entry point ends here: the checks of the common fields, then the launch on `mode` (magnet::ConvRoute, conv_common.hpp).
 // leaky: 1 selects LeakyReLU(leaky_slope) after bias, 2 SiLU (validated by the entry point)
 // split_k >= 2 (the split-K entry points, which have checked what that form serves): the split-K launches with workspace `work`; else 0
-using magnet::ConvRoute; using magnet::CONV_BF16X3; using magnet::CONV_F16; using magnet::CONV_F16P; using magnet::CONV_F16D;
+using magnet::ConvRoute; using magnet::CONV_BF16X3; using magnet::CONV_F16; using magnet::CONV_F16P; using magnet::CONV_F16D; using magnet::CONV_F16E;
 // src / src_c0 (magnet_conv_mfma_nchw, which has checked them): input channels [src_c0, cin) come from the NCHW fp32 tensor `src`
 static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, float leaky_slope, int tiling, int64_t* tiles_out, int split_k, float* work,
                          void* stream, const float* src = nullptr, int src_c0 = 0) {
@@ -319,6 +319,9 @@ static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, flo
     const bool f16 = mode != CONV_BF16X3;
     const bool planes = !src || src_c0 > 0;                          // the launch reads the activation planes
     if ((planes && (!a->in_hi || (!f16 && !a->in_lo))) || !a->w_hi || (!f16 && !a->w_lo) || !a->bias) return fail(MAGNET_E_NULL, "magnet_conv_mfma: NULL input pointer");
+    if (mode == CONV_F16E) {
+        if (a->out_mode != 1 && a->out_mode != 3) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16e: out_mode must be 1 or 3");
+    } else
     if (mode == CONV_F16D) {
         if (a->out_mode != 0 && a->out_mode != 1 && a->out_mode != 3) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16d: out_mode must be 0, 1 or 3");
     } else
@@ -369,7 +372,7 @@ static int conv_mfma_run(const MagnetConvArgs* a, ConvRoute mode, int leaky, flo
     p.out_ld = a->out_ld ? a->out_ld : a->cout_pad;
     if (p.out_ld < a->cout_pad || (p.out_ld % 8) != 0) return fail(MAGNET_E_DIM, "magnet_conv_mfma: out_ld=%d must be >= cout_pad and a multiple of 8", p.out_ld);
     p.add_hi = (const uint16_t*)a->add_hi; p.add_lo = (const uint16_t*)a->add_lo; p.add_ld = a->add_ld ? a->add_ld : a->cout_pad;
-    if (mode != CONV_F16P && (a->add_hi != nullptr) != (a->add_lo != nullptr)) return fail(MAGNET_E_NULL, "magnet_conv_mfma: add_hi and add_lo come together");
+    if (mode != CONV_F16P && mode != CONV_F16E && (a->add_hi != nullptr) != (a->add_lo != nullptr)) return fail(MAGNET_E_NULL, "magnet_conv_mfma: add_hi and add_lo come together");
     if (a->add_hi && (!aligned16(a->add_hi) || !aligned16(a->add_lo) || (p.add_ld % 8) != 0 || p.add_ld < a->cout_pad))
         return fail(MAGNET_E_ALIGN, "magnet_conv_mfma: add_hi/add_lo must be 16-byte aligned with add_ld >= cout_pad, a multiple of 8");
     // the epilogue holds ONE pre-bias term per channel: with both, the addend would replace the residual (no caller passes both)
@@ -529,6 +532,23 @@ MAGNET_API int magnet_conv_mfma_f16p(const MagnetConvExArgs* a, void* stream) {
     if (const int rc = conv_plain_check(a, "magnet_conv_mfma_f16p", "fp16", false)) return rc;
     if (b.cout_pad != 32 && b.cout_pad != 64 && b.cout_pad != 128) return fail(MAGNET_E_DIM, "magnet_conv_mfma_f16p: cout_pad=%d (32, 64 or 128)", b.cout_pad);
     return conv_mfma_run(a, CONV_F16P, 0, nullptr, stream);
+}
+
+// The EfficientNet encoder's 1x1 layers on fp16 planes: what magnet_conv_mfma_f16p (no SiLU) and magnet_conv_mfma_f16d (no SiLU, no
+// residual) refuse, on their kernel instances.  Every refusal of the form is made here, under this entry point's name
+MAGNET_API int magnet_conv_mfma_f16e(const MagnetConvExArgs* a, void* stream) {
+    const char* who = "magnet_conv_mfma_f16e";
+    if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
+    const MagnetConvArgs& b = a->base;
+    if (const int rc = conv_f16_planes_check(b, who, 1)) return rc;
+    if (a->act != MAGNET_ACT_BASE && a->act != MAGNET_ACT_SILU) return fail(MAGNET_E_DIM, "%s: act=%d (MAGNET_ACT_BASE or MAGNET_ACT_SILU)", who, a->act);
+    if (b.relu) return fail(MAGNET_E_DIM, "%s: relu=%d (no ReLU: the layers are linear or SiLU)", who, b.relu);
+    if (const int rc = conv_plain_check(a, who, "fp16", false)) return rc;
+    if (b.taps != 1 || b.dil > 1) return fail(MAGNET_E_DIM, "%s: taps=%d dil=%d (1x1 layers only: taps == 1, no dilation)", who, b.taps, b.dil);
+    if (b.cout_pad != 32 && b.cout_pad != 64 && (b.cout_pad <= 0 || b.cout_pad % 128 != 0))
+        return fail(MAGNET_E_DIM, "%s: cout_pad=%d (32, 64 or a multiple of 128)", who, b.cout_pad);
+    if (b.out_mode != 1 && b.out_mode != 3) return fail(MAGNET_E_DIM, "%s: out_mode=%d (3: one fp16 plane, 1: fp32)", who, b.out_mode);
+    return conv_mfma_run(a, CONV_F16E, 0, nullptr, stream);
 }
 
 // What magnet_conv_mfma_f16d and its split-K form serve (`who`), before conv_mfma_run's checks of the common fields
@@ -1195,44 +1215,58 @@ MAGNET_API int magnet_scatter_frames(const MagnetScatterFramesArgs* a, void* str
 }
 
 // ---- the D-Net's encoder (enc_kernels.hip) ----
+// Each of the stem, the depthwise convolution and the scale has two entry points (`who`): the (hi, lo) form and the `_f16` form on ONE
+// fp16 plane per grid (f16: the lo pointers do not exist there).  The checks are stated once.
+static int enc_stem_run(const char* who, bool f16, const float* img, const float* wgt, const float* bias, void* out_hi, void* out_lo, int32_t N,
+                        int32_t H, int32_t W, void* stream) {
+    if (!img || !wgt || !bias || !out_hi || (!f16 && !out_lo)) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (N <= 0 || H < 2 || W < 2 || (int64_t)N * ((H + 1) / 2 + 2) * ((W + 1) / 2 + 2) >= ((int64_t)1 << 31))
+        return fail(MAGNET_E_DIM, "%s: bad dims N=%d H=%d W=%d", who, N, H, W);
+    if (!aligned16(out_hi) || !aligned16(out_lo)) return fail(MAGNET_E_ALIGN, "%s: outputs not 16-byte aligned", who);
+    const hipError_t e = magnet::launch_enc_stem(img, wgt, bias, (uint16_t*)out_hi, (uint16_t*)out_lo, N, H, W, f16, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, f16 ? "magnet_enc_stem_f16 launch" : "magnet_enc_stem launch");
+}
+
 MAGNET_API int magnet_enc_stem(const float* img, const float* wgt, const float* bias, void* out_hi, void* out_lo, int32_t N, int32_t H, int32_t W,
                                void* stream) {
-    if (!img || !wgt || !bias || !out_hi || !out_lo) return fail(MAGNET_E_NULL, "magnet_enc_stem: NULL pointer");
-    if (N <= 0 || H < 2 || W < 2 || (int64_t)N * ((H + 1) / 2 + 2) * ((W + 1) / 2 + 2) >= ((int64_t)1 << 31))
-        return fail(MAGNET_E_DIM, "magnet_enc_stem: bad dims N=%d H=%d W=%d", N, H, W);
-    if (!aligned16(out_hi) || !aligned16(out_lo)) return fail(MAGNET_E_ALIGN, "magnet_enc_stem: outputs not 16-byte aligned");
-    const hipError_t e = magnet::launch_enc_stem(img, wgt, bias, (uint16_t*)out_hi, (uint16_t*)out_lo, N, H, W, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "magnet_enc_stem launch");
+    return enc_stem_run("magnet_enc_stem", false, img, wgt, bias, out_hi, out_lo, N, H, W, stream);
+}
+MAGNET_API int magnet_enc_stem_f16(const float* img, const float* wgt, const float* bias, void* out_f16, int32_t N, int32_t H, int32_t W, void* stream) {
+    return enc_stem_run("magnet_enc_stem_f16", true, img, wgt, bias, out_f16, nullptr, N, H, W, stream);
 }
 
 MAGNET_API int64_t magnet_dwconv_cl_parts(int32_t ho, int32_t wo) { return (ho <= 0 || wo <= 0) ? 0 : (int64_t)magnet::enc_dw_parts(ho, wo); }
 
-MAGNET_API int magnet_dwconv_cl(const MagnetDwConvArgs* a, void* stream) {
-    if (!a) return fail(MAGNET_E_NULL, "magnet_dwconv_cl: args is NULL");
-    if (!a->in_hi || !a->in_lo || !a->wgt || !a->bias || !a->out_hi || !a->out_lo || !a->part) return fail(MAGNET_E_NULL, "magnet_dwconv_cl: NULL pointer");
-    if (a->k != 3 && a->k != 5) return fail(MAGNET_E_DIM, "magnet_dwconv_cl: k=%d (3 or 5)", a->k);
-    if (a->stride != 1 && a->stride != 2) return fail(MAGNET_E_DIM, "magnet_dwconv_cl: stride=%d (1 or 2)", a->stride);
+static int dwconv_cl_run(const char* who, bool f16, const MagnetDwConvArgs* a, void* stream) {
+    if (!a) return fail(MAGNET_E_NULL, "%s: args is NULL", who);
+    if (!a->in_hi || (!f16 && !a->in_lo) || !a->wgt || !a->bias || !a->out_hi || (!f16 && !a->out_lo) || !a->part) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (f16 && (a->in_lo || a->out_lo)) return fail(MAGNET_E_DIM, "%s: in_lo and out_lo must be NULL (every grid is ONE fp16 plane)", who);
+    if (a->k != 3 && a->k != 5) return fail(MAGNET_E_DIM, "%s: k=%d (3 or 5)", who, a->k);
+    if (a->stride != 1 && a->stride != 2) return fail(MAGNET_E_DIM, "%s: stride=%d (1 or 2)", who, a->stride);
     if (a->N <= 0 || a->N > 65535 || a->h <= 0 || a->w <= 0 || a->c_pad <= 0 || (a->c_pad % 32) != 0)
-        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: bad dims N=%d h=%d w=%d c_pad=%d (c_pad %% 32 == 0, N <= 65535)", a->N, a->h, a->w, a->c_pad);
+        return fail(MAGNET_E_DIM, "%s: bad dims N=%d h=%d w=%d c_pad=%d (c_pad %% 32 == 0, N <= 65535)", who, a->N, a->h, a->w, a->c_pad);
     if (a->in_ld < a->c_pad || (a->in_ld % 8) != 0 || a->out_ld < a->c_pad || (a->out_ld % 8) != 0)
-        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: in_ld=%d / out_ld=%d must be >= c_pad and multiples of 8", a->in_ld, a->out_ld);
+        return fail(MAGNET_E_DIM, "%s: in_ld=%d / out_ld=%d must be >= c_pad and multiples of 8", who, a->in_ld, a->out_ld);
     if (a->pad_top < 0 || a->pad_top >= a->k || a->pad_left < 0 || a->pad_left >= a->k)
-        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: pad_top=%d pad_left=%d outside [0, k)", a->pad_top, a->pad_left);
+        return fail(MAGNET_E_DIM, "%s: pad_top=%d pad_left=%d outside [0, k)", who, a->pad_top, a->pad_left);
     const int ho = (a->h + a->stride - 1) / a->stride, wo = (a->w + a->stride - 1) / a->stride;
-    if ((int64_t)a->N * (a->h + 2) * (a->w + 2) >= ((int64_t)1 << 31)) return fail(MAGNET_E_DIM, "magnet_dwconv_cl: N (h+2) (w+2) must be < 2^31");
+    if ((int64_t)a->N * (a->h + 2) * (a->w + 2) >= ((int64_t)1 << 31)) return fail(MAGNET_E_DIM, "%s: N (h+2) (w+2) must be < 2^31", who);
     if (a->n_part != magnet::enc_dw_parts(ho, wo))
-        return fail(MAGNET_E_DIM, "magnet_dwconv_cl: n_part=%d, expected magnet_dwconv_cl_parts(%d, %d) = %lld", a->n_part, ho, wo, magnet::enc_dw_parts(ho, wo));
+        return fail(MAGNET_E_DIM, "%s: n_part=%d, expected magnet_dwconv_cl_parts(%d, %d) = %lld", who, a->n_part, ho, wo, magnet::enc_dw_parts(ho, wo));
     if (!aligned16(a->in_hi) || !aligned16(a->in_lo) || !aligned16(a->out_hi) || !aligned16(a->out_lo) || !aligned16(a->wgt) || !aligned16(a->bias))
-        return fail(MAGNET_E_ALIGN, "magnet_dwconv_cl: planes, wgt and bias must be 16-byte aligned");
-    if ((uintptr_t)a->part & 3) return fail(MAGNET_E_ALIGN, "magnet_dwconv_cl: part must be 4-byte aligned");
+        return fail(MAGNET_E_ALIGN, "%s: planes, wgt and bias must be 16-byte aligned", who);
+    if ((uintptr_t)a->part & 3) return fail(MAGNET_E_ALIGN, "%s: part must be 4-byte aligned", who);
     magnet::EncDwParams p;
     memset(&p, 0, sizeof(p));
     p.in_hi = (const uint16_t*)a->in_hi; p.in_lo = (const uint16_t*)a->in_lo; p.in_ld = a->in_ld; p.hi = a->h; p.wi = a->w; p.c_pad = a->c_pad;
     p.wgt = a->wgt; p.bias = a->bias; p.k = a->k; p.stride = a->stride; p.pad_top = a->pad_top; p.pad_left = a->pad_left;
     p.out_hi = (uint16_t*)a->out_hi; p.out_lo = (uint16_t*)a->out_lo; p.out_ld = a->out_ld; p.ho = ho; p.wo = wo; p.part = a->part;
-    const hipError_t e = magnet::launch_enc_dwconv(p, a->N, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "magnet_dwconv_cl launch");
+    const hipError_t e = magnet::launch_enc_dwconv(p, a->N, f16, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, f16 ? "magnet_dwconv_cl_f16 launch" : "magnet_dwconv_cl launch");
 }
+
+MAGNET_API int magnet_dwconv_cl(const MagnetDwConvArgs* a, void* stream) { return dwconv_cl_run("magnet_dwconv_cl", false, a, stream); }
+MAGNET_API int magnet_dwconv_cl_f16(const MagnetDwConvArgs* a, void* stream) { return dwconv_cl_run("magnet_dwconv_cl_f16", true, a, stream); }
 
 MAGNET_API int magnet_se_gate(const float* part, int32_t n_part, int64_t hw, const float* w_reduce, const float* b_reduce, const float* w_expand_t,
                               const float* b_expand, int32_t C, int32_t R, int32_t c_pad, float* gate, int32_t N, void* stream) {
@@ -1245,18 +1279,27 @@ MAGNET_API int magnet_se_gate(const float* part, int32_t n_part, int64_t hw, con
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_se_gate launch");
 }
 
-MAGNET_API int magnet_se_scale(const void* in_hi, const void* in_lo, int32_t in_ld, const float* gate, int32_t N, int32_t h, int32_t w, int32_t c_pad,
-                               void* out_hi, void* out_lo, int32_t out_ld, void* stream) {
-    if (!in_hi || !in_lo || !gate || !out_hi || !out_lo) return fail(MAGNET_E_NULL, "magnet_se_scale: NULL pointer");
+static int se_scale_run(const char* who, bool f16, const void* in_hi, const void* in_lo, int32_t in_ld, const float* gate, int32_t N, int32_t h, int32_t w,
+                        int32_t c_pad, void* out_hi, void* out_lo, int32_t out_ld, void* stream) {
+    if (!in_hi || (!f16 && !in_lo) || !gate || !out_hi || (!f16 && !out_lo)) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
     if (N <= 0 || h <= 0 || w <= 0 || c_pad <= 0 || (c_pad % 32) != 0 || in_ld < c_pad || (in_ld % 8) != 0 || out_ld < c_pad || (out_ld % 8) != 0 ||
         (int64_t)N * (h + 2) * (w + 2) >= ((int64_t)1 << 31))
-        return fail(MAGNET_E_DIM, "magnet_se_scale: bad dims N=%d h=%d w=%d c_pad=%d in_ld=%d out_ld=%d (c_pad %% 32 == 0; pitches >= c_pad, multiples of 8)", N, h,
+        return fail(MAGNET_E_DIM, "%s: bad dims N=%d h=%d w=%d c_pad=%d in_ld=%d out_ld=%d (c_pad %% 32 == 0; pitches >= c_pad, multiples of 8)", who, N, h,
                     w, c_pad, in_ld, out_ld);
     if (!aligned16(in_hi) || !aligned16(in_lo) || !aligned16(out_hi) || !aligned16(out_lo) || !aligned16(gate))
-        return fail(MAGNET_E_ALIGN, "magnet_se_scale: planes and gate must be 16-byte aligned");
+        return fail(MAGNET_E_ALIGN, "%s: planes and gate must be 16-byte aligned", who);
     const hipError_t e = magnet::launch_enc_se_scale((const uint16_t*)in_hi, (const uint16_t*)in_lo, in_ld, gate, N, h, w, c_pad, (uint16_t*)out_hi,
-                                                     (uint16_t*)out_lo, out_ld, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "magnet_se_scale launch");
+                                                     (uint16_t*)out_lo, out_ld, f16, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, f16 ? "magnet_se_scale_f16 launch" : "magnet_se_scale launch");
+}
+
+MAGNET_API int magnet_se_scale(const void* in_hi, const void* in_lo, int32_t in_ld, const float* gate, int32_t N, int32_t h, int32_t w, int32_t c_pad,
+                               void* out_hi, void* out_lo, int32_t out_ld, void* stream) {
+    return se_scale_run("magnet_se_scale", false, in_hi, in_lo, in_ld, gate, N, h, w, c_pad, out_hi, out_lo, out_ld, stream);
+}
+MAGNET_API int magnet_se_scale_f16(const void* in_f16, int32_t in_ld, const float* gate, int32_t N, int32_t h, int32_t w, int32_t c_pad, void* out_f16,
+                                   int32_t out_ld, void* stream) {
+    return se_scale_run("magnet_se_scale_f16", true, in_f16, nullptr, in_ld, gate, N, h, w, c_pad, out_f16, nullptr, out_ld, stream);
 }
 
 }  // extern "C"

@@ -96,8 +96,10 @@ __device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + __builti
 // magnet_conv_mfma and magnet_conv_mfma_ex.  CONV_F16: the single-plane fp16 operand format (magnet_conv_mfma_f16, which has checked
 // what that format serves): no lo planes.  CONV_F16P: the same operands, plane to plane (magnet_conv_mfma_f16p): the residual is ONE
 // fp16 plane (add_lo NULL) and out_mode 3 (one fp16 plane at out_hi) exists.  CONV_F16D: plane to plane, wide (magnet_conv_mfma_f16d,
-// the D-Net decoder's plain layers, cout_pad % 128 == 0, LeakyReLU): no residual; out_mode 0, 1 or 3
-enum ConvRoute { CONV_BF16X3, CONV_F16, CONV_F16P, CONV_F16D };
+// the D-Net decoder's plain layers, cout_pad % 128 == 0, LeakyReLU): no residual; out_mode 0, 1 or 3.  CONV_F16E: plane to plane, the
+// EfficientNet encoder's 1x1 layers (magnet_conv_mfma_f16e): taps 1, SiLU, the fp16 residual plane, out_mode 3 or 1; cout_pad 32 / 64 on
+// CONV_F16P's windowless instances, cout_pad % 128 == 0 on CONV_F16D's — no kernel instance of its own
+enum ConvRoute { CONV_BF16X3, CONV_F16, CONV_F16P, CONV_F16D, CONV_F16E };
 
 // magnet_conv_mfma_nchw: input channels [c0, cin) of the launch are read from ptr, (up_B, cin - c0, up_h, up_w) fp32, and split to
 // (hi, lo) in LDS; the planes hold channels [0, c0) only (in_hi / in_lo may be NULL when c0 == 0).  Kernel arguments of the two

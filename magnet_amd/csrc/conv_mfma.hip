@@ -1524,6 +1524,15 @@ static hipError_t launch_conv_mfma_f16d(const ConvParams& p, hipStream_t s) {
     return p.tap_n == 3 ? launch_wide<true, 2>(p, 0, nullptr, s) : launch_wide<true, 0>(p, 0, nullptr, s);
 }
 
+// The EfficientNet encoder's 1x1 layers on fp16 planes (magnet_conv_mfma_f16e): SiLU or none, an optional fp16 residual plane, fp16 /
+// fp32 output.  No instance of its own: 32 and 64 outputs run the windowless plane-to-plane instances of launch_conv_mfma_f16p, any
+// cout_pad % 128 == 0 the wide instance of launch_conv_mfma_f16d (whose plain epilogue reads the residual and applies SiLU already)
+static hipError_t launch_conv_mfma_f16e(const ConvParams& p, hipStream_t s) {
+    if (p.cout_pad == 64)  return launch_conv_nf<4, 1, 128, 1, 0, 256, false, 0, true, true>(p, s);
+    if (p.cout_pad == 32)  return launch_conv_nf<2, 1, 128, 1, 0, 256, false, 0, true, true>(p, s);
+    return launch_wide<true, 0>(p, 0, nullptr, s);
+}
+
 // What each route's instances serve, as the API has checked it before: the launchers' own refusal of anything else
 static bool route_serves(const ConvParams& p, ConvRoute route, int S, const float* work) {
     if (S && (S < 2 || S > 8 || !work)) return false;
@@ -1534,6 +1543,7 @@ static bool route_serves(const ConvParams& p, ConvRoute route, int S, const floa
     case CONV_F16:    return !S && p.cout_pad == 128 && p.tap_n == 3;
     case CONV_F16P:   return !S && plain;
     case CONV_F16D:   return plain && !p.add_hi && wide;
+    case CONV_F16E:   return !S && plain && p.tap_n == 1 && (p.cout_pad == 32 || p.cout_pad == 64 || wide);
     }
     return false;
 }
@@ -1546,6 +1556,7 @@ hipError_t launch_conv(const ConvParams& p, ConvRoute route, int S, float* work,
     case CONV_F16:    return S ? hipErrorInvalidValue : launch_conv_mfma_f16(p, s);
     case CONV_F16P:   return S ? hipErrorInvalidValue : launch_conv_mfma_f16p(p, s);
     case CONV_F16D:   return S ? launch_splitk<true>(p, S, work, s) : launch_conv_mfma_f16d(p, s);
+    case CONV_F16E:   return S ? hipErrorInvalidValue : launch_conv_mfma_f16e(p, s);
     }
     return hipErrorInvalidValue;
 }

@@ -22,9 +22,10 @@ struct EncDwParams {
     int n_part;                                       // set by the launcher: enc_dw_parts(ho, wo)
 };
 
-hipError_t launch_enc_stem(const float*, const float*, const float*, uint16_t*, uint16_t*, int, int, int, hipStream_t);
-hipError_t launch_enc_dwconv(const EncDwParams&, int N, hipStream_t);
+// f16 (the `_f16` entry points): the grids are ONE fp16 plane each, at the hi pointers; the lo pointers are NULL and unused
+hipError_t launch_enc_stem(const float*, const float*, const float*, uint16_t*, uint16_t*, int, int, int, bool f16, hipStream_t);
+hipError_t launch_enc_dwconv(const EncDwParams&, int N, bool f16, hipStream_t);
 hipError_t launch_enc_se_gate(const float*, int, long long, const float*, const float*, const float*, const float*, int, int, int, float*, int, hipStream_t);
-hipError_t launch_enc_se_scale(const uint16_t*, const uint16_t*, int, const float*, int, int, int, int, uint16_t*, uint16_t*, int, hipStream_t);
+hipError_t launch_enc_se_scale(const uint16_t*, const uint16_t*, int, const float*, int, int, int, int, uint16_t*, uint16_t*, int, bool f16, hipStream_t);
 
 }  // namespace magnet

@@ -8,6 +8,9 @@
 // Activations are the conv kernel's format: zero-bordered channel-last grids (N, h+2, w+2, C_pad) stored as two bf16 planes
 // (hi = bf16(x), lo = bf16(x - hi)), C_pad a multiple of 32, pad channels and border rows zero.  All are HBM-bound kernels with
 // 16-byte accesses, 8 channels per thread.  No atomics anywhere: every output element has exactly one writer.
+// The stem, the depthwise convolution and the scale are templates on the storage format: F16 = ONE fp16 plane per grid (the `_f16` entry
+// points, EncoderMFMA(precision="fp16")): the same geometry, arithmetic and order; a load is one 16-byte access (f16x8_unpack, exact), a
+// store is f16x8_pack_sat (saturating round-to-nearest-even), and the lo pointers are NULL and never touched.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "enc_common.hpp"
@@ -22,7 +25,12 @@ __device__ __forceinline__ uint16_t ek_bf16(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
+template <bool F16>
 __device__ __forceinline__ void ek_store8(uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, const size_t e, const float* v) {
+    if constexpr (F16) {
+        *reinterpret_cast<uint4*>(hi + e) = f16x8_pack_sat(v);
+        return;
+    }
     uint32_t h[4], l[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -35,7 +43,12 @@ __device__ __forceinline__ void ek_store8(uint16_t* __restrict__ hi, uint16_t* _
     *reinterpret_cast<uint4*>(hi + e) = make_uint4(h[0], h[1], h[2], h[3]);
     *reinterpret_cast<uint4*>(lo + e) = make_uint4(l[0], l[1], l[2], l[3]);
 }
+template <bool F16>
 __device__ __forceinline__ void ek_load8(const uint16_t* __restrict__ hi, const uint16_t* __restrict__ lo, const size_t e, float* v) {
+    if constexpr (F16) {
+        f16x8_unpack(*reinterpret_cast<const uint4*>(hi + e), v);
+        return;
+    }
     const uint4 a = *reinterpret_cast<const uint4*>(hi + e), b = *reinterpret_cast<const uint4*>(lo + e);
     const uint32_t h[4] = {a.x, a.y, a.z, a.w}, l[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
@@ -45,10 +58,18 @@ __device__ __forceinline__ void ek_load8(const uint16_t* __restrict__ hi, const 
     }
 }
 
+template <bool F16>
+__device__ __forceinline__ void ek_zero8(uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, const size_t e) {
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    *reinterpret_cast<uint4*>(hi + e) = z;
+    if constexpr (!F16) *reinterpret_cast<uint4*>(lo + e) = z;
+}
+
 }  // namespace
 
 // ---- stem: out[n, y, x, co] = silu(b[co] + sum_{ci,dy,dx} W[co][ci][dy][dx] * img[n, ci, 2y+dy-pt, 2x+dx-pl]) ----
 // one thread per output pixel; the 1 296 weights are read with wave-uniform addresses (scalar loads).  Channels 48..63 are written zero.
+template <bool F16>
 __global__ __launch_bounds__(256) void enc_stem_kernel(const float* __restrict__ img, const float* __restrict__ wgt,
                                                        const float* __restrict__ bias, uint16_t* __restrict__ out_hi,
                                                        uint16_t* __restrict__ out_lo, int N, int H, int W, int H2, int W2, int pt, int pl) {
@@ -78,23 +99,22 @@ __global__ __launch_bounds__(256) void enc_stem_kernel(const float* __restrict__
             for (int k = 0; k < 27; ++k) acc = __builtin_fmaf(wgt[co * 27 + k], in[k], acc);
             v[i] = silu_f32(acc + bias[co]);
         }
-        ek_store8(out_hi, out_lo, row * 64 + c8 * 8, v);
+        ek_store8<F16>(out_hi, out_lo, row * 64 + c8 * 8, v);
     }
-    const uint4 z = make_uint4(0, 0, 0, 0);
 #pragma unroll
-    for (int c8 = 6; c8 < 8; ++c8) {
-        *reinterpret_cast<uint4*>(out_hi + row * 64 + c8 * 8) = z;
-        *reinterpret_cast<uint4*>(out_lo + row * 64 + c8 * 8) = z;
-    }
+    for (int c8 = 6; c8 < 8; ++c8) ek_zero8<F16>(out_hi, out_lo, row * 64 + c8 * 8);
 }
 
+// out_lo == NULL: out_hi is ONE fp16 plane (magnet_enc_stem_f16)
 hipError_t launch_enc_stem(const float* img, const float* wgt, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int N, int H, int W,
-                           hipStream_t s) {
+                           bool f16, hipStream_t s) {
     const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
     const int th = (H2 - 1) * 2 + 3 - H, tw = (W2 - 1) * 2 + 3 - W;          // total TF-SAME padding (>= 0 for k 3, stride 2)
     const long long n = (long long)N * H2 * W2;
-    hipLaunchKernelGGL(enc_stem_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, wgt, bias, out_hi, out_lo, N, H, W, H2, W2,
-                       (th > 0 ? th : 0) / 2, (tw > 0 ? tw : 0) / 2);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    const int pt = (th > 0 ? th : 0) / 2, pl = (tw > 0 ? tw : 0) / 2;
+    if (f16) hipLaunchKernelGGL(enc_stem_kernel<true>, grid, dim3(256), 0, s, img, wgt, bias, out_hi, nullptr, N, H, W, H2, W2, pt, pl);
+    else hipLaunchKernelGGL(enc_stem_kernel<false>, grid, dim3(256), 0, s, img, wgt, bias, out_hi, out_lo, N, H, W, H2, W2, pt, pl);
     return hipGetLastError();
 }
 
@@ -107,7 +127,7 @@ hipError_t launch_enc_stem(const float* img, const float* wgt, const float* bias
 // then kx ascending, fp32 fmaf.
 // The partial sums: each thread adds its (up to 4) in-image outputs in x order, the workgroup adds the 32 strips in strip order
 // through LDS, and thread (group, lane) of the first strip row writes part[n][tile][channels]: one writer, written exactly once.
-template <int K, int S>
+template <int K, int S, bool F16>
 __global__ __launch_bounds__(256) void enc_dwconv_kernel(const EncDwParams p) {
     extern __shared__ float red[];                            // [32 strips][CGB * 8]
     const int cgb = blockDim.x >> 5;
@@ -145,7 +165,7 @@ __global__ __launch_bounds__(256) void enc_dwconv_kernel(const EncDwParams p) {
                 const int ix = ix0 + t;
                 if (ix < 0 || ix >= p.wi) continue;
                 float v[8];
-                ek_load8(p.in_hi, p.in_lo, (rowbase + ix) * p.in_ld + c, v);
+                ek_load8<F16>(p.in_hi, p.in_lo, (rowbase + ix) * p.in_ld + c, v);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int kx = t - j * S;                 // compile-time after unrolling
@@ -168,7 +188,7 @@ __global__ __launch_bounds__(256) void enc_dwconv_kernel(const EncDwParams p) {
                 v[i] = silu_f32(acc[j][i] + bv[i]);
                 psum[i] += v[i];
             }
-            ek_store8(p.out_hi, p.out_lo, (orow + ox0 + j) * p.out_ld + c, v);
+            ek_store8<F16>(p.out_hi, p.out_lo, (orow + ox0 + j) * p.out_ld + c, v);
         }
     }
     const int cw = cgb * 8;
@@ -185,19 +205,25 @@ __global__ __launch_bounds__(256) void enc_dwconv_kernel(const EncDwParams p) {
     }
 }
 
-hipError_t launch_enc_dwconv(const EncDwParams& p_in, int N, hipStream_t s) {
+template <bool F16>
+static hipError_t launch_enc_dwconv_fmt(const EncDwParams& p_in, int N, hipStream_t s) {
     EncDwParams p = p_in;
     p.n_part = (int)enc_dw_parts(p.ho, p.wo);
     const int groups = p.c_pad / 8;
     const int cgb = (groups % 8) == 0 ? 8 : 4;                // c_pad % 32 == 0: groups is a multiple of 4
     const dim3 grid((unsigned)p.n_part, (unsigned)(groups / cgb), (unsigned)N), block(32 * cgb);
     const size_t lds = (size_t)32 * cgb * 8 * sizeof(float);
-    if (p.k == 3 && p.stride == 1) hipLaunchKernelGGL((enc_dwconv_kernel<3, 1>), grid, block, lds, s, p);
-    else if (p.k == 3 && p.stride == 2) hipLaunchKernelGGL((enc_dwconv_kernel<3, 2>), grid, block, lds, s, p);
-    else if (p.k == 5 && p.stride == 1) hipLaunchKernelGGL((enc_dwconv_kernel<5, 1>), grid, block, lds, s, p);
-    else if (p.k == 5 && p.stride == 2) hipLaunchKernelGGL((enc_dwconv_kernel<5, 2>), grid, block, lds, s, p);
+    if (p.k == 3 && p.stride == 1) hipLaunchKernelGGL((enc_dwconv_kernel<3, 1, F16>), grid, block, lds, s, p);
+    else if (p.k == 3 && p.stride == 2) hipLaunchKernelGGL((enc_dwconv_kernel<3, 2, F16>), grid, block, lds, s, p);
+    else if (p.k == 5 && p.stride == 1) hipLaunchKernelGGL((enc_dwconv_kernel<5, 1, F16>), grid, block, lds, s, p);
+    else if (p.k == 5 && p.stride == 2) hipLaunchKernelGGL((enc_dwconv_kernel<5, 2, F16>), grid, block, lds, s, p);
     else return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+// f16: in_hi / out_hi are fp16 planes and the lo pointers NULL (magnet_dwconv_cl_f16)
+hipError_t launch_enc_dwconv(const EncDwParams& p, int N, bool f16, hipStream_t s) {
+    return f16 ? launch_enc_dwconv_fmt<true>(p, N, s) : launch_enc_dwconv_fmt<false>(p, N, s);
 }
 
 // ---- squeeze-excite gate: one workgroup of 1024 threads per image ----
@@ -284,6 +310,8 @@ hipError_t launch_enc_se_gate(const float* part, int n_part, long long hw, const
 }
 
 // ---- squeeze-excite scale: out = split((hi + lo) * gate[n][c]) over the interior; one thread per (pixel, 8 channels) ----
+// F16: out = f16(in * gate[n][c]) on ONE fp16 plane (magnet_se_scale_f16); in place is allowed either way (one reader = the one writer)
+template <bool F16>
 __global__ __launch_bounds__(256) void enc_se_scale_kernel(const uint16_t* __restrict__ in_hi, const uint16_t* __restrict__ in_lo, int in_ld,
                                                            const float* __restrict__ gate, int N, int h, int w, int c_pad,
                                                            uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo, int out_ld) {
@@ -295,19 +323,20 @@ __global__ __launch_bounds__(256) void enc_se_scale_kernel(const uint16_t* __res
     const int x = (int)(pix % w), y = (int)((pix / w) % h), n = (int)(pix / ((long long)w * h));
     const size_t row = ((size_t)n * (h + 2) + (y + 1)) * (w + 2) + (x + 1);
     float v[8];
-    ek_load8(in_hi, in_lo, row * in_ld + c, v);
+    ek_load8<F16>(in_hi, in_lo, row * in_ld + c, v);
     const float4 g0 = *reinterpret_cast<const float4*>(gate + (size_t)n * c_pad + c), g1 = *reinterpret_cast<const float4*>(gate + (size_t)n * c_pad + c + 4);
     const float gv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] *= gv[i];
-    ek_store8(out_hi, out_lo, row * out_ld + c, v);
+    ek_store8<F16>(out_hi, out_lo, row * out_ld + c, v);
 }
 
 hipError_t launch_enc_se_scale(const uint16_t* in_hi, const uint16_t* in_lo, int in_ld, const float* gate, int N, int h, int w, int c_pad,
-                               uint16_t* out_hi, uint16_t* out_lo, int out_ld, hipStream_t s) {
+                               uint16_t* out_hi, uint16_t* out_lo, int out_ld, bool f16, hipStream_t s) {
     const long long items = (long long)N * h * w * (c_pad / 8);
-    hipLaunchKernelGGL(enc_se_scale_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, in_hi, in_lo, in_ld, gate, N, h, w, c_pad,
-                       out_hi, out_lo, out_ld);
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (f16) hipLaunchKernelGGL(enc_se_scale_kernel<true>, grid, dim3(256), 0, s, in_hi, nullptr, in_ld, gate, N, h, w, c_pad, out_hi, nullptr, out_ld);
+    else hipLaunchKernelGGL(enc_se_scale_kernel<false>, grid, dim3(256), 0, s, in_hi, in_lo, in_ld, gate, N, h, w, c_pad, out_hi, out_lo, out_ld);
     return hipGetLastError();
 }
 

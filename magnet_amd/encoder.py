@@ -12,6 +12,14 @@ Two things live here, as in fnet.py:
   bf16x3 matrix-core kernel (`magnet_conv_mfma_ex`, SiLU in its epilogue for the expand layers, the skip connection as its residual
   input); the stem, the depthwise convolutions and squeeze-excite run on the kernels of csrc/enc_kernels.hip.  Activations are the
   convolution kernel's zero-bordered channel-last split-bf16 planes throughout.
+  `EncoderMFMA(model, precision="fp16")` (opt-in; default "bf16x3") stores every activation grid as ONE fp16 plane instead — the stem
+  output, the expanded tensor, the depthwise output, the scaled tensor and the block output (the residual stream) — and runs every 1x1
+  layer on magnet_conv_mfma_f16e: one matrix instruction per product instead of three, half the bytes per element-wise pass.  The 1x1
+  weights are rounded once to fp16 after the fp64 BatchNorm fold; depthwise weights, biases and squeeze-excite stay fp32, and the
+  squeeze mean is taken from fp32 values.  The feature list keeps its contract (NCHW fp32 taps).  A reduced-precision mode, outside the
+  project's 1e-4 contract: |activation| and |folded weight| <= 65504 — activation stores clamp, a larger folded weight raises at pack
+  time — and 39 blocks of 11-bit storage put the taps 1e-3 to 5e-3 of their largest magnitude from fp64
+  (profiles/encoder_precision/NOTES.md).
 """
 from __future__ import annotations
 
@@ -24,7 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import lib
-from .planes import PackCache, fold_bn, pack_taps, planes, round_up, timed
+from .planes import PackCache, fold_bn, pack_taps, pack_taps_f16, plane_f16, planes, round_up, timed
 
 BN_EPS = 1e-3
 STEM = 48
@@ -34,6 +42,8 @@ STAGES = (("ds", 3, 3, 1, 1, 24), ("ir", 5, 3, 2, 6, 40), ("ir", 5, 5, 2, 6, 64)
           ("ir", 7, 5, 1, 6, 176), ("ir", 9, 5, 2, 6, 304), ("ir", 3, 3, 1, 6, 512))
 N_FEATURES = 16                                              # [img] + conv_stem, bn1, act1, 7 stages, conv_head, bn2, act2, global_pool, classifier
 TAPS = (4, 5, 6, 8, 11)                                      # what the decoder (and the 1/2-scale skip) reads
+PRECISIONS = ("bf16x3", "fp16")                              # EncoderMFMA(precision=...): the storage / operand format
+F16_MAX = 65504.0                                            # largest finite fp16: the domain of precision="fp16"
 PARAMETERS = 28_340_784                                      # 30 389 784 (published B5) - 2 049 000 (the removed classifier)
 
 
@@ -141,18 +151,30 @@ class GenEfficientNetB5(nn.Module):
         return self.classifier(self.global_pool(self.act2(self.bn2(self.conv_head(self.blocks(x))))))
 
 
+def check_precision(precision, who="EncoderMFMA"):
+    """`precision` if it is one of PRECISIONS, else MagnetError naming `who`."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise lib.MagnetError(f"{who}: precision must be 'bf16x3' or 'fp16', got {precision!r}")
+    return precision
+
+
 class Encoder(nn.Module):
     """models/submodules/D_dense_depth.py:7-25.  backend: 'torch' (default) runs the modules as they are; 'hip' runs an eval-mode
     forward of a GPU tensor on EncoderMFMA (entries 0, 4, 5, 6, 8, 11 of the list are filled, the others are None: no decoder reads
-    them); a .train()-mode forward always runs the torch modules."""
+    them); a .train()-mode forward always runs the torch modules.
+    precision: EncoderMFMA's format, 'bf16x3' (default) or 'fp16' (reduced precision, opt-in: see EncoderMFMA); 'fp16' needs
+    backend='hip'."""
 
-    def __init__(self, backend: str = "torch"):
+    def __init__(self, backend: str = "torch", precision: str = "bf16x3"):
         super().__init__()
         if backend not in ("torch", "hip"):
             raise lib.MagnetError(f"Encoder: backend must be 'torch' or 'hip', got {backend!r}")
+        self.precision = check_precision(precision, "Encoder")
+        if precision == "fp16" and backend != "hip":
+            raise lib.MagnetError("Encoder: precision='fp16' is a mode of the HIP path: it needs backend='hip'")
         self.backend = backend
         self.original_model = GenEfficientNetB5()
-        self._runner = EncoderMFMA(self.original_model) if backend == "hip" else None
+        self._runner = EncoderMFMA(self.original_model, precision=precision) if backend == "hip" else None
 
     def forward(self, x):
         if self._runner is not None and not self.training:
@@ -245,13 +267,18 @@ def blocks_of(model):
 
 
 class EncoderMFMA:
-    """Inference runner for a `GenEfficientNetB5` (or a GenEfficientNet instance of the same attribute structure), eval mode, bf16x3."""
+    """Inference runner for a `GenEfficientNetB5` (or a GenEfficientNet instance of the same attribute structure), eval mode.
+    precision: 'bf16x3' (default: split-bf16 planes, three matrix instructions per product, fp32-grade) or 'fp16' (ONE fp16 plane per
+    activation grid, one matrix instruction per product; reduced precision, |activation| <= 65504 or clamped, a folded 1x1 weight
+    beyond 65504 raises when the weights are packed).  Weights and buffers are keyed by precision and live in the runner: two runners
+    on one module do not disturb each other."""
 
     # every launch appends (start_event, end_event, flops, layer name) when set to a list (tools/bench_encoder.py)
     event_sink = None
 
-    def __init__(self, model: nn.Module):
+    def __init__(self, model: nn.Module, precision: str = "bf16x3"):
         self.model = model
+        self.precision = check_precision(precision)
         self._packed = None
         self._cache = PackCache(lambda: list(model.parameters()) + list(model.buffers()))
         self._bufs = {}
@@ -259,22 +286,39 @@ class EncoderMFMA:
 
     # ---- weights ---------------------------------------------------------------------------------------------
     def packed(self, device):
-        self._packed = self._cache.get(device, lambda: self._pack(device))
+        self._packed = self._cache.get(device, lambda: self._pack(device), self.precision)   # one pack per precision
         return self._packed
 
     @staticmethod
-    def _pw(conv, bn, device):
-        """A 1x1 layer for the matrix-core kernel: split planes (1, cout_pad, cin_pad), bias (cout_pad), BatchNorm folded in fp64."""
+    def _pw(conv, bn, device, name="", f16=False):
+        """A 1x1 layer for the matrix-core kernel: split planes (1, cout_pad, cin_pad), bias (cout_pad), BatchNorm folded in fp64.
+        f16: (w, None, bias, cout, slices) with w ONE fp16 plane (1, width, cin_pad), rounded once from the fp32 cast of the fold.
+        slices = ((c0, w_slice, bias_slice), ...): the launches of the layer, one per channel slice [c0, c0 + w_slice.shape[1]) of the
+        `width`-wide output buffer.  One slice for every width magnet_conv_mfma_f16e serves (32, 64, multiples of 128); the 144
+        outputs of stage 1's expand layers are 128 + 32 in a 160-wide buffer (256 lanes would undo the halving on the largest tensor
+        of the network)."""
         if bn is None:
             w, b = conv.weight.detach().double(), torch.zeros(conv.out_channels, dtype=torch.float64)
         else:
             w, b = fold_bn(conv, bn)
         cout, cin = w.shape[:2]
         cp = cout_pad_of(cout)
+        cuts = (0, cp)
+        if f16:
+            peak = float(w.float().abs().max().cpu()) if w.numel() else 0.0
+            if not peak <= F16_MAX:                                  # an error, never a silent clamp
+                raise lib.MagnetError(f"EncoderMFMA {name}: folded weight magnitude {peak:.6g} is outside fp16's range (|w| <= {F16_MAX:.0f}): "
+                                      "precision='fp16' cannot hold this encoder; use precision='bf16x3'")
+            if cp == 144:
+                cp, cuts = 160, (0, 128, 160)
         wf = torch.zeros((cp, round_up(cin, 32), 1, 1), dtype=torch.float32)
         wf[:cout, :cin] = w.float().cpu()
         bias = torch.zeros(cp, dtype=torch.float32)
         bias[:cout] = b.float().cpu()
+        if f16:
+            wh, bias = pack_taps_f16(wf.to(device)), bias.to(device)
+            slices = tuple((c0, wh[:, c0:c1].contiguous(), bias[c0:c1].contiguous()) for c0, c1 in zip(cuts, cuts[1:]))
+            return wh, None, bias, cout, slices
         hi, lo = pack_taps(wf.to(device))
         return hi, lo, bias.to(device), cout
 
@@ -306,26 +350,28 @@ class EncoderMFMA:
         if tuple(w.shape) != (STEM, 3, 3, 3) or m.conv_stem.stride[0] != 2:
             raise lib.MagnetError("EncoderMFMA: the stem must be a 3x3 stride-2 convolution 3 -> 48")
         P["stem"] = (w.float().reshape(STEM, 27).contiguous().to(device), b.float().contiguous().to(device))
+        f16 = self.precision == "fp16"
         for name, blk, ds in blocks_of(m):
             if ds:
                 P[name + ".dw"] = self._dw(blk.conv_dw, blk.bn1, device)
-                P[name + ".pwl"] = self._pw(blk.conv_pw, blk.bn2, device)
+                P[name + ".pwl"] = self._pw(blk.conv_pw, blk.bn2, device, name + ".pwl", f16)
             else:
-                P[name + ".pw"] = self._pw(blk.conv_pw, blk.bn1, device)
+                P[name + ".pw"] = self._pw(blk.conv_pw, blk.bn1, device, name + ".pw", f16)
                 P[name + ".dw"] = self._dw(blk.conv_dw, blk.bn2, device)
-                P[name + ".pwl"] = self._pw(blk.conv_pwl, blk.bn3, device)
+                P[name + ".pwl"] = self._pw(blk.conv_pwl, blk.bn3, device, name + ".pwl", f16)
             P[name + ".se"] = self._se(blk.se, device)
-        P["conv_head"] = self._pw(m.conv_head, None, device)
+        P["conv_head"] = self._pw(m.conv_head, None, device, "conv_head", f16)
         return P
 
     # ---- activations -----------------------------------------------------------------------------------------
     def _grid(self, tag, dev, N, h, w, c):
         """A zero-bordered (N, h+2, w+2, c) grid as a (hi, lo) pair of (rows, c) planes, zero at allocation (border and pad lanes stay zero:
-        no launch writes them with anything else)."""
+        no launch writes them with anything else).  precision='fp16': (ONE fp16 plane, None)."""
         key = (tag, h, w, c)
         b = self._bufs.get(key)
         if b is None:
-            b = self._bufs[key] = planes(N * (h + 2) * (w + 2), c, dev, zero=True)
+            rows = N * (h + 2) * (w + 2)
+            b = self._bufs[key] = (plane_f16(rows, c, dev, zero=True), None) if self.precision == "fp16" else planes(rows, c, dev, zero=True)
         return b
 
     def _scratch(self, tag, dev, shape):
@@ -336,8 +382,16 @@ class EncoderMFMA:
         return b
 
     def _conv(self, name, src, in_ld, N, h, w, dst=None, out_ld=0, silu=False, add=None, out_f32=None):
-        hi, lo, bias, cout = self._packed[name]
+        hi, lo, bias, cout = self._packed[name][:4]
         rows, cin = N * (h + 2) * (w + 2), hi.shape[2]
+        if self.precision == "fp16":                                # one launch per channel slice of the layer (one, but for 144 outputs)
+            for c0, ws, bs in self._packed[name][4]:
+                with timed(EncoderMFMA.event_sink, 2.0 * rows * cin * ws.shape[1], name):
+                    lib.conv_mfma(src[0], None, in_ld, cin, ws, None, bs, 1, w + 2, False, rows, out_hi=None if dst is None else dst[0][:, c0:],
+                                  out_f32=None if out_f32 is None else out_f32[..., c0:], out_ld=out_ld or hi.shape[1],
+                                  add=None if add is None else (add[0][:, c0:], None, add[2]), border=(h + 2, 1),
+                                  repad=1 if out_f32 is not None else 0, silu=silu, f16="enc")
+            return
         with timed(EncoderMFMA.event_sink, 2.0 * rows * cin * hi.shape[1], name):
             lib.conv_mfma(src[0], src[1], in_ld, cin, hi, lo, bias, 1, w + 2, False, rows,
                           out_hi=None if dst is None else dst[0], out_lo=None if dst is None else dst[1], out_f32=out_f32,
@@ -354,19 +408,28 @@ class EncoderMFMA:
         n_part = lib.dwconv_parts(ho, wo)
         part = self._scratch("part", dev, (N, n_part, cp))
         sink = EncoderMFMA.event_sink
+        f16 = self.precision == "fp16"
         with timed(sink, 2.0 * N * ho * wo * C * k * k, name + ".dw"):
-            lib.dwconv_cl(src[0], src[1], src[0].shape[1], N, h, w, cp, wt, bias, k, stride, pt, pl, dst[0], dst[1], cp, part)
+            if f16:
+                lib.dwconv_cl_f16(src[0], src[0].shape[1], N, h, w, cp, wt, bias, k, stride, pt, pl, dst[0], cp, part)
+            else:
+                lib.dwconv_cl(src[0], src[1], src[0].shape[1], N, h, w, cp, wt, bias, k, stride, pt, pl, dst[0], dst[1], cp, part)
         w1, b1, w2t, b2, C, R = self._packed[name + ".se"]
         gate = self._scratch("gate", dev, (N, cp))
         with timed(sink, 4.0 * N * C * R, name + ".se_gate"):
             lib.se_gate(part, n_part, ho * wo, w1, b1, w2t, b2, C, R, gate)
         with timed(sink, 1.0 * N * ho * wo * C, name + ".se_scale"):
-            lib.se_scale(dst[0], dst[1], cp, gate, N, ho, wo, cp, dst[0], dst[1], cp)
+            if f16:
+                lib.se_scale_f16(dst[0], cp, gate, N, ho, wo, cp, dst[0], cp)
+            else:
+                lib.se_scale(dst[0], dst[1], cp, gate, N, ho, wo, cp, dst[0], dst[1], cp)
         return dst, ho, wo
 
     @staticmethod
     def _nchw(buf, N, h, w, C):
-        """The interior of a grid as an NCHW fp32 tensor."""
+        """The interior of a grid as an NCHW fp32 tensor (an fp16 plane: a slice, then .float())."""
+        if buf[1] is None:
+            return buf[0].view(N, h + 2, w + 2, -1)[:, 1:h + 1, 1:w + 1, :C].float().permute(0, 3, 1, 2).contiguous()
         hi, lo = (t.view(N, h + 2, w + 2, -1)[:, 1:h + 1, 1:w + 1, :C] for t in buf)
         return (hi.float() + lo.float()).permute(0, 3, 1, 2).contiguous()
 
@@ -384,7 +447,7 @@ class EncoderMFMA:
         N, _, H, W = x_img.shape
         dev = x_img.device
         P = self.packed(dev)
-        sig = (str(dev), N, H, W)
+        sig = (str(dev), N, H, W, self.precision)
         if self._bufs_sig != sig:                                   # one batch shape at a time
             self._bufs.clear()
             self._bufs_sig = sig
@@ -392,7 +455,10 @@ class EncoderMFMA:
         h, w = -(-H // 2), -(-W // 2)
         x = self._grid("X0", dev, N, h, w, 64)
         with timed(EncoderMFMA.event_sink, 2.0 * N * h * w * 27 * STEM, "stem"):
-            lib.enc_stem(x_img, P["stem"][0], P["stem"][1], x[0], x[1])
+            if self.precision == "fp16":
+                lib.enc_stem_f16(x_img, P["stem"][0], P["stem"][1], x[0])
+            else:
+                lib.enc_stem(x_img, P["stem"][0], P["stem"][1], x[0], x[1])
         x_ld, flip = 64, 0
         for name, blk, ds in blocks_of(self.model):
             s = int(name.split(".")[1])

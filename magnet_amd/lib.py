@@ -290,6 +290,7 @@ _PROTOS = {
     "magnet_conv_mfma_f16d": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_conv_mfma_f16d_splitk_workspace": (_L, [_S(MagnetConvExArgs), _I]),
     "magnet_conv_mfma_f16d_splitk": (_C, [_S(MagnetConvExArgs), _I, _P, _L, _P]),
+    "magnet_conv_mfma_f16e": (_C, [_S(MagnetConvExArgs), _P]),
     "magnet_pack_f16": (_C, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
     "magnet_planes_to_f16": (_C, [_P, _P, _I, _P, _I, _L, _I, _I, _P]),
     "magnet_fnet_stem_f16": (_C, [_P, _P, _P, _P, _I, _I, _I, _P]),
@@ -304,6 +305,9 @@ _PROTOS = {
     "magnet_dwconv_cl": (_C, [_S(MagnetDwConvArgs), _P]),
     "magnet_se_gate": (_C, [_P, _I, _L, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "magnet_se_scale": (_C, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "magnet_enc_stem_f16": (_C, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "magnet_dwconv_cl_f16": (_C, [_S(MagnetDwConvArgs), _P]),
+    "magnet_se_scale_f16": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
     "magnet_gather_views": (_C, [_S(MagnetGatherViewsArgs), _P]),
     "magnet_scatter_frames": (_C, [_S(MagnetScatterFramesArgs), _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
@@ -643,6 +647,7 @@ _CONV_ROUTES = {
     True: ("magnet_conv_mfma_f16", None, None),
     "plane": ("magnet_conv_mfma_f16p", None, None),
     "wide": ("magnet_conv_mfma_f16d", "magnet_conv_mfma_f16d_splitk", "magnet_conv_mfma_f16d_splitk_workspace"),
+    "enc": ("magnet_conv_mfma_f16e", None, None),
 }
 
 
@@ -676,6 +681,9 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     layers): taps 1 / 9, relu or leaky, border, repad and channel slices; the output is out_f16 (passed as out_hi with out_lo None),
     out_f32 or the split-bf16 pair out_hi / out_lo; no tail, addend, add, dil or out_bf16.  split_k / work are allowed on this route
     (magnet_conv_mfma_f16d_splitk).  Returns the row tile count.
+    f16 = "enc": the same operand format, plane to plane, for the EfficientNet encoder's 1x1 layers (magnet_conv_mfma_f16e): taps 1,
+    cout_pad 32 / 64 / any multiple of 128, silu allowed, `add` = (fp16 plane, None, ld); the output is out_f16 (passed as out_hi with
+    out_lo None) or out_f32; border, repad and channel slices; no relu, leaky, tail, addend, dil or out_bf16.  Returns the row tile count.
     src_nchw = (x (B, C, h, w) fp32 contiguous, c0): input channels [c0, c0 + C) with c0 + C == cin are read in place from x and split
     inside the kernel (magnet_conv_mfma_nchw: the fused-tail 3x3 launches on 256-row tiles under per-image tiling, nothing else); the
     planes hold channels [0, c0) and may be None when c0 == 0.  Returns the row tile count."""
@@ -695,17 +703,21 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
             raise MagnetError("conv_mfma (split_k): work must be a contiguous float32 GPU tensor")
     elif work is not None:
         raise MagnetError("conv_mfma: work goes with split_k")
-    if silu and (relu or leaky is not None or tail is not None or f16 or split_k is not None):
-        raise MagnetError("conv_mfma (silu): the bf16x3 layer without relu, leaky, tail, f16 or split_k")
+    enc = isinstance(f16, str) and f16 == "enc"
+    if silu and (relu or leaky is not None or tail is not None or (f16 and not enc) or split_k is not None):
+        raise MagnetError("conv_mfma (silu): the bf16x3 layer (or f16='enc') without relu, leaky, tail or split_k")
     a = MagnetConvArgs()
     if f16 not in tuple(_CONV_ROUTES):
-        raise MagnetError(f"conv_mfma: f16 must be False, True, 'plane' or 'wide', got {f16!r}")
+        raise MagnetError(f"conv_mfma: f16 must be False, True, 'plane', 'wide' or 'enc', got {f16!r}")
     entry, entry_splitk, _ = _CONV_ROUTES[f16]                          # the route, looked up once
     plane = isinstance(f16, str) and f16 == "plane"
     if wide and (tail is not None or addend is not None or add is not None or out_bf16 is not None or dil):
         raise MagnetError("conv_mfma (f16='wide'): the plain layer — no tail, addend, add, out_bf16 or dil")
     if plane and (tail is not None or addend is not None or out_lo is not None or (add is not None and add[1] is not None)):
         raise MagnetError("conv_mfma (f16='plane'): one fp16 plane per buffer — out_lo and add[1] must be None; no tail, no addend")
+    if enc and (tail is not None or addend is not None or out_lo is not None or out_bf16 is not None or dil or relu or
+                (add is not None and add[1] is not None)):
+        raise MagnetError("conv_mfma (f16='enc'): one fp16 plane per buffer — out_lo and add[1] must be None; no relu, tail, addend, out_bf16 or dil")
     if f16:
         if in_lo is not None or w_lo is not None or (leaky is not None and not wide):
             raise MagnetError("conv_mfma (f16): one fp16 plane per operand — in_lo, w_lo and leaky (but for f16='wide') must be None")
@@ -725,7 +737,7 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
     if addend is not None:
         a.addend, a.addend_ld = _dev(addend, "addend", torch.float32).data_ptr(), int(addend.shape[1])
     a.dil, a.out_ld, a.repad = int(dil), int(out_ld), int(repad)
-    if add is not None and plane:
+    if add is not None and (plane or enc):
         a.add_hi, a.add_ld = _f16_ptr(add[0], "add (fp16 plane)"), int(add[2])
     elif add is not None:
         a.add_hi, a.add_lo, a.add_ld = _bf16_ptr(add[0], "add_hi"), _bf16_ptr(add[1], "add_lo"), int(add[2])
@@ -754,7 +766,7 @@ def conv_mfma(in_hi, in_lo, in_ld, cin, w_hi, w_lo, bias, taps, wp, relu, rows, 
         a.out_mode, a.out_f32 = 1, out_f32.data_ptr()
     elif out_bf16 is not None:
         a.out_mode, a.out_hi = 2, _bf16_ptr(out_bf16, "out_bf16")
-    elif plane or (wide and out_lo is None):
+    elif plane or enc or (wide and out_lo is None):
         a.out_mode, a.out_hi = 3, _f16_ptr(out_hi, "out_hi (fp16 plane)")
     else:
         a.out_mode, a.out_hi, a.out_lo = 0, _bf16_ptr(out_hi, "out_hi"), _bf16_ptr(out_lo, "out_lo")
@@ -1590,6 +1602,20 @@ def enc_stem(img, wgt, bias, out_hi, out_lo):
             out_hi.data_ptr(), out_lo.data_ptr(), N, H, W)
 
 
+def enc_stem_f16(img, wgt, bias, out_f16):
+    """enc_stem on the single-plane fp16 format (magnet_enc_stem_f16): the interior of ONE fp16 plane (N,H2+2,W2+2,64)."""
+    x = _dev(img, "img", torch.float32)
+    N, C, H, W = x.shape
+    if C != 3:
+        raise MagnetError(f"enc_stem_f16: expected 3 input channels, got {C}")
+    if tuple(wgt.shape) != (48, 27) or tuple(bias.shape) != (48,):
+        raise MagnetError(f"enc_stem_f16: wgt (48, 27) and bias (48,), got {tuple(wgt.shape)} / {tuple(bias.shape)}")
+    rows = N * ((H + 1) // 2 + 2) * ((W + 1) // 2 + 2)
+    _f16_plane("enc_stem_f16: out_f16", out_f16, rows * 64)
+    _launch("magnet_enc_stem_f16", x, x.data_ptr(), _dev(wgt, "wgt", torch.float32).data_ptr(), _dev(bias, "bias", torch.float32).data_ptr(),
+            out_f16.data_ptr(), N, H, W)
+
+
 def dwconv_parts(ho, wo) -> int:
     """magnet_dwconv_cl_parts: rows of the partial-sum scratch per image for an (ho, wo) output.  Host arithmetic: no GPU needed."""
     return int(load().magnet_dwconv_cl_parts(int(ho), int(wo)))
@@ -1600,6 +1626,16 @@ def _grid_planes(who, t, N, h, w, ld):
     _bf16_ptr(t, who, contiguous=True)
     if t.numel() < N * (h + 2) * (w + 2) * ld:
         raise MagnetError(f"{who} holds {t.numel()} elements, needs {N * (h + 2) * (w + 2) * ld}")
+    return t.data_ptr()
+
+
+def _f16_plane(who, t, numel):
+    """ONE fp16 plane of a zero-bordered grid: a contiguous fp16 GPU tensor of at least numel elements (its data_ptr is row 0)."""
+    _f16_ptr(t, who)
+    if not t.is_contiguous():
+        raise MagnetError(f"{who} must be contiguous")
+    if t.numel() < numel:
+        raise MagnetError(f"{who} holds {t.numel()} elements, needs {numel}")
     return t.data_ptr()
 
 
@@ -1621,6 +1657,26 @@ def dwconv_cl(in_hi, in_lo, in_ld, N, h, w, c_pad, wgt, bias, k, stride, pad_top
     a.N, a.h, a.w, a.c_pad, a.in_ld, a.out_ld = int(N), int(h), int(w), int(c_pad), int(in_ld), int(out_ld)
     a.k, a.stride, a.pad_top, a.pad_left, a.n_part = int(k), int(stride), int(pad_top), int(pad_left), n_part
     _launch("magnet_dwconv_cl", in_hi, ctypes.byref(a))
+    return n_part
+
+
+def dwconv_cl_f16(in_f16, in_ld, N, h, w, c_pad, wgt, bias, k, stride, pad_top, pad_left, out_f16, out_ld, part):
+    """dwconv_cl on the single-plane fp16 format (magnet_dwconv_cl_f16): in / out are ONE fp16 plane each; `part` holds the sums of the
+    fp32 values before the fp16 store, as dwconv_cl's."""
+    ho, wo = -(-int(h) // int(stride)), -(-int(w) // int(stride))
+    n_part = dwconv_parts(ho, wo)
+    a = MagnetDwConvArgs()
+    a.in_hi = _f16_plane("dwconv_cl_f16: in_f16", in_f16, N * (h + 2) * (w + 2) * in_ld)
+    a.out_hi = _f16_plane("dwconv_cl_f16: out_f16", out_f16, N * (ho + 2) * (wo + 2) * out_ld)
+    if tuple(wgt.shape) != (k * k, c_pad) or tuple(bias.shape) != (c_pad,):
+        raise MagnetError(f"dwconv_cl_f16: wgt ({k * k}, {c_pad}) and bias ({c_pad},), got {tuple(wgt.shape)} / {tuple(bias.shape)}")
+    a.wgt, a.bias = _dev(wgt, "wgt", torch.float32).data_ptr(), _dev(bias, "bias", torch.float32).data_ptr()
+    if _dev(part, "part", torch.float32).numel() < N * n_part * c_pad:
+        raise MagnetError(f"dwconv_cl_f16: part holds {part.numel()} elements, needs {N * n_part * c_pad}")
+    a.part = part.data_ptr()
+    a.N, a.h, a.w, a.c_pad, a.in_ld, a.out_ld = int(N), int(h), int(w), int(c_pad), int(in_ld), int(out_ld)
+    a.k, a.stride, a.pad_top, a.pad_left, a.n_part = int(k), int(stride), int(pad_top), int(pad_left), n_part
+    _launch("magnet_dwconv_cl_f16", in_f16, ctypes.byref(a))
     return n_part
 
 
@@ -1648,3 +1704,13 @@ def se_scale(in_hi, in_lo, in_ld, gate, N, h, w, c_pad, out_hi, out_lo, out_ld):
     ih, il = (_grid_planes(f"se_scale: {n}", t, N, h, w, in_ld) for t, n in ((in_hi, "in_hi"), (in_lo, "in_lo")))
     oh, ol = (_grid_planes(f"se_scale: {n}", t, N, h, w, out_ld) for t, n in ((out_hi, "out_hi"), (out_lo, "out_lo")))
     _launch("magnet_se_scale", in_hi, ih, il, int(in_ld), g.data_ptr(), int(N), int(h), int(w), int(c_pad), oh, ol, int(out_ld))
+
+
+def se_scale_f16(in_f16, in_ld, gate, N, h, w, c_pad, out_f16, out_ld):
+    """se_scale on the single-plane fp16 format (magnet_se_scale_f16): out = f16(in * gate[n][c]); out may be the input."""
+    g = _dev(gate, "gate", torch.float32)
+    if tuple(g.shape) != (N, c_pad):
+        raise MagnetError(f"se_scale_f16: gate must be {(N, c_pad)}, got {tuple(g.shape)}")
+    i = _f16_plane("se_scale_f16: in_f16", in_f16, N * (h + 2) * (w + 2) * in_ld)
+    o = _f16_plane("se_scale_f16: out_f16", out_f16, N * (h + 2) * (w + 2) * out_ld)
+    _launch("magnet_se_scale_f16", in_f16, i, int(in_ld), g.data_ptr(), int(N), int(h), int(w), int(c_pad), o, int(out_ld))

@@ -102,18 +102,22 @@ def make_dnet_args(downsample_ratio=4):
 
 
 def make_dnet(seed=0, enc_seed=0, depth_prior=True, dnet=False, backend="torch", split_k=0, precision="bf16x3", encoder="standin",
-              encoder_backend="torch"):
+              encoder_backend="torch", encoder_precision="bf16x3"):
     """magnet_amd.dnet.DNET with the stand-in encoder and seeded decoder weights (magnet_amd.dnet.seeded_decoder_state), in eval mode.
     encoder: "standin" (default: StandinEncoder(enc_seed)) or "b5": magnet_amd.encoder.Encoder(backend=encoder_backend), the real
     EfficientNet-B5 with calibrated seeded weights (magnet_amd.encoder.load_seeded_encoder(enc_seed)).
+    encoder_precision: EncoderMFMA's format, "bf16x3" (default) or "fp16" (reduced precision, opt-in); "fp16" goes with encoder="b5" and
+    encoder_backend="hip".
     dnet=False: MaGNet's D-Net; dnet=True: the stand-alone D-Net (img -> (N, 2, H, W) [mu, variance]); backend, split_k, precision: see DNET.
     depth_prior: the depth head's last layer is scaled by 1/4 and its bias set to (2.5, -3) so that the stand-in predicts
     plausible scenes for the matcher, mu around 2.5 m (+-1.5) and sigma around 0.2 m (StubDNet's ranges); the raw recipe's mu is
     centred on zero, where depth candidates cross the camera plane."""
     from .dnet import DNET, load_seeded_decoder
+    if encoder_precision != "bf16x3" and not (encoder == "b5" and encoder_backend == "hip"):
+        raise ValueError(f"make_dnet: encoder_precision={encoder_precision!r} goes with encoder='b5' and encoder_backend='hip' (a mode of EncoderMFMA)")
     if encoder == "b5":
         from .encoder import Encoder, load_seeded_encoder
-        enc = load_seeded_encoder(Encoder(backend=encoder_backend), enc_seed)
+        enc = load_seeded_encoder(Encoder(backend=encoder_backend, precision=encoder_precision), enc_seed)
     elif encoder == "standin":
         if encoder_backend != "torch":
             raise ValueError("make_dnet: encoder_backend='hip' goes with encoder='b5' (the stand-in is a torch module)")

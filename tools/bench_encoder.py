@@ -4,8 +4,13 @@ timed with a host clock around work that ends in a device synchronise.  Then one
 the per-layer times (HIP events around every launch, summed by layer kind and by stage), and the end-to-end times follow with the real
 encoder in place of the stand-in: the stand-alone D-Net (DNET(dnet=True), both backends of encoder and decoder) and, with --magnet,
 MAGNET.forward at the C2 workload.  Prints one JSON line per shape; --out FILE appends the lines.
+--precision fp16 adds, per shape, a second line ("bench": "encoder_precision"): --pairs interleaved pairs of an fp16 runner against the
+bf16x3 runner ON THE SAME MODULE (EncoderMFMA(model, precision="fp16"); the yardstick is the default path in the same process), the
+fp16 side's events by launch kind and by stage next to the bf16x3 side's, the fp16 taps' differences from torch fp32, and the
+stand-alone D-Net end to end with every fp16 mode on (encoder and decoder) against all off.
 
-    python tools/bench_encoder.py [--pairs 12] [--warmup 3] [--shapes 1x480x640,5x480x640,3x352x1216] [--out profiles/encoder/bench_encoder.jsonl]
+    python tools/bench_encoder.py [--pairs 12] [--warmup 3] [--shapes 1x480x640,5x480x640,3x352x1216] [--precision fp16]
+                                  [--out profiles/encoder/bench_encoder.jsonl]
 """
 import argparse
 import json
@@ -68,11 +73,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default="1x480x640,5x480x640,3x352x1216")
     ap.add_argument("--magnet", action="store_true", help="also time MAGNET.forward (C2 workload) with the real encoder on both backends")
+    ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "fp16"],
+                    help="fp16: also pair the fp16 runner against the bf16x3 runner on the same module, with its own per-kind and per-stage events")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from magnet_amd import lib
     from magnet_amd.dnet import DNET, load_seeded_decoder
-    from magnet_amd.encoder import Encoder, load_seeded_encoder
+    from magnet_amd.encoder import Encoder, EncoderMFMA, load_seeded_encoder
     from magnet_amd.standin import make_dnet_args
     lib.load()
     dev = torch.device("cuda:0")
@@ -85,7 +92,21 @@ def main():
         d.d_net.encoder.load_state_dict(hip.state_dict())
         load_seeded_decoder(d.d_net.decoder, 0)
         dn[(eb, db)] = d.to(dev).eval()
+    f16 = dn16 = None
+    if a.precision == "fp16":
+        f16 = EncoderMFMA(hip.original_model, precision="fp16")      # a second runner on the SAME module
+        dn16 = DNET(make_dnet_args(), Encoder(backend="hip", precision="fp16"), dnet=True, backend="hip", precision="fp16")
+        dn16.load_state_dict(dn[("hip", "hip")].state_dict())
+        dn16 = dn16.to(dev).eval()
     med = statistics.median
+
+    def emit(line):
+        print(json.dumps(line), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as fh:
+                fh.write(json.dumps(line) + "\n")
+
     for shape in a.shapes.split(","):
         N, H, W = (int(v) for v in shape.split("x"))
         img = torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(1)).to(dev)
@@ -105,12 +126,27 @@ def main():
             t_c, _ = pairs_of(lambda: dn[("torch", "torch")](img), lambda: None, 1, max(3, a.pairs // 4))
             line["dnet_ms_median"] = {"encoder hip + decoder hip": round(med(t_a), 3), "encoder torch + decoder hip": round(med(t_b), 3),
                                       "encoder torch + decoder torch": round(med(t_c), 3)}
-        print(json.dumps(line), flush=True)
-        if a.out:
-            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-            with open(a.out, "a") as fh:
-                fh.write(json.dumps(line) + "\n")
-        for d in dn.values():                                       # one shape's buffers at a time
+        emit(line)
+        if f16 is not None:
+            with torch.no_grad():
+                t_f, t_b = pairs_of(lambda: f16(img), lambda: hip(img), a.warmup, a.pairs)
+                k16, s16, ev16, n16 = layer_times(f16, img)
+                got, want = f16(img), ref(img)
+                diff16 = {str(i): float((got[i] - want[i]).abs().max() / want[i].abs().max()) for i in (4, 5, 6, 8, 11)}
+                del got, want
+                t_d16, t_d = pairs_of(lambda: dn16(img), lambda: dn[("hip", "hip")](img), a.warmup, a.pairs)
+            emit({"bench": "encoder_precision", "shape": [N, H, W], "pairs": a.pairs, "gpu": torch.cuda.get_device_name(0),
+                  "fp16_ms": [round(v, 3) for v in t_f], "bf16x3_ms": [round(v, 3) for v in t_b],
+                  "fp16_ms_median": round(med(t_f), 3), "bf16x3_ms_median": round(med(t_b), 3),
+                  "pairs_won": {"fp16": sum(x < y for x, y in zip(t_f, t_b)), "bf16x3": sum(y < x for x, y in zip(t_f, t_b))},
+                  "launches": {"fp16": n16, "bf16x3": launches}, "event_ms_total": {"fp16": ev16, "bf16x3": ev_total},
+                  "ms_by_kind": {"fp16": k16, "bf16x3": kinds}, "ms_by_stage": {"fp16": s16, "bf16x3": stages},
+                  "max_rel_diff_fp16_vs_torch": diff16,
+                  "dnet_ms": {"all fp16": [round(v, 3) for v in t_d16], "all bf16x3": [round(v, 3) for v in t_d]},
+                  "dnet_ms_median": {"all fp16": round(med(t_d16), 3), "all bf16x3": round(med(t_d), 3)},
+                  "dnet_pairs_won": {"all fp16": sum(x < y for x, y in zip(t_d16, t_d)), "all bf16x3": sum(y < x for x, y in zip(t_d16, t_d))}})
+            f16._bufs.clear(); f16._bufs_sig = None
+        for d in list(dn.values()) + ([dn16] if dn16 is not None else []):     # one shape's buffers at a time
             if d._runner is not None:
                 d._runner._bufs.clear(); d._runner._bufs_sig = None
             r = getattr(d.d_net.encoder, "_runner", None)
