@@ -7,7 +7,7 @@ magnet_amd/data.py's folders (the reference frame of each window), the encoder i
 heads and tail run on the HIP path (DNET(dnet=True, backend='hip')), and the metric reductions run on the device.
 
     python eval_dnet.py --frames 8 [--batch 1] [--backend hip] [--log out.txt]
-    python eval_dnet.py --dataset_path ROOT --split split.txt [--dataset_format 7scenes]
+    python eval_dnet.py --dataset_path ROOT --split split.txt [--dataset_format 7scenes] [--device_images]
     python eval_dnet.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
 """
 import argparse
@@ -20,6 +20,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 from magnet_amd import evaluate as E  # noqa: E402
+from magnet_amd import ingest  # noqa: E402
 from magnet_amd import metrics as M  # noqa: E402
 
 
@@ -116,7 +117,10 @@ def main():
                     help="with --encoder b5 --encoder_backend hip: EncoderMFMA's format; fp16 = one fp16 plane per activation grid, reduced "
                          "precision, |activation| <= 65504 or clamped")
     E.add_arguments(ap)
+    ingest.add_arguments(ap)
     a = ap.parse_args()
+    if a.device_images and not a.dataset_path:
+        ap.error("--device_images needs --dataset_path: the synthetic frames are normalised images already")
     if a.encoder_backend == "hip" and a.encoder != "b5":
         ap.error("--encoder_backend hip is a mode of --encoder b5")
     if a.encoder_precision != "bf16x3" and not (a.encoder == "b5" and a.encoder_backend == "hip"):
@@ -133,8 +137,10 @@ def main():
         Folder = data.SevenScenesFolder if a.dataset_format == "7scenes" else data.ScanNetFolder
         # window_radius 0: every window entry is the reference frame itself, so no neighbour has to exist
         ds = Folder(a.dataset_path, samples, n_views=2, window_radius=0, input_hw=(a.input_height, a.input_width),
-                    dpv_hw=(a.input_height // 4, a.input_width // 4))
+                    dpv_hw=(a.input_height // 4, a.input_width // 4), **({"raw_images": True} if a.device_images else {}))
         loader = FolderFrames(ds, a.batch)
+        if a.device_images:
+            loader, _ = ingest.device_image_loader(a, loader, device)
         title = "%s-format folder %s (%d frames) D-Net backend=%s" % (a.dataset_format, a.dataset_path, len(ds), a.backend)
     else:
         loader = SyntheticFrames(a.frames, a.batch, a.input_height, a.input_width, seed=a.seed)

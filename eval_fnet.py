@@ -9,7 +9,7 @@ and homography.expected_depth_F fuses softmax and expectation in one pass, and t
 kernel takes (mu, sigma): sigma = 1 is passed and nll is reported as 0.0, as utils.compute_depth_errors(..., None) does.
 
     python eval_fnet.py --frames 8 [--batch 1] [--V 4] [--D 80] [--log out.txt]
-    python eval_fnet.py --dataset_path ROOT --split split.txt [--dataset_format 7scenes]
+    python eval_fnet.py --dataset_path ROOT --split split.txt [--dataset_format 7scenes] [--device_images]
     python eval_fnet.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
 """
 import argparse
@@ -24,6 +24,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 from magnet_amd import evaluate as E  # noqa: E402
+from magnet_amd import ingest  # noqa: E402
 from magnet_amd import metrics as M  # noqa: E402
 from magnet_amd.homography import expected_depth_F  # noqa: E402
 from magnet_amd.preprocess import data_preprocess_device  # noqa: E402
@@ -99,7 +100,10 @@ def main():
     ap.add_argument("--garg_crop", action="store_true", help="KITTI: evaluate inside the Garg ECCV16 window (train_FNet.py:180-181)")
     ap.add_argument("--eigen_crop", action="store_true", help="KITTI: evaluate inside the Eigen NIPS14 window (train_FNet.py:182-183)")
     E.add_arguments(ap)
+    ingest.add_arguments(ap)
     a = ap.parse_args()
+    if a.device_images and not a.dataset_path:
+        ap.error("--device_images needs --dataset_path: the synthetic frames are normalised images already")
     rank, world, device, sharded = E.start(a, __file__)
     from magnet_amd.magnet import MAGNET_F
     args = argparse.Namespace(min_depth=a.min_depth, max_depth=a.max_depth, garg_crop=a.garg_crop, eigen_crop=a.eigen_crop,
@@ -113,8 +117,10 @@ def main():
             samples = [ln.split()[:3 if a.dataset_format == "7scenes" else 2] for ln in f if ln.strip()]
         Folder = data.SevenScenesFolder if a.dataset_format == "7scenes" else data.ScanNetFolder
         ds = Folder(a.dataset_path, samples, n_views=a.V, window_radius=a.window_radius, input_hw=(a.input_height, a.input_width),
-                    dpv_hw=(a.input_height // 4, a.input_width // 4))
+                    dpv_hw=(a.input_height // 4, a.input_width // 4), **({"raw_images": True} if a.device_images else {}))
         loader = data.batches(ds, a.batch)
+        if a.device_images:
+            loader, _ = ingest.device_image_loader(a, loader, device)
         title = "%s-format folder %s (%d windows) F-Net V=%d D=%d" % (a.dataset_format, a.dataset_path, len(ds), a.V, a.D)
     else:
         from eval_synthetic import SyntheticWindows

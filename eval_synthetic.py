@@ -9,6 +9,7 @@ the backbones are caller-provided (stub D-Net/F-Net here), and the metric reduct
     python eval_synthetic.py --frames 8 --batch 2 [--D 5] [--iters 3] [--V 4] [--log out.txt]
     python eval_synthetic.py --sharded [--gpus N] [--dist_backend gloo] [--dump_metrics out.json]     (or under torch.distributed.run)
     python eval_synthetic.py --dataset_path ROOT --split split.txt --reuse_backbones [--pool_frames 64] [--graph]
+    python eval_synthetic.py --dataset_path ROOT --split split.txt --device_images [--reuse_backbones]
 """
 import argparse
 import os
@@ -20,6 +21,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 from magnet_amd import evaluate as E  # noqa: E402
+from magnet_amd import ingest  # noqa: E402
 from magnet_amd import metrics as M  # noqa: E402
 from magnet_amd import synth  # noqa: E402
 from magnet_amd.magnet import MAGNET  # noqa: E402
@@ -154,7 +156,10 @@ def main():
                     help="with --encoder b5 --encoder_backend hip: EncoderMFMA's format; fp16 = one fp16 plane per activation grid, reduced "
                          "precision, |activation| <= 65504 or clamped")
     E.add_arguments(ap)
+    ingest.add_arguments(ap)
     a = ap.parse_args()
+    if a.device_images and not a.dataset_path:
+        ap.error("--device_images needs --dataset_path: the synthetic frames are normalised images already")
     if a.encoder_backend == "hip" and a.encoder != "b5":
         ap.error("--encoder_backend hip is a mode of --encoder b5")
     if a.encoder_precision != "bf16x3" and not (a.encoder == "b5" and a.encoder_backend == "hip"):
@@ -189,11 +194,17 @@ def main():
             samples = [ln.split()[:3 if a.dataset_format == "7scenes" else 2] for ln in f if ln.strip()]
         Folder = data.SevenScenesFolder if a.dataset_format == "7scenes" else data.ScanNetFolder
         ds = Folder(a.dataset_path, samples, n_views=a.V, window_radius=a.window_radius,
-                                input_hw=(a.input_height, a.input_width), dpv_hw=(a.input_height // 4, a.input_width // 4))
+                                input_hw=(a.input_height, a.input_width), dpv_hw=(a.input_height // 4, a.input_width // 4),
+                                **({"raw_images": True} if a.device_images else {}))
         loader = FolderBatches(ds, a.batch)
+        preps = None
+        if a.device_images:
+            # with a frame pool the frames stay uint8 up to the runner, which prepares only those the pool lacks
+            loader, preps = ingest.device_image_loader(a, loader, device, to_runner=a.reuse_backbones)
         if a.reuse_backbones:
             from magnet_amd.sequence import SequenceRunner
-            runner = SequenceRunner(model, a.pool_frames, graph=True) if a.graph else SequenceRunner(model, a.pool_frames)
+            kw = {**({"graph": True} if a.graph else {}), **({"image_prep": preps} if preps is not None else {})}
+            runner = SequenceRunner(model, a.pool_frames, **kw)
         title = "scannet-format folder %s (%d windows) V=%d D=%d iters=%d" % (a.dataset_path, len(ds), a.V, a.D, a.iters)
     else:
         loader = SyntheticWindows((a.frames + a.batch - 1) // a.batch, a.batch, a.V, a.input_height, a.input_width, nan_every=3)

@@ -51,7 +51,8 @@ extern "C" {
                                            * v500 REMOVED the v302 fp16 + block-scaled e4m3 operand format (the last three fields of MagnetConvArgs and its
                                            * pack entry point) and magnet_conv1x1_chain: MagnetConvArgs, and with it every struct that embeds it, is shorter.
                                            * Added since, with no struct change and therefore under the same number: magnet_conv_mfma_f16e,
-                                           * magnet_enc_stem_f16, magnet_dwconv_cl_f16, magnet_se_scale_f16 (the encoder's fp16 single-plane mode). */
+                                           * magnet_enc_stem_f16, magnet_dwconv_cl_f16, magnet_se_scale_f16 (the encoder's fp16 single-plane mode);
+                                           * magnet_image_prep_u8 with its own new MagnetImagePrepArgs (uint8 camera frames to the backbones' input). */
 
 enum {                                     /* storage dtype of channel-last feature maps */
     MAGNET_FEAT_F32  = 0,
@@ -891,6 +892,39 @@ typedef struct MagnetScatterFramesArgs {
     void          *pool_xd3_lo;
 } MagnetScatterFramesArgs;
 MAGNET_API int magnet_scatter_frames(const MagnetScatterFramesArgs *args, void *stream);
+
+/* magnet_image_prep_u8: N raw camera frames of one size, uint8 channel-last (N, Hin, Win, 3), to the (N, 3, Hout, Wout) fp32 NCHW
+ * tensor the backbones read, in one launch (csrc/image_prep.hip; magnet_amd/ingest.py builds the tables):
+ *   1. crop: the box (crop_left, crop_top, crop_w, crop_h) of every frame, the semantics of PIL's im.crop(box) for a box inside the
+ *      frame.  No byte outside the box is read.
+ *   2. resize to (Wout, Hout) as PIL's Image.resize(..., resample=BILINEAR) does on 8-bit images: horizontal pass, then vertical pass
+ *      over its uint8 result, each   ss = (1 << 21) + sum_k coef[xx][k] * pixel[xmin[xx] + k];  out = clamp(ss >> 22, 0, 255)   in
+ *      int32.  coef_* is (out size, k*) int32, bounds_* (out size, 2) int32 rows of (xmin, n) with n <= k* taps used, both relative
+ *      to the crop box.  A pass whose output size equals its input size (crop_w == Wout, crop_h == Hout) is skipped, its tables are
+ *      not read and may be NULL, its k* is ignored.  Otherwise k* must be 2 * ceil(max(in / out, 1)) + 1, PIL's row length, and at
+ *      most MAGNET_IMAGE_PREP_KMAX: a larger downscale ratio returns MAGNET_E_SHAPE.
+ *   3. normalise: out[n][c][y][x] = lut[c * 256 + v] for the 8-bit result v; lut is (3, 256) fp32, the caller's normalisation of
+ *      every byte value per channel.  The kernel does no floating-point arithmetic.
+ * src_pitch: bytes between rows (>= 3 * Win), src_frame: bytes between frames (>= Hin * src_pitch).  The tables and out 4-byte
+ * aligned.  The tables are read from device memory unchecked by the host; the kernel clamps every window into the crop box and every
+ * tap count to k*, so tables other than the ones above give other pixels, never an access outside src's crop box or out.
+ * Limits: N <= 65535, every size <= 32768 (MAGNET_E_DIM). */
+#define MAGNET_IMAGE_PREP_KMAX 17          /* taps per axis: downscale ratios up to 8 */
+typedef struct MagnetImagePrepArgs {
+    const uint8_t *src;                    /* (N, Hin, Win, 3) uint8 through src_frame / src_pitch */
+    int64_t        src_pitch, src_frame;   /* bytes */
+    const int32_t *coef_x;                 /* (Wout, kx) */
+    const int32_t *bounds_x;               /* (Wout, 2) */
+    const int32_t *coef_y;                 /* (Hout, ky) */
+    const int32_t *bounds_y;               /* (Hout, 2) */
+    const float   *lut;                    /* (3, 256) */
+    float         *out;                    /* (N, 3, Hout, Wout) dense */
+    int32_t        N, Hin, Win;
+    int32_t        crop_left, crop_top, crop_w, crop_h;
+    int32_t        Hout, Wout;
+    int32_t        kx, ky;
+} MagnetImagePrepArgs;
+MAGNET_API int magnet_image_prep_u8(const MagnetImagePrepArgs *args, void *stream);
 
 /* FnetLoss: the tail of the F-Net training step (train_FNet.py:95-104) on the raw volume x (B, D, h, w) of
  * magnet_cost_volume_cw(mode = 1): p = softmax over the D bins, pred = sum_j p_j d_j, loss = mean over the valid pixels of

@@ -62,6 +62,7 @@ hipError_t launch_dnet_nll_forward(const MagnetDnetNllArgs&, hipStream_t);
 hipError_t launch_dnet_nll_backward(const MagnetDnetNllArgs&, hipStream_t);
 hipError_t launch_gather_views(const MagnetGatherViewsArgs&, hipStream_t);
 hipError_t launch_scatter_frames(const MagnetScatterFramesArgs&, hipStream_t);
+hipError_t launch_image_prep(const MagnetImagePrepArgs&, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -1212,6 +1213,41 @@ MAGNET_API int magnet_scatter_frames(const MagnetScatterFramesArgs* a, void* str
         return fail(MAGNET_E_ALIGN, "magnet_scatter_frames: slots and the (mu, sigma) tensors must be 4-byte aligned");
     hipError_t e = magnet::launch_scatter_frames(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_scatter_frames launch");
+}
+
+// PIL's coefficient row length for a pass from `in` to `out` pixels: 2 * ceil(max(in / out, 1)) + 1
+static int image_prep_taps(int in, int out) { return 2 * (in > out ? (in + out - 1) / out : 1) + 1; }
+
+MAGNET_API int magnet_image_prep_u8(const MagnetImagePrepArgs* a, void* stream) {
+    if (!a || !a->src || !a->lut || !a->out) return fail(MAGNET_E_NULL, "magnet_image_prep_u8: NULL pointer");
+    const int lim = 32768;
+    if (a->N <= 0 || a->N > 65535 || a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0 || a->Hin > lim || a->Win > lim ||
+        a->Hout > lim || a->Wout > lim)
+        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: bad dims N=%d Hin=%d Win=%d Hout=%d Wout=%d (N <= 65535, sizes in [1, %d])",
+                    a->N, a->Hin, a->Win, a->Hout, a->Wout, lim);
+    if (a->crop_left < 0 || a->crop_top < 0 || a->crop_w <= 0 || a->crop_h <= 0 || a->crop_left > a->Win - a->crop_w ||
+        a->crop_top > a->Hin - a->crop_h)
+        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: crop box left=%d top=%d %d x %d is not inside the %d x %d frame",
+                    a->crop_left, a->crop_top, a->crop_w, a->crop_h, a->Win, a->Hin);
+    if (a->src_pitch < 3LL * a->Win || (a->N > 1 && a->src_frame < a->src_pitch * a->Hin))
+        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: src_pitch=%lld src_frame=%lld do not hold a row of %d pixels / a frame of %d rows",
+                    (long long)a->src_pitch, (long long)a->src_frame, a->Win, a->Hin);
+    const bool horiz = a->crop_w != a->Wout, vert = a->crop_h != a->Hout;
+    const int kx = image_prep_taps(a->crop_w, a->Wout), ky = image_prep_taps(a->crop_h, a->Hout);
+    if ((horiz && kx > MAGNET_IMAGE_PREP_KMAX) || (vert && ky > MAGNET_IMAGE_PREP_KMAX))
+        return fail(MAGNET_E_SHAPE, "magnet_image_prep_u8: %d x %d -> %d x %d needs %d x %d taps, MAGNET_IMAGE_PREP_KMAX is %d per axis "
+                    "(downscale ratios up to %d)", a->crop_w, a->crop_h, a->Wout, a->Hout, horiz ? kx : 0, vert ? ky : 0,
+                    MAGNET_IMAGE_PREP_KMAX, (MAGNET_IMAGE_PREP_KMAX - 1) / 2);
+    if ((horiz && (!a->coef_x || !a->bounds_x)) || (vert && (!a->coef_y || !a->bounds_y)))
+        return fail(MAGNET_E_NULL, "magnet_image_prep_u8: a pass that resizes needs its coef and bounds tables");
+    if ((horiz && a->kx != kx) || (vert && a->ky != ky))
+        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: kx=%d ky=%d, the sizes imply rows of %d and %d taps", a->kx, a->ky,
+                    horiz ? kx : 0, vert ? ky : 0);
+    if ((reinterpret_cast<uintptr_t>(a->coef_x) | reinterpret_cast<uintptr_t>(a->bounds_x) | reinterpret_cast<uintptr_t>(a->coef_y) |
+         reinterpret_cast<uintptr_t>(a->bounds_y) | reinterpret_cast<uintptr_t>(a->lut) | reinterpret_cast<uintptr_t>(a->out)) & 3u)
+        return fail(MAGNET_E_ALIGN, "magnet_image_prep_u8: the tables and out must be 4-byte aligned");
+    hipError_t e = magnet::launch_image_prep(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_image_prep_u8 launch");
 }
 
 // ---- the D-Net's encoder (enc_kernels.hip) ----

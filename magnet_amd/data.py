@@ -100,9 +100,11 @@ def window_indices(center: int, n_views: int, window_radius: int, exists) -> lis
 class ScanNetFolder:
     """samples: list of (scene_name, frame_index).  __getitem__ -> (data_array, cam_intrins): a list of n_views + 1 dicts
     {'img' (3,H,W) normalised fp32, 'gt_dmap' (1,H,W) metres for the reference frame else 0.0, 'extM' (4,4) float64,
-    'scene_name', 'img_idx'} and the intrinsics dict — the structure of dataloader_scannet.py:155-217."""
+    'scene_name', 'img_idx'} and the intrinsics dict — the structure of dataloader_scannet.py:155-217.
+    raw_images=True (opt-in): 'img' is the decoded frame itself, a uint8 (Hraw, Wraw, 3) tensor, neither resized nor normalised —
+    magnet_amd.ingest.ImagePrep does both on the device, to the same bits.  Everything else of an item is unchanged."""
 
-    def __init__(self, root, samples, n_views=4, window_radius=20, input_hw=(480, 640), dpv_hw=(120, 160), raw_wh=None):
+    def __init__(self, root, samples, n_views=4, window_radius=20, input_hw=(480, 640), dpv_hw=(120, 160), raw_wh=None, raw_images=False):
         from PIL import Image  # noqa: F401  (fail early if Pillow is missing)
         self.root, self.samples = root, list(samples)
         self.n_views, self.window_radius = n_views, window_radius
@@ -110,6 +112,7 @@ class ScanNetFolder:
         self.dpv_h, self.dpv_w = dpv_hw
         self.raw_wh = dict(raw_wh or {})
         self.center = n_views // 2
+        self.raw_images = bool(raw_images)
 
     def __len__(self):
         return len(self.samples)
@@ -154,9 +157,14 @@ class ScanNetFolder:
         data_array = []
         for j, k in enumerate(frames):
             with Image.open(self._color(sdir, k)) as im:
-                rgb = im.convert("RGB").resize((self.img_w, self.img_h), resample=Image.BILINEAR)
-            img = torch.from_numpy(np.asarray(rgb).astype(np.float32) / 255.0).permute(2, 0, 1)
-            img = (img - mean) / std
+                rgb = im.convert("RGB")
+                if not self.raw_images:
+                    rgb = rgb.resize((self.img_w, self.img_h), resample=Image.BILINEAR)
+            if self.raw_images:
+                img = torch.from_numpy(np.array(rgb, dtype=np.uint8))           # (Hraw, Wraw, 3), a copy the tensor owns
+            else:
+                img = torch.from_numpy(np.asarray(rgb).astype(np.float32) / 255.0).permute(2, 0, 1)
+                img = (img - mean) / std
             if j == self.center:
                 with Image.open(self._depth(sdir, k)) as dm:
                     d = self._depth_metres(np.asarray(dm.resize((self.img_w, self.img_h), resample=Image.NEAREST)))
@@ -198,8 +206,13 @@ class SevenScenesFolder(ScanNetFolder):
 
 def collate(items):
     """What torch's default_collate makes of a list of (data_array, cam_intrins): per-frame dicts with a leading batch
-    dimension ('extM' becomes a (B,4,4) float64 tensor), intrinsics stacked to (B,3,3) / (B,3,hw)."""
+    dimension ('extM' becomes a (B,4,4) float64 tensor), intrinsics stacked to (B,3,3) / (B,3,hw).  The uint8 frames of
+    `raw_images=True` items stack to (B,Hraw,Wraw,3); one batch holds one raw size."""
     n_frames = len(items[0][0])
+    raw_sizes = {tuple(d["img"].shape[:2]) for it in items for d in it[0] if d["img"].dtype == torch.uint8}
+    if len(raw_sizes) > 1:
+        raise ValueError("collate: the raw frames of one batch have sizes %s; batch scenes of one raw size together (or use batch size 1)"
+                         % sorted(raw_sizes))
     data_array = []
     for f in range(n_frames):
         ds = [it[0][f] for it in items]

@@ -29,6 +29,7 @@ ACT_BASE, ACT_LEAKY_RELU, ACT_SILU = 0, 1, 2
 TILING_FLAT, TILING_BM256, TILING_BM64 = 1, 2, 4
 SPLITK_MAX, SPLITK_MIN_CHUNKS = 8, 2
 METRICS_SIGMA, METRICS_VARIANCE, METRICS_NONE = 0, 1, 2
+IMAGE_PREP_KMAX = 17                                             # taps per axis of magnet_image_prep_u8: downscale ratios up to 8
 
 
 class MagnetError(RuntimeError):
@@ -225,6 +226,16 @@ class MagnetScatterFramesArgs(ctypes.Structure):
                 ("pool_feat", ctypes.c_void_p), ("pool_gmm", ctypes.c_void_p), ("pool_xd3_hi", ctypes.c_void_p), ("pool_xd3_lo", ctypes.c_void_p)]
 
 
+class MagnetImagePrepArgs(ctypes.Structure):
+    """Mirror of `struct MagnetImagePrepArgs` (include/magnet_hip.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("src_pitch", ctypes.c_int64), ("src_frame", ctypes.c_int64),
+                ("coef_x", ctypes.c_void_p), ("bounds_x", ctypes.c_void_p), ("coef_y", ctypes.c_void_p), ("bounds_y", ctypes.c_void_p),
+                ("lut", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("N", ctypes.c_int32), ("Hin", ctypes.c_int32), ("Win", ctypes.c_int32),
+                ("crop_left", ctypes.c_int32), ("crop_top", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("Hout", ctypes.c_int32), ("Wout", ctypes.c_int32), ("kx", ctypes.c_int32), ("ky", ctypes.c_int32)]
+
+
 class MagnetDwConvArgs(ctypes.Structure):
     """Mirror of `struct MagnetDwConvArgs` (include/magnet_hip.h)."""
     _fields_ = [("in_hi", ctypes.c_void_p), ("in_lo", ctypes.c_void_p), ("wgt", ctypes.c_void_p), ("bias", ctypes.c_void_p),
@@ -310,6 +321,7 @@ _PROTOS = {
     "magnet_se_scale_f16": (_C, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
     "magnet_gather_views": (_C, [_S(MagnetGatherViewsArgs), _P]),
     "magnet_scatter_frames": (_C, [_S(MagnetScatterFramesArgs), _P]),
+    "magnet_image_prep_u8": (_C, [_S(MagnetImagePrepArgs), _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_fnet_loss_backward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_bn_sync_moments": (_C, [_S(MagnetBnTrainArgs), _P, _P]),
@@ -1581,6 +1593,45 @@ def scatter_frames(slots, pool_feat=None, pool_gmm=None, pool_xd3=None, feat=Non
     if any(x.device != t.device for x in used):
         raise MagnetError("scatter_frames: all tensors must be on the same device")
     _launch("magnet_scatter_frames", t, ctypes.byref(a))
+
+
+# ---- image ingest (include/magnet_hip.h: magnet_image_prep_u8; csrc/image_prep.hip; magnet_amd/ingest.py) ------------------------------------------
+def image_prep_u8(frames, out, crop, tables_x, tables_y, lut):
+    """One launch: uint8 channel-last frames (N, Hin, Win, 3) (the last two dimensions dense, rows and frames through their strides)
+    -> out (N, 3, Hout, Wout) fp32: crop = (left, top, width, height), PIL's 8-bit BILINEAR resize of the box to (Wout, Hout) through
+    tables_x / tables_y = (coef (out size, k) int32, bounds (out size, 2) int32), or None for a pass whose size does not change, then
+    out[n, c, y, x] = lut[c, v] with lut (3, 256) fp32.  magnet_amd.ingest.ImagePrep builds the tables and owns them."""
+    f = frames
+    if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3:
+        raise MagnetError("image_prep_u8: frames must be a uint8 GPU tensor (N, Hin, Win, 3)")
+    N, Hin, Win, _ = (int(v) for v in f.shape)
+    if N < 1 or f.stride(3) != 1 or f.stride(2) != 3 or f.stride(1) < 3 * Win or (N > 1 and f.stride(0) < f.stride(1) * Hin):
+        raise MagnetError(f"image_prep_u8: frames {tuple(f.shape)} with strides {tuple(f.stride())}: pixels must be dense and rows and frames must not overlap")
+    o = _dev(out, "out", torch.float32)
+    if o.dim() != 4 or o.shape[0] != N or o.shape[1] != 3:
+        raise MagnetError(f"image_prep_u8: out has shape {tuple(o.shape)}, expected ({N}, 3, Hout, Wout)")
+    Hout, Wout = int(o.shape[2]), int(o.shape[3])
+    left, top, cw, ch = (int(v) for v in crop)
+    lut = _dev(lut, "lut", torch.float32)
+    if tuple(lut.shape) != (3, 256):
+        raise MagnetError(f"image_prep_u8: lut has shape {tuple(lut.shape)}, expected (3, 256)")
+    a = MagnetImagePrepArgs(src=f.data_ptr(), src_pitch=f.stride(1), src_frame=f.stride(0), lut=lut.data_ptr(), out=o.data_ptr(),
+                            N=N, Hin=Hin, Win=Win, crop_left=left, crop_top=top, crop_w=cw, crop_h=ch, Hout=Hout, Wout=Wout)
+    used = [f, o, lut]
+    for axis, tables, n_in, n_out in (("x", tables_x, cw, Wout), ("y", tables_y, ch, Hout)):
+        if (tables is None) != (n_in == n_out):
+            raise MagnetError(f"image_prep_u8: the {axis} pass goes from {n_in} to {n_out} pixels: it takes tables exactly when the size changes")
+        if tables is None:
+            continue
+        coef, bounds = _dev(tables[0], f"coef_{axis}", torch.int32), _dev(tables[1], f"bounds_{axis}", torch.int32)
+        if coef.dim() != 2 or coef.shape[0] != n_out or tuple(bounds.shape) != (n_out, 2):
+            raise MagnetError(f"image_prep_u8: coef_{axis} {tuple(coef.shape)} / bounds_{axis} {tuple(bounds.shape)}, expected ({n_out}, k) and ({n_out}, 2)")
+        setattr(a, "coef_" + axis, coef.data_ptr()); setattr(a, "bounds_" + axis, bounds.data_ptr()); setattr(a, "k" + axis, int(coef.shape[1]))
+        used += [coef, bounds]
+    if any(x.device != f.device for x in used):
+        raise MagnetError("image_prep_u8: all tensors must be on the same device")
+    _launch("magnet_image_prep_u8", f, ctypes.byref(a))
+    return out
 
 
 # ---- the D-Net's encoder (EfficientNet-B5): stem, depthwise convolution, squeeze-excite --------------------------------

@@ -420,10 +420,14 @@ class SequenceRunner:
     caches' (data_ptr, _version) keys) that is recomputed on the host before every replay: using the model eagerly with another
     shape, an optimiser step or load_state_dict between two steps costs one new capture, never a wrong answer.  The timing sinks
     (FNetMFMA.event_sink and the like) must be off.  Not captured: the caller's encoder; uint8 ingest.
+    image_prep (opt-in; magnet_amd.ingest.ImagePrep or ImagePrepSet): add() and forward() then also take the decoded camera frames,
+    uint8 (N, Hin, Win, 3) on the GPU or the host, in place of normalised images.  The frames the pool lacks are selected first and
+    only those are prepared, by one eager launch into a buffer of this runner (`prepared` counts them); from there on the step is
+    the one above, graph=True included.  uint8 frames without an image_prep raise.
     `graph_stats`: None without graph, else {"captures": {key: count}, "replays": {key: count}} with keys
     ("add", n, image shape) and ("refine", B, V, mode); a step that captures is not counted as a replay."""
 
-    def __init__(self, model, capacity, graph=False):
+    def __init__(self, model, capacity, graph=False, image_prep=None):
         if getattr(model, "conv_backend", None) != "mfma":
             raise MagnetError("SequenceRunner gathers into the matrix-core path's buffers: it needs a MAGNET with conv_backend='mfma'")
         if model.downsample_ratio != 4:
@@ -438,6 +442,12 @@ class SequenceRunner:
         self.encoded = 0                                 # images run through the backbones so far
         self._dst = {}                                   # (B, V) -> the gather's destination tensors, reused from call to call
         self._stage = None                               # zero-bordered x_d3 staging planes for the most frames staged so far
+        if image_prep is not None and not (callable(getattr(image_prep, "prep", None)) and callable(getattr(image_prep, "check", None))
+                                           and hasattr(image_prep, "out_hw")):
+            raise MagnetError(f"SequenceRunner: image_prep must be a magnet_amd.ingest.ImagePrep or ImagePrepSet, got {type(image_prep).__name__}")
+        self.image_prep = image_prep
+        self.prepared = 0                                # uint8 frames run through image_prep so far
+        self._prep_buf = None                            # (frames, 3, H, W) fp32: where image_prep writes the new frames of a call
         self.graph = graph
         self.graph_stats = {"captures": {}, "replays": {}} if graph else None
         self._graphs = {}                                # key -> _Captured
@@ -451,14 +461,20 @@ class SequenceRunner:
                               "training goes through MAGNET.forward")
 
     @staticmethod
-    def _take(parts, idx):
-        """Images `idx` (ascending positions in the concatenation of the tensors `parts`) as one tensor, by slices only."""
+    def _take_runs(parts, idx):
+        """Images `idx` (ascending positions in the concatenation of the tensors `parts`) as slices of `parts`, one per run."""
         out, first = [], 0
         for t in parts:
             n = t.shape[0]
             for _, lo, k in _runs([i - first for i in idx if first <= i < first + n]):
                 out.append(t[lo:lo + k])
             first += n
+        return out
+
+    @staticmethod
+    def _take(parts, idx):
+        """Images `idx` as one tensor, by slices only."""
+        out = SequenceRunner._take_runs(parts, idx)
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
 
     @staticmethod
@@ -483,14 +499,26 @@ class SequenceRunner:
         named = {fid for fid in frame_ids if fid is not None}
         if len(named) > self.capacity:
             raise MagnetError(f"add: the call names {len(named)} distinct frames, the pool holds {self.capacity}")
-        if any(not t.is_cuda for t in parts):
+        raw = any(t.dtype == torch.uint8 for t in parts)
+        if raw:
+            if self.image_prep is None:
+                raise MagnetError("add: uint8 frames need SequenceRunner(..., image_prep=magnet_amd.ingest.ImagePrep(...)); without one the "
+                                  "images must be normalised fp32 (N, 3, H, W)")
+            if len({(t.dtype, t.device, tuple(t.shape[1:])) for t in parts}) != 1:
+                raise MagnetError("add: the uint8 frames of one call must share raw size and device")
+            for t in parts:
+                self.image_prep.check(t)
+        elif any(not t.is_cuda for t in parts):
             raise MagnetError("add: images must be on the GPU (no CPU fallback)")
         idx = self.pool.missing(frame_ids) if self.pool is not None else _first_missing(frame_ids, ())
         if not idx:
             if self.pool is not None:
                 self.pool.assign(frame_ids)              # marks them used
             return 0
-        sel = self._take(parts, idx)
+        if raw:
+            sel = self._prepare(self._take_runs(parts, idx))
+        else:
+            sel = self._take(parts, idx)
         n, dev = sel.shape[0], sel.device
         if self.graph:
             return self._add_graphed(frame_ids, sel)
@@ -515,6 +543,33 @@ class SequenceRunner:
             raise
         self.encoded += n
         return n
+
+    def _prepare(self, runs):
+        """The uint8 frames the pool lacks (`runs`: slices of the caller's tensors) -> their normalised (n, 3, H, W) images in this
+        runner's buffer: one launch.  Several runs of host frames are uploaded run by run into one device tensor (a pinned run without
+        blocking): concatenating them on the host first would make a pageable copy."""
+        n = sum(t.shape[0] for t in runs)
+        host = not runs[0].is_cuda
+        dev = runs[0].device if not host else (self.pool.device if self.pool is not None else torch.device(self.image_prep.device))
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if len(runs) == 1:
+            frames_u8 = runs[0]
+        elif host:
+            frames_u8 = torch.empty((n,) + tuple(runs[0].shape[1:]), dtype=torch.uint8, device=dev)
+            first = 0
+            for t in runs:
+                frames_u8[first:first + t.shape[0]].copy_(t, non_blocking=t.is_pinned())
+                first += t.shape[0]
+        else:
+            frames_u8 = torch.cat(runs, dim=0)
+        buf = self._prep_buf
+        if buf is None or buf.shape[0] < n or buf.device != dev or tuple(buf.shape[2:]) != tuple(self.image_prep.out_hw):
+            self._prep_buf = None                        # let go of the smaller one first
+            buf = self._prep_buf = torch.empty((n, 3) + tuple(self.image_prep.out_hw), dtype=torch.float32, device=dev)
+        out = self.image_prep.prep(frames_u8, out=buf[:n])
+        self.prepared += n
+        return out
 
     def _stage_planes(self, n):
         """The zero-bordered (n rows, 256) x_d3 staging planes for n frames."""
