@@ -52,7 +52,9 @@ extern "C" {
                                            * pack entry point) and magnet_conv1x1_chain: MagnetConvArgs, and with it every struct that embeds it, is shorter.
                                            * Added since, with no struct change and therefore under the same number: magnet_conv_mfma_f16e,
                                            * magnet_enc_stem_f16, magnet_dwconv_cl_f16, magnet_se_scale_f16 (the encoder's fp16 single-plane mode);
-                                           * magnet_image_prep_u8 with its own new MagnetImagePrepArgs (uint8 camera frames to the backbones' input). */
+                                           * magnet_image_prep_u8 with its own new MagnetImagePrepArgs (uint8 camera frames to the backbones' input);
+                                           * magnet_train_prep_u8 and magnet_depth_prep_u16 with their own new MagnetTrainPrepArgs and MagnetDepthPrepArgs
+                                           * (training samples: the same resize with a per-frame flip, crop window and augmentation table; ground-truth depth). */
 
 enum {                                     /* storage dtype of channel-last feature maps */
     MAGNET_FEAT_F32  = 0,
@@ -925,6 +927,63 @@ typedef struct MagnetImagePrepArgs {
     int32_t        kx, ky;
 } MagnetImagePrepArgs;
 MAGNET_API int magnet_image_prep_u8(const MagnetImagePrepArgs *args, void *stream);
+
+/* Training samples (csrc/image_prep.hip, csrc/depth_prep.hip; magnet_amd/ingest.py: TrainPrep).  Both entry points read one record per
+ * frame from device memory,
+ *     frame_params: int32 (N, 4) = (lut_index, flip, win_x, win_y),
+ * and produce, of the Hres x Wres image R that the resize of the crop box gives (the crop box itself where the sizes are equal), the
+ * window   O[y][x] = R[win_y + y][flip ? Wres - 1 - (win_x + x) : win_x + x],   0 <= y < Hout, 0 <= x < Wout:   a horizontal flip
+ * first, then a crop window of the flipped image.  The records are not trusted: lut_index is clamped to [0, n_luts), flip is any
+ * non-zero value, the window origin is clamped into [0, Wres - Wout] x [0, Hres - Hout]; with records that respect these ranges no
+ * clamp acts.
+ *
+ * magnet_train_prep_u8: magnet_image_prep_u8's computation (the same crop, the same two integer passes from the same tables, which are
+ * built for crop_w -> Wres and crop_h -> Hres and have Wres / Hres rows; the same limits and the same clamps on the tables) with
+ *     out[n][c][y][x] = luts[lut_index[n]][c][O_c[y][x]],   luts (n_luts, 3, 256) fp32:
+ * the augmentation of a sample (gamma, brightness, colour, clip) and the normalisation are functions of (byte value, channel) and
+ * arrive as one table per augmented sample.  No floating-point arithmetic happens on the device.
+ *
+ * magnet_depth_prep_u16: uint16 depth maps (N, Hin, Win) through src_pitch / src_frame (in ELEMENTS), the crop box, and PIL's NEAREST
+ * resize as index tables: idx_x (Wres) / idx_y (Hres) int32 hold the source column / row inside the crop box of every resized column /
+ * row; each is NULL exactly when that axis is not resized (crop_w == Wres / crop_h == Hres).  Every index is clamped into the box.
+ *     out[n][0][y][x] = (v == invalid_code ? 0 : (float)v) / divisor,   v = O[y][x],
+ * one correctly rounded fp32 division (not a multiplication by a reciprocal).  invalid_code -1: none.  divisor finite and > 0.
+ * frame_params' lut_index is ignored.  Limits as magnet_image_prep_u8's: N <= 65535, every size <= 32768; the tables, frame_params and
+ * out 4-byte aligned, the uint16 source 2-byte aligned. */
+typedef struct MagnetTrainPrepArgs {
+    const uint8_t *src;                    /* (N, Hin, Win, 3) uint8 through src_frame / src_pitch */
+    int64_t        src_pitch, src_frame;   /* bytes */
+    const int32_t *coef_x;                 /* (Wres, kx) */
+    const int32_t *bounds_x;               /* (Wres, 2) */
+    const int32_t *coef_y;                 /* (Hres, ky) */
+    const int32_t *bounds_y;               /* (Hres, 2) */
+    const float   *luts;                   /* (n_luts, 3, 256) */
+    const int32_t *frame_params;           /* (N, 4) */
+    float         *out;                    /* (N, 3, Hout, Wout) dense */
+    int32_t        N, Hin, Win;
+    int32_t        crop_left, crop_top, crop_w, crop_h;
+    int32_t        Hres, Wres;             /* the resized image the tables are built for */
+    int32_t        Hout, Wout;             /* the window: Hout <= Hres, Wout <= Wres */
+    int32_t        kx, ky;
+    int32_t        n_luts;
+} MagnetTrainPrepArgs;
+MAGNET_API int magnet_train_prep_u8(const MagnetTrainPrepArgs *args, void *stream);
+
+typedef struct MagnetDepthPrepArgs {
+    const uint16_t *src;                   /* (N, Hin, Win) uint16 through src_frame / src_pitch */
+    int64_t        src_pitch, src_frame;   /* elements */
+    const int32_t *idx_x;                  /* (Wres), or NULL when crop_w == Wres */
+    const int32_t *idx_y;                  /* (Hres), or NULL when crop_h == Hres */
+    const int32_t *frame_params;           /* (N, 4) */
+    float         *out;                    /* (N, 1, Hout, Wout) dense */
+    int32_t        N, Hin, Win;
+    int32_t        crop_left, crop_top, crop_w, crop_h;
+    int32_t        Hres, Wres;
+    int32_t        Hout, Wout;
+    int32_t        invalid_code;           /* a sample equal to it becomes 0; -1: none */
+    float          divisor;
+} MagnetDepthPrepArgs;
+MAGNET_API int magnet_depth_prep_u16(const MagnetDepthPrepArgs *args, void *stream);
 
 /* FnetLoss: the tail of the F-Net training step (train_FNet.py:95-104) on the raw volume x (B, D, h, w) of
  * magnet_cost_volume_cw(mode = 1): p = softmax over the D bins, pred = sum_j p_j d_j, loss = mean over the valid pixels of

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmagnet_hip.so")
 DEV_LIB = os.path.join(HERE, "libmagnet_hip_dev.so")      # the same sources with -DMAGNET_DEV, loaded only by tools/ (lib.use_dev_build())
-SOURCES = ["api.hip", "cost_volume.hip", "cost_volume_worklist.hip", "cost_volume_cand.hip", "cost_volume_fast.hip", "cost_volume_fast64.hip", "cost_volume_v3.hip", "cost_volume_f_bwd.hip", "cost_volume_f_gather.hip", "conv_mfma.hip", "fnet_kernels.hip", "elementwise.hip", "train_bwd.hip", "train_fnet_fwd.hip", "train_fnet_bwd.hip", "dnet_kernels.hip", "fnet_loss.hip", "dnet_loss.hip", "frame_pool.hip", "pack.hip", "enc_kernels.hip", "image_prep.hip"]
+SOURCES = ["api.hip", "cost_volume.hip", "cost_volume_worklist.hip", "cost_volume_cand.hip", "cost_volume_fast.hip", "cost_volume_fast64.hip", "cost_volume_v3.hip", "cost_volume_f_bwd.hip", "cost_volume_f_gather.hip", "conv_mfma.hip", "fnet_kernels.hip", "elementwise.hip", "train_bwd.hip", "train_fnet_fwd.hip", "train_fnet_bwd.hip", "dnet_kernels.hip", "fnet_loss.hip", "dnet_loss.hip", "frame_pool.hip", "pack.hip", "enc_kernels.hip", "image_prep.hip", "depth_prep.hip"]
 HEADERS = ["cv_common.hpp", "cv_fast_common.hpp", "cv_runs.hpp", "conv_common.hpp", "enc_common.hpp", "warp_math.hpp", "pack.hpp", os.path.join("..", "..", "include", "magnet_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fvisibility=hidden",

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <initializer_list>
 #include "cv_common.hpp"
 #include "conv_common.hpp"
 #include "pack.hpp"
@@ -63,6 +64,8 @@ hipError_t launch_dnet_nll_backward(const MagnetDnetNllArgs&, hipStream_t);
 hipError_t launch_gather_views(const MagnetGatherViewsArgs&, hipStream_t);
 hipError_t launch_scatter_frames(const MagnetScatterFramesArgs&, hipStream_t);
 hipError_t launch_image_prep(const MagnetImagePrepArgs&, hipStream_t);
+hipError_t launch_train_prep(const MagnetTrainPrepArgs&, hipStream_t);
+hipError_t launch_depth_prep(const MagnetDepthPrepArgs&, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -1218,36 +1221,96 @@ MAGNET_API int magnet_scatter_frames(const MagnetScatterFramesArgs* a, void* str
 // PIL's coefficient row length for a pass from `in` to `out` pixels: 2 * ceil(max(in / out, 1)) + 1
 static int image_prep_taps(int in, int out) { return 2 * (in > out ? (in + out - 1) / out : 1) + 1; }
 
-MAGNET_API int magnet_image_prep_u8(const MagnetImagePrepArgs* a, void* stream) {
-    if (!a || !a->src || !a->lut || !a->out) return fail(MAGNET_E_NULL, "magnet_image_prep_u8: NULL pointer");
+// ---- frame preparation (image_prep.hip, depth_prep.hip): what the three entry points check alike ----
+// The frames of N x Hin x Win pixels of `px` units (bytes or elements) each, their crop box, their pitches, and the size Hres x Wres
+// the crop box is resized to.
+static int prep_frames_check(const char* who, int N, int Hin, int Win, int Hres, int Wres, int left, int top, int cw, int ch,
+                             long long pitch, long long frame, int px) {
     const int lim = 32768;
-    if (a->N <= 0 || a->N > 65535 || a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0 || a->Hin > lim || a->Win > lim ||
-        a->Hout > lim || a->Wout > lim)
-        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: bad dims N=%d Hin=%d Win=%d Hout=%d Wout=%d (N <= 65535, sizes in [1, %d])",
-                    a->N, a->Hin, a->Win, a->Hout, a->Wout, lim);
-    if (a->crop_left < 0 || a->crop_top < 0 || a->crop_w <= 0 || a->crop_h <= 0 || a->crop_left > a->Win - a->crop_w ||
-        a->crop_top > a->Hin - a->crop_h)
-        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: crop box left=%d top=%d %d x %d is not inside the %d x %d frame",
-                    a->crop_left, a->crop_top, a->crop_w, a->crop_h, a->Win, a->Hin);
-    if (a->src_pitch < 3LL * a->Win || (a->N > 1 && a->src_frame < a->src_pitch * a->Hin))
-        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: src_pitch=%lld src_frame=%lld do not hold a row of %d pixels / a frame of %d rows",
-                    (long long)a->src_pitch, (long long)a->src_frame, a->Win, a->Hin);
-    const bool horiz = a->crop_w != a->Wout, vert = a->crop_h != a->Hout;
-    const int kx = image_prep_taps(a->crop_w, a->Wout), ky = image_prep_taps(a->crop_h, a->Hout);
+    if (N <= 0 || N > 65535 || Hin <= 0 || Win <= 0 || Hres <= 0 || Wres <= 0 || Hin > lim || Win > lim || Hres > lim || Wres > lim)
+        return fail(MAGNET_E_DIM, "%s: bad dims N=%d Hin=%d Win=%d resized to H=%d W=%d (N <= 65535, sizes in [1, %d])", who, N, Hin, Win, Hres,
+                    Wres, lim);
+    if (left < 0 || top < 0 || cw <= 0 || ch <= 0 || left > Win - cw || top > Hin - ch)
+        return fail(MAGNET_E_DIM, "%s: crop box left=%d top=%d %d x %d is not inside the %d x %d frame", who, left, top, cw, ch, Win, Hin);
+    if (pitch < (long long)px * Win || (N > 1 && frame < pitch * Hin))
+        return fail(MAGNET_E_DIM, "%s: src_pitch=%lld src_frame=%lld do not hold a row of %d pixels / a frame of %d rows", who, pitch, frame,
+                    Win, Hin);
+    return 0;
+}
+
+// The window of the training forms inside the resized image.
+static int prep_window_check(const char* who, int Hres, int Wres, int Hout, int Wout) {
+    if (Hout <= 0 || Wout <= 0 || Hout > Hres || Wout > Wres)
+        return fail(MAGNET_E_DIM, "%s: the window %d x %d is not inside the resized %d x %d image", who, Wout, Hout, Wres, Hres);
+    return 0;
+}
+
+// The two BILINEAR passes crop_w -> Wres and crop_h -> Hres: tap counts within the kernel's limit, tables exactly for a pass that
+// resizes, row lengths what the sizes imply.
+static int prep_passes_check(const char* who, int cw, int ch, int Hres, int Wres, const int32_t* coef_x, const int32_t* bounds_x,
+                             const int32_t* coef_y, const int32_t* bounds_y, int akx, int aky) {
+    const bool horiz = cw != Wres, vert = ch != Hres;
+    const int kx = image_prep_taps(cw, Wres), ky = image_prep_taps(ch, Hres);
     if ((horiz && kx > MAGNET_IMAGE_PREP_KMAX) || (vert && ky > MAGNET_IMAGE_PREP_KMAX))
-        return fail(MAGNET_E_SHAPE, "magnet_image_prep_u8: %d x %d -> %d x %d needs %d x %d taps, MAGNET_IMAGE_PREP_KMAX is %d per axis "
-                    "(downscale ratios up to %d)", a->crop_w, a->crop_h, a->Wout, a->Hout, horiz ? kx : 0, vert ? ky : 0,
+        return fail(MAGNET_E_SHAPE, "%s: %d x %d -> %d x %d needs %d x %d taps, MAGNET_IMAGE_PREP_KMAX is %d per axis "
+                    "(downscale ratios up to %d)", who, cw, ch, Wres, Hres, horiz ? kx : 0, vert ? ky : 0,
                     MAGNET_IMAGE_PREP_KMAX, (MAGNET_IMAGE_PREP_KMAX - 1) / 2);
-    if ((horiz && (!a->coef_x || !a->bounds_x)) || (vert && (!a->coef_y || !a->bounds_y)))
-        return fail(MAGNET_E_NULL, "magnet_image_prep_u8: a pass that resizes needs its coef and bounds tables");
-    if ((horiz && a->kx != kx) || (vert && a->ky != ky))
-        return fail(MAGNET_E_DIM, "magnet_image_prep_u8: kx=%d ky=%d, the sizes imply rows of %d and %d taps", a->kx, a->ky,
-                    horiz ? kx : 0, vert ? ky : 0);
-    if ((reinterpret_cast<uintptr_t>(a->coef_x) | reinterpret_cast<uintptr_t>(a->bounds_x) | reinterpret_cast<uintptr_t>(a->coef_y) |
-         reinterpret_cast<uintptr_t>(a->bounds_y) | reinterpret_cast<uintptr_t>(a->lut) | reinterpret_cast<uintptr_t>(a->out)) & 3u)
-        return fail(MAGNET_E_ALIGN, "magnet_image_prep_u8: the tables and out must be 4-byte aligned");
+    if ((horiz && (!coef_x || !bounds_x)) || (vert && (!coef_y || !bounds_y)))
+        return fail(MAGNET_E_NULL, "%s: a pass that resizes needs its coef and bounds tables", who);
+    if ((horiz && akx != kx) || (vert && aky != ky))
+        return fail(MAGNET_E_DIM, "%s: kx=%d ky=%d, the sizes imply rows of %d and %d taps", who, akx, aky, horiz ? kx : 0, vert ? ky : 0);
+    return 0;
+}
+
+static bool aligned4(std::initializer_list<const void*> ps) {
+    uintptr_t bits = 0;
+    for (const void* p : ps) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 3u) == 0;
+}
+
+MAGNET_API int magnet_image_prep_u8(const MagnetImagePrepArgs* a, void* stream) {
+    const char* who = "magnet_image_prep_u8";
+    if (!a || !a->src || !a->lut || !a->out) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (int r = prep_frames_check(who, a->N, a->Hin, a->Win, a->Hout, a->Wout, a->crop_left, a->crop_top, a->crop_w, a->crop_h,
+                                  a->src_pitch, a->src_frame, 3)) return r;
+    if (int r = prep_passes_check(who, a->crop_w, a->crop_h, a->Hout, a->Wout, a->coef_x, a->bounds_x, a->coef_y, a->bounds_y, a->kx, a->ky))
+        return r;
+    if (!aligned4({a->coef_x, a->bounds_x, a->coef_y, a->bounds_y, a->lut, a->out}))
+        return fail(MAGNET_E_ALIGN, "%s: the tables and out must be 4-byte aligned", who);
     hipError_t e = magnet::launch_image_prep(*a, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "magnet_image_prep_u8 launch");
+}
+
+MAGNET_API int magnet_train_prep_u8(const MagnetTrainPrepArgs* a, void* stream) {
+    const char* who = "magnet_train_prep_u8";
+    if (!a || !a->src || !a->luts || !a->frame_params || !a->out) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (int r = prep_frames_check(who, a->N, a->Hin, a->Win, a->Hres, a->Wres, a->crop_left, a->crop_top, a->crop_w, a->crop_h,
+                                  a->src_pitch, a->src_frame, 3)) return r;
+    if (int r = prep_window_check(who, a->Hres, a->Wres, a->Hout, a->Wout)) return r;
+    if (a->n_luts < 1) return fail(MAGNET_E_DIM, "%s: n_luts=%d, at least one table is needed", who, a->n_luts);
+    if (int r = prep_passes_check(who, a->crop_w, a->crop_h, a->Hres, a->Wres, a->coef_x, a->bounds_x, a->coef_y, a->bounds_y, a->kx, a->ky))
+        return r;
+    if (!aligned4({a->coef_x, a->bounds_x, a->coef_y, a->bounds_y, a->luts, a->frame_params, a->out}))
+        return fail(MAGNET_E_ALIGN, "%s: the tables, frame_params and out must be 4-byte aligned", who);
+    hipError_t e = magnet::launch_train_prep(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_train_prep_u8 launch");
+}
+
+MAGNET_API int magnet_depth_prep_u16(const MagnetDepthPrepArgs* a, void* stream) {
+    const char* who = "magnet_depth_prep_u16";
+    if (!a || !a->src || !a->frame_params || !a->out) return fail(MAGNET_E_NULL, "%s: NULL pointer", who);
+    if (int r = prep_frames_check(who, a->N, a->Hin, a->Win, a->Hres, a->Wres, a->crop_left, a->crop_top, a->crop_w, a->crop_h,
+                                  a->src_pitch, a->src_frame, 1)) return r;
+    if (int r = prep_window_check(who, a->Hres, a->Wres, a->Hout, a->Wout)) return r;
+    if (!(a->divisor > 0.0f) || !__builtin_isfinite(a->divisor))
+        return fail(MAGNET_E_DIM, "%s: divisor=%g must be finite and positive", who, (double)a->divisor);
+    if ((a->idx_x == nullptr) != (a->crop_w == a->Wres) || (a->idx_y == nullptr) != (a->crop_h == a->Hres))
+        return fail(MAGNET_E_NULL, "%s: %d x %d -> %d x %d takes an index table exactly for an axis that is resized", who, a->crop_w,
+                    a->crop_h, a->Wres, a->Hres);
+    if (!aligned4({a->idx_x, a->idx_y, a->frame_params, a->out}) || (reinterpret_cast<uintptr_t>(a->src) & 1u))
+        return fail(MAGNET_E_ALIGN, "%s: the tables, frame_params and out must be 4-byte aligned, src 2-byte aligned", who);
+    hipError_t e = magnet::launch_depth_prep(*a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "magnet_depth_prep_u16 launch");
 }
 
 // ---- the D-Net's encoder (enc_kernels.hip) ----

@@ -10,7 +10,10 @@ unless given.  Everything here is host code feeding the device path; nothing is 
 """
 from __future__ import annotations
 
+import dataclasses
 import os
+import random
+import typing
 
 import numpy as np
 import torch
@@ -97,14 +100,89 @@ def window_indices(center: int, n_views: int, window_radius: int, exists) -> lis
     return out
 
 
+# ---- training-mode augmentation (dataloader_scannet.py:171-200,219-232, dataloader_scannet_D.py:80-156, and their KITTI twins) ----
+@dataclasses.dataclass(frozen=True)
+class AugmentSpec:
+    """Which of the reference loaders' augmentations a folder draws.  color: gamma in [0.9, 1.1], brightness in `brightness`
+    ((0.75, 1.25) for ScanNet and 7-Scenes, (0.9, 1.1) for KITTI) and three channel factors in [0.9, 1.1], with probability 1/2;
+    flip: a horizontal flip with probability 1/2; crop_hw: a random (height, width) window of the resized image.  The loaders'
+    rotation (data_augmentation_rotate: Pillow's affine transform in double precision) is out of scope: there is no field for it."""
+    color: bool = False
+    brightness: tuple = (0.75, 1.25)
+    flip: bool = False
+    crop_hw: tuple | None = None
+
+
+class Augment(typing.NamedTuple):
+    """One sample's draw.  color: None or (gamma, brightness, (c_r, c_g, c_b)); flip: bool; window: None (the whole resized image) or
+    the (x, y) origin of the crop window in the (flipped) resized image."""
+    color: tuple | None = None
+    flip: bool = False
+    window: tuple | None = None
+
+
+def draw_augment(spec, py_rng, np_rng, resized_hw):
+    """The reference's draws in its order and from the same kinds of generator (py_rng: a random.Random, np_rng: a
+    numpy.random.RandomState): flip coin (dataloader_scannet_D.py:92-95), crop x then y with randint (:134-135), colour coin (:108),
+    gamma, brightness (:142-146), then the three colours from numpy (:150).  A draw that `spec` switches off consumes nothing."""
+    flip = bool(py_rng.random() > 0.5) if spec.flip else False
+    window = None
+    if spec.crop_hw is not None:
+        ch, cw = (int(v) for v in spec.crop_hw)
+        if ch < 1 or cw < 1 or ch > resized_hw[0] or cw > resized_hw[1]:
+            raise ValueError(f"draw_augment: a crop of {(ch, cw)} does not fit the resized image {tuple(resized_hw)}")
+        x = py_rng.randint(0, resized_hw[1] - cw)
+        window = (x, py_rng.randint(0, resized_hw[0] - ch))
+    color = None
+    if spec.color and py_rng.random() > 0.5:
+        gamma = py_rng.uniform(0.9, 1.1)
+        brightness = py_rng.uniform(*spec.brightness)
+        color = (gamma, brightness, tuple(float(c) for c in np_rng.uniform(0.9, 1.1, size=3)))
+    return Augment(color, flip, window)
+
+
+def augment_rngs(seed, epoch, index):
+    """The two generators of one item, seeded from (seed, epoch, item index) alone: a sample's draw does not depend on the worker
+    count, on the order of iteration or on which path prepares it."""
+    key = [int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, int(index) & 0xFFFFFFFF]
+    return random.Random((key[0] << 64) | (key[1] << 32) | key[2]), np.random.RandomState(key)
+
+
+def augment_image(image, gamma, brightness, colors):
+    """The loaders' colour augmentation of an (H, W, 3) float32 image in [0, 1], with their dtypes (dataloader_scannet.py:219-232):
+    float32 power and product, an in-place product with a float64 colour image (computed in float64, rounded to float32), a clip."""
+    image_aug = image ** gamma
+    image_aug = image_aug * brightness
+    white = np.ones((image.shape[0], image.shape[1]))
+    image_aug *= np.stack([white * colors[i] for i in range(3)], axis=2)
+    return np.clip(image_aug, 0, 1)
+
+
+def _check_spec(augment, multi_view):
+    if augment is None:
+        return None
+    if not isinstance(augment, AugmentSpec):
+        raise TypeError(f"augment must be an AugmentSpec or None, got {type(augment).__name__}")
+    if multi_view and (augment.flip or augment.crop_hw is not None):
+        raise ValueError("a multi-view folder takes the colour augmentation only, as the reference's multi-view loaders do: a flip or a "
+                         "crop would invalidate the intrinsics and the poses of the window")
+    return augment
+
+
 class ScanNetFolder:
     """samples: list of (scene_name, frame_index).  __getitem__ -> (data_array, cam_intrins): a list of n_views + 1 dicts
     {'img' (3,H,W) normalised fp32, 'gt_dmap' (1,H,W) metres for the reference frame else 0.0, 'extM' (4,4) float64,
     'scene_name', 'img_idx'} and the intrinsics dict — the structure of dataloader_scannet.py:155-217.
     raw_images=True (opt-in): 'img' is the decoded frame itself, a uint8 (Hraw, Wraw, 3) tensor, neither resized nor normalised —
-    magnet_amd.ingest.ImagePrep does both on the device, to the same bits.  Everything else of an item is unchanged."""
+    magnet_amd.ingest.ImagePrep does both on the device, to the same bits.  Everything else of an item is unchanged.
+    augment (opt-in; an AugmentSpec with colour only): the training mode of the reference's multi-view loader (:171-194), one colour
+    draw per sample, shared by its views, from generators seeded by (seed, epoch, item index); set_epoch(e) before each epoch.  The
+    host path applies it.  With raw_images=True the frames stay untouched, every dict carries the draw under 'aug', and the reference
+    frame's dict carries the decoded uint16 depth map under 'gt_dmap_raw' in place of 'gt_dmap': magnet_amd.ingest.TrainPrep
+    prepares both on the device, to the host path's bits.  The loaders' rotation augmentation is out of scope (AugmentSpec)."""
 
-    def __init__(self, root, samples, n_views=4, window_radius=20, input_hw=(480, 640), dpv_hw=(120, 160), raw_wh=None, raw_images=False):
+    def __init__(self, root, samples, n_views=4, window_radius=20, input_hw=(480, 640), dpv_hw=(120, 160), raw_wh=None, raw_images=False,
+                 augment=None, seed=0):
         from PIL import Image  # noqa: F401  (fail early if Pillow is missing)
         self.root, self.samples = root, list(samples)
         self.n_views, self.window_radius = n_views, window_radius
@@ -113,9 +191,13 @@ class ScanNetFolder:
         self.raw_wh = dict(raw_wh or {})
         self.center = n_views // 2
         self.raw_images = bool(raw_images)
+        self.augment, self.seed, self.epoch = _check_spec(augment, multi_view=True), int(seed), 0
 
     def __len__(self):
         return len(self.samples)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
 
     def _scene(self, name):
         return os.path.join(self.root, name)
@@ -138,6 +220,8 @@ class ScanNetFolder:
         scene, idx = sample
         return scene, self._scene(scene), int(idx)
 
+    depth_divisor, depth_invalid = 1000.0, None                                # what ingest.TrainPrep needs to restate _depth_metres
+
     def _depth_metres(self, raw):
         return raw.astype(np.float32) / 1000.0                                  # uint16 millimetres
 
@@ -154,6 +238,7 @@ class ScanNetFolder:
         frames = window_indices(idx, self.n_views, self.window_radius, lambda k: os.path.exists(self._color(sdir, k)))
         intr = self._intrinsics(scene, sdir, idx)
         mean = torch.tensor(IMAGENET_MEAN).view(3, 1, 1); std = torch.tensor(IMAGENET_STD).view(3, 1, 1)
+        aug = None if self.augment is None else draw_augment(self.augment, *augment_rngs(self.seed, self.epoch, i), (self.img_h, self.img_w))
         data_array = []
         for j, k in enumerate(frames):
             with Image.open(self._color(sdir, k)) as im:
@@ -163,16 +248,23 @@ class ScanNetFolder:
             if self.raw_images:
                 img = torch.from_numpy(np.array(rgb, dtype=np.uint8))           # (Hraw, Wraw, 3), a copy the tensor owns
             else:
-                img = torch.from_numpy(np.asarray(rgb).astype(np.float32) / 255.0).permute(2, 0, 1)
+                img = np.asarray(rgb).astype(np.float32) / 255.0
+                if aug is not None and aug.color is not None:
+                    img = augment_image(img, *aug.color)
+                img = torch.from_numpy(img).permute(2, 0, 1)
                 img = (img - mean) / std
+            entry = {"img": img, "gt_dmap": 0.0, "extM": read_pose_txt(self._pose(sdir, k)), "scene_name": scene, "img_idx": str(k)}
             if j == self.center:
                 with Image.open(self._depth(sdir, k)) as dm:
-                    d = self._depth_metres(np.asarray(dm.resize((self.img_w, self.img_h), resample=Image.NEAREST)))
-                gt = torch.from_numpy(d)[None]
-            else:
-                gt = 0.0
-            data_array.append({"img": img, "gt_dmap": gt, "extM": read_pose_txt(self._pose(sdir, k)),
-                               "scene_name": scene, "img_idx": str(k)})
+                    if self.raw_images and aug is not None:
+                        del entry["gt_dmap"]
+                        entry["gt_dmap_raw"] = torch.from_numpy(np.array(dm, dtype=np.uint16))       # (Hd, Wd), decoded only
+                    else:
+                        d = self._depth_metres(np.asarray(dm.resize((self.img_w, self.img_h), resample=Image.NEAREST)))
+                        entry["gt_dmap"] = torch.from_numpy(d)[None]
+            if self.raw_images and aug is not None:
+                entry["aug"] = aug
+            data_array.append(entry)
         return data_array, intr
 
 
@@ -184,6 +276,8 @@ class SevenScenesFolder(ScanNetFolder):
     def _split(self, sample):
         scene, seq, idx = sample
         return "%s_seq-%02d" % (scene, int(seq)), os.path.join(self.root, scene, "seq-%02d" % int(seq)), int(idx)
+
+    depth_invalid = 65535
 
     def _depth_metres(self, raw):
         raw = raw.copy()
@@ -204,10 +298,73 @@ class SevenScenesFolder(ScanNetFolder):
         return cam_intrinsics(K, self.img_w, self.img_h, self.dpv_h, self.dpv_w)
 
 
+class ScanNetFrames(ScanNetFolder):
+    """Single-view training items, the structure of dataloader_scannet_D.py:73-127: samples as ScanNetFolder's, __getitem__ ->
+    {'img' (3,H,W) normalised fp32, 'depth' (1,H,W) metres, 'scene_name', 'img_idx'}.  augment: an AugmentSpec with any of flip, crop
+    and colour, applied in the reference's order (:91-109): flip of image and depth, /255 and /1000, the crop window of both, colour,
+    normalisation; with crop_hw the item is (3, crop_h, crop_w) / (1, crop_h, crop_w).  Draws as ScanNetFolder's: seeded by
+    (seed, epoch, item index).  raw_images=True: 'img' is the decoded uint8 frame (Hraw, Wraw, 3), 'depth' the decoded uint16 map
+    (Hd, Wd), and 'aug' the draw (an all-default Augment without a spec), for magnet_amd.ingest.TrainPrep.  The loaders' rotation
+    augmentation is out of scope (AugmentSpec).  SevenScenesFrames is the 7-Scenes variant."""
+
+    def __init__(self, root, samples, input_hw=(480, 640), raw_images=False, augment=None, seed=0):
+        ScanNetFolder.__init__(self, root, samples, input_hw=input_hw, raw_images=raw_images, seed=seed)
+        self.augment = _check_spec(augment, multi_view=False)
+        if self.augment is not None and self.augment.crop_hw is not None:
+            ch, cw = self.augment.crop_hw
+            if ch < 1 or cw < 1 or ch > self.img_h or cw > self.img_w:
+                raise ValueError(f"ScanNetFrames: a crop of {(ch, cw)} does not fit the resized image {(self.img_h, self.img_w)}")
+
+    def __getitem__(self, i):
+        from PIL import Image
+        scene, sdir, idx = self._split(self.samples[i])
+        aug = Augment() if self.augment is None else draw_augment(self.augment, *augment_rngs(self.seed, self.epoch, i), (self.img_h, self.img_w))
+        with Image.open(self._color(sdir, idx)) as im, Image.open(self._depth(sdir, idx)) as dm:
+            if self.raw_images:
+                return {"img": torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8)),
+                        "depth": torch.from_numpy(np.array(dm, dtype=np.uint16)), "scene_name": scene, "img_idx": str(idx), "aug": aug}
+            rgb = im.convert("RGB").resize((self.img_w, self.img_h), resample=Image.BILINEAR)
+            dep = dm.resize((self.img_w, self.img_h), resample=Image.NEAREST)
+            if aug.flip:
+                rgb, dep = rgb.transpose(Image.FLIP_LEFT_RIGHT), dep.transpose(Image.FLIP_LEFT_RIGHT)
+            img = np.array(rgb).astype(np.float32) / 255.0
+            depth = self._depth_metres(np.array(dep))[:, :, None]
+        if self.augment is not None and self.augment.crop_hw is not None:
+            (x, y), (ch, cw) = aug.window, self.augment.crop_hw
+            img, depth = img[y:y + ch, x:x + cw, :], depth[y:y + ch, x:x + cw, :]
+        if aug.color is not None:
+            img = augment_image(img, *aug.color)
+        mean = torch.tensor(IMAGENET_MEAN).view(3, 1, 1); std = torch.tensor(IMAGENET_STD).view(3, 1, 1)
+        img = (torch.from_numpy(img).permute(2, 0, 1) - mean) / std
+        return {"img": img, "depth": torch.from_numpy(np.ascontiguousarray(depth)).permute(2, 0, 1), "scene_name": scene, "img_idx": str(idx)}
+
+
+class SevenScenesFrames(ScanNetFrames, SevenScenesFolder):
+    """ScanNetFrames over the 7-Scenes layout: SevenScenesFolder's samples, file names and "no measurement" code."""
+
+
+def collate_frames(items):
+    """default_collate of ScanNetFrames items: tensors stacked (the raw uint8 frames and uint16 depth maps of one batch must share one
+    raw size each), names and draws as lists."""
+    for key in ("img", "depth"):
+        sizes = {tuple(it[key].shape) for it in items}
+        if len(sizes) > 1:
+            raise ValueError("collate_frames: the %s entries of one batch have shapes %s; batch scenes of one raw size together" % (key, sorted(sizes)))
+    out = {"img": torch.stack([it["img"] for it in items]), "depth": torch.stack([it["depth"] for it in items]),
+           "scene_name": [it["scene_name"] for it in items], "img_idx": [it["img_idx"] for it in items]}
+    if "aug" in items[0]:
+        out["aug"] = [it["aug"] for it in items]
+    return out
+
+
 def collate(items):
     """What torch's default_collate makes of a list of (data_array, cam_intrins): per-frame dicts with a leading batch
     dimension ('extM' becomes a (B,4,4) float64 tensor), intrinsics stacked to (B,3,3) / (B,3,hw).  The uint8 frames of
-    `raw_images=True` items stack to (B,Hraw,Wraw,3); one batch holds one raw size."""
+    `raw_images=True` items stack to (B,Hraw,Wraw,3); one batch holds one raw size.  Of an augmenting raw folder, 'aug' becomes the
+    list of the B draws and the reference frame's 'gt_dmap_raw' stacks to (B,Hd,Wd) uint16 (one depth size per batch); that dict
+    has no 'gt_dmap' until ingest.prepare_train_batch makes it.  A list of ScanNetFrames items goes to collate_frames."""
+    if isinstance(items[0], dict):
+        return collate_frames(items)
     n_frames = len(items[0][0])
     raw_sizes = {tuple(d["img"].shape[:2]) for it in items for d in it[0] if d["img"].dtype == torch.uint8}
     if len(raw_sizes) > 1:
@@ -216,12 +373,20 @@ def collate(items):
     data_array = []
     for f in range(n_frames):
         ds = [it[0][f] for it in items]
-        gt = ds[0]["gt_dmap"]
-        data_array.append({
-            "img": torch.stack([d["img"] for d in ds]),
-            "gt_dmap": torch.stack([d["gt_dmap"] for d in ds]) if torch.is_tensor(gt) else torch.zeros(len(ds), dtype=torch.float64),
-            "extM": torch.from_numpy(np.stack([d["extM"] for d in ds])),
-            "scene_name": [d["scene_name"] for d in ds], "img_idx": [d["img_idx"] for d in ds]})
+        entry = {"img": torch.stack([d["img"] for d in ds])}
+        if "gt_dmap_raw" in ds[0]:
+            if len({tuple(d["gt_dmap_raw"].shape) for d in ds}) > 1:
+                raise ValueError("collate: the raw depth maps of one batch have sizes %s; batch scenes of one raw size together"
+                                 % sorted({tuple(d["gt_dmap_raw"].shape) for d in ds}))
+            entry["gt_dmap_raw"] = torch.stack([d["gt_dmap_raw"] for d in ds])
+        else:
+            gt = ds[0]["gt_dmap"]
+            entry["gt_dmap"] = torch.stack([d["gt_dmap"] for d in ds]) if torch.is_tensor(gt) else torch.zeros(len(ds), dtype=torch.float64)
+        entry.update({"extM": torch.from_numpy(np.stack([d["extM"] for d in ds])),
+                      "scene_name": [d["scene_name"] for d in ds], "img_idx": [d["img_idx"] for d in ds]})
+        if "aug" in ds[0]:
+            entry["aug"] = [d["aug"] for d in ds]
+        data_array.append(entry)
     intr = {k: torch.stack([it[1][k] for it in items]) for k in items[0][1]}
     return data_array, intr
 

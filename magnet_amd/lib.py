@@ -11,6 +11,7 @@ entry point, which load() applies before it returns the handle.  tests/test_abi.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch  # noqa: F401  (must precede CDLL: shares torch's HIP runtime)
@@ -236,6 +237,27 @@ class MagnetImagePrepArgs(ctypes.Structure):
                 ("Hout", ctypes.c_int32), ("Wout", ctypes.c_int32), ("kx", ctypes.c_int32), ("ky", ctypes.c_int32)]
 
 
+class MagnetTrainPrepArgs(ctypes.Structure):
+    """Mirror of `struct MagnetTrainPrepArgs` (include/magnet_hip.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("src_pitch", ctypes.c_int64), ("src_frame", ctypes.c_int64),
+                ("coef_x", ctypes.c_void_p), ("bounds_x", ctypes.c_void_p), ("coef_y", ctypes.c_void_p), ("bounds_y", ctypes.c_void_p),
+                ("luts", ctypes.c_void_p), ("frame_params", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("N", ctypes.c_int32), ("Hin", ctypes.c_int32), ("Win", ctypes.c_int32),
+                ("crop_left", ctypes.c_int32), ("crop_top", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("Hres", ctypes.c_int32), ("Wres", ctypes.c_int32), ("Hout", ctypes.c_int32), ("Wout", ctypes.c_int32),
+                ("kx", ctypes.c_int32), ("ky", ctypes.c_int32), ("n_luts", ctypes.c_int32)]
+
+
+class MagnetDepthPrepArgs(ctypes.Structure):
+    """Mirror of `struct MagnetDepthPrepArgs` (include/magnet_hip.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("src_pitch", ctypes.c_int64), ("src_frame", ctypes.c_int64),
+                ("idx_x", ctypes.c_void_p), ("idx_y", ctypes.c_void_p), ("frame_params", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("N", ctypes.c_int32), ("Hin", ctypes.c_int32), ("Win", ctypes.c_int32),
+                ("crop_left", ctypes.c_int32), ("crop_top", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("Hres", ctypes.c_int32), ("Wres", ctypes.c_int32), ("Hout", ctypes.c_int32), ("Wout", ctypes.c_int32),
+                ("invalid_code", ctypes.c_int32), ("divisor", ctypes.c_float)]
+
+
 class MagnetDwConvArgs(ctypes.Structure):
     """Mirror of `struct MagnetDwConvArgs` (include/magnet_hip.h)."""
     _fields_ = [("in_hi", ctypes.c_void_p), ("in_lo", ctypes.c_void_p), ("wgt", ctypes.c_void_p), ("bias", ctypes.c_void_p),
@@ -322,6 +344,8 @@ _PROTOS = {
     "magnet_gather_views": (_C, [_S(MagnetGatherViewsArgs), _P]),
     "magnet_scatter_frames": (_C, [_S(MagnetScatterFramesArgs), _P]),
     "magnet_image_prep_u8": (_C, [_S(MagnetImagePrepArgs), _P]),
+    "magnet_train_prep_u8": (_C, [_S(MagnetTrainPrepArgs), _P]),
+    "magnet_depth_prep_u16": (_C, [_S(MagnetDepthPrepArgs), _P]),
     "magnet_fnet_loss_forward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_fnet_loss_backward": (_C, [_S(MagnetFnetLossArgs), _P]),
     "magnet_bn_sync_moments": (_C, [_S(MagnetBnTrainArgs), _P, _P]),
@@ -1631,6 +1655,99 @@ def image_prep_u8(frames, out, crop, tables_x, tables_y, lut):
     if any(x.device != f.device for x in used):
         raise MagnetError("image_prep_u8: all tensors must be on the same device")
     _launch("magnet_image_prep_u8", f, ctypes.byref(a))
+    return out
+
+
+# ---- training samples (magnet_train_prep_u8: csrc/image_prep.hip; magnet_depth_prep_u16: csrc/depth_prep.hip; ingest.TrainPrep) ----
+def _frame_params(frame_params, N, who):
+    r = _dev(frame_params, "frame_params", torch.int32)
+    if tuple(r.shape) != (N, 4):
+        raise MagnetError(f"{who}: frame_params has shape {tuple(r.shape)}, expected ({N}, 4) rows of (lut_index, flip, win_x, win_y)")
+    return r
+
+
+def _window(out, N, channels, res_hw, who):
+    o = _dev(out, "out", torch.float32)
+    if o.dim() != 4 or o.shape[0] != N or o.shape[1] != channels:
+        raise MagnetError(f"{who}: out has shape {tuple(o.shape)}, expected ({N}, {channels}, Hout, Wout)")
+    Hres, Wres = (int(v) for v in res_hw)
+    if not (1 <= o.shape[2] <= Hres and 1 <= o.shape[3] <= Wres):
+        raise MagnetError(f"{who}: the window {tuple(o.shape[2:])} of out is not inside the resized image {(Hres, Wres)}")
+    return o, Hres, Wres
+
+
+def train_prep_u8(frames, out, crop, res_hw, tables_x, tables_y, luts, frame_params):
+    """One launch: image_prep_u8's crop and resize, to res_hw = (Hres, Wres), of uint8 frames (N, Hin, Win, 3); then per frame n, from
+    frame_params[n] = (lut_index, flip, win_x, win_y) (int32 (N, 4) on the device), the (Hout, Wout) window at (win_x, win_y) of the
+    horizontally flipped (flip != 0) resized image, looked up in luts[lut_index] ((L, 3, 256) fp32) -> out (N, 3, Hout, Wout) fp32.
+    The tables are those of crop -> res_hw, present exactly when a size changes.  The device clamps the records into their ranges;
+    ingest.TrainPrep validates them on the host."""
+    f = frames
+    if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3:
+        raise MagnetError("train_prep_u8: frames must be a uint8 GPU tensor (N, Hin, Win, 3)")
+    N, Hin, Win, _ = (int(v) for v in f.shape)
+    if N < 1 or f.stride(3) != 1 or f.stride(2) != 3 or f.stride(1) < 3 * Win or (N > 1 and f.stride(0) < f.stride(1) * Hin):
+        raise MagnetError(f"train_prep_u8: frames {tuple(f.shape)} with strides {tuple(f.stride())}: pixels must be dense and rows and frames must not overlap")
+    o, Hres, Wres = _window(out, N, 3, res_hw, "train_prep_u8")
+    left, top, cw, ch = (int(v) for v in crop)
+    luts = _dev(luts, "luts", torch.float32)
+    if luts.dim() != 3 or luts.shape[0] < 1 or tuple(luts.shape[1:]) != (3, 256):
+        raise MagnetError(f"train_prep_u8: luts has shape {tuple(luts.shape)}, expected (L, 3, 256) with L >= 1")
+    rec = _frame_params(frame_params, N, "train_prep_u8")
+    a = MagnetTrainPrepArgs(src=f.data_ptr(), src_pitch=f.stride(1), src_frame=f.stride(0), luts=luts.data_ptr(), frame_params=rec.data_ptr(),
+                            out=o.data_ptr(), N=N, Hin=Hin, Win=Win, crop_left=left, crop_top=top, crop_w=cw, crop_h=ch, Hres=Hres, Wres=Wres,
+                            Hout=int(o.shape[2]), Wout=int(o.shape[3]), n_luts=int(luts.shape[0]))
+    used = [f, o, luts, rec]
+    for axis, tables, n_in, n_out in (("x", tables_x, cw, Wres), ("y", tables_y, ch, Hres)):
+        if (tables is None) != (n_in == n_out):
+            raise MagnetError(f"train_prep_u8: the {axis} pass goes from {n_in} to {n_out} pixels: it takes tables exactly when the size changes")
+        if tables is None:
+            continue
+        coef, bounds = _dev(tables[0], f"coef_{axis}", torch.int32), _dev(tables[1], f"bounds_{axis}", torch.int32)
+        if coef.dim() != 2 or coef.shape[0] != n_out or tuple(bounds.shape) != (n_out, 2):
+            raise MagnetError(f"train_prep_u8: coef_{axis} {tuple(coef.shape)} / bounds_{axis} {tuple(bounds.shape)}, expected ({n_out}, k) and ({n_out}, 2)")
+        setattr(a, "coef_" + axis, coef.data_ptr()); setattr(a, "bounds_" + axis, bounds.data_ptr()); setattr(a, "k" + axis, int(coef.shape[1]))
+        used += [coef, bounds]
+    if any(x.device != f.device for x in used):
+        raise MagnetError("train_prep_u8: all tensors must be on the same device")
+    _launch("magnet_train_prep_u8", f, ctypes.byref(a))
+    return out
+
+
+def depth_prep_u16(depth, out, crop, res_hw, idx_x, idx_y, frame_params, divisor, invalid_code=-1):
+    """One launch: uint16 depth maps (N, Hin, Win) (the last dimension dense, rows and frames through their strides) -> out
+    (N, 1, Hout, Wout) fp32: crop = (left, top, width, height), PIL's NEAREST resize of the box to res_hw through idx_x (Wres) / idx_y (Hres)
+    int32 source indices (None for an axis whose size does not change), the frame's flip and window as train_prep_u8 (lut_index is
+    ignored), a sample equal to invalid_code -> 0 (-1: none), then one correctly rounded fp32 division by `divisor`."""
+    d = depth
+    if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.uint16 or d.dim() != 3:
+        raise MagnetError("depth_prep_u16: depth must be a uint16 GPU tensor (N, Hin, Win)")
+    N, Hin, Win = (int(v) for v in d.shape)
+    if N < 1 or d.stride(2) != 1 or d.stride(1) < Win or (N > 1 and d.stride(0) < d.stride(1) * Hin):
+        raise MagnetError(f"depth_prep_u16: depth {tuple(d.shape)} with strides {tuple(d.stride())}: pixels must be dense and rows and frames must not overlap")
+    o, Hres, Wres = _window(out, N, 1, res_hw, "depth_prep_u16")
+    left, top, cw, ch = (int(v) for v in crop)
+    rec = _frame_params(frame_params, N, "depth_prep_u16")
+    divisor = float(divisor)
+    if not (math.isfinite(divisor) and divisor > 0.0):
+        raise MagnetError(f"depth_prep_u16: divisor {divisor} must be finite and positive")
+    a = MagnetDepthPrepArgs(src=d.data_ptr(), src_pitch=d.stride(1), src_frame=d.stride(0), frame_params=rec.data_ptr(), out=o.data_ptr(),
+                            N=N, Hin=Hin, Win=Win, crop_left=left, crop_top=top, crop_w=cw, crop_h=ch, Hres=Hres, Wres=Wres,
+                            Hout=int(o.shape[2]), Wout=int(o.shape[3]), invalid_code=int(invalid_code), divisor=divisor)
+    used = [d, o, rec]
+    for axis, idx, n_in, n_out in (("x", idx_x, cw, Wres), ("y", idx_y, ch, Hres)):
+        if (idx is None) != (n_in == n_out):
+            raise MagnetError(f"depth_prep_u16: the {axis} axis goes from {n_in} to {n_out} pixels: it takes an index table exactly when the size changes")
+        if idx is None:
+            continue
+        t = _dev(idx, f"idx_{axis}", torch.int32)
+        if tuple(t.shape) != (n_out,):
+            raise MagnetError(f"depth_prep_u16: idx_{axis} has shape {tuple(t.shape)}, expected ({n_out},)")
+        setattr(a, "idx_" + axis, t.data_ptr())
+        used.append(t)
+    if any(x.device != d.device for x in used):
+        raise MagnetError("depth_prep_u16: all tensors must be on the same device")
+    _launch("magnet_depth_prep_u16", d, ctypes.byref(a))
     return out
 
 
