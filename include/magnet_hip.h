@@ -183,7 +183,9 @@ MAGNET_API int magnet_cost_volume_cw(const MagnetCostVolumeArgs *args, void *str
  *   grad_src_pad (V*B,h+2,w+2,F)   fp32 padded channel-last, ACCUMULATED into with atomics — zero it first;
  *                                  what lands in the one-texel border is the (discarded) gradient of the
  *                                  zero padding.
- * Depth bins, poses and intrinsics receive no gradient (they are data in the reference's training loop). */
+ * Depth bins, poses and intrinsics receive no gradient (they are data in the reference's training loop).
+ * Limits (MAGNET_E_DIM otherwise, outputs untouched): V <= 29 (the per-wave projection table, 4 * (512 V + 1360) bytes, must fit
+ * 64 KB of LDS); F <= 128, or any F % 32 == 0 while V <= 4 (the LDS hash kernel walks the channels in slices of 32). */
 MAGNET_API int magnet_cost_volume_f_backward(const MagnetCostVolumeArgs *args, const float *grad_cost, float *grad_ref_cl,
                                   float *grad_src_pad, void *stream);
 

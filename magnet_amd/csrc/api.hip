@@ -243,7 +243,7 @@ MAGNET_API int magnet_cost_volume_f_backward(const MagnetCostVolumeArgs* a, cons
     bool handled = false;
     hipError_t e = magnet::launch_cvf_bwd(p, grad_cost, grad_ref_cl, grad_src_pad, (hipStream_t)stream, &handled);
     if (e != hipSuccess) return hip_fail(e, "magnet_cost_volume_f_backward launch");
-    if (!handled) return fail(MAGNET_E_DIM, "magnet_cost_volume_f_backward: shape not supported (F > 128, V > 31 or image too large)");
+    if (!handled) return fail(MAGNET_E_DIM, "magnet_cost_volume_f_backward: shape not supported (V > 29; F > 128 unless F %% 32 == 0 and V <= 4; or image too large)");
     return 0;
 }
 
@@ -290,7 +290,7 @@ MAGNET_API int magnet_cost_volume_f_backward_ws(const MagnetCostVolumeArgs* a, c
     bool handled = false;
     e = magnet::launch_cvf_bwd(p, grad_cost, grad_ref_cl, grad_src_pad, (hipStream_t)stream, &handled);
     if (e != hipSuccess) return hip_fail(e, "magnet_cost_volume_f_backward_ws launch");
-    if (!handled) return fail(MAGNET_E_DIM, "magnet_cost_volume_f_backward_ws: shape not supported (F > 128, V > 31 or image too large)");
+    if (!handled) return fail(MAGNET_E_DIM, "magnet_cost_volume_f_backward_ws: shape not supported (V > 29; F > 128 unless F %% 32 == 0 and V <= 4; or image too large)");
     return 0;
 }
 

@@ -605,11 +605,23 @@ def cost_volume_cw(ref_feat_cl, src_feat_pad, src_gmm_pad, poses, is_valid, intM
 
 
 def cost_volume_f_backward(ref_feat_cl, src_feat_pad, poses, is_valid, intM, rays, d_center, grad_cost, path: int = 0,
-                           stats=None):
+                           stats=None, grad_ref=None, grad_src=None, workspace=None):
     """Gradients of the mode-1 volume (est_costvolume_F before its softmax) w.r.t. the two feature maps.
 
     Same tensors as the forward call (fp32 features) + grad_cost (B,D,h,w).  Returns
-    (grad_ref_cl (B,h,w,F), grad_src_pad (V*B,h+2,w+2,F)), both fp32 channel-last."""
+    (grad_ref_cl (B,h,w,F), grad_src_pad (V*B,h+2,w+2,F)), both fp32 channel-last.
+
+    `path`: only its low byte selects the entry point.  Low byte 0 is magnet_cost_volume_f_backward_ws, the gather (deterministic;
+    it stores every interior texel of grad_src_pad once and leaves the border alone, and falls back to the scatter kernels, which
+    accumulate, when the workspace is short or the gather refuses the shape).  Any other low byte is
+    magnet_cost_volume_f_backward, the scatter entry point: the LDS hash kernel when F % 32 == 0 and V <= 4, the per-item atomic
+    kernel otherwise.  Bits 8 and up are forwarded as dev_flags exactly as cost_volume_cw does (the product build ignores them;
+    the dev build: 0x1000 no gather, 0x2000 no gather and the per-item kernel, 0x4000 32-texel gather segments).
+
+    `grad_ref` / `grad_src`: caller-owned output buffers of the shapes above (tests: views into guarded allocations).  The
+    default is a fresh grad_ref and a zeroed grad_src; a caller's grad_src is used as it is (the scatter kernels add to it).
+    `workspace`: a caller-owned uint8 buffer for the gather, or a function that is handed the number of bytes the library asks for
+    and returns that buffer (it may be deliberately short: the call then takes the scatter fallback)."""
     r = _dev(ref_feat_cl, "ref_feat_cl", torch.float32)
     s = _dev(src_feat_pad, "src_feat_pad", torch.float32)
     B, h, w, F = r.shape
@@ -629,19 +641,31 @@ def cost_volume_f_backward(ref_feat_cl, src_feat_pad, poses, is_valid, intM, ray
     a.B, a.V, a.F, a.D, a.h, a.w = B, V, F, D, h, w
     a.feat_dtype = FEAT_F32
     a.mode = 1
-    a.path = int(path)                                             # dev: 0x2000 = the per-item atomic kernel
+    a.path = int(path) & 0xff
+    a.dev_flags = int(path) >> 8
     if stats is not None:
         a.stats = _dev(stats, "stats", torch.int32).data_ptr()       # [_, flushed texels, units merged in LDS, units sent to global atomics]
     a.ref_feat_cl, a.src_feat_pad = r.data_ptr(), s.data_ptr()
     kbuf = (ctypes.c_double * D)(*[float(k) for k in d_center])
     a.k_list = ctypes.addressof(kbuf)
     a.poses, a.is_valid, a.intM, a.rays = po.data_ptr(), iv.data_ptr(), K.data_ptr(), ry.data_ptr()
-    grad_ref = torch.empty_like(r)
-    grad_src = torch.zeros_like(s)
-    if (int(path) & 0xff) == 0:
+    grad_ref = torch.empty_like(r) if grad_ref is None else _dev(grad_ref, "grad_ref", torch.float32)
+    grad_src = torch.zeros_like(s) if grad_src is None else _dev(grad_src, "grad_src", torch.float32)
+    if grad_ref.shape != r.shape or grad_src.shape != s.shape:
+        raise MagnetError(f"grad_ref / grad_src shapes {tuple(grad_ref.shape)} / {tuple(grad_src.shape)}, expected "
+                          f"{tuple(r.shape)} / {tuple(s.shape)}")
+    if grad_ref.device != r.device or grad_src.device != r.device:
+        raise MagnetError("grad_ref / grad_src must be on the features' device")
+    if a.path == 0:
         # gather path: deterministic, no atomics; workspace = projection terms + per-(view, bin, tile) bounding boxes
-        nbytes = _workspace("magnet_cost_volume_f_backward_workspace", a)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
+        if workspace is None or callable(workspace):
+            nbytes = _workspace("magnet_cost_volume_f_backward_workspace", a)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=r.device) if workspace is None else workspace(nbytes)
+        else:
+            ws = workspace
+        if ws.device != r.device:
+            raise MagnetError("workspace must be on the features' device")
+        nbytes = _dev(ws, "workspace", torch.uint8).numel()
         _launch("magnet_cost_volume_f_backward_ws", r, ctypes.byref(a), g.data_ptr(), grad_ref.data_ptr(), grad_src.data_ptr(),
                 ws.data_ptr(), nbytes)
     else:

@@ -196,6 +196,47 @@ ORACLE_API int magnet_oracle_cost_volume_cw(
 }
 
 /*
+ * The sample geometry of est_costvolume_F for one (pixel, view, depth bin): homography.py:54-66 in the arithmetic contract
+ * of the header.  magnet_oracle_cost_volume_f and magnet_oracle_cost_volume_f_geometry both go through this one function,
+ * so what the second reports is, by construction, what the first used.
+ */
+typedef struct {
+    taps_t tp;            /* quad origin and the four fp32 bilinear weights */
+    int    inw;           /* some tap of the quad may lie inside the image: x0 in [-1, w-1] and y0 in [-1, h-1] */
+    float  Pz;            /* projected depth before the + 1e-10 (<= 0: behind the source camera, not tested by the reference) */
+    int    clamp_x, clamp_y; /* the normalised coordinate hit the +-10 clamp */
+} fgeo_t;
+
+static inline void f_sample_geometry(const float *K, const float *T, float ray0, float ray1, float ray2, float d,
+                                     float cw, float ch, float sw_, float sh_, int h, int w, fgeo_t *g) {
+    float R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+    float t[3] = {T[3], T[7], T[11]};
+    float KR[9], Kt[3];
+    for (int i = 0; i < 3; ++i) {
+        for (int c = 0; c < 3; ++c)
+            KR[i * 3 + c] = dot3(K + i * 3, R[0 * 3 + c], R[1 * 3 + c], R[2 * 3 + c]);
+        Kt[i] = dot3_gemv(K + i * 3, t[0], t[1], t[2]);
+    }
+    const float rpx = dot3(KR + 0, ray0, ray1, ray2);
+    const float rpy = dot3(KR + 3, ray0, ray1, ray2);
+    const float rpz = dot3(KR + 6, ray0, ray1, ray2);
+    float Px = Kt[0] + rpx * d;
+    float Py = Kt[1] + rpy * d;
+    float Pz = Kt[2] + rpz * d;
+    const float zz = Pz + 1e-10f;
+    Px = Px / zz; Py = Py / zz;
+    float gx = (Px - cw) / cw, gy = (Py - ch) / ch;
+    g->clamp_x = (gx > 10.f) || (gx < -10.f);
+    g->clamp_y = (gy > 10.f) || (gy < -10.f);
+    gx = clampf(gx, -10.f, 10.f); gy = clampf(gy, -10.f, 10.f);
+    const float ix = __builtin_fmaf(gx + 1.0f, sw_, -0.5f);
+    const float iy = __builtin_fmaf(gy + 1.0f, sh_, -0.5f);
+    make_taps(ix, iy, &g->tp);
+    g->Pz = Pz;
+    g->inw = g->tp.finite && g->tp.x0 >= -1 && g->tp.x0 < w && g->tp.y0 >= -1 && g->tp.y0 < h;
+}
+
+/*
  * est_costvolume_F / _compute_cost_F (models/submodules/homography.py:10-75), BEFORE the final softmax:
  * fixed depth bins d_center[j] shared by all pixels, no consistency gate, feature cost summed over valid views
  * in FP32 (homography.py:42: ref_mv_cost = ref_mv_cost + cost, both fp32) and divided by ALL views (:46).
@@ -231,33 +272,14 @@ ORACLE_API int magnet_oracle_cost_volume_f(
                     float acc = 0.f;
                     for (int v = 0; v < V; ++v) {
                         if (is_valid[b * V + v] != 1) continue;
-                        const float *T = poses + ((size_t)b * V + v) * 16;
-                        float R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-                        float t[3] = {T[3], T[7], T[11]};
-                        float KR[9], Kt[3];
-                        for (int i = 0; i < 3; ++i) {
-                            for (int c = 0; c < 3; ++c)
-                                KR[i * 3 + c] = dot3(K + i * 3, R[0 * 3 + c], R[1 * 3 + c], R[2 * 3 + c]);
-                            Kt[i] = dot3_gemv(K + i * 3, t[0], t[1], t[2]);
-                        }
-                        const float rpx = dot3(KR + 0, ray0, ray1, ray2);
-                        const float rpy = dot3(KR + 3, ray0, ray1, ray2);
-                        const float rpz = dot3(KR + 6, ray0, ray1, ray2);
-                        float Px = Kt[0] + rpx * d;
-                        float Py = Kt[1] + rpy * d;
-                        float Pz = Kt[2] + rpz * d;
-                        const float zz = Pz + 1e-10f;
-                        Px = Px / zz; Py = Py / zz;
-                        float gx = (Px - cw) / cw, gy = (Py - ch) / ch;
-                        gx = clampf(gx, -10.f, 10.f); gy = clampf(gy, -10.f, 10.f);
-                        const float ix = __builtin_fmaf(gx + 1.0f, sw_, -0.5f);
-                        const float iy = __builtin_fmaf(gy + 1.0f, sh_, -0.5f);
-                        taps_t tp; make_taps(ix, iy, &tp);
+                        fgeo_t ge;
+                        f_sample_geometry(K, poses + ((size_t)b * V + v) * 16, ray0, ray1, ray2, d, cw, ch, sw_, sh_, h, w, &ge);
+                        const taps_t tp = ge.tp;
                         const size_t sidx = (size_t)v * B + b;
                         const float *sf = src_feat + sidx * F * hw;
                         const float *rf = ref_feat + (size_t)b * F * hw + p;
                         float c = 0.f;
-                        const int inw = tp.finite && tp.x0 >= -1 && tp.x0 < w && tp.y0 >= -1 && tp.y0 < h;
+                        const int inw = ge.inw;
                         if (inw) {
                             float lvl0 = 0.f, lvl1 = 0.f, lvl2 = 0.f;
                             for (int f = 0; f < F; ++f) {
@@ -288,6 +310,47 @@ ORACLE_API int magnet_oracle_cost_volume_f(
                         acc = acc + c;
                     }
                     out[((size_t)b * D + j) * hw + p] = acc / (float)V;
+                }
+            }
+        }
+    }
+    return 0;
+}
+
+/*
+ * The geometry magnet_oracle_cost_volume_f computes internally, for every (b, v, j, pixel) — invalid views included, with
+ * their flag bit clear — as (B,V,D,h*w) arrays: the quad origin (x0, y0) (-100000 where the position is not finite), the four
+ * fp32 tap weights in ATen's order (nw, ne, sw, se), the projected depth Pz, and flags: bit 0 in-window (the sample
+ * contributes when the view is valid), bit 1 gx clamped at +-10, bit 2 gy clamped, bit 3 view valid.  Same helper as above.
+ */
+ORACLE_API int magnet_oracle_cost_volume_f_geometry(
+    const float *d_center, const float *poses, const int32_t *is_valid, const float *intM, const float *rays,
+    int B, int V, int D, int h, int w,
+    int32_t *x0, int32_t *y0, float *weights, float *Pz, uint8_t *flags, int n_threads)
+{
+    const size_t hw = (size_t)h * w;
+    const float cw = (float)((double)w / 2.0), ch = (float)((double)h / 2.0);
+    const float sw_ = (float)w / 2.0f, sh_ = (float)h / 2.0f;
+#ifdef _OPENMP
+    if (n_threads > 0) omp_set_num_threads(n_threads);
+#endif
+    #pragma omp parallel for collapse(2) schedule(static)
+    for (int b = 0; b < B; ++b) {
+        for (int v = 0; v < V; ++v) {
+            const float *K = intM + (size_t)b * 9;
+            const int valid = is_valid[b * V + v] == 1;
+            for (int j = 0; j < D; ++j) {
+                for (size_t p = 0; p < hw; ++p) {
+                    fgeo_t ge;
+                    f_sample_geometry(K, poses + ((size_t)b * V + v) * 16, rays[((size_t)b * 3 + 0) * hw + p],
+                                      rays[((size_t)b * 3 + 1) * hw + p], rays[((size_t)b * 3 + 2) * hw + p],
+                                      d_center[j], cw, ch, sw_, sh_, h, w, &ge);
+                    const size_t o = (((size_t)b * V + v) * D + j) * hw + p;
+                    x0[o] = ge.tp.x0; y0[o] = ge.tp.y0;
+                    weights[o * 4 + 0] = ge.tp.nw; weights[o * 4 + 1] = ge.tp.ne;
+                    weights[o * 4 + 2] = ge.tp.sw; weights[o * 4 + 3] = ge.tp.se;
+                    Pz[o] = ge.Pz;
+                    flags[o] = (uint8_t)((ge.inw ? 1 : 0) | (ge.clamp_x ? 2 : 0) | (ge.clamp_y ? 4 : 0) | (valid ? 8 : 0));
                 }
             }
         }

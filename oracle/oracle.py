@@ -45,6 +45,9 @@ def _lib():
         ff = _LIB.magnet_oracle_cost_volume_f
         ff.restype = ctypes.c_int
         ff.argtypes = [P] * 7 + [ctypes.c_int] * 6 + [P] * 4 + [ctypes.c_int]
+        fg = _LIB.magnet_oracle_cost_volume_f_geometry
+        fg.restype = ctypes.c_int
+        fg.argtypes = [P] * 5 + [ctypes.c_int] * 5 + [P] * 5 + [ctypes.c_int]
     return _LIB
 
 
@@ -156,6 +159,28 @@ def cost_volume_f_raw(d_center, ref_feat, src_feat, poses, is_valid, intM, rays,
                                             int(n_threads))
     assert rc == 0
     return (out, gr, gs) if gout is not None else out
+
+
+def cost_volume_f_geometry(d_center, poses, is_valid, intM, rays, h, w, n_threads=0) -> dict:
+    """The sample geometry cost_volume_f_raw computes internally (one C helper serves both), for every (b, v, j, pixel), invalid
+    views included: x0, y0 int32 (B,V,D,h,w) quad origins (-100000 where the position is not finite); weights fp32 (B,V,D,h,w,4)
+    in ATen's order nw, ne, sw, se; Pz fp32 (the projected depth before its + 1e-10); inwin, clamp_x, clamp_y, valid bool."""
+    poses = _f32(poses); intM = _f32(intM); rays = _f32(rays)
+    dc = np.ascontiguousarray(np.asarray(d_center.detach().cpu().numpy() if hasattr(d_center, "detach") else d_center,
+                                         dtype=np.float32).reshape(-1))
+    iv = np.ascontiguousarray(is_valid.detach().cpu().numpy() if hasattr(is_valid, "detach") else is_valid, dtype=np.int32)
+    B, V = iv.shape
+    D = dc.shape[0]
+    assert poses.shape == (B, V, 4, 4) and intM.shape == (B, 3, 3) and rays.shape == (B, 3, h * w)
+    x0 = np.empty((B, V, D, h, w), np.int32); y0 = np.empty_like(x0)
+    wts = np.empty((B, V, D, h, w, 4), np.float32)
+    pz = np.empty((B, V, D, h, w), np.float32)
+    flags = np.empty((B, V, D, h, w), np.uint8)
+    rc = _lib().magnet_oracle_cost_volume_f_geometry(_ptr(dc), _ptr(poses), _ptr(iv), _ptr(intM), _ptr(rays), B, V, D, h, w,
+                                                     _ptr(x0), _ptr(y0), _ptr(wts), _ptr(pz), _ptr(flags), int(n_threads))
+    assert rc == 0
+    return dict(x0=x0, y0=y0, weights=wts, Pz=pz, inwin=(flags & 1) != 0, clamp_x=(flags & 2) != 0, clamp_y=(flags & 4) != 0,
+                valid=(flags & 8) != 0)
 
 
 def softmax_dim1(x):

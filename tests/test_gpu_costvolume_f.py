@@ -117,9 +117,9 @@ def test_backward_rejects_bad_mode(hip_lib, gpu):
 
 
 def test_backward_kernels_agree(hip_lib, gpu):
-    """Gather backward (default: no atomics, deterministic) vs the tile-privatised scatter kernel (LDS hash table, path bit
-    0x1000) vs the per-item atomic kernel (path bit 0x2000) vs the oracle, on a shape with long epipolar runs and an invalid
-    view; the gather path must also be bit-identical run to run."""
+    """Gather backward (default: no atomics, deterministic) vs the tile-privatised scatter kernel (LDS hash table: the scatter entry
+    point, a non-zero low byte of `path`) vs the per-item atomic kernel (dev library only) vs the oracle, on a shape with long
+    epipolar runs and an invalid view; the gather path must also be bit-identical run to run."""
     from magnet_amd import lib
     wl = synth.Workload("f", "scannet", 28, 36, V=3, D=80, F=64)
     inp = synth.make_inputs(wl, B=2, seed=21, invalid=[(1, 0)])
@@ -135,8 +135,13 @@ def test_backward_kernels_agree(hip_lib, gpu):
               inp["cam_intrins"]["unit_ray_array_2D"].to(gpu), bins, gout.to(gpu))
     a1 = lib.cost_volume_f_backward(*common, path=0); a2 = lib.cost_volume_f_backward(*common, path=0)
     assert torch.equal(a1[0], a2[0]) and torch.equal(a1[1], a2[1])      # production gather: fixed summation order, no atomics
-    for path in (0, 0x4000, 0x1000, 0x2000):                            # gather (16- / 32-texel segments), hash scatter, plain atomics
-        gr, gs = lib.cost_volume_f_backward(*common, path=path)
+    # the routes of tests/test_gpu_costvolume_f_pointwise.py: gather; the scatter entry point (F = 64, V = 3: the LDS hash kernel); the
+    # gather entry point with a workspace one byte short (its fallback to the scatter kernels); and, against the dev library only,
+    # 32-texel gather segments and the forced per-item atomic kernel
+    short = lambda nbytes: torch.empty(nbytes - 1, dtype=torch.uint8, device=gpu)
+    routes = [(0, None), (1, None), (0, short)] + ([(0x4000, None), (0x2001, None)] if "_dev" in lib.LIB_PATH else [])
+    for path, workspace in routes:
+        gr, gs = lib.cost_volume_f_backward(*common, path=path, workspace=workspace)
         gr = gr.permute(0, 3, 1, 2).cpu().numpy(); gs = gs[:, 1:-1, 1:-1].permute(0, 3, 1, 2).cpu().numpy()
         for got, exp in ((gr, o_gr), (gs, o_gs)):
             np.testing.assert_allclose(got, exp, rtol=1e-4, atol=2e-5 * max(1.0, float(np.abs(exp).max())))
